@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: waveforms/s of the 4096-sample fp32 Ge energy chain (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path (bl_subtract -> pole_zero -> trap_filter -> fixed_time_pickoff) over one synthetic batch that is
 already resident in HBM.  The chain is built the way a dspeed user builds it -- build_processing_chain(<the recipe as a LEGEND configuration
@@ -14,9 +14,14 @@ same program handed to dsp_chain_create directly is timed beside it (roofline.ra
             one process per GPU, NO data-path collective
 
 Rank 0 prints ONE JSON line.  `value` = rows processed by all ranks / wall time of the K timed steps
-(max over ranks, bracketed by barrier + device sync).  `roofline` prices the single kernel of the chain with
-the ALGORITHMIC bytes of SURVEY.md 8(d): 16 396 B per waveform (4096x4 read + baseline + pick-off time read
-+ energy written) against the 8 TB/s HBM3E peak, from per-launch HIP-event durations on the launch stream.
+(max over ranks, bracketed by barrier + device sync); `ms_per_step` = that wall time / K.  A plain run does nothing else: set-up, W warm-up
+steps, the K timed steps, the line.  `--dump-outputs DIR` writes what the last timed step computed (trapEftp of every row of the shard,
+float32) to DIR before the line; the synthetic batch is seeded, so two builds run with the same arguments can be compared output for output.
+
+`--full` adds what is measured or checked beside the headline, after the timed region, and the fields below.
+`parity_max_rel_vs_oracle`: the timed launches' result on the first rows of every rank's shard against the CPU oracle.
+`roofline` prices the single kernel of the chain with the ALGORITHMIC bytes of SURVEY.md 8(d): 16 396 B per waveform
+(4096x4 read + baseline + pick-off time read + energy written) against the 8 TB/s HBM3E peak, from per-launch HIP-event durations on the launch stream.
 `cpu_baseline` times the CPU oracle (C restatement of the reference's numba loops, run the way dspeed's
 ProcessingChain runs them: 16-row blocks, one processor call per block) on a bounded sample of the same batch, on rank 0,
 after the timed region, for every N.  `ge_recipe` (N = 1 only, after the timed region, not part of `value`) is the whole Ge recipe of
@@ -33,7 +38,7 @@ non-zero if any child does.  A process that has touched the GPU is never re-exec
 skip the device (rendezvous, barrier and the line's bookkeeping only): the CPU tests drive the launcher with it.
 
 The bench refuses to print a number when the result of the timed launches deviates from the oracle by more than the
-parity bar (exit code 3), when DSPEED_HIP_ABLATE / a non-default kernel variant is set without --allow-variants
+parity bar (--full; exit code 3), when DSPEED_HIP_ABLATE / a non-default kernel variant is set without --allow-variants
 (exit code 4), or when fewer GPUs are visible than ranks asked for (exit code 5).
 """
 from __future__ import annotations
@@ -73,16 +78,39 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=400)  # (3 ms each: a timed region of more than a second, long enough for the driver's own GPU-activity samples)
     ap.add_argument("--warmup", type=int, default=20)  # (the first ~6 launches after start-up run 5-20 % slower: clocks, first touch)
     ap.add_argument("--rows", type=int, default=0, help="rows per rank (default: 1 000 000 at N=1, 1 250 000 at N>1)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target duration of the single-thread CPU baseline sample")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the legs beside the timed region: cpu_baseline and the Ge recipe (profiling runs)")
-    ap.add_argument("--no-recipe", action="store_true", help="skip the whole-Ge-recipe leg beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check beside the headline: oracle parity, roofline (raw chain, stream read), cpu_baseline, ge_recipe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; rank r > 0 of N: <name>_rank<r>.npy)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(--full) target duration of the single-thread CPU baseline sample")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the legs beside the timed region: cpu_baseline and the Ge recipe (profiling runs)")
+    ap.add_argument("--no-recipe", action="store_true", help="(--full) skip the whole-Ge-recipe leg beside the headline")
     ap.add_argument("--wf-len", type=int, default=0, help="experiment only: other waveform length (trap geometry scaled)")
     ap.add_argument("--dry-run", action="store_true", help="workers skip the device: launcher / rendezvous / bookkeeping only (CPU tests)")
     ap.add_argument("--allow-variants", action="store_true", help="A/B experiments: run although DSPEED_HIP_* kernel switches are set")
     ap.add_argument("--share-gpus", action="store_true", help="rehearsal only: let ranks share devices when fewer GPUs than ranks are visible")
     ap.add_argument("--fail-rank", type=int, default=-1, help="(dry run) this rank exits non-zero: tests the launcher's error path")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="launcher: seconds before the ranks are given up")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BYTES = 64_000_000  # all ranks' dumped outputs together
+
+
+def dump_outputs(out_dir: str, arrays: dict, rows: int, rank: int, world: int) -> None:
+    """Each per-row output of this rank's shard as <out_dir>/<name>.npy (<name>_rank<r>.npy for rank r > 0).  Where all ranks' rows would
+    exceed DUMP_BYTES, the same seeded sample of rows (ascending) is written for every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    keep = max(1, DUMP_BYTES // (4 * len(arrays) * world))
+    idx = None if rows <= keep else np.sort(np.random.default_rng(SEED).choice(rows, keep, replace=False))
+    for name, arr in arrays.items():
+        a = arr.to_numpy()
+        if idx is not None:
+            a = a[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def energy_recipe(tau: float, rise: int, flat: int) -> dict:
@@ -298,12 +326,47 @@ def worker(args) -> int:
     except Exception as exc:  # a DSPFatal of the timed passes: rows of this rank's shard
         print(f"bench.py: rank {rank} (rows from {first_row}): {exc}", file=sys.stderr)
         return 3
+    if args.dump_outputs:  # what the caller of the timed path receives from its last step, before anything below reuses `out`
+        dump_outputs(args.dump_outputs, {"trapEftp": out}, rows, rank, world)
     elapsed = max(gather_floats(t1 - t0))
+    ranks_seen = sorted(int(r) for r in gather_floats(rank))
+    devices_seen = [int(d) for d in gather_floats(device)]
+
+    total_rows = rows * n_gpus
+    value = total_rows * args.steps / elapsed
+    geo = chain.geometry(rows)
+    src_hash = kernel_source_hash()
+    info = device_info(device)
+    line = {
+        "metric": "waveforms/sec, 4096-sample fp32 trap-energy chain",
+        "value": value,
+        "unit": "waveforms/s",
+        "n_gpus": n_gpus,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": (f"{rows} x {WF_LEN} float32 rows per GPU, fused bl_subtract->pole_zero(tau={TAU})->trap_filter({RISE},{FLAT})"
+                                "->fixed_time_pickoff('l'); " + ("BASELINE configs[1]" if n_gpus == 1 else "BASELINE configs[3] shard")),
+                   "rows_per_gpu": rows, "wf_len": WF_LEN, "sharding": "event axis, no collectives", "device": info["name"],
+                   "entry": "build_processing_chain", "kernel": kernel_name, "lds_bytes_per_wave": geo["lds_bytes_per_wave"], "waves_per_block": geo["waves_per_block"],
+                   "blocks": geo["blocks"], "ranks_seen": ranks_seen, "devices_seen": devices_seen, "env": env_switches,
+                   "kernel_source_hash": src_hash},
+    }
+    if not args.full:  # the headline alone: everything below measures or checks beside it
+        if dist is not None:
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(line))
+        return 0
+
     kernel_ms = [starts[k].elapsed_ms(stops[k]) for k in range(args.steps)]
     avg_kernel_ms = float(np.mean(kernel_ms)) if kernel_ms else float("nan")
     rank_kernel_ms = gather_floats(avg_kernel_ms)
-    ranks_seen = sorted(int(r) for r in gather_floats(rank))
-    devices_seen = [int(d) for d in gather_floats(device)]
 
     # ---- parity guard on the output of the TIMED launches (every rank checks its own shard's first rows against the oracle)
     sample_n = 4096 if rank == 0 else 512
@@ -326,11 +389,8 @@ def worker(args) -> int:
             dist.destroy_process_group()
         return 0 if parity <= PARITY_BAR else 3
 
-    total_rows = rows * n_gpus
-    value = total_rows * args.steps / elapsed
     avg_kernel_s = float(np.mean(rank_kernel_ms)) * 1e-3
     achieved = rows * BYTES_PER_WF / avg_kernel_s / 1e9
-    geo = chain.geometry(rows)
 
     # the same program handed to dsp_chain_create directly (no recipe, no ProcessingChain): the number the boundary must not cost
     raw = None
@@ -410,7 +470,6 @@ def worker(args) -> int:
     # prescribes; tools/profile_bench.sh + tools/summarise_profile.py write the file).  Quoted only when the record is for this
     # kernel, these rows and exactly these kernel sources (hash); otherwise null -- counters cannot be read from inside the run.
     traffic, traffic_src = None, None
-    src_hash = kernel_source_hash()
     prof_dir = os.path.join(ROOT, "profiles")
     for name in sorted(os.listdir(prof_dir) if os.path.isdir(prof_dir) else [], reverse=True):
         if not name.endswith("_pmc_traffic.json"):
@@ -440,26 +499,7 @@ def worker(args) -> int:
     except Exception as exc:  # a measurement extra: never fails the bench line
         print(f"[bench] stream-read measurement skipped: {exc}", file=sys.stderr)
 
-    info = device_info(device)
-    line = {
-        "metric": "waveforms/sec, 4096-sample fp32 trap-energy chain",
-        "value": value,
-        "unit": "waveforms/s",
-        "n_gpus": n_gpus,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": (f"{rows} x {WF_LEN} float32 rows per GPU, fused bl_subtract->pole_zero(tau={TAU})->trap_filter({RISE},{FLAT})"
-                                "->fixed_time_pickoff('l'); " + ("BASELINE configs[1]" if n_gpus == 1 else "BASELINE configs[3] shard")),
-                   "rows_per_gpu": rows, "wf_len": WF_LEN, "sharding": "event axis, no collectives", "device": info["name"],
-                   "entry": "build_processing_chain", "kernel": kernel_name, "lds_bytes_per_wave": geo["lds_bytes_per_wave"], "waves_per_block": geo["waves_per_block"],
-                   "blocks": geo["blocks"], "ranks_seen": ranks_seen, "devices_seen": devices_seen, "env": env_switches,
-                   "kernel_source_hash": src_hash},
+    line.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                      "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes_per_launch": rows * BYTES_PER_WF,
                      "bytes_per_waveform": BYTES_PER_WF, "kernel_ms_avg": 1e3 * avg_kernel_s,
@@ -470,7 +510,7 @@ def worker(args) -> int:
         "ge_recipe": ge,
         "parity_max_rel_vs_oracle": parity,
         "parity_bar": PARITY_BAR,
-    }
+    })
     if dist is not None:
         dist.destroy_process_group()
     if not parity <= PARITY_BAR:

@@ -486,6 +486,28 @@ def test_the_recipe_with_the_references_values_is_the_references_file_op_for_op(
         assert sa == sb, sa[0]
 
 
+@pytest.mark.parametrize("fmt", ["json", "yaml"])
+def test_the_recipe_with_the_references_values_as_a_file_is_the_dict_op_for_op(tmp_path, fmt):
+    """recipes.ICPC_REF written out as a recipe file, in the two formats the reference's Ge configurations come in, goes through
+    build_processing_chain as a path and becomes the same device programs as the dict, within the device limits the checks on the reference's
+    own files above hold it to: the file side of those checks, from this repository alone."""
+    import json
+
+    import yaml
+
+    path = tmp_path / f"icpc-dsp-config.{fmt}"
+    path.write_text(json.dumps(recipes.ICPC_REF, indent=1) if fmt == "json" else yaml.safe_dump(recipes.ICPC_REF))
+    tb = _tb(t0=np.zeros(4, dtype=np.float32))
+    theirs, mask_f, out_f = build_processing_chain(str(path), tb)
+    ours, mask_d, out_d = build_processing_chain(recipes.ICPC_REF, tb)
+    assert sorted(mask_f) == sorted(mask_d) and list(out_f) == list(out_d) and len(out_f) == 34
+    P = theirs.program
+    assert len(P.ops) <= _lib.MAX_OPS and len(P.slots) <= _lib.MAX_SLOTS and P.n_sregs <= _lib.MAX_SREGS
+    _check_program_order(P)
+    assert _peak_live_samples(P) <= 2 * 8192 + 1024
+    assert _programs(theirs) == _programs(ours)
+
+
 def test_the_compilers_idea_of_a_piecewise_constant_kernel_is_the_kernels():
     """compiler._piecewise_constant sets CONVOLVE's hint with the limits of csrc/dsp_fir_runs.hip (DSP_FIR_RUNS_MAX runs, DSP_FIR_RUNS_MAX_TAPS taps):
     the two files must agree, and the kernels of the Ge recipes fall where they should"""

@@ -41,7 +41,7 @@ python3 tools/e2e_recipe_rate.py 400000 > "$OUT/e2e_recipe_rate.json" 2> /dev/nu
 for r in 16384 32768 65536; do python3 tools/icpc_rate.py $r 10; done > "$OUT/icpc_rate_small.jsonl" 2> /dev/null
 DSPEED_HIP_NO_FUSED=1 tools/pmc_kernel.sh gpurun_out/prof_${TAG}_vm bench.py --allow-variants --no-cpu --rows 500000 --steps 5 --warmup 2 > /dev/null 2>&1
 python3 tools/pmc_table.py gpurun_out/prof_${TAG}_vm "dsp_vm" "$OUT/vm_pmc.json" > /dev/null
-python3 bench.py --wf-len 8192 --rows 500000 --no-cpu --steps 10 --warmup 5 > "$OUT/bench_8192.json" 2>/dev/null
+python3 bench.py --full --wf-len 8192 --rows 500000 --no-cpu --steps 10 --warmup 5 > "$OUT/bench_8192.json" 2>/dev/null
 tools/pmc_kernel.sh gpurun_out/prof_${TAG}_icpc tools/icpc_rate.py 131072 3 > /dev/null 2>&1
 python3 tools/pmc_table.py gpurun_out/prof_${TAG}_icpc "" "$OUT/icpc_pmc.json" > /dev/null
 python3 tools/c5_instruction_roofline.py "$OUT/c5_rate.json" "$OUT/c5_pmc.json" > "$OUT/c5_rate_roofline.json" 2> /dev/null
