@@ -676,8 +676,16 @@ __device__ __forceinline__ double keep_larger(double a, double b) { return __bui
 // RED = 3: only the threshold walk is wanted (no min_max registers): the first replay tracks nothing, it just yields the carries.
 // RED = 4: as 2 on rows that fill their chunks (len = 64 C: every index is a sample): one v_max per sample -- a NaN never replaces the
 // running maximum in either form; the two differ in the sign of a maximum that is zero.
+//
+// Infinite input samples: an inf enters the running value and leaves it L_k samples later, and inf - inf is NaN from there to the
+// last sample (the recurrence adds to y, so a NaN, once made, persists).  The speculative carries cannot follow that (the float64
+// prefix sums turn every later chunk NaN), so a row whose pass-A sums are not finite takes the true carries lane after lane: each
+// lane replays its chunk from the previous lane's end value, in the reference's order.  The replay that follows then starts from
+// exact carries (no correction), and the trapezoid's NaN state is its value at the row's last sample.  Finite rows never get
+// there: one wave vote per row.
+// Returns whether the trapezoid holds a NaN (the reference's np.isnan(w_in).any() in whatever reads it).
 template <typename T, int KIND, bool STORE, int RED = 0>
-__device__ __forceinline__ void trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, const DSP_PROG DevSlot& ss, const DSP_PROG DevSlot& sd, const int* cap_idx, T* cap_val) {
+__device__ __forceinline__ bool trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, const DSP_PROG DevSlot& ss, const DSP_PROG DevSlot& sd, const int* cap_idx, T* cap_val) {
     const int C = ss.C, lane = lane_id();
     const auto* ps = cx.chunk(ss);
     const double rr = op.fc[0], ll = op.fc[1];
@@ -724,7 +732,8 @@ __device__ __forceinline__ void trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, 
         G = (((E - A[0]) - A[1]) + A[2]) / rr;
     else
         G = (E - A[0]) / rr - (A[1] - A[2]) / ll;
-    const T g = (lane == 0) ? (T)-0.0 : (T)G;
+    T g = (lane == 0) ? (T)-0.0 : (T)G;
+    const bool nonfinite = wave_any(!__builtin_isfinite(run));
 
     // ---- pass B: replay the reference's rounding sequence from the speculative carry
     // lagged sample i - L_k lives in chunk (lane - q_k - 1) at offset C - rho_k + t, one element further once t >= rho_k
@@ -748,8 +757,26 @@ __device__ __forceinline__ void trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, 
         capv[c] = (T)0;
     }
     typename Ctx<T>::LT* __restrict__ pd = STORE ? cx.chunk(sd) : nullptr;  // (another slot than the ones the steps read: loads may pass stores)
-    T y = g;
     const int n_valid = ss.len, i_first = lane * C;
+    bool nan_made = false;
+    if (nonfinite) {  // true carries, one lane at a time (rows with an infinite sample only)
+        T carry = (T)-0.0, yend = (T)0, ylast = (T)0;
+        for (int d = 0; d < 64; ++d) {
+            if (lane == d) {
+                g = carry;
+                T yy = carry;
+                for (int u = 0; u < C; ++u) {
+                    yy = trap_step_r<T, KIND>(yy, ps[u], lag[0][u + (u >= rho[0] ? 1 : 0)], lag[1][u + (u >= rho[1] ? 1 : 0)],
+                                              lag[2][u + (u >= rho[2] ? 1 : 0)], rr, ll, inv_rr, inv_ll);
+                    if (i_first + u == n_valid - 1) ylast = yy;
+                }
+                yend = yy;
+            }
+            carry = readlane(yend, d);
+        }
+        nan_made = wave_any(ylast != ylast);
+    }
+    T y = g;
     T vmin = __builtin_huge_val(), vmax = -__builtin_huge_val();
     int imin = 0x7fffffff, imax = 0x7fffffff;
     {
@@ -791,7 +818,7 @@ __device__ __forceinline__ void trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, 
     // ---- true carries: exact scan of the per-chunk increments
     const double D = (double)y - (double)g;
     const double tstart = wave_exscan_add(D);
-    const double delta = tstart - (double)g;
+    const double delta = nonfinite ? 0.0 : tstart - (double)g;
     if (STORE) {
         if (delta != 0.0) {
 #pragma unroll 8
@@ -893,6 +920,7 @@ __device__ __forceinline__ void trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, 
             wave_sync();
         }
     }
+    return nan_made;
 }
 
 // TRAP_REDUCE: trap filter whose only consumers are min_max and / or time_point_thresh -- the filtered waveform never exists
@@ -906,7 +934,7 @@ __device__ __forceinline__ void op_trap_reduce(Ctx<T>& cx, const DSP_PROG DevOp&
     // sp[3], into register bits 16-29 minus one; bit 30: of the four min_max values only a_max is wanted (numpy.amax)
     const int kind = op.ip[3] & 0xff, pk_mode = (op.ip[3] >> 8) & 0xff, pk_reg = ((op.ip[3] >> 16) & 0x3fff) - 1;
     const bool amax_only = ((op.ip[3] >> 30) & 1) != 0;
-    if (cx.slot_nan(op.src) || op.ic[9]) {
+    auto all_nan = [&]() {  // what min_max, time_point_thresh and fixed_time_pickoff return for a waveform with a NaN in it
         if (lane_id() == 0) {
             auto* r = cx.sregs();
             if (op.dst >= 0)
@@ -915,6 +943,9 @@ __device__ __forceinline__ void op_trap_reduce(Ctx<T>& cx, const DSP_PROG DevOp&
             if (pk_reg >= 0) r[pk_reg] = quiet_nan<T>();
         }
         wave_sync();
+    };
+    if (cx.slot_nan(op.src) || op.ic[9]) {
+        all_nan();
         return;
     }
     int idx[TRAP_NCAP] = {-1, -1, -1, -1};
@@ -935,24 +966,29 @@ __device__ __forceinline__ void op_trap_reduce(Ctx<T>& cx, const DSP_PROG DevOp&
         }
     }
     const bool full = VM_FULL_AMAX && ss.len == 64 * ss.C;  // (every Ge recipe's rows: 8192 = 64 x 128)
+    bool nan_made;
     if (amax_only && kind == DSP_OP_TRAP_FILTER && full)
-        trap_core<T, TRAP_FILTER, false, 4>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_FILTER, false, 4>(cx, op, ss, ss, idx, w4);
     else if (amax_only && kind == DSP_OP_TRAP_NORM && full)
-        trap_core<T, TRAP_NORM, false, 4>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_NORM, false, 4>(cx, op, ss, ss, idx, w4);
     else if (amax_only && kind == DSP_OP_TRAP_FILTER)
-        trap_core<T, TRAP_FILTER, false, 2>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_FILTER, false, 2>(cx, op, ss, ss, idx, w4);
     else if (amax_only && kind == DSP_OP_TRAP_NORM)
-        trap_core<T, TRAP_NORM, false, 2>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_NORM, false, 2>(cx, op, ss, ss, idx, w4);
     else if (kind == DSP_OP_TRAP_FILTER)
-        trap_core<T, TRAP_FILTER, false, 1>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_FILTER, false, 1>(cx, op, ss, ss, idx, w4);
     else if (kind == DSP_OP_TRAP_NORM)
-        trap_core<T, TRAP_NORM, false, 1>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_NORM, false, 1>(cx, op, ss, ss, idx, w4);
     else if (op.dst < 0 && op.ic[10])  // the t0 chain of the Ge recipes: asymmetric trapezoid, rise a power of two, threshold walk only
-        trap_core<T, TRAP_ASYM_P2, false, 3>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_ASYM_P2, false, 3>(cx, op, ss, ss, idx, w4);
     else if (op.dst < 0)
-        trap_core<T, TRAP_ASYM, false, 3>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_ASYM, false, 3>(cx, op, ss, ss, idx, w4);
     else
-        trap_core<T, TRAP_ASYM, false, 1>(cx, op, ss, ss, idx, w4);
+        nan_made = trap_core<T, TRAP_ASYM, false, 1>(cx, op, ss, ss, idx, w4);
+    if (nan_made) {  // (a NaN in the trapezoid: the reductions above saw it through compares and fmax, which drop it)
+        all_nan();
+        return;
+    }
     if (pk_reg >= 0) {
         T out = quiet_nan<T>();
         if (pick) {
@@ -976,13 +1012,17 @@ __device__ __forceinline__ void op_trap(Ctx<T>& cx, const DSP_PROG DevOp& op) {
     }
     const int none[TRAP_NCAP] = {-1, -1, -1, -1};
     T dummy[TRAP_NCAP];
+    bool nan_made;
     if (op.opcode == DSP_OP_TRAP_FILTER)
-        trap_core<T, TRAP_FILTER, true>(cx, op, ss, sd, none, dummy);
+        nan_made = trap_core<T, TRAP_FILTER, true>(cx, op, ss, sd, none, dummy);
     else if (op.opcode == DSP_OP_TRAP_NORM)
-        trap_core<T, TRAP_NORM, true>(cx, op, ss, sd, none, dummy);
+        nan_made = trap_core<T, TRAP_NORM, true>(cx, op, ss, sd, none, dummy);
     else
-        trap_core<T, TRAP_ASYM, true>(cx, op, ss, sd, none, dummy);
-    cx.set_nan(op.dst, false);
+        nan_made = trap_core<T, TRAP_ASYM, true>(cx, op, ss, sd, none, dummy);
+    if (nan_made)
+        cx.set_some_nan(op.dst);  // (the samples before the NaN are real: a store writes them)
+    else
+        cx.set_nan(op.dst, false);
     wave_sync();
 }
 
@@ -1093,15 +1133,18 @@ __device__ __forceinline__ void op_trap_pickoff(Ctx<T>& cx, const DSP_PROG DevOp
             idx[k] = (need && e >= 0 && e < ss.len) ? e : -1;
         }
         T w4[TRAP_NCAP];
+        bool nan_made;
         if (op.ip[3] == DSP_OP_TRAP_FILTER)
-            trap_core<T, TRAP_FILTER, false>(cx, op, ss, ss, idx, w4);
+            nan_made = trap_core<T, TRAP_FILTER, false>(cx, op, ss, ss, idx, w4);
         else if (op.ip[3] == DSP_OP_TRAP_NORM)
-            trap_core<T, TRAP_NORM, false>(cx, op, ss, ss, idx, w4);
+            nan_made = trap_core<T, TRAP_NORM, false>(cx, op, ss, ss, idx, w4);
         else
-            trap_core<T, TRAP_ASYM, false>(cx, op, ss, ss, idx, w4);
-        int fc = 0;
-        out = pickoff_eval(t_in, op.io, ss.len, w4, fc);
-        if (fc) cx.fatal(fc);
+            nan_made = trap_core<T, TRAP_ASYM, false>(cx, op, ss, ss, idx, w4);
+        if (!nan_made) {  // (a NaN anywhere in the trapezoid: NaN, fixed_time_pickoff.py:70)
+            int fc = 0;
+            out = pickoff_eval(t_in, op.io, ss.len, w4, fc);
+            if (fc) cx.fatal(fc);
+        }
     }
     if (lane_id() == 0) cx.sregs()[op.dst] = out;
     wave_sync();
@@ -1308,8 +1351,9 @@ __device__ __forceinline__ double div_by_length(double a, double d, double inv_d
 // the chunk is walked downwards (what has been overwritten lies above), and the L samples below the chunk -- the end of the previous
 // lane's chunk, which that lane overwrites first -- are copied to `side` (64 x Ls elements) before anybody writes.  Needs L <= C.  One
 // 4784-sample waveform less in LDS for the current branch of the Ge recipes: four waveforms per CU instead of three.
+// Returns whether the pass met a non-finite increment (an infinite or NaN sample in its input).
 template <typename T, bool RIGHT, bool INPLACE = false>
-__device__ __forceinline__ void mw_pass_dir(Ctx<T>& cx, const DSP_PROG DevSlot& in, const DSP_PROG DevSlot& out, int L, T length,
+__device__ __forceinline__ bool mw_pass_dir(Ctx<T>& cx, const DSP_PROG DevSlot& in, const DSP_PROG DevSlot& out, int L, T length,
                                             typename Ctx<T>::LT* side = nullptr, int Ls = 0) {
     typedef typename Ctx<T>::LT LT;
     const int n = in.len, C = in.C, lane = lane_id(), v0 = lane * C;
@@ -1445,7 +1489,7 @@ __device__ __forceinline__ void mw_pass_dir(Ctx<T>& cx, const DSP_PROG DevSlot& 
     const double E = wave_exscan_add(S);
     const T g = (lane == 0) ? (T)-0.0 : (T)E;
     // pass B: the reference recurrence from g over the parked increments (each lane reads back what it wrote)
-    T y = g;
+    auto replay = [&](T y) {
     for (int t = 0; t < C;) {
         const int nb = next_cut(t, false);
         LT* yo = p_out + D * (t >= brk_io ? pad_out : 0);
@@ -1471,6 +1515,22 @@ __device__ __forceinline__ void mw_pass_dir(Ctx<T>& cx, const DSP_PROG DevSlot& 
         }
         t = nb;
     }
+    return y;
+    };
+    // An infinite input sample makes an infinite increment, and the speculative starts after it are inf or NaN where the reference
+    // still has finite values or infinities (inf - inf happens only when the sample leaves the window): such a pass takes the true starts
+    // lane after lane -- each lane runs the recurrence from the previous lane's end value, as the reference does.  One vote per pass.
+    const bool nonfinite = wave_any(!__builtin_isfinite(S));
+    if (nonfinite) {
+        T carry = (T)-0.0, yend = (T)0;
+        for (int d = 0; d < 64; ++d) {
+            if (lane == d) yend = replay(carry);
+            carry = readlane(yend, d);
+        }
+        wave_sync();
+        return true;
+    }
+    const T y = replay(g);
     // true starts: exact scan of the per-chunk increments (y before sample 0 is 0)
     const double Dd = (double)y - (double)g;
     const double delta = wave_exscan_add(Dd) - (double)g;
@@ -1496,21 +1556,41 @@ __device__ __forceinline__ void mw_pass_dir(Ctx<T>& cx, const DSP_PROG DevSlot& 
         }
     }
     wave_sync();
+    return false;
 }
 
 template <typename T>
-__device__ __forceinline__ void mw_pass(Ctx<T>& cx, const DSP_PROG DevSlot& in, const DSP_PROG DevSlot& out, int L, T length, bool right) {
+__device__ __forceinline__ bool mw_pass(Ctx<T>& cx, const DSP_PROG DevSlot& in, const DSP_PROG DevSlot& out, int L, T length, bool right) {
     if (right)
-        mw_pass_dir<T, true>(cx, in, out, L, length);
+        return mw_pass_dir<T, true>(cx, in, out, L, length);
     else
-        mw_pass_dir<T, false>(cx, in, out, L, length);
+        return mw_pass_dir<T, false>(cx, in, out, L, length);
 }
 template <typename T>
-__device__ __forceinline__ void mw_pass_inplace(Ctx<T>& cx, const DSP_PROG DevSlot& io, typename Ctx<T>::LT* side, int Ls, int L, T length, bool right) {
+__device__ __forceinline__ bool mw_pass_inplace(Ctx<T>& cx, const DSP_PROG DevSlot& io, typename Ctx<T>::LT* side, int Ls, int L, T length, bool right) {
     if (right)
-        mw_pass_dir<T, true, true>(cx, io, io, L, length, side, Ls);
+        return mw_pass_dir<T, true, true>(cx, io, io, L, length, side, Ls);
     else
-        mw_pass_dir<T, false, true>(cx, io, io, L, length, side, Ls);
+        return mw_pass_dir<T, false, true>(cx, io, io, L, length, side, Ls);
+}
+
+// Whether any of the slot's samples is NaN (a wave vote; for outputs that may hold a NaN that no input sample was).
+template <typename T>
+__device__ __forceinline__ bool slot_any_nan(Ctx<T>& cx, const DSP_PROG DevSlot& s) {
+    bool nan = false;
+    for (int e = lane_id(); e < s.len; e += 64) {
+        const T v = cx.lds[padded_index(s, e)];
+        nan |= v != v;
+    }
+    return wave_any(nan);
+}
+// The NaN state of an output that holds real content: all-NaN-free unless a NaN is in it (then "some NaN": a store writes the samples).
+template <typename T>
+__device__ __forceinline__ void set_nan_from(Ctx<T>& cx, int dst, bool nan) {
+    if (nan)
+        cx.set_some_nan(dst);
+    else
+        cx.set_nan(dst, false);
 }
 
 template <typename T>
@@ -1525,9 +1605,10 @@ __device__ __forceinline__ void op_moving_window_multi(Ctx<T>& cx, const DSP_PRO
     }
     if (op.ip[3] == 1) {  // in place (dst is src), ip[2] = a side slot of 64 * L samples for the chunk ends: every pass in the same buffer
         const T length = (T)op.fc[0];
+        bool nonfinite = false;
         for (int p = 0; p < num; ++p)
-            mw_pass_inplace<T>(cx, ss, cx.lds + sq.off, L | 1, L, length, ((p % 2 == 1) && type == 0) || type == 2);
-        cx.set_nan(op.dst, false);
+            nonfinite |= mw_pass_inplace<T>(cx, ss, cx.lds + sq.off, L | 1, L, length, ((p % 2 == 1) && type == 0) || type == 2);
+        set_nan_from(cx, op.dst, nonfinite && slot_any_nan(cx, sd));  // (finite input, finite increments: no NaN to look for)
         wave_sync();
         return;
     }
@@ -1537,13 +1618,14 @@ __device__ __forceinline__ void op_moving_window_multi(Ctx<T>& cx, const DSP_PRO
     }
     wave_sync();
     const T length = (T)op.fc[0];
+    bool nonfinite = false;
     for (int p = 0; p < num; ++p) {
         const bool right = ((p % 2 == 1) && type == 0) || type == 2;
         const bool to_dst = ((num - 1 - p) % 2) == 0;  // the last pass lands in dst
         const DSP_PROG DevSlot& in = p == 0 ? ss : (to_dst ? sq : sd);
-        mw_pass(cx, in, to_dst ? sd : sq, L, length, right);
+        nonfinite |= mw_pass(cx, in, to_dst ? sd : sq, L, length, right);
     }
-    cx.set_nan(op.dst, false);
+    set_nan_from(cx, op.dst, nonfinite && slot_any_nan(cx, sd));
     wave_sync();
 }
 
@@ -1921,7 +2003,7 @@ __device__ __forceinline__ void op_dwt_haar(Ctx<T>& cx, const DSP_PROG DevOp& op
         }
         wave_sync();
         for (int e = sd.len + lane; e < 64 * sd.C; e += 64) cx.lds[padded_index(sd, e)] = (T)0;
-        cx.set_nan(op.dst, false);
+        set_nan_from(cx, op.dst, slot_any_nan(cx, sd));  // (inf - inf in a Haar pair, or further down the levels)
         wave_sync();
         return;
     }
@@ -1960,7 +2042,7 @@ __device__ __forceinline__ void op_dwt_haar(Ctx<T>& cx, const DSP_PROG DevOp& op
     }
     // keep the pad of dst finite
     for (int e = sd.len + lane; e < 64 * sd.C; e += 64) cx.lds[padded_index(sd, e)] = (T)0;
-    cx.set_nan(op.dst, false);
+    set_nan_from(cx, op.dst, slot_any_nan(cx, sd));
     wave_sync();
 }
 
@@ -2189,8 +2271,8 @@ __device__ __forceinline__ void op_convolve(Ctx<T>& cx, const DSP_PROG DevOp& op
             const int o = ob + r;
             if (o >= ob_true && o < p) {
                 const T v = (T)(tot[r] + (double)acc[r]);
+                vnan |= (v != v);  // (an infinite sample times a zero tap, or infinities of both signs under the kernel)
                 if (AMAX) {
-                    vnan |= (v != v);
                     vmax = v > vmax ? v : vmax;
                 } else {
                     cx.lds[padded_index(sd, o)] = v;
@@ -2207,7 +2289,7 @@ __device__ __forceinline__ void op_convolve(Ctx<T>& cx, const DSP_PROG DevOp& op
         if (lane == 0) cx.sregs()[op.dst] = wave_any(vnan) ? quiet_nan<T>() : vmax;  // numpy.amax propagates NaN
     } else {
         for (int e = p + lane; e < 64 * sd.C; e += 64) cx.lds[padded_index(sd, e)] = (T)0;
-        cx.set_nan(op.dst, false);
+        set_nan_from(cx, op.dst, wave_any(vnan));
     }
     wave_sync();
 }

@@ -28,6 +28,7 @@ Usage:  python oracle/gen_golden.py            (writes tests/golden/*.npz)
         /opt/conda/bin/python3.9 oracle/gen_golden.py --dwt   (PyWavelets 1.1.1 lives there)
         python oracle/gen_golden.py --arithmetic   (only tests/golden/arithmetic.npz)
         python oracle/gen_golden.py --windows      (only tests/golden/windows.npz)
+        python oracle/gen_golden.py --nonfinite    (only tests/golden/nonfinite.npz)
 """
 from __future__ import annotations
 
@@ -796,6 +797,58 @@ def gen_itpt():
     b.save()
 
 
+def gen_nonfinite():
+    """Infinite samples through filters and what reads them (trapezoids, moving windows, convolution, double pole-zero): the filters make
+    NaNs of their own (inf - inf when a sample leaves the running value; inf * 0 under a zero tap), and every reader returns NaN for a
+    waveform with a NaN in it.  Own seed, own book; every intermediate is stored."""
+    rng = np.random.default_rng(0x1AF)
+    b = Book("nonfinite")
+    mm, mv = _ref("min_max"), _ref("moving_windows")
+    rise, flat, fall = 20, 6, 50
+    for dt, tag, n in ((np.float32, "f32", 300), (np.float64, "f64", 160)):
+        x = synth_waveforms(rng, 1, n, dtype=dt, bl=(-20, 20), amp=(300, 900))[0][0]
+        rows = {"clean": x.copy()}
+        for name, places in (("first", [(0, 1)]), ("mid", [(n // 2, 1)]), ("near_end", [(n - rise // 2, 1)]), ("last", [(n - 1, -1)]),
+                             ("pair", [(n // 2, 1), (n // 2 + 1, 1)]), ("both", [(n // 3, 1), (n // 3 + rise // 2, -1)])):
+            r = x.copy()
+            for at, sgn in places:
+                r[at] = sgn * np.inf
+            rows[name] = r
+        rows["all_inf"] = np.full(n, np.inf, dtype=dt)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for rn, w in rows.items():
+                for kind, ints in (("trap_filter", (rise, flat)), ("trap_norm", (rise, flat)), ("asym_trap_filter", (rise, flat, fall))):
+                    f, fatal = call_trap(kind, w, *ints)
+                    red, _ = call_min_max(f)
+                    arrays = {"w_in": w, "w_out": f, "min_max": red, "amax": np.amax(f)}
+                    thr = 0.5 * float(np.max(np.abs(f[np.isfinite(f)]), initial=20.0))
+                    for k, (start, walk) in enumerate(((0, 1), (n - 1, 0), ("t_max", 0), ("t_max", 1))):
+                        ts = red[1] if start == "t_max" else dt(start)  # (t_max NaN: NaN)
+                        arrays[f"tpt{k}"] = call_tpt(f, thr, ts, walk, dt)[0]
+                        arrays[f"tpt{k}_args"] = np.array([thr, ts, walk], dtype=dt)
+                    for mode in "nilh":
+                        arrays[f"pick_{mode}"] = call_pickoff(f, n // 2 + 0.25, mode, dt)[0]
+                    b.add(f"{tag}_{kind}_{rn}", kind, tag, arrays, {"ints": list(ints)})
+                out = np.empty(n, dtype=dt)
+                fatal = run_body(mv.moving_window_multi, w, dt(8), dt(3), np.int32(0), out)
+                b.add(f"{tag}_mw_{rn}", "moving_window_multi", tag, {"w_in": w, "w_out": out, "min_max": call_min_max(out)[0]},
+                      {"length": 8, "num_mw": 3, "mw_type": 0}, fatal)
+                out = np.empty(n - 1, dtype=dt)
+                fatal = run_body(mv.avg_current, w, dt(1), out)
+                b.add(f"{tag}_cur_{rn}", "avg_current", tag, {"w_in": w, "w_out": out, "min_max": call_min_max(out)[0]}, {"length": 1.0}, fatal)
+                k = np.array([0.25, 0.0, -0.5, 1.0, 0.125], dtype=dt)  # (a zero tap: inf * 0)
+                for mode, m in (("v", n - 4), ("s", n), ("f", n + 4)):
+                    out, fatal = call_convolve(w, k, mode, m)
+                    b.add(f"{tag}_conv_{mode}_{rn}", "convolve_wf", tag, {"w_in": w, "kernel": k, "w_out": out, "min_max": call_min_max(out)[0]},
+                          {"mode": mode}, fatal)
+                pz, fatal = call_double_pole_zero(w, 1716.28, 400.0, 0.02, dt)
+                at, _ = call_trap("asym_trap_filter", pz, rise, flat, fall)
+                b.add(f"{tag}_dpz_asym_{rn}", "double_pole_zero>asym_trap_filter", tag,
+                      {"w_in": w, "w_pz": pz, "w_out": at, "min_max": call_min_max(at)[0]},
+                      {"tau1": 1716.28, "tau2": 400.0, "frac": 0.02, "ints": [rise, flat, fall]}, fatal)
+    b.save()
+
+
 def main():
     if "--dwt" in sys.argv:
         gen_dwt()
@@ -822,6 +875,9 @@ def main():
     if "--norm" in sys.argv:
         gen_min_max_norm()
         return
+    if "--nonfinite" in sys.argv:
+        gen_nonfinite()
+        return
     rng = np.random.default_rng(0xD5BEED)
     gen_elementwise(rng)
     gen_pole_zero(rng)
@@ -837,6 +893,7 @@ def main():
     gen_linear_slope_fit()
     gen_itpt()
     gen_min_max_norm()
+    gen_nonfinite()
 
 
 if __name__ == "__main__":

@@ -185,6 +185,26 @@ def test_filter_and_reductions(which, mode, n, offset, stride):
         peak = max(np.abs(got3["filtered"][r]).max(), 1e-30)
         f32_sums = 2.0 ** -23 * np.abs(taps).sum() * np.abs(x[r]).max()  # (what a float32 sum over the taps may lose: 512 taps of both signs)
         assert np.abs(got3["filtered"][r] - got["filtered"][r]).max() <= max(4 * TOL * peak, f32_sums)
+    # the VM on the rows with infinities: its filtered samples and its reductions against the oracle's convolution of those rows and the
+    # oracle's processors on it (a NaN the filter makes is a NaN waveform for every reduction)
+    inf_rows = [5, 6]
+    yo = oracle.convolve_wf(np.ascontiguousarray(x[inf_rows]), taps, mode, got3["filtered"].shape[1])[0]
+    _same_nonfinite(got3["filtered"][inf_rows], yo)
+    want_inf = _reductions_of(yo, thr[inf_rows], walk_from, picks)
+    for name in outs:
+        g, v = got3[name][inf_rows], want_inf[name]
+        if name.startswith(("t_", "walk")):
+            np.testing.assert_array_equal(g, v, err_msg=name)
+        else:
+            _same_nonfinite(g, v)
+            ok = np.isfinite(v)
+            assert np.all(np.abs(g[ok] - v[ok]) <= 1e-5 * np.maximum(np.abs(v[ok]), 1.0)), name
+
+
+def _same_nonfinite(got, want):
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
+    np.testing.assert_array_equal(np.isposinf(got), np.isposinf(want))
+    np.testing.assert_array_equal(np.isneginf(got), np.isneginf(want))
 
 
 def test_stored_only_and_many_rounds():

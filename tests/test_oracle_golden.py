@@ -340,3 +340,77 @@ def test_golden_chains():
     tp0, rc = oracle.time_point_thresh(at, c5["thr"], tmax, 0)
     assert rc == 0
     _eq(tp0, c5["tp_0"], "c5 tp0")
+
+
+# ------------------------------------------------------------------ infinite samples through filters and their readers
+def _same_nonfinite(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    for f in (np.isnan, np.isposinf, np.isneginf):
+        assert np.array_equal(f(got), f(want)), f"{what}: {f.__name__} pattern differs"
+
+
+def _readers_of(c, f):
+    """the book's readers of the filtered row f, recomputed by the oracle from the oracle's f: bit for bit"""
+    f = np.asarray(f)
+    t_min, t_max, a_min, a_max, rc = oracle.min_max(f)
+    assert rc == 0
+    _eq(np.array([t_min[0], t_max[0], a_min[0], a_max[0]], f.dtype), c["min_max"], f"{c.name} min_max")
+
+
+@pytest.mark.parametrize("c", cases("nonfinite"), ids=lambda c: c.name)
+def test_golden_nonfinite(c):
+    w = c["w_in"]
+    if c.kernel in ("trap_filter", "trap_norm", "asym_trap_filter"):
+        f, rc = getattr(oracle, c.kernel)(w, *c.params["ints"])
+        _check_fatal(c, rc)
+        _eq(f[0], c["w_out"], c.name)
+        _readers_of(c, f[0])
+        with np.errstate(invalid="ignore"):
+            _eq(np.float64(np.max(f[0])).astype(w.dtype), c["amax"], f"{c.name} amax")  # numpy.amax: a NaN wins
+        for k in range(4):
+            thr, ts, walk = c[f"tpt{k}_args"]
+            got, rc = oracle.time_point_thresh(f[0], np.array([thr], w.dtype), np.array([ts], w.dtype), int(walk))
+            _eq(got[0], c[f"tpt{k}"], f"{c.name} tpt{k}")
+        for mode in "nilh":
+            got, rc = oracle.fixed_time_pickoff(f[0], len(w) // 2 + 0.25, mode)
+            _eq(got[0], c[f"pick_{mode}"], f"{c.name} pick {mode}")
+        return
+    if c.kernel == "moving_window_multi":
+        p = c.params
+        out, rc = oracle.moving_window_multi(w, p["length"], p["num_mw"], p["mw_type"])
+        want = c["w_out"]
+    elif c.kernel == "avg_current":
+        out, rc = oracle.avg_current(w, c.params["length"], c["w_out"].shape[-1])
+        want = c["w_out"]
+    elif c.kernel == "convolve_wf":
+        out, rc = oracle.convolve_wf(w, c["kernel"], c.params["mode"], c["w_out"].shape[-1])
+        want = c["w_out"]
+        _check_fatal(c, rc)
+        _same_nonfinite(out[0], want, c.name)  # (np.convolve's summation order is its own: finite values to the usual bar)
+        fin = np.isfinite(want)
+        assert_rel_to_peak(np.where(fin, out[0], 0), np.where(fin, want, 0), 1e-6 if c.tag == "f32" else 1e-12, c.name)
+        t_min, t_max, a_min, a_max, _ = oracle.min_max(out[0])
+        mm = c["min_max"]
+        _same_nonfinite(np.array([t_min[0], t_max[0], a_min[0], a_max[0]]), mm, f"{c.name} min_max")
+        if np.isfinite(want).all():
+            assert np.array_equal([t_min[0], t_max[0]], mm[:2]), c.name
+        return
+    else:  # double_pole_zero -> asym_trap_filter
+        p = c.params
+        pz, rc = oracle.double_pole_zero(w, p["tau1"], p["tau2"], p["frac"])
+        _check_fatal(c, rc)
+        _eq_or_libm(c, pz[0], c["w_pz"])
+        out, rc = oracle.asym_trap_filter(c["w_pz"], *p["ints"])  # (from the book's own pole-zero row: the trapezoid bit for bit)
+        want = c["w_out"]
+    _check_fatal(c, rc)
+    _eq(out[0], want, c.name)
+    _readers_of(c, out[0])
+
+
+def test_golden_nonfinite_covers_filter_made_nans():
+    """the book holds the cases the device tests lean on: a NaN that only the filter made, and an infinity the filter keeps to the end"""
+    made = [c.name for c in cases("nonfinite") if not np.isnan(c["w_in"]).any() and np.isnan(c["w_out"]).any()]
+    kept = [c.name for c in cases("nonfinite") if np.isinf(c["w_out"]).any() and not np.isnan(c["w_out"]).any()]
+    for k in ("trap_filter_mid", "trap_norm_both", "asym_trap_filter_first", "mw_mid", "conv_f_first", "dpz_asym_mid"):
+        assert f"f32_{k}" in made, k
+    assert "f32_trap_filter_near_end" in kept and "f32_trap_filter_last" in kept
