@@ -1,10 +1,22 @@
-"""From the steps of a recipe to device programs (``dsp_chain_create``): the fits that run on the rows ahead of the chain, the stages the planner gives
-to specialised kernels (``_extract_stages``), the integer program (``_int_island``), the main program with its slots, fusions and scalar tail
-(``_compile``, ``_split_scalar_tail``) -- and ``_add_step``, which resolves one recipe entry into a step (the role of ProcessorManager.__init__,
-reference src/dspeed/processing_chain.py:1527-1775, and of the processor loop of build_processing_chain, :2655-2823)."""
+"""From the steps of a recipe to device programs (``dsp_chain_create``).  ``_add_step`` resolves one recipe entry into a step (the role of
+ProcessorManager.__init__, reference src/dspeed/processing_chain.py:1527-1775, and of the processor loop of build_processing_chain,
+:2655-2823); ``_compile`` runs the passes over the steps, in this order:
+
+``_int_island``          per-event integer arithmetic into the integer program ahead of everything
+``_extract_fits``        linear_slope_fit onto the rows of the batch, ahead of the chain
+``_extract_stages``      what the planner gives to specialised kernels ahead of the program (``_Stager``: ``_stage_long_firs``,
+                         ``_stage_short_traps``, ``_stage_current_branch``, ``_stage_row_reductions``)
+``_schedule``            the remaining processors ordered for short waveform lifetimes
+``_push_down_slices``, ``_last_uses``    an element-wise result read through one slice computed on it alone; who reads what last
+``_Emitter``             the steps into ops: slots, registers, bindings, fusions (a method per processor family: ``_EMIT``, ``_READ_OFF``)
+``_emit_outputs``, ``_fit_descriptors``  the stores of the outputs; what the runtime launches for the fits
+``_split_scalar_tail``, ``_split_scalar_head``, ``_split_walks``    arithmetic behind / ahead of the waveform ops and the threshold walks
+                         leave the program for kernels with a row per lane or wavefront
+"""
 from __future__ import annotations
 
 import ast
+import copy
 import os
 from types import SimpleNamespace
 
@@ -20,6 +32,8 @@ from .language import (Grid, Quantity, SExpr, Var, _Builder, _GENERATORS, _MODUL
 # processors whose output waveform has the input's dimension name in the gufunc signature ("(n),...->(n)") and therefore its
 # coordinate grid (reference :1601-1619, 1700); the others' outputs have no grid unless the recipe declares one
 _SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi")
+# processors whose result may take the place of their source waveform
+_IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
 
 
 def _add_step(b: _Builder, key, node, new_vars, proc_strings):
@@ -201,6 +215,67 @@ def _loop_dtype(b: _Builder):
                 return np.dtype(np.float64)
     return np.dtype(np.float32)
 
+# ----------------------------------------------------------------------------------------------------------------
+# steps: (processor name, arguments, recipe key); what every pass asks of them
+# ----------------------------------------------------------------------------------------------------------------
+def _is_number(x) -> bool:
+    """a plain number: not a bool, not a ``Quantity``"""
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, Quantity))
+
+
+def _is_integral(x) -> bool:
+    return _is_number(x) and float(x) == int(float(x))
+
+
+def _leaves(a, acc):
+    """the variables an argument is made of (an expression's operands, the waveform under a slice), appended to ``acc``"""
+    if isinstance(a, SExpr):
+        for x in a.args:
+            _leaves(x, acc)
+    elif isinstance(a, Var):
+        acc.append(a)
+    elif isinstance(a, tuple) and a and a[0] == "slice":
+        acc.append(a[1])
+    return acc
+
+
+def _base_of(a):
+    """the waveform variable of an argument, whole or under a slice (None: not a waveform argument)"""
+    if isinstance(a, Var):
+        return a
+    if isinstance(a, tuple) and a and a[0] == "slice":
+        return a[1]
+    return None
+
+
+def _outputs_of(step):
+    return [a for a, r in zip(step[1], _roles(step[0])) if r in "WS"]
+
+
+def _inputs_of(step):
+    return [a for a, r in zip(step[1], _roles(step[0])) if r not in "WS"]
+
+
+def _reads(step, v) -> bool:
+    """does the step read the waveform v, whole or through a slice"""
+    return any(_base_of(a) is v for a in _inputs_of(step))
+
+
+def _without(steps, gone):
+    return [x for x in steps if not any(x is g for g in gone)]
+
+
+def _live_steps(b: _Builder, steps, out_pars):
+    """the steps the outputs depend on, in their order"""
+    needed = {id(v) for o in out_pars for v in _leaves(b.vars.get(o), [])}
+    live = []
+    for st in reversed(steps):
+        if any(id(v) in needed for a in _outputs_of(st) for v in _leaves(a, [])):
+            live.append(st)
+            for a in _inputs_of(st):
+                needed.update(id(v) for v in _leaves(a, []))
+    return live[::-1]
+
 
 def _schedule(steps):
     """Order the processors so that few waveforms are alive at a time -- every waveform variable of a chain lives in LDS, and the
@@ -210,27 +285,14 @@ def _schedule(steps):
     operands exist (it can only end lifetimes); among the ones that create a waveform, the one reading the oldest waveform goes
     first (finish with a waveform before starting on newer ones), an element-wise or recursive filter that may then take its place
     last; a processor whose result could not be consumed yet (a consumer waits for another operand) yields to the others."""
-    def leaves(a, acc):
-        if isinstance(a, SExpr):
-            for x in a.args:
-                leaves(x, acc)
-        elif isinstance(a, Var):
-            acc.append(a)
-        elif isinstance(a, tuple) and a and a[0] == "slice":
-            acc.append(a[1])
-        return acc
-
     producer = {}
     ins, creates = [], []
-    for j, (fn, args, _k) in enumerate(steps):
-        roles = _roles(fn)
-        mine, reads = [], []
-        for a, r in zip(args, roles):
-            (mine if r in "WS" else reads).extend(leaves(a, []))
-        ins.append(reads)
-        creates.append(any(r == "W" for r in roles))
-        for v in mine:
-            producer.setdefault(id(v), j)
+    for j, st in enumerate(steps):
+        ins.append([v for a in _inputs_of(st) for v in _leaves(a, [])])
+        creates.append("W" in _roles(st[0]))
+        for a in _outputs_of(st):
+            for v in _leaves(a, []):
+                producer.setdefault(id(v), j)
     deps = [{producer[id(v)] for v in reads if id(v) in producer and producer[id(v)] != j} for j, reads in enumerate(ins)]
     consumers = [[] for _ in steps]
     for c, d in enumerate(deps):
@@ -258,39 +320,13 @@ def _schedule(steps):
                             todo.append(c)
                 return any(deps[c] - done - family for c in consumers[j])
             # (same oldest waveform: the one that could overwrite it in place waits until the others have read it)
-            j = min(ready, key=lambda j: (waits(j), age(j), steps[j][0].startswith("ew:") or steps[j][0] in ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero"), j))
+            j = min(ready, key=lambda j: (waits(j), age(j), steps[j][0].startswith("ew:") or steps[j][0] in _IN_PLACE, j))
         for a, r in zip(steps[j][1], _roles(steps[j][0])):
             if r == "W" and isinstance(a, Var):
                 born[id(a)] = len(order)
         order.append(j)
         done.add(j)
     return [steps[j] for j in order]
-
-
-def _leaves(a, acc):
-    if isinstance(a, SExpr):
-        for x in a.args:
-            _leaves(x, acc)
-    elif isinstance(a, Var):
-        acc.append(a)
-    elif isinstance(a, tuple) and a and a[0] == "slice":
-        acc.append(a[1])
-    return acc
-
-
-def _live_steps(b: _Builder, steps, out_pars):
-    """the steps the outputs depend on, in their order"""
-    needed = {id(v) for o in out_pars for v in _leaves(b.vars.get(o), [])}
-    live = []
-    for fn, args, key in reversed(steps):
-        roles = _roles(fn)
-        mine = [v for a, r in zip(args, roles) if r in "WS" for v in _leaves(a, [])]
-        if any(id(v) in needed for v in mine):
-            live.append((fn, args, key))
-            for a, r in zip(args, roles):
-                if r not in "WS":
-                    needed.update(id(v) for v in _leaves(a, []))
-    return live[::-1]
 
 
 #: taps from which a convolve_wf / fft_convolve_wf goes to the matrix-core FIR kernels ahead of the program (dsp_fir_mfma.hip needs 64)
@@ -311,6 +347,294 @@ def _piecewise_constant(taps) -> bool:
     return int(np.count_nonzero(edges[1:] != edges[:-1])) <= FIR_RUNS_MAX + 1
 
 
+def _stage_record(what, program, consts, in_vars, alias, outs, **more):
+    """a program that runs ahead of the main one, as the runtime reads it: ``outs`` are (its binding, the binding later programs read the
+    buffer under, samples or None for a column); the device chain and the buffers are made on first use"""
+    return {"what": what, "program": program, "consts": consts, "in_vars": in_vars, "alias": alias, "outs": outs, **more, "chain": None, "bufs": {}}
+
+
+#: how many of each the reductions kernels take in one program (dsp_reduce.hip, and dsp_fir_runs.hip on the waveform it has just filtered)
+_REDUCTIONS_MAX = {"min_max": 1, "amax": 1, "fixed_time_pickoff": 4, "time_point_thresh": 2}
+
+
+def _within_reductions_max(group) -> bool:
+    by_fn = [g[0] for g in group]
+    return all(by_fn.count(fn) <= most for fn, most in _REDUCTIONS_MAX.items())
+
+
+class _Stager:
+    """What the stage families of ``_extract_stages`` share: the steps still left to the program, the stages made so far in launch order,
+    the names of the recipe's outputs, and the questions they ask of the steps."""
+
+    def __init__(self, b: _Builder, steps, out_pars, n_rows, ft):
+        self.b, self.steps, self.n_rows, self.ft = b, steps, n_rows, ft
+        self.stages = []
+        self.out_names = set(out_pars)
+        for o in out_pars:
+            self.out_names.update(v.name for v in _leaves(b.vars.get(o), []))
+
+    def has(self, st) -> bool:
+        return any(st is x for x in self.steps)
+
+    def producer_of(self, v):
+        for st in self.steps:
+            if any(a is v for a in _outputs_of(st)):
+                return st
+        return None
+
+    def users_of(self, v, but=None):
+        return [x for x in self.steps if x is not but and _reads(x, v)]
+
+    def only_user(self, v, fn_name):
+        users = self.users_of(v)
+        return users[0] if len(users) == 1 and users[0][0] == fn_name and users[0][1][0] is v and v.name not in self.out_names else None
+
+    @staticmethod
+    def plain_scalar(x) -> bool:  # a constant, a per-event input column or a fit / stage result: in HBM before the stage runs
+        if isinstance(x, Var):
+            return x.kind == "scalar" and x.sreg is None and ((x.is_input and x.source is not None) or getattr(x, "ext_key", None) is not None)
+        return _is_number(x)
+
+    @staticmethod
+    def row_input(v) -> bool:  # rows of the input table or of an earlier stage
+        return isinstance(v, Var) and v.kind == "wf" and ((v.is_input and v.source is not None) or getattr(v, "ext_key", None) is not None)
+
+    def ancestors(self, v):
+        """steps that compute v from inputs and earlier results, in order"""
+        want, todo = [], [v]
+        seen = set()
+        while todo:
+            x = todo.pop()
+            if id(x) in seen or self.row_input(x):
+                continue
+            seen.add(id(x))
+            st = self.producer_of(x)
+            if st is None:
+                continue
+            if not any(st is w for w in want):
+                want.append(st)
+            for a in _inputs_of(st):
+                todo.extend(_leaves(a, []))
+        return [st for st in self.steps if any(st is w for w in want)]
+
+    def rows_steps(self, v):
+        """steps that read only the rows v and per-event values already in HBM and make per-event values only; in order, closed under
+        their own results"""
+        made, picked = set(), []
+        for st in self.steps:
+            ins, outs = _inputs_of(st), _outputs_of(st)
+            if not outs or "W" in _roles(st[0]) or not any(a is v for a in ins if isinstance(a, Var)):
+                continue
+            others = [a for a in ins if a is not v and isinstance(a, (Var, SExpr, tuple)) and not (isinstance(a, tuple) and a and a[0] == "char")]
+            if all(isinstance(a, Var) and (self.plain_scalar(a) or id(a) in made) for a in others) and all(isinstance(o, Var) for o in outs):
+                picked.append(st)
+                made.update(id(o) for o in outs)
+        return picked
+
+    def reads_off_row(self, st, extremes=()) -> bool:
+        """what the reductions kernels read off a row (dsp_reduce.hip; dsp_fir_runs.hip off the waveform it has just filtered): min_max,
+        numpy.amax, a sample at a constant integral time, time_point_thresh from a constant sample -- or from one of ``extremes``, the t_min /
+        t_max of a min_max in the same launch"""
+        if st[0] in ("min_max", "amax"):
+            return True
+        if st[0] == "fixed_time_pickoff":
+            return _is_integral(st[1][1])
+        if st[0] == "time_point_thresh":
+            _w, thr, start, walk, _o = st[1]
+            return ((_is_number(thr) or self.plain_scalar(thr)) and _is_number(walk) and float(walk) in (0.0, 1.0)
+                    and (_is_integral(start) or any(start is o for o in extremes)))
+        return False
+
+    def stage(self, group, scalars, what, wf=None, drop=None):
+        """Compile the steps ``group`` (on copies of the variables) into a program of its own that writes the per-event values ``scalars``
+        and the waveform ``wf``; from here on these are columns / rows in HBM, and the steps ``drop`` (default: the group) leave the program."""
+        b, outs = self.b, list(scalars) + ([wf] if wf is not None else [])
+        vars2, steps2 = copy.deepcopy((b.vars, group))
+        b2 = copy.copy(b)
+        b2.vars, b2.steps, b2._conversions, b2.stage_ft = vars2, list(steps2), {}, self.ft
+        for v in vars2.values():
+            if isinstance(v, Var) and getattr(v, "aux_io", None) is not None:
+                v.aux_io = None  # (an index into the main program's bindings; the stage binds the fit's column by its name)
+        pc, _tb = _compile(b2, [o.name for o in outs], self.n_rows, [], stage_mode=True)
+        self.stages.append(_stage_record(what, pc._program, pc._consts, pc._in_vars, pc._ext_alias,
+                                         [(f"out:{o.name}", f"in:{o.name}", o.length if o.kind == "wf" else None) for o in outs]))
+        for o in outs:
+            if o.kind == "wf":  # pole_zero returns an all-NaN waveform for an input with a NaN and DSPFatal for a NaN of its own making
+                made_by = self.producer_of(o)
+                o.nan_uniform = made_by is not None and made_by[0] == "pole_zero"
+            o.ext_key, o.is_input, o.slot, o.sreg = f"in:{o.name}", True, None, None
+            if o.kind == "wf":
+                o.ext_len, o.offset, o.dtype = o.length, 0, np.dtype(np.float32)
+        for o in scalars:
+            o.kind = "scalar"
+        self.steps = _without(self.steps, group if drop is None else drop)
+
+    def move_ahead(self, operands) -> bool:
+        """What computes these per-event operands from rows in HBM (min_max of the t0-filtered waveform, the t0 estimate) moves ahead of the
+        program, as a small program of its own on the same rows.  False, and nothing moved, if one of them is not computed that way."""
+        movers = []
+        for a in operands:
+            pst = self.producer_of(a) if isinstance(a, Var) else None
+            rows_v = next((x for x in _inputs_of(pst) if isinstance(x, Var) and self.row_input(x)), None) if pst else None
+            group = self.rows_steps(rows_v) if rows_v is not None else []
+            if pst is None or not any(pst is g for g in group):
+                return False
+            movers.append((rows_v, group))
+        for rows_v, group in movers:
+            group = [g for g in group if self.has(g)]  # (two operands off the same rows: moved with the first)
+            if group:
+                self.stage(group, [o for g in group for o in _outputs_of(g)], f"per-event values of {rows_v.name}")
+        return True
+
+
+def _fir_input_as_rows(cx: _Stager, base):
+    """The FIR kernels read rows from HBM.  Returns what joins the filter's own stage ahead of it: nothing for a chain input or what a
+    stage wrote (made here, if need be, by a small program that writes the filter's input to HBM), the bl_subtract of an input that is done
+    while staging; None if the input cannot become rows."""
+    if cx.row_input(base):
+        return []
+    pst = cx.producer_of(base)
+    if (pst is not None and pst[0] == "bl_subtract" and cx.row_input(_base_of(pst[1][0])) and cx.plain_scalar(pst[1][1])
+            and base.name not in cx.out_names):
+        return [pst]
+    anc = cx.ancestors(base)
+    if not anc or any(a[0] in ("convolve_wf", "fft_convolve_wf") for a in anc):
+        return None
+    # min_max of the raw rows goes along: the pole-zero rows kernel streams them anyway (dsp_pz.hip), a launch of the
+    # reductions kernel would read them once more
+    extra, made = [], []
+    raw = _base_of(anc[0][1][0]) if anc[0][0] in ("bl_subtract", "pole_zero") else None
+    if (cx.ft == np.dtype(np.float32) and isinstance(raw, Var) and cx.row_input(raw) and [a[0] for a in anc] in (["bl_subtract", "pole_zero"], ["pole_zero"])
+            and os.environ.get("DSPEED_HIP_NO_ROW_REDUCTIONS") != "1"):
+        mm = [g for g in cx.rows_steps(raw) if g[0] == "min_max" and g[1][0] is raw]
+        if len(mm) == 1:
+            extra, made = mm, list(mm[0][1][1:5])
+    cx.stage(extra + anc, made, f"{base.name} -> HBM" + (f" + min_max of {raw.name}" if extra else ""), wf=base, drop=extra)
+    return []
+
+
+def _stage_long_firs(cx: _Stager):
+    """Each ``convolve_wf`` with a constant kernel of STAGE_MIN_TAPS or more taps, with its input as rows."""
+    for st in list(cx.steps):
+        fn, args, key = st
+        if fn not in ("convolve_wf", "fft_convolve_wf") or not cx.has(st):
+            continue
+        taps, out = args[1], args[3]
+        if not (isinstance(taps, Var) and taps.kind == "taps" and taps.const is not None and isinstance(out, Var) and out.length):
+            continue
+        m = int(taps.length)
+        base, n_in = _base_of(args[0]), _wf_len(args[0])
+        if base is None or n_in is None or m < STAGE_MIN_TAPS or m > n_in or not np.isfinite(taps.const).all():
+            continue
+        mode = args[2][1][0] if isinstance(args[2], tuple) and args[2][0] == "char" else (chr(args[2]) if isinstance(args[2], (int, np.integer)) else None)
+        want_len = {"v": n_in - m + 1, "s": n_in, "f": n_in + m - 1}.get(mode)
+        if want_len is None or want_len != out.length:
+            continue  # (the program's own op reports it)
+        pre = _fir_input_as_rows(cx, base)
+        if pre is None:
+            continue
+        # --- the filter itself; numpy.amax goes along when it is the only reader
+        users = cx.users_of(out, but=st)
+        if (len(users) == 1 and users[0][0] == "amax" and users[0][1][0] is out and out.name not in cx.out_names and isinstance(users[0][1][2], Var)
+                and mode == "v" and out.length <= 320):  # (what the amax form of the kernel takes; else the filtered waveform is kept)
+            cx.stage(pre + [st, users[0]], [users[0][1][2]], f"{fn} {key} + amax", drop=[st, users[0]])
+            continue
+        # a piecewise-constant kernel (the t0 filter) on float32 rows: prefix sums instead of products, and what the recipe reads off
+        # the filtered waveform -- min_max, the threshold walk of the t0 estimate -- in the same pass; a filtered waveform that nothing
+        # else reads then never reaches HBM (csrc/dsp_fir_runs.hip)
+        group = []
+        if (cx.ft == np.dtype(np.float32) and not pre and isinstance(args[0], Var) and cx.row_input(args[0]) and np.dtype(args[0].dtype) == np.dtype(np.float32)
+                and n_in % 8 == 0 and _piecewise_constant(taps.const) and os.environ.get("DSPEED_HIP_NO_FIR_RUNS") != "1"):
+            for g in cx.rows_steps(out):
+                if g[1][0] is out and cx.reads_off_row(g, extremes=[o for x in group if x[0] == "min_max" for o in x[1][1:3]]):
+                    group.append(g)
+            if not _within_reductions_max(group):
+                group = []
+        if group:
+            keep = out.name in cx.out_names or any(not any(x is g for g in group) for x in users)
+            cx.stage([st] + group, [o for g in group for o in _outputs_of(g)], f"{fn} {key} on prefix sums + per-event values of {out.name}",
+                     wf=out if keep else None)
+        else:
+            cx.stage(pre + [st], [], f"{fn} {key}", wf=out, drop=[st])
+
+
+def _stage_short_traps(cx: _Stager):
+    """Short trapezoids that only feed min_max / time_point_thresh, on rows: the lane-per-waveform kernel (dsp_rows.hip) runs the
+    reference's recurrence as it is, 64 waveforms per instruction, where the program replays it twice per waveform (the t0 chain of the
+    Ge recipes, asym_trap_filter -> time_point_thresh: a fifth of the program).  The kernel reads rows, so the trapezoid's input must
+    be rows (an input or what a stage above wrote) and every per-event operand a column in HBM: what such an operand depends on --
+    min_max of the t0-filtered waveform -- moves ahead of the program as well, as a small program of its own on the same rows."""
+    for st in list(cx.steps):
+        fn, args, key = st
+        if fn not in ("trap_filter", "trap_norm", "asym_trap_filter") or not cx.has(st):
+            continue
+        src, dst = args[0], args[-1]
+        ints = args[1:-1]
+        if not (isinstance(src, Var) and cx.row_input(src) and isinstance(dst, Var) and dst.name not in cx.out_names and src.length and src.length % 8 == 0
+                and src.length >= 16 and all(_is_integral(x) for x in ints)):
+            continue
+        iv = [int(x) for x in ints]
+        lags = (iv[0], iv[0] + iv[1], iv[0] + iv[1] + iv[2]) if fn == "asym_trap_filter" else (iv[0], iv[0] + iv[1], 2 * iv[0] + iv[1])
+        if min(lags) < 8 or (((max(lags) + 8 + 7) // 8) * 8 + 8) * 256 > 80 * 1024:
+            continue
+        users = cx.users_of(dst, but=st)
+        kinds = sorted(x[0] for x in users)
+        if kinds not in (["min_max"], ["time_point_thresh"], ["min_max", "time_point_thresh"]) or not all(x[1][0] is dst for x in users):
+            continue
+        mm_outs = [o for x in users if x[0] == "min_max" for o in x[1][1:5]]
+        # per-event operands of the walk: in HBM already, the reduction's own t_min / t_max, or movable ahead of the program
+        need = [a for x in users if x[0] == "time_point_thresh" for a in x[1][1:4] if isinstance(a, (Var, SExpr))]
+        if not cx.move_ahead([a for a in need if not (isinstance(a, Var) and (cx.plain_scalar(a) or any(a is o for o in mm_outs)))]):
+            continue
+        cx.stage([st] + users, [o for x in users for o in _outputs_of(x)], f"{fn} {key} on rows")
+
+
+def _stage_current_branch(cx: _Stager):
+    """The current branch (windower -> avg_current -> upsampler -> moving_window_multi -> min_max, the A/E part of the Ge recipes) on
+    rows: three moving averages that alternate direction are float32 recurrences over 4784 samples each -- 30 % of the program, which
+    replays their rounding twice per pass.  dsp_current.hip gives every waveform a lane and runs them as written (bit-exact), keeping
+    checkpoints instead of the intermediate waveforms.  Needs the window's source as rows in HBM and its start as a column there."""
+    for st in list(cx.steps):
+        if st[0] != "windower" or not cx.has(st):
+            continue
+        src, start, w_le = st[1]
+        if not (isinstance(src, Var) and cx.row_input(src) and np.dtype(src.dtype) == np.dtype(np.float32) and isinstance(w_le, Var)):
+            continue
+        # the window's start (tp_0_est) is computed by the program from rows in HBM (the t0-filtered waveform): what computes it moves ahead
+        # as a small program of its own on those rows, like the operands of the t0 chain's walk above
+        if not cx.plain_scalar(start) and not cx.move_ahead([start]):
+            continue
+        chain_steps, v = [st], w_le
+        for fn_name in ("avg_current", "upsampler", "moving_window_multi", "min_max"):
+            nxt = cx.only_user(v, fn_name)
+            if nxt is None:
+                break
+            chain_steps.append(nxt)
+            v = nxt[1][-1]
+        outs = list(chain_steps[-1][1][1:5])
+        if len(chain_steps) == 5 and all(isinstance(o, Var) for o in outs):
+            cx.stage(chain_steps, outs, f"current branch of {src.name} on rows")
+
+
+def _stage_row_reductions(cx: _Stager):
+    """Per-event values read straight off rows in HBM: min_max, numpy.amax and a sample at a constant integral time of an input or of a
+    stage's waveform, a walk from a constant sample (from an extreme of the same rows: what the t0 chain above moves).  In the program they
+    cost a LOAD of the whole row into LDS and a pass over it, at the occupancy the longest waveform leaves (one wavefront per SIMD for 8192
+    samples); dsp_reduce.hip streams the row through registers once."""
+    for v in [x for x in list(cx.b.vars.values()) if cx.row_input(x)]:
+        if np.dtype(v.dtype) not in (np.dtype(np.float32), np.dtype(np.int16), np.dtype(np.uint16)):
+            continue
+        group = [g for g in cx.rows_steps(v) if cx.reads_off_row(g) and g[1][0] is v]
+        if not group or not _within_reductions_max(group):
+            continue
+        rest = _without(cx.steps, group)
+        if any(_reads(x, v) for x in rest):
+            continue  # (the program loads these rows for something else as well: there the reduction is one more pass over LDS, no row traffic)
+        if not any(r in "wW" for x in rest for r in _roles(x[0])):
+            continue  # (the program would be left without a waveform: nothing gained by a launch of its own)
+        cx.stage(group, [o for g in group for o in _outputs_of(g)], f"per-event values of {v.name} off its rows")
+
+
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     """Long FIRs leave the program: each ``convolve_wf`` with a constant kernel of STAGE_MIN_TAPS or more taps becomes a launch of the
     matrix-core FIR kernels ahead of the program (one waveform per wavefront is the wrong shape for 133 x 8192 or 5792 x 301
@@ -318,334 +642,60 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     input and output slots leave the program's LDS).  The FIR kernels read rows from HBM, so a filter's input is a chain input, the
     input minus a per-event value (bl_subtract: done while staging), or -- anything else, the pole-zero corrected waveform of the Ge
     recipes -- a waveform that a small program of its own writes to HBM first (32 kB per waveform: noise at a recipe's rate).  What a
-    stage wrote is an input of the later stages and of the program; processors that only fed a stage drop out of the program.
+    stage wrote is an input of the later stages and of the program; processors that only fed a stage drop out of the program.  With rows
+    in HBM, the other stage families follow: short trapezoids, the current branch, reductions read off rows.
     Returns (steps left to the program, stages in launch order)."""
-    import copy
-
     if all(st[0] in ("convolve_wf", "fft_convolve_wf", "amax", "bl_subtract", "alias") for st in steps):
         return steps, []  # the program is nothing but filters (BASELINE configs[2]): dsp_chain_create gives it the FIR kernel as a whole
-    out_names = set(out_pars)
-    for o in out_pars:
-        for v in _leaves(b.vars.get(o), []):
-            out_names.add(v.name)
-    stages = []
-
-    def base_of(a):
-        if isinstance(a, Var):
-            return a
-        if isinstance(a, tuple) and a and a[0] == "slice":
-            return a[1]
-        return None
-
-    def producer_of(v):
-        for st in steps:
-            for a, r in zip(st[1], _roles(st[0])):
-                if r in "WS" and a is v:
-                    return st
-        return None
-
-    def plain_scalar(x):  # a constant, a per-event input column or a fit / stage result: in HBM before the stage runs
-        if isinstance(x, Var):
-            return x.kind == "scalar" and x.sreg is None and ((x.is_input and x.source is not None) or getattr(x, "ext_key", None) is not None)
-        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, Quantity))
-
-    def row_input(v):  # rows of the input table or of an earlier stage
-        return isinstance(v, Var) and v.kind == "wf" and ((v.is_input and v.source is not None) or getattr(v, "ext_key", None) is not None)
-
-    def ancestors(v):
-        """steps that compute v from inputs and earlier results, in order"""
-        want, todo = [], [v]
-        seen = set()
-        while todo:
-            x = todo.pop()
-            if id(x) in seen or row_input(x):
-                continue
-            seen.add(id(x))
-            st = producer_of(x)
-            if st is None:
-                continue
-            if not any(st is w for w in want):
-                want.append(st)
-            for a, r in zip(st[1], _roles(st[0])):
-                if r not in "WS":
-                    todo.extend(_leaves(a, []))
-        return [st for st in steps if any(st is w for w in want)]
-
-    def build(stage_steps, outs, what):
-        """compile stage_steps (on copies of the variables) into a program that writes the variables ``outs``"""
-        vars2, steps2 = copy.deepcopy((b.vars, stage_steps))
-        b2 = copy.copy(b)
-        b2.vars, b2.steps, b2._conversions, b2.stage_ft = vars2, list(steps2), {}, ft
-        for v in vars2.values():
-            if isinstance(v, Var) and getattr(v, "aux_io", None) is not None:
-                v.aux_io = None  # (an index into the main program's bindings; the stage binds the fit's column by its name)
-        pc, _tb = _compile(b2, [o.name for o in outs], n_rows, [], stage_mode=True)
-        rec = {"what": what, "program": pc._program, "consts": pc._consts, "in_vars": pc._in_vars, "alias": pc._ext_alias,
-               "outs": [(f"out:{o.name}", f"in:{o.name}", o.length if o.kind == "wf" else None) for o in outs], "chain": None, "bufs": {}}
-        stages.append(rec)
-        for o in outs:  # from here on the variable is a row / column in HBM
-            if o.kind == "wf":  # pole_zero returns an all-NaN waveform for an input with a NaN and DSPFatal for a NaN of its own making
-                made_by = producer_of(o)
-                o.nan_uniform = made_by is not None and made_by[0] == "pole_zero"
-            o.ext_key, o.is_input, o.slot, o.sreg = f"in:{o.name}", True, None, None
-            if o.kind == "wf":
-                o.ext_len, o.offset, o.dtype = o.length, 0, np.dtype(np.float32)
-
-    def rows_steps(v):
-        """steps that read only the rows v and per-event values already in HBM and make per-event values only; in order, closed under
-        their own results"""
-        made, picked = set(), []
-        for st in steps:
-            roles = _roles(st[0])
-            ins = [(a, r) for a, r in zip(st[1], roles) if r not in "WS"]
-            outs = [a for a, r in zip(st[1], roles) if r in "WS"]
-            if not outs or any(r == "W" for r in roles) or st[0] in ("alias",) or not any(base_of(a) is v and isinstance(a, Var) for a, r in ins):
-                continue
-            ok = True
-            for a, r in ins:
-                if base_of(a) is v and isinstance(a, Var):
-                    continue
-                if isinstance(a, (Var, SExpr, tuple)) and not (isinstance(a, tuple) and a and a[0] == "char"):
-                    ok = ok and isinstance(a, Var) and (plain_scalar(a) or id(a) in made)
-            if ok and all(isinstance(o, Var) and o.name not in out_names for o in outs[:0]) and all(isinstance(o, Var) for o in outs):
-                picked.append(st)
-                made.update(id(o) for o in outs)
-        return picked
-
-    def fusable(g, group):
-        """what the run-length FIR kernel reads off the waveform it has just filtered (the reductions of dsp_reduce.hip): min_max, numpy.amax,
-        a sample at a constant integral time, time_point_thresh from a constant sample or from min_max's t_min / t_max"""
-        number = lambda x: isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, Quantity))  # noqa: E731
-        if g[0] in ("min_max", "amax"):
-            return True
-        if g[0] == "fixed_time_pickoff":
-            return number(g[1][1]) and float(g[1][1]) == int(float(g[1][1]))
-        if g[0] == "time_point_thresh":
-            _w, thr, start, walk, _o = g[1]
-            extremes = [o for x in group if x[0] == "min_max" for o in x[1][1:3]]
-            return ((number(thr) or plain_scalar(thr)) and number(walk) and float(walk) in (0.0, 1.0)
-                    and ((number(start) and float(start) == int(float(start))) or any(start is o for o in extremes)))
-        return False
-
-    for st in list(steps):
-        fn, args, key = st
-        if fn not in ("convolve_wf", "fft_convolve_wf") or not any(st is x for x in steps):
-            continue
-        taps, out = args[1], args[3]
-        if not (isinstance(taps, Var) and taps.kind == "taps" and taps.const is not None and isinstance(out, Var) and out.length):
-            continue
-        m = int(taps.length)
-        base, n_in = base_of(args[0]), _wf_len(args[0])
-        if base is None or n_in is None or m < STAGE_MIN_TAPS or m > n_in or not np.isfinite(taps.const).all():
-            continue
-        mode = args[2][1][0] if isinstance(args[2], tuple) and args[2][0] == "char" else (chr(args[2]) if isinstance(args[2], (int, np.integer)) else None)
-        want_len = {"v": n_in - m + 1, "s": n_in, "f": n_in + m - 1}.get(mode)
-        if want_len is None or want_len != out.length:
-            continue  # (the program's own op reports it)
-        # --- the filter's input as rows in HBM
-        pre = []
-        if not row_input(base):
-            pst = producer_of(base)
-            direct = (pst is not None and pst[0] == "bl_subtract" and row_input(base_of(pst[1][0])) and plain_scalar(pst[1][1])
-                      and base.name not in out_names)
-            if direct:
-                pre = [pst]
-            else:
-                anc = ancestors(base)
-                if not anc or any(a[0] in ("convolve_wf", "fft_convolve_wf") for a in anc):
-                    continue
-                # min_max of the raw rows goes along: the pole-zero rows kernel streams them anyway (dsp_pz.hip), a launch of the
-                # reductions kernel would read them once more
-                extra, made = [], []
-                raw = base_of(anc[0][1][0]) if anc and anc[0][0] in ("bl_subtract", "pole_zero") else None
-                if (ft == np.dtype(np.float32) and isinstance(raw, Var) and row_input(raw) and [a[0] for a in anc] in (["bl_subtract", "pole_zero"], ["pole_zero"])
-                        and os.environ.get("DSPEED_HIP_NO_ROW_REDUCTIONS") != "1"):
-                    mm = [g for g in rows_steps(raw) if g[0] == "min_max" and g[1][0] is raw]
-                    if len(mm) == 1:
-                        extra, made = mm, [o for o in mm[0][1][1:5]]
-                build(extra + anc, made + [base], f"{base.name} -> HBM" + (f" + min_max of {raw.name}" if extra else ""))
-                for o in made:
-                    o.kind = "scalar"
-                steps = [x for x in steps if not any(x is g for g in extra)]
-        # --- the filter itself; numpy.amax goes along when it is the only reader
-        users = [x for x in steps if x is not st and any(base_of(a) is out for a, r in zip(x[1], _roles(x[0])) if r not in "WS")]
-        if (len(users) == 1 and users[0][0] == "amax" and users[0][1][0] is out and out.name not in out_names and isinstance(users[0][1][2], Var)
-                and mode == "v" and out.length <= 320):  # (what the amax form of the kernel takes; else the filtered waveform is kept)
-            build(pre + [st, users[0]], [users[0][1][2]], f"{fn} {key} + amax")
-            users[0][1][2].kind = "scalar"
-            gone = [st, users[0]]
-        else:
-            # a piecewise-constant kernel (the t0 filter) on float32 rows: prefix sums instead of products, and what the recipe reads off
-            # the filtered waveform -- min_max, the threshold walk of the t0 estimate -- in the same pass; a filtered waveform that nothing
-            # else reads then never reaches HBM (csrc/dsp_fir_runs.hip)
-            group = []
-            if (ft == np.dtype(np.float32) and not pre and isinstance(args[0], Var) and row_input(args[0]) and np.dtype(args[0].dtype) == np.dtype(np.float32)
-                    and n_in % 8 == 0 and _piecewise_constant(taps.const) and os.environ.get("DSPEED_HIP_NO_FIR_RUNS") != "1"):
-                for g in rows_steps(out):
-                    if g[1][0] is out and fusable(g, group):
-                        group.append(g)
-                by_fn = [g[0] for g in group]
-                if by_fn.count("min_max") > 1 or by_fn.count("amax") > 1 or by_fn.count("fixed_time_pickoff") > 4 or by_fn.count("time_point_thresh") > 2:
-                    group = []
-            if group:
-                made = [o for g in group for o, r in zip(g[1], _roles(g[0])) if r in "WS"]
-                keep = out.name in out_names or any(not any(x is g for g in group) for x in users)
-                build([st] + group, made + ([out] if keep else []), f"{fn} {key} on prefix sums + per-event values of {out.name}")
-                for o in made:
-                    o.kind = "scalar"
-                gone = [st] + group
-            else:
-                build(pre + [st], [out], f"{fn} {key}")
-                gone = [st]
-        steps = [x for x in steps if not any(x is g for g in gone)]
-    if not stages:
-        return steps, stages
-
-    # --- short trapezoids that only feed min_max / time_point_thresh, on rows: the lane-per-waveform kernel (dsp_rows.hip) runs the
-    # reference's recurrence as it is, 64 waveforms per instruction, where the program replays it twice per waveform (the t0 chain of the
-    # Ge recipes, asym_trap_filter -> time_point_thresh: a fifth of the program).  The kernel reads rows, so the trapezoid's input must
-    # be rows (an input or what a stage above wrote) and every per-event operand a column in HBM: what such an operand depends on --
-    # min_max of the t0-filtered waveform -- moves ahead of the program as well, as a small program of its own on the same rows.
-    trap_fns = ("trap_filter", "trap_norm", "asym_trap_filter")
-    for st in list(steps):
-        fn, args, key = st
-        if fn not in trap_fns or not any(st is x for x in steps):
-            continue
-        src, dst = args[0], args[-1]
-        ints = args[1:-1]
-        if not (isinstance(src, Var) and row_input(src) and isinstance(dst, Var) and dst.name not in out_names and src.length and src.length % 8 == 0
-                and src.length >= 16 and all(isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, Quantity)) and float(x) == int(x)
-                                             for x in ints)):
-            continue
-        iv = [int(x) for x in ints]
-        lags = (iv[0], iv[0] + iv[1], iv[0] + iv[1] + iv[2]) if fn == "asym_trap_filter" else (iv[0], iv[0] + iv[1], 2 * iv[0] + iv[1])
-        if min(lags) < 8 or (((max(lags) + 8 + 7) // 8) * 8 + 8) * 256 > 80 * 1024:
-            continue
-        users = [x for x in steps if x is not st and any(base_of(a) is dst for a, r in zip(x[1], _roles(x[0])) if r not in "WS")]
-        kinds = sorted(x[0] for x in users)
-        if kinds not in (["min_max"], ["time_point_thresh"], ["min_max", "time_point_thresh"]) or not all(x[1][0] is dst for x in users):
-            continue
-        mm_outs = [o for x in users if x[0] == "min_max" for o in x[1][1:5]]
-        # per-event operands of the walk: in HBM already, the reduction's own t_min / t_max, or movable ahead of the program
-        need = [a for x in users if x[0] == "time_point_thresh" for a in x[1][1:4] if isinstance(a, (Var, SExpr))]
-        movers, fine = [], True
-        for a in need:
-            if isinstance(a, Var) and (plain_scalar(a) or any(a is o for o in mm_outs)):
-                continue
-            pst = producer_of(a) if isinstance(a, Var) else None
-            rows_v = next((base_of(x) for x, r in zip(pst[1], _roles(pst[0])) if r not in "WS" and isinstance(x, Var) and row_input(x)), None) if pst else None
-            group = rows_steps(rows_v) if rows_v is not None else []
-            if pst is None or not any(pst is g for g in group):
-                fine = False
-                break
-            movers.append((rows_v, group))
-        if not fine:
-            continue
-        for rows_v, group in movers:
-            group = [g for g in group if any(g is x for x in steps)]
-            if not group:
-                continue
-            outs = [o for g in group for o, r in zip(g[1], _roles(g[0])) if r in "WS"]
-            build(group, outs, f"per-event values of {rows_v.name}")
-            for o in outs:
-                o.kind = "scalar"
-            steps = [x for x in steps if not any(x is g for g in group)]
-        outs = [o for x in users for o, r in zip(x[1], _roles(x[0])) if r in "WS"]
-        build([st] + users, outs, f"{fn} {key} on rows")
-        for o in outs:
-            o.kind = "scalar"
-        steps = [x for x in steps if x is not st and not any(x is u for u in users)]
-
-    # --- the current branch (windower -> avg_current -> upsampler -> moving_window_multi -> min_max, the A/E part of the Ge recipes) on
-    # rows: three moving averages that alternate direction are float32 recurrences over 4784 samples each -- 30 % of the program, which
-    # replays their rounding twice per pass.  dsp_current.hip gives every waveform a lane and runs them as written (bit-exact), keeping
-    # checkpoints instead of the intermediate waveforms.  Needs the window's source as rows in HBM and its start as a column there.
-    def only_user(v, fn_name):
-        users = [x for x in steps if any(base_of(a) is v for a, r in zip(x[1], _roles(x[0])) if r not in "WS")]
-        return users[0] if len(users) == 1 and users[0][0] == fn_name and users[0][1][0] is v and v.name not in out_names else None
-
-    for st in list(steps):
-        if st[0] != "windower" or not any(st is x for x in steps):
-            continue
-        src, start, w_le = st[1]
-        if not (isinstance(src, Var) and row_input(src) and np.dtype(src.dtype) == np.dtype(np.float32) and isinstance(w_le, Var)):
-            continue
-        if not plain_scalar(start):
-            # the window's start (tp_0_est) is computed by the program from rows in HBM (the t0-filtered waveform): what computes it moves ahead
-            # as a small program of its own on those rows, like the operands of the t0 chain's walk above
-            pst = producer_of(start) if isinstance(start, Var) else None
-            rows_v = next((base_of(x) for x, r in zip(pst[1], _roles(pst[0])) if r not in "WS" and isinstance(x, Var) and row_input(x)), None) if pst else None
-            group = [g for g in (rows_steps(rows_v) if rows_v is not None else []) if any(g is x for x in steps)]
-            if pst is None or not any(pst is g for g in group):
-                continue
-            moved = [o for g in group for o, r in zip(g[1], _roles(g[0])) if r in "WS"]
-            build(group, moved, f"per-event values of {rows_v.name}")
-            for o in moved:
-                o.kind = "scalar"
-            steps = [x for x in steps if not any(x is g for g in group)]
-        chain_steps, v = [st], w_le
-        for fn_name in ("avg_current", "upsampler", "moving_window_multi", "min_max"):
-            nxt = only_user(v, fn_name)
-            if nxt is None:
-                break
-            chain_steps.append(nxt)
-            v = nxt[1][-1]
-        if len(chain_steps) != 5:
-            continue
-        outs = [o for o in chain_steps[-1][1][1:5]]
-        if not all(isinstance(o, Var) for o in outs):
-            continue
-        build(chain_steps, outs, f"current branch of {src.name} on rows")
-        for o in outs:
-            o.kind = "scalar"
-        steps = [x for x in steps if not any(x is c for c in chain_steps)]
-
+    cx = _Stager(b, steps, out_pars, n_rows, ft)
+    _stage_long_firs(cx)
+    if not cx.stages:
+        return cx.steps, cx.stages
+    _stage_short_traps(cx)
+    _stage_current_branch(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and getattr(v, "ext_key", None) is not None and getattr(v, "aux_io", None) is None}
-    steps = [x for x in steps if not any(r in "WS" and id(a) in staged for a, r in zip(x[1], _roles(x[0])))]
-    steps = _live_steps(b, steps, out_pars)
-
-    # --- per-event values read straight off rows in HBM: min_max, numpy.amax and a sample at a constant integral time of an input or of a
-    # stage's waveform.  In the program they cost a LOAD of the whole row into LDS and a pass over it, at the occupancy the longest
-    # waveform leaves (one wavefront per SIMD for 8192 samples); dsp_reduce.hip streams the row through registers once.
-    def reducible(st):
-        if st[0] in ("min_max", "amax"):
-            return True
-        if st[0] == "fixed_time_pickoff":
-            t = st[1][1]
-            return isinstance(t, (int, float, np.integer, np.floating)) and not isinstance(t, (bool, Quantity)) and float(t) == int(float(t))
-        if st[0] == "time_point_thresh":  # a walk from a constant sample (from an extreme of the same rows: what the t0 chain above moves)
-            _w, thr, start, walk, _o = st[1]
-            number = lambda x: isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, Quantity))  # noqa: E731
-            return (number(thr) or plain_scalar(thr)) and number(start) and float(start) == int(float(start)) and number(walk) and float(walk) in (0.0, 1.0)
-        return False
-
+    cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
     if ft == np.dtype(np.float32) and os.environ.get("DSPEED_HIP_NO_ROW_REDUCTIONS") != "1":
-        for v in [x for x in list(b.vars.values()) if row_input(x)]:
-            if np.dtype(v.dtype) not in (np.dtype(np.float32), np.dtype(np.int16), np.dtype(np.uint16)):
-                continue
-            group = [g for g in rows_steps(v) if reducible(g) and g[1][0] is v]
-            by_fn = [g[0] for g in group]
-            if not group or by_fn.count("min_max") > 1 or by_fn.count("amax") > 1 or by_fn.count("fixed_time_pickoff") > 4 or by_fn.count("time_point_thresh") > 2:
-                continue
-            rest = [x for x in steps if not any(x is g for g in group)]
-            if any(base_of(a) is v for x in rest for a, r in zip(x[1], _roles(x[0])) if r not in "WS"):
-                continue  # (the program loads these rows for something else as well: there the reduction is one more pass over LDS, no row traffic)
-            if not any(r in "wW" for x in rest for r in _roles(x[0])):
-                continue  # (the program would be left without a waveform: nothing gained by a launch of its own)
-            outs = [o for g in group for o, r in zip(g[1], _roles(g[0])) if r in "WS"]
-            build(group, outs, f"per-event values of {v.name} off its rows")
-            for o in outs:
-                o.kind = "scalar"
-            steps = rest
-
-    return steps, stages
+        _stage_row_reductions(cx)
+    return cx.steps, cx.stages
 
 
 def _column_dtype(dt):
     """type of the column an integer value travels in (the 8-bit integer types have no column type of their own: 16 bits hold them)"""
     dt = np.dtype(dt)
     return {np.dtype(np.int8): np.dtype(np.int16), np.dtype(np.uint8): np.dtype(np.uint16)}.get(dt, dt)
+
+
+def _int_dtype_of(x):
+    """the integer (or bool) type of a per-event column or of an expression between such values; None: not one"""
+    dt = getattr(x, "dtype", None)
+    if (isinstance(x, SExpr) and x.op == "func") or (isinstance(x, Var) and x.kind == "scalar"):
+        return np.dtype(dt) if dt is not None and np.dtype(dt).kind in "iub" else None
+    return None
+
+
+def _is_table_column(x) -> bool:  # a column of the input table: in HBM before any program runs
+    return isinstance(x, Var) and x.kind == "scalar" and x.is_input and x.source is not None and x.sreg is None and getattr(x, "ext_key", None) is None
+
+
+def _expressions(b: _Builder, steps, out_pars):
+    """every expression between per-event values that the steps or the outputs read, operands first"""
+    nodes, seen = [], set()
+
+    def visit(x):
+        if isinstance(x, SExpr) and id(x) not in seen:
+            seen.add(id(x))
+            for y in x.args:
+                visit(y)
+            nodes.append(x)
+
+    for _fn, args, _key in steps:
+        for a in args:
+            visit(a)
+    for o in out_pars:
+        visit(b.vars.get(o))
+    return nodes
 
 
 def _int_island(b: _Builder, steps, out_pars, ft):
@@ -657,43 +707,18 @@ def _int_island(b: _Builder, steps, out_pars, ft):
     table, constants or such arithmetic itself: a 64-bit loop on a value a processor computes is refused by name (a 32-bit one then stays
     where it was: the float operation, exact below 2^24).  Returns the stage's description (None: nothing to do) and {output: dtype} of the
     recipe outputs it writes itself."""
-    nodes, seen = [], set()
-
-    def visit(x):
-        if isinstance(x, SExpr) and id(x) not in seen:
-            seen.add(id(x))
-            for y in x.args:
-                visit(y)
-            nodes.append(x)  # (operands first)
-
-    for _fn, args, _key in steps:
-        for a in args:
-            visit(a)
-    for o in out_pars:
-        visit(b.vars.get(o))
-
-    def int_dt(x):
-        dt = getattr(x, "dtype", None)
-        if isinstance(x, SExpr):
-            return np.dtype(dt) if x.op == "func" and dt is not None and np.dtype(dt).kind in "iub" else None
-        if isinstance(x, Var) and x.kind == "scalar":
-            return np.dtype(dt) if dt is not None and np.dtype(dt).kind in "iub" else None
-        return None
-
-    def is_leaf(x):  # a column of the input table: in HBM before any program runs
-        return isinstance(x, Var) and x.kind == "scalar" and x.is_input and x.source is not None and x.sreg is None and getattr(x, "ext_key", None) is None
-
+    nodes = _expressions(b, steps, out_pars)
     wide = lambda dt: dt is not None and dt.itemsize == 8 and dt.kind in "iu"  # noqa: E731
     eligible = {}
 
     def ok(x):  # computable ahead of the programs, in integers
-        if isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, Quantity):
+        if _is_number(x) or isinstance(x, bool):
             return True
-        if is_leaf(x):
-            return int_dt(x) is not None
+        if _is_table_column(x):
+            return _int_dtype_of(x) is not None
         if isinstance(x, SExpr):
             if id(x) not in eligible:
-                eligible[id(x)] = x.op == "func" and int_dt(x) is not None and all(ok(y) for y in x.args[1:])
+                eligible[id(x)] = x.op == "func" and _int_dtype_of(x) is not None and all(ok(y) for y in x.args[1:])
             return eligible[id(x)]
         return False
 
@@ -702,10 +727,10 @@ def _int_island(b: _Builder, steps, out_pars, ft):
         if n.op != "func":
             continue
         opn = [x for x in n.args[1:] if isinstance(x, (Var, SExpr))]
-        is_wide = wide(int_dt(n)) or any(wide(int_dt(x)) for x in opn)
-        narrow32 = ((int(n.args[0]) >> 8) & 0xff) == 32 and ft != np.dtype(np.float64) and int_dt(n) is not None
+        is_wide = wide(_int_dtype_of(n)) or any(wide(_int_dtype_of(x)) for x in opn)
+        narrow32 = ((int(n.args[0]) >> 8) & 0xff) == 32 and ft != np.dtype(np.float64) and _int_dtype_of(n) is not None
         if is_wide:
-            if int_dt(n) is None or not ok(n):
+            if _int_dtype_of(n) is None or not ok(n):
                 raise NotImplementedError(f"'{n.name}': 64-bit integers reach the device as columns of the input table and arithmetic between them; "
                                           "here they meet a value a processor computes, or leave as a float (astype of a 64-bit integer)")
             need.append(n)
@@ -760,7 +785,7 @@ def _int_island(b: _Builder, steps, out_pars, ft):
         sp = [opnd(x) for x in n.args[1:]]
         t.add_op(_lib.OP_SCALAR_FUNC, dst=n.sreg, ip=(int(n.args[0]),), sp=tuple(sp + [Scalar.const(0.0)] * (3 - len(sp))))
     for k, n in enumerate(members):
-        nat = int_dt(n)
+        nat = _int_dtype_of(n)
         is_u64 = int(nat == np.dtype(np.uint64))
         for o in direct.get(id(n), ()):
             t.add_op(_lib.OP_STORE_SCALAR, io=t.add_io(f"out:{o}", _lib.IO_SCALAR_OUT, _column_dtype(nat)), ip=(n.sreg, is_u64))
@@ -772,164 +797,105 @@ def _int_island(b: _Builder, steps, out_pars, ft):
             out_dtypes[key] = _column_dtype(nat)
             n.ext_key = key
     for n in members:  # from here on a member is a column in HBM to everybody else
-        n.ext_dtype = _column_dtype(int_dt(n))
+        n.ext_dtype = _column_dtype(_int_dtype_of(n))
         n.op, n.args, n.sreg = "ext", (), None
     if len(t.ops) > _lib.MAX_OPS or len(t.io) > _lib.MAX_IO or t.n_sregs > _lib.MAX_SREGS:
         raise NotImplementedError("the recipe's integer arithmetic is too large for one device program (ops/bindings/registers limit)")
-    stage = {"what": "integer arithmetic between per-event columns (64-bit registers)", "program": t, "consts": {}, "in_vars": in_vars, "alias": {},
-             "outs": outs, "out_dtypes": out_dtypes, "compute": np.dtype(np.int64), "chain": None, "bufs": {}}
+    stage = _stage_record("integer arithmetic between per-event columns (64-bit registers)", t, {}, in_vars, {}, outs,
+                          out_dtypes=out_dtypes, compute=np.dtype(np.int64))
     return stage, direct_out
 
 
-def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
-    """``stage_mode``: the program of a stage that runs ahead of the main program (_extract_stages): fits and other stages are not taken
-    out of it again; their results arrive as bindings (``Var.ext_key``)."""
-    p = Program()
-    ft = b.stage_ft if stage_mode else _loop_dtype(b)
-    in_bind, out_bind, consts = {}, {}, {}
-    ext_alias = {}  # binding name -> name of the buffer a fit / stage ahead of the program filled (a slice of it has a name of its own)
-    vector_lens = {}
-    steps = b.steps
-    island, island_out = (None, {}) if stage_mode else _int_island(b, steps, out_pars, ft)
-    # --- linear_slope_fit on the rows of the batch (dsp_linear_slope_fit_rows: one waveform per lane) instead of inside the program,
-    # where its sequential float32 recurrences cost a third of a LEGEND recipe: a fit whose waveform is an input, the input minus a
-    # per-event input / constant (bl_subtract or numpy.subtract), or the pole_zero of that (constant tau), read whole or through a
-    # constant slice.  The kernel runs ahead of the chain on the same stream; the chain reads its results as per-event inputs.
-    aux = []  # one launch per (input waveform, subtraction, pole-zero) pipeline
-    if not stage_mode and os.environ.get("DSPEED_HIP_FIT_IN_CHAIN", "0") != "1":
-        producer = {}
-        for fn, args, _k in steps:
-            for a, r in zip(args, _roles(fn)):
-                if r == "W" and isinstance(a, Var):
-                    producer[a.name] = (fn, args)
+def _extract_fits(b: _Builder, steps, out_pars, p: Program, ft):
+    """linear_slope_fit on the rows of the batch (dsp_linear_slope_fit_rows: one waveform per lane) instead of inside the program,
+    where its sequential float32 recurrences cost a third of a LEGEND recipe: a fit whose waveform is an input, the input minus a
+    per-event input / constant (bl_subtract or numpy.subtract), or the pole_zero of that (constant tau), read whole or through a
+    constant slice.  The kernel runs ahead of the chain on the same stream; the chain reads its results as per-event inputs.
+    Returns (one group per (input waveform, subtraction, pole-zero) pipeline = launch, the steps that remain)."""
+    producer = {}
+    for fn, args, _k in steps:
+        for a, r in zip(args, _roles(fn)):
+            if r == "W" and isinstance(a, Var):
+                producer[a.name] = (fn, args)
 
-        def plain_scalar(x):  # a constant or a per-event input column (known before the chain runs)
-            if isinstance(x, Var):
-                return x.kind == "scalar" and x.is_input and x.sreg is None
-            return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, Quantity))
+    def plain_scalar(x):  # a constant or a per-event input column (known before the chain runs)
+        if isinstance(x, Var):
+            return x.kind == "scalar" and x.is_input and x.sreg is None
+        return _is_number(x)
 
-        def pipeline_of(v):
-            """(input wf Var, first sample, length, sub operand, sub mode, tau) of waveform v, or None"""
-            tau = None
-            if not v.is_input and v.name in producer and producer[v.name][0] == "pole_zero":
-                _fn, a = producer[v.name]
-                if not isinstance(a[0], Var) or isinstance(a[1], (Var, SExpr, Quantity, tuple)):
-                    return None
-                tau, v = float(a[1]), a[0]
-            sub, mode = None, 0
-            src = v
-            if not v.is_input:
-                if v.name not in producer or producer[v.name][0] not in ("bl_subtract", "numpy_subtract"):
-                    return None
-                fn2, a = producer[v.name]
-                if not plain_scalar(a[1]):
-                    return None
-                sub, mode, src = a[1], (1 if fn2 == "bl_subtract" else 2), a[0]
-            lo, n = 0, None
-            if isinstance(src, tuple) and src[0] == "slice":
-                src, lo, n = src[1], src[2], src[3] - src[2]
-            if not (isinstance(src, Var) and src.is_input and src.kind == "wf" and src.offset == 0):
+    def pipeline_of(v):
+        """(input wf Var, first sample, length, sub operand, sub mode, tau) of waveform v, or None"""
+        tau = None
+        if not v.is_input and v.name in producer and producer[v.name][0] == "pole_zero":
+            _fn, a = producer[v.name]
+            if not isinstance(a[0], Var) or isinstance(a[1], (Var, SExpr, Quantity, tuple)):
                 return None
-            return src, lo, (src.length if n is None else n), sub, mode, tau
+            tau, v = float(a[1]), a[0]
+        sub, mode = None, 0
+        src = v
+        if not v.is_input:
+            if v.name not in producer or producer[v.name][0] not in ("bl_subtract", "numpy_subtract"):
+                return None
+            fn2, a = producer[v.name]
+            if not plain_scalar(a[1]):
+                return None
+            sub, mode, src = a[1], (1 if fn2 == "bl_subtract" else 2), a[0]
+        lo, n = 0, None
+        if isinstance(src, tuple) and src[0] == "slice":
+            src, lo, n = src[1], src[2], src[3] - src[2]
+        if not (isinstance(src, Var) and src.is_input and src.kind == "wf" and src.offset == 0):
+            return None
+        return src, lo, (src.length if n is None else n), sub, mode, tau
 
-        kept = []
-        for fn, args, key in steps:
-            done = False
-            if fn == "linear_slope_fit" and all(isinstance(a, Var) for a in args[1:5]):
-                a0, first, count = args[0], 0, None
-                if isinstance(a0, tuple) and a0[0] == "slice":
-                    a0, first, count = a0[1], a0[2], a0[3] - a0[2]
-                pl = pipeline_of(a0) if isinstance(a0, Var) else None
-                if pl is not None:
-                    src, lo, n, sub, mode, tau = pl
-                    count = n - first if count is None else count
-                    if 0 <= first and first + count <= n and count >= 1:
-                        gkey = (src.name, lo, n, id(sub) if isinstance(sub, Var) else ("c", sub), mode)
-                        grp = next((g for g in aux if g["key"] == gkey and len(g["fits"]) < _lib.FIT_MAX
-                                    and (g["tau"] == tau or tau is None or g["tau"] is None)), None)
-                        if grp is None:
-                            grp = {"key": gkey, "src": src, "lo": lo, "len": n, "sub": sub, "mode": mode, "tau": tau, "fits": [], "outs": []}
-                            aux.append(grp)
-                        if tau is not None:
-                            grp["tau"] = tau
-                        grp["fits"].append((1 if tau is not None else 0, first, count))
-                        grp["outs"].append(list(args[1:5]))
-                        done = True
-            if not done:
-                kept.append((fn, args, key))
-        steps = kept
-        if aux:  # what only fed those fits is not computed any more
-            def leaves(a, acc):
-                if isinstance(a, SExpr):
-                    for x in a.args:
-                        leaves(x, acc)
-                elif isinstance(a, Var):
-                    acc.append(a)
-                elif isinstance(a, tuple) and a and a[0] == "slice":
-                    acc.append(a[1])
-                return acc
+    aux, kept = [], []
+    for st in steps:
+        fn, args, _key = st
+        kept.append(st)
+        if fn != "linear_slope_fit" or not all(isinstance(a, Var) for a in args[1:5]):
+            continue
+        a0, first, count = args[0], 0, None
+        if isinstance(a0, tuple) and a0[0] == "slice":
+            a0, first, count = a0[1], a0[2], a0[3] - a0[2]
+        pl = pipeline_of(a0) if isinstance(a0, Var) else None
+        if pl is None:
+            continue
+        src, lo, n, sub, mode, tau = pl
+        count = n - first if count is None else count
+        if not (0 <= first and first + count <= n and count >= 1):
+            continue
+        gkey = (src.name, lo, n, id(sub) if isinstance(sub, Var) else ("c", sub), mode)
+        grp = next((g for g in aux if g["key"] == gkey and len(g["fits"]) < _lib.FIT_MAX
+                    and (g["tau"] == tau or tau is None or g["tau"] is None)), None)
+        if grp is None:
+            grp = {"key": gkey, "src": src, "lo": lo, "len": n, "sub": sub, "mode": mode, "tau": tau, "fits": [], "outs": []}
+            aux.append(grp)
+        if tau is not None:
+            grp["tau"] = tau
+        grp["fits"].append((1 if tau is not None else 0, first, count))
+        grp["outs"].append(list(args[1:5]))
+        kept.pop()  # (the fit leaves the program)
+    if aux:  # what only fed those fits is not computed any more
+        kept = _live_steps(b, kept, out_pars)
+    for gi, g in enumerate(aux):  # the chain reads the results as per-event input columns
+        for k, outs in enumerate(g["outs"]):
+            for q, o in enumerate(outs):
+                o.kind = "scalar"
+                o.aux_io = p.add_io(f"aux:{gi}:{4 * k + q}", _lib.IO_SCALAR_IN, ft)
+                o.ext_key = f"aux:{gi}:{4 * k + q}"
+    return aux, kept
 
-            needed = {id(v) for o in out_pars for v in leaves(b.vars.get(o), [])}
-            live = []
-            for fn, args, key in reversed(steps):
-                roles = _roles(fn)
-                mine = [v for a, r in zip(args, roles) if r in "WS" for v in leaves(a, [])]
-                if any(id(v) in needed for v in mine):
-                    live.append((fn, args, key))
-                    for a, r in zip(args, roles):
-                        if r not in "WS":
-                            needed.update(id(v) for v in leaves(a, []))
-            steps = live[::-1]
-        for gi, g in enumerate(aux):  # the chain reads the results as per-event input columns
-            for k, outs in enumerate(g["outs"]):
-                for q, o in enumerate(outs):
-                    o.kind = "scalar"
-                    o.aux_io = p.add_io(f"aux:{gi}:{4 * k + q}", _lib.IO_SCALAR_IN, ft)
-                    o.ext_key = f"aux:{gi}:{4 * k + q}"
 
-    # --- long FIRs on the matrix cores, ahead of the program (DESIGN.md section 4a): their results are bindings of the program
-    stages = []
-    if not stage_mode and ft == np.dtype(np.float32) and os.environ.get("DSPEED_HIP_NO_STAGES", "0") != "1":
-        steps, stages = _extract_stages(b, steps, out_pars, n_rows, ft)
-
-    if island is not None:
-        stages = [island] + stages
-    steps = b.steps = _schedule(steps)
-    out_names = set(out_pars)  # names of the variables that are outputs (a variable may have another name than the output: alias, named slice)
-    for o in out_pars:
-        ov = b.vars.get(o)
-        ov = ov[1] if _is_wf(ov) and isinstance(ov, tuple) else ov
-        if isinstance(ov, Var):
-            out_names.add(ov.name)
-
-    # --- uses: which step reads which variable last (slot reuse, in-place decisions, fusions)
-    def wf_of(a):
-        if isinstance(a, Var):
-            return a
-        if isinstance(a, tuple) and a[0] == "slice":
-            return a[1]
-        return None
-
-    # --- slice push-down: an element-wise result (bl_subtract) that is read ONLY through one constant slice [lo:hi] -- the
-    # long-FIR recipes do that, icpc-dsp-config.json:160-239 -- is computed on that slice alone: a 6092-sample slot instead of
-    # an 8192-sample one plus a copy.  Same values: the op is per sample.
-    whole_nan_rule = {}  # sliced-input variable -> (samples before, samples after) the slice that a LOAD screens for NaN
-
-    def slices_of(v):
-        found, plain = set(), False
-        for _fn, a2, _k in steps:
-            for x in a2:
-                if isinstance(x, tuple) and x[0] == "slice" and x[1] is v:
-                    found.add((x[2], x[3]))
-                elif x is v:
-                    plain = True
-        return found, plain
-
+def _push_down_slices(steps, out_names):
+    """Slice push-down: an element-wise result (bl_subtract) that is read ONLY through one constant slice [lo:hi] -- the
+    long-FIR recipes do that, icpc-dsp-config.json:160-239 -- is computed on that slice alone: a 6092-sample slot instead of
+    an 8192-sample one plus a copy.  Same values: the op is per sample.  ``steps`` is changed in place; returns
+    {sliced-input variable: (samples before, samples after) the slice that a LOAD screens for NaN}."""
+    whole_nan_rule = {}
     for si, (fn, args, key) in enumerate(steps):
         if fn != "bl_subtract" or not isinstance(args[0], Var) or not isinstance(args[-1], Var) or args[-1].name in out_names:
             continue
         src_v, dst_v = args[0], args[-1]
-        found, plain = slices_of(dst_v)
+        found = {(x[2], x[3]) for _fn, a2, _k in steps for x in a2 if isinstance(x, tuple) and x[0] == "slice" and x[1] is dst_v}
         uses_of_dst = sum(1 for _fn, a2, _k in steps for x in a2 if x is dst_v)  # the producing step itself counts once
         if len(found) != 1 or uses_of_dst != 1 or not src_v.is_input or src_v.kind != "wf":
             continue
@@ -948,71 +914,113 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
         for sj, (fn2, a2, k2) in enumerate(steps):
             if sj != si:
                 steps[sj] = (fn2, [dst_v if (isinstance(x, tuple) and x[0] == "slice" and x[1] is dst_v) else x for x in a2], k2)
+    return whole_nan_rule
 
+
+def _last_uses(b: _Builder, steps, out_pars):
+    """which step reads which variable last (slot reuse, in-place decisions, fusions); an output lives beyond the last step"""
     last_use = {}
     for si, (fn, args, _) in enumerate(steps):
-        roles = _roles(fn)
-        for a, r in zip(args, roles):
-            v = wf_of(a)
+        for a, r in zip(args, _roles(fn)):
+            v = _base_of(a)
             if v is not None and r in "wts":
                 last_use[v.name] = si
     for o in out_pars:  # (a variable may be known by another name than the output's: an alias, a named slice)
         last_use[o] = len(steps) + 1
-        v = wf_of(b.vars.get(o)) if isinstance(b.vars.get(o), (Var, tuple)) else None
+        v = _base_of(b.vars.get(o)) if isinstance(b.vars.get(o), (Var, tuple)) else None
         if v is not None:
             last_use[v.name] = len(steps) + 1
+    return last_use
 
-    free_slots, slot_len = [], []
 
-    def new_slot(length):
+_TRAP_OPS = {"trap_filter": _lib.OP_TRAP_FILTER, "trap_norm": _lib.OP_TRAP_NORM, "asym_trap_filter": _lib.OP_ASYM_TRAP}
+_WINDOW_OPS = {"windower": _lib.OP_WINDOWER, "avg_current": _lib.OP_AVG_CURRENT, "upsampler": _lib.OP_UPSAMPLER}
+
+
+class _Emitter:
+    """The steps of a program, in their scheduled order, into ops: waveforms get slots, per-event values registers, inputs bindings.  The order
+    in which these are handed out is visible in the program; each processor family is a method (``_EMIT``)."""
+
+    def __init__(self, b: _Builder, p: Program, ft, steps, out_names, whole_nan_rule, last_use):
+        self.b, self.p, self.ft, self.steps, self.out_names = b, p, ft, steps, out_names
+        self.whole_nan_rule, self.last_use = whole_nan_rule, last_use
+        self.in_bind, self.consts = {}, {}
+        self.ext_alias = {}  # binding name -> name of the buffer a fit / stage ahead of the program filled (a slice of it has a name of its own)
+        self.free_slots, self.slot_len = [], []
+        self.skip = set()  # steps a fusion has emitted together with an earlier one
+        self.pending_reduce = {}  # trapezoid output name -> what its fused min_max / time_point_thresh op needs
+
+    def run(self):
+        for si, (fn, args, key) in enumerate(self.steps):
+            if si in self.skip or fn == "alias":
+                continue
+            what = f"{fn} ({key})"
+            if fn in ("min_max", "time_point_thresh", "amax", "fixed_time_pickoff") and isinstance(args[0], Var) and args[0].name in self.pending_reduce:
+                self.fused_reduction(si, fn, args, what)
+            elif fn in _READ_OFF:
+                self.read_off(si, fn, args, what)
+            elif fn.startswith("ew:"):
+                self.elementwise(si, fn, args, what)
+            elif fn in _EMIT:
+                _EMIT[fn](self, si, fn, args, what)
+            else:
+                raise NotImplementedError(f"processor '{fn}' is not implemented on the device path")
+
+    # --- slots, registers, operands
+    def new_slot(self, length):
         # one slot per waveform variable: dsp_chain_create packs slots with disjoint lifetimes into the same LDS, whatever their
         # lengths.  Only a recipe with more variables than slot ids goes back to an id whose variable is dead.
-        if len(slot_len) >= _lib.MAX_SLOTS:
-            for s in free_slots:
-                if slot_len[s] == length:
-                    free_slots.remove(s)
+        if len(self.slot_len) >= _lib.MAX_SLOTS:
+            for s in self.free_slots:
+                if self.slot_len[s] == length:
+                    self.free_slots.remove(s)
                     return s
-        slot_len.append(int(length))
-        return len(slot_len) - 1
+        self.slot_len.append(int(length))
+        return len(self.slot_len) - 1
 
-    def release(v, si):
-        if v.slot is not None and last_use.get(v.name, -1) <= si and v.kind == "wf":
-            if v.slot not in free_slots:
-                free_slots.append(v.slot)
+    def free(self, slot):
+        if slot not in self.free_slots:
+            self.free_slots.append(slot)
 
-    def period_of(args):
+    def dead_after(self, v, si) -> bool:
+        return self.last_use.get(v.name, -1) <= si
+
+    def release(self, v, si):
+        if v.slot is not None and self.dead_after(v, si) and v.kind == "wf":
+            self.free(v.slot)
+
+    def period_of(self, args):
         for a in args:
-            v = wf_of(a)
+            v = _base_of(a)
             if v is not None and v.period is not None:
                 return v.period
-        return b.default_period
+        return self.b.default_period
 
-    def ensure_loaded(a, si):
+    def ensure_loaded(self, a, si):
         """Waveform operand -> slot.  Chain inputs are loaded on first use (a constant slice of an input is free)."""
+        b, p = self.b, self.p
         if isinstance(a, tuple) and a[0] == "slice":
             _, base, lo, hi = a
+            key = f"{base.name}[{lo}:{hi}]"
+            v = b.vars.get(key)
             if base.is_input:
-                key = f"{base.name}[{lo}:{hi}]"
-                v = b.vars.get(key)
                 if v is None:
                     v = Var(key, "wf", hi - lo, base.dtype, source=base.source, offset=lo, grid=_grid_of(a), is_coord=False)
                     v.is_input = True
                     if getattr(base, "ext_key", None) is not None:  # (a waveform a stage wrote: same buffer, first sample lo)
                         v.ext_key, v.ext_len = base.ext_key, getattr(base, "ext_len", base.length)
                     b.vars[key] = v
-                    last_use[key] = last_use.get(base.name, si)
-                return ensure_loaded(v, si)
-            key = f"{base.name}[{lo}:{hi}]"
-            v = b.vars.get(key)
+                    self.last_use[key] = self.last_use.get(base.name, si)
+                return self.ensure_loaded(v, si)
             if v is not None and v.slot is not None:
                 return v  # the same slice was materialised for an earlier processor and is still alive
-            src = ensure_loaded(base, si)
+            src = self.ensure_loaded(base, si)
             v = Var(key, "wf", hi - lo, np.float32, grid=_grid_of(a), is_coord=False)
-            v.slot = new_slot(v.length)
+            v.slot = self.new_slot(v.length)
             p.add_op(_lib.OP_COPY, dst=v.slot, src=src.slot, ip=(lo,))
             b.vars[key] = v
-            last_use[key] = max((sj for sj, (_, a2, _k) in enumerate(steps)
-                                 for x in a2 if isinstance(x, tuple) and x[0] == "slice" and x[1] is base and x[2] == lo and x[3] == hi), default=si)
+            self.last_use[key] = max((sj for sj, (_, a2, _k) in enumerate(self.steps)
+                                      for x in a2 if isinstance(x, tuple) and x[0] == "slice" and x[1] is base and x[2] == lo and x[3] == hi), default=si)
             return v
         v = a
         if v.kind != "wf":
@@ -1022,58 +1030,71 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
                 raise ProcessingChainError(f"waveform '{v.name}' is used before it is computed")
             if getattr(v, "ext_key", None) is not None:  # written by a stage ahead of the program: float32 rows of the variable's length
                 io = p.add_io(f"in:{v.name}", _lib.IO_WF_IN, np.float32, v.length, v.offset, getattr(v, "ext_len", v.length))
-                ext_alias[f"in:{v.name}"] = v.ext_key
+                self.ext_alias[f"in:{v.name}"] = v.ext_key
             else:
                 col = _column(b.tb_in, v.source)
-                full_len = col.shape[1]
-                io = p.add_io(f"in:{v.name}", _lib.IO_WF_IN, col.dtype, v.length, v.offset, full_len)
-                in_bind[f"in:{v.name}"] = v
-            v.slot = new_slot(v.length)
-            screens = whole_nan_rule.get(v.name, ())
+                io = p.add_io(f"in:{v.name}", _lib.IO_WF_IN, col.dtype, v.length, v.offset, col.shape[1])
+                self.in_bind[f"in:{v.name}"] = v
+            v.slot = self.new_slot(v.length)
+            screens = self.whole_nan_rule.get(v.name, ())
             if getattr(v, "nan_uniform", False):  # rows a stage wrote with pole_zero's rule: all NaN or free of NaN (DSP_OP_LOAD ip[2])
                 screens = (*(screens or (0, 0)), 1)
             p.add_op(_lib.OP_LOAD, dst=v.slot, io=io, ip=screens)
         return v
 
-    def scalar_operand(a, args, integer=False, what=""):
+    def expression(self, a: SExpr, args, what):
+        """the register of an expression between per-event values; its first reader emits the op (its operands were computed by earlier
+        processors)"""
+        p, ft = self.p, self.ft
+        if a.sreg is not None:
+            return Scalar.reg(a.sreg)
+
+        def opnd(x):
+            return self.scalar_operand(x, args, what=what) if isinstance(x, (Var, SExpr)) else Scalar.const(float(x))
+
+        r = p.add_sregs(1)
+        if a.op in ("affine", "div"):
+            p.add_op(_lib.OP_SCALAR_AFFINE if a.op == "affine" else _lib.OP_SCALAR_DIV, dst=r, sp=tuple(opnd(x) for x in a.args))
+        elif a.op == "func":
+            code, *xs = a.args
+            if code == _lib.FN_COPY and getattr(a, "want_dtype", None) not in (None, ft):
+                raise NotImplementedError(f"{what}: astype to {a.want_dtype} in a chain whose loop type is {ft}")
+            if (code >> 8) & 0xff == 32 and ft != np.dtype(np.float64):
+                # a 32-bit integer loop between per-event values of a float32 chain (len(v) // 2, eventnumber + 1): the registers are
+                # float32, so the operation is the float one -- the same integer as long as operands and result stay below 2**24
+                float_fn = {_lib.FN_IADD: _lib.FN_ADD, _lib.FN_ISUB: _lib.FN_SUB, _lib.FN_IMUL: _lib.FN_MUL, _lib.FN_IFLOORDIV: _lib.FN_FLOORDIV}
+                if code & 0xff not in float_fn:
+                    raise NotImplementedError(f"{what}: astype to a 32-bit integer in a chain whose loop type is {ft}")
+                code = float_fn[code & 0xff]
+            sp = [opnd(x) for x in xs] + [Scalar.const(0.0)] * (3 - len(xs))
+            p.add_op(_lib.OP_SCALAR_FUNC, dst=r, ip=(code,), sp=tuple(sp))
+        elif a.op == "convert":
+            x, off_in, off_out, ratio = a.args
+            p.add_op(_lib.OP_SCALAR_CONVERT, dst=r, ip=(a.mode,), sp=(opnd(x), opnd(off_in), opnd(off_out), Scalar.const(ratio)))
+        else:
+            raise ProcessingChainError(f"{what}: cannot evaluate '{a.name}'")
+        a.sreg = r
+        return Scalar.reg(a.sreg)
+
+    def column(self, a, name, dtype, buffer=None, var=None):
+        """a per-event value that is in HBM before the program runs, bound on first use: a column of the input table (``var``), or one a fit,
+        a stage or the integer program ahead of this one wrote (``buffer``)"""
+        if a.io is None:
+            a.io = self.p.add_io(name, _lib.IO_SCALAR_IN, dtype)
+            if var is not None:
+                self.in_bind[name] = var
+            else:
+                self.ext_alias[name] = buffer
+        return Scalar.input(a.io)
+
+    def scalar_operand(self, a, args, integer=False, what=""):
         """Scalar argument -> Scalar (const / input column / register)."""
         if isinstance(a, SExpr) and a.op == "ext":  # a column the integer program ahead of this one wrote (_int_island)
             if getattr(a, "ext_key", None) is None:
                 raise ProcessingChainError(f"{what}: '{a.name}' is written by the integer program as an output only")
-            if a.io is None:
-                a.io = p.add_io(a.ext_key, _lib.IO_SCALAR_IN, a.ext_dtype)
-                ext_alias[a.ext_key] = a.ext_key
-            return Scalar.input(a.io)
+            return self.column(a, a.ext_key, a.ext_dtype, buffer=a.ext_key)
         if isinstance(a, SExpr):
-            if a.sreg is None:  # first reader: emit the op (its operands were computed by earlier processors)
-                def opnd(x):
-                    return scalar_operand(x, args, what=what) if isinstance(x, (Var, SExpr)) else Scalar.const(float(x))
-
-                r = p.add_sregs(1)
-                if a.op == "affine":
-                    p.add_op(_lib.OP_SCALAR_AFFINE, dst=r, sp=tuple(opnd(x) for x in a.args))
-                elif a.op == "div":
-                    p.add_op(_lib.OP_SCALAR_DIV, dst=r, sp=tuple(opnd(x) for x in a.args))
-                elif a.op == "func":
-                    code, *xs = a.args
-                    if code == _lib.FN_COPY and getattr(a, "want_dtype", None) not in (None, ft):
-                        raise NotImplementedError(f"{what}: astype to {a.want_dtype} in a chain whose loop type is {ft}")
-                    if (code >> 8) & 0xff == 32 and ft != np.dtype(np.float64):
-                        # a 32-bit integer loop between per-event values of a float32 chain (len(v) // 2, eventnumber + 1): the registers are
-                        # float32, so the operation is the float one -- the same integer as long as operands and result stay below 2**24
-                        float_fn = {_lib.FN_IADD: _lib.FN_ADD, _lib.FN_ISUB: _lib.FN_SUB, _lib.FN_IMUL: _lib.FN_MUL, _lib.FN_IFLOORDIV: _lib.FN_FLOORDIV}
-                        if code & 0xff not in float_fn:
-                            raise NotImplementedError(f"{what}: astype to a 32-bit integer in a chain whose loop type is {ft}")
-                        code = float_fn[code & 0xff]
-                    sp = [opnd(x) for x in xs] + [Scalar.const(0.0)] * (3 - len(xs))
-                    p.add_op(_lib.OP_SCALAR_FUNC, dst=r, ip=(code,), sp=tuple(sp))
-                elif a.op == "convert":
-                    x, off_in, off_out, ratio = a.args
-                    p.add_op(_lib.OP_SCALAR_CONVERT, dst=r, ip=(a.mode,), sp=(opnd(x), opnd(off_in), opnd(off_out), Scalar.const(ratio)))
-                else:
-                    raise ProcessingChainError(f"{what}: cannot evaluate '{a.name}'")
-                a.sreg = r
-            return Scalar.reg(a.sreg)
+            return self.expression(a, args, what)
         if isinstance(a, Var):
             if a.kind == "const":
                 a = a.const
@@ -1083,21 +1104,14 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
                 if getattr(a, "aux_io", None) is not None:  # a fit done ahead of the chain
                     return Scalar.input(a.aux_io)
                 if getattr(a, "ext_key", None) is not None:  # a fit or a stage ahead of this program
-                    if a.io is None:
-                        a.io = p.add_io(f"in:{a.name}", _lib.IO_SCALAR_IN, ft)
-                        ext_alias[f"in:{a.name}"] = a.ext_key
-                    return Scalar.input(a.io)
+                    return self.column(a, f"in:{a.name}", self.ft, buffer=a.ext_key)
                 if a.is_input:
-                    if a.io is None:
-                        col = _column(b.tb_in, a.source)
-                        a.io = p.add_io(f"in:{a.name}", _lib.IO_SCALAR_IN, col.dtype)
-                        in_bind[f"in:{a.name}"] = a
-                    return Scalar.input(a.io)
+                    return self.column(a, f"in:{a.name}", _column(self.b.tb_in, a.source).dtype, var=a)
                 raise ProcessingChainError(f"scalar '{a.name}' is used before it is computed")
             else:
                 raise ProcessingChainError(f"{what}: '{a.name}' is not a scalar")
         if isinstance(a, Quantity):  # (no grid on this processor: the reference refuses; the input's sampling period is used)
-            per = period_of(args)
+            per = self.period_of(args)
             if per is None:
                 raise ProcessingChainError(f"{what}: time quantity without a sampling period (wrap the input in WaveformInput)")
             a = float(a) / per
@@ -1107,6 +1121,7 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
             return int(a) if isinstance(a, (int, np.integer)) else int(np.rint(float(a)))
         return Scalar.const(float(a))
 
+    @staticmethod
     def char_of(a):
         if isinstance(a, tuple) and a[0] == "char":
             return ord(a[1][0])
@@ -1114,7 +1129,9 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
             return int(a)
         raise ProcessingChainError(f"expected a character argument, got {a!r}")
 
-    def out_wf(a, length, src_var=None):
+    @staticmethod
+    def out_wf(a, length, fn=None):
+        """the waveform a processor writes, ``length`` samples if nothing declared it (None: it must be declared)"""
         if not isinstance(a, Var):
             raise ProcessingChainError("output argument must be a variable name")
         if a.kind is None:
@@ -1124,295 +1141,270 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
         if a.length is None:
             a.length = length
         a.dtype = np.dtype(np.float32)
+        if a.length is None:
+            raise ProcessingChainError(f"{fn}: declare the output as name(length, 'f')")
         return a
 
-    def out_scalar(a):
+    def out_scalar(self, a):
         if not isinstance(a, Var):
             raise ProcessingChainError("output argument must be a variable name")
         if a.kind is None:
             a.kind = "scalar"
         if a.sreg is None:
-            a.sreg = p.add_sregs(1)
+            a.sreg = self.p.add_sregs(1)
         return a
 
-    trap_ops = {"trap_filter": _lib.OP_TRAP_FILTER, "trap_norm": _lib.OP_TRAP_NORM, "asym_trap_filter": _lib.OP_ASYM_TRAP}
-    skip = set()
-    pending_reduce = {}  # trapezoid output name -> what its fused min_max / time_point_thresh op needs
-    for si, (fn, args, key) in enumerate(steps):
-        if si in skip:
-            continue
-        what = f"{fn} ({key})"
-        if fn == "alias":
-            continue
-        if fn in ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero"):
-            src = ensure_loaded(args[0], si)
-            dst = out_wf(args[-1], src.length, src)
-            inplace = last_use.get(src.name, -1) <= si
-            dst.slot = src.slot if inplace else new_slot(src.length)
-            if fn == "bl_subtract":
-                p.add_op(_lib.OP_BL_SUBTRACT, dst=dst.slot, src=src.slot, sp=(scalar_operand(args[1], args, what=what),))
-            elif fn in ("numpy_subtract", "numpy_add"):
-                y = args[1]
-                if fn == "numpy_add":  # w + y = w - (-y), exactly
-                    y = SExpr("affine", (y, -1.0, -0.0), "(-...)", None, False, None) if isinstance(y, (Var, SExpr)) else -float(y)
-                p.add_op(_lib.OP_BL_SUBTRACT, dst=dst.slot, src=src.slot, ip=(1,), sp=(scalar_operand(y, args, what=what),))
-            elif fn == "min_max_norm":
-                p.add_op(_lib.OP_MIN_MAX_NORM, dst=dst.slot, src=src.slot, sp=(scalar_operand(args[1], args, what=what),
-                                                                                scalar_operand(args[2], args, what=what)))
-            elif fn == "pole_zero":
-                tau = scalar_operand(args[1], args, what=what)
-                p.add_op(_lib.OP_POLE_ZERO, dst=dst.slot, src=src.slot, sp=(tau,))
+    def out_four(self, outs, name):
+        """four registers in a row for the results of min_max / linear_slope_fit"""
+        first = self.p.add_sregs(4)
+        for k, a in enumerate(outs):
+            if not isinstance(a, Var):
+                raise ProcessingChainError(f"{name} outputs must be variable names")
+            a.kind, a.sreg = "scalar", first + k
+        return first
+
+    # --- the processor families
+    def read_off(self, si, fn, args, what):
+        """one per-event value read off a waveform: load the source, make the output's register, emit one op, release (``_READ_OFF``)"""
+        opcode, out, operands, operands_first = _READ_OFF[fn]
+        so = lambda a, **kw: self.scalar_operand(a, args, what=what, **kw)  # noqa: E731
+        src = self.ensure_loaded(args[0], si)
+        if operands_first:
+            ip, sp = operands(self, args, so)
+        o = self.out_scalar(args[out])
+        if not operands_first:
+            ip, sp = operands(self, args, so)
+        self.p.add_op(opcode, dst=o.sreg, src=src.slot, ip=ip, sp=sp)
+        self.release(src, si)
+
+    def in_place(self, si, fn, args, what):
+        """a result that may take its source's place: the subtractions, min_max_norm, the pole-zero corrections"""
+        p = self.p
+        src = self.ensure_loaded(args[0], si)
+        dst = self.out_wf(args[-1], src.length)
+        inplace = self.dead_after(src, si)
+        dst.slot = src.slot if inplace else self.new_slot(src.length)
+        if fn == "bl_subtract":
+            p.add_op(_lib.OP_BL_SUBTRACT, dst=dst.slot, src=src.slot, sp=(self.scalar_operand(args[1], args, what=what),))
+        elif fn in ("numpy_subtract", "numpy_add"):
+            y = args[1]
+            if fn == "numpy_add":  # w + y = w - (-y), exactly
+                y = SExpr("affine", (y, -1.0, -0.0), "(-...)", None, False, None) if isinstance(y, (Var, SExpr)) else -float(y)
+            p.add_op(_lib.OP_BL_SUBTRACT, dst=dst.slot, src=src.slot, ip=(1,), sp=(self.scalar_operand(y, args, what=what),))
+        else:
+            opcode = {"min_max_norm": _lib.OP_MIN_MAX_NORM, "pole_zero": _lib.OP_POLE_ZERO, "double_pole_zero": _lib.OP_DOUBLE_POLE_ZERO}[fn]
+            p.add_op(opcode, dst=dst.slot, src=src.slot, sp=tuple(self.scalar_operand(a, args, what=what) for a in args[1:-1]))
+        if not inplace:
+            self.release(src, si)
+
+    def elementwise(self, si, fn, args, what):
+        code, *opn, dst = args
+        if code == _lib.FN_COPY and getattr(dst, "want_dtype", None) not in (None, self.ft):
+            raise NotImplementedError(f"{what}: astype to {dst.want_dtype} in a chain whose loop type is {self.ft}")
+        if (code >> 8) & 0xff == 32 and self.ft != np.dtype(np.float64):
+            raise NotImplementedError(f"{what}: a 32-bit integer loop on waveforms in a chain whose loop type is {self.ft} (its values do not hold every "
+                                      "32-bit integer); make one operand a float (astype)")
+        slots, sps, srcs = [], [], []
+        for x, r in zip(opn, fn[3:]):
+            if r == "w":
+                v = self.ensure_loaded(x, si)
+                slots.append(v.slot)
+                sps.append(Scalar.const(0.0))
+                srcs.append(v)
             else:
-                sp = tuple(scalar_operand(a, args, what=what) for a in args[1:4])
-                p.add_op(_lib.OP_DOUBLE_POLE_ZERO, dst=dst.slot, src=src.slot, sp=sp)
-            if not inplace:
-                release(src, si)
-        elif fn.startswith("ew:"):
-            code, *opn, dst = args
-            if code == _lib.FN_COPY and getattr(dst, "want_dtype", None) not in (None, ft):
-                raise NotImplementedError(f"{what}: astype to {dst.want_dtype} in a chain whose loop type is {ft}")
-            if (code >> 8) & 0xff == 32 and ft != np.dtype(np.float64):
-                raise NotImplementedError(f"{what}: a 32-bit integer loop on waveforms in a chain whose loop type is {ft} (its values do not hold every "
-                                          "32-bit integer); make one operand a float (astype)")
-            slots, sps, srcs = [], [], []
-            for x, r in zip(opn, fn[3:]):
-                if r == "w":
-                    v = ensure_loaded(x, si)
-                    slots.append(v.slot)
-                    sps.append(Scalar.const(0.0))
-                    srcs.append(v)
-                else:
-                    slots.append(-1)
-                    sps.append(scalar_operand(x, args, what=what) if r == "s" else Scalar.const(0.0))
-            dead = next((v for v in srcs if last_use.get(v.name, -1) <= si), None)  # the result may take the place of an operand nobody reads again
-            dst.slot = dead.slot if dead is not None else new_slot(dst.length)
-            p.add_op(_lib.OP_ELEMENTWISE, dst=dst.slot, src=slots[0], ip=(code, slots[1], slots[2]), sp=tuple(sps))
-            for v in srcs:
-                if v is not dead and v.slot != dst.slot:
-                    release(v, si)
-        elif fn == "sample":
-            src = ensure_loaded(args[0], si)
-            o = out_scalar(args[2])
-            p.add_op(_lib.OP_PICKOFF, dst=o.sreg, src=src.slot, ip=(ord("n"), 1), sp=(Scalar.const(float(args[1])),))
-            release(src, si)
-        elif fn == "get":
-            src = ensure_loaded(args[0], si)
-            o = out_scalar(args[2])
-            p.add_op(_lib.OP_PICKOFF, dst=o.sreg, src=src.slot, ip=(ord("n"), 2), sp=(scalar_operand(args[1], args, what=what), Scalar.const(float("nan"))))
-            release(src, si)
-        elif fn == "slice":
-            src = ensure_loaded(args[0], si)
-            dst = args[3]
-            dst.slot = new_slot(dst.length)
-            p.add_op(_lib.OP_COPY, dst=dst.slot, src=src.slot, ip=(int(args[1]), int(args[2])))
-            release(src, si)
-        elif fn in trap_ops:
-            src = ensure_loaded(args[0], si)
-            ints = [scalar_operand(a, args, integer=True, what=what) for a in args[1:-1]]
-            ints += [0] * (3 - len(ints))
-            dst = out_wf(args[-1], src.length, src)
-            # fusion: the trapezoid's only consumer is the next fixed_time_pickoff and it is not an output
-            nxt = steps[si + 1] if si + 1 < len(steps) else None
-            if (nxt and nxt[0] == "fixed_time_pickoff" and wf_of(nxt[1][0]) is dst and last_use.get(dst.name) == si + 1
-                    and dst.name not in out_names and char_of(nxt[1][2]) != ord("s")):
-                t_in = scalar_operand(nxt[1][1], nxt[1], what=what)
-                o = out_scalar(nxt[1][3])
-                p.add_op(_lib.OP_TRAP_PICKOFF, dst=o.sreg, src=src.slot, io=char_of(nxt[1][2]), ip=(*ints, trap_ops[fn]), sp=(t_in,))
-                skip.add(si + 1)
-                release(src, si + 1)
-                continue
-            # fusion: the trapezoid only feeds one min_max and / or one time_point_thresh (the t0 chain of the LEGEND recipes:
-            # asym_trap_filter -> min_max -> time_point_thresh) and is not an output -> it is never stored.  The fused op is emitted
-            # where the last of the two stands, so their scalar operands (a threshold computed in between) are ready
-            users = [sj for sj, (f2, a2, _k) in enumerate(steps) if sj > si and sj not in skip and any(wf_of(x) is dst for x in a2)]
-            kinds = [steps[sj][0] for sj in users]
-            plain = all(steps[sj][1][0] is dst for sj in users)  # (not through a slice)
-            pick_ok = all(char_of(steps[sj][1][2]) != ord("s") for sj in users if steps[sj][0] == "fixed_time_pickoff")
-            if (users and plain and pick_ok and dst.name not in out_names
-                    and sorted(kinds) in (["min_max"], ["time_point_thresh"], ["min_max", "time_point_thresh"], ["amax"], ["amax", "fixed_time_pickoff"])
-                    and not any(isinstance(x, tuple) and x[0] == "slice" and x[1] is dst for _f, a2, _k in steps for x in a2)):
-                pending_reduce[dst.name] = {"src": src, "ints": ints, "kind": trap_ops[fn], "emit_at": max(users), "mm_first": -1}
-                last_use[src.name] = max(last_use.get(src.name, si), max(users))
-                continue
-            dst.slot = new_slot(src.length)
-            p.add_op(trap_ops[fn], dst=dst.slot, src=src.slot, ip=ints)
-            release(src, si)
-        elif fn in ("min_max", "time_point_thresh", "amax", "fixed_time_pickoff") and isinstance(args[0], Var) and args[0].name in pending_reduce:
-            pr = pending_reduce[args[0].name]
-            if fn == "fixed_time_pickoff":  # trapEftp beside trapEmax: the samples around the pick-off time are captured in the same pass
-                pr["pick"] = (scalar_operand(args[1], args, what=what), char_of(args[2]), out_scalar(args[3]))
-            elif fn == "amax":  # numpy.amax of a trapezoid (trapEmax): the a_max of the same reduction (NaN in, NaN out in both)
-                pr["mm_first"] = p.add_sregs(4)
-                pr["amax_only"] = pr["kind"] != _lib.OP_ASYM_TRAP
-                if not isinstance(args[2], Var):
-                    raise ProcessingChainError("numpy.amax output must be a variable name")
-                args[2].kind, args[2].sreg = "scalar", pr["mm_first"] + 3
-            elif fn == "min_max":
-                pr["mm_first"] = p.add_sregs(4)
-                for k, a in enumerate(args[1:5]):
-                    if not isinstance(a, Var):
-                        raise ProcessingChainError("min_max outputs must be variable names")
-                    a.kind, a.sreg = "scalar", pr["mm_first"] + k
-            else:
-                pr["tpt"] = (tuple(scalar_operand(a, args, what=what) for a in args[1:4]), out_scalar(args[4]))
-            if si == pr["emit_at"]:
-                sp, o = pr.get("tpt", ((), None))
-                code = pr["kind"] | ((1 << 30) if pr.get("amax_only") else 0)
-                if "pick" in pr:
-                    t_in, mode, po = pr["pick"]
-                    code |= (mode << 8) | ((po.sreg + 1) << 16)
-                    sp = tuple(sp) + (Scalar.const(0.0),) * (3 - len(sp)) + (t_in,)
-                p.add_op(_lib.OP_TRAP_REDUCE, dst=pr["mm_first"], src=pr["src"].slot, io=(o.sreg if o is not None else -1),
-                         ip=(*pr["ints"], code), sp=sp)
-                release(pr["src"], si)
-                del pending_reduce[args[0].name]
-        elif fn == "fixed_time_pickoff":
-            src = ensure_loaded(args[0], si)
-            o = out_scalar(args[3])
-            p.add_op(_lib.OP_PICKOFF, dst=o.sreg, src=src.slot, ip=(char_of(args[2]),), sp=(scalar_operand(args[1], args, what=what),))
-            release(src, si)
-        elif fn == "time_point_thresh":
-            src = ensure_loaded(args[0], si)
-            sp = tuple(scalar_operand(a, args, what=what) for a in args[1:4])
-            o = out_scalar(args[4])
-            p.add_op(_lib.OP_TIME_POINT_THRESH, dst=o.sreg, src=src.slot, sp=sp)
-            release(src, si)
-        elif fn == "interpolated_time_point_thresh":
-            src = ensure_loaded(args[0], si)
-            walk = scalar_operand(args[3], args, integer=True, what=what)
-            sp = (scalar_operand(args[1], args, what=what), scalar_operand(args[2], args, what=what), Scalar.const(float(walk)))
-            o = out_scalar(args[5])
-            p.add_op(_lib.OP_INTERP_TIME_POINT_THRESH, dst=o.sreg, src=src.slot, ip=(char_of(args[4]),), sp=sp)
-            release(src, si)
+                slots.append(-1)
+                sps.append(self.scalar_operand(x, args, what=what) if r == "s" else Scalar.const(0.0))
+        dead = next((v for v in srcs if self.dead_after(v, si)), None)  # the result may take the place of an operand nobody reads again
+        dst.slot = dead.slot if dead is not None else self.new_slot(dst.length)
+        self.p.add_op(_lib.OP_ELEMENTWISE, dst=dst.slot, src=slots[0], ip=(code, slots[1], slots[2]), sp=tuple(sps))
+        for v in srcs:
+            if v is not dead and v.slot != dst.slot:
+                self.release(v, si)
+
+    def copy_slice(self, si, fn, args, what):
+        src = self.ensure_loaded(args[0], si)
+        dst = args[3]
+        dst.slot = self.new_slot(dst.length)
+        self.p.add_op(_lib.OP_COPY, dst=dst.slot, src=src.slot, ip=(int(args[1]), int(args[2])))
+        self.release(src, si)
+
+    def trapezoid(self, si, fn, args, what):
+        p, steps, last_use, char_of = self.p, self.steps, self.last_use, self.char_of
+        src = self.ensure_loaded(args[0], si)
+        ints = [self.scalar_operand(a, args, integer=True, what=what) for a in args[1:-1]]
+        ints += [0] * (3 - len(ints))
+        dst = self.out_wf(args[-1], src.length)
+        # fusion: the trapezoid's only consumer is the next fixed_time_pickoff and it is not an output
+        nxt = steps[si + 1] if si + 1 < len(steps) else None
+        if (nxt and nxt[0] == "fixed_time_pickoff" and _base_of(nxt[1][0]) is dst and last_use.get(dst.name) == si + 1
+                and dst.name not in self.out_names and char_of(nxt[1][2]) != ord("s")):
+            t_in = self.scalar_operand(nxt[1][1], nxt[1], what=what)
+            o = self.out_scalar(nxt[1][3])
+            p.add_op(_lib.OP_TRAP_PICKOFF, dst=o.sreg, src=src.slot, io=char_of(nxt[1][2]), ip=(*ints, _TRAP_OPS[fn]), sp=(t_in,))
+            self.skip.add(si + 1)
+            self.release(src, si + 1)
+            return
+        # fusion: the trapezoid only feeds one min_max and / or one time_point_thresh (the t0 chain of the LEGEND recipes:
+        # asym_trap_filter -> min_max -> time_point_thresh) and is not an output -> it is never stored.  The fused op is emitted
+        # where the last of the two stands, so their scalar operands (a threshold computed in between) are ready
+        users = [sj for sj, (f2, a2, _k) in enumerate(steps) if sj > si and sj not in self.skip and any(_base_of(x) is dst for x in a2)]
+        kinds = [steps[sj][0] for sj in users]
+        plain = all(steps[sj][1][0] is dst for sj in users)  # (not through a slice)
+        pick_ok = all(char_of(steps[sj][1][2]) != ord("s") for sj in users if steps[sj][0] == "fixed_time_pickoff")
+        if (users and plain and pick_ok and dst.name not in self.out_names
+                and sorted(kinds) in (["min_max"], ["time_point_thresh"], ["min_max", "time_point_thresh"], ["amax"], ["amax", "fixed_time_pickoff"])
+                and not any(isinstance(x, tuple) and x[0] == "slice" and x[1] is dst for _f, a2, _k in steps for x in a2)):
+            self.pending_reduce[dst.name] = {"src": src, "ints": ints, "kind": _TRAP_OPS[fn], "emit_at": max(users), "mm_first": -1}
+            last_use[src.name] = max(last_use.get(src.name, si), max(users))
+            return
+        dst.slot = self.new_slot(src.length)
+        p.add_op(_TRAP_OPS[fn], dst=dst.slot, src=src.slot, ip=ints)
+        self.release(src, si)
+
+    def fused_reduction(self, si, fn, args, what):
+        """a reader of a trapezoid that is never stored (``trapezoid``): its part of the fused op, which the last reader emits"""
+        p = self.p
+        pr = self.pending_reduce[args[0].name]
+        if fn == "fixed_time_pickoff":  # trapEftp beside trapEmax: the samples around the pick-off time are captured in the same pass
+            pr["pick"] = (self.scalar_operand(args[1], args, what=what), self.char_of(args[2]), self.out_scalar(args[3]))
+        elif fn == "amax":  # numpy.amax of a trapezoid (trapEmax): the a_max of the same reduction (NaN in, NaN out in both)
+            pr["mm_first"] = p.add_sregs(4)
+            pr["amax_only"] = pr["kind"] != _lib.OP_ASYM_TRAP
+            if not isinstance(args[2], Var):
+                raise ProcessingChainError("numpy.amax output must be a variable name")
+            args[2].kind, args[2].sreg = "scalar", pr["mm_first"] + 3
         elif fn == "min_max":
-            src = ensure_loaded(args[0], si)
-            first = p.add_sregs(4)
-            for k, a in enumerate(args[1:5]):
-                if not isinstance(a, Var):
-                    raise ProcessingChainError("min_max outputs must be variable names")
-                a.kind, a.sreg = "scalar", first + k
-            p.add_op(_lib.OP_MIN_MAX, dst=first, src=src.slot)
-            release(src, si)
-        elif fn in ("windower", "avg_current"):
-            src = ensure_loaded(args[0], si)
-            dst = out_wf(args[2], None, src)
-            if dst.length is None:
-                raise ProcessingChainError(f"{fn}: declare the output as name(length, 'f')")
-            dst.slot = new_slot(dst.length)
-            p.add_op(_lib.OP_WINDOWER if fn == "windower" else _lib.OP_AVG_CURRENT, dst=dst.slot, src=src.slot,
-                     sp=(scalar_operand(args[1], args, what=what),))
-            release(src, si)
-        elif fn == "upsampler":
-            src = ensure_loaded(args[0], si)
-            dst = out_wf(args[2], None, src)
-            if dst.length is None:
-                raise ProcessingChainError("upsampler: declare the output as name(length, 'f')")
-            dst.slot = new_slot(dst.length)
-            p.add_op(_lib.OP_UPSAMPLER, dst=dst.slot, src=src.slot, sp=(scalar_operand(args[1], args, what=what),))
-            release(src, si)
-        elif fn == "moving_window_multi":
-            src = ensure_loaded(args[0], si)
-            num = scalar_operand(args[2], args, integer=True, what=what)
-            typ = scalar_operand(args[3], args, integer=True, what=what)
-            dst = out_wf(args[4], src.length, src)
-            win = args[1]
-            chunk = -(-(-(-src.length // 64)) // 16) * 16  # samples of a waveform per lane (dsp_chain_create: a multiple of 16)
-            if (last_use.get(src.name, -1) <= si and num >= 1 and isinstance(win, (int, float, np.integer, np.floating)) and not isinstance(win, Quantity)
-                    and float(win) == int(win) and 1 <= int(win) <= chunk):
-                # in place: a source nobody reads again is overwritten pass by pass; only the ends of the lanes' chunks (64 x window
-                # samples) are kept aside.  One waveform instead of two in LDS for the averaged current of the Ge recipes (22 + 13 kB
-                # instead of 43): with that the whole recipe fits four times into a CU instead of three
-                dst.slot = src.slot
-                side = new_slot(64 * int(win))
-                p.add_op(_lib.OP_MOVING_WINDOW_MULTI, dst=dst.slot, src=src.slot, ip=(typ, num, side, 1), sp=(scalar_operand(win, args, what=what),))
-                if side not in free_slots:
-                    free_slots.append(side)
-                continue
-            dst.slot = new_slot(src.length)
-            # ping-pong target of the passes before the last: with an odd number of windows the first pass goes source -> target, so a
-            # source nobody reads again serves
-            own = num > 1 and not (num % 2 == 1 and last_use.get(src.name, -1) <= si)
-            tmp = new_slot(src.length) if own else (src.slot if num > 1 else dst.slot)
-            p.add_op(_lib.OP_MOVING_WINDOW_MULTI, dst=dst.slot, src=src.slot, ip=(typ, num, tmp), sp=(scalar_operand(args[1], args, what=what),))
-            if own and tmp not in free_slots:
-                free_slots.append(tmp)
-            release(src, si)
-        elif fn == "trap_pickoff":
-            src = ensure_loaded(args[0], si)
-            ints = [scalar_operand(a, args, integer=True, what=what) for a in args[1:3]]
-            o = out_scalar(args[4])
-            p.add_op(_lib.OP_TRAP_WINDOW_PICKOFF, dst=o.sreg, src=src.slot, ip=tuple(ints), sp=(scalar_operand(args[3], args, what=what),))
-            release(src, si)
-        elif fn == "mean_below_threshold":
-            src = ensure_loaded(args[0], si)
-            o = out_scalar(args[2])
-            p.add_op(_lib.OP_MEAN_BELOW, dst=o.sreg, src=src.slot, sp=(scalar_operand(args[1], args, what=what),))
-            release(src, si)
-        elif fn == "linear_slope_fit":
-            a0, view = args[0], (0, 0)
+            pr["mm_first"] = self.out_four(args[1:5], "min_max")
+        else:
+            pr["tpt"] = (tuple(self.scalar_operand(a, args, what=what) for a in args[1:4]), self.out_scalar(args[4]))
+        if si == pr["emit_at"]:
+            sp, o = pr.get("tpt", ((), None))
+            code = pr["kind"] | ((1 << 30) if pr.get("amax_only") else 0)
+            if "pick" in pr:
+                t_in, mode, po = pr["pick"]
+                code |= (mode << 8) | ((po.sreg + 1) << 16)
+                sp = tuple(sp) + (Scalar.const(0.0),) * (3 - len(sp)) + (t_in,)
+            p.add_op(_lib.OP_TRAP_REDUCE, dst=pr["mm_first"], src=pr["src"].slot, io=(o.sreg if o is not None else -1),
+                     ip=(*pr["ints"], code), sp=sp)
+            self.release(pr["src"], si)
+            del self.pending_reduce[args[0].name]
+
+    def four_values(self, si, fn, args, what):
+        """min_max, and linear_slope_fit where it stayed in the program"""
+        a0, view = args[0], ()
+        if fn == "linear_slope_fit":
+            view = (0, 0)
             if isinstance(a0, tuple) and a0[0] == "slice" and not a0[1].is_input:  # a window of an intermediate: read in place
                 a0, view = a0[1], (a0[2], a0[3] - a0[2])
-            src = ensure_loaded(a0, si)
-            first = p.add_sregs(4)
-            for k, a in enumerate(args[1:5]):
-                if not isinstance(a, Var):
-                    raise ProcessingChainError("linear_slope_fit outputs must be variable names")
-                a.kind, a.sreg = "scalar", first + k
-            p.add_op(_lib.OP_LINEAR_SLOPE_FIT, dst=first, src=src.slot, ip=view)
-            release(src, si)
-        elif fn == "amax":
-            src = ensure_loaded(args[0], si)
-            o = out_scalar(args[2])
-            p.add_op(_lib.OP_AMAX, dst=o.sreg, src=src.slot)
-            release(src, si)
-        elif fn == "discrete_wavelet_transform":
-            src = ensure_loaded(args[0], si)
-            level = scalar_operand(args[1], args, integer=True, what=what)
-            wt, part = char_of(args[2]), char_of(args[3])
-            if wt not in (ord("h"), ord("d")):
-                raise NotImplementedError("only the Haar wavelet ('h' / 'd') is implemented on the device")
-            dst = out_wf(args[4], None, src)
-            if dst.length is None:
-                raise ProcessingChainError("discrete_wavelet_transform: declare the output as name(length, 'f')")
-            dead = last_use.get(src.name, -1) <= si and not src.is_input or (src.is_input and last_use.get(src.name, -1) <= si)
-            scratch = src.slot if dead else new_slot(src.length)
-            dst.slot = new_slot(dst.length)
-            p.add_op(_lib.OP_DWT_HAAR, dst=dst.slot, src=src.slot, ip=(level, part, scratch))
-            if dead:
-                release(src, si)
-            elif scratch not in free_slots:
-                free_slots.append(scratch)
-        elif fn in ("convolve_wf", "fft_convolve_wf"):
-            src = ensure_loaded(args[0], si)
-            taps = args[1]
-            if not (isinstance(taps, Var) and taps.kind == "taps"):
-                raise NotImplementedError(f"{fn}: the kernel must be a constant computed in the recipe (cusp_filter / zac_filter)")
-            if taps.io is None:  # (zeros after the taps up to a multiple of the FIR op's tap block: its fast path then covers every tap)
-                padded = -(-taps.length // 16) * 16
-                taps.io = p.add_io(f"taps:{taps.name}", _lib.IO_TAPS, ft, padded, 0, 0)
-                consts[f"taps:{taps.name}"] = np.concatenate([taps.const.astype(ft), np.zeros(padded - taps.length, dtype=ft)])
-            dst = out_wf(args[3], None, src)
-            if dst.length is None:
-                raise ProcessingChainError(f"{fn}: declare the output as name(length, 'f')")
-            has_nan = int(np.isnan(taps.const).any()) | (2 if np.isinf(taps.const).any() else 0)  # (bit 1: an infinite tap)
-            # fusion: the filtered waveform's only consumer is one numpy.amax and it is not an output -> it is never stored
-            users = [sj for sj, (f2, a2, _k) in enumerate(steps) if sj != si and any(wf_of(x) is dst for x in a2)]
-            if (len(users) == 1 and steps[users[0]][0] == "amax" and steps[users[0]][1][0] is dst and dst.name not in out_names
-                    and users[0] > si and users[0] not in skip):
-                o = out_scalar(steps[users[0]][1][2])
-                p.add_op(_lib.OP_CONVOLVE_AMAX, dst=o.sreg, src=src.slot, io=taps.io, ip=(char_of(args[2]), has_nan, int(dst.length), int(taps.length)))
-                skip.add(users[0])
-                last_use[src.name] = max(last_use.get(src.name, si), si)
-                release(src, si)
-                continue
-            dst.slot = new_slot(dst.length)
-            p.add_op(_lib.OP_CONVOLVE, dst=dst.slot, src=src.slot, io=taps.io,
-                     ip=(char_of(args[2]), has_nan, int(_piecewise_constant(taps.const)), int(taps.length)))
-            release(src, si)
-        else:
-            raise NotImplementedError(f"processor '{fn}' is not implemented on the device path")
+        src = self.ensure_loaded(a0, si)
+        first = self.out_four(args[1:5], fn)
+        self.p.add_op(_lib.OP_MIN_MAX if fn == "min_max" else _lib.OP_LINEAR_SLOPE_FIT, dst=first, src=src.slot, ip=view)
+        self.release(src, si)
 
-    tb_out = {}
+    def window(self, si, fn, args, what):
+        """windower, avg_current, upsampler: a declared output of another length, one per-event operand"""
+        src = self.ensure_loaded(args[0], si)
+        dst = self.out_wf(args[2], None, fn)
+        dst.slot = self.new_slot(dst.length)
+        self.p.add_op(_WINDOW_OPS[fn], dst=dst.slot, src=src.slot, sp=(self.scalar_operand(args[1], args, what=what),))
+        self.release(src, si)
+
+    def moving_window_multi(self, si, fn, args, what):
+        p = self.p
+        src = self.ensure_loaded(args[0], si)
+        num = self.scalar_operand(args[2], args, integer=True, what=what)
+        typ = self.scalar_operand(args[3], args, integer=True, what=what)
+        dst = self.out_wf(args[4], src.length)
+        win = args[1]
+        chunk = -(-(-(-src.length // 64)) // 16) * 16  # samples of a waveform per lane (dsp_chain_create: a multiple of 16)
+        if (self.dead_after(src, si) and num >= 1 and (_is_number(win) or win is True) and float(win) == int(win) and 1 <= int(win) <= chunk):
+            # in place: a source nobody reads again is overwritten pass by pass; only the ends of the lanes' chunks (64 x window
+            # samples) are kept aside.  One waveform instead of two in LDS for the averaged current of the Ge recipes (22 + 13 kB
+            # instead of 43): with that the whole recipe fits four times into a CU instead of three
+            dst.slot = src.slot
+            side = self.new_slot(64 * int(win))
+            p.add_op(_lib.OP_MOVING_WINDOW_MULTI, dst=dst.slot, src=src.slot, ip=(typ, num, side, 1), sp=(self.scalar_operand(win, args, what=what),))
+            self.free(side)
+            return
+        dst.slot = self.new_slot(src.length)
+        # ping-pong target of the passes before the last: with an odd number of windows the first pass goes source -> target, so a
+        # source nobody reads again serves
+        own = num > 1 and not (num % 2 == 1 and self.dead_after(src, si))
+        tmp = self.new_slot(src.length) if own else (src.slot if num > 1 else dst.slot)
+        p.add_op(_lib.OP_MOVING_WINDOW_MULTI, dst=dst.slot, src=src.slot, ip=(typ, num, tmp), sp=(self.scalar_operand(args[1], args, what=what),))
+        if own:
+            self.free(tmp)
+        self.release(src, si)
+
+    def wavelet(self, si, fn, args, what):
+        src = self.ensure_loaded(args[0], si)
+        level = self.scalar_operand(args[1], args, integer=True, what=what)
+        wt, part = self.char_of(args[2]), self.char_of(args[3])
+        if wt not in (ord("h"), ord("d")):
+            raise NotImplementedError("only the Haar wavelet ('h' / 'd') is implemented on the device")
+        dst = self.out_wf(args[4], None, fn)
+        dead = self.dead_after(src, si)
+        scratch = src.slot if dead else self.new_slot(src.length)
+        dst.slot = self.new_slot(dst.length)
+        self.p.add_op(_lib.OP_DWT_HAAR, dst=dst.slot, src=src.slot, ip=(level, part, scratch))
+        if dead:
+            self.release(src, si)
+        else:
+            self.free(scratch)
+
+    def convolve(self, si, fn, args, what):
+        p, steps = self.p, self.steps
+        src = self.ensure_loaded(args[0], si)
+        taps = args[1]
+        if not (isinstance(taps, Var) and taps.kind == "taps"):
+            raise NotImplementedError(f"{fn}: the kernel must be a constant computed in the recipe (cusp_filter / zac_filter)")
+        if taps.io is None:  # (zeros after the taps up to a multiple of the FIR op's tap block: its fast path then covers every tap)
+            padded = -(-taps.length // 16) * 16
+            taps.io = p.add_io(f"taps:{taps.name}", _lib.IO_TAPS, self.ft, padded, 0, 0)
+            self.consts[f"taps:{taps.name}"] = np.concatenate([taps.const.astype(self.ft), np.zeros(padded - taps.length, dtype=self.ft)])
+        dst = self.out_wf(args[3], None, fn)
+        has_nan = int(np.isnan(taps.const).any()) | (2 if np.isinf(taps.const).any() else 0)  # (bit 1: an infinite tap)
+        # fusion: the filtered waveform's only consumer is one numpy.amax and it is not an output -> it is never stored
+        users = [sj for sj, (f2, a2, _k) in enumerate(steps) if sj != si and any(_base_of(x) is dst for x in a2)]
+        if (len(users) == 1 and steps[users[0]][0] == "amax" and steps[users[0]][1][0] is dst and dst.name not in self.out_names
+                and users[0] > si and users[0] not in self.skip):
+            o = self.out_scalar(steps[users[0]][1][2])
+            p.add_op(_lib.OP_CONVOLVE_AMAX, dst=o.sreg, src=src.slot, io=taps.io, ip=(self.char_of(args[2]), has_nan, int(dst.length), int(taps.length)))
+            self.skip.add(users[0])
+            self.last_use[src.name] = max(self.last_use.get(src.name, si), si)
+            self.release(src, si)
+            return
+        dst.slot = self.new_slot(dst.length)
+        p.add_op(_lib.OP_CONVOLVE, dst=dst.slot, src=src.slot, io=taps.io,
+                 ip=(self.char_of(args[2]), has_nan, int(_piecewise_constant(taps.const)), int(taps.length)))
+        self.release(src, si)
+
+
+#: processors that read one per-event value off a waveform (``_Emitter.read_off``): name -> (op, index of the output argument, (emitter,
+#: arguments, ``so``: a scalar argument as an operand) -> (ip, sp) of the op, are the operands resolved before the output's register is made?)
+_READ_OFF = {
+    "sample": (_lib.OP_PICKOFF, 2, lambda e, a, so: ((ord("n"), 1), (Scalar.const(float(a[1])),)), False),
+    "get": (_lib.OP_PICKOFF, 2, lambda e, a, so: ((ord("n"), 2), (so(a[1]), Scalar.const(float("nan")))), False),
+    "fixed_time_pickoff": (_lib.OP_PICKOFF, 3, lambda e, a, so: ((e.char_of(a[2]),), (so(a[1]),)), False),
+    "time_point_thresh": (_lib.OP_TIME_POINT_THRESH, 4, lambda e, a, so: ((), tuple(so(x) for x in a[1:4])), True),
+    "interpolated_time_point_thresh": (_lib.OP_INTERP_TIME_POINT_THRESH, 5, lambda e, a, so: (
+        (e.char_of(a[4]),), (so(a[1]), so(a[2]), Scalar.const(float(so(a[3], integer=True))))), True),
+    "amax": (_lib.OP_AMAX, 2, lambda e, a, so: ((), ()), False),
+    "mean_below_threshold": (_lib.OP_MEAN_BELOW, 2, lambda e, a, so: ((), (so(a[1]),)), False),
+    "trap_pickoff": (_lib.OP_TRAP_WINDOW_PICKOFF, 4, lambda e, a, so: (tuple(so(x, integer=True) for x in a[1:3]), (so(a[3]),)), False),
+}
+#: the other processors -> the method of ``_Emitter`` that emits their family
+_EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OPS, _Emitter.trapezoid), **dict.fromkeys(_WINDOW_OPS, _Emitter.window),
+         "slice": _Emitter.copy_slice, "min_max": _Emitter.four_values, "linear_slope_fit": _Emitter.four_values,
+         "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
+         "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve}
+
+
+def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
+    """The stores of the recipe's outputs, behind the last processor.  Returns (the output table, the output bindings, {variable-length
+    output: the input column that holds its per-event lengths})."""
+    b, p, ft = e.b, e.p, e.ft
+    tb_out, out_bind, vector_lens = {}, {}, {}
     for o in out_pars:
         v = b.vars.get(o)
         if o in island_out:  # written by the integer program, in its own type
@@ -1421,7 +1413,7 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
             tb_out[o] = np.empty(n_rows, dtype=nat)
             continue
         if _is_wf(v) and isinstance(v, tuple):  # a named slice: of an input it is read straight from the rows, else copied out of its waveform
-            v = ensure_loaded(v, len(steps))
+            v = e.ensure_loaded(v, len(e.steps))
         if v is None or v.kind in (None,):
             raise ProcessingChainError(f"output '{o}' was never computed")
         if v.kind == "const":
@@ -1433,7 +1425,7 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
             continue
         if v.kind == "wf":
             if v.slot is None and v.is_input:  # (an input under another name, or astype of nothing: load it to store it)
-                v = ensure_loaded(v, len(steps))
+                v = e.ensure_loaded(v, len(e.steps))
             if v.slot is None:
                 raise ProcessingChainError(f"output waveform '{o}' was never computed")
             odt = np.dtype(np.bool_) if v.dtype == np.dtype(np.bool_) else ft
@@ -1446,71 +1438,142 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
                     raise NotImplementedError(f"output '{o}': vector_len must be the length of an input array (len(<input>))")
                 vector_lens[o] = vl.source
             tb_out[o] = np.empty((n_rows, v.length), dtype=v.dtype if _is_int_dtype(v) and v.dtype.kind != "b" else odt)
-        else:
-            # a time coordinate is written in its unit, not in samples: (index + grid offset) * period (reference :1990-2014, get_buffer(unit))
-            unit_ns = _time_unit_ns(v.unit)
-            if v.is_coord is True and v.grid is not None and unit_ns is not None and not stage_mode:  # (a stage hands on sample indices)
-                v = b.converted(v, Grid(unit_ns))
-            if isinstance(v, Var) and v.sreg is None and (getattr(v, "aux_io", None) is not None or getattr(v, "ext_key", None) is not None):
-                src_op = scalar_operand(v, [], what=f"output {o}")  # (stores read registers)
-                v.sreg = p.add_sregs(1)
-                p.add_op(_lib.OP_SCALAR_FUNC, dst=v.sreg, ip=(_lib.FN_COPY,), sp=(src_op, Scalar.const(0.0), Scalar.const(0.0)))
-            if isinstance(v, Var) and v.sreg is None:
-                if v.is_input:
-                    tb_out[o] = _column(b.tb_in, v.source)
-                    continue
-                raise ProcessingChainError(f"output '{o}' was never computed")
-            reg = scalar_operand(v, [], what=f"output {o}")
-            odt = np.dtype(np.bool_) if getattr(v, "dtype", None) == np.dtype(np.bool_) else ft
-            io = p.add_io(f"out:{o}", _lib.IO_SCALAR_OUT, odt)
-            p.add_op(_lib.OP_STORE_SCALAR, io=io, ip=(reg.index,))
-            out_bind[f"out:{o}"] = (SimpleNamespace(name=o, dtype=odt), None)
-            tb_out[o] = np.empty(n_rows, dtype=v.dtype if isinstance(v, SExpr) and _is_int_dtype(v) and v.dtype.kind != "b" else odt)
+            continue
+        # a time coordinate is written in its unit, not in samples: (index + grid offset) * period (reference :1990-2014, get_buffer(unit))
+        unit_ns = _time_unit_ns(v.unit)
+        if v.is_coord is True and v.grid is not None and unit_ns is not None and not stage_mode:  # (a stage hands on sample indices)
+            v = b.converted(v, Grid(unit_ns))
+        if isinstance(v, Var) and v.sreg is None and (getattr(v, "aux_io", None) is not None or getattr(v, "ext_key", None) is not None):
+            src_op = e.scalar_operand(v, [], what=f"output {o}")  # (stores read registers)
+            v.sreg = p.add_sregs(1)
+            p.add_op(_lib.OP_SCALAR_FUNC, dst=v.sreg, ip=(_lib.FN_COPY,), sp=(src_op, Scalar.const(0.0), Scalar.const(0.0)))
+        if isinstance(v, Var) and v.sreg is None:
+            if v.is_input:
+                tb_out[o] = _column(b.tb_in, v.source)
+                continue
+            raise ProcessingChainError(f"output '{o}' was never computed")
+        reg = e.scalar_operand(v, [], what=f"output {o}")
+        odt = np.dtype(np.bool_) if getattr(v, "dtype", None) == np.dtype(np.bool_) else ft
+        io = p.add_io(f"out:{o}", _lib.IO_SCALAR_OUT, odt)
+        p.add_op(_lib.OP_STORE_SCALAR, io=io, ip=(reg.index,))
+        out_bind[f"out:{o}"] = (SimpleNamespace(name=o, dtype=odt), None)
+        tb_out[o] = np.empty(n_rows, dtype=v.dtype if isinstance(v, SExpr) and _is_int_dtype(v) and v.dtype.kind != "b" else odt)
+    return tb_out, out_bind, vector_lens
+
+
+def _fit_descriptors(e: _Emitter, aux):
+    """what the runtime launches for the fits that ``_extract_fits`` took out, with the program's bindings of their rows and subtrahends"""
+    b, p = e.b, e.p
     aux_desc = []
     for gi, g in enumerate(aux):
         src = g["src"]
         col = _column(b.tb_in, src.source)
-        wf_bind = next((nm for nm, v in in_bind.items() if isinstance(v, Var) and v.kind == "wf" and v.source == src.source and v.offset == 0
+        wf_bind = next((nm for nm, v in e.in_bind.items() if isinstance(v, Var) and v.kind == "wf" and v.source == src.source and v.offset == 0
                         and v.length == src.length), None)
         if wf_bind is None:  # (nothing in the program reads the whole row: bind it for the fit alone)
             wf_bind = f"in:{src.name}:fit{gi}"
             p.add_io(wf_bind, _lib.IO_WF_IN, col.dtype, src.length, 0, col.shape[1])
-            in_bind[wf_bind] = src
+            e.in_bind[wf_bind] = src
         sub_bind, sub_const, sub_code = None, 0.0, _lib.F32
         if isinstance(g["sub"], Var):
-            sub_bind = p.io[scalar_operand(g["sub"], [], what="linear_slope_fit").index][0]
+            sub_bind = p.io[e.scalar_operand(g["sub"], [], what="linear_slope_fit").index][0]
             sub_code = dtype_code(_column(b.tb_in, g["sub"].source).dtype)
         elif g["sub"] is not None:
             sub_const = float(g["sub"])
         aux_desc.append({"wf": wf_bind, "dtype": dtype_code(col.dtype), "itemsize": np.dtype(col.dtype).itemsize, "lo": g["lo"], "len": g["len"],
                          "stride": col.shape[1], "sub": sub_bind, "sub_dtype": sub_code, "sub_const": sub_const, "mode": g["mode"],
                          "tau": g["tau"], "fits": list(g["fits"]), "names": [f"aux:{gi}:{j}" for j in range(4 * len(g["fits"]))]})
-    p.slots = slot_len
+    return aux_desc
+
+
+def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
+    """The passes, in order.  ``stage_mode``: the program of a stage that runs ahead of the main program (_extract_stages): the integer
+    program, fits and other stages are not taken out of it again; their results arrive as bindings (``Var.ext_key``)."""
+    p = Program()
+    ft = b.stage_ft if stage_mode else _loop_dtype(b)
+    main = not stage_mode
+    off = lambda switch: os.environ.get(switch) == "1"  # noqa: E731
+    steps = b.steps
+    island, island_out = _int_island(b, steps, out_pars, ft) if main else (None, {})
+    aux, stages = [], []
+    if main and not off("DSPEED_HIP_FIT_IN_CHAIN"):
+        aux, steps = _extract_fits(b, steps, out_pars, p, ft)
+    # long FIRs on the matrix cores, ahead of the program (DESIGN.md section 4a): their results are bindings of the program
+    if main and ft == np.dtype(np.float32) and not off("DSPEED_HIP_NO_STAGES"):
+        steps, stages = _extract_stages(b, steps, out_pars, n_rows, ft)
+    if island is not None:
+        stages = [island] + stages
+    steps = b.steps = _schedule(steps)
+    out_names = set(out_pars)  # names of the variables that are outputs (a variable may have another name than the output: alias, named slice)
+    out_names.update(v.name for v in (_base_of(b.vars.get(o)) for o in out_pars) if v is not None)
+    whole_nan_rule = _push_down_slices(steps, out_names)
+    e = _Emitter(b, p, ft, steps, out_names, whole_nan_rule, _last_uses(b, steps, out_pars))
+    e.run()
+    tb_out, out_bind, vector_lens = _emit_outputs(e, out_pars, island_out, n_rows, stage_mode)
+    aux_desc = _fit_descriptors(e, aux)
+    p.slots = e.slot_len
     if not p.ops:  # (every output is written by the integer program or handed through: the program is a placeholder)
         p.add_op(_lib.OP_SCALAR_AFFINE, dst=p.add_sregs(1), sp=(Scalar.const(0.0), Scalar.const(0.0), Scalar.const(0.0)))
     if len(p.ops) > _lib.MAX_OPS or len(p.slots) > _lib.MAX_SLOTS or len(p.io) > _lib.MAX_IO or p.n_sregs > _lib.MAX_SREGS:
         raise NotImplementedError("recipe is too large for one device chain (ops/slots/bindings limit)")
     for st in stages:  # columns of the input table that only a stage reads are linked like the program's own
         for nm, v in st["in_vars"].items():
-            in_bind.setdefault(nm, v)
-    tail = None
-    if not stage_mode and os.environ.get("DSPEED_HIP_NO_SCALAR_TAIL", "0") != "1":
-        tail = _split_scalar_tail(p, ft)
-    if not stage_mode and os.environ.get("DSPEED_HIP_NO_SCALAR_HEAD", "0") != "1":  # (behind the tail's cut: what is only stored is the tail's)
-        head = _split_scalar_head(p, ft, ext_alias)
+            e.in_bind.setdefault(nm, v)
+    tail = _split_scalar_tail(p, ft) if main and not off("DSPEED_HIP_NO_SCALAR_TAIL") else None
+    if main and not off("DSPEED_HIP_NO_SCALAR_HEAD"):  # (behind the tail's cut: what is only stored is the tail's)
+        head = _split_scalar_head(p, ft, e.ext_alias)
         if head is not None:
             stages.append(head)
-    walks = None
-    if not stage_mode and os.environ.get("DSPEED_HIP_NO_WALKS_BEHIND", "0") != "1":
-        walks = _split_walks(p, ft)
+    walks = _split_walks(p, ft) if main and not off("DSPEED_HIP_NO_WALKS_BEHIND") else None
     from .processing_chain import ProcessingChain  # (the runtime imports this module)
 
-    chain = ProcessingChain(p, in_bind, out_bind, consts, n_rows, proc_strings, ft, aux_desc, stages=stages, ext_alias=ext_alias, tail=tail, walks=walks)
+    chain = ProcessingChain(p, e.in_bind, out_bind, e.consts, n_rows, proc_strings, ft, aux_desc, stages=stages, ext_alias=e.ext_alias, tail=tail, walks=walks)
     chain.vector_lens = vector_lens  # variable-length outputs -> the input column that holds their per-event lengths
     return chain, tb_out
 
 
 _SCALAR_OPS = (_lib.OP_SCALAR_AFFINE, _lib.OP_SCALAR_DIV, _lib.OP_SCALAR_CONVERT, _lib.OP_SCALAR_FUNC, _lib.OP_STORE_SCALAR)
+
+
+def _reads_of(op):
+    """the registers an op reads"""
+    opcode, _dst, _src, _io, ip, sp = op
+    return [a.index for a in sp if a.kind == _lib.ARG_REG] + ([ip[0]] if opcode == _lib.OP_STORE_SCALAR else [])
+
+
+def _writes_of(op):
+    """the registers an op writes"""
+    opcode, dst, _src, io, ip, _sp = op
+    if opcode in (_lib.OP_STORE_SCALAR, _lib.OP_LOAD, _lib.OP_STORE):
+        return []
+    if opcode == _lib.OP_MIN_MAX:
+        return [dst + k for k in range(4)]
+    if opcode == _lib.OP_TRAP_REDUCE:  # (its extremes, the maximum alone, a pick-off of the same trapezoid: include/dspeed_hip.h)
+        w = [dst + k for k in range(4)] if dst >= 0 else []
+        if io >= 0:
+            w.append(io)
+        if ((ip[3] >> 16) & 0x3fff) - 1 >= 0:
+            w.append(((ip[3] >> 16) & 0x3fff) - 1)
+        return w
+    return [dst]
+
+
+def _split_off(p: Program, slots=False):
+    """an empty program with the registers of ``p``, and the function that gives a binding of ``p`` its place in it (copied on first use)"""
+    q = Program()
+    q.n_sregs = p.n_sregs
+    if slots:
+        q.slots = list(p.slots)
+    io_map = {}
+
+    def binding(idx):
+        if idx not in io_map:
+            io_map[idx] = q.add_io(*p.io[idx])
+        return io_map[idx]
+
+    return q, binding
+
+
 #: a tail is cut off when it has at least this many ops (a launch and a column per handed-over register have to pay for themselves)
 SCALAR_TAIL_MIN_OPS = 8
 
@@ -1531,32 +1594,12 @@ def _split_scalar_head(p: Program, ft, ext_alias: dict):
     from_head = {}          # register -> (column name, index into `made`) while the register's current value comes from a head op
     head_ops, made = [], []  # made: [column name, register, read by the program?]
     new_ops = []
-
-    def reads_of(opcode, ip, sp):
-        r = [a.index for a in sp if a.kind == _lib.ARG_REG]
-        if opcode == _lib.OP_STORE_SCALAR:
-            r.append(ip[0])
-        return r
-
-    def writes_of(opcode, dst, io, ip):
-        if opcode == _lib.OP_STORE_SCALAR or opcode in (_lib.OP_LOAD, _lib.OP_STORE):
-            return []
-        if opcode in (_lib.OP_MIN_MAX,):
-            return [dst + k for k in range(4)]
-        if opcode == _lib.OP_TRAP_REDUCE:  # (its extremes, the maximum alone, a pick-off of the same trapezoid: include/dspeed_hip.h)
-            w = [dst + k for k in range(4)] if dst >= 0 else []
-            if io >= 0:
-                w.append(io)
-            if ((ip[3] >> 16) & 0x3fff) - 1 >= 0:
-                w.append(((ip[3] >> 16) & 0x3fff) - 1)
-            return w
-        return [dst]
-
-    for k, (opcode, dst, src, io, ip, sp) in enumerate(p.ops):
+    for op in p.ops:
+        opcode, dst, src, io, ip, sp = op
         is_head = (opcode in _SCALAR_OPS and opcode != _lib.OP_STORE_SCALAR
                    and all(a.kind in (_lib.ARG_CONST, _lib.ARG_INPUT) or (a.kind == _lib.ARG_REG and a.index in from_head) for a in sp))
         if is_head:
-            head_ops.append((opcode, dst, src, io, ip, sp))
+            head_ops.append(op)
             made.append([f"head:r{dst}.{len(made)}", dst, False])
             from_head[dst] = len(made) - 1
             continue
@@ -1573,20 +1616,11 @@ def _split_scalar_head(p: Program, ft, ext_alias: dict):
             new_ops.append(("copy", ip[0], from_head[ip[0]]))
             del from_head[ip[0]]
         new_ops.append((opcode, dst, src, io, ip, tuple(sp2)))
-        for r in writes_of(opcode, dst, io, ip):
+        for r in _writes_of(op):
             from_head.pop(r, None)
     if len(head_ops) < SCALAR_HEAD_MIN_OPS or not any(m[2] for m in made):
         return None
-    h = Program()
-    h.n_sregs = p.n_sregs
-    io_map = {}
-
-    def head_io(idx):
-        if idx not in io_map:
-            name, kind, code, length, offset, stride = p.io[idx]
-            io_map[idx] = h.add_io(name, kind, code, length, offset, stride)
-        return io_map[idx]
-
+    h, head_io = _split_off(p)
     for (opcode, dst, src, io, ip, sp), (name, r, used) in zip(head_ops, made):
         h.add_op(opcode, dst=dst, src=src, io=io, ip=ip, sp=tuple(Scalar.input(head_io(a.index)) if a.kind == _lib.ARG_INPUT else a for a in sp))
         if used:  # (stored right behind the op that made it: the head may write the register again)
@@ -1610,8 +1644,8 @@ def _split_scalar_head(p: Program, ft, ext_alias: dict):
     if len(p.io) > _lib.MAX_IO or len(h.io) > _lib.MAX_IO:
         raise NotImplementedError("recipe is too large for one device chain (ops/slots/bindings limit)")
     names = [io[0] for io in h.io if io[1] == _lib.IO_SCALAR_IN]
-    return {"what": "per-event arithmetic ahead of the program", "program": h, "consts": {}, "in_vars": {}, "alias": {n: ext_alias.get(n, n) for n in names},
-            "outs": [("out:" + name, "in:" + name, None) for name, _r, used in made if used], "chain": None, "bufs": {}}
+    return _stage_record("per-event arithmetic ahead of the program", h, {}, {}, {n: ext_alias.get(n, n) for n in names},
+                         [("out:" + name, "in:" + name, None) for name, _r, used in made if used])
 
 
 #: the rise-time walks leave a program whose waveform has at least this many samples (LDS then holds a handful of rows per CU)
@@ -1636,26 +1670,11 @@ def _split_walks(p: Program, ft):
     slot = ops[0][1]
     TPT, AFF, STS = _lib.OP_TIME_POINT_THRESH, _lib.OP_SCALAR_AFFINE, _lib.OP_STORE_SCALAR
 
-    def writes_of(op):
-        opcode, dst, _src, io, ip, _sp = op
-        if opcode in (STS, _lib.OP_LOAD, _lib.OP_STORE):
-            return []
-        if opcode == _lib.OP_MIN_MAX:
-            return [dst + k for k in range(4)]
-        if opcode == _lib.OP_TRAP_REDUCE:
-            w = [dst + k for k in range(4)] if dst >= 0 else []
-            if io >= 0:
-                w.append(io)
-            if ((ip[3] >> 16) & 0x3fff) - 1 >= 0:
-                w.append(((ip[3] >> 16) & 0x3fff) - 1)
-            return w
-        return [dst]
-
     n_writes = {}
     for op in ops:
-        for r in writes_of(op):
+        for r in _writes_of(op):
             n_writes[r] = n_writes.get(r, 0) + 1
-    writer = {r: k for k, op in enumerate(ops) for r in writes_of(op)}
+    writer = {r: k for k, op in enumerate(ops) for r in _writes_of(op)}
 
     def readers(r):
         return [(k, j) for k, op in enumerate(ops) for j, a in enumerate(op[5]) if a.kind == _lib.ARG_REG and a.index == r] + \
@@ -1704,17 +1723,7 @@ def _split_walks(p: Program, ft):
         for a in ops[k][5][:2] if ops[k][0] == TPT else ops[k][5][:1]:
             if a.kind == _lib.ARG_REG and writer[a.index] not in moved and a.index not in handed:
                 handed.append(a.index)
-    w = Program()
-    w.n_sregs = p.n_sregs
-    w.slots = list(p.slots)
-    io_map = {}
-
-    def w_io(idx):
-        if idx not in io_map:
-            name, kind, code, length, offset, stride = p.io[idx]
-            io_map[idx] = w.add_io(name, kind, code, length, offset, stride)
-        return io_map[idx]
-
+    w, w_io = _split_off(p, slots=True)
     col = {r: w.add_io(f"walk:r{r}", _lib.IO_SCALAR_IN, ft) for r in handed}
 
     def operand(a):
@@ -1766,25 +1775,12 @@ def _split_scalar_tail(p: Program, ft):
         return None
     tail_ops = ops[k:]
     written, live_in = set(), []
-    for opcode, dst, _src, _io, ip, sp in tail_ops:
-        reads = [a.index for a in sp if a.kind == _lib.ARG_REG]
-        if opcode == _lib.OP_STORE_SCALAR:
-            reads.append(ip[0])
-        for r in reads:
+    for op in tail_ops:
+        for r in _reads_of(op):
             if r not in written and r not in live_in:
                 live_in.append(r)
-        if opcode != _lib.OP_STORE_SCALAR:
-            written.add(dst)
-    t = Program()
-    t.n_sregs = p.n_sregs
-    io_map = {}  # binding of the head -> the tail's copy of it
-
-    def tail_io(idx):
-        if idx not in io_map:
-            name, kind, code, length, offset, stride = p.io[idx]
-            io_map[idx] = t.add_io(name, kind, code, length, offset, stride)
-        return io_map[idx]
-
+        written.update(_writes_of(op))
+    t, tail_io = _split_off(p)
     handover = []
     del ops[k:]
     for r in live_in:
@@ -1799,5 +1795,3 @@ def _split_scalar_tail(p: Program, ft):
     if len(t.io) > _lib.MAX_IO or len(p.io) > _lib.MAX_IO or len(p.ops) > _lib.MAX_OPS:
         raise NotImplementedError("recipe is too large for one device chain (ops/slots/bindings limit)")
     return {"program": t, "handover": handover}
-
-

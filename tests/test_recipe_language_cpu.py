@@ -455,14 +455,17 @@ def test_the_scalar_tail_of_a_program_becomes_a_program_of_its_own(monkeypatch):
 
 
 def _programs(chain):
-    """everything the device is given for a recipe: the main program, the stages ahead of it, the scalar tail behind it, the fits on the rows"""
+    """everything the device is given for a recipe: the main program, the stages ahead of it, the scalar tail and the walks behind it with what
+    is handed over to them, the fits on the rows, the bindings of the input table and of the buffers the stages fill"""
     def prog(p):
         return {"ops": [(o[0], o[1], o[2], o[3], o[4], tuple((a.kind, a.index, a.value if a.value == a.value else "nan") for a in o[5])) for o in p.ops],
                 "io": list(p.io), "slots": list(p.slots), "n_sregs": p.n_sregs}
 
     out = {"main": prog(chain.program), "stages": [(st["what"], prog(st["program"]), {k: v.tobytes() for k, v in st["consts"].items()}) for st in chain._stages],
            "tail": prog(chain._tail["program"]) if chain._tail else None, "fits": [{k: v for k, v in g.items()} for g in chain._aux],
-           "consts": {k: v.tobytes() for k, v in chain._consts.items()}}
+           "consts": {k: v.tobytes() for k, v in chain._consts.items()},
+           "walks": (prog(chain._walks["program"]), chain._walks["handover"]) if chain._walks else None,
+           "handover": chain._tail["handover"] if chain._tail else None, "in": sorted(chain._in_vars), "alias": dict(chain._ext_alias)}
     return out
 
 
@@ -481,6 +484,7 @@ def test_the_recipe_with_the_references_values_is_the_references_file_op_for_op(
     assert sorted(mask_t) == sorted(mask_o) and list(out_t) == list(out_o) and len(out_o) == 34
     a, b = _programs(theirs), _programs(ours)
     assert a["main"] == b["main"] and a["tail"] == b["tail"] and a["fits"] == b["fits"] and a["consts"] == b["consts"]
+    assert a["walks"] == b["walks"] and a["handover"] == b["handover"] and a["in"] == b["in"] and a["alias"] == b["alias"]
     assert len(a["stages"]) == len(b["stages"])
     for sa, sb in zip(a["stages"], b["stages"]):
         assert sa == sb, sa[0]
