@@ -171,18 +171,15 @@ def test_the_references_parameter_values_all_34_outputs():
     assert (out["tp_01"] <= out["tp_10"]).all() and (out["tp_80"] <= out["tp_95"]).all() and not np.isnan(out["tp_01"]).any()
 
 
-def test_index_outputs_are_bit_exact_on_the_devices_own_waveforms():
-    """SURVEY H5 made checkable: every index / threshold / pick-off / extremum output of the recipe is recomputed by the ORACLE from the
-    DEVICE's own intermediate waveforms and per-event values (requested as extra outputs, a few at a time: they all live in LDS) and must
-    agree bit for bit in 100 % of the rows.  Whatever differs end to end can then only come from the <= 1e-6 differences of the filtered
-    waveforms themselves, which are asserted beside it; and the production program (no extra outputs, fused ops) must print the same
-    numbers as the instrumented ones."""
+def _index_outputs_on_the_devices_own_waveforms(wf, bl, t0_ns, dt=16.0):
+    """recipes.ICPC on these rows: every index / threshold / pick-off / extremum output recomputed by the ORACLE from the DEVICE's own
+    intermediate waveforms and per-event values (requested as extra outputs, a few at a time: they all live in LDS), asserted bit for bit in
+    every row (NaN == NaN); the production program (no extra outputs, fused ops) must print the same numbers as the instrumented ones.
+    Returns the production outputs, the seven intermediate filtered waveforms paired with the oracle's own (device, oracle), and the
+    instrumented program's three moving averages paired with the oracle's on the device's window: for the caller to hold to its bars."""
     from dspeed_amd.processing_chain import WaveformInput, build_processing_chain
 
-    rng = np.random.default_rng(2027)
-    n, dt = 96, 16.0
-    wf, bl = _synth(rng, n)
-    t0_ns = (rng.integers(2900, 3100, n) * 16).astype(F)
+    n = len(wf)
     tb = {"waveform": WaveformInput(wf, dt, t0_ns), "baseline": bl}
     off = _convert(t0_ns, 0.0, 0.0, 1.0 / dt)
     to_ns = lambda t: _convert(t, off.astype(np.float64), 0.0, dt)  # noqa: E731
@@ -257,7 +254,7 @@ def test_index_outputs_are_bit_exact_on_the_devices_own_waveforms():
     # (the instrumented one, which keeps curr_av) they replay the reference's rounding, 1e-6 of the peak ...
     up = oracle.upsampler(oracle.avg_current(oracle.windower(g["wf_pz"], tp0, 301)[0], 1)[0], 16, 4784)[0]
     av = oracle.moving_window_multi(up, 48, 3, 0)[0]
-    assert np.max(np.nanmax(np.abs(g["curr_av"] - av), axis=1) / np.nanmax(np.abs(av), axis=1)) <= 1e-6
+    curr_av_pair = (g["curr_av"], av)
     # ... and the production recipe runs the branch on the lane-per-waveform kernel (dsp_current.hip), which walks the reference's loops
     # themselves: its outputs are the ORACLE's on the device's pole-zero rows and start time, bit for bit
     _, ta_x, _, amax_x, _ = oracle.min_max(av)
@@ -282,6 +279,23 @@ def test_index_outputs_are_bit_exact_on_the_devices_own_waveforms():
              "wf_atrap": (atrap_dev, oracle.asym_trap_filter(o_pz, 8, 4, 125)[0]), "wf_trap": (trap_dev, oracle.trap_norm(o_pz, 625, 188)[0]),
              "wf_etrap": (etrap_dev, oracle.trap_norm(o_pz, 500, 125)[0]), "wf_trap2": (trap2_dev, oracle.trap_norm(o_pz, 250, 6)[0]),
              "wf_cusp": (cusp_dev, oracle.convolve_wf(o_bl, kc, "v", 301, in_len=8192 - 2100)[0])}
+    return {"prod": prod, "pairs": pairs, "curr_av": curr_av_pair}
+
+
+def test_index_outputs_are_bit_exact_on_the_devices_own_waveforms():
+    """SURVEY H5 made checkable: every index / threshold / pick-off / extremum output of the recipe is recomputed by the ORACLE from the
+    DEVICE's own intermediate waveforms and per-event values (requested as extra outputs, a few at a time: they all live in LDS) and must
+    agree bit for bit in 100 % of the rows.  Whatever differs end to end can then only come from the <= 1e-6 differences of the filtered
+    waveforms themselves, which are asserted beside it; and the production program (no extra outputs, fused ops) must print the same
+    numbers as the instrumented ones."""
+    rng = np.random.default_rng(2027)
+    n, dt = 96, 16.0
+    wf, bl = _synth(rng, n)
+    t0_ns = (rng.integers(2900, 3100, n) * 16).astype(F)
+    res = _index_outputs_on_the_devices_own_waveforms(wf, bl, t0_ns, dt)
+    prod, pairs = res["prod"], res["pairs"]
+    curr_av, av = res["curr_av"]
+    assert np.max(np.nanmax(np.abs(curr_av - av), axis=1) / np.nanmax(np.abs(av), axis=1)) <= 1e-6
     worst = {}
     for k, (got, want) in pairs.items():
         worst[k] = float(np.max(np.max(np.abs(got - want), axis=1) / np.max(np.abs(want), axis=1)))
