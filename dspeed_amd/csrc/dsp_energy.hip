@@ -6,16 +6,19 @@
 // shape.  One wavefront per waveform, lane j owns a chunk of consecutive samples, the next waveform's 16 KB are already in
 // flight (16-byte global loads into registers) while the current one is filtered, and the trapezoid output is never stored
 // (only the picked-off samples are kept).  Two kernels:
-//   * dsp_energy_rr_kernel ("register resident", the default for 1024/2048/4096 samples): pad-free LDS image (sample i at
-//     element i, C = len/64 + 1 samples per lane: an odd lane stride, so every "offset t of my chunk" access is
-//     conflict-free), every pass over the chunk fully unrolled (immediate LDS offsets, counted waits), the lane's own chunk
-//     in VGPRs from the staging to the end of the replay.  Per sample the LDS sees 2 writes (staging, pole-zero output) and
-//     4 reads (own chunk once, three lagged trapezoid streams).
+//   * dsp_energy_rr_kernel ("register resident", the default for 1024 .. 8192 samples): pad-free LDS image (sample i at
+//     element i, C = len/64 + 2 samples per lane: an even lane stride, so every lane's chunk starts 8-byte aligned and
+//     "offsets t, t + 1 of my chunk" is one conflict-free 8-byte access), every pass over the chunk fully unrolled (immediate
+//     LDS offsets, counted waits), the lane's own chunk in VGPRs from the staging to the end of the replay.  Per sample the
+//     LDS sees 2 writes (staging, pole-zero output) and 4 reads (own chunk once, three lagged trapezoid streams), the reads
+//     and the pole-zero output 8 bytes a lane at a time.
 //   * dsp_energy_kernel ("classic"): the VM's slot layout (C = len/64, pitch C + 1, zero guard of 2 pitches below the slot),
 //     chunk loops software-pipelined in groups of 8 samples.  Bit-identical to the VM; kept as the cross-check of the
 //     default kernel and for A/B measurements (set_fused(15)).
 // Reference bodies: processors/bl_subtract.py:11-46, pole_zero.py:24-77, trap_filters.py:12-227, fixed_time_pickoff.py:12-125.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "dsp_program.h"
 #include "dsp_wave.h"
@@ -67,6 +70,14 @@ struct EnergyArgs {
 constexpr int rr_prio_after_phase[6] = {1, 2, 3, 3, 3, 0};  // priority of the phase that FOLLOWS boundary n (5: the next row's staging)
 #define RR_PRIO_AT(n) __builtin_amdgcn_s_setprio(rr_prio_after_phase[n]);
 
+// Two 8-byte LDS accesses of one lane are otherwise merged into one ds_read2_b64 / ds_write2_b64, which the LDS serves at the rate of the
+// 4-byte forms (8 array cycles for 16 bytes a lane; ds_read_b64: 2 cycles for 8).  An instruction with side effects between them, itself
+// nothing, ends the merge.  The "memory" clobber is a full compiler barrier for memory: besides ending the merge it keeps every LDS and
+// global access, related or not, on its side of the macro (about 150 places per row, all inside passes that are ordered by their data
+// anyway; the prefetch and the result store sit between sched_barriers of their own).  It emits no instruction and no wait.  The build
+// counts the fused forms in the rr kernels' code and fails if any appear (RR_NO_FUSED_LDS in build.py).
+#define RR_NO_MERGE() asm volatile("" ::: "memory")
+
 namespace {
 
 constexpr int G = 8;   // samples per software-pipeline group in the pole-zero passes
@@ -86,6 +97,9 @@ __device__ __forceinline__ unsigned long long stamp() {
         tsum[i] += now_ - tlast;                   \
         tlast = now_;                              \
     }
+
+// first pair that stage st of the replay loads of a lagged stream with parity par (dsp_energy_rr_kernel), np = pairs the sub-chain needs
+constexpr int rr_pair_lo(int st, int par, int np) { return st == 0 ? 0 : (2 * st + par < np ? 2 * st + par : np); }
 
 template <int N>
 __device__ __forceinline__ void load_group(float (&v)[N], const float* p) {
@@ -350,7 +364,7 @@ __global__ void __launch_bounds__(256, 2) dsp_energy_kernel(EnergyArgs A, int64_
 }
 
 // ------------------------------------------------------------------------------------------------
-// Capture plan of the pad-free layout (C = len/64 + 1 samples per lane, sample i at LDS element i): for lag k and replay
+// Capture plan of the pad-free layout (C = len/64 + 2 samples per lane, sample i at LDS element i): for lag k and replay
 // sub-chain s the speculative carry needs the prefix sum `local` samples into sub-chain `cs` of the lane `shift` below.
 // Row-invariant, built by the host (dsp_host.cpp).
 // ------------------------------------------------------------------------------------------------
@@ -376,6 +390,19 @@ struct EnergyPlan {
 //     group end and the replay state at each group start go to a 9-entry per-lane LDS side array (a run-time group number is
 //     then an address); the two trapezoid samples every pick-off mode needs are copied out of a 16-sample register window
 //     by one uniform branch per 16 samples (a not-taken branch costs tens of cycles; 32 of them cost more than they saved).
+//   * the LDS array serves a ds_read_b64 in 2 cycles and a ds_read2_b32 -- the same 8 bytes a lane -- in 4, and the array was busy
+//     two thirds of the kernel's time.  So the lane pitch is even, C = len/64 + 2: every lane's chunk starts 8-byte aligned, the
+//     chunk is NG = (C - 2) / 8 groups of 8 samples and a two-sample tail (the tail extends the last replay chain; where the
+//     passes speak of "group NG" they mean it), the 64 C - len = 128 virtual samples above len are cleared with every staging,
+//     and lanes past (len - 1) / C filter zeros.  The own chunk is read as C / 2 pairs, pass 2 stores its output as pairs (4-byte
+//     stores at an even pitch put two lanes on one bank), the capture reads are pairs.  A lagged window starts at element
+//     lane C - lag: aligned when the lag is even; when it is odd the aligned pairs start one element lower and step t takes
+//     element t + 1 of them.  Which register that is, is a compile-time matter once the lag's parity is: the replay is a generic
+//     lambda over the three parities, instantiated per case (4 for trap_filter / trap_norm, whose third lag 2 rise + flat has the
+//     parity of the other two's sum; 8 for asym_trap) and selected by one wave-uniform switch per row -- a wavefront runs one copy for
+//     the whole launch.  The compiler would fuse neighbouring 8-byte accesses into ds_read2_b64 / ds_write2_b64, which the LDS
+//     serves at the 4-byte rate again: RR_NO_MERGE keeps them apart.  The 8-sample re-run of the 4-point pick-off mode reads
+//     4 bytes at a run-time position and needs no parity case.  Figures: profiles/r05_headline_lds.md.
 // S = sub-chains of the replay per lane: 2 halves the dependent-add chain but doubles the carry captures; measured slower.
 // ------------------------------------------------------------------------------------------------
 // IN: waveform element type in HBM: 0 float32, 1 int16, 2 uint16 (digitiser samples; widened to float32 while staging, exactly
@@ -387,9 +414,12 @@ __device__ __attribute__((noinline)) double rr_decay(double tau) { return exp(-1
 template <int NPF, int KIND, int S, int IN, bool TAU = false>
 __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(EnergyArgs A, EnergyPlan PL, int64_t n_wf, int* err) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int C = 4 * NPF + 1, len = 256 * NPF, NG = (C - 1) / 8, CS = (C - 1) / S, NGS = CS / 8;
+    // a chunk = NG groups of 8 samples (S sub-chains of NGS groups) and a two-sample tail that extends the last sub-chain
+    constexpr int C = 4 * NPF + 2, len = 256 * NPF, NG = (C - 2) / 8, CS = (C - 2) / S, NGS = CS / 8;
     constexpr int BS = CS >= 16 ? 16 : CS;  // samples per capture block
-    static_assert((C - 1) % (8 * S) == 0, "sub-chain length must be a whole number of 8-sample groups");
+    static_assert((C - 2) % (8 * S) == 0, "sub-chain length must be a whole number of 8-sample groups");
+    static_assert(C % 2 == 0 && 64 * C - len == 128, "even pitch: 8-byte aligned lane chunks, two rows of virtual samples above len");
+    typedef float f2 __attribute__((ext_vector_type(2)));
     const int lane = lane_id();
     const double inv_rr = 1.0 / A.rr, inv_ll = 1.0 / A.ll;  // trap_norm / asym_trap divide by these counts every sample
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), wpb = (int)(blockDim.x >> 6);
@@ -398,16 +428,22 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
     wave_sync();
     float* slot = lds + A.slot_off;
     float* mine = slot + lane * C;
+    f2* mine2 = reinterpret_cast<f2*>(mine);  // (the wave's region, slot_off and lane * C are all even numbers of elements)
     // per-lane side array (pitch 9, odd): group-end prefix sums of pass 2, later the group-start states of the replay.  Kept in
     // LDS so that "the value of group gi" with a run-time gi is an address, not a register select chain
     constexpr int AUXP = NG + 1 <= 9 ? 9 : ((NG + 1) | 1);  // (9 for up to 4096 samples, 17 for 8192; the host sizes the region the same way)
     static_assert(NG + 1 <= AUXP && S * NGS + 1 <= AUXP && (AUXP & 1) == 1, "side array too small");
     float* aux = slot + 64 * C + 16 + lane * AUXP;
-    const float* lagp[3];
+    // the lagged window of the lane starts at element lane*C - lag: 8-byte aligned for an even lag; for an odd one the aligned pairs
+    // start one element lower and step t takes element t + 1 of them.  lagb[] is that aligned start (windows wholly below sample 0
+    // read the zero guard, whatever the parity), lagpar[] the wave-uniform, row-invariant parity of each lag
+    const float* lagb[3];
+    int lagpar[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int pos0 = lane * C - A.q[k];  // q[] carries the lags
-        lagp[k] = (pos0 >= -C) ? slot + pos0 : slot - (2 * C + 8);
+        lagpar[k] = A.q[k] & 1;                           // q[] carries the lags
+        const int pos0 = lane * C - A.q[k] - lagpar[k];  // >= -C - 1: inside the guard
+        lagb[k] = (pos0 + lagpar[k] >= -C) ? slot + pos0 : slot - (2 * C + 8);
     }
 
     const int64_t stride_rows = (int64_t)gridDim.x * wpb;
@@ -470,7 +506,8 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 *reinterpret_cast<f4*>(slot + (b * 64 + lane) * 8 + 4) = hi - pf_bl;
             }
         }
-        slot[len + lane] = 0.0f;  // virtual samples above len
+        // the 64*C - len = 128 virtual samples above len, every row: pass 2 left the decaying pole-zero tail of the last row in them
+        reinterpret_cast<f2*>(slot + len)[lane] = f2{0.0f, 0.0f};
         const float t_in = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pf_tp)));
         const int64_t next = row + stride_rows;
         __builtin_amdgcn_sched_barrier(0);
@@ -485,11 +522,16 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
         // ---- the lane's chunk lives in registers from here to the end of the replay: x, then (in place) the pole-zero output
         float xr[C];
 #pragma unroll
-        for (int t = 0; t < C; ++t) xr[t] = mine[t];
+        for (int j = 0; j < C / 2; ++j) {  // 8 bytes per lane and read: lane bases are 8-byte aligned at the even pitch
+            const f2 v = mine2[j];
+            RR_NO_MERGE();
+            xr[2 * j] = v.x;
+            xr[2 * j + 1] = v.y;
+        }
         const float xprev = (lane > 0) ? mine[-1] : 0.0f;
         // ---- pass 1: float64 sum of x over the chunk
-        // (four partial sums: the float64 sum of 65 float32 samples is exact for one waveform's dynamic range, so the order is free,
-        // and one chain of dependent float64 adds would cost their full latency 65 times)
+        // (four partial sums: the float64 sum of 66 float32 samples is exact for one waveform's dynamic range, so the order is free,
+        // and one chain of dependent float64 adds would cost their full latency 66 times)
         double Xp[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int t = 0; t < C; ++t) {
@@ -530,7 +572,11 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 acc += __builtin_fma(-c, xp, x);
                 const float y = (float)acc;
                 xr[t] = y;
-                mine[t] = y;  // other lanes read it with a lag
+                // other lanes read it with a lag; stored as pairs: 4-byte stores at the even pitch land two lanes on one bank
+                if (t & 1) {
+                    mine2[t >> 1] = f2{xr[t - 1], y};
+                    RR_NO_MERGE();
+                }
                 xp = x;
                 run += y;
                 if ((t & 7) == 7) aux[t >> 3] = run;
@@ -563,12 +609,17 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                         // row loop and the kernel drowns in spilled SGPR pairs
                         asm volatile("" : "+s"(r));
                         const int gi = (r > 0 ? r - 1 : 0) >> 3;  // group that contains sample r-1
-                        pn[k] = r - 8 * gi;                        // 0..8 samples of group gi (gi == NG: the odd sample)
+                        pn[k] = r - 8 * gi;                        // 0..8 samples of group gi (gi == NG: the first sample of the two-sample tail)
                         const float b = aux[gi > 0 ? gi - 1 : 0];
                         pbase[k] = gi > 0 ? b : 0.0f;
-                        const float* p = mine + 8 * gi;
+                        const f2* p = mine2 + 4 * gi;
 #pragma unroll
-                        for (int u = 0; u < 8; ++u) pv[k][u] = p[u];  // (reads at most 7 past the chunk: inside the slot tail)
+                        for (int u = 0; u < 4; ++u) {  // (reads at most 6 past the chunk: inside the slot tail)
+                            const f2 v = p[u];
+                            RR_NO_MERGE();
+                            pv[k][2 * u] = v.x;
+                            pv[k][2 * u + 1] = v.y;
+                        }
                     }
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
@@ -590,7 +641,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 }
                 PHASE(3)
         RR_PRIO_AT(3)
-                // ---- pass 3: replay; own samples from registers, the three lagged streams software-pipelined one 8-sample group ahead
+                // ---- pass 3: replay; own samples from registers, the three lagged streams software-pipelined PD stages of GL = 4 samples ahead
                 wave_sync();  // the prefix sums in aux are consumed; aux now receives the replay state at every group start
                 // the two samples every pick-off mode needs (floor and ceil of the time point) are caught on the fly: stage numbers
                 const int i0 = (int)t_in;
@@ -601,68 +652,113 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                     const bool ok = e >= 0 && e < len;
                     caplane[k] = ok ? e / C : 0;
                     capoff[k] = ok ? e - caplane[k] * C : 0;
-                    capst[k] = ok ? capoff[k] / BS : -1;  // capture block of the chunk; block (C-1)/BS (never reached) = the odd sample
+                    capst[k] = ok ? capoff[k] / BS : -1;  // capture block of the chunk; block (C-2)/BS (never reached) = the two-sample tail
                 }
                 // one test per BS samples (a not-taken branch still costs tens of cycles): bit q set = block q holds a wanted sample
                 int capmask = (capst[0] >= 0 ? 1 << capst[0] : 0) | (capst[1] >= 0 ? 1 << capst[1] : 0);
                 asm volatile("" : "+s"(capmask));  // one live scalar, not a recomputation at each test
                 float* capbuf = slot + 64 * C + 16 + 64 * AUXP;  // 2 x 16 floats per wavefront, written by the lane that owns the sample
-                float ysb[S][BS];
-                constexpr int GL = 4, NL = CS / GL;  // samples per pipeline stage of the lagged streams (registers: 2 x S x 3 x GL)
-                constexpr int PD = S == 1 ? 2 : 1;  // stages the lagged loads run ahead of their use (lgkmcnt counts to 15: 6*S reads per stage)
-                float lb[PD + 1][S][GL][3], lodd[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int p = 0; p < PD; ++p)
-#pragma unroll
-                    for (int s = 0; s < S; ++s)
-#pragma unroll
-                        for (int u = 0; u < GL; ++u)
-#pragma unroll
-                            for (int k = 0; k < 3; ++k) lb[p][s][u][k] = lagp[k][s * CS + p * GL + u];
-#pragma unroll
-                for (int gl = 0; gl < NL; ++gl) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (gl + PD < NL) {
+                float ytail[2];  // the replay's output at the two samples of the tail
+                // The lagged streams are read as aligned 8-byte pairs.  With the parity par[k] of lag k a compile-time constant, "element
+                // t + par[k] of the pair sequence" names a register in this straight-line code: one copy of the replay per parity case,
+                // chosen by one uniform switch per row (a wavefront runs the same copy for the whole launch).
+                auto replay = [&](auto p0, auto p1, auto p2) __attribute__((always_inline)) {
+                    constexpr int par[3] = {decltype(p0)::value, decltype(p1)::value, decltype(p2)::value};
+                    constexpr int GL = 4, NL = CS / GL;  // samples per pipeline stage of the lagged streams
+                    // stages the lagged loads run ahead of their use (lgkmcnt counts to 15: 6*S reads per stage).  8192 samples: one stage; its 130
+                    // samples a lane leave no registers for a second stage of pairs in flight, the compiler parks values in AGPRs and copies
+                    // them back inside the dependent chain (profiles/r05_headline_lds.md, "8192 samples: one stage ahead or two", has both measured)
+                    constexpr int PD = S == 1 && NPF < 32 ? 2 : 1;
+                    constexpr int NPS = CS / 2 + 2;      // pairs a sub-chain can need: CS / 2, one more for an odd lag, one more for the tail
+                    f2 lp[3][S][NPS];
+                    const f2* lagb2[3] = {reinterpret_cast<const f2*>(lagb[0]), reinterpret_cast<const f2*>(lagb[1]), reinterpret_cast<const f2*>(lagb[2])};
+                    float ysb[S][BS];
+                    // stage st of sub-chain s consumes elements 4 st + par .. 4 st + 3 + par: an odd lag's stage ends in the first half of the
+                    // pair after it, so its loads are the pairs [rr_pair_lo(st), rr_pair_lo(st + 1)) -- two per stage and stream either way, the
+                    // first stage one more, stage NL (the tail, last sub-chain only) the one pair that is left
+                    auto load_stage = [&](int st) __attribute__((always_inline)) {
 #pragma unroll
                         for (int s = 0; s < S; ++s)
 #pragma unroll
-                            for (int u = 0; u < GL; ++u)
+                            for (int jj = 0; jj < 3; ++jj)
 #pragma unroll
-                                for (int k = 0; k < 3; ++k) lb[(gl + PD) % (PD + 1)][s][u][k] = lagp[k][s * CS + (gl + PD) * GL + u];
-                    } else if (gl + PD == NL) {
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) lodd[k] = lagp[k][C - 1];
-                    }
-                    if ((gl * GL) % 8 == 0) {
-#pragma unroll
-                        for (int s = 0; s < S; ++s) aux[s * NGS + (gl * GL) / 8] = y[s];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);  // the reads just issued are younger than the stage consumed next: a counted wait
-#pragma unroll
-                    for (int u = 0; u < GL; ++u)
-#pragma unroll
-                        for (int s = 0; s < S; ++s) {
-                            y[s] = trap_step_r<float, KIND>(y[s], xr[s * CS + gl * GL + u], lb[gl % (PD + 1)][s][u][0], lb[gl % (PD + 1)][s][u][1],
-                                                          lb[gl % (PD + 1)][s][u][2], A.rr, A.ll, inv_rr, inv_ll);
-                            ysb[s][(gl * GL + u) % BS] = y[s];
-                        }
-                    if (((gl + 1) * GL) % BS == 0) {
-#pragma unroll
-                        for (int s = 0; s < S; ++s) {
-                            const int q = s * (CS / BS) + (gl * GL) / BS;
-                            if (capmask & (1 << q)) {  // uniform, taken at most twice per waveform
-#pragma unroll
-                                for (int k = 0; k < 2; ++k)
-                                    if (capst[k] == q && lane == caplane[k]) {
-#pragma unroll
-                                        for (int u = 0; u < BS; ++u) capbuf[k * 16 + u] = ysb[s][u];
+                                for (int k = 0; k < 3; ++k) {
+                                    const int np = (CS + (s == S - 1 ? 2 : 0) + par[k] + 1) / 2;  // pairs sub-chain s needs of stream k
+                                    const int j = rr_pair_lo(st, par[k], np) + jj;
+                                    if (j < rr_pair_lo(st + 1, par[k], np)) {
+                                        lp[k][s][j] = lagb2[k][s * (CS / 2) + j];
+                                        RR_NO_MERGE();
                                     }
+                                }
+                    };
+                    auto lagged = [&](int k, int s, int t) __attribute__((always_inline)) { return lp[k][s][(t + par[k]) >> 1][(t + par[k]) & 1]; };
+#pragma unroll
+                    for (int st = 0; st < PD; ++st) load_stage(st);
+#pragma unroll
+                    for (int gl = 0; gl < NL; ++gl) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        load_stage(gl + PD);  // (nothing past stage NL)
+                        if ((gl * GL) % 8 == 0) {
+#pragma unroll
+                            for (int s = 0; s < S; ++s) aux[s * NGS + (gl * GL) / 8] = y[s];
+                        }
+                        __builtin_amdgcn_sched_barrier(0);  // the reads just issued are younger than the stage consumed next: a counted wait
+#pragma unroll
+                        for (int u = 0; u < GL; ++u)
+#pragma unroll
+                            for (int s = 0; s < S; ++s) {
+                                const int t = gl * GL + u;
+                                y[s] = trap_step_r<float, KIND>(y[s], xr[s * CS + t], lagged(0, s, t), lagged(1, s, t), lagged(2, s, t), A.rr, A.ll, inv_rr, inv_ll);
+                                ysb[s][t % BS] = y[s];
+                            }
+                        if (((gl + 1) * GL) % BS == 0) {
+#pragma unroll
+                            for (int s = 0; s < S; ++s) {
+                                const int q = s * (CS / BS) + (gl * GL) / BS;
+                                if (capmask & (1 << q)) {  // uniform, taken at most twice per waveform
+#pragma unroll
+                                    for (int k = 0; k < 2; ++k)
+                                        if (capst[k] == q && lane == caplane[k]) {
+#pragma unroll
+                                            for (int u = 0; u < BS; ++u) capbuf[k * 16 + u] = ysb[s][u];
+                                        }
+                                }
                             }
                         }
                     }
+                    aux[S * NGS] = y[S - 1];  // state before the two-sample tail (it extends the last chain)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        y[S - 1] = trap_step_r<float, KIND>(y[S - 1], xr[C - 2 + u], lagged(0, S - 1, CS + u), lagged(1, S - 1, CS + u), lagged(2, S - 1, CS + u),
+                                                          A.rr, A.ll, inv_rr, inv_ll);
+                        ytail[u] = y[S - 1];
+                    }
+                };
+                {
+                    typedef std::integral_constant<int, 0> E;  // even lag
+                    typedef std::integral_constant<int, 1> O;  // odd lag
+                    // trap_filter / trap_norm: the lags are rise, rise + flat, 2 rise + flat, so the third parity is the sum of the other two and
+                    // four cases exist; asym_trap's fall time makes the third lag's parity free
+                    if constexpr (KIND == TRAP_ASYM) {
+                        switch (lagpar[0] | (lagpar[1] << 1) | (lagpar[2] << 2)) {
+                            case 0: replay(E{}, E{}, E{}); break;
+                            case 1: replay(O{}, E{}, E{}); break;
+                            case 2: replay(E{}, O{}, E{}); break;
+                            case 3: replay(O{}, O{}, E{}); break;
+                            case 4: replay(E{}, E{}, O{}); break;
+                            case 5: replay(O{}, E{}, O{}); break;
+                            case 6: replay(E{}, O{}, O{}); break;
+                            default: replay(O{}, O{}, O{}); break;
+                        }
+                    } else {
+                        switch (lagpar[0] | (lagpar[1] << 1)) {
+                            case 0: replay(E{}, E{}, E{}); break;
+                            case 1: replay(O{}, E{}, O{}); break;
+                            case 2: replay(E{}, O{}, O{}); break;
+                            default: replay(O{}, O{}, E{}); break;
+                        }
+                    }
                 }
-                aux[S * NGS] = y[S - 1];  // state before the odd sample (it extends the last chain)
-                y[S - 1] = trap_step_r<float, KIND>(y[S - 1], xr[C - 1], lodd[0], lodd[1], lodd[2], A.rr, A.ll, inv_rr, inv_ll);
                 PHASE(4)
         RR_PRIO_AT(4)
                 // ---- true carries: exact scan of the increments
@@ -679,8 +775,8 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 float w4[4];
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    float v = capbuf[k * 16 + (capoff[k] % BS)];  // (stale when the sample is the odd one or out of range: not used then)
-                    v = capoff[k] == C - 1 ? y[S - 1] : v;
+                    float v = capbuf[k * 16 + (capoff[k] % BS)];  // (stale when the sample is in the tail or out of range: not used then)
+                    v = capoff[k] >= C - 2 ? (capoff[k] == C - 2 ? ytail[0] : ytail[1]) : v;
                     double delta = T0 - (double)g[0];
 #pragma unroll
                     for (int s = 1; s < S; ++s)
@@ -697,7 +793,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                         const int l = e / C, off = e - l * C;
                         int ch = off / CS;
                         if (ch > S - 1) ch = S - 1;
-                        const int loc = off - ch * CS;  // 0..CS (CS: the odd sample, chain S-1 only)
+                        const int loc = off - ch * CS;  // 0..CS+1 (CS, CS+1: the two-sample tail, chain S-1 only)
                         const int gi = loc >> 3, u0 = loc & 7;
                         float ys = aux[ch * NGS + gi], gsel = 0.0f;  // (chain S-1, group NGS) -> aux[S*NGS]
                         double dsel = 0.0;
@@ -711,8 +807,11 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                         float yk = ys;
 #pragma unroll
                         for (int u = 0; u < 8; ++u) {
-                            const int tt = base + u;  // (beyond the chunk for the odd sample's group: reads stay in the slot tail, unused)
-                            ys = trap_step_r<float, KIND>(ys, mine[tt], lagp[0][tt], lagp[1][tt], lagp[2][tt], A.rr, A.ll, inv_rr, inv_ll);
+                            const int tt = base + u;  // (beyond the chunk for the tail's group: reads stay in the slot tail, unused)
+                            // (4-byte reads at a run-time position: no parity case needed, and the 4-point mode alone comes here.  At the even
+                            // pitch they put two lanes on a bank, (2 lane + tt) mod 32: twice the array cycles, for 32 reads at most twice a row)
+                            ys = trap_step_r<float, KIND>(ys, mine[tt], lagb[0][tt + lagpar[0]], lagb[1][tt + lagpar[1]], lagb[2][tt + lagpar[2]], A.rr, A.ll,
+                                                          inv_rr, inv_ll);
                             if (u == u0) yk = ys;
                         }
                         const double delta = (T0 + dsel) - (double)gsel;
@@ -744,7 +843,7 @@ int launch_rr_kind(const EnergyArgs& A, const EnergyPlan& PL, int npf, int64_t n
         case 4: hipLaunchKernelGGL((dsp_energy_rr_kernel<4, KIND, S, IN, TAU>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
         case 8: hipLaunchKernelGGL((dsp_energy_rr_kernel<8, KIND, S, IN, TAU>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
         case 16: hipLaunchKernelGGL((dsp_energy_rr_kernel<16, KIND, S, IN, TAU>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
-        case 32:  // 8192 samples (production LEGEND rows): 129 samples per lane, one wavefront per SIMD (512-register budget, 36 KB of LDS)
+        case 32:  // 8192 samples (production LEGEND rows): 130 samples per lane, one wavefront per SIMD (512-register budget, 38.9 KB of LDS)
             if (S != 1) return (int)hipErrorInvalidValue;
             hipLaunchKernelGGL((dsp_energy_rr_kernel<32, KIND, 1, IN, TAU>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err);
             break;

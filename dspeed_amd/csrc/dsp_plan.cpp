@@ -1437,17 +1437,18 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
             ch->wf_dtype = wdt;
             const char* env = getenv("DSPEED_HIP_NO_FUSED");
             ch->fused_on = !(env && env[0] == '1');
-            {  // register-resident kernel: C = len/64 + 1 samples per lane, linear LDS image of the waveform (1024 .. 8192 samples)
+            {  // register-resident kernel: C = len/64 + 2 samples per lane (an even pitch: every lane's chunk is 8-byte aligned), linear LDS
+               // image of the waveform (1024 .. 8192 samples); a chunk is (C - 2) / 8 groups of 8 samples and a two-sample tail
                 EnergyArgs& I = ch->rr;
                 I = F;
-                const int Ci = slot_len[0] / 64 + 1;
+                const int Ci = slot_len[0] / 64 + 2;
                 I.C = Ci;
                 I.pitch = Ci;
                 I.invC = 1.0f / (float)Ci;
-                int guard = 2 * Ci + 8;  // zeros below the image: lagged reads before sample 0
-                guard = ((guard + 3) / 4) * 4;
+                int guard = 2 * Ci + 8;  // zeros below the image: lagged reads before sample 0 (an odd lag's pairs start one element lower: covered)
+                guard = ((guard + 3) / 4) * 4;  // (the image stays 16-byte aligned)
                 I.slot_off = guard;
-                const int ng1 = (Ci - 1) / 8 + 1, auxp = ng1 <= 9 ? 9 : (ng1 | 1);
+                const int ng1 = (Ci - 2) / 8 + 1, auxp = ng1 <= 9 ? 9 : (ng1 | 1);
                 int elems = guard + 64 * Ci + 16 + 64 * auxp + 32;  // image, tail, per-lane side array (auxp per lane), capture buffer (2 x 16)
                 elems = ((elems + 3) / 4) * 4;
                 I.lds_elems_per_wave = elems;
@@ -1457,7 +1458,7 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
                     I.rho[k] = 0;
                 }
                 for (int S = 1; S <= 2; ++S) {
-                    const int CS = (Ci - 1) / S;
+                    const int CS = (Ci - 2) / S;
                     for (int k = 0; k < 3; ++k)
                         for (int sidx = 0; sidx < S; ++sidx) {
                             const int pos = sidx * CS - dtp.ic[k];          // samples before the sub-chain start, relative to the chunk
