@@ -1403,6 +1403,8 @@ int dsp_linear_slope_fit_rows(const void* wf, int wf_dtype, int64_t n_wf, int32_
         const dsp_fit_window& w = fits[k];
         if (w.stage < 0 || w.stage > 1 || (w.stage == 1 && !has_pz)) return fail(DSP_ERR_ARG, "fit rows: window %d: stage 1 is the pole-zero corrected waveform (has_pz)", k);
         if (w.first < 0 || w.count < 1 || (int64_t)w.first + w.count > wf_len) return fail(DSP_ERR_ARG, "fit rows: window %d is not inside the waveform", k);
+        // one sample: the line fit's denominator is 0 (linear_slope_fit.py raises ZeroDivisionError) -- refused as the in-chain op refuses it
+        if (w.count < 2) return fail(DSP_E_ZERODIV, "%s", dsp_fatal_message(DSP_E_ZERODIV));
         A.stage[k] = w.stage;
         A.first[k] = w.first;
         A.count[k] = w.count;

@@ -359,7 +359,9 @@ int dsp_chain_set_async_check(dsp_chain* chain, int enable);
  * does up to DSP_FIT_MAX fits on windows of the waveform as the recipes read it: after an optional per-row subtraction (sub_mode 1 =
  * bl_subtract.py:11-46 with its NaN rule, 2 = numpy.subtract; sub_dev a device column of sub_dtype or NULL = sub_const) -- stage 0 --
  * and after pole_zero (pole_zero.py:24-77, has_pz, constant pz_tau in samples) on that -- stage 1.  out: n_fits x 4 columns of n_wf
- * values of the compute type (mean, stdev, slope, intercept of fit 0, then fit 1 ...).  dspeed_amd's recipe builder moves eligible
+ * values of the compute type (mean, stdev, slope, intercept of fit 0, then fit 1 ...).  A window of fewer than 2 samples is refused
+ * with DSP_E_ZERODIV ("division by zero": the line fit's denominator, as the reference's ZeroDivisionError and the in-chain op) and
+ * nothing is launched.  dspeed_amd's recipe builder moves eligible
  * fits of a recipe here and feeds the columns to the chain as per-event inputs. */
 #define DSP_FIT_MAX 4
 typedef struct dsp_fit_window {
