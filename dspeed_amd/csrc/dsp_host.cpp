@@ -179,6 +179,18 @@ static hipError_t staged_d2h(void* host, const void* dev, size_t bytes) {
     return e;
 }
 
+// a kernel the chain is planned for that needs more dynamic LDS than a launch gets unasked is told so once, at chain creation
+// (`label`: what the error text names, with the bytes where it has a %d)
+template <typename Setter>
+static int raise_lds(bool planned, int bytes, int limit, const char* label, Setter set) {
+    if (!planned || bytes <= limit) return DSP_OK;
+    const hipError_t e = (hipError_t)set(bytes);
+    if (e == hipSuccess) return DSP_OK;
+    char what[64];
+    snprintf(what, sizeof what, label, bytes);
+    return fail(DSP_ERR_HIP, "hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------ device / memory
@@ -396,52 +408,45 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     HIP_TRY(staged_h2d(ch->dev, &P, ch->dev_bytes));
     HIP_TRY(hipMalloc((void**)&ch->dev_err, DSP_ERR_WORDS * sizeof(int)));
     HIP_TRY(hipMemset(ch->dev_err, 0, DSP_ERR_WORDS * sizeof(int)));
-    const int block_lds = ch->lds_bytes_per_wave * ch->waves_per_block;
-    if (block_lds > 64 * 1024) {
-        hipError_t e = (hipError_t)dsp_internal_set_vm_lds(block_lds);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d): %s", block_lds, hipGetErrorString(e));
-    }
-    const int classic_lds = ch->lds_bytes_per_wave * ch->classic_wpb;
-    if (ch->fused_ok && classic_lds > 64 * 1024) {
-        hipError_t e = (hipError_t)dsp_internal_set_energy_lds(ch->fused_trap, ch->fused_npf, classic_lds);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "hipFuncSetAttribute(energy kernel, %d): %s", classic_lds, hipGetErrorString(e));
-    }
-    if (ch->fir_f16 && dsp_internal_fir_f16_lds_bytes() > 64 * 1024) {
-        hipError_t e = (hipError_t)dsp_internal_set_fir_f16_lds(dsp_internal_fir_f16_lds_bytes());
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "hipFuncSetAttribute(float16 FIR kernel): %s", hipGetErrorString(e));
-    }
-    if (ch->fir_ok && ch->fir_lds_bytes > 64 * 1024) {
-        hipError_t e = (hipError_t)(ch->fir.store ? dsp_internal_set_fir_store_lds(ch->fir_lds_bytes) : dsp_internal_set_fir_mfma_lds(ch->fir_lds_bytes));
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "hipFuncSetAttribute(FIR kernel, %d): %s", ch->fir_lds_bytes, hipGetErrorString(e));
-    }
-    if (ch->scalar_ok && n_sregs * 64 * esz > 48 * 1024) {
-        hipError_t e = (hipError_t)dsp_internal_set_scalar_lds(n_sregs * 64 * esz);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "hipFuncSetAttribute(scalar kernel): %s", hipGetErrorString(e));
-    }
-    if (ch->cur_ok && ch->cur_lds_bytes > 64 * 1024) {
-        hipError_t e = (hipError_t)dsp_internal_set_current_lds(ch->cur_lds_bytes);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "hipFuncSetAttribute(current kernel, %d): %s", ch->cur_lds_bytes, hipGetErrorString(e));
-    }
-    if (ch->rows_ok && ch->rows_lds_bytes > 64 * 1024) {
-        hipError_t e = (hipError_t)dsp_internal_set_rows_lds(ch->rows_lds_bytes);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "hipFuncSetAttribute(rows kernel, %d): %s", ch->rows_lds_bytes, hipGetErrorString(e));
-    }
+    const int block_lds = ch->lds_bytes_per_wave * ch->waves_per_block, classic_lds = ch->lds_bytes_per_wave * ch->classic_wpb;
+    int rc = raise_lds(true, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
+    if (!rc) rc = raise_lds(ch->fused_ok, classic_lds, 64 * 1024, "energy kernel, %d", [&](int n) { return dsp_internal_set_energy_lds(ch->fused_trap, ch->fused_npf, n); });
+    if (!rc) rc = raise_lds(ch->fir_f16, dsp_internal_fir_f16_lds_bytes(), 64 * 1024, "float16 FIR kernel", dsp_internal_set_fir_f16_lds);
+    if (!rc) rc = raise_lds(ch->fir_ok, ch->fir_lds_bytes, 64 * 1024, "FIR kernel, %d", ch->fir.store ? dsp_internal_set_fir_store_lds : dsp_internal_set_fir_mfma_lds);
+    if (!rc) rc = raise_lds(ch->scalar_ok, n_sregs * 64 * esz, 48 * 1024, "scalar kernel", dsp_internal_set_scalar_lds);
+    if (!rc) rc = raise_lds(ch->cur_ok, ch->cur_lds_bytes, 64 * 1024, "current kernel, %d", dsp_internal_set_current_lds);
+    if (!rc) rc = raise_lds(ch->rows_ok, ch->rows_lds_bytes, 64 * 1024, "rows kernel, %d", dsp_internal_set_rows_lds);
+    if (rc) return rc;
     *out = ch.release();
     return DSP_OK;
 }
 
-// the lane-per-waveform kernel runs when the program has its shape and the row / coefficient buffers of this call keep 16-byte alignment
-static bool rows_applies(const dsp_chain* ch, void* const* io_ptrs) {
-    if (!ch->rows_ok || !ch->fused_on) return false;
-    if (reinterpret_cast<uintptr_t>(io_ptrs[ch->rio_wf]) & 15u) return false;
-    if (ch->rio_dwt >= 0 && ((reinterpret_cast<uintptr_t>(io_ptrs[ch->rio_dwt]) + 4u * (uintptr_t)ch->host.io[ch->rio_dwt].offset) & 15u)) return false;
-    return true;
+// a binding's first element: io_ptrs[k] + offset (the waveform input's offset travels in the kernels' arguments instead)
+static void* io_at(const dsp_chain* ch, void* const* io_ptrs, int k) {
+    return k < 0 ? nullptr : (void*)((char*)io_ptrs[k] + (int64_t)ch->host.io[k].offset * elem_size(ch->host.io[k].dtype));
 }
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-static bool fir_applies(const dsp_chain* ch, void* const* io_ptrs) {
-    if (!ch->fir_ok || !ch->fused_on) return false;
-    return (reinterpret_cast<uintptr_t>(io_ptrs[ch->fio_wf]) & 15u) == 0;
+// Does the kernel of a route run THIS launch?  The program has its shape, the specialised kernels are on, and the buffers of this call keep
+// the 16-byte alignment its wide loads need (the plan vouches for strides and offsets, nobody for the pointers).  dsp_chain_execute asks
+// in the order of dsp_plan_route; a launch whose planned route does not apply runs on the next that does.
+static bool scalar_applies(const dsp_chain* ch, void* const*) { return ch->scalar_ok && ch->fused_on; }
+static bool pz_rows_applies(const dsp_chain* ch, void* const* io_ptrs) {
+    return ch->pz_ok && ch->fused_on && aligned16(io_ptrs[ch->pio_wf]) && aligned16(io_at(ch, io_ptrs, ch->pio_out));
 }
+static bool reduce_applies(const dsp_chain* ch, void* const*) { return ch->red_ok && ch->fused_on; }  // (unaligned rows: its scalar loads)
+static bool fir_runs_applies(const dsp_chain* ch, void* const* io_ptrs) { return ch->runs_ok && ch->fused_on && aligned16(io_ptrs[ch->uio_wf]); }
+static bool current_applies(const dsp_chain* ch, void* const* io_ptrs) { return ch->cur_ok && ch->fused_on && aligned16(io_ptrs[ch->cio_wf]); }
+static bool fir_applies(const dsp_chain* ch, void* const* io_ptrs) { return ch->fir_ok && ch->fused_on && aligned16(io_ptrs[ch->fio_wf]); }
+// (the rows kernel: the rows and the coefficient buffer of its Haar transform)
+static bool rows_applies(const dsp_chain* ch, void* const* io_ptrs) {
+    if (!ch->rows_ok || !ch->fused_on || !aligned16(io_ptrs[ch->rio_wf])) return false;
+    return ch->rio_dwt < 0 || aligned16((const char*)io_ptrs[ch->rio_dwt] + 4u * (uintptr_t)ch->host.io[ch->rio_dwt].offset);
+}
+static bool energy_rr_applies(const dsp_chain* ch, void* const* io_ptrs) {
+    return ch->rr_ok && ch->fused_on && ch->variant != 1 && aligned16(io_ptrs[ch->io_wf]);
+}
+static bool energy_applies(const dsp_chain* ch, void* const* io_ptrs) { return ch->fused_ok && ch->fused_on && aligned16(io_ptrs[ch->io_wf]); }
 
 static int chain_blocks(const dsp_chain* ch, int64_t n_wf, int wpb, int cap_waves) {
     const int block_lds = ch->lds_bytes_per_wave * wpb;
@@ -561,6 +566,194 @@ int dsp_chain_share_row_scales(dsp_chain* producer, dsp_chain* consumer) {
     return 0;
 }
 
+// the outputs, pick-offs and walks of ReduceArgs: the reduce kernel's own and the ones the run-length FIR runs on its filtered rows
+static void bind_reductions(const dsp_chain* ch, void* const* io_ptrs, ReduceArgs& A) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    for (int k = 0; k < 5; ++k) A.out[k] = at(ch->dio_out[k]);
+    for (int k = 0; k < DSP_REDUCE_PICKS; ++k) A.pick_out[k] = at(ch->dio_pick[k]);
+    for (int k = 0; k < DSP_REDUCE_WALKS; ++k) {
+        A.walk_out[k] = at(ch->dio_walk[k]);
+        A.walk_thr[k] = (const float*)at(ch->dio_walk_thr[k]);
+        A.walk_ts[k] = (const float*)at(ch->dio_walk_ts[k]);
+    }
+}
+
+// ---- one launch per route: the kernel's argument block with the pointers of this call, its launch, the error word on its way to the host
+static int launched(dsp_chain* ch, void* stream, hipError_t e, const char* what) {
+    if (e != hipSuccess) return fail(DSP_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    return post_err(ch, stream);
+}
+
+static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
+    hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
+    return launched(ch, stream, e, "scalar kernel launch");
+}
+
+static int launch_pz_rows(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    PzArgs A = ch->pz;
+    A.wf = io_ptrs[ch->pio_wf];
+    A.bl = (const float*)at(ch->pio_bl);
+    A.out = at(ch->pio_out);
+    A.tau = (const float*)at(ch->pio_tau);
+    for (int k = 0; k < 4; ++k) A.mm_out[k] = at(ch->pio_mm[k]);
+    A.row_scale = nullptr;
+    A.row_flags = nullptr;
+    if (dsp_chain* sink = ch->scale_sink) {
+        const int rc = f16_rows_reserve(sink, n_wf);
+        if (rc != DSP_OK) return rc;
+        A.row_scale = (float*)const_cast<void*>(sink->f16.row_scale);
+        A.row_flags = (uint32_t*)const_cast<void*>(sink->f16.row_flags);
+        sink->fed_rows_ptr = A.out;
+        sink->fed_stream = stream;
+        sink->fed_n_wf = n_wf;
+        sink->fed_stride = A.out_stride;
+        sink->fed_len = A.len;
+    }
+    A.in_scale = nullptr;
+    A.in_flags = nullptr;
+    if (dsp_chain* sink = ch->scale_sink_in) {
+        const int rc = f16_rows_reserve(sink, n_wf);
+        if (rc != DSP_OK) return rc;
+        const int es = A.in_kind == 0 ? 4 : 2;
+        A.in_scale = (float*)const_cast<void*>(sink->f16.row_scale);
+        A.in_flags = (uint32_t*)const_cast<void*>(sink->f16.row_flags);
+        A.in_lo = sink->fir.wf_offset - A.wf_offset;
+        A.in_hi = A.in_lo + sink->fir.n;
+        sink->fed_rows_ptr = (const char*)A.wf + (size_t)sink->fir.wf_offset * es;  // the consumer's first sample, if it is bound to these rows
+        sink->fed_bl = A.bl;
+        sink->fed_stream = stream;
+        sink->fed_n_wf = n_wf;
+        sink->fed_stride = A.wf_stride;
+        sink->fed_len = sink->fir.n;
+    }
+    hipError_t e = (hipError_t)dsp_internal_launch_pz_rows(&A, n_wf, ch->dev_err, (hipStream_t)stream);
+    return launched(ch, stream, e, "pole-zero rows kernel launch");
+}
+
+static int launch_reduce(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    ReduceArgs A = ch->red;
+    A.wf = io_ptrs[ch->dio_wf];
+    bind_reductions(ch, io_ptrs, A);
+    const int vec = ch->red_vec && (reinterpret_cast<uintptr_t>(A.wf) & 15u) == 0;
+    hipError_t e = (hipError_t)dsp_internal_launch_reduce(&A, n_wf, ch->red_dtype, vec, ch->dev_err, (hipStream_t)stream);
+    return launched(ch, stream, e, "reduce kernel launch");
+}
+
+static int launch_fir_runs(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    if (!ch->runs_table) HIP_TRY(hipMalloc((void**)&ch->runs_table, sizeof(FirRunsTable)));
+    FirRunsArgs A = ch->runs;
+    if (!A.keep && !ch->runs_scratch)
+        HIP_TRY(hipMalloc((void**)&ch->runs_scratch, (size_t)runs_blocks_cap(ch) * 4 * (size_t)A.out_stride * sizeof(float)));
+    A.wf = (const float*)io_ptrs[ch->uio_wf];
+    A.taps = (const float*)at(ch->uio_taps);
+    A.out = A.keep ? (float*)at(ch->uio_out) : ch->runs_scratch;
+    A.table = ch->runs_table;
+    bind_reductions(ch, io_ptrs, A.red);
+    hipError_t e = (hipError_t)dsp_internal_launch_fir_runs(&A, ch->runs_table, n_wf, runs_blocks(ch, n_wf), ch->dev_err, (hipStream_t)stream);
+    return launched(ch, stream, e, "run-length FIR kernel launch");
+}
+
+static int launch_current(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    // persistent wavefronts, as many as a CU's LDS takes (at most 12 per CU): each keeps its scratch area for the groups of rows it walks
+    const int cap = current_blocks_cap(ch);
+    if (!ch->cur_scratch) {
+        HIP_TRY(hipMalloc((void**)&ch->cur_scratch, (size_t)cap * (size_t)ch->cur.scratch_per_wave * sizeof(float)));
+        ch->cur_blocks_cap = cap;
+    }
+    CurrentArgs A = ch->cur;
+    A.wf = io_ptrs[ch->cio_wf];
+    A.t0 = (const float*)at(ch->cio_t0);
+    for (int k = 0; k < 4; ++k) A.out[k] = at(ch->cio_out[k]);
+    A.scratch = ch->cur_scratch;
+    const int blocks = current_blocks(ch, n_wf);
+    hipError_t e = (hipError_t)dsp_internal_launch_current(&A, n_wf, blocks, ch->cur_lds_bytes, (hipStream_t)stream);
+    return launched(ch, stream, e, "current kernel launch");
+}
+
+static int launch_fir(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    FirArgs A = ch->fir;
+    A.wf = io_ptrs[ch->fio_wf];
+    A.bl = (const float*)at(ch->fio_bl);
+    for (int k = 0; k < A.n_kernels; ++k) {
+        A.taps[k] = (const float*)at(ch->fio_taps[k]);
+        A.out[k] = at(ch->fio_out[k]);
+    }
+    if (ch->fir_f16) {
+        const int rc = f16_rows_reserve(ch, n_wf);
+        if (rc != DSP_OK) return rc;
+        // scales and flags already there?  Only if the kernel in front wrote exactly the rows this one reads, and just now
+        const void* first = (const char*)A.wf + (size_t)A.wf_offset * (A.in_kind == 0 ? sizeof(float) : sizeof(int16_t));
+        // -- and on this stream: scales and flags are written by the producer's launch, so only stream order puts them ahead of this one
+        const bool same_batch = ch->scale_feeder && ch->fed_rows_ptr == first && ch->fed_n_wf == n_wf && ch->fed_stream == stream &&
+                                ch->fed_stride == A.wf_stride && ch->fed_len == A.n;
+        ch->f16.rows_done = (same_batch && (ch->fed_in_side ? (A.in_kind != 0 && A.sub_mode == 1 && ch->fed_bl == (const void*)A.bl && A.bl != nullptr)
+                                                            : (A.in_kind == 0 && A.sub_mode == 0))) ? 1 : 0;
+        ch->fed_n_wf = -1;  // (a note is good for one execute)
+    }
+    hipError_t e = (hipError_t)(ch->fir_f16 ? dsp_internal_launch_fir_f16(&A, &ch->f16, n_wf, dsp_internal_fir_f16_lds_bytes(), (hipStream_t)stream)
+                                : A.store   ? dsp_internal_launch_fir_store(&A, n_wf, ch->fir_lds_bytes, (hipStream_t)stream)
+                                            : dsp_internal_launch_fir_mfma(&A, n_wf, ch->fir_lds_bytes, (hipStream_t)stream));
+    return launched(ch, stream, e, "FIR kernel launch");
+}
+
+static int launch_rows(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    RowsArgs A = ch->rows;
+    A.wf = io_ptrs[ch->rio_wf];
+    A.bl = (const float*)at(ch->rio_bl);
+    A.thr = (const float*)at(ch->rio_thr);
+    A.ts = (const float*)at(ch->rio_ts);
+    for (int k = 0; k < 4; ++k) A.out_mm[k] = at(ch->rio_mm[k]);
+    A.out_tpt = at(ch->rio_tpt);
+    A.dwt_out = at(ch->rio_dwt);
+    hipError_t e = (hipError_t)dsp_internal_launch_rows(&A, n_wf, ch->dev_err, ch->rows_lds_bytes, (hipStream_t)stream);
+    return launched(ch, stream, e, "rows kernel launch");
+}
+
+static int launch_energy_rr(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    EnergyArgs F = ch->rr;
+    F.wf = io_ptrs[ch->io_wf];
+    F.bl = (const float*)at(ch->io_bl);
+    F.tp = (const float*)at(ch->io_tp);
+    F.tau = (const float*)at(ch->io_tau);
+    F.out = (float*)at(ch->io_out);
+    const int S = (ch->variant == 8 && ch->wf_dtype == DSP_F32) ? 2 : 1;
+    int rwpb, rblocks;
+    rr_geometry(ch, n_wf, &rwpb, &rblocks);
+    hipError_t e = (hipError_t)dsp_internal_launch_energy_rr(&F, &ch->plan[S - 1], ch->fused_trap, ch->fused_npf, S, ch->wf_dtype, n_wf,
+                                                             ch->dev_err, rblocks, 64 * rwpb, ch->rr_lds_bytes * rwpb, (hipStream_t)stream);
+    return launched(ch, stream, e, "energy kernel launch");
+}
+
+static int launch_energy(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    EnergyArgs F = ch->fused;
+    F.wf = io_ptrs[ch->io_wf];
+    F.bl = (const float*)at(ch->io_bl);
+    F.tp = (const float*)at(ch->io_tp);
+    F.out = (float*)at(ch->io_out);
+    const int cw = ch->classic_wpb;
+    hipError_t e = (hipError_t)dsp_internal_launch_energy(&F, ch->fused_trap, ch->fused_npf, n_wf, ch->dev_err, chain_blocks(ch, n_wf, cw, 8),
+                                                          64 * cw, ch->lds_bytes_per_wave * cw, (hipStream_t)stream);
+    return launched(ch, stream, e, "energy kernel launch");
+}
+
+static int launch_vm(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
+    const int blocks = vm_blocks(ch, n_wf);
+    const int threads = 64 * ch->waves_per_block;
+    const int lds = ch->lds_bytes_per_wave * ch->waves_per_block;
+    hipError_t e = ch->f64 ? (hipError_t)dsp_internal_launch_vm_f64(ch->dev, ptrs, n_wf, ch->dev_err, blocks, threads, lds, ch->has_fir,
+                                                                    (hipStream_t)stream)
+                           : (hipError_t)dsp_internal_launch_vm_f32(ch->dev, ptrs, n_wf, ch->dev_err, blocks, threads * ch->host.team, lds, ch->has_fir,
+                                                                    ch->host.team, (hipStream_t)stream);
+    return launched(ch, stream, e, "kernel launch");
+}
+
 int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
     if (!ch || !io_ptrs) return fail(DSP_ERR_ARG, "null chain or io_ptrs");
     if (n_wf <= 0) return DSP_OK;
@@ -572,183 +765,17 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     DeviceScope on_chain_device(ch->device);  // the chain's program and error word live there; the caller's current device comes back on return
     if (!on_chain_device.ok) return fail(DSP_ERR_HIP, "hipSetDevice(%d) failed", ch->device);
     (void)hipGetLastError();  // launch checks below report this launch, not a stale error of an unrelated earlier call
-    // a binding's first element: io_ptrs[k] + offset (the waveform input's offset travels in the kernels' arguments instead)
-    auto at = [&](int k) -> void* {
-        return k < 0 ? nullptr : (void*)((char*)io_ptrs[k] + (int64_t)ch->host.io[k].offset * elem_size(ch->host.io[k].dtype));
-    };
-    if (ch->scalar_ok && ch->fused_on) {
-        hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, &ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "scalar kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    if (ch->pz_ok && ch->fused_on && (reinterpret_cast<uintptr_t>(io_ptrs[ch->pio_wf]) & 15u) == 0 && (reinterpret_cast<uintptr_t>(at(ch->pio_out)) & 15u) == 0) {
-        PzArgs A = ch->pz;
-        A.wf = io_ptrs[ch->pio_wf];
-        A.bl = (const float*)at(ch->pio_bl);
-        A.out = at(ch->pio_out);
-        A.tau = (const float*)at(ch->pio_tau);
-        for (int k = 0; k < 4; ++k) A.mm_out[k] = at(ch->pio_mm[k]);
-        A.row_scale = nullptr;
-        A.row_flags = nullptr;
-        if (dsp_chain* sink = ch->scale_sink) {
-            const int rc = f16_rows_reserve(sink, n_wf);
-            if (rc != DSP_OK) return rc;
-            A.row_scale = (float*)const_cast<void*>(sink->f16.row_scale);
-            A.row_flags = (uint32_t*)const_cast<void*>(sink->f16.row_flags);
-            sink->fed_rows_ptr = A.out;
-            sink->fed_stream = stream;
-            sink->fed_n_wf = n_wf;
-            sink->fed_stride = A.out_stride;
-            sink->fed_len = A.len;
-        }
-        A.in_scale = nullptr;
-        A.in_flags = nullptr;
-        if (dsp_chain* sink = ch->scale_sink_in) {
-            const int rc = f16_rows_reserve(sink, n_wf);
-            if (rc != DSP_OK) return rc;
-            const int es = A.in_kind == 0 ? 4 : 2;
-            A.in_scale = (float*)const_cast<void*>(sink->f16.row_scale);
-            A.in_flags = (uint32_t*)const_cast<void*>(sink->f16.row_flags);
-            A.in_lo = sink->fir.wf_offset - A.wf_offset;
-            A.in_hi = A.in_lo + sink->fir.n;
-            sink->fed_rows_ptr = (const char*)A.wf + (size_t)sink->fir.wf_offset * es;  // the consumer's first sample, if it is bound to these rows
-            sink->fed_bl = A.bl;
-            sink->fed_stream = stream;
-            sink->fed_n_wf = n_wf;
-            sink->fed_stride = A.wf_stride;
-            sink->fed_len = sink->fir.n;
-        }
-        hipError_t e = (hipError_t)dsp_internal_launch_pz_rows(&A, n_wf, ch->dev_err, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "pole-zero rows kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    if (ch->red_ok && ch->fused_on) {
-        ReduceArgs A = ch->red;
-        A.wf = io_ptrs[ch->dio_wf];
-        for (int k = 0; k < 5; ++k) A.out[k] = at(ch->dio_out[k]);
-        for (int k = 0; k < DSP_REDUCE_PICKS; ++k) A.pick_out[k] = at(ch->dio_pick[k]);
-        for (int k = 0; k < DSP_REDUCE_WALKS; ++k) {
-            A.walk_out[k] = at(ch->dio_walk[k]);
-            A.walk_thr[k] = (const float*)at(ch->dio_walk_thr[k]);
-            A.walk_ts[k] = (const float*)at(ch->dio_walk_ts[k]);
-        }
-        const int vec = ch->red_vec && (reinterpret_cast<uintptr_t>(A.wf) & 15u) == 0;
-        hipError_t e = (hipError_t)dsp_internal_launch_reduce(&A, n_wf, ch->red_dtype, vec, ch->dev_err, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "reduce kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    if (ch->runs_ok && ch->fused_on && (reinterpret_cast<uintptr_t>(io_ptrs[ch->uio_wf]) & 15u) == 0) {
-        if (!ch->runs_table) HIP_TRY(hipMalloc((void**)&ch->runs_table, sizeof(FirRunsTable)));
-        FirRunsArgs A = ch->runs;
-        if (!A.keep && !ch->runs_scratch)
-            HIP_TRY(hipMalloc((void**)&ch->runs_scratch, (size_t)runs_blocks_cap(ch) * 4 * (size_t)A.out_stride * sizeof(float)));
-        A.wf = (const float*)io_ptrs[ch->uio_wf];
-        A.taps = (const float*)at(ch->uio_taps);
-        A.out = A.keep ? (float*)at(ch->uio_out) : ch->runs_scratch;
-        A.table = ch->runs_table;
-        for (int k = 0; k < 5; ++k) A.red.out[k] = at(ch->dio_out[k]);
-        for (int k = 0; k < DSP_REDUCE_PICKS; ++k) A.red.pick_out[k] = at(ch->dio_pick[k]);
-        for (int k = 0; k < DSP_REDUCE_WALKS; ++k) {
-            A.red.walk_out[k] = at(ch->dio_walk[k]);
-            A.red.walk_thr[k] = (const float*)at(ch->dio_walk_thr[k]);
-            A.red.walk_ts[k] = (const float*)at(ch->dio_walk_ts[k]);
-        }
-        hipError_t e = (hipError_t)dsp_internal_launch_fir_runs(&A, ch->runs_table, n_wf, runs_blocks(ch, n_wf), ch->dev_err, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "run-length FIR kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    if (ch->cur_ok && ch->fused_on && (reinterpret_cast<uintptr_t>(io_ptrs[ch->cio_wf]) & 15u) == 0) {
-        // persistent wavefronts, as many as a CU's LDS takes (at most 12 per CU): each keeps its scratch area for the groups of rows it walks
-        const int cap = current_blocks_cap(ch);
-        if (!ch->cur_scratch) {
-            HIP_TRY(hipMalloc((void**)&ch->cur_scratch, (size_t)cap * (size_t)ch->cur.scratch_per_wave * sizeof(float)));
-            ch->cur_blocks_cap = cap;
-        }
-        CurrentArgs A = ch->cur;
-        A.wf = io_ptrs[ch->cio_wf];
-        A.t0 = (const float*)at(ch->cio_t0);
-        for (int k = 0; k < 4; ++k) A.out[k] = at(ch->cio_out[k]);
-        A.scratch = ch->cur_scratch;
-        const int blocks = current_blocks(ch, n_wf);
-        hipError_t e = (hipError_t)dsp_internal_launch_current(&A, n_wf, blocks, ch->cur_lds_bytes, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "current kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    if (fir_applies(ch, io_ptrs)) {
-        FirArgs A = ch->fir;
-        A.wf = io_ptrs[ch->fio_wf];
-        A.bl = (const float*)at(ch->fio_bl);
-        for (int k = 0; k < A.n_kernels; ++k) {
-            A.taps[k] = (const float*)at(ch->fio_taps[k]);
-            A.out[k] = at(ch->fio_out[k]);
-        }
-        if (ch->fir_f16) {
-            const int rc = f16_rows_reserve(ch, n_wf);
-            if (rc != DSP_OK) return rc;
-            // scales and flags already there?  Only if the kernel in front wrote exactly the rows this one reads, and just now
-            const void* first = (const char*)A.wf + (size_t)A.wf_offset * (A.in_kind == 0 ? sizeof(float) : sizeof(int16_t));
-            // -- and on this stream: scales and flags are written by the producer's launch, so only stream order puts them ahead of this one
-            const bool same_batch = ch->scale_feeder && ch->fed_rows_ptr == first && ch->fed_n_wf == n_wf && ch->fed_stream == stream &&
-                                    ch->fed_stride == A.wf_stride && ch->fed_len == A.n;
-            ch->f16.rows_done = (same_batch && (ch->fed_in_side ? (A.in_kind != 0 && A.sub_mode == 1 && ch->fed_bl == (const void*)A.bl && A.bl != nullptr)
-                                                                : (A.in_kind == 0 && A.sub_mode == 0))) ? 1 : 0;
-            ch->fed_n_wf = -1;  // (a note is good for one execute)
-        }
-        hipError_t e = (hipError_t)(ch->fir_f16 ? dsp_internal_launch_fir_f16(&A, &ch->f16, n_wf, dsp_internal_fir_f16_lds_bytes(), (hipStream_t)stream)
-                                    : A.store   ? dsp_internal_launch_fir_store(&A, n_wf, ch->fir_lds_bytes, (hipStream_t)stream)
-                                                : dsp_internal_launch_fir_mfma(&A, n_wf, ch->fir_lds_bytes, (hipStream_t)stream));
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "FIR kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    if (rows_applies(ch, io_ptrs)) {
-        RowsArgs A = ch->rows;
-        A.wf = io_ptrs[ch->rio_wf];
-        A.bl = (const float*)at(ch->rio_bl);
-        A.thr = (const float*)at(ch->rio_thr);
-        A.ts = (const float*)at(ch->rio_ts);
-        for (int k = 0; k < 4; ++k) A.out_mm[k] = at(ch->rio_mm[k]);
-        A.out_tpt = at(ch->rio_tpt);
-        A.dwt_out = at(ch->rio_dwt);
-        hipError_t e = (hipError_t)dsp_internal_launch_rows(&A, n_wf, ch->dev_err, ch->rows_lds_bytes, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "rows kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    const int blocks = vm_blocks(ch, n_wf);
-    const int threads = 64 * ch->waves_per_block;
-    const int lds = ch->lds_bytes_per_wave * ch->waves_per_block;
-    if (ch->rr_ok && ch->fused_on && ch->variant != 1 && ((reinterpret_cast<uintptr_t>(io_ptrs[ch->io_wf]) & 15u) == 0)) {
-        EnergyArgs F = ch->rr;
-        F.wf = io_ptrs[ch->io_wf];
-        F.bl = (const float*)at(ch->io_bl);
-        F.tp = (const float*)at(ch->io_tp);
-        F.tau = (const float*)at(ch->io_tau);
-        F.out = (float*)at(ch->io_out);
-        const int S = (ch->variant == 8 && ch->wf_dtype == DSP_F32) ? 2 : 1;
-        int rwpb, rblocks;
-        rr_geometry(ch, n_wf, &rwpb, &rblocks);
-        hipError_t e = (hipError_t)dsp_internal_launch_energy_rr(&F, &ch->plan[S - 1], ch->fused_trap, ch->fused_npf, S, ch->wf_dtype, n_wf,
-                                                                 ch->dev_err, rblocks, 64 * rwpb, ch->rr_lds_bytes * rwpb, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "energy kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    if (ch->fused_ok && ch->fused_on && ((reinterpret_cast<uintptr_t>(io_ptrs[ch->io_wf]) & 15u) == 0)) {
-        EnergyArgs F = ch->fused;
-        F.wf = io_ptrs[ch->io_wf];
-        F.bl = (const float*)at(ch->io_bl);
-        F.tp = (const float*)at(ch->io_tp);
-        F.out = (float*)at(ch->io_out);
-        const int cw = ch->classic_wpb;
-        hipError_t e = (hipError_t)dsp_internal_launch_energy(&F, ch->fused_trap, ch->fused_npf, n_wf, ch->dev_err, chain_blocks(ch, n_wf, cw, 8),
-                                                              64 * cw, ch->lds_bytes_per_wave * cw, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DSP_ERR_HIP, "energy kernel launch failed: %s", hipGetErrorString(e));
-        return post_err(ch, stream);
-    }
-    hipError_t e = ch->f64 ? (hipError_t)dsp_internal_launch_vm_f64(ch->dev, &ptrs, n_wf, ch->dev_err, blocks, threads, lds, ch->has_fir,
-                                                                    (hipStream_t)stream)
-                           : (hipError_t)dsp_internal_launch_vm_f32(ch->dev, &ptrs, n_wf, ch->dev_err, blocks, threads * ch->host.team, lds, ch->has_fir,
-                                                                    ch->host.team, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DSP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return post_err(ch, stream);
+    // the first kernel, in the order of dsp_plan_route, that takes this launch's pointers
+    if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
+    if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
+    if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
+    if (fir_runs_applies(ch, io_ptrs)) return launch_fir_runs(ch, io_ptrs, n_wf, stream);
+    if (current_applies(ch, io_ptrs)) return launch_current(ch, io_ptrs, n_wf, stream);
+    if (fir_applies(ch, io_ptrs)) return launch_fir(ch, io_ptrs, n_wf, stream);  // (float16, kept output or float32 amax form)
+    if (rows_applies(ch, io_ptrs)) return launch_rows(ch, io_ptrs, n_wf, stream);
+    if (energy_rr_applies(ch, io_ptrs)) return launch_energy_rr(ch, io_ptrs, n_wf, stream);
+    if (energy_applies(ch, io_ptrs)) return launch_energy(ch, io_ptrs, n_wf, stream);
+    return launch_vm(ch, &ptrs, n_wf, stream);
 }
 
 int dsp_chain_check(dsp_chain* ch, void* stream, int64_t* row) {
@@ -825,53 +852,36 @@ int dsp_chain_destroy(dsp_chain* ch) {
 
 int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int* waves_per_block, int* blocks) {
     if (!ch) return fail(DSP_ERR_ARG, "null chain");
-    if (ch->scalar_ok && ch->fused_on) {
-        if (lds_bytes_per_wave) *lds_bytes_per_wave = ch->host.n_sregs * 64 * ((ch->f64 || ch->i64) ? 8 : 4);
-        if (waves_per_block) *waves_per_block = 1;
-        if (blocks) *blocks = (int)((n_wf + 63) / 64);
-        return DSP_OK;
+    int lds = 0, wpb = 0, b = 0;
+    switch (dsp_plan_route(ch)) {
+        case DSP_ROUTE_SCALAR:
+            lds = ch->host.n_sregs * 64 * ((ch->f64 || ch->i64) ? 8 : 4), wpb = 1, b = (int)((n_wf + 63) / 64);
+            break;
+        case DSP_ROUTE_PZ_ROWS:
+        case DSP_ROUTE_REDUCE: lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4); break;
+        case DSP_ROUTE_FIR_RUNS: lds = dsp_internal_fir_runs_lds_bytes(ch->runs.m) / 4, wpb = 4, b = runs_blocks(ch, n_wf); break;
+        case DSP_ROUTE_CURRENT: lds = ch->cur_lds_bytes, wpb = 1, b = current_blocks(ch, n_wf); break;
+        case DSP_ROUTE_FIR_F16:
+        case DSP_ROUTE_FIR_STORE:
+        case DSP_ROUTE_FIR_MFMA:  // 8 wavefronts per 64 waveforms and kernel
+            lds = ch->fir_lds_bytes / 8, wpb = 8, b = (int)((n_wf + 63) / 64) * (ch->fir.store ? (ch->fir.p[0] + 319) / 320 : ch->fir.n_kernels);
+            break;
+        case DSP_ROUTE_ROWS:  // a pair of wavefronts per 64 waveforms shares one history ring
+            lds = ch->rows_lds_bytes / 2, wpb = 2, b = (int)((n_wf + 63) / 64);
+            break;
+        case DSP_ROUTE_ENERGY_RR:
+            rr_geometry(ch, n_wf, &wpb, &b);
+            lds = ch->rr_lds_bytes;
+            break;
+        case DSP_ROUTE_ENERGY:  // (reported as the interpreter's: the classic kernel runs on its LDS layout)
+        case DSP_ROUTE_VM:
+            lds = ch->lds_bytes_per_wave / ch->host.team;  // (a team of wavefronts shares a row's image)
+            wpb = ch->waves_per_block * ch->host.team, b = vm_blocks(ch, n_wf);
+            break;
     }
-    if ((ch->red_ok || ch->pz_ok) && ch->fused_on) {
-        if (lds_bytes_per_wave) *lds_bytes_per_wave = 0;
-        if (waves_per_block) *waves_per_block = 4;
-        if (blocks) *blocks = (int)((n_wf + 3) / 4);
-        return DSP_OK;
-    }
-    if (ch->runs_ok && ch->fused_on) {
-        if (lds_bytes_per_wave) *lds_bytes_per_wave = dsp_internal_fir_runs_lds_bytes(ch->runs.m) / 4;
-        if (waves_per_block) *waves_per_block = 4;
-        if (blocks) *blocks = runs_blocks(ch, n_wf);
-        return DSP_OK;
-    }
-    if (ch->cur_ok && ch->fused_on) {
-        if (lds_bytes_per_wave) *lds_bytes_per_wave = ch->cur_lds_bytes;
-        if (waves_per_block) *waves_per_block = 1;
-        if (blocks) *blocks = current_blocks(ch, n_wf);
-        return DSP_OK;
-    }
-    if (ch->fir_ok && ch->fused_on) {  // 8 wavefronts per 64 waveforms and kernel
-        if (lds_bytes_per_wave) *lds_bytes_per_wave = ch->fir_lds_bytes / 8;
-        if (waves_per_block) *waves_per_block = 8;
-        if (blocks) *blocks = (int)((n_wf + 63) / 64) * (ch->fir.store ? (ch->fir.p[0] + 319) / 320 : ch->fir.n_kernels);
-        return DSP_OK;
-    }
-    if (ch->rows_ok && ch->fused_on) {  // a pair of wavefronts per 64 waveforms shares one history ring
-        if (lds_bytes_per_wave) *lds_bytes_per_wave = ch->rows_lds_bytes / 2;
-        if (waves_per_block) *waves_per_block = 2;
-        if (blocks) *blocks = (int)((n_wf + 63) / 64);
-        return DSP_OK;
-    }
-    if (ch->rr_ok && ch->fused_on && ch->variant != 1) {
-        int wpb, b;
-        rr_geometry(ch, n_wf, &wpb, &b);
-        if (lds_bytes_per_wave) *lds_bytes_per_wave = ch->rr_lds_bytes;
-        if (waves_per_block) *waves_per_block = wpb;
-        if (blocks) *blocks = b;
-        return DSP_OK;
-    }
-    if (lds_bytes_per_wave) *lds_bytes_per_wave = ch->lds_bytes_per_wave / ch->host.team;  // (a team of wavefronts shares a row's image)
-    if (waves_per_block) *waves_per_block = ch->waves_per_block * ch->host.team;
-    if (blocks) *blocks = vm_blocks(ch, n_wf);
+    if (lds_bytes_per_wave) *lds_bytes_per_wave = lds;
+    if (waves_per_block) *waves_per_block = wpb;
+    if (blocks) *blocks = b;
     return DSP_OK;
 }
 
@@ -879,8 +889,7 @@ const char* dsp_chain_kernel_name(dsp_chain* ch) { return dsp_plan_kernel_name(c
 
 const char* dsp_chain_kernel_note(dsp_chain* ch) {
     if (!ch) return "";
-    const bool specialised = ch->fused_on && (ch->scalar_ok || ch->pz_ok || ch->red_ok || ch->runs_ok || ch->cur_ok || ch->fir_ok || ch->rows_ok || ch->rr_ok || ch->fused_ok);
-    return specialised ? "" : ch->note.c_str();
+    return dsp_plan_specialised(ch) ? "" : ch->note.c_str();
 }
 
 int dsp_chain_set_async_check(dsp_chain* ch, int enable) {
@@ -902,7 +911,7 @@ int dsp_chain_set_fused(dsp_chain* ch, int enable) {
     // 7 = classic (VM layout); anything else = default
     const int v = (enable >> 1) & 7;
     ch->variant = (v == 7 || !ch->rr_ok) ? 1 : 6;
-    return ((ch->fused_ok || ch->rr_ok || ch->rows_ok || ch->fir_ok || ch->cur_ok || ch->scalar_ok || ch->red_ok || ch->runs_ok || ch->pz_ok) && ch->fused_on) ? 1 : 0;
+    return dsp_plan_specialised(ch) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------ single processors

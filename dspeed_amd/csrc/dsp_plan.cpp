@@ -1,6 +1,6 @@
 // dsp_plan.cpp -- chain translation without the device: validation, host-evaluated constants, LDS packing by slot lifetime, the shape
 // matchers of the specialised kernels and the launch geometry (see dsp_plan.h).  No HIP header, no HIP call: this file is also built for
-// the CPU under AddressSanitizer / UBSan and fuzzed (tools/planner_fuzz.cpp).
+// the CPU under AddressSanitizer / UBSan and fuzzed (tests/planner_fuzz.cpp).
 //
 // Reference behaviour mirrored here: constant-only DSPFatal conditions are raised at chain creation with the reference's own
 // codes / messages (processors/*.py, cited in include/dspeed_hip.h).
@@ -87,6 +87,25 @@ static void note(ChainPlan* ch, const char* fmt, ...) {
     ch->note = buf;
 }
 
+// What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
+struct PlanCtx {
+    const dsp_op* ops;
+    int n_ops;
+    const dsp_io_desc* io;
+    int n_io;
+    const int32_t* slot_len;
+    int n_slots, n_sregs, compute_dtype;
+    ChainPlan* ch;
+    bool f64 = false, i64 = false;
+    int esz = 4;  // bytes of an LDS element
+    // FIR inputs (laid out without the chunk pad); slots that share their LDS region with another
+    bool linear[DSP_MAX_SLOTS] = {false}, shares[DSP_MAX_SLOTS] = {false};
+    // lifetime (first .. last op of the caller's program that touches the slot) and LDS region [base, base + foot) of every slot
+    int first_op[DSP_MAX_SLOTS] = {0}, last_op[DSP_MAX_SLOTS] = {0}, foot[DSP_MAX_SLOTS] = {0}, base[DSP_MAX_SLOTS] = {0};
+    std::vector<int> dev_index{};  // caller's op -> position in the device program
+    int n_dev_ops = 0;
+};
+
 static bool fn_code_ok(int ip0, bool f64, bool i64 = false) {
     const int code = DSP_FN_CODE(ip0), bits = DSP_FN_INT_BITS(ip0);
     if (ip0 < 0 || code > DSP_FN_LAST || (ip0 >> 17) != 0) return false;
@@ -101,9 +120,14 @@ static bool fn_code_ok(int ip0, bool f64, bool i64 = false) {
 
 // Is the program  LOAD s; [MIN_MAX of s;] [BL_SUBTRACT s <- s;]  POLE_ZERO s <- s;  STORE s  [+ STORE_SCALARs of MIN_MAX's values]  on 16-byte aligned rows
 // (dsp_pz.hip)?  The MIN_MAX is that of the rows as they are read: every Ge recipe asks for tp_min / tp_max / wf_min / wf_max of the raw waveform.
-static bool match_pz_rows_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, const int32_t* slot_len, int n_slots,
-                                const std::vector<int>& dev_index, bool f64) {
-    if (f64 || n_slots != 1 || n_ops < 3 || n_ops > 9 || ops[0].opcode != DSP_OP_LOAD) return false;
+static bool match_pz_rows_shape(const PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int32_t* slot_len = c.slot_len;
+    int n_ops = c.n_ops;
+    const int n_slots = c.n_slots;
+    if (c.f64 || n_slots != 1 || n_ops < 3 || n_ops > 9 || ops[0].opcode != DSP_OP_LOAD) return false;
     const dsp_op& ld = ops[0];
     const dsp_io_desc& w = io[ld.io];
     const int len = slot_len[ld.dst];
@@ -160,7 +184,7 @@ static bool match_pz_rows_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, con
     if (tau_col) A.tau_stride = io[ch->pio_tau].row_stride;
     const dsp_io_desc& o = io[st.io];
     if (o.dtype != DSP_F32 || o.len != len || o.row_stride % 4 != 0 || o.offset % 4 != 0) return false;
-    const DevOp& dpz = ch->host.ops[dev_index[pz_at]];
+    const DevOp& dpz = ch->host.ops[c.dev_index[pz_at]];
     A.c = dpz.fc[0];
     A.tau_nan = dpz.ic[0];
     A.wf_stride = w.row_stride;
@@ -300,14 +324,15 @@ static bool match_reduce_ops(ChainPlan* ch, const dsp_op* ops, int first, int n_
     return true;
 }
 
-static bool match_reduce_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, const int32_t* slot_len, bool f64) {
-    if (f64 || n_ops < 3 || ops[0].opcode != DSP_OP_LOAD) return false;
-    const dsp_op& ld = ops[0];
-    const dsp_io_desc& w = io[ld.io];
-    if ((w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16) || ld.ip[0] != 0 || ld.ip[1] != 0 || w.len < 1 || slot_len[ld.dst] != w.len)
+static bool match_reduce_shape(const PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    if (c.f64 || c.n_ops < 3 || c.ops[0].opcode != DSP_OP_LOAD) return false;
+    const dsp_op& ld = c.ops[0];
+    const dsp_io_desc& w = c.io[ld.io];
+    if ((w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16) || ld.ip[0] != 0 || ld.ip[1] != 0 || w.len < 1 || c.slot_len[ld.dst] != w.len)
         return false;
     ReduceArgs& A = ch->red;
-    if (!match_reduce_ops(ch, ops, 1, n_ops, ld.dst, w.len, io, A)) return false;
+    if (!match_reduce_ops(ch, c.ops, 1, c.n_ops, ld.dst, w.len, c.io, A)) return false;
     if (!(ld.ip[2] & 1) && w.dtype == DSP_F32) A.need_stream = 1;  // (float rows without the promise of LOAD ip[2]: a NaN may sit anywhere)
     const int es = w.dtype == DSP_F32 ? 4 : 2;
     A.wf_stride = w.row_stride;
@@ -321,8 +346,13 @@ static bool match_reduce_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, cons
 // Does the program have the shape of the current-branch kernel (dsp_current.hip)?
 //   LOAD s0;  WINDOWER s1 <- s0 (start: constant or float32 column);  AVG_CURRENT s2 <- s1;  UPSAMPLER s3 <- s2;
 //   MOVING_WINDOW_MULTI d <- s3 (3 windows, alternating);  MIN_MAX of d;  STORE_SCALARs of its four registers
-static bool match_current_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, const int32_t* slot_len, bool f64) {
-    if (f64 || n_ops < 7) return false;
+static bool match_current_shape(const PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int32_t* slot_len = c.slot_len;
+    const int n_ops = c.n_ops;
+    if (c.f64 || n_ops < 7) return false;
     const dsp_op &ld = ops[0], &wi = ops[1], &ac = ops[2], &up = ops[3], &mw = ops[4], &mm = ops[5];
     if (ld.opcode != DSP_OP_LOAD || wi.opcode != DSP_OP_WINDOWER || ac.opcode != DSP_OP_AVG_CURRENT || up.opcode != DSP_OP_UPSAMPLER ||
         mw.opcode != DSP_OP_MOVING_WINDOW_MULTI || mm.opcode != DSP_OP_MIN_MAX)
@@ -398,9 +428,13 @@ static bool match_current_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, con
     return true;
 }
 
-static bool match_fir_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, const int32_t* slot_len, int n_slots, bool f64) {
-    const DevProgram& P = ch->host;
-    if (f64 || n_ops < 3 || n_slots != 1 || ops[0].opcode != DSP_OP_LOAD) return false;
+static bool match_fir_shape(const PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int32_t* slot_len = c.slot_len;
+    const int n_ops = c.n_ops, n_slots = c.n_slots;
+    if (c.f64 || n_ops < 3 || n_slots != 1 || ops[0].opcode != DSP_OP_LOAD) return false;
     const dsp_op& ld = ops[0];
     const int s = ld.dst, wdt = io[ld.io].dtype, n = slot_len[s];
     if (wdt != DSP_F32 && wdt != DSP_I16 && wdt != DSP_U16) return false;
@@ -464,14 +498,18 @@ static bool match_fir_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const d
     A.scan_after = ld.ip[1];
     ch->fio_wf = ld.io;
     ch->fir_lds_bytes = dsp_internal_fir_mfma_lds_bytes(kend);
-    (void)P;
     return ch->fir_lds_bytes <= 80 * 1024;
 }
 
 // The matrix-core FIR with its output kept (dsp_fir_store_kernel):  LOAD s; [BL_SUBTRACT s <- s]; CONVOLVE d <- s (any mode, >= 64 finite taps);
 // STORE d.  What whole recipes run ahead of their program for the filters other processors read (the t0 filter).
-static bool match_fir_store_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, const int32_t* slot_len, int n_slots, bool f64) {
-    if (f64 || n_ops < 3 || n_ops > 4 || n_slots != 2 || ops[0].opcode != DSP_OP_LOAD) return false;
+static bool match_fir_store_shape(const PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int32_t* slot_len = c.slot_len;
+    const int n_ops = c.n_ops, n_slots = c.n_slots;
+    if (c.f64 || n_ops < 3 || n_ops > 4 || n_slots != 2 || ops[0].opcode != DSP_OP_LOAD) return false;
     const dsp_op& ld = ops[0];
     const int s = ld.dst, wdt = io[ld.io].dtype, n = slot_len[s];
     if (wdt != DSP_F32 && wdt != DSP_I16 && wdt != DSP_U16) return false;
@@ -529,8 +567,13 @@ static bool match_fir_store_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, c
 // The run-length FIR (dsp_fir_runs.hip):  LOAD s (float32 rows);  CONVOLVE d <- s with ip[2] = 1 (the caller found the kernel piecewise constant:
 // at most DSP_FIR_RUNS_MAX runs) and at most DSP_FIR_RUNS_MAX_TAPS finite taps, any mode;  [STORE d];  [the reductions of match_reduce_ops on d].
 // At least one of the two: a filtered waveform nobody keeps and nobody reads is no program.
-static bool match_fir_runs_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, const int32_t* slot_len, int n_slots, bool f64) {
-    if (f64 || n_ops < 3 || n_slots != 2 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_CONVOLVE) return false;
+static bool match_fir_runs_shape(const PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int32_t* slot_len = c.slot_len;
+    const int n_ops = c.n_ops, n_slots = c.n_slots;
+    if (c.f64 || n_ops < 3 || n_slots != 2 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_CONVOLVE) return false;
     const dsp_op &ld = ops[0], &o = ops[1];
     const dsp_io_desc& w = io[ld.io];
     const int s = ld.dst, n = slot_len[s];
@@ -585,10 +628,14 @@ static bool match_fir_runs_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, co
 // Does the program have the shape of the lane-per-waveform kernel?  Fills ch->rows / ch->rio_* and returns true if so.
 //   LOAD s;  [BL_SUBTRACT s <- s];  POLE_ZERO | DOUBLE_POLE_ZERO s <- s;  then in any order: one TRAP_REDUCE of s, at most one DWT_HAAR of s
 //   into a slot that is stored, STORE_SCALARs of the reduction's registers.
-static bool match_rows_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_io, const int32_t* slot_len, int n_slots,
-                             const std::vector<int>& dev_index, bool f64) {
+static bool match_rows_shape(const PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int32_t* slot_len = c.slot_len;
+    const int n_ops = c.n_ops, n_slots = c.n_slots;
     const DevProgram& P = ch->host;
-    if (f64 || n_ops < 3 || n_slots < 1 || n_slots > 2) return false;
+    if (c.f64 || n_ops < 3 || n_slots < 1 || n_slots > 2) return false;
     int i = 0;
     if (ops[i].opcode != DSP_OP_LOAD) return false;
     const dsp_op& ld = ops[i++];
@@ -606,7 +653,7 @@ static bool match_rows_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const 
     // (no pole-zero step at all: the rows are a waveform another program already corrected -- what whole recipes stage in HBM)
     const bool has_pz = ops[i].opcode == DSP_OP_POLE_ZERO || ops[i].opcode == DSP_OP_DOUBLE_POLE_ZERO;
     const dsp_op& pz = ops[has_pz ? i : 0];
-    const DevOp& dpz = P.ops[dev_index[has_pz ? i : 0]];
+    const DevOp& dpz = P.ops[c.dev_index[has_pz ? i : 0]];
     if (has_pz) {
         ++i;
         if (pz.dst != s || pz.src != s) return false;
@@ -641,7 +688,7 @@ static bool match_rows_shape(ChainPlan* ch, const dsp_op* ops, int n_ops, const 
         note(ch, "rows of %d samples: the lane-per-waveform rows kernel takes float32 / int16 / uint16 rows of a multiple of 8 samples (16 and more) that start on 16-byte boundaries", len);
         return false;
     }
-    const DevOp& dtr = P.ops[dev_index[tr_at]];
+    const DevOp& dtr = P.ops[c.dev_index[tr_at]];
     RowsArgs& A = ch->rows;
     memset(&A, 0, sizeof A);
     A.wf_stride = io[ld.io].row_stride;
@@ -845,40 +892,42 @@ static int op_slots(const dsp_op& o, int out[4]) {
 }
 
 
-int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_io, const int32_t* slot_len, int n_slots,
-                   int n_sregs, int compute_dtype) {
-    if (!ops || !ch || n_ops <= 0 || n_ops > DSP_MAX_OPS) return fail(DSP_ERR_ARG, "n_ops=%d out of range (1..%d)", n_ops, DSP_MAX_OPS);
+static int check_call(PlanCtx& c) {
+    const int n_ops = c.n_ops, n_io = c.n_io, n_slots = c.n_slots, n_sregs = c.n_sregs, compute_dtype = c.compute_dtype;
+    if (!c.ops || !c.ch || n_ops <= 0 || n_ops > DSP_MAX_OPS) return fail(DSP_ERR_ARG, "n_ops=%d out of range (1..%d)", n_ops, DSP_MAX_OPS);
     if (n_io < 0 || n_io > DSP_MAX_IO) return fail(DSP_ERR_ARG, "n_io=%d out of range", n_io);
     if (n_slots < 0 || n_slots > DSP_MAX_SLOTS) return fail(DSP_ERR_ARG, "n_slots=%d out of range", n_slots);
     if (n_sregs < 0 || n_sregs > DSP_MAX_SREGS) return fail(DSP_ERR_ARG, "n_sregs=%d out of range", n_sregs);
     if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64 && compute_dtype != DSP_I64)
         return fail(DSP_ERR_ARG, "compute_dtype must be DSP_F32, DSP_F64 or DSP_I64");
-    const bool i64 = compute_dtype == DSP_I64;  // an integer program of per-event values (dspeed_hip.h): 64-bit integer registers
-    const int esz = compute_dtype == DSP_F32 ? 4 : 8;
-    const bool f64 = compute_dtype == DSP_F64;
-    if (i64) {
+    c.i64 = compute_dtype == DSP_I64;  // an integer program of per-event values (dspeed_hip.h): 64-bit integer registers
+    c.esz = compute_dtype == DSP_F32 ? 4 : 8;
+    c.f64 = compute_dtype == DSP_F64;
+    if (c.i64) {
         if (n_slots != 0) return fail(DSP_ERR_ARG, "an integer program (DSP_I64) has no waveform slots");
         for (int i = 0; i < n_ops; ++i)
-            if (ops[i].opcode != DSP_OP_SCALAR_FUNC && ops[i].opcode != DSP_OP_STORE_SCALAR)
+            if (c.ops[i].opcode != DSP_OP_SCALAR_FUNC && c.ops[i].opcode != DSP_OP_STORE_SCALAR)
                 return fail(DSP_ERR_ARG, "op %d: an integer program (DSP_I64) holds SCALAR_FUNC and STORE_SCALAR ops only", i);
     }
 
-    DevProgram& P = ch->host;
+    DevProgram& P = c.ch->host;
     P.n_ops = n_ops;
     P.n_slots = n_slots;
     P.n_io = n_io;
     P.n_sregs = n_sregs;
-    ch->f64 = f64;
-    ch->i64 = i64;
+    c.ch->f64 = c.f64;
+    c.ch->i64 = c.i64;
+    return DSP_OK;
+}
 
-    // ---- LDS layout: [guard 2*pitch][slot 64*pitch][tail 8] per slot, then the scalar registers
-    // FIR inputs are laid out linearly (no chunk pad): a slot qualifies when a CONVOLVE reads it and everything else that touches
-    // it is layout-agnostic (load, store, copy, bl_subtract); the chunk-serial filters keep the padded, conflict-free layout
-    bool linear[DSP_MAX_SLOTS] = {false};
-    for (int s = 0; s < n_slots; ++s) {
+// ---- LDS layout: [guard 2*pitch][slot 64*pitch][tail 8] per slot, then the scalar registers
+// FIR inputs are laid out linearly (no chunk pad): a slot qualifies when a CONVOLVE reads it and everything else that touches
+// it is layout-agnostic (load, store, copy, bl_subtract); the chunk-serial filters keep the padded, conflict-free layout
+static void choose_linear_slots(PlanCtx& c) {
+    for (int s = 0; s < c.n_slots; ++s) {
         bool fir_in = false, only_plain = true;
-        for (int i = 0; i < n_ops; ++i) {
-            const dsp_op& o = ops[i];
+        for (int i = 0; i < c.n_ops; ++i) {
+            const dsp_op& o = c.ops[i];
             int touched[4];
             const int nt = op_slots(o, touched);
             bool uses = false;
@@ -892,29 +941,41 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
                                o.opcode == DSP_OP_BL_SUBTRACT || o.opcode == DSP_OP_MIN_MAX_NORM || (conv && reads && !writes);
             if (!plain) only_plain = false;
         }
-        linear[s] = fir_in && only_plain;
+        c.linear[s] = fir_in && only_plain;
     }
-    // Slots whose lifetimes (first .. last op that touches them) do not overlap share LDS: the ICPC recipe has 14 waveform variables
-    // and at most four alive at a time.  Interval packing, first fit by first use; a slot that shares its region gets a
-    // DSP_OP_INTERNAL_ZERO in front of its first op (guards must read 0, pads finite -- also for the next row, which finds the region
-    // as the last tenant of the previous row left it).
-    int first_op[DSP_MAX_SLOTS], last_op[DSP_MAX_SLOTS], foot[DSP_MAX_SLOTS], base[DSP_MAX_SLOTS];
-    for (int s = 0; s < n_slots; ++s) {
-        first_op[s] = n_ops;
-        last_op[s] = -1;
+}
+
+// first .. last op that touches each slot (a slot nothing touches: pack_lds keeps it alive throughout)
+static void slot_lifetimes(PlanCtx& c) {
+    for (int s = 0; s < c.n_slots; ++s) {
+        c.first_op[s] = c.n_ops;
+        c.last_op[s] = -1;
     }
-    for (int i = 0; i < n_ops; ++i) {
+    for (int i = 0; i < c.n_ops; ++i) {
         int touched[4];
-        const int nt = op_slots(ops[i], touched);
+        const int nt = op_slots(c.ops[i], touched);
         for (int k = 0; k < nt; ++k) {
             const int s = touched[k];
-            if (s < 0 || s >= n_slots) continue;  // (rejected by the op checks below)
-            if (i < first_op[s]) first_op[s] = i;
-            if (i > last_op[s]) last_op[s] = i;
+            if (s < 0 || s >= c.n_slots) continue;  // (rejected by the op checks of lower_ops)
+            if (i < c.first_op[s]) c.first_op[s] = i;
+            if (i > c.last_op[s]) c.last_op[s] = i;
         }
     }
+}
+
+// Slots whose lifetimes (first .. last op that touches them) do not overlap share LDS: the ICPC recipe has 14 waveform variables
+// and at most four alive at a time.  Interval packing, first fit by first use; a slot that shares its region gets a
+// DSP_OP_INTERNAL_ZERO in front of its first op (guards must read 0, pads finite -- also for the next row, which finds the region
+// as the last tenant of the previous row left it).  Behind the slots: the register file and the scratch area.
+static int pack_lds(PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    DevProgram& P = ch->host;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int n_ops = c.n_ops, n_io = c.n_io, n_slots = c.n_slots;
+    int *first_op = c.first_op, *last_op = c.last_op, *foot = c.foot, *base = c.base;
     for (int s = 0; s < n_slots; ++s) {
-        const int len = slot_len[s];
+        const int len = c.slot_len[s];
         if (len <= 0) return fail(DSP_ERR_ARG, "slot %d has length %d", s, len);
         // (40 000 float32 samples fill a CU's LDS; the bound keeps the layout arithmetic below -- and the kernels' index -> (lane, offset)
         // split, exact for indices under 2^20 -- inside int)
@@ -924,7 +985,7 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
         DevSlot& d = P.slots[s];
         d.len = len;
         d.C = C;
-        d.padw = linear[s] ? 0 : 1;
+        d.padw = c.linear[s] ? 0 : 1;
         d.pitch = C + d.padw;
         d.invC = 1.0f / (float)C;
         // a short FIR kernel (the t0 filter) in 'same' / 'full' mode reads up to m - 1 samples past either end of its input: give the
@@ -948,7 +1009,6 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
     for (int s = 0; s < n_slots; ++s) order[s] = s;
     std::stable_sort(order, order + n_slots, [&](int a, int b) { return first_op[a] < first_op[b]; });
     int cursor = 0;
-    bool shares[DSP_MAX_SLOTS] = {false};
     for (int oi = 0; oi < n_slots; ++oi) {
         const int s = order[oi];
         int at = 0;
@@ -966,24 +1026,29 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
         base[s] = at;
         for (int oj = 0; oj < oi; ++oj) {
             const int t = order[oj];
-            if (at < base[t] + foot[t] && base[t] < at + foot[s]) shares[s] = shares[t] = true;
+            if (at < base[t] + foot[t] && base[t] < at + foot[s]) c.shares[s] = c.shares[t] = true;
         }
         P.slots[s].off = at + 2 * P.slots[s].pitch;
         if (at + foot[s] > cursor) cursor = at + foot[s];
     }
     P.sreg_off = cursor;
-    cursor += ((n_sregs + 7) / 8) * 8 + 8;
+    cursor += ((c.n_sregs + 7) / 8) * 8 + 8;
     cursor = ((cursor + 3) / 4) * 4;
     P.scratch_off = cursor;
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
-    ch->lds_bytes_per_wave = cursor * esz;
+    ch->lds_bytes_per_wave = cursor * c.esz;
     if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
-    // wavefronts per workgroup (1..4): the size that fits the most wavefronts into a CU's LDS and register budget (25 KB per
-    // waveform: 3 per group and 2 groups = 6 wavefronts, where 4 per group would leave one group of 4); ties go to the larger group.
-    // Register budget: the VM without the FIR op and 3 wavefronts per SIMD = 12 per CU, everything else 2 per SIMD = 8 per CU.
-    for (int i = 0; i < n_ops; ++i) ch->has_fir |= (ops[i].opcode == DSP_OP_CONVOLVE || ops[i].opcode == DSP_OP_CONVOLVE_AMAX);
+    return DSP_OK;
+}
+
+// wavefronts per workgroup (1..4): the size that fits the most wavefronts into a CU's LDS and register budget (25 KB per
+// waveform: 3 per group and 2 groups = 6 wavefronts, where 4 per group would leave one group of 4); ties go to the larger group.
+// Register budget: the VM without the FIR op and 3 wavefronts per SIMD = 12 per CU, everything else 2 per SIMD = 8 per CU.
+static void pick_waves_per_block(PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    for (int i = 0; i < c.n_ops; ++i) ch->has_fir |= (c.ops[i].opcode == DSP_OP_CONVOLVE || c.ops[i].opcode == DSP_OP_CONVOLVE_AMAX);
     auto pick_wpb = [&](int cap_waves) {
         int best_w = 1, best_waves = 0;
         for (int w = 1; w <= 4; ++w) {
@@ -1000,12 +1065,15 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
     int wpb = pick_wpb(ch->has_fir ? 8 : 12);
     ch->classic_wpb = pick_wpb(8);
     ch->waves_per_block = wpb;
-    P.waves_per_block = wpb;
+    ch->host.waves_per_block = wpb;
+}
 
-    // ---- I/O bindings
-    for (int k = 0; k < n_io; ++k) {
-        const dsp_io_desc& a = io[k];
-        DevIO& d = P.io[k];
+// ---- I/O bindings
+static int bind_io(PlanCtx& c) {
+    const bool f64 = c.f64, i64 = c.i64;
+    for (int k = 0; k < c.n_io; ++k) {
+        const dsp_io_desc& a = c.io[k];
+        DevIO& d = c.ch->host.io[k];
         const int es = elem_size(a.dtype);
         if (!es) return fail(DSP_ERR_ARG, "io %d: unknown dtype %d", k, a.dtype);
         if (a.kind < DSP_IO_WF_IN || a.kind > DSP_IO_TAPS) return fail(DSP_ERR_ARG, "io %d: unknown kind %d", k, a.kind);
@@ -1020,7 +1088,7 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
         if (a.kind == DSP_IO_WF_IN && !f64 && (a.dtype == DSP_I32 || a.dtype == DSP_U32 || a.dtype == DSP_F64))
             return fail(DSP_ERR_ARG, "io %d: int32/uint32/float64 rows select the float64 loop (compute_dtype DSP_F64)", k);
         const bool is_out = a.kind == DSP_IO_WF_OUT || a.kind == DSP_IO_SCALAR_OUT;
-        if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT))
+        if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT))
             return fail(DSP_ERR_ARG, "io %d: outputs have the chain's compute type or DSP_BOOL, taps the compute type", k);
         if ((a.dtype == DSP_BOOL || a.dtype == DSP_I64 || a.dtype == DSP_U64) && a.kind != DSP_IO_SCALAR_IN && a.kind != DSP_IO_SCALAR_OUT && !(a.dtype == DSP_BOOL && is_out))
             return fail(DSP_ERR_ARG, "io %d: DSP_BOOL / DSP_I64 / DSP_U64 are types of per-event columns (DSP_BOOL also of waveform outputs)", k);
@@ -1035,23 +1103,327 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
         d.row_stride = a.row_stride;
         d.vec_ok = ((a.row_stride * es) % 16 == 0) && (((int64_t)a.offset * es) % 16 == 0);
     }
+    return DSP_OK;
+}
 
-    // ---- ops
-    std::vector<int> dev_index(n_ops);  // caller's op -> position in the device program
-    int n_dev_ops = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        const dsp_op& o = ops[i];
-        for (int s = 0; s < n_slots; ++s)
-            if (shares[s] && first_op[s] == i) {
-                DevOp& z = P.ops[n_dev_ops++];
+static bool need_io(const PlanCtx& c, const dsp_op& o, int kind) { return o.io >= 0 && o.io < c.n_io && c.io[o.io].kind == kind; }
+// the float32 loop receives float32 scalars, the float64 loop float64 ones
+static double op_const(const PlanCtx& c, const dsp_op& o, int k) { return c.f64 ? o.sp[k].value : (double)(float)o.sp[k].value; }
+
+// DOUBLE_POLE_ZERO: the coefficients of pole_zero.py:168-174 and the scan matrices M^(C*2^d)
+static int lower_double_pole_zero(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
+    const DevProgram& P = c.ch->host;
+    const int32_t* slot_len = c.slot_len;
+    if (!check_slot(P, o.src) || !check_slot(P, o.dst) || slot_len[o.src] != slot_len[o.dst])
+        return fail(DSP_ERR_ARG, "op %d: bad DOUBLE_POLE_ZERO", i);
+    bool per_event = false;
+    for (int k = 0; k < 3; ++k) per_event |= o.sp[k].kind != DSP_ARG_CONST;
+    if (per_event) {  // a time constant or the fraction per event: coefficients and scan matrices are formed on the device
+        if (slot_len[o.src] <= 3) return fail(DSP_E_DPZ_SHORT, "%s", dsp_fatal_message(DSP_E_DPZ_SHORT));
+        d.ic[1] = 1;
+        return DSP_OK;
+    }
+    const double tau1 = op_const(c, o, 0), tau2 = op_const(c, o, 1), fr = op_const(c, o, 2);
+    d.ic[0] = (std::isnan(tau1) || std::isnan(tau2) || std::isnan(fr)) ? 1 : 0;
+    if (!d.ic[0] && slot_len[o.src] <= 3) return fail(DSP_E_DPZ_SHORT, "%s", dsp_fatal_message(DSP_E_DPZ_SHORT));
+    if (slot_len[o.src] <= 3) d.ic[0] = 1;
+    const double a = std::exp(-1.0 / tau1), b = std::exp(-1.0 / tau2);  // pole_zero.py:168-174
+    const double den1 = ((fr * b - fr * a) - b) - 1.0;
+    const double den2 = -1.0 * ((fr * b - fr * a) - b);
+    const double num1 = -1.0 * (a + b);
+    const double num2 = a * b;
+    d.fc[0] = num1;
+    d.fc[1] = num2;
+    d.fc[2] = den1;
+    d.fc[3] = den2;
+    // M^(C*2^d), d = 0..5, M = [[-den1, -den2], [1, 0]]
+    long double M[4] = {-(long double)den1, -(long double)den2, 1.0L, 0.0L}, Pw[4] = {1, 0, 0, 1};
+    const int C = P.slots[o.src].C;
+    long double base[4];
+    memcpy(base, M, sizeof base);
+    for (int e = C; e; e >>= 1) {  // Pw = M^C
+        if (e & 1) mat2_mul(Pw, base, Pw);
+        mat2_mul(base, base, base);
+    }
+    for (int dd = 0; dd < 6; ++dd) {
+        for (int k = 0; k < 4; ++k) d.fc[4 + 4 * dd + k] = (double)Pw[k];
+        mat2_mul(Pw, Pw, Pw);
+    }
+    return DSP_OK;
+}
+
+static int lower_moving_window(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
+    const DevProgram& P = c.ch->host;
+    const int32_t* slot_len = c.slot_len;
+    const bool in_place = o.ip[3] == 1;
+    if (!check_slot(P, o.src) || !check_slot(P, o.dst) || (o.src == o.dst) != in_place || slot_len[o.src] != slot_len[o.dst])
+        return fail(DSP_ERR_ARG, "op %d: bad MOVING_WINDOW_MULTI", i);
+    if (o.sp[0].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "moving_window_multi: the window length must be a constant");
+    const double length = op_const(c, o, 0);
+    const int num = o.ip[1], n = slot_len[o.src];
+    if (floor(length) != length) return fail(DSP_E_MW_LEN_INT, "%s", dsp_fatal_message(DSP_E_MW_LEN_INT));
+    if ((long long)length < 0 || (long long)length >= n) return fail(DSP_E_MW_LEN_RANGE, "%s", dsp_fatal_message(DSP_E_MW_LEN_RANGE));
+    if (num < 0) return fail(DSP_E_MW_NUM_NEG, "%s", dsp_fatal_message(DSP_E_MW_NUM_NEG));
+    if (num > 0 && (long long)length == 0) return fail(DSP_E_ZERODIV, "%s", dsp_fatal_message(DSP_E_ZERODIV));
+    // (the scratch may be the source itself when the number of windows is odd: the first pass goes source -> target, so the
+    // source is free from the second pass on -- and is overwritten)
+    if (in_place) {  // ip[2]: a side slot for the ends of the chunks, 64 lanes x (L | 1) elements; the window inside one chunk
+        const long long Lw = (long long)length;
+        if (!check_slot(P, o.ip[2]) || o.ip[2] == o.src || Lw > P.slots[o.src].C || 64 * (Lw | 1) > 64LL * P.slots[o.ip[2]].pitch)
+            return fail(DSP_ERR_ARG, "op %d: MOVING_WINDOW_MULTI in place needs a window of at most %d samples and a side slot of 64 x window samples (ip[2])",
+                        i, P.slots[o.src].C);
+    } else
+    if (num > 1 && (!check_slot(P, o.ip[2]) || (o.ip[2] == o.src && num % 2 == 0) || o.ip[2] == o.dst || slot_len[o.ip[2]] != n))
+        return fail(DSP_ERR_ARG, "op %d: MOVING_WINDOW_MULTI with several windows needs a scratch slot of the same length (ip[2])", i);
+    d.ic[0] = (int)length;
+    d.ic[1] = num;
+    d.ic[2] = o.ip[0];
+    d.fc[0] = length;
+    return DSP_OK;
+}
+
+static int lower_convolve(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
+    const DevProgram& P = c.ch->host;
+    const int32_t* slot_len = c.slot_len;
+    const dsp_io_desc* io = c.io;
+    const bool fusedmax = o.opcode == DSP_OP_CONVOLVE_AMAX;
+    if (!check_slot(P, o.src) || !need_io(c, o, DSP_IO_TAPS)) return fail(DSP_ERR_ARG, "op %d: bad CONVOLVE", i);
+    if (fusedmax ? (o.dst < 0 || o.dst >= c.n_sregs || o.ip[2] <= 0) : (!check_slot(P, o.dst) || o.src == o.dst))
+        return fail(DSP_ERR_ARG, "op %d: bad CONVOLVE destination", i);
+    // ip[3] > 0: the kernel has ip[3] taps and the binding holds zeros after them (up to a multiple of the tap block, so the
+    // blocked path covers every tap; the op falls back to the true length for a waveform with an infinity in it: 0 * inf)
+    if (o.ip[3] < 0 || o.ip[3] > io[o.io].len) return fail(DSP_ERR_ARG, "op %d: CONVOLVE kernel length beyond its binding", i);
+    const int m = o.ip[3] > 0 ? o.ip[3] : io[o.io].len;
+    const int n = slot_len[o.src], p = fusedmax ? o.ip[2] : slot_len[o.dst], mode = o.ip[0];
+    d.ic[1] = m;
+    d.ic[6] = io[o.io].len;
+    d.ic[2] = (o.ip[1] & 1) ? 1 : 0;  // caller found a NaN among the taps -> output NaN (convolutions.py:45-46)
+    d.ic[5] = (o.ip[1] & 2) ? 1 : 0;  // ... an infinity: 0 * inf is NaN, so windows must not reach into the zero margins
+    d.ic[3] = p;
+    if (m > n) return fail(DSP_E_CONV_LONG, "%s", dsp_fatal_message(DSP_E_CONV_LONG));
+    if (mode == 'f') {
+        if (p != n + m - 1) return fail(DSP_E_CONV_OUTLEN, "Output waveform has length %d; expect %d", p, n + m - 1);
+        d.ic[0] = 0;
+    } else if (mode == 'v') {
+        if (p != n - m + 1) return fail(DSP_E_CONV_OUTLEN, "Output waveform has length %d; expect %d", p, n - m + 1);
+        d.ic[0] = m - 1;
+    } else if (mode == 's') {
+        if (p != n) return fail(DSP_E_CONV_OUTLEN, "Output waveform has length %d; expect %d", p, n);
+        d.ic[0] = (m - 1) / 2;
+    } else {
+        return fail(DSP_E_CONV_MODE, "%s", dsp_fatal_message(DSP_E_CONV_MODE));
+    }
+    return DSP_OK;
+}
+
+// validates one op of the caller's program and fills the constants of its device op `d` (a copy of the op already)
+static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
+    const DevProgram& P = c.ch->host;
+    const dsp_io_desc* io = c.io;
+    const int32_t* slot_len = c.slot_len;
+    const int n_sregs = c.n_sregs;
+    const bool f64 = c.f64, i64 = c.i64;
+    switch (o.opcode) {
+        case DSP_OP_LOAD:
+            if (!check_slot(P, o.dst) || !need_io(c, o, DSP_IO_WF_IN)) return fail(DSP_ERR_ARG, "op %d: bad LOAD", i);
+            if (io[o.io].len != slot_len[o.dst]) return fail(DSP_ERR_ARG, "op %d: LOAD length mismatch", i);
+            if (o.ip[0] < 0 || o.ip[1] < 0 || o.ip[0] > io[o.io].offset || (int64_t)io[o.io].offset + io[o.io].len + o.ip[1] > io[o.io].row_stride)
+                return fail(DSP_ERR_ARG, "op %d: LOAD screens samples outside the row (ip[0], ip[1])", i);
+            break;
+        case DSP_OP_STORE:
+            if (!check_slot(P, o.src) || !need_io(c, o, DSP_IO_WF_OUT)) return fail(DSP_ERR_ARG, "op %d: bad STORE", i);
+            if (io[o.io].len != slot_len[o.src]) return fail(DSP_ERR_ARG, "op %d: STORE length mismatch", i);
+            break;
+        case DSP_OP_STORE_SCALAR:
+            if (!need_io(c, o, DSP_IO_SCALAR_OUT) || o.ip[0] < 0 || o.ip[0] >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad STORE_SCALAR", i);
+            break;
+        case DSP_OP_BL_SUBTRACT:
+        case DSP_OP_MIN_MAX_NORM:
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || slot_len[o.src] != slot_len[o.dst])
+                return fail(DSP_ERR_ARG, "op %d: bad element-wise op", i);
+            break;
+        case DSP_OP_POLE_ZERO: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || slot_len[o.src] != slot_len[o.dst])
+                return fail(DSP_ERR_ARG, "op %d: bad POLE_ZERO", i);
+            if (o.sp[0].kind != DSP_ARG_CONST) {  // one tau per event: the constant is formed on the device (op_pole_zero)
+                d.ic[1] = 1;
+                break;
+            }
+            const double tau = op_const(c, o, 0);
+            d.ic[0] = std::isnan(tau) ? 1 : 0;
+            d.fc[0] = std::exp(-1.0 / tau);  // pole_zero.py:60 -- float64 via libm, like numba's lowering
+            break;
+        }
+        case DSP_OP_DOUBLE_POLE_ZERO: return lower_double_pole_zero(c, i, o, d);
+        case DSP_OP_TRAP_FILTER:
+        case DSP_OP_TRAP_NORM:
+        case DSP_OP_ASYM_TRAP: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst || slot_len[o.src] != slot_len[o.dst])
+                return fail(DSP_ERR_ARG, "op %d: bad trapezoid (source and destination slots must differ)", i);
+            int rc = setup_trap(d, o.opcode, o.ip[0], o.ip[1], o.ip[2], slot_len[o.src], P.slots[o.src].C);
+            if (rc) return fail(rc, "%s", dsp_fatal_message(rc));
+            break;
+        }
+        case DSP_OP_TRAP_PICKOFF: {
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad TRAP_PICKOFF", i);
+            if (o.ip[3] != DSP_OP_TRAP_FILTER && o.ip[3] != DSP_OP_TRAP_NORM && o.ip[3] != DSP_OP_ASYM_TRAP)
+                return fail(DSP_ERR_ARG, "op %d: TRAP_PICKOFF ip[3] must name a trapezoid opcode", i);
+            if (o.io == 's')
+                return fail(DSP_ERR_UNSUPPORTED, "TRAP_PICKOFF cannot take mode 's' (the spline needs the whole filtered waveform): use TRAP_FILTER + PICKOFF");
+            int rc = setup_trap(d, o.ip[3], o.ip[0], o.ip[1], o.ip[2], slot_len[o.src], P.slots[o.src].C);
+            if (rc) return fail(rc, "%s", dsp_fatal_message(rc));
+            break;
+        }
+        case DSP_OP_TRAP_REDUCE: {
+            if (!check_slot(P, o.src) || (o.dst < 0 && o.io < 0) || (o.dst >= 0 && o.dst > n_sregs - 4) || o.io >= n_sregs)
+                return fail(DSP_ERR_ARG, "op %d: bad TRAP_REDUCE", i);
+            const int tk = o.ip[3] & 0xff, pk_mode = (o.ip[3] >> 8) & 0xff, pk_reg = ((o.ip[3] >> 16) & 0x3fff) - 1;
+            if (tk != DSP_OP_TRAP_FILTER && tk != DSP_OP_TRAP_NORM && tk != DSP_OP_ASYM_TRAP)
+                return fail(DSP_ERR_ARG, "op %d: TRAP_REDUCE ip[3] must name a trapezoid opcode", i);
+            if (pk_reg >= n_sregs || (pk_reg >= 0 && (pk_mode == 0 || pk_mode == 's')) || (pk_reg < 0 && pk_mode != 0))
+                return fail(DSP_ERR_ARG, "op %d: bad pick-off in TRAP_REDUCE (register %d, mode %d)", i, pk_reg, pk_mode);
+            if (((o.ip[3] >> 30) & 1) && (o.dst < 0 || tk == DSP_OP_ASYM_TRAP))
+                return fail(DSP_ERR_ARG, "op %d: TRAP_REDUCE amax-only needs the min_max registers and trap_filter / trap_norm", i);
+            int rc = setup_trap(d, tk, o.ip[0], o.ip[1], o.ip[2], slot_len[o.src], P.slots[o.src].C);
+            if (rc) return fail(rc, "%s", dsp_fatal_message(rc));
+            break;
+        }
+        case DSP_OP_PICKOFF:
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad PICKOFF", i);
+            if (o.ip[1] < 0 || o.ip[1] > 2) return fail(DSP_ERR_ARG, "op %d: PICKOFF ip[1] must be 0, 1 or 2", i);
+            if (o.ip[1] == 2 && o.sp[1].kind != DSP_ARG_CONST) return fail(DSP_ERR_ARG, "op %d: PICKOFF ip[1] = 2 takes a constant default (sp[1])", i);
+            if (o.ip[1] == 1 && (o.sp[0].kind != DSP_ARG_CONST || o.sp[0].value < 0 || o.sp[0].value >= slot_len[o.src] ||
+                                 o.sp[0].value != std::floor(o.sp[0].value)))
+                return fail(DSP_ERR_ARG, "op %d: PICKOFF of one sample (ip[1] = 1) needs a constant index inside the waveform", i);
+            break;
+        case DSP_OP_TIME_POINT_THRESH:
+        case DSP_OP_INTERP_TIME_POINT_THRESH:
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad TIME_POINT_THRESH", i);
+            break;
+        case DSP_OP_MEAN_BELOW:
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad MEAN_BELOW", i);
+            break;
+        case DSP_OP_WINDOWER:
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst) return fail(DSP_ERR_ARG, "op %d: bad WINDOWER", i);
+            if (slot_len[o.dst] >= slot_len[o.src]) return fail(DSP_E_WINDOW_LONG, "%s", dsp_fatal_message(DSP_E_WINDOW_LONG));
+            break;
+        case DSP_OP_AVG_CURRENT: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst) return fail(DSP_ERR_ARG, "op %d: bad AVG_CURRENT", i);
+            if (o.sp[0].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "avg_current: the window length must be a constant");
+            const double length = op_const(c, o, 0);
+            const int n = slot_len[o.src];
+            if (!(length >= 0) || !(length < (double)n)) return fail(DSP_E_AVGCUR_RANGE, "%s", dsp_fatal_message(DSP_E_AVGCUR_RANGE));
+            const int L = (int)length;
+            if (L <= 0 || slot_len[o.dst] != n - L)
+                return fail(DSP_ERR_ARG, "avg_current: the output must hold len(w_in) - int(length) = %d samples (it holds %d)", n - L,
+                            slot_len[o.dst]);
+            d.ic[0] = L;
+            d.fc[0] = length;
+            break;
+        }
+        case DSP_OP_UPSAMPLER: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst) return fail(DSP_ERR_ARG, "op %d: bad UPSAMPLER", i);
+            if (o.sp[0].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "upsampler: the factor must be a constant");
+            const double up = op_const(c, o, 0);
+            if (!(up > 0)) return fail(DSP_E_UPSAMPLE, "%s", dsp_fatal_message(DSP_E_UPSAMPLE));
+            d.fc[0] = up;
+            d.fc[1] = floor(up / 2.0);
+            d.ic[0] = (int)up;
+            break;
+        }
+        case DSP_OP_MOVING_WINDOW_MULTI: return lower_moving_window(c, i, o, d);
+        case DSP_OP_TRAP_WINDOW_PICKOFF: {
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad TRAP_WINDOW_PICKOFF", i);
+            const int rise = o.ip[0], flat = o.ip[1];
+            if (rise < 0) return fail(DSP_E_TRAP_RISE, "%s", dsp_fatal_message(DSP_E_TRAP_RISE));
+            if (flat < 0) return fail(DSP_E_TRAP_FLAT, "%s", dsp_fatal_message(DSP_E_TRAP_FLAT));
+            if (2 * (long long)rise + flat > slot_len[o.src]) return fail(DSP_E_TRAP_WIDE, "%s", dsp_fatal_message(DSP_E_TRAP_WIDE));
+            break;
+        }
+        case DSP_OP_MIN_MAX:
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst > n_sregs - 4) return fail(DSP_ERR_ARG, "op %d: bad MIN_MAX", i);
+            break;
+        case DSP_OP_LINEAR_SLOPE_FIT: {
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst > n_sregs - 4) return fail(DSP_ERR_ARG, "op %d: bad LINEAR_SLOPE_FIT", i);
+            const int first = o.ip[0];
+            if (first < 0 || first > slot_len[o.src]) return fail(DSP_ERR_ARG, "op %d: LINEAR_SLOPE_FIT slice out of range", i);
+            const int count = o.ip[1] > 0 ? o.ip[1] : slot_len[o.src] - first;  // ip[1] == 0: to the end of the slot
+            if (count < 0 || count > slot_len[o.src] - first) return fail(DSP_ERR_ARG, "op %d: LINEAR_SLOPE_FIT slice out of range", i);
+            if (count < 2) return fail(DSP_E_ZERODIV, "%s", dsp_fatal_message(DSP_E_ZERODIV));  // the line fit's denominator
+            d.ic[0] = first;
+            d.ic[1] = count;
+            break;
+        }
+        case DSP_OP_AMAX:
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad AMAX", i);
+            break;
+        case DSP_OP_DWT_HAAR: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || !check_slot(P, o.ip[2]) || o.dst == o.src || o.dst == o.ip[2])
+                return fail(DSP_ERR_ARG, "op %d: bad DWT_HAAR slots", i);
+            if (o.ip[0] <= 0) return fail(DSP_E_DWT_LEVEL, "%s", dsp_fatal_message(DSP_E_DWT_LEVEL));
+            if (o.ip[1] != 'a' && o.ip[1] != 'd') return fail(DSP_ERR_ARG, "op %d: DWT coefficient must be 'a' or 'd'", i);
+            int len = slot_len[o.src];
+            if (slot_len[o.ip[2]] < (len + 1) / 2 && o.ip[0] > 1) return fail(DSP_ERR_ARG, "op %d: DWT scratch slot too small", i);
+            for (int l = 0; l < o.ip[0]; ++l) len = (len + 1) / 2;
+            if (len != slot_len[o.dst]) return fail(DSP_E_DWT_OUTLEN, "%s (got %d, expect %d)", dsp_fatal_message(DSP_E_DWT_OUTLEN), slot_len[o.dst], len);
+            break;
+        }
+        case DSP_OP_COPY: {  // dst[k] = src[ip[0] + k * step], step = ip[1] (0 means 1; negative: backwards)
+            const int64_t step = o.ip[1] != 0 ? o.ip[1] : 1;
+            const int64_t last = check_slot(P, o.dst) ? (int64_t)o.ip[0] + (int64_t)(slot_len[o.dst] - 1) * step : -1;
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst || o.ip[0] < 0 || o.ip[0] >= slot_len[o.src] || last < 0 ||
+                last >= slot_len[o.src])
+                return fail(DSP_ERR_ARG, "op %d: bad COPY", i);
+            break;
+        }
+        case DSP_OP_ELEMENTWISE: {
+            if (!check_slot(P, o.dst) || !fn_code_ok(o.ip[0], f64)) return fail(DSP_ERR_ARG, "op %d: bad ELEMENTWISE", i);
+            const int opnd[3] = {o.src, o.ip[1], o.ip[2]};
+            int n_wf_opnd = 0;
+            for (int k = 0; k < 3; ++k) {
+                if (opnd[k] < 0) continue;
+                if (!check_slot(P, opnd[k]) || slot_len[opnd[k]] != slot_len[o.dst])
+                    return fail(DSP_ERR_ARG, "op %d: ELEMENTWISE operand %d is not a waveform of the length of the result", i, k);
+                ++n_wf_opnd;
+            }
+            if (!n_wf_opnd) return fail(DSP_ERR_ARG, "op %d: ELEMENTWISE needs a waveform operand (DSP_OP_SCALAR_FUNC otherwise)", i);
+            break;
+        }
+        case DSP_OP_SCALAR_FUNC:
+            if (o.dst < 0 || o.dst >= n_sregs || !fn_code_ok(o.ip[0], f64, i64)) return fail(DSP_ERR_ARG, "op %d: bad SCALAR_FUNC", i);
+            break;
+        case DSP_OP_CONVOLVE:
+        case DSP_OP_CONVOLVE_AMAX: return lower_convolve(c, i, o, d);
+        case DSP_OP_SCALAR_AFFINE:
+        case DSP_OP_SCALAR_DIV:
+            if (o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad scalar arithmetic op", i);
+            break;
+        case DSP_OP_SCALAR_CONVERT:
+            if (o.dst < 0 || o.dst >= n_sregs || o.ip[0] < 0 || o.ip[0] > 4 || o.sp[3].kind != DSP_ARG_CONST)
+                return fail(DSP_ERR_ARG, "op %d: bad SCALAR_CONVERT (ip[0] = rounding 0..4, sp[3] = constant period ratio)", i);
+            break;
+        default: return fail(DSP_ERR_ARG, "op %d: unknown opcode %d", i, o.opcode);
+    }
+    return DSP_OK;
+}
+
+// ---- ops: the device program, an op of the caller's after the other, each behind the clearing ops of the shared slots it is the first to use
+static int lower_ops(PlanCtx& c) {
+    DevProgram& P = c.ch->host;
+    c.dev_index.assign(c.n_ops, 0);
+    for (int i = 0; i < c.n_ops; ++i) {
+        const dsp_op& o = c.ops[i];
+        for (int s = 0; s < c.n_slots; ++s)
+            if (c.shares[s] && c.first_op[s] == i) {
+                DevOp& z = P.ops[c.n_dev_ops++];
                 memset(&z, 0, sizeof z);
                 z.opcode = DSP_OP_INTERNAL_ZERO;
                 z.dst = s;
-                z.ic[0] = base[s];
-                z.ic[1] = foot[s];
+                z.ic[0] = c.base[s];
+                z.ic[1] = c.foot[s];
             }
-        dev_index[i] = n_dev_ops;
-        DevOp& d = P.ops[n_dev_ops++];
+        c.dev_index[i] = c.n_dev_ops;
+        DevOp& d = P.ops[c.n_dev_ops++];
         memset(&d, 0, sizeof d);
         d.opcode = o.opcode;
         d.dst = o.dst;
@@ -1061,293 +1433,25 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
         memcpy(d.sp, o.sp, sizeof d.sp);
         for (int k = 0; k < 4; ++k) {
             const dsp_scalar_arg& a = o.sp[k];
-            if (a.kind == DSP_ARG_INPUT && (a.index < 0 || a.index >= n_io || io[a.index].kind != DSP_IO_SCALAR_IN))
+            if (a.kind == DSP_ARG_INPUT && (a.index < 0 || a.index >= c.n_io || c.io[a.index].kind != DSP_IO_SCALAR_IN))
                 return fail(DSP_ERR_ARG, "op %d: scalar operand %d is not a scalar input binding", i, k);
-            if (a.kind == DSP_ARG_REG && (a.index < 0 || a.index >= n_sregs)) return fail(DSP_ERR_ARG, "op %d: bad scalar register", i);
+            if (a.kind == DSP_ARG_REG && (a.index < 0 || a.index >= c.n_sregs)) return fail(DSP_ERR_ARG, "op %d: bad scalar register", i);
             if (a.kind < DSP_ARG_CONST || a.kind > DSP_ARG_REG) return fail(DSP_ERR_ARG, "op %d: bad scalar operand kind", i);
         }
-        auto need_io = [&](int kind) { return o.io >= 0 && o.io < n_io && io[o.io].kind == kind; };
-        // the float32 loop receives float32 scalars, the float64 loop float64 ones
-        auto cst = [&](int k) { return f64 ? o.sp[k].value : (double)(float)o.sp[k].value; };
-        switch (o.opcode) {
-            case DSP_OP_LOAD:
-                if (!check_slot(P, o.dst) || !need_io(DSP_IO_WF_IN)) return fail(DSP_ERR_ARG, "op %d: bad LOAD", i);
-                if (io[o.io].len != slot_len[o.dst]) return fail(DSP_ERR_ARG, "op %d: LOAD length mismatch", i);
-                if (o.ip[0] < 0 || o.ip[1] < 0 || o.ip[0] > io[o.io].offset || (int64_t)io[o.io].offset + io[o.io].len + o.ip[1] > io[o.io].row_stride)
-                    return fail(DSP_ERR_ARG, "op %d: LOAD screens samples outside the row (ip[0], ip[1])", i);
-                break;
-            case DSP_OP_STORE:
-                if (!check_slot(P, o.src) || !need_io(DSP_IO_WF_OUT)) return fail(DSP_ERR_ARG, "op %d: bad STORE", i);
-                if (io[o.io].len != slot_len[o.src]) return fail(DSP_ERR_ARG, "op %d: STORE length mismatch", i);
-                break;
-            case DSP_OP_STORE_SCALAR:
-                if (!need_io(DSP_IO_SCALAR_OUT) || o.ip[0] < 0 || o.ip[0] >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad STORE_SCALAR", i);
-                break;
-            case DSP_OP_BL_SUBTRACT:
-            case DSP_OP_MIN_MAX_NORM:
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || slot_len[o.src] != slot_len[o.dst])
-                    return fail(DSP_ERR_ARG, "op %d: bad element-wise op", i);
-                break;
-            case DSP_OP_POLE_ZERO: {
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || slot_len[o.src] != slot_len[o.dst])
-                    return fail(DSP_ERR_ARG, "op %d: bad POLE_ZERO", i);
-                if (o.sp[0].kind != DSP_ARG_CONST) {  // one tau per event: the constant is formed on the device (op_pole_zero)
-                    d.ic[1] = 1;
-                    break;
-                }
-                const double tau = cst(0);
-                d.ic[0] = std::isnan(tau) ? 1 : 0;
-                d.fc[0] = std::exp(-1.0 / tau);  // pole_zero.py:60 -- float64 via libm, like numba's lowering
-                break;
-            }
-            case DSP_OP_DOUBLE_POLE_ZERO: {
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || slot_len[o.src] != slot_len[o.dst])
-                    return fail(DSP_ERR_ARG, "op %d: bad DOUBLE_POLE_ZERO", i);
-                bool per_event = false;
-                for (int k = 0; k < 3; ++k) per_event |= o.sp[k].kind != DSP_ARG_CONST;
-                if (per_event) {  // a time constant or the fraction per event: coefficients and scan matrices are formed on the device
-                    if (slot_len[o.src] <= 3) return fail(DSP_E_DPZ_SHORT, "%s", dsp_fatal_message(DSP_E_DPZ_SHORT));
-                    d.ic[1] = 1;
-                    break;
-                }
-                const double tau1 = cst(0), tau2 = cst(1), fr = cst(2);
-                d.ic[0] = (std::isnan(tau1) || std::isnan(tau2) || std::isnan(fr)) ? 1 : 0;
-                if (!d.ic[0] && slot_len[o.src] <= 3) return fail(DSP_E_DPZ_SHORT, "%s", dsp_fatal_message(DSP_E_DPZ_SHORT));
-                if (slot_len[o.src] <= 3) d.ic[0] = 1;
-                const double a = std::exp(-1.0 / tau1), b = std::exp(-1.0 / tau2);  // pole_zero.py:168-174
-                const double den1 = ((fr * b - fr * a) - b) - 1.0;
-                const double den2 = -1.0 * ((fr * b - fr * a) - b);
-                const double num1 = -1.0 * (a + b);
-                const double num2 = a * b;
-                d.fc[0] = num1;
-                d.fc[1] = num2;
-                d.fc[2] = den1;
-                d.fc[3] = den2;
-                // M^(C*2^d), d = 0..5, M = [[-den1, -den2], [1, 0]]
-                long double M[4] = {-(long double)den1, -(long double)den2, 1.0L, 0.0L}, Pw[4] = {1, 0, 0, 1};
-                const int C = P.slots[o.src].C;
-                long double base[4];
-                memcpy(base, M, sizeof base);
-                for (int e = C; e; e >>= 1) {  // Pw = M^C
-                    if (e & 1) mat2_mul(Pw, base, Pw);
-                    mat2_mul(base, base, base);
-                }
-                for (int dd = 0; dd < 6; ++dd) {
-                    for (int k = 0; k < 4; ++k) d.fc[4 + 4 * dd + k] = (double)Pw[k];
-                    mat2_mul(Pw, Pw, Pw);
-                }
-                break;
-            }
-            case DSP_OP_TRAP_FILTER:
-            case DSP_OP_TRAP_NORM:
-            case DSP_OP_ASYM_TRAP: {
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst || slot_len[o.src] != slot_len[o.dst])
-                    return fail(DSP_ERR_ARG, "op %d: bad trapezoid (source and destination slots must differ)", i);
-                int rc = setup_trap(d, o.opcode, o.ip[0], o.ip[1], o.ip[2], slot_len[o.src], P.slots[o.src].C);
-                if (rc) return fail(rc, "%s", dsp_fatal_message(rc));
-                break;
-            }
-            case DSP_OP_TRAP_PICKOFF: {
-                if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad TRAP_PICKOFF", i);
-                if (o.ip[3] != DSP_OP_TRAP_FILTER && o.ip[3] != DSP_OP_TRAP_NORM && o.ip[3] != DSP_OP_ASYM_TRAP)
-                    return fail(DSP_ERR_ARG, "op %d: TRAP_PICKOFF ip[3] must name a trapezoid opcode", i);
-                if (o.io == 's')
-                    return fail(DSP_ERR_UNSUPPORTED, "TRAP_PICKOFF cannot take mode 's' (the spline needs the whole filtered waveform): use TRAP_FILTER + PICKOFF");
-                int rc = setup_trap(d, o.ip[3], o.ip[0], o.ip[1], o.ip[2], slot_len[o.src], P.slots[o.src].C);
-                if (rc) return fail(rc, "%s", dsp_fatal_message(rc));
-                break;
-            }
-            case DSP_OP_TRAP_REDUCE: {
-                if (!check_slot(P, o.src) || (o.dst < 0 && o.io < 0) || (o.dst >= 0 && o.dst > n_sregs - 4) || o.io >= n_sregs)
-                    return fail(DSP_ERR_ARG, "op %d: bad TRAP_REDUCE", i);
-                const int tk = o.ip[3] & 0xff, pk_mode = (o.ip[3] >> 8) & 0xff, pk_reg = ((o.ip[3] >> 16) & 0x3fff) - 1;
-                if (tk != DSP_OP_TRAP_FILTER && tk != DSP_OP_TRAP_NORM && tk != DSP_OP_ASYM_TRAP)
-                    return fail(DSP_ERR_ARG, "op %d: TRAP_REDUCE ip[3] must name a trapezoid opcode", i);
-                if (pk_reg >= n_sregs || (pk_reg >= 0 && (pk_mode == 0 || pk_mode == 's')) || (pk_reg < 0 && pk_mode != 0))
-                    return fail(DSP_ERR_ARG, "op %d: bad pick-off in TRAP_REDUCE (register %d, mode %d)", i, pk_reg, pk_mode);
-                if (((o.ip[3] >> 30) & 1) && (o.dst < 0 || tk == DSP_OP_ASYM_TRAP))
-                    return fail(DSP_ERR_ARG, "op %d: TRAP_REDUCE amax-only needs the min_max registers and trap_filter / trap_norm", i);
-                int rc = setup_trap(d, tk, o.ip[0], o.ip[1], o.ip[2], slot_len[o.src], P.slots[o.src].C);
-                if (rc) return fail(rc, "%s", dsp_fatal_message(rc));
-                break;
-            }
-            case DSP_OP_PICKOFF:
-                if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad PICKOFF", i);
-                if (o.ip[1] < 0 || o.ip[1] > 2) return fail(DSP_ERR_ARG, "op %d: PICKOFF ip[1] must be 0, 1 or 2", i);
-                if (o.ip[1] == 2 && o.sp[1].kind != DSP_ARG_CONST) return fail(DSP_ERR_ARG, "op %d: PICKOFF ip[1] = 2 takes a constant default (sp[1])", i);
-                if (o.ip[1] == 1 && (o.sp[0].kind != DSP_ARG_CONST || o.sp[0].value < 0 || o.sp[0].value >= slot_len[o.src] ||
-                                     o.sp[0].value != std::floor(o.sp[0].value)))
-                    return fail(DSP_ERR_ARG, "op %d: PICKOFF of one sample (ip[1] = 1) needs a constant index inside the waveform", i);
-                break;
-            case DSP_OP_TIME_POINT_THRESH:
-            case DSP_OP_INTERP_TIME_POINT_THRESH:
-                if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad TIME_POINT_THRESH", i);
-                break;
-            case DSP_OP_MEAN_BELOW:
-                if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad MEAN_BELOW", i);
-                break;
-            case DSP_OP_WINDOWER:
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst) return fail(DSP_ERR_ARG, "op %d: bad WINDOWER", i);
-                if (slot_len[o.dst] >= slot_len[o.src]) return fail(DSP_E_WINDOW_LONG, "%s", dsp_fatal_message(DSP_E_WINDOW_LONG));
-                break;
-            case DSP_OP_AVG_CURRENT: {
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst) return fail(DSP_ERR_ARG, "op %d: bad AVG_CURRENT", i);
-                if (o.sp[0].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "avg_current: the window length must be a constant");
-                const double length = f64 ? o.sp[0].value : (double)(float)o.sp[0].value;
-                const int n = slot_len[o.src];
-                if (!(length >= 0) || !(length < (double)n)) return fail(DSP_E_AVGCUR_RANGE, "%s", dsp_fatal_message(DSP_E_AVGCUR_RANGE));
-                const int L = (int)length;
-                if (L <= 0 || slot_len[o.dst] != n - L)
-                    return fail(DSP_ERR_ARG, "avg_current: the output must hold len(w_in) - int(length) = %d samples (it holds %d)", n - L,
-                                slot_len[o.dst]);
-                d.ic[0] = L;
-                d.fc[0] = length;
-                break;
-            }
-            case DSP_OP_UPSAMPLER: {
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst) return fail(DSP_ERR_ARG, "op %d: bad UPSAMPLER", i);
-                if (o.sp[0].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "upsampler: the factor must be a constant");
-                const double up = f64 ? o.sp[0].value : (double)(float)o.sp[0].value;
-                if (!(up > 0)) return fail(DSP_E_UPSAMPLE, "%s", dsp_fatal_message(DSP_E_UPSAMPLE));
-                d.fc[0] = up;
-                d.fc[1] = floor(up / 2.0);
-                d.ic[0] = (int)up;
-                break;
-            }
-            case DSP_OP_MOVING_WINDOW_MULTI: {
-                const bool in_place = o.ip[3] == 1;
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || (o.src == o.dst) != in_place || slot_len[o.src] != slot_len[o.dst])
-                    return fail(DSP_ERR_ARG, "op %d: bad MOVING_WINDOW_MULTI", i);
-                if (o.sp[0].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "moving_window_multi: the window length must be a constant");
-                const double length = f64 ? o.sp[0].value : (double)(float)o.sp[0].value;
-                const int num = o.ip[1], n = slot_len[o.src];
-                if (floor(length) != length) return fail(DSP_E_MW_LEN_INT, "%s", dsp_fatal_message(DSP_E_MW_LEN_INT));
-                if ((long long)length < 0 || (long long)length >= n) return fail(DSP_E_MW_LEN_RANGE, "%s", dsp_fatal_message(DSP_E_MW_LEN_RANGE));
-                if (num < 0) return fail(DSP_E_MW_NUM_NEG, "%s", dsp_fatal_message(DSP_E_MW_NUM_NEG));
-                if (num > 0 && (long long)length == 0) return fail(DSP_E_ZERODIV, "%s", dsp_fatal_message(DSP_E_ZERODIV));
-                // (the scratch may be the source itself when the number of windows is odd: the first pass goes source -> target, so the
-                // source is free from the second pass on -- and is overwritten)
-                if (in_place) {  // ip[2]: a side slot for the ends of the chunks, 64 lanes x (L | 1) elements; the window inside one chunk
-                    const long long Lw = (long long)length;
-                    if (!check_slot(P, o.ip[2]) || o.ip[2] == o.src || Lw > P.slots[o.src].C || 64 * (Lw | 1) > 64LL * P.slots[o.ip[2]].pitch)
-                        return fail(DSP_ERR_ARG, "op %d: MOVING_WINDOW_MULTI in place needs a window of at most %d samples and a side slot of 64 x window samples (ip[2])",
-                                    i, P.slots[o.src].C);
-                } else
-                if (num > 1 && (!check_slot(P, o.ip[2]) || (o.ip[2] == o.src && num % 2 == 0) || o.ip[2] == o.dst || slot_len[o.ip[2]] != n))
-                    return fail(DSP_ERR_ARG, "op %d: MOVING_WINDOW_MULTI with several windows needs a scratch slot of the same length (ip[2])", i);
-                d.ic[0] = (int)length;
-                d.ic[1] = num;
-                d.ic[2] = o.ip[0];
-                d.fc[0] = length;
-                break;
-            }
-            case DSP_OP_TRAP_WINDOW_PICKOFF: {
-                if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad TRAP_WINDOW_PICKOFF", i);
-                const int rise = o.ip[0], flat = o.ip[1];
-                if (rise < 0) return fail(DSP_E_TRAP_RISE, "%s", dsp_fatal_message(DSP_E_TRAP_RISE));
-                if (flat < 0) return fail(DSP_E_TRAP_FLAT, "%s", dsp_fatal_message(DSP_E_TRAP_FLAT));
-                if (2 * (long long)rise + flat > slot_len[o.src]) return fail(DSP_E_TRAP_WIDE, "%s", dsp_fatal_message(DSP_E_TRAP_WIDE));
-                break;
-            }
-            case DSP_OP_MIN_MAX:
-                if (!check_slot(P, o.src) || o.dst < 0 || o.dst > n_sregs - 4) return fail(DSP_ERR_ARG, "op %d: bad MIN_MAX", i);
-                break;
-            case DSP_OP_LINEAR_SLOPE_FIT: {
-                if (!check_slot(P, o.src) || o.dst < 0 || o.dst > n_sregs - 4) return fail(DSP_ERR_ARG, "op %d: bad LINEAR_SLOPE_FIT", i);
-                const int first = o.ip[0];
-                if (first < 0 || first > slot_len[o.src]) return fail(DSP_ERR_ARG, "op %d: LINEAR_SLOPE_FIT slice out of range", i);
-                const int count = o.ip[1] > 0 ? o.ip[1] : slot_len[o.src] - first;  // ip[1] == 0: to the end of the slot
-                if (count < 0 || count > slot_len[o.src] - first) return fail(DSP_ERR_ARG, "op %d: LINEAR_SLOPE_FIT slice out of range", i);
-                if (count < 2) return fail(DSP_E_ZERODIV, "%s", dsp_fatal_message(DSP_E_ZERODIV));  // the line fit's denominator
-                d.ic[0] = first;
-                d.ic[1] = count;
-                break;
-            }
-            case DSP_OP_AMAX:
-                if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad AMAX", i);
-                break;
-            case DSP_OP_DWT_HAAR: {
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || !check_slot(P, o.ip[2]) || o.dst == o.src || o.dst == o.ip[2])
-                    return fail(DSP_ERR_ARG, "op %d: bad DWT_HAAR slots", i);
-                if (o.ip[0] <= 0) return fail(DSP_E_DWT_LEVEL, "%s", dsp_fatal_message(DSP_E_DWT_LEVEL));
-                if (o.ip[1] != 'a' && o.ip[1] != 'd') return fail(DSP_ERR_ARG, "op %d: DWT coefficient must be 'a' or 'd'", i);
-                int len = slot_len[o.src];
-                if (slot_len[o.ip[2]] < (len + 1) / 2 && o.ip[0] > 1) return fail(DSP_ERR_ARG, "op %d: DWT scratch slot too small", i);
-                for (int l = 0; l < o.ip[0]; ++l) len = (len + 1) / 2;
-                if (len != slot_len[o.dst]) return fail(DSP_E_DWT_OUTLEN, "%s (got %d, expect %d)", dsp_fatal_message(DSP_E_DWT_OUTLEN), slot_len[o.dst], len);
-                break;
-            }
-            case DSP_OP_COPY: {  // dst[k] = src[ip[0] + k * step], step = ip[1] (0 means 1; negative: backwards)
-                const int64_t step = o.ip[1] != 0 ? o.ip[1] : 1;
-                const int64_t last = check_slot(P, o.dst) ? (int64_t)o.ip[0] + (int64_t)(slot_len[o.dst] - 1) * step : -1;
-                if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.src == o.dst || o.ip[0] < 0 || o.ip[0] >= slot_len[o.src] || last < 0 ||
-                    last >= slot_len[o.src])
-                    return fail(DSP_ERR_ARG, "op %d: bad COPY", i);
-                break;
-            }
-            case DSP_OP_ELEMENTWISE: {
-                if (!check_slot(P, o.dst) || !fn_code_ok(o.ip[0], f64)) return fail(DSP_ERR_ARG, "op %d: bad ELEMENTWISE", i);
-                const int opnd[3] = {o.src, o.ip[1], o.ip[2]};
-                int n_wf_opnd = 0;
-                for (int k = 0; k < 3; ++k) {
-                    if (opnd[k] < 0) continue;
-                    if (!check_slot(P, opnd[k]) || slot_len[opnd[k]] != slot_len[o.dst])
-                        return fail(DSP_ERR_ARG, "op %d: ELEMENTWISE operand %d is not a waveform of the length of the result", i, k);
-                    ++n_wf_opnd;
-                }
-                if (!n_wf_opnd) return fail(DSP_ERR_ARG, "op %d: ELEMENTWISE needs a waveform operand (DSP_OP_SCALAR_FUNC otherwise)", i);
-                break;
-            }
-            case DSP_OP_SCALAR_FUNC:
-                if (o.dst < 0 || o.dst >= n_sregs || !fn_code_ok(o.ip[0], f64, i64)) return fail(DSP_ERR_ARG, "op %d: bad SCALAR_FUNC", i);
-                break;
-            case DSP_OP_CONVOLVE:
-            case DSP_OP_CONVOLVE_AMAX: {
-                const bool fusedmax = o.opcode == DSP_OP_CONVOLVE_AMAX;
-                if (!check_slot(P, o.src) || !need_io(DSP_IO_TAPS)) return fail(DSP_ERR_ARG, "op %d: bad CONVOLVE", i);
-                if (fusedmax ? (o.dst < 0 || o.dst >= n_sregs || o.ip[2] <= 0) : (!check_slot(P, o.dst) || o.src == o.dst))
-                    return fail(DSP_ERR_ARG, "op %d: bad CONVOLVE destination", i);
-                // ip[3] > 0: the kernel has ip[3] taps and the binding holds zeros after them (up to a multiple of the tap block, so the
-                // blocked path covers every tap; the op falls back to the true length for a waveform with an infinity in it: 0 * inf)
-                if (o.ip[3] < 0 || o.ip[3] > io[o.io].len) return fail(DSP_ERR_ARG, "op %d: CONVOLVE kernel length beyond its binding", i);
-                const int m = o.ip[3] > 0 ? o.ip[3] : io[o.io].len;
-                const int n = slot_len[o.src], p = fusedmax ? o.ip[2] : slot_len[o.dst], mode = o.ip[0];
-                d.ic[1] = m;
-                d.ic[6] = io[o.io].len;
-                d.ic[2] = (o.ip[1] & 1) ? 1 : 0;  // caller found a NaN among the taps -> output NaN (convolutions.py:45-46)
-                d.ic[5] = (o.ip[1] & 2) ? 1 : 0;  // ... an infinity: 0 * inf is NaN, so windows must not reach into the zero margins
-                d.ic[3] = p;
-                if (m > n) return fail(DSP_E_CONV_LONG, "%s", dsp_fatal_message(DSP_E_CONV_LONG));
-                if (mode == 'f') {
-                    if (p != n + m - 1) return fail(DSP_E_CONV_OUTLEN, "Output waveform has length %d; expect %d", p, n + m - 1);
-                    d.ic[0] = 0;
-                } else if (mode == 'v') {
-                    if (p != n - m + 1) return fail(DSP_E_CONV_OUTLEN, "Output waveform has length %d; expect %d", p, n - m + 1);
-                    d.ic[0] = m - 1;
-                } else if (mode == 's') {
-                    if (p != n) return fail(DSP_E_CONV_OUTLEN, "Output waveform has length %d; expect %d", p, n);
-                    d.ic[0] = (m - 1) / 2;
-                } else {
-                    return fail(DSP_E_CONV_MODE, "%s", dsp_fatal_message(DSP_E_CONV_MODE));
-                }
-                break;
-            }
-            case DSP_OP_SCALAR_AFFINE:
-            case DSP_OP_SCALAR_DIV:
-                if (o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad scalar arithmetic op", i);
-                break;
-            case DSP_OP_SCALAR_CONVERT:
-                if (o.dst < 0 || o.dst >= n_sregs || o.ip[0] < 0 || o.ip[0] > 4 || o.sp[3].kind != DSP_ARG_CONST)
-                    return fail(DSP_ERR_ARG, "op %d: bad SCALAR_CONVERT (ip[0] = rounding 0..4, sp[3] = constant period ratio)", i);
-                break;
-            default: return fail(DSP_ERR_ARG, "op %d: unknown opcode %d", i, o.opcode);
-        }
+        if (const int rc = lower_op(c, i, o, d)) return rc;
     }
-    // LOAD s; BL_SUBTRACT s <- s (what nearly every recipe starts with): the load subtracts while it writes the samples to LDS and the
-    // second op becomes a no-op -- one pass over the waveform in LDS less.  Same results: one float subtraction per sample in the loop's
-    // type, and the NaN rule of bl_subtract.py:41-44 (a NaN anywhere, or a NaN baseline: a NaN waveform) is the load's own flag.
-    for (int i = 0; i + 1 < n_ops; ++i) {
-        const dsp_op &ld = ops[i], &bs = ops[i + 1];
+    P.n_ops = c.n_dev_ops;
+    return DSP_OK;
+}
+
+// LOAD s; BL_SUBTRACT s <- s (what nearly every recipe starts with): the load subtracts while it writes the samples to LDS and the
+// second op becomes a no-op -- one pass over the waveform in LDS less.  Same results: one float subtraction per sample in the loop's
+// type, and the NaN rule of bl_subtract.py:41-44 (a NaN anywhere, or a NaN baseline: a NaN waveform) is the load's own flag.
+static void fold_load_bl_subtract(PlanCtx& c) {
+    DevProgram& P = c.ch->host;
+    const std::vector<int>& dev_index = c.dev_index;
+    for (int i = 0; i + 1 < c.n_ops; ++i) {
+        const dsp_op &ld = c.ops[i], &bs = c.ops[i + 1];
         if (ld.opcode == DSP_OP_LOAD && bs.opcode == DSP_OP_BL_SUBTRACT && bs.src == ld.dst && bs.dst == ld.dst && bs.ip[0] == 0 &&
             dev_index[i + 1] == dev_index[i] + 1) {
             DevOp& L = P.ops[dev_index[i]];
@@ -1357,372 +1461,372 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
             B.opcode = DSP_OP_INTERNAL_NOP;
         }
     }
-    P.n_ops = n_dev_ops;
+}
 
-    // ---- does the program have the shape LOAD [-> BL_SUBTRACT] -> POLE_ZERO -> TRAP_PICKOFF -> STORE_SCALAR on one slot?
-    {
-        int i = 0;
-        const dsp_op* ld = (n_ops > i && ops[i].opcode == DSP_OP_LOAD) ? &ops[i++] : nullptr;
-        const dsp_op* bs = (ld && n_ops > i && ops[i].opcode == DSP_OP_BL_SUBTRACT) ? &ops[i++] : nullptr;
-        const dsp_op* pz = (ld && n_ops > i && ops[i].opcode == DSP_OP_POLE_ZERO) ? &ops[i++] : nullptr;
-        const dsp_op* tp = (pz && n_ops > i && ops[i].opcode == DSP_OP_TRAP_PICKOFF) ? &ops[i++] : nullptr;
-        const dsp_op* st = (tp && n_ops > i && ops[i].opcode == DSP_OP_STORE_SCALAR) ? &ops[i++] : nullptr;
-        const int wdt = ld ? io[ld->io].dtype : -1;
-        // (a time constant per event, a float32 column: the register-resident kernel's TAU builds form exp(-1/tau) per row like the interpreter's op)
-        const bool tau_col = pz && pz->sp[0].kind == DSP_ARG_INPUT && io[pz->sp[0].index].dtype == DSP_F32;
-        const bool shape = !f64 && st && i == n_ops && n_slots == 1 && ld->ip[0] == 0 && ld->ip[1] == 0 && (wdt == DSP_F32 || wdt == DSP_I16 || wdt == DSP_U16) && P.io[ld->io].vec_ok &&
-                           (!bs || (bs->dst == 0 && bs->src == 0 && bs->sp[0].kind != DSP_ARG_REG)) && pz->dst == 0 && pz->src == 0 &&
-                           (pz->sp[0].kind == DSP_ARG_CONST || tau_col) &&
-                           tp->src == 0 && tp->sp[0].kind != DSP_ARG_REG && st->ip[0] == tp->dst &&
-                           (slot_len[0] == 1024 || slot_len[0] == 2048 || slot_len[0] == 4096 || slot_len[0] == 8192);
-        if (!shape && st && i == n_ops && n_slots == 1) {  // the ops of the energy chain, but not the kernels' case of it
-            if (f64) note(ch, "the energy chain in a float64 loop: the fused energy kernels are float32");
-            else if (pz->sp[0].kind != DSP_ARG_CONST && !tau_col)
-                note(ch, "a pole-zero time constant per event that is not a float32 column: the fused energy kernels take a constant or such a column");
-            else if (!(slot_len[0] == 1024 || slot_len[0] == 2048 || slot_len[0] == 4096 || slot_len[0] == 8192))
-                note(ch, "waveforms of %d samples: the fused energy kernels take 1024, 2048, 4096 or 8192", slot_len[0]);
-            else if (!P.io[ld->io].vec_ok) note(ch, "rows that do not start on 16-byte boundaries: the fused energy kernels read 16 bytes per lane");
-        }
-        auto f32_col = [&](const dsp_scalar_arg& a) { return a.kind != DSP_ARG_INPUT || io[a.index].dtype == DSP_F32; };
-        if (shape && (!bs || f32_col(bs->sp[0])) && f32_col(tp->sp[0]) && io[st->io].dtype == DSP_F32) {  // (the kernels store a float)
-            EnergyArgs& F = ch->fused;
-            const DevOp& dpz = P.ops[dev_index[pz - ops]];
-            const DevOp& dtp = P.ops[dev_index[tp - ops]];
-            F.wf_stride = io[ld->io].row_stride;
-            F.wf_offset = io[ld->io].offset;
-            F.len = slot_len[0];
-            F.has_bl = bs ? 1 : 0;
-            if (bs) {
-                if (bs->sp[0].kind == DSP_ARG_INPUT) {
-                    ch->io_bl = bs->sp[0].index;
-                    F.bl_stride = io[ch->io_bl].row_stride;
-                } else {
-                    F.bl_const = (float)bs->sp[0].value;
-                }
-            }
-            if (tp->sp[0].kind == DSP_ARG_INPUT) {
-                ch->io_tp = tp->sp[0].index;
-                F.tp_stride = io[ch->io_tp].row_stride;
-            } else {
-                F.tp_const = (float)tp->sp[0].value;
-            }
-            F.mode = tp->io;
-            F.out_stride = io[st->io].row_stride;
-            F.c = dpz.fc[0];
-            F.tau_nan = dpz.ic[0];
-            F.rr = dtp.fc[0];
-            F.ll = dtp.fc[1];
-            F.all_nan = dtp.ic[9];
-            F.C = P.slots[0].C;
-            F.pitch = P.slots[0].pitch;
-            F.invC = P.slots[0].invC;
-            for (int k = 0; k < 3; ++k) {
-                F.q[k] = dtp.ic[3 + k];
-                F.rho[k] = dtp.ic[6 + k];
-            }
-            F.lds_elems_per_wave = P.lds_elems_per_wave;
-            F.slot_off = P.slots[0].off;
-#ifdef DSPEED_HIP_DIAG
-            if (const char* ab = getenv("DSPEED_HIP_ABLATE")) F.ablate = atoi(ab);  // diagnostic library only: skip passes / stamp phases
-#endif
-            ch->io_wf = ld->io;
-            ch->io_out = st->io;
-            ch->fused_trap = tp->ip[3];
-            ch->fused_npf = slot_len[0] / 256;          // one wavefront per waveform: len == 256 * npf, npf in {4, 8, 16}
-            ch->fused_ok = slot_len[0] <= 4096 && wdt == DSP_F32 && !tau_col;  // the classic kernel reads float32 rows only, one time constant
-            if (tau_col) {
-                ch->io_tau = pz->sp[0].index;
-                F.tau_stride = io[ch->io_tau].row_stride;
-            }
-            ch->wf_dtype = wdt;
-            const char* env = getenv("DSPEED_HIP_NO_FUSED");
-            ch->fused_on = !(env && env[0] == '1');
-            {  // register-resident kernel: C = len/64 + 2 samples per lane (an even pitch: every lane's chunk is 8-byte aligned), linear LDS
-               // image of the waveform (1024 .. 8192 samples); a chunk is (C - 2) / 8 groups of 8 samples and a two-sample tail
-                EnergyArgs& I = ch->rr;
-                I = F;
-                const int Ci = slot_len[0] / 64 + 2;
-                I.C = Ci;
-                I.pitch = Ci;
-                I.invC = 1.0f / (float)Ci;
-                int guard = 2 * Ci + 8;  // zeros below the image: lagged reads before sample 0 (an odd lag's pairs start one element lower: covered)
-                guard = ((guard + 3) / 4) * 4;  // (the image stays 16-byte aligned)
-                I.slot_off = guard;
-                const int ng1 = (Ci - 2) / 8 + 1, auxp = ng1 <= 9 ? 9 : (ng1 | 1);
-                int elems = guard + 64 * Ci + 16 + 64 * auxp + 32;  // image, tail, per-lane side array (auxp per lane), capture buffer (2 x 16)
-                elems = ((elems + 3) / 4) * 4;
-                I.lds_elems_per_wave = elems;
-                ch->rr_lds_bytes = elems * 4;
-                for (int k = 0; k < 3; ++k) {
-                    I.q[k] = dtp.ic[k];  // the lags themselves
-                    I.rho[k] = 0;
-                }
-                for (int S = 1; S <= 2; ++S) {
-                    const int CS = (Ci - 2) / S;
-                    for (int k = 0; k < 3; ++k)
-                        for (int sidx = 0; sidx < S; ++sidx) {
-                            const int pos = sidx * CS - dtp.ic[k];          // samples before the sub-chain start, relative to the chunk
-                            const int r = ((pos % Ci) + Ci) % Ci;           // ... = r samples into the chunk of the lane `shift` below
-                            const int shift = (r - pos) / Ci;
-                            int cs = r / CS;
-                            if (cs > S - 1) cs = S - 1;
-                            ch->plan[S - 1].shift[k][sidx] = shift;
-                            ch->plan[S - 1].cs[k][sidx] = cs;
-                            ch->plan[S - 1].local[k][sidx] = r - cs * CS;
-                        }
-                }
-                ch->rr_ok = true;
-                ch->variant = 6;
-                if (const char* venv = getenv("DSPEED_HIP_VARIANT")) ch->variant = atoi(venv);  // A/B runs: 1, 6, 8
-                if (ch->variant != 1 && ch->variant != 8) ch->variant = 6;
-            }
-        }
+// Register-resident kernel: C = len/64 + 2 samples per lane (an even pitch: every lane's chunk is 8-byte aligned), linear LDS
+// image of the waveform (1024 .. 8192 samples); a chunk is (C - 2) / 8 groups of 8 samples and a two-sample tail
+static void plan_energy_rr(PlanCtx& c, const DevOp& dtp) {
+    ChainPlan* ch = c.ch;
+    EnergyArgs& I = ch->rr;
+    I = ch->fused;
+    const int Ci = c.slot_len[0] / 64 + 2;
+    I.C = Ci;
+    I.pitch = Ci;
+    I.invC = 1.0f / (float)Ci;
+    int guard = 2 * Ci + 8;  // zeros below the image: lagged reads before sample 0 (an odd lag's pairs start one element lower: covered)
+    guard = ((guard + 3) / 4) * 4;  // (the image stays 16-byte aligned)
+    I.slot_off = guard;
+    const int ng1 = (Ci - 2) / 8 + 1, auxp = ng1 <= 9 ? 9 : (ng1 | 1);
+    int elems = guard + 64 * Ci + 16 + 64 * auxp + 32;  // image, tail, per-lane side array (auxp per lane), capture buffer (2 x 16)
+    elems = ((elems + 3) / 4) * 4;
+    I.lds_elems_per_wave = elems;
+    ch->rr_lds_bytes = elems * 4;
+    for (int k = 0; k < 3; ++k) {
+        I.q[k] = dtp.ic[k];  // the lags themselves
+        I.rho[k] = 0;
     }
+    for (int S = 1; S <= 2; ++S) {
+        const int CS = (Ci - 2) / S;
+        for (int k = 0; k < 3; ++k)
+            for (int sidx = 0; sidx < S; ++sidx) {
+                const int pos = sidx * CS - dtp.ic[k];          // samples before the sub-chain start, relative to the chunk
+                const int r = ((pos % Ci) + Ci) % Ci;           // ... = r samples into the chunk of the lane `shift` below
+                const int shift = (r - pos) / Ci;
+                int cs = r / CS;
+                if (cs > S - 1) cs = S - 1;
+                ch->plan[S - 1].shift[k][sidx] = shift;
+                ch->plan[S - 1].cs[k][sidx] = cs;
+                ch->plan[S - 1].local[k][sidx] = r - cs * CS;
+            }
+    }
+    ch->rr_ok = true;
+    ch->variant = 6;
+    if (const char* venv = getenv("DSPEED_HIP_VARIANT")) ch->variant = atoi(venv);  // A/B runs: 1, 6, 8
+    if (ch->variant != 1 && ch->variant != 8) ch->variant = 6;
+}
 
-    ch->fir_ok = match_fir_shape(ch, ops, n_ops, io, slot_len, n_slots, f64);
+// ---- does the program have the shape LOAD [-> BL_SUBTRACT] -> POLE_ZERO -> TRAP_PICKOFF -> STORE_SCALAR on one slot?
+static void match_energy_shape(PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const DevProgram& P = ch->host;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int32_t* slot_len = c.slot_len;
+    const int n_ops = c.n_ops, n_slots = c.n_slots;
+    const bool f64 = c.f64;
+    int i = 0;
+    const dsp_op* ld = (n_ops > i && ops[i].opcode == DSP_OP_LOAD) ? &ops[i++] : nullptr;
+    const dsp_op* bs = (ld && n_ops > i && ops[i].opcode == DSP_OP_BL_SUBTRACT) ? &ops[i++] : nullptr;
+    const dsp_op* pz = (ld && n_ops > i && ops[i].opcode == DSP_OP_POLE_ZERO) ? &ops[i++] : nullptr;
+    const dsp_op* tp = (pz && n_ops > i && ops[i].opcode == DSP_OP_TRAP_PICKOFF) ? &ops[i++] : nullptr;
+    const dsp_op* st = (tp && n_ops > i && ops[i].opcode == DSP_OP_STORE_SCALAR) ? &ops[i++] : nullptr;
+    const int wdt = ld ? io[ld->io].dtype : -1;
+    // (a time constant per event, a float32 column: the register-resident kernel's TAU builds form exp(-1/tau) per row like the interpreter's op)
+    const bool tau_col = pz && pz->sp[0].kind == DSP_ARG_INPUT && io[pz->sp[0].index].dtype == DSP_F32;
+    const bool shape = !f64 && st && i == n_ops && n_slots == 1 && ld->ip[0] == 0 && ld->ip[1] == 0 && (wdt == DSP_F32 || wdt == DSP_I16 || wdt == DSP_U16) && P.io[ld->io].vec_ok &&
+                       (!bs || (bs->dst == 0 && bs->src == 0 && bs->sp[0].kind != DSP_ARG_REG)) && pz->dst == 0 && pz->src == 0 &&
+                       (pz->sp[0].kind == DSP_ARG_CONST || tau_col) &&
+                       tp->src == 0 && tp->sp[0].kind != DSP_ARG_REG && st->ip[0] == tp->dst &&
+                       (slot_len[0] == 1024 || slot_len[0] == 2048 || slot_len[0] == 4096 || slot_len[0] == 8192);
+    if (!shape && st && i == n_ops && n_slots == 1) {  // the ops of the energy chain, but not the kernels' case of it
+        if (f64) note(ch, "the energy chain in a float64 loop: the fused energy kernels are float32");
+        else if (pz->sp[0].kind != DSP_ARG_CONST && !tau_col)
+            note(ch, "a pole-zero time constant per event that is not a float32 column: the fused energy kernels take a constant or such a column");
+        else if (!(slot_len[0] == 1024 || slot_len[0] == 2048 || slot_len[0] == 4096 || slot_len[0] == 8192))
+            note(ch, "waveforms of %d samples: the fused energy kernels take 1024, 2048, 4096 or 8192", slot_len[0]);
+        else if (!P.io[ld->io].vec_ok) note(ch, "rows that do not start on 16-byte boundaries: the fused energy kernels read 16 bytes per lane");
+    }
+    auto f32_col = [&](const dsp_scalar_arg& a) { return a.kind != DSP_ARG_INPUT || io[a.index].dtype == DSP_F32; };
+    if (shape && (!bs || f32_col(bs->sp[0])) && f32_col(tp->sp[0]) && io[st->io].dtype == DSP_F32) {  // (the kernels store a float)
+        EnergyArgs& F = ch->fused;
+        const DevOp& dpz = P.ops[c.dev_index[pz - ops]];
+        const DevOp& dtp = P.ops[c.dev_index[tp - ops]];
+        F.wf_stride = io[ld->io].row_stride;
+        F.wf_offset = io[ld->io].offset;
+        F.len = slot_len[0];
+        F.has_bl = bs ? 1 : 0;
+        if (bs) {
+            if (bs->sp[0].kind == DSP_ARG_INPUT) {
+                ch->io_bl = bs->sp[0].index;
+                F.bl_stride = io[ch->io_bl].row_stride;
+            } else {
+                F.bl_const = (float)bs->sp[0].value;
+            }
+        }
+        if (tp->sp[0].kind == DSP_ARG_INPUT) {
+            ch->io_tp = tp->sp[0].index;
+            F.tp_stride = io[ch->io_tp].row_stride;
+        } else {
+            F.tp_const = (float)tp->sp[0].value;
+        }
+        F.mode = tp->io;
+        F.out_stride = io[st->io].row_stride;
+        F.c = dpz.fc[0];
+        F.tau_nan = dpz.ic[0];
+        F.rr = dtp.fc[0];
+        F.ll = dtp.fc[1];
+        F.all_nan = dtp.ic[9];
+        F.C = P.slots[0].C;
+        F.pitch = P.slots[0].pitch;
+        F.invC = P.slots[0].invC;
+        for (int k = 0; k < 3; ++k) {
+            F.q[k] = dtp.ic[3 + k];
+            F.rho[k] = dtp.ic[6 + k];
+        }
+        F.lds_elems_per_wave = P.lds_elems_per_wave;
+        F.slot_off = P.slots[0].off;
+#ifdef DSPEED_HIP_DIAG
+        if (const char* ab = getenv("DSPEED_HIP_ABLATE")) F.ablate = atoi(ab);  // diagnostic library only: skip passes / stamp phases
+#endif
+        ch->io_wf = ld->io;
+        ch->io_out = st->io;
+        ch->fused_trap = tp->ip[3];
+        ch->fused_npf = slot_len[0] / 256;          // one wavefront per waveform: len == 256 * npf, npf in {4, 8, 16}
+        ch->fused_ok = slot_len[0] <= 4096 && wdt == DSP_F32 && !tau_col;  // the classic kernel reads float32 rows only, one time constant
+        if (tau_col) {
+            ch->io_tau = pz->sp[0].index;
+            F.tau_stride = io[ch->io_tau].row_stride;
+        }
+        ch->wf_dtype = wdt;
+        plan_energy_rr(c, dtp);
+    }
+}
+
+// the amax form runs on the float16 matrix instructions (two-way split operands, float32-accurate: dsp_fir_f16.hip) unless asked
+// for the float32 ones (DSPEED_HIP_FIR_F32=1: A/B and the exact float32 chain); its staging loads are 16 bytes of any row type
+static void choose_fir_f16(PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const char* f32 = getenv("DSPEED_HIP_FIR_F32");
+    const dsp_io_desc& w = c.io[ch->fio_wf];
+    const int es = w.dtype == DSP_F32 ? 4 : 2;
+    const int n_slice = ch->fir.n;  // (its 8-sample vectors are read whole: the last one must end inside the row)
+    if (!(f32 && f32[0] == '1') && (w.row_stride * es) % 16 == 0 && (w.offset * es) % 16 == 0 &&
+        ((n_slice & 7) == 0 || w.offset + ((n_slice + 7) & ~7) <= w.row_stride)) {
+        ch->fir_f16 = true;
+        ch->f16.tz = dsp_internal_fir_f16_tz(ch->fir.kend);
+    }
+}
+
+// nothing but arithmetic between per-event values and stores: one row per lane instead of one per wavefront
+static bool match_scalar_shape(const PlanCtx& c) {
+    bool only_scalar = true;
+    for (int i = 0; i < c.n_ops; ++i) {
+        const int oc = c.ops[i].opcode;
+        only_scalar &= oc == DSP_OP_SCALAR_AFFINE || oc == DSP_OP_SCALAR_DIV || oc == DSP_OP_SCALAR_CONVERT || oc == DSP_OP_SCALAR_FUNC ||
+                       oc == DSP_OP_STORE_SCALAR;
+    }
+    return only_scalar && c.n_dev_ops == c.n_ops;
+}
+
+// Every specialised kernel's shape against the program: the *_ok flags, the kernels' argument blocks and binding indices.  Several may
+// hold at once; which kernel runs is dsp_plan_route's business (and, with the pointers of a launch in hand, dsp_chain_execute's).
+static void match_shapes(PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    const char* env = getenv("DSPEED_HIP_NO_FUSED");  // every specialised kernel off: the interpreter runs the program
+    ch->fused_on = !(env && env[0] == '1');
+    match_energy_shape(c);
+    ch->fir_ok = match_fir_shape(c);
     if (!ch->fir_ok) {
         for (int k = 0; k < DSP_FIR_MAXK; ++k) ch->fio_taps[k] = ch->fio_out[k] = -1;
-        ch->fir_ok = match_fir_store_shape(ch, ops, n_ops, io, slot_len, n_slots, f64);
+        ch->fir_ok = match_fir_store_shape(c);
     }
-    if (ch->fir_ok) {
-        const char* env = getenv("DSPEED_HIP_NO_FUSED");
-        ch->fused_on = !(env && env[0] == '1');
-        // the amax form runs on the float16 matrix instructions (two-way split operands, float32-accurate: dsp_fir_f16.hip) unless asked
-        // for the float32 ones (DSPEED_HIP_FIR_F32=1: A/B and the exact float32 chain); its staging loads are 16 bytes of any row type
-        const char* f32 = getenv("DSPEED_HIP_FIR_F32");
-        const dsp_io_desc& w = io[ch->fio_wf];
-        const int es = w.dtype == DSP_F32 ? 4 : 2;
-        const int n_slice = ch->fir.n;  // (its 8-sample vectors are read whole: the last one must end inside the row)
-        if (!(f32 && f32[0] == '1') && (w.row_stride * es) % 16 == 0 && (w.offset * es) % 16 == 0 &&
-            ((n_slice & 7) == 0 || w.offset + ((n_slice + 7) & ~7) <= w.row_stride)) {
-            ch->fir_f16 = true;
-            ch->f16.tz = dsp_internal_fir_f16_tz(ch->fir.kend);
-        }
-    }
-    ch->rows_ok = match_rows_shape(ch, ops, n_ops, io, n_io, slot_len, n_slots, dev_index, f64);
+    if (ch->fir_ok) choose_fir_f16(c);
+    ch->rows_ok = match_rows_shape(c);
     if (!ch->rows_ok) {
         ch->rio_wf = ch->rio_bl = ch->rio_thr = ch->rio_ts = ch->rio_tpt = ch->rio_dwt = -1;
         for (int k = 0; k < 4; ++k) ch->rio_mm[k] = -1;
-    } else {
-        const char* env = getenv("DSPEED_HIP_NO_FUSED");
-        ch->fused_on = !(env && env[0] == '1');
     }
-
-    {  // nothing but arithmetic between per-event values and stores: one row per lane instead of one per wavefront
-        bool only_scalar = true;
-        for (int i = 0; i < n_ops; ++i) {
-            const int oc = ops[i].opcode;
-            only_scalar &= oc == DSP_OP_SCALAR_AFFINE || oc == DSP_OP_SCALAR_DIV || oc == DSP_OP_SCALAR_CONVERT || oc == DSP_OP_SCALAR_FUNC ||
-                           oc == DSP_OP_STORE_SCALAR;
-        }
-        ch->scalar_ok = only_scalar && n_dev_ops == n_ops;
-        if (ch->scalar_ok) {
-            const char* env = getenv("DSPEED_HIP_NO_FUSED");
-            ch->fused_on = !(env && env[0] == '1');
-        }
-    }
-    ch->pz_ok = match_pz_rows_shape(ch, ops, n_ops, io, slot_len, n_slots, dev_index, f64);
-    if (ch->pz_ok) {
-        const char* env = getenv("DSPEED_HIP_NO_FUSED");
-        ch->fused_on = !(env && env[0] == '1');
-    }
-    ch->red_ok = match_reduce_shape(ch, ops, n_ops, io, slot_len, f64);
-    if (ch->red_ok) {
-        const char* env = getenv("DSPEED_HIP_NO_FUSED");
-        ch->fused_on = !(env && env[0] == '1');
-    }
-    {
-        const char* off = getenv("DSPEED_HIP_NO_FIR_RUNS");  // A/B runs: the matrix-core FIR for piecewise-constant kernels too
-        if (!ch->red_ok && !(off && off[0] == '1')) ch->runs_ok = match_fir_runs_shape(ch, ops, n_ops, io, slot_len, n_slots, f64);
-        if (ch->runs_ok) {
-            const char* env = getenv("DSPEED_HIP_NO_FUSED");
-            ch->fused_on = !(env && env[0] == '1');
-            ch->fir_ok = ch->fir_f16 = false;  // (LOAD, CONVOLVE, STORE has the matrix-core kernel's shape as well)
-        }
-    }
-    ch->cur_ok = match_current_shape(ch, ops, n_ops, io, slot_len, f64);
+    ch->scalar_ok = match_scalar_shape(c);
+    ch->pz_ok = match_pz_rows_shape(c);
+    ch->red_ok = match_reduce_shape(c);
+    const char* off = getenv("DSPEED_HIP_NO_FIR_RUNS");  // A/B runs: the matrix-core FIR for piecewise-constant kernels too
+    if (!ch->red_ok && !(off && off[0] == '1')) ch->runs_ok = match_fir_runs_shape(c);
+    if (ch->runs_ok) ch->fir_ok = ch->fir_f16 = false;  // (LOAD, CONVOLVE, STORE has the matrix-core kernel's shape as well)
+    ch->cur_ok = match_current_shape(c);
     if (!ch->cur_ok) {
         ch->cio_wf = ch->cio_t0 = -1;
         for (int k = 0; k < 4; ++k) ch->cio_out[k] = -1;
-    } else {
-        const char* env = getenv("DSPEED_HIP_NO_FUSED");
-        ch->fused_on = !(env && env[0] == '1');
     }
+}
 
-    // ---- a team of two wavefronts per row?  A program that loads ONE waveform and then only reads it -- the trapezoid reductions, pick-offs and
-    // walks a whole recipe runs on its pole-zero rows -- whose image leaves LDS for one wavefront per SIMD: its ops fall into groups that share
-    // no scalar register, and two wavefronts can run two groups on the one image at the same time.
-    // ---- a threshold that is a fraction of a per-event value (the rise-time walks of the Ge recipes: time_point_thresh at 0.99 / 0.9 / 0.5 /
-    // 0.1 of the trapezoid's maximum) costs the interpreter an op of its own -- ~ 1 700 cycles of a row's lone wavefront, whatever the op
-    // computes -- for one multiplication.  SCALAR_AFFINE d <- x * const + 0 whose result only TIME_POINT_THRESH ops read as their threshold
-    // is folded into them: they multiply (the same float multiplication: x * b + (+-0) is x * b) and the op becomes a no-op.
-    if (const char* nf = getenv("DSPEED_HIP_NO_THRESHOLD_FOLD"); !(nf && nf[0] == '1')) {  // (A/B runs and the bit-identity test)
-        auto writes_reg = [&](const DevOp& o, int r) {
-            switch (o.opcode) {
-                case DSP_OP_MIN_MAX: return r >= o.dst && r < o.dst + 4;
-                case DSP_OP_TRAP_REDUCE:
-                    return (o.dst >= 0 && r >= o.dst && r < o.dst + 4) || (o.io >= 0 && r == o.io) || r == ((o.ip[3] >> 16) & 0x3fff) - 1;
-                case DSP_OP_LOAD: case DSP_OP_STORE: case DSP_OP_STORE_SCALAR: case DSP_OP_INTERNAL_NOP: case DSP_OP_INTERNAL_ZERO: return false;
-                default: return o.dst == r;  // (waveform ops name a slot there: a spurious match only ends a window early)
-            }
-        };
-        for (int i = 0; i < P.n_ops; ++i) {
-            DevOp& a = P.ops[i];
-            if (a.opcode != DSP_OP_SCALAR_AFFINE || a.sp[0].kind != DSP_ARG_REG || a.sp[1].kind != DSP_ARG_CONST || a.sp[2].kind != DSP_ARG_CONST ||
-                a.sp[2].value != 0.0 || a.sp[0].index == a.dst)
-                continue;
-            const int r = a.dst, x = a.sp[0].index;
-            std::vector<int> users;
-            bool fine = true;
-            for (int j = i + 1; j < P.n_ops && fine; ++j) {
-                const DevOp& o = P.ops[j];
-                bool reads_r = false;
-                for (int k = 0; k < 4; ++k)
-                    if (o.sp[k].kind == DSP_ARG_REG && o.sp[k].index == r) {
-                        reads_r = true;
-                        if (!(o.opcode == DSP_OP_TIME_POINT_THRESH && k == 0 && o.ic[0] == 0)) fine = false;
-                    }
-                if (o.opcode == DSP_OP_STORE_SCALAR && o.ip[0] == r) fine = false;
-                if (reads_r && fine) users.push_back(j);
-                if (writes_reg(o, r)) break;                        // the register starts another life: what follows reads that
-                if (writes_reg(o, x) && fine) {                     // the value the walks would multiply changes here: nothing may read r after it
-                    for (int j2 = j + 1; j2 < P.n_ops; ++j2) {
-                        const DevOp& o2 = P.ops[j2];
-                        for (int k = 0; k < 4; ++k)
-                            if (o2.sp[k].kind == DSP_ARG_REG && o2.sp[k].index == r) fine = false;
-                        if (o2.opcode == DSP_OP_STORE_SCALAR && o2.ip[0] == r) fine = false;
-                        if (writes_reg(o2, r)) break;
-                    }
-                    break;
+// scalar registers an op writes (waveform ops name a slot in dst: to the threshold fold a spurious match only ends a window early, and
+// a program that forms teams holds none behind its load)
+static int written_regs(const DevOp& o, int* r) {
+    int n = 0;
+    switch (o.opcode) {
+        case DSP_OP_MIN_MAX: for (int k = 0; k < 4; ++k) r[n++] = o.dst + k; break;
+        case DSP_OP_TRAP_REDUCE:
+            if (o.dst >= 0) for (int k = 0; k < 4; ++k) r[n++] = o.dst + k;
+            if (o.io >= 0) r[n++] = o.io;
+            if ((((o.ip[3] >> 16) & 0x3fff) - 1) >= 0) r[n++] = ((o.ip[3] >> 16) & 0x3fff) - 1;  // (a pick-off that reads the same trapezoid)
+            break;
+        case DSP_OP_LOAD: case DSP_OP_STORE: case DSP_OP_STORE_SCALAR: case DSP_OP_INTERNAL_NOP: case DSP_OP_INTERNAL_ZERO: break;
+        default: r[n++] = o.dst;
+    }
+    return n;
+}
+static bool writes_reg(const DevOp& o, int r) {
+    int w[8];
+    const int n = written_regs(o, w);
+    return std::find(w, w + n, r) != w + n;
+}
+
+// ---- a threshold that is a fraction of a per-event value (the rise-time walks of the Ge recipes: time_point_thresh at 0.99 / 0.9 / 0.5 /
+// 0.1 of the trapezoid's maximum) costs the interpreter an op of its own -- ~ 1 700 cycles of a row's lone wavefront, whatever the op
+// computes -- for one multiplication.  SCALAR_AFFINE d <- x * const + 0 whose result only TIME_POINT_THRESH ops read as their threshold
+// is folded into them: they multiply (the same float multiplication: x * b + (+-0) is x * b) and the op becomes a no-op.
+static void fold_scaled_thresholds(PlanCtx& c) {
+    DevProgram& P = c.ch->host;
+    const char* nf = getenv("DSPEED_HIP_NO_THRESHOLD_FOLD");  // (A/B runs and the bit-identity test)
+    if (nf && nf[0] == '1') return;
+    for (int i = 0; i < P.n_ops; ++i) {
+        DevOp& a = P.ops[i];
+        if (a.opcode != DSP_OP_SCALAR_AFFINE || a.sp[0].kind != DSP_ARG_REG || a.sp[1].kind != DSP_ARG_CONST || a.sp[2].kind != DSP_ARG_CONST ||
+            a.sp[2].value != 0.0 || a.sp[0].index == a.dst)
+            continue;
+        const int r = a.dst, x = a.sp[0].index;
+        std::vector<int> users;
+        bool fine = true;
+        for (int j = i + 1; j < P.n_ops && fine; ++j) {
+            const DevOp& o = P.ops[j];
+            bool reads_r = false;
+            for (int k = 0; k < 4; ++k)
+                if (o.sp[k].kind == DSP_ARG_REG && o.sp[k].index == r) {
+                    reads_r = true;
+                    if (!(o.opcode == DSP_OP_TIME_POINT_THRESH && k == 0 && o.ic[0] == 0)) fine = false;
                 }
+            if (o.opcode == DSP_OP_STORE_SCALAR && o.ip[0] == r) fine = false;
+            if (reads_r && fine) users.push_back(j);
+            if (writes_reg(o, r)) break;                        // the register starts another life: what follows reads that
+            if (writes_reg(o, x) && fine) {                     // the value the walks would multiply changes here: nothing may read r after it
+                for (int j2 = j + 1; j2 < P.n_ops; ++j2) {
+                    const DevOp& o2 = P.ops[j2];
+                    for (int k = 0; k < 4; ++k)
+                        if (o2.sp[k].kind == DSP_ARG_REG && o2.sp[k].index == r) fine = false;
+                    if (o2.opcode == DSP_OP_STORE_SCALAR && o2.ip[0] == r) fine = false;
+                    if (writes_reg(o2, r)) break;
+                }
+                break;
             }
-            if (!fine || users.empty()) continue;
-            for (int j : users) {
-                P.ops[j].sp[0] = a.sp[0];
-                P.ops[j].ic[0] = 1;
-                P.ops[j].fc[0] = a.sp[1].value;
-            }
-            a.opcode = DSP_OP_INTERNAL_NOP;
         }
+        if (!fine || users.empty()) continue;
+        for (int j : users) {
+            P.ops[j].sp[0] = a.sp[0];
+            P.ops[j].ic[0] = 1;
+            P.ops[j].fc[0] = a.sp[1].value;
+        }
+        a.opcode = DSP_OP_INTERNAL_NOP;
     }
+}
 
+// ---- a team of two wavefronts per row?  A program that loads ONE waveform and then only reads it -- the trapezoid reductions, pick-offs and
+// walks a whole recipe runs on its pole-zero rows -- whose image leaves LDS for one wavefront per SIMD: its ops fall into groups that share
+// no scalar register, and two wavefronts can run two groups on the one image at the same time.
+static void form_teams(PlanCtx& c) {
+    ChainPlan* ch = c.ch;
+    DevProgram& P = ch->host;
     P.team = 1;
     for (int i = 0; i < P.n_ops; ++i) P.ops[i].member = DSP_MEMBER_ALL;
-    {
-        const char* env = getenv("DSPEED_HIP_NO_TEAMS");
-        const bool vm_runs = !(ch->fused_ok || ch->rr_ok || ch->rows_ok || ch->fir_ok || ch->cur_ok || ch->red_ok || ch->pz_ok || ch->scalar_ok);
-        bool ok = vm_runs && !(env && env[0] == '1') && !f64 && !ch->has_fir && n_slots == 1 && ch->lds_bytes_per_wave > 0 &&
-                  LDS_BYTES_PER_CU / ch->lds_bytes_per_wave <= 4 && ch->waves_per_block * 2 <= 16 && n_sregs <= 128;
-        int first = 0;
-        while (first < P.n_ops && P.ops[first].opcode == DSP_OP_INTERNAL_NOP) ++first;
-        ok = ok && first < P.n_ops && P.ops[first].opcode == DSP_OP_LOAD;
-        // registers an op writes / reads (scalar registers only: after the load nothing writes the waveform)
-        auto writes = [&](const DevOp& o, int* r) {
-            int n = 0;
-            switch (o.opcode) {
-                case DSP_OP_MIN_MAX: for (int k = 0; k < 4; ++k) r[n++] = o.dst + k; break;
-                case DSP_OP_TRAP_REDUCE:
-                    if (o.dst >= 0) for (int k = 0; k < 4; ++k) r[n++] = o.dst + k;
-                    if (o.io >= 0) r[n++] = o.io;
-                    if ((((o.ip[3] >> 16) & 0x3fff) - 1) >= 0) r[n++] = ((o.ip[3] >> 16) & 0x3fff) - 1;  // (a pick-off that reads the same trapezoid)
-                    break;
-                case DSP_OP_AMAX: case DSP_OP_TRAP_PICKOFF: case DSP_OP_TIME_POINT_THRESH: case DSP_OP_PICKOFF: case DSP_OP_SCALAR_AFFINE:
-                case DSP_OP_SCALAR_DIV: case DSP_OP_SCALAR_CONVERT: case DSP_OP_SCALAR_FUNC: r[n++] = o.dst; break;
-                default: break;
-            }
-            return n;
-        };
-        auto reads = [&](const DevOp& o, int* r) {
-            int n = 0;
-            for (int k = 0; k < 4; ++k)
-                if (o.sp[k].kind == DSP_ARG_REG) r[n++] = o.sp[k].index;
-            if (o.opcode == DSP_OP_STORE_SCALAR) r[n++] = o.ip[0];
-            return n;
-        };
-        for (int i = first + 1; ok && i < P.n_ops; ++i) {
-            switch (P.ops[i].opcode) {
-                case DSP_OP_TRAP_REDUCE: case DSP_OP_TRAP_PICKOFF: case DSP_OP_TIME_POINT_THRESH: case DSP_OP_PICKOFF: case DSP_OP_MIN_MAX: case DSP_OP_AMAX:
-                case DSP_OP_SCALAR_AFFINE: case DSP_OP_SCALAR_DIV: case DSP_OP_SCALAR_CONVERT: case DSP_OP_SCALAR_FUNC: case DSP_OP_STORE_SCALAR:
-                case DSP_OP_INTERNAL_NOP: break;
-                default: ok = false;
-            }
-        }
-        if (ok) {
-            // groups: ops joined by any register one writes and the other reads or writes
-            std::vector<int> parent(P.n_ops);
-            for (int i = 0; i < P.n_ops; ++i) parent[i] = i;
-            auto find = [&](int x) { while (parent[x] != x) x = parent[x] = parent[parent[x]]; return x; };
-            std::vector<int> owner(DSP_MAX_SREGS + 8, -1);  // register -> an op that touched it
-            for (int i = first + 1; i < P.n_ops; ++i) {
-                int regs[16], n = writes(P.ops[i], regs);
-                n += reads(P.ops[i], regs + n);
-                for (int k = 0; k < n; ++k) {
-                    const int r = regs[k];
-                    if (r < 0 || r >= (int)owner.size()) { ok = false; break; }
-                    if (owner[r] < 0) owner[r] = i;
-                    else parent[find(i)] = find(owner[r]);
-                }
-            }
-            auto weight = [&](int oc) {
-                switch (oc) {
-                    case DSP_OP_TRAP_REDUCE: return 27;
-                    case DSP_OP_TRAP_PICKOFF: return 20;
-                    case DSP_OP_MIN_MAX: return 16;
-                    case DSP_OP_TIME_POINT_THRESH: case DSP_OP_AMAX: return 4;
-                    case DSP_OP_PICKOFF: return 3;
-                    case DSP_OP_STORE_SCALAR: return 1;
-                    default: return 2;
-                }
-            };
-            std::vector<int> w(P.n_ops, 0);
-            for (int i = first + 1; i < P.n_ops; ++i) w[find(i)] += weight(P.ops[i].opcode);
-            std::vector<int> roots;
-            for (int i = first + 1; i < P.n_ops; ++i)
-                if (find(i) == i) roots.push_back(i);
-            std::sort(roots.begin(), roots.end(), [&](int a, int b) { return w[a] > w[b]; });
-            // groups dealt out to two or three members, heaviest first, each to the member with the least so far (three: when the third
-            // member still gets a real share -- the Ge recipe's program is a trapezoid with its five walks, a trapezoid with a pick-off and
-            // a pick-off of a third: the recurrences are latency-bound, a third wavefront on the image fills a SIMD's idle issue slots)
-            int load[3] = {0, 0, 0}, n_team = 2;
-            std::vector<int> side(P.n_ops, 0);
-            auto deal = [&](int members) {
-                load[0] = load[1] = load[2] = 0;
-                for (int r : roots) {
-                    int m = 0;
-                    for (int k = 1; k < members; ++k)
-                        if (load[k] < load[m]) m = k;
-                    side[r] = m;
-                    load[m] += w[r];
-                }
-            };
-            const char* t3 = getenv("DSPEED_HIP_TEAM_MAX");  // (A/B runs: 2 keeps teams of two)
-            deal(3);
-            {
-                const int total = load[0] + load[1] + load[2];
-                int least = load[0] < load[1] ? load[0] : load[1];
-                least = load[2] < least ? load[2] : least;
-                if ((int)roots.size() >= 3 && 6 * least >= total && !(t3 && atoi(t3) < 3) && ch->waves_per_block * 3 <= 16)
-                    n_team = 3;
-                else
-                    deal(2);
-            }
-            // worth more wavefronts only when each takes a real share of the work
-            if (ok && load[0] > 0 && load[1] > 0 && (n_team == 3 || 5 * (load[0] < load[1] ? load[0] : load[1]) >= load[0] + load[1])) {
-                P.team = n_team;
-                for (int i = first + 1; i < P.n_ops; ++i) P.ops[i].member = side[find(i)];
-                // a workgroup per team: the barrier at the end of a row then holds the two members of one row, not four rows' worth of
-                // wavefronts whose walks take different times (DSPEED_HIP_TEAM_WPB: the teams per workgroup, for the A/B)
-                int twpb = 1;
-                if (const char* tw = getenv("DSPEED_HIP_TEAM_WPB")) twpb = atoi(tw);
-                if (twpb >= 1 && twpb < ch->waves_per_block) ch->waves_per_block = P.waves_per_block = twpb;
-            }
+    const char* env = getenv("DSPEED_HIP_NO_TEAMS");
+    const bool vm_runs = !(ch->fused_ok || ch->rr_ok || ch->rows_ok || ch->fir_ok || ch->cur_ok || ch->red_ok || ch->pz_ok || ch->scalar_ok);
+    bool ok = vm_runs && !(env && env[0] == '1') && !c.f64 && !ch->has_fir && c.n_slots == 1 && ch->lds_bytes_per_wave > 0 &&
+              LDS_BYTES_PER_CU / ch->lds_bytes_per_wave <= 4 && ch->waves_per_block * 2 <= 16 && c.n_sregs <= 128;
+    int first = 0;
+    while (first < P.n_ops && P.ops[first].opcode == DSP_OP_INTERNAL_NOP) ++first;
+    ok = ok && first < P.n_ops && P.ops[first].opcode == DSP_OP_LOAD;
+    for (int i = first + 1; ok && i < P.n_ops; ++i) {
+        switch (P.ops[i].opcode) {
+            case DSP_OP_TRAP_REDUCE: case DSP_OP_TRAP_PICKOFF: case DSP_OP_TIME_POINT_THRESH: case DSP_OP_PICKOFF: case DSP_OP_MIN_MAX: case DSP_OP_AMAX:
+            case DSP_OP_SCALAR_AFFINE: case DSP_OP_SCALAR_DIV: case DSP_OP_SCALAR_CONVERT: case DSP_OP_SCALAR_FUNC: case DSP_OP_STORE_SCALAR:
+            case DSP_OP_INTERNAL_NOP: break;
+            default: ok = false;
         }
     }
+    if (!ok) return;
+    // registers an op reads (scalar registers only: after the load nothing writes the waveform)
+    auto reads = [&](const DevOp& o, int* r) {
+        int n = 0;
+        for (int k = 0; k < 4; ++k)
+            if (o.sp[k].kind == DSP_ARG_REG) r[n++] = o.sp[k].index;
+        if (o.opcode == DSP_OP_STORE_SCALAR) r[n++] = o.ip[0];
+        return n;
+    };
+    // groups: ops joined by any register one writes and the other reads or writes
+    std::vector<int> parent(P.n_ops);
+    for (int i = 0; i < P.n_ops; ++i) parent[i] = i;
+    auto find = [&](int x) { while (parent[x] != x) x = parent[x] = parent[parent[x]]; return x; };
+    std::vector<int> owner(DSP_MAX_SREGS + 8, -1);  // register -> an op that touched it
+    for (int i = first + 1; i < P.n_ops; ++i) {
+        int regs[16], n = written_regs(P.ops[i], regs);
+        n += reads(P.ops[i], regs + n);
+        for (int k = 0; k < n; ++k) {
+            const int r = regs[k];
+            if (r < 0 || r >= (int)owner.size()) { ok = false; break; }
+            if (owner[r] < 0) owner[r] = i;
+            else parent[find(i)] = find(owner[r]);
+        }
+    }
+    auto weight = [&](int oc) {
+        switch (oc) {
+            case DSP_OP_TRAP_REDUCE: return 27;
+            case DSP_OP_TRAP_PICKOFF: return 20;
+            case DSP_OP_MIN_MAX: return 16;
+            case DSP_OP_TIME_POINT_THRESH: case DSP_OP_AMAX: return 4;
+            case DSP_OP_PICKOFF: return 3;
+            case DSP_OP_STORE_SCALAR: return 1;
+            default: return 2;
+        }
+    };
+    std::vector<int> w(P.n_ops, 0);
+    for (int i = first + 1; i < P.n_ops; ++i) w[find(i)] += weight(P.ops[i].opcode);
+    std::vector<int> roots;
+    for (int i = first + 1; i < P.n_ops; ++i)
+        if (find(i) == i) roots.push_back(i);
+    std::sort(roots.begin(), roots.end(), [&](int a, int b) { return w[a] > w[b]; });
+    // groups dealt out to two or three members, heaviest first, each to the member with the least so far (three: when the third
+    // member still gets a real share -- the Ge recipe's program is a trapezoid with its five walks, a trapezoid with a pick-off and
+    // a pick-off of a third: the recurrences are latency-bound, a third wavefront on the image fills a SIMD's idle issue slots)
+    int load[3] = {0, 0, 0}, n_team = 2;
+    std::vector<int> side(P.n_ops, 0);
+    auto deal = [&](int members) {
+        load[0] = load[1] = load[2] = 0;
+        for (int r : roots) {
+            int m = 0;
+            for (int k = 1; k < members; ++k)
+                if (load[k] < load[m]) m = k;
+            side[r] = m;
+            load[m] += w[r];
+        }
+    };
+    const char* t3 = getenv("DSPEED_HIP_TEAM_MAX");  // (A/B runs: 2 keeps teams of two)
+    deal(3);
+    {
+        const int total = load[0] + load[1] + load[2];
+        int least = load[0] < load[1] ? load[0] : load[1];
+        least = load[2] < least ? load[2] : least;
+        if ((int)roots.size() >= 3 && 6 * least >= total && !(t3 && atoi(t3) < 3) && ch->waves_per_block * 3 <= 16)
+            n_team = 3;
+        else
+            deal(2);
+    }
+    // worth more wavefronts only when each takes a real share of the work
+    if (ok && load[0] > 0 && load[1] > 0 && (n_team == 3 || 5 * (load[0] < load[1] ? load[0] : load[1]) >= load[0] + load[1])) {
+        P.team = n_team;
+        for (int i = first + 1; i < P.n_ops; ++i) P.ops[i].member = side[find(i)];
+        // a workgroup per team: the barrier at the end of a row then holds the two members of one row, not four rows' worth of
+        // wavefronts whose walks take different times (DSPEED_HIP_TEAM_WPB: the teams per workgroup, for the A/B)
+        int twpb = 1;
+        if (const char* tw = getenv("DSPEED_HIP_TEAM_WPB")) twpb = atoi(tw);
+        if (twpb >= 1 && twpb < ch->waves_per_block) ch->waves_per_block = P.waves_per_block = twpb;
+    }
+}
 
-    // The interpreter pays a dispatch per op and row (a lone wavefront: op fetch, decode, a few hundred cycles), and a recipe ends in
-    // dozens of one-lane stores.  Last step, after every shape matcher has read the ops: a run of STORE_SCALARs becomes one op whose lanes
-    // store one value each, and the no-ops a folded BL_SUBTRACT left are dropped.  (The row-per-lane kernel keeps its plain stores.)
-    if (!ch->scalar_ok) {
+// The interpreter pays a dispatch per op and row (a lone wavefront: op fetch, decode, a few hundred cycles), and a recipe ends in
+// dozens of one-lane stores.  Last step, after every shape matcher has read the ops: a run of STORE_SCALARs becomes one op whose lanes
+// store one value each, and the no-ops a folded BL_SUBTRACT left are dropped.  (The row-per-lane kernel keeps its plain stores.)
+static void merge_scalar_stores(PlanCtx& c) {
+    DevProgram& P = c.ch->host;
+    if (!c.ch->scalar_ok) {
         int w = 0;
         for (int r = 0; r < P.n_ops;) {
             if (P.ops[r].opcode == DSP_OP_INTERNAL_NOP) {
@@ -1746,30 +1850,73 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
         }
         P.n_ops = w;
     }
-
     for (int i = 0; i < P.n_ops; ++i) P.ops[i].prio = (i * 4) / P.n_ops;
-    for (int s = 0; s < n_slots; ++s) {
-        ch->slot_base[s] = base[s];
-        ch->slot_foot[s] = foot[s];
-        ch->slot_first_op[s] = first_op[s];
-        ch->slot_last_op[s] = last_op[s];
-        ch->slot_shares[s] = shares[s] ? 1 : 0;
+}
+
+// the LDS packing as decided, for dsp_chain_plan and the fuzzer's invariants
+static void publish_packing(PlanCtx& c) {
+    for (int s = 0; s < c.n_slots; ++s) {
+        c.ch->slot_base[s] = c.base[s];
+        c.ch->slot_foot[s] = c.foot[s];
+        c.ch->slot_first_op[s] = c.first_op[s];
+        c.ch->slot_last_op[s] = c.last_op[s];
+        c.ch->slot_shares[s] = c.shares[s] ? 1 : 0;
     }
+}
+
+int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_io, const int32_t* slot_len, int n_slots,
+                   int n_sregs, int compute_dtype) {
+    PlanCtx c{ops, n_ops, io, n_io, slot_len, n_slots, n_sregs, compute_dtype, ch};
+    if (const int rc = check_call(c)) return rc;
+    choose_linear_slots(c);
+    slot_lifetimes(c);
+    if (const int rc = pack_lds(c)) return rc;  // (slot lengths are checked here: ahead of the bindings, those ahead of the ops)
+    pick_waves_per_block(c);
+    if (const int rc = bind_io(c)) return rc;
+    if (const int rc = lower_ops(c)) return rc;
+    fold_load_bl_subtract(c);
+    match_shapes(c);
+    fold_scaled_thresholds(c);
+    form_teams(c);
+    merge_scalar_stores(c);
+    publish_packing(c);
     return DSP_OK;
 }
 
-const char* dsp_plan_kernel_name(const ChainPlan* ch) {
-    if (ch && ch->scalar_ok && ch->fused_on) return dsp_internal_scalar_kernel_name();
-    if (ch && ch->pz_ok && ch->fused_on) return dsp_internal_pz_rows_kernel_name();
-    if (ch && ch->red_ok && ch->fused_on) return dsp_internal_reduce_kernel_name();
-    if (ch && ch->runs_ok && ch->fused_on) return dsp_internal_fir_runs_kernel_name();
-    if (ch && ch->cur_ok && ch->fused_on) return dsp_internal_current_kernel_name();
-    if (ch && ch->fir_ok && ch->fused_on)
-        return ch->fir_f16 ? dsp_internal_fir_f16_kernel_name() : (ch->fir.store ? dsp_internal_fir_store_kernel_name() : dsp_internal_fir_mfma_kernel_name());
-    if (ch && ch->rows_ok && ch->fused_on) return dsp_internal_rows_kernel_name();
-    if (ch && ch->rr_ok && ch->fused_on && ch->variant != 1) return dsp_internal_energy_rr_kernel_name();
-    return (ch && ch->fused_ok && ch->fused_on) ? dsp_internal_energy_kernel_name() : dsp_internal_vm_kernel_name();
+dsp_route dsp_plan_route(const ChainPlan* ch) {
+    if (!ch || !ch->fused_on) return DSP_ROUTE_VM;
+    if (ch->scalar_ok) return DSP_ROUTE_SCALAR;
+    if (ch->pz_ok) return DSP_ROUTE_PZ_ROWS;
+    if (ch->red_ok) return DSP_ROUTE_REDUCE;
+    if (ch->runs_ok) return DSP_ROUTE_FIR_RUNS;
+    if (ch->cur_ok) return DSP_ROUTE_CURRENT;
+    if (ch->fir_ok) return ch->fir_f16 ? DSP_ROUTE_FIR_F16 : (ch->fir.store ? DSP_ROUTE_FIR_STORE : DSP_ROUTE_FIR_MFMA);
+    if (ch->rows_ok) return DSP_ROUTE_ROWS;
+    if (ch->rr_ok && ch->variant != 1) return DSP_ROUTE_ENERGY_RR;
+    return ch->fused_ok ? DSP_ROUTE_ENERGY : DSP_ROUTE_VM;
 }
+
+const char* dsp_plan_route_kernel_name(dsp_route route) {
+    switch (route) {
+        case DSP_ROUTE_SCALAR: return dsp_internal_scalar_kernel_name();
+        case DSP_ROUTE_PZ_ROWS: return dsp_internal_pz_rows_kernel_name();
+        case DSP_ROUTE_REDUCE: return dsp_internal_reduce_kernel_name();
+        case DSP_ROUTE_FIR_RUNS: return dsp_internal_fir_runs_kernel_name();
+        case DSP_ROUTE_CURRENT: return dsp_internal_current_kernel_name();
+        case DSP_ROUTE_FIR_F16: return dsp_internal_fir_f16_kernel_name();
+        case DSP_ROUTE_FIR_STORE: return dsp_internal_fir_store_kernel_name();
+        case DSP_ROUTE_FIR_MFMA: return dsp_internal_fir_mfma_kernel_name();
+        case DSP_ROUTE_ROWS: return dsp_internal_rows_kernel_name();
+        case DSP_ROUTE_ENERGY_RR: return dsp_internal_energy_rr_kernel_name();
+        case DSP_ROUTE_ENERGY: return dsp_internal_energy_kernel_name();
+        case DSP_ROUTE_VM: break;
+    }
+    return dsp_internal_vm_kernel_name();
+}
+
+const char* dsp_plan_kernel_name(const ChainPlan* ch) { return dsp_plan_route_kernel_name(dsp_plan_route(ch)); }
+
+bool dsp_plan_specialised(const ChainPlan* ch) { return ch && (dsp_plan_route(ch) != DSP_ROUTE_VM || (ch->rr_ok && ch->fused_on)); }
 
 extern "C" int dsp_chain_plan(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_io, const int32_t* slot_len, int n_slots, int n_sregs,
                               int compute_dtype, dsp_plan_info* info) {
@@ -1779,8 +1926,7 @@ extern "C" int dsp_chain_plan(const dsp_op* ops, int n_ops, const dsp_io_desc* i
     const int rc = dsp_plan_build(ch.get(), ops, n_ops, io, n_io, slot_len, n_slots, n_sregs, compute_dtype);
     if (rc != DSP_OK) return rc;
     snprintf(info->kernel, sizeof info->kernel, "%s", dsp_plan_kernel_name(ch.get()));
-    const bool specialised = ch->fused_on && (ch->scalar_ok || ch->pz_ok || ch->red_ok || ch->runs_ok || ch->cur_ok || ch->fir_ok || ch->rows_ok || ch->rr_ok || ch->fused_ok);
-    snprintf(info->note, sizeof info->note, "%s", specialised ? "" : ch->note.c_str());
+    snprintf(info->note, sizeof info->note, "%s", dsp_plan_specialised(ch.get()) ? "" : ch->note.c_str());
     const DevProgram& P = ch->host;
     info->lds_bytes_per_wave = ch->lds_bytes_per_wave;
     info->waves_per_block = ch->waves_per_block;

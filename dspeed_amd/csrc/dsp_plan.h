@@ -3,7 +3,7 @@
 // dsp_plan_build validates the program (every constant-only DSPFatal condition of the reference included), evaluates the constants the
 // reference evaluates once per call, packs the waveform slots into LDS by lifetime, matches the program against the specialised kernels'
 // shapes and picks the launch geometry.  It makes no HIP call and includes no HIP header: the same translation unit is compiled for the
-// CPU with -fsanitize=address,undefined and fuzzed there (tests/test_planner_fuzz.py, tools/planner_fuzz.cpp).  dsp_host.cpp puts the
+// CPU with -fsanitize=address,undefined and fuzzed there (tests/test_planner_fuzz.py, tests/planner_fuzz.cpp).  dsp_host.cpp puts the
 // device resources on top (struct dsp_chain : ChainPlan).  Internal header; the public contract is include/dspeed_hip.h.
 #pragma once
 #include <stddef.h>
@@ -147,5 +147,18 @@ struct ChainPlan {
 // 0 or the DSP_ERR_* / DSP_E_* code (text in dsp_plan_last_error()); `ch` must be a freshly constructed plan
 int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_io, const int32_t* slot_len, int n_slots,
                    int n_sregs, int compute_dtype);
-// the kernel a planned chain launches on rows that keep 16-byte alignment (what rocprofv3 --kernel-trace lists)
+// The kernels a chain can run on, in their order of precedence: a program that has the shape of several (the *_ok flags) runs on the first
+// whose switch is on.  dsp_plan_route is the one place that holds this order for everything that reports a plan (kernel name, note,
+// geometry); dsp_chain_execute walks the same list with the alignment of the pointers it is handed and may fall through to a later entry.
+enum dsp_route {
+    DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
+    DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
+};
+// the route a planned chain takes on rows that keep 16-byte alignment (fused_on and variant included; null: the interpreter)
+dsp_route dsp_plan_route(const ChainPlan* ch);
+// its kernel (what rocprofv3 --kernel-trace lists)
+const char* dsp_plan_route_kernel_name(dsp_route route);
 const char* dsp_plan_kernel_name(const ChainPlan* ch);
+// does a specialised kernel's shape stand behind the chain (its note is then not shown)?  The route, but for one case: the classic energy
+// kernel asked for (variant 1) on a program only the register-resident one takes runs on the interpreter and still counts
+bool dsp_plan_specialised(const ChainPlan* ch);

@@ -1,7 +1,7 @@
 // planner_fuzz.cpp -- test infrastructure: random programs through the device-free planner (dspeed_amd/csrc/dsp_plan.cpp), built for the
 // CPU with -fsanitize=address,undefined by tests/test_planner_fuzz.py.
 //
-//   planner_fuzz <programs> <seed>
+//   planner_fuzz <programs> <seed> [digest]
 //
 // Two kinds of programs: (1) op lists drawn from every opcode with operands that are valid most of the time (so that the validation, the
 // constant evaluation and the LDS packing behind it are reached) and garbage some of the time (so that the validation itself is); (2) the
@@ -13,11 +13,16 @@
 //   * the device program's ops stay inside the table, team members are 0 / 1 / 2.
 // Exit code 0 and a one-line summary when every program passed; a message and exit code 1 on the first violated invariant (the sanitizers
 // end the process themselves).
+//
+// With `digest` the summary also carries a 64-bit FNV-1a hash over every program's outcome -- the code and message of a refusal; of a plan
+// every field the host or a kernel later reads -- so that two builds of the planner can be compared program by program: a refactoring of
+// dsp_plan.cpp must print the digest its parent printed, for every seed and under every DSPEED_HIP_* switch.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <random>
+#include <type_traits>
 #include <vector>
 
 #include "../dspeed_amd/csrc/dsp_plan.h"
@@ -784,11 +789,99 @@ void dump(const Prog& p) {
     }
 }
 
+// ---- the digest: FNV-1a over named fields (never over a whole argument block: their padding is not defined)
+struct Digest {
+    uint64_t h = 1469598103934665603ull;
+    void bytes(const void* p, size_t n) {
+        for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull;
+    }
+    template <typename T>
+    void operator()(const T& v) {
+        static_assert(std::is_arithmetic<T>::value, "hash a field, not a structure");
+        bytes(&v, sizeof v);
+    }
+    template <typename T, size_t N>
+    void operator()(const T (&a)[N]) {
+        for (const T& v : a) (*this)(v);
+    }
+    void text(const char* s) { bytes(s, strlen(s) + 1); }
+};
+
+void digest_reduce(Digest& H, const ReduceArgs& A) {
+    H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.out_stride), H(A.pick_stride), H(A.pick_at), H(A.pick_rule), H(A.walk_stride), H(A.walk_thr_stride);
+    H(A.walk_thr_const), H(A.walk_from), H(A.walk_start), H(A.walk_forward), H(A.walk_thr_factor), H(A.walk_thr_scaled), H(A.walk_ts_stride), H(A.n_walks), H(A.need_stream);
+}
+
+void digest_energy(Digest& H, const EnergyArgs& A) {
+    H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.bl_stride), H(A.bl_const), H(A.has_bl), H(A.tp_stride), H(A.tp_const), H(A.mode), H(A.out_stride), H(A.c), H(A.rr), H(A.ll);
+    H(A.tau_nan), H(A.all_nan), H(A.C), H(A.pitch), H(A.invC), H(A.q), H(A.rho), H(A.lds_elems_per_wave), H(A.slot_off), H(A.tau_stride), H(A.ablate);
+}
+
+void digest_plan(Digest& H, const ChainPlan& c, int n_slots) {
+    const DevProgram& P = c.host;
+    const bool any_ok = c.scalar_ok || c.pz_ok || c.red_ok || c.runs_ok || c.cur_ok || c.fir_ok || c.rows_ok || c.rr_ok || c.fused_ok;
+    H.text(dsp_plan_kernel_name(&c));
+    H.text(c.note.c_str());
+    H.text(dsp_plan_specialised(&c) ? "" : c.note.c_str());  // (the note as dsp_chain_plan and dsp_chain_kernel_note hand it out)
+    H(c.lds_bytes_per_wave), H(c.waves_per_block), H(c.classic_wpb), H(c.has_fir), H(c.f64), H(c.i64);
+    H(c.fused_ok), H(c.rr_ok), H(c.rows_ok), H(c.fir_ok), H(c.scalar_ok), H(c.cur_ok), H(c.pz_ok), H(c.red_ok), H(c.runs_ok);
+    H((bool)(c.fused_on && any_ok));  // (the switch alone, on a program no kernel takes, shows through no accessor)
+    H(c.variant), H(c.fused_trap), H(c.fused_npf), H(c.wf_dtype), H(c.rr_lds_bytes), H(c.rows_lds_bytes), H(c.fir_lds_bytes), H(c.cur_lds_bytes), H(c.fir_f16), H(c.f16.tz);
+    H(c.red_dtype), H(c.red_vec);
+    H(c.io_wf), H(c.io_bl), H(c.io_tp), H(c.io_out), H(c.io_tau), H(c.rio_wf), H(c.rio_bl), H(c.rio_thr), H(c.rio_ts), H(c.rio_mm), H(c.rio_tpt), H(c.rio_dwt);
+    H(c.fio_wf), H(c.fio_bl), H(c.fio_taps), H(c.fio_out), H(c.cio_wf), H(c.cio_t0), H(c.cio_out), H(c.pio_wf), H(c.pio_bl), H(c.pio_out), H(c.pio_tau), H(c.pio_mm);
+    H(c.dio_wf), H(c.dio_out), H(c.dio_pick), H(c.dio_walk), H(c.dio_walk_thr), H(c.dio_walk_ts), H(c.uio_wf), H(c.uio_taps), H(c.uio_out);
+    for (int S = 0; S < 2; ++S)
+        for (int k = 0; k < 3; ++k) H(c.plan[S].shift[k]), H(c.plan[S].cs[k]), H(c.plan[S].local[k]);
+    H(c.slot_base), H(c.slot_foot), H(c.slot_first_op), H(c.slot_last_op), H(c.slot_shares);
+    H(P.n_ops), H(P.n_slots), H(P.n_io), H(P.n_sregs), H(P.lds_elems_per_wave), H(P.sreg_off), H(P.waves_per_block), H(P.scratch_off), H(P.team);
+    for (int s = 0; s < n_slots; ++s) {
+        const DevSlot& d = P.slots[s];
+        H(d.off), H(d.len), H(d.C), H(d.pitch), H(d.invC), H(d.padw), H(d.zero_below), H(d.zero_above);
+    }
+    for (int k = 0; k < P.n_io; ++k) {
+        const DevIO& d = P.io[k];
+        H(d.kind), H(d.dtype), H(d.len), H(d.offset), H(d.row_stride), H(d.vec_ok);
+    }
+    H.bytes(P.ops, (size_t)P.n_ops * sizeof(DevOp));  // (every DevOp is cleared before it is filled)
+    if (c.fused_ok) digest_energy(H, c.fused);
+    if (c.rr_ok) digest_energy(H, c.rr);
+    if (c.rows_ok) {
+        const RowsArgs& A = c.rows;
+        H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.in_kind), H(A.sub_mode), H(A.bl_stride), H(A.bl_const), H(A.pz_kind), H(A.pz_param_nan), H(A.pz_c), H(A.n1), H(A.n2), H(A.d1), H(A.d2);
+        H(A.trap_kind), H(A.rise_pow2), H(A.lag), H(A.trap_all_nan), H(A.rr), H(A.ll), H(A.inv_rr), H(A.inv_ll), H(A.out_mm_stride), H(A.tpt_mode), H(A.tpt_use_min), H(A.thr_stride);
+        H(A.ts_stride), H(A.thr_const), H(A.ts_const), H(A.walk_nan), H(A.walk_frac), H(A.out_tpt_stride), H(A.dwt_level), H(A.dwt_part), H(A.dwt_stride), H(A.ring_entries), H(A.stop_at_start);
+    }
+    if (c.fir_ok) {
+        const FirArgs& A = c.fir;
+        H(A.wf_stride), H(A.wf_offset), H(A.n), H(A.in_kind), H(A.sub_mode), H(A.bl_stride), H(A.bl_const), H(A.n_kernels), H(A.m), H(A.p), H(A.out_stride), H(A.kend), H(A.scan_before);
+        H(A.scan_after), H(A.store), H(A.dshift);
+    }
+    if (c.cur_ok) {
+        const CurrentArgs& A = c.cur;
+        H(A.wf_stride), H(A.wf_offset), H(A.n_in), H(A.t0_stride), H(A.t0_const), H(A.win_len), H(A.ac_lag), H(A.ac_length), H(A.n_c), H(A.up_shift), H(A.up_half), H(A.n_up), H(A.ma_len);
+        H(A.ma_length), H(A.scan_rows), H(A.out_stride), H(A.scratch_per_wave);
+    }
+    if (c.pz_ok) {
+        const PzArgs& A = c.pz;
+        H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.in_kind), H(A.sub_mode), H(A.bl_stride), H(A.bl_const), H(A.tau_nan), H(A.c), H(A.out_stride), H(A.tau_stride), H(A.mm_stride), H(A.mm_on);
+        H(A.in_lo), H(A.in_hi);
+    }
+    if (c.red_ok) digest_reduce(H, c.red);
+    if (c.runs_ok) {
+        const FirRunsArgs& A = c.runs;
+        H(A.wf_stride), H(A.wf_offset), H(A.n), H(A.m), H(A.p), H(A.start), H(A.keep), H(A.out_stride), H(A.has_red);
+        if (A.has_red) digest_reduce(H, A.red);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     const long n_programs = argc > 1 ? atol(argv[1]) : 10000;
     const unsigned long long seed = argc > 2 ? strtoull(argv[2], nullptr, 0) : 0xD5BEEDull;
+    const bool with_digest = argc > 3 && !strcmp(argv[3], "digest");
+    Digest digest;
     rng.seed(seed);
     long accepted = 0, by_kind[9] = {0}, n_integer = 0;
     long kernels[11] = {0};
@@ -817,12 +910,25 @@ int main(int argc, char** argv) {
                 dump(p);
                 return 1;
             }
+            if (with_digest) digest(rc), digest.text(dsp_plan_last_error());
             continue;
         }
+        if (with_digest) digest(rc), digest_plan(digest, *plan, (int)p.slots.size());
         ++accepted;
         ++by_kind[kind <= 7 ? kind : 8];
         n_integer += plan->i64 ? 1 : 0;
-        kernels[plan->scalar_ok ? 0 : plan->pz_ok ? 1 : plan->red_ok ? 2 : plan->runs_ok ? 10 : plan->cur_ok ? 3 : plan->fir_ok ? 4 : plan->rows_ok ? 5 : plan->rr_ok ? 6 : plan->fused_ok ? 7 : plan->host.team >= 2 ? 8 : 9]++;
+        switch (dsp_plan_route(plan.get())) {  // (the summary's buckets: the three FIR kernels as one, the interpreter's teams apart)
+            case DSP_ROUTE_SCALAR: kernels[0]++; break;
+            case DSP_ROUTE_PZ_ROWS: kernels[1]++; break;
+            case DSP_ROUTE_REDUCE: kernels[2]++; break;
+            case DSP_ROUTE_FIR_RUNS: kernels[10]++; break;
+            case DSP_ROUTE_CURRENT: kernels[3]++; break;
+            case DSP_ROUTE_FIR_F16: case DSP_ROUTE_FIR_STORE: case DSP_ROUTE_FIR_MFMA: kernels[4]++; break;
+            case DSP_ROUTE_ROWS: kernels[5]++; break;
+            case DSP_ROUTE_ENERGY_RR: kernels[6]++; break;
+            case DSP_ROUTE_ENERGY: kernels[7]++; break;
+            case DSP_ROUTE_VM: kernels[plan->host.team >= 2 ? 8 : 9]++; break;
+        }
         if (!check(p, *plan)) {
             fprintf(stderr, "program %ld (seed %llu, kind %d, kernel %s)\n", it, seed, kind, dsp_plan_kernel_name(plan.get()));
             dump(p);
@@ -830,8 +936,10 @@ int main(int argc, char** argv) {
         }
     }
     printf("{\"programs\": %ld, \"accepted\": %ld, \"accepted_by_generator\": {\"energy\": %ld, \"rows\": %ld, \"fir\": %ld, \"pz\": %ld, \"reduce\": %ld, \"current\": %ld, \"scalar\": %ld, \"fir_runs\": %ld, \"random\": %ld}, "
-           "\"kernels\": {\"scalar\": %ld, \"pz_rows\": %ld, \"reduce\": %ld, \"current\": %ld, \"fir\": %ld, \"rows\": %ld, \"energy_rr\": %ld, \"energy\": %ld, \"vm_team\": %ld, \"vm\": %ld, \"fir_runs\": %ld}, \"integer_programs\": %ld}\n",
+           "\"kernels\": {\"scalar\": %ld, \"pz_rows\": %ld, \"reduce\": %ld, \"current\": %ld, \"fir\": %ld, \"rows\": %ld, \"energy_rr\": %ld, \"energy\": %ld, \"vm_team\": %ld, \"vm\": %ld, \"fir_runs\": %ld}, \"integer_programs\": %ld",
            n_programs, accepted, by_kind[0], by_kind[1], by_kind[2], by_kind[3], by_kind[4], by_kind[5], by_kind[6], by_kind[7], by_kind[8], kernels[0], kernels[1], kernels[2], kernels[3], kernels[4], kernels[5],
            kernels[6], kernels[7], kernels[8], kernels[9], kernels[10], n_integer);
+    if (with_digest) printf(", \"digest\": \"0x%016llx\"", (unsigned long long)digest.h);
+    printf("}\n");
     return 0;
 }
