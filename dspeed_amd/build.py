@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdspeed_hip.so")
 LIB_DIAG = os.path.join(HERE, "libdspeed_hip_diag.so")
-SOURCES = ["dsp_vm.hip", "dsp_energy.hip", "dsp_fit.hip", "dsp_rows.hip", "dsp_current.hip", "dsp_scalar.hip", "dsp_reduce.hip", "dsp_pz.hip", "dsp_fir_mfma.hip", "dsp_fir_f16.hip", "dsp_fir_runs.hip", "dsp_plan.cpp", "dsp_host.cpp"]
+SOURCES = ["dsp_vm.hip", "dsp_energy.hip", "dsp_energy_h.hip", "dsp_fit.hip", "dsp_rows.hip", "dsp_current.hip", "dsp_scalar.hip", "dsp_reduce.hip", "dsp_pz.hip", "dsp_fir_mfma.hip", "dsp_fir_f16.hip", "dsp_fir_runs.hip", "dsp_plan.cpp", "dsp_host.cpp"]
 DEPS = SOURCES + ["dsp_program.h", "dsp_plan.h", "dsp_wave.h", "dsp_reduce_tail.h", os.path.join("..", "..", "include", "dspeed_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall",
          "-Wno-unused-function"]
@@ -61,8 +61,10 @@ def _check_scratch(src: str, remarks: str) -> None:
 #: energy kernel reads and writes LDS 8 bytes a lane because ds_read_b64 costs the LDS array 2 cycles; hipcc fuses two neighbouring ones
 #: into ds_read2_b64 / ds_write2_b64, which the array serves at the 4-byte rate (8 cycles for 16 bytes), and only RR_NO_MERGE in
 #: dsp_energy.hip keeps it from doing so.  Every test passes either way and the kernel is 2 % slower: the build fails rather than ship that.
-RR_NO_FUSED_LDS = {"dsp_energy.hip": ("dsp_energy_rr_kernel", ("ds_read2_b64", "ds_write2_b64"),
-                                      "RR_NO_MERGE no longer keeps neighbouring 8-byte LDS accesses apart (see dsp_energy.hip)")}
+#: (dsp_energy_h.hip is dsp_energy.hip's second translation unit: the same kernel built for the 4-point pick-off mode)
+RR_NO_FUSED_LDS = {src: ("dsp_energy_rr_kernel", ("ds_read2_b64", "ds_write2_b64"),
+                         "RR_NO_MERGE no longer keeps neighbouring 8-byte LDS accesses apart (see dsp_energy.hip)")
+                   for src in ("dsp_energy.hip", "dsp_energy_h.hip")}
 
 
 def _llvm_tool(name: str) -> str | None:

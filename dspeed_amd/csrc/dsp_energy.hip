@@ -12,6 +12,7 @@
 //     LDS offsets, counted waits), the lane's own chunk in VGPRs from the staging to the end of the replay.  Per sample the
 //     LDS sees 2 writes (staging, pole-zero output) and 4 reads (own chunk once, three lagged trapezoid streams), the reads
 //     and the pole-zero output 8 bytes a lane at a time.
+//     Built twice: for the two-point pick-off modes here, for the 4-point mode in dsp_energy_h.hip (this file again, as a second unit).
 //   * dsp_energy_kernel ("classic"): the VM's slot layout (C = len/64, pitch C + 1, zero guard of 2 pitches below the slot),
 //     chunk loops software-pipelined in groups of 8 samples.  Bit-identical to the VM; kept as the cross-check of the
 //     default kernel and for A/B measurements (set_fused(15)).
@@ -364,14 +365,18 @@ __global__ void __launch_bounds__(256, 2) dsp_energy_kernel(EnergyArgs A, int64_
 }
 
 // ------------------------------------------------------------------------------------------------
-// Capture plan of the pad-free layout (C = len/64 + 2 samples per lane, sample i at LDS element i): for lag k and replay
-// sub-chain s the speculative carry needs the prefix sum `local` samples into sub-chain `cs` of the lane `shift` below.
-// Row-invariant, built by the host (dsp_host.cpp).
+// Carry plan of the pad-free layout (C = len/64 + 2 samples per lane, sample i at LDS element i): for lag k and replay sub-chain s the
+// speculative carry needs the float32 prefix sum of the first r samples of the chunk of the lane `shift` below.  The prefix is the side
+// array's group-end sum in front of the 8-sample group that holds sample r - 1, plus the first pn samples of that group.  Row-invariant,
+// built by the planner (plan_energy_carries in dsp_plan.cpp, which the CPU can test) in the form the kernel uses as it stands.
 // ------------------------------------------------------------------------------------------------
 struct EnergyPlan {
     int32_t shift[3][4];  // lane distance
-    int32_t cs[3][4];     // sub-chain that holds the capture point
-    int32_t local[3][4];  // capture after `local` samples of that sub-chain (0: nothing of it)
+    int32_t cs[3][4];     // sub-chain that holds the capture point, and ...
+    int32_t local[3][4];  // ... the samples of it in front of the point (the plan as the planner's checks read it; the kernel uses the form below)
+    int32_t grp[3][4];    // element offset, from the start of the lane's chunk, of the group's four pairs (8 * group; group NG: the two-sample tail)
+    int32_t side[3][4];   // element of the lane's side array that holds the sum of the groups in front, -1: none (group 0), read a word that holds 0.0f
+    int32_t pn[3][4];     // samples of the group in front of the capture point, 0 .. 8
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -403,6 +408,14 @@ struct EnergyPlan {
 //     the whole launch.  The compiler would fuse neighbouring 8-byte accesses into ds_read2_b64 / ds_write2_b64, which the LDS
 //     serves at the 4-byte rate again: RR_NO_MERGE keeps them apart.  The 8-sample re-run of the 4-point pick-off mode reads
 //     4 bytes at a run-time position and needs no parity case.  Figures: profiles/r05_headline_lds.md.
+//   * a wavefront issues at most one instruction per four cycles and the kernel's two wavefronts per SIMD saturate no pipe: outside the
+//     sample passes every instruction, scalar ones included, costs its four cycles, a branch tens.  So what a row does not need to work
+//     out is not worked out per row.  The carries take their plan from the host as it is used (EnergyPlan: pair address, side-array
+//     element, count; a capture in group 0 reads a word that holds 0.0f instead of selecting), held as lane addresses and one packed
+//     scalar across the row loop, and sum "the first pn of 8 samples" as all eight running prefixes and one indexed register move
+//     (s_set_gpr_idx_on with the wave-uniform pn) instead of eight masked additions.  The pick-off mode is a build of the kernel
+//     (WIDE): the two-point modes n f c l i end in straight-line selects, and only the build for the 4-point mode h holds the two
+//     8-sample re-runs.  Figures: profiles/r06_headline_serial.md.
 // S = sub-chains of the replay per lane: 2 halves the dependent-add chain but doubles the carry captures; measured slower.
 // ------------------------------------------------------------------------------------------------
 // IN: waveform element type in HBM: 0 float32, 1 int16, 2 uint16 (digitiser samples; widened to float32 while staging, exactly
@@ -411,7 +424,7 @@ struct EnergyPlan {
 // out of line, the device's exp is 200 instructions
 __device__ __attribute__((noinline)) double rr_decay(double tau) { return exp(-1.0 / tau); }
 
-template <int NPF, int KIND, int S, int IN, bool TAU = false>
+template <int NPF, int KIND, int S, int IN, bool TAU, bool WIDE>
 __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(EnergyArgs A, EnergyPlan PL, int64_t n_wf, int* err) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     // a chunk = NG groups of 8 samples (S sub-chains of NGS groups) and a two-sample tail that extends the last sub-chain
@@ -420,6 +433,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
     static_assert((C - 2) % (8 * S) == 0, "sub-chain length must be a whole number of 8-sample groups");
     static_assert(C % 2 == 0 && 64 * C - len == 128, "even pitch: 8-byte aligned lane chunks, two rows of virtual samples above len");
     typedef float f2 __attribute__((ext_vector_type(2)));
+    typedef float f9 __attribute__((ext_vector_type(9)));
     const int lane = lane_id();
     const double inv_rr = 1.0 / A.rr, inv_ll = 1.0 / A.ll;  // trap_norm / asym_trap divide by these counts every sample
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), wpb = (int)(blockDim.x >> 6);
@@ -444,6 +458,27 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
         lagpar[k] = A.q[k] & 1;                           // q[] carries the lags
         const int pos0 = lane * C - A.q[k] - lagpar[k];  // >= -C - 1: inside the guard
         lagb[k] = (pos0 + lagpar[k] >= -C) ? slot + pos0 : slot - (2 * C + 8);
+    }
+    // the carry plan as addresses of this lane (row-invariant): the capture group's pairs and the side-array element in front of it.  A
+    // capture in group 0 has nothing in front: it reads the first word above the image, which nothing ever writes (0.0f since the clear)
+    const f2* capp[3][S];
+    const float* sidep[3][S];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            capp[k][s] = mine2 + (PL.grp[k][s] >> 1);
+            sidep[k][s] = PL.side[k][s] >= 0 ? aux + PL.side[k][s] : slot + 64 * C;
+        }
+    // ... and the three counts pn of a sub-chain in one scalar, opaque to the optimiser: it is then one live register, not three words
+    // of the kernel's arguments loaded again in every row (the kernel is at its scalar-register limit)
+    float zero = 0.0f;  // P[0] of the prefixes, as a register (a constant element makes the compiler fill the vector from scalars first)
+    asm volatile("" : "+v"(zero));
+    int pnpack[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        pnpack[s] = PL.pn[0][s] | (PL.pn[1][s] << 4) | (PL.pn[2][s] << 8);
+        asm volatile("" : "+s"(pnpack[s]));
     }
 
     const int64_t stride_rows = (int64_t)gridDim.x * wpb;
@@ -601,21 +636,12 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 for (int s = 0; s < S; ++s) {
                     double Ak[3];
                     float pbase[3], pv[3][8];
-                    int pn[3];
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
-                        int r = PL.cs[k][s] * CS + PL.local[k][s];  // samples of the source lane's chunk before the capture point
-                        // opaque to the optimiser: otherwise every mask derived from the (row-invariant) plan is hoisted out of the
-                        // row loop and the kernel drowns in spilled SGPR pairs
-                        asm volatile("" : "+s"(r));
-                        const int gi = (r > 0 ? r - 1 : 0) >> 3;  // group that contains sample r-1
-                        pn[k] = r - 8 * gi;                        // 0..8 samples of group gi (gi == NG: the first sample of the two-sample tail)
-                        const float b = aux[gi > 0 ? gi - 1 : 0];
-                        pbase[k] = gi > 0 ? b : 0.0f;
-                        const f2* p = mine2 + 4 * gi;
+                        pbase[k] = *sidep[k][s];
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {  // (reads at most 6 past the chunk: inside the slot tail)
-                            const f2 v = p[u];
+                            const f2 v = capp[k][s][u];
                             RR_NO_MERGE();
                             pv[k][2 * u] = v.x;
                             pv[k][2 * u + 1] = v.y;
@@ -623,9 +649,15 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                     }
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
-                        float part = 0.0f;
+                        // all eight running prefixes of the group, then the one the plan names: P[i] has the bits the sum of the first i
+                        // samples had when the other 8 - i terms were added as +0.0f (the first addition to +0.0f makes every P[i], i >= 1,
+                        // a sum that cannot be -0.0f, so a trailing + 0.0f changed nothing).  pn is wave-uniform: one indexed register move
+                        float p[9];
+                        p[0] = zero;
 #pragma unroll
-                        for (int u = 0; u < 8; ++u) part += (u < pn[k]) ? pv[k][u] : 0.0f;
+                        for (int u = 0; u < 8; ++u) p[u + 1] = p[u] + pv[k][u];
+                        const f9 P = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8]};
+                        const float part = P[(pnpack[s] >> (4 * k)) & 15];
                         Ak[k] = wave_shift_up(Ep + (double)(pbase[k] + part), PL.shift[k][s]);
                     }
                     const double own = Ep + (s ? (double)aux[s * NGS - 1] : 0.0);
@@ -656,6 +688,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 }
                 // one test per BS samples (a not-taken branch still costs tens of cycles): bit q set = block q holds a wanted sample
                 int capmask = (capst[0] >= 0 ? 1 << capst[0] : 0) | (capst[1] >= 0 ? 1 << capst[1] : 0);
+                const bool ok1 = capst[1] >= 0;  // (sample i0 itself always exists here: 0 <= t_in <= len - 1)
                 asm volatile("" : "+s"(capmask));  // one live scalar, not a recomputation at each test
                 float* capbuf = slot + 64 * C + 16 + 64 * AUXP;  // 2 x 16 floats per wavefront, written by the lane that owns the sample
                 float ytail[2];  // the replay's output at the two samples of the tail
@@ -770,8 +803,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                     Dtot += D[s];
                 }
                 const double T0 = wave_exscan_add(Dtot);
-                // ---- wanted samples: re-run the one 8-sample group that contains each of them from its saved start state
-                const bool wide = (A.mode == 'h');
+                // ---- the two samples every mode needs, out of the capture buffer (or the tail's registers), with their lane's true carry
                 float w4[4];
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
@@ -781,46 +813,61 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
 #pragma unroll
                     for (int s = 1; s < S; ++s)
                         if (capoff[k] >= s * CS) delta = (T0 + Dbefore[s]) - (double)g[s];
-                    w4[1 + k] = capst[k] >= 0 ? readlane((float)((double)v + delta), caplane[k]) : 0.0f;
+                    w4[1 + k] = (k == 0 || ok1) ? readlane((float)((double)v + delta), caplane[k]) : 0.0f;
                 }
+                if constexpr (!WIDE) {
+                    // ---- the two-point modes n f c l i (and an unknown mode's error), straight line: the expressions of pickoff_eval
+                    // (dsp_wave.h), all evaluated, the mode and "t_in is a whole number" applied as selects on wave-uniform values.  (A time
+                    // between two samples has both in range: t_in <= len - 1.)
+                    const int mode = A.mode;
+                    const double t0 = (double)t_in - (double)i0, t1 = 1.0 - t0;
+                    const float lin = (float)(t1 * (double)w4[1] + t0 * (double)w4[2]);
+                    const bool whole = (float)i0 == t_in, lo = t0 < 0.5;
+                    const bool take1 = whole || mode == 'f' || (mode == 'n' && lo), take2 = mode == 'c' || (mode == 'n' && !lo);
+                    result = take1 ? w4[1] : (take2 ? w4[2] : (mode == 'l' ? lin : quiet_nan<float>()));
+                    const int fc = (take1 || take2 || mode == 'l') ? 0 : (mode == 'i' ? DSP_E_FTP_INT : DSP_E_FTP_MODE);
+                    if (fc) report(fc, row);
+                } else {
+                    // ---- the 4-point mode h: its outer two samples by re-running the one 8-sample group that holds each from its saved start state
 #pragma unroll
-                for (int k = 0; k < 4; k += 3) {  // the outer two samples of the 4-point mode: re-run their 8-sample group
-                    const int e = i0 - 1 + k;
-                    const bool need = wide && e >= 0 && e < len;
-                    w4[k] = 0.0f;
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (need) {  // uniform
-                        const int l = e / C, off = e - l * C;
-                        int ch = off / CS;
-                        if (ch > S - 1) ch = S - 1;
-                        const int loc = off - ch * CS;  // 0..CS+1 (CS, CS+1: the two-sample tail, chain S-1 only)
-                        const int gi = loc >> 3, u0 = loc & 7;
-                        float ys = aux[ch * NGS + gi], gsel = 0.0f;  // (chain S-1, group NGS) -> aux[S*NGS]
-                        double dsel = 0.0;
+                    for (int k = 0; k < 4; k += 3) {
+                        const int e = i0 - 1 + k;
+                        const bool need = e >= 0 && e < len;
+                        w4[k] = 0.0f;
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (need) {  // uniform
+                            const int l = e / C, off = e - l * C;
+                            int ch = off / CS;
+                            if (ch > S - 1) ch = S - 1;
+                            const int loc = off - ch * CS;  // 0..CS+1 (CS, CS+1: the two-sample tail, chain S-1 only)
+                            const int gi = loc >> 3, u0 = loc & 7;
+                            float ys = aux[ch * NGS + gi], gsel = 0.0f;  // (chain S-1, group NGS) -> aux[S*NGS]
+                            double dsel = 0.0;
 #pragma unroll
-                        for (int s = 0; s < S; ++s)
-                            if (ch == s) {
-                                gsel = g[s];
-                                dsel = Dbefore[s];
+                            for (int s = 0; s < S; ++s)
+                                if (ch == s) {
+                                    gsel = g[s];
+                                    dsel = Dbefore[s];
+                                }
+                            const int base = ch * CS + gi * 8;
+                            float yk = ys;
+#pragma unroll
+                            for (int u = 0; u < 8; ++u) {
+                                const int tt = base + u;  // (beyond the chunk for the tail's group: reads stay in the slot tail, unused)
+                                // (4-byte reads at a run-time position: no parity case needed, and the 4-point mode alone comes here.  At the even
+                                // pitch they put two lanes on a bank, (2 lane + tt) mod 32: twice the array cycles, for 32 reads at most twice a row)
+                                ys = trap_step_r<float, KIND>(ys, mine[tt], lagb[0][tt + lagpar[0]], lagb[1][tt + lagpar[1]], lagb[2][tt + lagpar[2]], A.rr, A.ll,
+                                                              inv_rr, inv_ll);
+                                if (u == u0) yk = ys;
                             }
-                        const int base = ch * CS + gi * 8;
-                        float yk = ys;
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) {
-                            const int tt = base + u;  // (beyond the chunk for the tail's group: reads stay in the slot tail, unused)
-                            // (4-byte reads at a run-time position: no parity case needed, and the 4-point mode alone comes here.  At the even
-                            // pitch they put two lanes on a bank, (2 lane + tt) mod 32: twice the array cycles, for 32 reads at most twice a row)
-                            ys = trap_step_r<float, KIND>(ys, mine[tt], lagb[0][tt + lagpar[0]], lagb[1][tt + lagpar[1]], lagb[2][tt + lagpar[2]], A.rr, A.ll,
-                                                          inv_rr, inv_ll);
-                            if (u == u0) yk = ys;
+                            const double delta = (T0 + dsel) - (double)gsel;
+                            w4[k] = readlane((float)((double)yk + delta), l);
                         }
-                        const double delta = (T0 + dsel) - (double)gsel;
-                        w4[k] = readlane((float)((double)yk + delta), l);
                     }
+                    int fc = 0;
+                    result = pickoff_eval(t_in, (int)'h', len, w4, fc);
+                    if (fc) report(fc, row);
                 }
-                int fc = 0;
-                result = pickoff_eval(t_in, A.mode, len, w4, fc);
-                if (fc) report(fc, row);
             }
         }
         pend_result = result;
@@ -836,22 +883,49 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
     }
 }
 
+// This file is two translation units (build.py compiles it twice; the kernels are templates in an unnamed namespace, each unit holds the
+// instantiations it launches): unit 0, the file as it stands, has the classic kernel and the register-resident kernel of the two-point
+// pick-off modes; unit 1 (dsp_energy_h.hip: DSP_ENERGY_UNIT 1 and this file included) has the register-resident kernel of the 4-point
+// mode h -- the only code that holds the two 8-sample re-runs.  The pick-off mode is fixed for a chain's life; the host knows it at the launch.
+#ifndef DSP_ENERGY_UNIT
+#define DSP_ENERGY_UNIT 0
+#endif
+
 template <int KIND, int S, int IN, bool TAU = false>
 int launch_rr_kind(const EnergyArgs& A, const EnergyPlan& PL, int npf, int64_t n_wf, int* err, int blocks, int threads, int lds_bytes,
                    hipStream_t st) {
+    constexpr bool W = DSP_ENERGY_UNIT == 1;
     switch (npf) {
-        case 4: hipLaunchKernelGGL((dsp_energy_rr_kernel<4, KIND, S, IN, TAU>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
-        case 8: hipLaunchKernelGGL((dsp_energy_rr_kernel<8, KIND, S, IN, TAU>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
-        case 16: hipLaunchKernelGGL((dsp_energy_rr_kernel<16, KIND, S, IN, TAU>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
+        case 4: hipLaunchKernelGGL((dsp_energy_rr_kernel<4, KIND, S, IN, TAU, W>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
+        case 8: hipLaunchKernelGGL((dsp_energy_rr_kernel<8, KIND, S, IN, TAU, W>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
+        case 16: hipLaunchKernelGGL((dsp_energy_rr_kernel<16, KIND, S, IN, TAU, W>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err); break;
         case 32:  // 8192 samples (production LEGEND rows): 130 samples per lane, one wavefront per SIMD (512-register budget, 38.9 KB of LDS)
             if (S != 1) return (int)hipErrorInvalidValue;
-            hipLaunchKernelGGL((dsp_energy_rr_kernel<32, KIND, 1, IN, TAU>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err);
+            hipLaunchKernelGGL((dsp_energy_rr_kernel<32, KIND, 1, IN, TAU, W>), dim3(blocks), dim3(threads), lds_bytes, st, A, PL, n_wf, err);
             break;
         default: return (int)hipErrorInvalidValue;
     }
     return (int)hipGetLastError();
 }
 
+// S = sub-chains of the trapezoid replay (1: default, 2: measured slower, kept for A/B, float32 rows only); wf_dtype = DSP_F32 / DSP_I16 / DSP_U16 rows
+int launch_rr(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype, int64_t n_wf, int* err, int blocks,
+              int threads, int lds_bytes, hipStream_t stream) {
+#define GO_(KIND)                                                                                                          \
+    if (A->tau && wf_dtype == DSP_I16) return launch_rr_kind<KIND, 1, 1, true>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream); \
+    if (A->tau && wf_dtype == DSP_U16) return launch_rr_kind<KIND, 1, 2, true>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream); \
+    if (A->tau) return launch_rr_kind<KIND, 1, 0, true>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream);       \
+    if (wf_dtype == DSP_I16) return launch_rr_kind<KIND, 1, 1>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream); \
+    if (wf_dtype == DSP_U16) return launch_rr_kind<KIND, 1, 2>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream); \
+    return S == 2 ? launch_rr_kind<KIND, 2, 0>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream)                \
+                  : launch_rr_kind<KIND, 1, 0>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream);
+    if (trap_opcode == DSP_OP_TRAP_FILTER) { GO_(TRAP_FILTER) }
+    if (trap_opcode == DSP_OP_TRAP_NORM) { GO_(TRAP_NORM) }
+    GO_(TRAP_ASYM)
+#undef GO_
+}
+
+#if DSP_ENERGY_UNIT == 0
 template <int KIND>
 int launch_kind(const EnergyArgs& A, int npf, int64_t n_wf, int* err, int blocks, int threads, int lds_bytes, hipStream_t s) {
     switch (npf) {
@@ -887,23 +961,22 @@ extern "C" int dsp_internal_set_energy_lds(int trap_opcode, int npf, int lds_byt
     return (int)hipErrorInvalidValue;
 }
 
-// register-resident kernel; S = sub-chains of the trapezoid replay (1: default, 2: measured slower, kept for A/B, float32 rows only);
-// plan[S - 1]; wf_dtype = DSP_F32 / DSP_I16 / DSP_U16 rows
+extern "C" int dsp_internal_launch_energy_rr_h(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype,
+                                               int64_t n_wf, int* err, int blocks, int threads, int lds_bytes, hipStream_t stream);  // (unit 1)
+
+// register-resident kernel, plan[S - 1]: the build for the chain's pick-off mode class
 extern "C" int dsp_internal_launch_energy_rr(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype,
                                              int64_t n_wf, int* err, int blocks, int threads, int lds_bytes, hipStream_t stream) {
-#define GO_(KIND)                                                                                                          \
-    if (A->tau && wf_dtype == DSP_I16) return launch_rr_kind<KIND, 1, 1, true>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream); \
-    if (A->tau && wf_dtype == DSP_U16) return launch_rr_kind<KIND, 1, 2, true>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream); \
-    if (A->tau) return launch_rr_kind<KIND, 1, 0, true>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream);       \
-    if (wf_dtype == DSP_I16) return launch_rr_kind<KIND, 1, 1>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream); \
-    if (wf_dtype == DSP_U16) return launch_rr_kind<KIND, 1, 2>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream); \
-    return S == 2 ? launch_rr_kind<KIND, 2, 0>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream)                \
-                  : launch_rr_kind<KIND, 1, 0>(*A, *PL, npf, n_wf, err, blocks, threads, lds_bytes, stream);
-    if (trap_opcode == DSP_OP_TRAP_FILTER) { GO_(TRAP_FILTER) }
-    if (trap_opcode == DSP_OP_TRAP_NORM) { GO_(TRAP_NORM) }
-    GO_(TRAP_ASYM)
-#undef GO_
+    return (A->mode == 'h' ? dsp_internal_launch_energy_rr_h : launch_rr)(A, PL, trap_opcode, npf, S, wf_dtype, n_wf, err, blocks, threads, lds_bytes, stream);
 }
 extern "C" const char* dsp_internal_energy_rr_kernel_name() { return "dsp_energy_rr_kernel"; }
 
 extern "C" const char* dsp_internal_energy_kernel_name() { return "dsp_energy_kernel"; }
+#else
+}  // namespace
+
+extern "C" int dsp_internal_launch_energy_rr_h(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype,
+                                               int64_t n_wf, int* err, int blocks, int threads, int lds_bytes, hipStream_t stream) {
+    return launch_rr(A, PL, trap_opcode, npf, S, wf_dtype, n_wf, err, blocks, threads, lds_bytes, stream);
+}
+#endif

@@ -1463,6 +1463,29 @@ static void fold_load_bl_subtract(PlanCtx& c) {
     }
 }
 
+// Carry plan of the register-resident energy kernel (EnergyPlan, dsp_plan.h): Ci samples per lane, S replay sub-chains of (Ci - 2) / S
+// samples (the chunk's last two extend the last one), the three lags of the trapezoid.  Sub-chain s of a lane starts at sample s CS of its
+// chunk; its lagged stream k starts `lag` samples lower, r samples into the chunk of the lane `shift` below (0 <= r < Ci).  The carry is
+// the prefix sum of those r samples: the side array's group-end sum in front of the 8-sample group that holds sample r - 1 (none in
+// front of group 0) plus the first pn samples of that group -- all of it in the form the kernel uses without arithmetic of its own.
+extern "C" void dsp_internal_plan_energy_carries(int Ci, int S, const int32_t* lags, EnergyPlan* plan) {
+    const int CS = (Ci - 2) / S;
+    for (int k = 0; k < 3; ++k)
+        for (int sidx = 0; sidx < 4; ++sidx) {
+            const bool used = sidx < S;
+            const int pos = used ? sidx * CS - lags[k] : 0;  // samples before the sub-chain start, relative to the chunk
+            const int r = ((pos % Ci) + Ci) % Ci;             // ... = r samples into the chunk of the lane `shift` below
+            const int gi = (r > 0 ? r - 1 : 0) >> 3;          // group that holds sample r - 1 (group (Ci - 2) / 8: the two-sample tail)
+            const int cs = r / CS > S - 1 ? S - 1 : r / CS;
+            plan->shift[k][sidx] = (r - pos) / Ci;
+            plan->cs[k][sidx] = cs;
+            plan->local[k][sidx] = r - cs * CS;
+            plan->grp[k][sidx] = 8 * gi;
+            plan->side[k][sidx] = gi - 1;  // (-1: nothing in front)
+            plan->pn[k][sidx] = r - 8 * gi;
+        }
+}
+
 // Register-resident kernel: C = len/64 + 2 samples per lane (an even pitch: every lane's chunk is 8-byte aligned), linear LDS
 // image of the waveform (1024 .. 8192 samples); a chunk is (C - 2) / 8 groups of 8 samples and a two-sample tail
 static void plan_energy_rr(PlanCtx& c, const DevOp& dtp) {
@@ -1485,20 +1508,7 @@ static void plan_energy_rr(PlanCtx& c, const DevOp& dtp) {
         I.q[k] = dtp.ic[k];  // the lags themselves
         I.rho[k] = 0;
     }
-    for (int S = 1; S <= 2; ++S) {
-        const int CS = (Ci - 2) / S;
-        for (int k = 0; k < 3; ++k)
-            for (int sidx = 0; sidx < S; ++sidx) {
-                const int pos = sidx * CS - dtp.ic[k];          // samples before the sub-chain start, relative to the chunk
-                const int r = ((pos % Ci) + Ci) % Ci;           // ... = r samples into the chunk of the lane `shift` below
-                const int shift = (r - pos) / Ci;
-                int cs = r / CS;
-                if (cs > S - 1) cs = S - 1;
-                ch->plan[S - 1].shift[k][sidx] = shift;
-                ch->plan[S - 1].cs[k][sidx] = cs;
-                ch->plan[S - 1].local[k][sidx] = r - cs * CS;
-            }
-    }
+    for (int S = 1; S <= 2; ++S) dsp_internal_plan_energy_carries(Ci, S, dtp.ic, &ch->plan[S - 1]);
     ch->rr_ok = true;
     ch->variant = 6;
     if (const char* venv = getenv("DSPEED_HIP_VARIANT")) ch->variant = atoi(venv);  // A/B runs: 1, 6, 8

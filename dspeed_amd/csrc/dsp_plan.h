@@ -45,11 +45,16 @@ struct EnergyArgs {
     int32_t ablate;
 };
 
-struct EnergyPlan {
+struct EnergyPlan {  // [lag][replay sub-chain]
     int32_t shift[3][4];
     int32_t cs[3][4];
     int32_t local[3][4];
+    int32_t grp[3][4];
+    int32_t side[3][4];
+    int32_t pn[3][4];
 };
+// (dsp_plan.cpp; exported for the CPU tests)
+extern "C" void dsp_internal_plan_energy_carries(int Ci, int S, const int32_t* lags, EnergyPlan* plan);
 
 // geometry of the kernels, defined beside them (host arithmetic on their tile constants: dsp_current.hip, dsp_fir_mfma.hip, dsp_fir_f16.hip)
 extern "C" int dsp_internal_current_lds_bytes(int ma_len);
