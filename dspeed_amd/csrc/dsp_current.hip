@@ -25,7 +25,8 @@
 // upsampler.py:13-56, min_max.py:11-82.  Compiled with -ffp-contract=off: one rounding per written operation.
 #include <hip/hip_runtime.h>
 
-#include "dsp_program.h"
+#include "dsp_kernels.h"
+#include "dsp_launch.h"
 #include "dsp_wave.h"
 
 #define CUR_LDS __attribute__((address_space(3)))
@@ -34,7 +35,7 @@
 
 namespace {
 
-constexpr int CB = 16;  // samples per block (= per checkpoint)
+using namespace dsp_current;  // CB: samples per block (= per checkpoint)
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -283,8 +284,6 @@ int set_lds_sh(int lds_bytes) {
 
 }  // namespace
 
-extern "C" int dsp_internal_current_lds_bytes(int ma_len) { return (ma_len / CB + 1) * CB * 64 * 4; }
-
 extern "C" int dsp_internal_launch_current(const CurrentArgs* A, int64_t n_wf, int blocks, int lds_bytes, hipStream_t stream) {
     if (n_wf <= 0) return 0;
     switch (A->up_shift) {
@@ -304,5 +303,3 @@ extern "C" int dsp_internal_set_current_lds(int lds_bytes) {
     if (!rc) rc = set_lds_sh<4>(lds_bytes);
     return rc;
 }
-
-extern "C" const char* dsp_internal_current_kernel_name() { return "dsp_current_kernel"; }

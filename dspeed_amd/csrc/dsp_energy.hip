@@ -21,38 +21,9 @@
 
 #include <type_traits>
 
-#include "dsp_program.h"
+#include "dsp_kernels.h"
+#include "dsp_launch.h"
 #include "dsp_wave.h"
-
-struct EnergyArgs {
-    const void* wf;        // waveform rows
-    int64_t wf_stride;     // elements between rows
-    int32_t wf_offset;     // first sample used
-    int32_t len;           // samples per waveform
-    const float* bl;       // per-waveform baseline column, or nullptr
-    int64_t bl_stride;
-    float bl_const;
-    int32_t has_bl;        // 0: the chain has no bl_subtract (bl_const is then 0: x - 0 == x exactly)
-    const float* tp;       // per-waveform pick-off time column, or nullptr
-    int64_t tp_stride;
-    float tp_const;
-    int32_t mode;          // pick-off mode char
-    float* out;
-    int64_t out_stride;
-    double c;              // exp(-1/tau)
-    double rr, ll;         // rise, fall as float64
-    int32_t tau_nan;
-    int32_t all_nan;       // trap_filter with rise == 0
-    int32_t C, pitch;      // samples per lane, C + 1
-    float invC;
-    int32_t q[3], rho[3];  // lag = q*C + rho
-    int32_t lds_elems_per_wave;
-    int32_t slot_off;      // element offset of the slot inside the wave's region (2*pitch guard below it)
-    const float* tau;      // or null: the pole-zero time constant per event (a column) instead of c / tau_nan -- the TAU builds of the register-resident kernel
-    int64_t tau_stride;
-    int32_t ablate;        // diagnostic build only (-DDSPEED_HIP_DIAG, libdspeed_hip_diag.so): bit 0/1/2 = skip pass 1/2/3 (results are then
-                           // wrong), bit 3 = per-phase cycle stamps.  The product library ignores the field: ABLATE below is a constant 0.
-};
 
 #ifdef DSPEED_HIP_DIAG
 #define ABLATE(A) ((A).ablate)
@@ -365,21 +336,6 @@ __global__ void __launch_bounds__(256, 2) dsp_energy_kernel(EnergyArgs A, int64_
 }
 
 // ------------------------------------------------------------------------------------------------
-// Carry plan of the pad-free layout (C = len/64 + 2 samples per lane, sample i at LDS element i): for lag k and replay sub-chain s the
-// speculative carry needs the float32 prefix sum of the first r samples of the chunk of the lane `shift` below.  The prefix is the side
-// array's group-end sum in front of the 8-sample group that holds sample r - 1, plus the first pn samples of that group.  Row-invariant,
-// built by the planner (plan_energy_carries in dsp_plan.cpp, which the CPU can test) in the form the kernel uses as it stands.
-// ------------------------------------------------------------------------------------------------
-struct EnergyPlan {
-    int32_t shift[3][4];  // lane distance
-    int32_t cs[3][4];     // sub-chain that holds the capture point, and ...
-    int32_t local[3][4];  // ... the samples of it in front of the point (the plan as the planner's checks read it; the kernel uses the form below)
-    int32_t grp[3][4];    // element offset, from the start of the lane's chunk, of the group's four pairs (8 * group; group NG: the two-sample tail)
-    int32_t side[3][4];   // element of the lane's side array that holds the sum of the groups in front, -1: none (group 0), read a word that holds 0.0f
-    int32_t pn[3][4];     // samples of the group in front of the capture point, 0 .. 8
-};
-
-// ------------------------------------------------------------------------------------------------
 // "rr" (register resident) kernel.
 //
 // What the measurements on MI355X said (profiles/r01_summary.md has the counters): a wavefront of this chain is bound by its
@@ -445,9 +401,11 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
     f2* mine2 = reinterpret_cast<f2*>(mine);  // (the wave's region, slot_off and lane * C are all even numbers of elements)
     // per-lane side array (pitch 9, odd): group-end prefix sums of pass 2, later the group-start states of the replay.  Kept in
     // LDS so that "the value of group gi" with a run-time gi is an address, not a register select chain
-    constexpr int AUXP = NG + 1 <= 9 ? 9 : ((NG + 1) | 1);  // (9 for up to 4096 samples, 17 for 8192; the host sizes the region the same way)
+    // (9 for up to 4096 samples, 17 for 8192).  The region's layout is the planner's, which sizes it and sets slot_off: dsp_kernels.h
+    constexpr int AUXP = dsp_energy_rr::layout(C).side_pitch, GUARD = dsp_energy_rr::layout(C).guard, TAIL = dsp_energy_rr::layout(C).tail;
     static_assert(NG + 1 <= AUXP && S * NGS + 1 <= AUXP && (AUXP & 1) == 1, "side array too small");
-    float* aux = slot + 64 * C + 16 + lane * AUXP;
+    static_assert(GUARD >= 2 * C + 8 && dsp_energy_rr::layout(C).slot_off >= GUARD, "lagged reads before sample 0 stay inside the guard");
+    float* aux = slot + 64 * C + TAIL + lane * AUXP;
     // the lagged window of the lane starts at element lane*C - lag: 8-byte aligned for an even lag; for an odd one the aligned pairs
     // start one element lower and step t takes element t + 1 of them.  lagb[] is that aligned start (windows wholly below sample 0
     // read the zero guard, whatever the parity), lagpar[] the wave-uniform, row-invariant parity of each lag
@@ -457,7 +415,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
     for (int k = 0; k < 3; ++k) {
         lagpar[k] = A.q[k] & 1;                           // q[] carries the lags
         const int pos0 = lane * C - A.q[k] - lagpar[k];  // >= -C - 1: inside the guard
-        lagb[k] = (pos0 + lagpar[k] >= -C) ? slot + pos0 : slot - (2 * C + 8);
+        lagb[k] = (pos0 + lagpar[k] >= -C) ? slot + pos0 : slot - GUARD;
     }
     // the carry plan as addresses of this lane (row-invariant): the capture group's pairs and the side-array element in front of it.  A
     // capture in group 0 has nothing in front: it reads the first word above the image, which nothing ever writes (0.0f since the clear)
@@ -690,7 +648,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 int capmask = (capst[0] >= 0 ? 1 << capst[0] : 0) | (capst[1] >= 0 ? 1 << capst[1] : 0);
                 const bool ok1 = capst[1] >= 0;  // (sample i0 itself always exists here: 0 <= t_in <= len - 1)
                 asm volatile("" : "+s"(capmask));  // one live scalar, not a recomputation at each test
-                float* capbuf = slot + 64 * C + 16 + 64 * AUXP;  // 2 x 16 floats per wavefront, written by the lane that owns the sample
+                float* capbuf = slot + 64 * C + TAIL + 64 * AUXP;  // 2 x 16 floats per wavefront, written by the lane that owns the sample
                 float ytail[2];  // the replay's output at the two samples of the tail
                 // The lagged streams are read as aligned 8-byte pairs.  With the parity par[k] of lag k a compile-time constant, "element
                 // t + par[k] of the pair sequence" names a register in this straight-line code: one copy of the replay per parity case,
@@ -961,17 +919,11 @@ extern "C" int dsp_internal_set_energy_lds(int trap_opcode, int npf, int lds_byt
     return (int)hipErrorInvalidValue;
 }
 
-extern "C" int dsp_internal_launch_energy_rr_h(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype,
-                                               int64_t n_wf, int* err, int blocks, int threads, int lds_bytes, hipStream_t stream);  // (unit 1)
-
-// register-resident kernel, plan[S - 1]: the build for the chain's pick-off mode class
+// register-resident kernel, plan[S - 1]: the build for the chain's pick-off mode class (mode h: unit 1)
 extern "C" int dsp_internal_launch_energy_rr(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype,
                                              int64_t n_wf, int* err, int blocks, int threads, int lds_bytes, hipStream_t stream) {
     return (A->mode == 'h' ? dsp_internal_launch_energy_rr_h : launch_rr)(A, PL, trap_opcode, npf, S, wf_dtype, n_wf, err, blocks, threads, lds_bytes, stream);
 }
-extern "C" const char* dsp_internal_energy_rr_kernel_name() { return "dsp_energy_rr_kernel"; }
-
-extern "C" const char* dsp_internal_energy_kernel_name() { return "dsp_energy_kernel"; }
 #else
 }  // namespace
 

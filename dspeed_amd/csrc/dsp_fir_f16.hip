@@ -22,7 +22,8 @@
 //   * rows holding a NaN / an infinity are handled as by the float32 kernels (all NaN, or tap by tap in float32).
 #include <hip/hip_runtime.h>
 
-#include "dsp_program.h"
+#include "dsp_kernels.h"
+#include "dsp_launch.h"
 #include "dsp_wave.h"
 
 #include <cstdlib>
@@ -34,26 +35,12 @@
 
 namespace {
 
-#ifndef F16_BK
-#define F16_BK 64
-#endif
-#ifndef F16_BM
-#define F16_BM 64
-#endif
-constexpr int BM = F16_BM, BN = 320, BK = F16_BK, MT = 2, NT = 5;  // BM 64: 8 wavefronts (2 x 4); BM 32: 4 wavefronts, two workgroups per CU
+using namespace dsp_fir_f16;  // BM, BK (the F16_BM / F16_BK A/B macros), APITCH, TB, TWIN, TPITCH
+constexpr int BN = 320, MT = 2, NT = 5;
 constexpr int NTHR = BM * 8;                                        // 8 threads stage a row
 constexpr int TAPV = (16 * ((336 + F16_BK) / 8) + NTHR - 1) / NTHR;  // tap-window vectors a thread stages
 constexpr int SV = BK / 64;  // 8-sample vectors a thread stages per stage
-// LDS reads are ds_read_b128: four fixed groups of 16 lanes per instruction, 64 banks -- a group is conflict-free when its 16 addresses fall
-// into 16 different 16-byte slots of the 256-byte bank line (MI355X_MICROARCH.md, LDS).
-constexpr int APITCH = BK + 16;  // halfs per A row: 10 (BK 64) / 18 (BK 128) slots, = 2 modulo 16: lane (row j, k-block h) sits in slot 10 j + h, no two alike in a group
-constexpr int TB = 336;          // zero margin below tap 0: window index TB + k - column - e - shift is never negative
-constexpr int TWIN = TB + BK;    // taps a stage's fragments can reach
-// a tap copy in LDS: a multiple of 256 bytes, so that a copy's slot is its own offset only; copy r starts tap_slot[e][r] slots in -- for
-// every alignment e of the window a table that puts the 16 lanes of every group (eight columns x two k-blocks, five copies apart at most
-// identical addresses, which broadcast) into 16 different slots (found by search, tools/fir_f16_banks.py; the plain pitch had 51 % of the
-// LDS-array cycles as conflicts)
-constexpr int TPITCH = ((TWIN + 8 + 15 * 8 + 127) / 128) * 128;
+// copy r of the taps starts tap_slot[e][r] 16-byte slots into its TPITCH (dsp_kernels.h), e the alignment of the window
 __constant__ unsigned char tap_slot[8][8] = {{2, 5, 9, 6, 15, 12, 9, 15}, {7, 2, 8, 3, 5, 0, 15, 12}, {1, 11, 2, 13, 5, 9, 8, 6}, {8, 4, 11, 1, 4, 0, 15, 8},
                                              {7, 9, 3, 12, 15, 7, 13, 2}, {8, 11, 2, 14, 6, 9, 12, 3}, {3, 7, 6, 11, 0, 4, 15, 11}, {5, 4, 8, 9, 13, 3, 11, 1}};
 // F16_PIPE 0: the stages of the amax form as those of the kept-output form (A/B: C3 34.0 M waveforms/s; 35.2 M with one vector instruction dealt
@@ -636,14 +623,6 @@ __global__ void __launch_bounds__(NTHR, 1) dsp_fir_f16_kernel(FirArgs A_, FirF16
 
 }  // namespace
 
-// halfs of the tap image of one kernel: 16 copies of TZ = the longest K window rounded up to a stage + the window the last stage reaches +
-// the margin the shifted copies reach into, then the inverse scale (one float, kept 16-byte aligned)
-extern "C" int dsp_internal_fir_f16_tz(int kend) { return ((kend + 8 + BK - 1) / BK) * BK + TWIN + 16; }
-extern "C" size_t dsp_internal_fir_f16_taps_bytes(int kend) { return (size_t)16 * dsp_internal_fir_f16_tz(kend) * 2 + 16; }
-extern "C" int dsp_internal_fir_f16_lds_bytes() { return (2 * 2 * BM * APITCH + 2 * 16 * TPITCH) * 2 + (BM * 4 * 2 + BM) * 4; }
-
-extern "C" int dsp_internal_fir_fixup(const FirArgs* A, int64_t n_wf, hipStream_t stream);  // dsp_fir_mfma.hip
-
 template <int IN>
 static void launch_f16(const FirArgs* A, const FirF16Taps* T, int64_t n_wf, int lds_bytes, hipStream_t stream) {
     if (!T->rows_done)
@@ -698,5 +677,3 @@ extern "C" int dsp_internal_set_fir_f16_lds(int lds_bytes) {
     }
     return 0;
 }
-
-extern "C" const char* dsp_internal_fir_f16_kernel_name() { return "dsp_fir_f16_kernel"; }

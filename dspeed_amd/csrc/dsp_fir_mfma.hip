@@ -23,7 +23,8 @@
 // outputs into NaN that the reference leaves finite or infinite.
 #include <hip/hip_runtime.h>
 
-#include "dsp_program.h"
+#include "dsp_kernels.h"
+#include "dsp_launch.h"
 #include "dsp_wave.h"
 
 #define FIR_LDS __attribute__((address_space(3)))
@@ -32,7 +33,8 @@
 
 namespace {
 
-constexpr int BM = 64, BN = 320, BK = 32, APITCH = 36, KCHUNK = 128;
+using namespace dsp_fir_mfma;  // BM, BN, APITCH, TB
+constexpr int BK = 32, KCHUNK = 128;
 constexpr int MT = 2, NT = 5;  // 16 x 16 tiles per wavefront: 32 rows x 80 columns
 
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -266,7 +268,7 @@ __global__ void __launch_bounds__(512, 2) dsp_fir_mfma_kernel(FirArgs A_, int64_
 // index) with the same zero-margined reversed kernel; K = 320 + m - 1 + e rounded up to 32.  A wavefront's 80 columns meet the band of a
 // short kernel only in some of the stages: the others are skipped (the tile's barriers stay).  No screening here: dsp_fir_fixup_kernel
 // looks at the rows afterwards and rewrites the ones holding a NaN (all NaN, convolutions.py:40-43) or an infinity (tap by tap).
-constexpr int TB = BN + 4, SCHUNK = 64;
+constexpr int SCHUNK = 64;
 
 template <int IN>
 __global__ void __launch_bounds__(512, 2) dsp_fir_store_kernel(FirArgs A_, int64_t n_wf) {
@@ -484,8 +486,6 @@ __global__ void __launch_bounds__(256) dsp_fir_fixup_kernel(FirArgs A_, int64_t 
 
 }  // namespace
 
-extern "C" int dsp_internal_fir_store_lds_bytes(int kend) { return (((TB + kend + 3) & ~3) + 2 * BM * APITCH) * 4; }
-
 extern "C" int dsp_internal_launch_fir_store(const FirArgs* A, int64_t n_wf, int lds_bytes, hipStream_t stream) {
     if (n_wf <= 0 || A->p[0] <= 0) return 0;
     const dim3 grid((unsigned)((A->p[0] + BN - 1) / BN), (unsigned)((n_wf + BM - 1) / BM));
@@ -529,10 +529,6 @@ extern "C" int dsp_internal_set_fir_store_lds(int lds_bytes) {
     return 0;
 }
 
-extern "C" const char* dsp_internal_fir_store_kernel_name() { return "dsp_fir_store_kernel"; }
-
-extern "C" int dsp_internal_fir_mfma_lds_bytes(int kend) { return (((BN + kend + 3) & ~3) + 2 * BM * APITCH + BM * 4 * 2) * 4; }
-
 extern "C" int dsp_internal_launch_fir_mfma(const FirArgs* A, int64_t n_wf, int lds_bytes, hipStream_t stream) {
     if (n_wf <= 0 || A->n_kernels <= 0) return 0;
     const dim3 grid((unsigned)A->n_kernels, (unsigned)((n_wf + BM - 1) / BM));
@@ -553,5 +549,3 @@ extern "C" int dsp_internal_set_fir_mfma_lds(int lds_bytes) {
     }
     return 0;
 }
-
-extern "C" const char* dsp_internal_fir_mfma_kernel_name() { return "dsp_fir_mfma_kernel"; }

@@ -26,7 +26,8 @@
 // tap by tap, as dsp_fir_fixup_kernel does them.
 #include <hip/hip_runtime.h>
 
-#include "dsp_program.h"
+#include "dsp_kernels.h"
+#include "dsp_launch.h"
 #include "dsp_reduce_tail.h"
 #include "dsp_wave.h"
 
@@ -37,7 +38,7 @@
 namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-constexpr int STEP = 512;  // samples per step: 8 per lane
+using namespace dsp_fir_runs;  // STEP: samples per step, 8 per lane
 
 // One wavefront: the breakpoints of the kernel and their weights.  A breakpoint is a tap index t in [0, m] where kernel[t] differs from
 // kernel[t - 1] (zeros in front of the kernel and behind it).
@@ -237,6 +238,8 @@ __global__ void __launch_bounds__(256) dsp_fir_runs_kernel(FirRunsArgs A_, int64
                 }
                 // ---- the last mp sums move to the front
                 constexpr int NK = (DSP_FIR_RUNS_MAX_TAPS + DSP_FIR_RUNS_MAX_TAPS / 8) / 64;
+                static_assert((DSP_FIR_RUNS_MAX_TAPS * 9 / 8) % 64 == 0, "NK rounds of 64 lanes cover the longest padded window exactly");
+                static_assert(DSP_FIR_RUNS_MAX + 2 <= 64, "the table is held a breakpoint per lane");
                 double keep[NK];
 #pragma unroll
                 for (int k = 0; k < NK; ++k)
@@ -297,16 +300,9 @@ __global__ void __launch_bounds__(256) dsp_fir_runs_kernel(FirRunsArgs A_, int64
 
 }  // namespace
 
-extern "C" int dsp_internal_fir_runs_lds_bytes(int m) {
-    const int mp = (m + 63) & ~63;
-    return (4 * (mp + mp / 8 + STEP + STEP / 8) + 64) * (int)sizeof(double);  // (+ the round of the window's copy that reads past the last window)
-}
-
 extern "C" int dsp_internal_launch_fir_runs(const FirRunsArgs* A, FirRunsTable* table, int64_t n_wf, int blocks, int* err, hipStream_t stream) {
     if (n_wf <= 0 || A->p <= 0) return 0;
     hipLaunchKernelGGL(dsp_fir_runs_prep_kernel, dim3(1), dim3(64), 0, stream, A->taps, A->m, table);
-    hipLaunchKernelGGL(dsp_fir_runs_kernel, dim3((unsigned)blocks), dim3(256), (size_t)dsp_internal_fir_runs_lds_bytes(A->m), stream, *A, n_wf, err);
+    hipLaunchKernelGGL(dsp_fir_runs_kernel, dim3((unsigned)blocks), dim3(256), (size_t)dsp_fir_runs::lds_bytes(A->m), stream, *A, n_wf, err);
     return (int)hipGetLastError();
 }
-
-extern "C" const char* dsp_internal_fir_runs_kernel_name() { return "dsp_fir_runs_kernel"; }

@@ -12,6 +12,7 @@
 // done in one pass over the row.  Arithmetic of a fit: as op_linear_slope_fit (same typing, same div_by_count, same closing formulas).
 #include <hip/hip_runtime.h>
 
+#include "dsp_launch.h"
 #include "dsp_wave.h"
 
 namespace {

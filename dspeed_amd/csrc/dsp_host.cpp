@@ -26,56 +26,8 @@
 #include <string>
 #include <vector>
 
+#include "dsp_launch.h"
 #include "dsp_plan.h"
-
-extern "C" int dsp_internal_launch_vm_f32(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int* err, int blocks,
-                                          int threads, int lds_bytes, int with_fir, int team, hipStream_t stream);
-extern "C" int dsp_internal_launch_vm_f64(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int* err, int blocks,
-                                          int threads, int lds_bytes, int with_fir, hipStream_t stream);
-extern "C" int dsp_internal_set_vm_lds(int lds_bytes);
-extern "C" const char* dsp_internal_vm_kernel_name();
-extern "C" int dsp_internal_launch_stream_read(const void* src, int64_t bytes, uint32_t* sink, int blocks, hipStream_t stream);
-extern "C" int dsp_internal_launch_fit_rows(const FitArgs* A, int wf_dtype, int compute_dtype, hipStream_t stream);
-extern "C" int dsp_internal_launch_synth(void* wf, int out_dtype, int64_t n_wf, int wf_len, int64_t row_stride, float* baseline,
-                                         float* t_pick, uint64_t seed, int64_t first_row, float tau, float sigma, float pick_offset,
-                                         float bl_lo, float bl_hi, float amp_lo, float amp_hi, float rise_lo, float rise_hi, hipStream_t stream);
-
-extern "C" int dsp_internal_launch_energy(const EnergyArgs* A, int trap_opcode, int npf, int64_t n_wf, int* err, int blocks,
-                                          int threads, int lds_bytes, hipStream_t stream);
-extern "C" int dsp_internal_set_energy_lds(int trap_opcode, int npf, int lds_bytes);
-extern "C" const char* dsp_internal_energy_kernel_name();
-extern "C" int dsp_internal_launch_energy_rr(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype,
-                                             int64_t n_wf, int* err, int blocks, int threads, int lds_bytes, hipStream_t stream);
-extern "C" const char* dsp_internal_energy_rr_kernel_name();
-extern "C" int dsp_internal_launch_rows(const RowsArgs* A, int64_t n_wf, int* err, int lds_bytes, hipStream_t stream);
-extern "C" int dsp_internal_set_rows_lds(int lds_bytes);
-extern "C" const char* dsp_internal_rows_kernel_name();
-extern "C" int dsp_internal_launch_pz_rows(const PzArgs* A, int64_t n_wf, int* err, hipStream_t stream);
-extern "C" const char* dsp_internal_pz_rows_kernel_name();
-extern "C" int dsp_internal_launch_reduce(const ReduceArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
-extern "C" const char* dsp_internal_reduce_kernel_name();
-extern "C" int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);  // type: 0 float32, 1 float64, 2 int64 registers
-extern "C" int dsp_internal_set_scalar_lds(int lds_bytes);
-extern "C" const char* dsp_internal_scalar_kernel_name();
-extern "C" int dsp_internal_current_lds_bytes(int ma_len);
-extern "C" int dsp_internal_launch_fir_runs(const FirRunsArgs* A, FirRunsTable* table, int64_t n_wf, int blocks, int* err, hipStream_t stream);
-extern "C" int dsp_internal_launch_current(const CurrentArgs* A, int64_t n_wf, int blocks, int lds_bytes, hipStream_t stream);
-extern "C" int dsp_internal_set_current_lds(int lds_bytes);
-extern "C" const char* dsp_internal_current_kernel_name();
-extern "C" int dsp_internal_fir_mfma_lds_bytes(int kend);
-extern "C" int dsp_internal_launch_fir_mfma(const FirArgs* A, int64_t n_wf, int lds_bytes, hipStream_t stream);
-extern "C" int dsp_internal_launch_fir_f16(const FirArgs* A, const FirF16Taps* T, int64_t n_wf, int lds_bytes, hipStream_t stream);
-extern "C" int dsp_internal_fir_f16_tz(int kend);
-extern "C" size_t dsp_internal_fir_f16_taps_bytes(int kend);
-extern "C" int dsp_internal_fir_f16_lds_bytes();
-extern "C" int dsp_internal_set_fir_f16_lds(int lds_bytes);
-extern "C" const char* dsp_internal_fir_f16_kernel_name();
-extern "C" int dsp_internal_set_fir_mfma_lds(int lds_bytes);
-extern "C" const char* dsp_internal_fir_mfma_kernel_name();
-extern "C" int dsp_internal_fir_store_lds_bytes(int kend);
-extern "C" int dsp_internal_launch_fir_store(const FirArgs* A, int64_t n_wf, int lds_bytes, hipStream_t stream);
-extern "C" int dsp_internal_set_fir_store_lds(int lds_bytes);
-extern "C" const char* dsp_internal_fir_store_kernel_name();
 
 #define fail dsp_fail
 #define elem_size dsp_elem_size
@@ -394,7 +346,7 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     if (ch->fir_f16)  // device images of the float16 FIR's taps (rewritten by every launch: the taps are a binding)
         for (int k = 0; k < ch->fir.n_kernels; ++k) {
             void* buf = nullptr;
-            HIP_TRY(hipMalloc(&buf, dsp_internal_fir_f16_taps_bytes(ch->fir.kend)));
+            HIP_TRY(hipMalloc(&buf, dsp_fir_f16::taps_bytes(ch->fir.kend)));
             ch->f16.taps16[k] = buf;
         }
     HIP_TRY(hipGetDevice(&ch->device));
@@ -411,7 +363,7 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     const int block_lds = ch->lds_bytes_per_wave * ch->waves_per_block, classic_lds = ch->lds_bytes_per_wave * ch->classic_wpb;
     int rc = raise_lds(true, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
     if (!rc) rc = raise_lds(ch->fused_ok, classic_lds, 64 * 1024, "energy kernel, %d", [&](int n) { return dsp_internal_set_energy_lds(ch->fused_trap, ch->fused_npf, n); });
-    if (!rc) rc = raise_lds(ch->fir_f16, dsp_internal_fir_f16_lds_bytes(), 64 * 1024, "float16 FIR kernel", dsp_internal_set_fir_f16_lds);
+    if (!rc) rc = raise_lds(ch->fir_f16, dsp_fir_f16::lds_bytes(), 64 * 1024, "float16 FIR kernel", dsp_internal_set_fir_f16_lds);
     if (!rc) rc = raise_lds(ch->fir_ok, ch->fir_lds_bytes, 64 * 1024, "FIR kernel, %d", ch->fir.store ? dsp_internal_set_fir_store_lds : dsp_internal_set_fir_mfma_lds);
     if (!rc) rc = raise_lds(ch->scalar_ok, n_sregs * 64 * esz, 48 * 1024, "scalar kernel", dsp_internal_set_scalar_lds);
     if (!rc) rc = raise_lds(ch->cur_ok, ch->cur_lds_bytes, 64 * 1024, "current kernel, %d", dsp_internal_set_current_lds);
@@ -495,7 +447,7 @@ static int current_blocks(const dsp_chain* ch, int64_t n_wf) {
 // launch geometry of the run-length FIR (dsp_fir_runs.hip): persistent workgroups of four wavefronts, a row per wavefront and round; four
 // workgroups per CU where LDS allows (the kernel's registers leave room for five wavefronts per SIMD), every one the same number of rounds
 static int runs_blocks_cap(const dsp_chain* ch) {
-    int per_cu = LDS_BYTES_PER_CU / dsp_internal_fir_runs_lds_bytes(ch->runs.m);
+    int per_cu = LDS_BYTES_PER_CU / dsp_fir_runs::lds_bytes(ch->runs.m);
     if (per_cu > 4) per_cu = 4;
     return ch->num_cu * (per_cu < 1 ? 1 : per_cu);
 }
@@ -694,7 +646,7 @@ static int launch_fir(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
                                                             : (A.in_kind == 0 && A.sub_mode == 0))) ? 1 : 0;
         ch->fed_n_wf = -1;  // (a note is good for one execute)
     }
-    hipError_t e = (hipError_t)(ch->fir_f16 ? dsp_internal_launch_fir_f16(&A, &ch->f16, n_wf, dsp_internal_fir_f16_lds_bytes(), (hipStream_t)stream)
+    hipError_t e = (hipError_t)(ch->fir_f16 ? dsp_internal_launch_fir_f16(&A, &ch->f16, n_wf, dsp_fir_f16::lds_bytes(), (hipStream_t)stream)
                                 : A.store   ? dsp_internal_launch_fir_store(&A, n_wf, ch->fir_lds_bytes, (hipStream_t)stream)
                                             : dsp_internal_launch_fir_mfma(&A, n_wf, ch->fir_lds_bytes, (hipStream_t)stream));
     return launched(ch, stream, e, "FIR kernel launch");
@@ -859,7 +811,7 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             break;
         case DSP_ROUTE_PZ_ROWS:
         case DSP_ROUTE_REDUCE: lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4); break;
-        case DSP_ROUTE_FIR_RUNS: lds = dsp_internal_fir_runs_lds_bytes(ch->runs.m) / 4, wpb = 4, b = runs_blocks(ch, n_wf); break;
+        case DSP_ROUTE_FIR_RUNS: lds = dsp_fir_runs::lds_bytes(ch->runs.m) / 4, wpb = 4, b = runs_blocks(ch, n_wf); break;
         case DSP_ROUTE_CURRENT: lds = ch->cur_lds_bytes, wpb = 1, b = current_blocks(ch, n_wf); break;
         case DSP_ROUTE_FIR_F16:
         case DSP_ROUTE_FIR_STORE:

@@ -1,0 +1,86 @@
+// dsp_kernels.h -- what the host and the planner have to know about the kernels without seeing them: the tile constants their LDS
+// footprint follows from, that footprint as constexpr functions, and the kernels' names by route.  One namespace per kernel; the kernel
+// file takes its constants from here (using namespace), the planner and the host call the functions, and the CPU test programs, which
+// cannot link a .hip file, see the same arithmetic.  No HIP: plain C++17.  Internal header; the public contract is include/dspeed_hip.h.
+#pragma once
+#include <stddef.h>
+
+// The kernels a chain can run on, in their order of precedence: a program that has the shape of several (the *_ok flags) runs on the first
+// whose switch is on.  dsp_plan_route is the one place that holds this order for everything that reports a plan (kernel name, note,
+// geometry); dsp_chain_execute walks the same list with the alignment of the pointers it is handed and may fall through to a later entry.
+enum dsp_route {
+    DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
+    DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
+};
+// a route's kernel (what rocprofv3 --kernel-trace lists)
+inline constexpr const char* dsp_route_kernel_names[] = {
+    "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
+    "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
+static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
+
+namespace dsp_current {  // dsp_current.hip
+constexpr int CB = 16;   // samples per block (= per checkpoint)
+constexpr int lds_bytes(int ma_len) { return (ma_len / CB + 1) * CB * 64 * 4; }
+}  // namespace dsp_current
+
+namespace dsp_fir_mfma {  // dsp_fir_mfma.hip: the amax kernel and the kept-output ("store") kernel
+constexpr int BM = 64, BN = 320, APITCH = 36;
+constexpr int TB = BN + 4;
+constexpr int lds_bytes(int kend) { return (((BN + kend + 3) & ~3) + 2 * BM * APITCH + BM * 4 * 2) * 4; }
+constexpr int store_lds_bytes(int kend) { return (((TB + kend + 3) & ~3) + 2 * BM * APITCH) * 4; }
+}  // namespace dsp_fir_mfma
+
+// A/B builds of the float16 FIR: build.py hands its defines to every unit, so the host sizes what the kernel was built for
+#ifndef F16_BK
+#define F16_BK 64
+#endif
+#ifndef F16_BM
+#define F16_BM 64
+#endif
+namespace dsp_fir_f16 {  // dsp_fir_f16.hip
+constexpr int BM = F16_BM, BK = F16_BK;  // BM 64: 8 wavefronts (2 x 4); BM 32: 4 wavefronts, two workgroups per CU
+// LDS reads are ds_read_b128: four fixed groups of 16 lanes per instruction, 64 banks -- a group is conflict-free when its 16 addresses fall
+// into 16 different 16-byte slots of the 256-byte bank line (MI355X_MICROARCH.md, LDS).
+constexpr int APITCH = BK + 16;  // halfs per A row: 10 (BK 64) / 18 (BK 128) slots, = 2 modulo 16: lane (row j, k-block h) sits in slot 10 j + h, no two alike in a group
+constexpr int TB = 336;          // zero margin below tap 0: window index TB + k - column - e - shift is never negative
+constexpr int TWIN = TB + BK;    // taps a stage's fragments can reach
+// a tap copy in LDS: a multiple of 256 bytes, so that a copy's slot is its own offset only; copy r starts tap_slot[e][r] slots in -- for
+// every alignment e of the window a table that puts the 16 lanes of every group (eight columns x two k-blocks, five copies apart at most
+// identical addresses, which broadcast) into 16 different slots (found by search, tools/fir_f16_banks.py; the plain pitch had 51 % of the
+// LDS-array cycles as conflicts)
+constexpr int TPITCH = ((TWIN + 8 + 15 * 8 + 127) / 128) * 128;
+// halfs of the tap image of one kernel: 16 copies of TZ = the longest K window rounded up to a stage + the window the last stage reaches +
+// the margin the shifted copies reach into, then the inverse scale (one float, kept 16-byte aligned)
+constexpr int tz(int kend) { return ((kend + 8 + BK - 1) / BK) * BK + TWIN + 16; }
+constexpr size_t taps_bytes(int kend) { return (size_t)16 * tz(kend) * 2 + 16; }
+constexpr int lds_bytes() { return (2 * 2 * BM * APITCH + 2 * 16 * TPITCH) * 2 + (BM * 4 * 2 + BM) * 4; }
+}  // namespace dsp_fir_f16
+
+namespace dsp_fir_runs {    // dsp_fir_runs.hip
+constexpr int STEP = 512;  // samples per step: 8 per lane
+constexpr int lds_bytes(int m) {
+    const int mp = (m + 63) & ~63;
+    return (4 * (mp + mp / 8 + STEP + STEP / 8) + 64) * (int)sizeof(double);  // (+ the round of the window's copy that reads past the last window)
+}
+}  // namespace dsp_fir_runs
+
+namespace dsp_rows {    // dsp_rows.hip
+constexpr int RB = 8;  // samples per block (= per barrier)
+constexpr int ring_entries(int maxlag) { return ((maxlag + RB + RB - 1) / RB) * RB; }  // R > largest lag + 7, a whole number of blocks
+constexpr int lds_bytes(int R) { return (R + RB) * 64 * 4; }                           // the history ring and the block in flight, 64 lanes
+}  // namespace dsp_rows
+
+// The register-resident energy kernel's LDS region of one wavefront (dsp_energy.hip), in float32 elements, for C samples per lane: `guard`
+// zeros below the image (lagged reads before sample 0; an odd lag's pairs start one element lower: covered), the image of 64 C elements at
+// slot_off (16-byte aligned), `tail` elements above it, a side array of side_pitch (odd) elements per lane for the (C - 2) / 8 + 1 group
+// sums, a capture buffer of 2 x 16.
+namespace dsp_energy_rr {
+struct Layout {
+    int guard, slot_off, tail, side_pitch, elems;
+};
+constexpr Layout layout(int C) {
+    const int guard = 2 * C + 8, slot_off = (guard + 3) / 4 * 4, tail = 16, ng1 = (C - 2) / 8 + 1;
+    const int side_pitch = ng1 <= 9 ? 9 : (ng1 | 1);  // (9 for up to 4096 samples, 17 for 8192)
+    return {guard, slot_off, tail, side_pitch, (slot_off + 64 * C + tail + 64 * side_pitch + 2 * 16 + 3) / 4 * 4};
+}
+}  // namespace dsp_energy_rr

@@ -1,0 +1,51 @@
+// dsp_launch.h -- the launchers the .hip files define for dsp_host.cpp (and for each other), each declared here and nowhere else.  Every
+// file that defines one includes this header, so a definition that disagrees with what its caller sees does not compile (with C linkage it
+// would link).  They return a hipError_t as int; dsp_internal_set_*_lds raises a kernel's dynamic-LDS limit.  Internal header.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "dsp_program.h"
+
+extern "C" {
+// dsp_vm.hip
+int dsp_internal_launch_vm_f32(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int* err, int blocks, int threads, int lds_bytes,
+                               int with_fir, int team, hipStream_t stream);
+int dsp_internal_launch_vm_f64(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int* err, int blocks, int threads, int lds_bytes,
+                               int with_fir, hipStream_t stream);
+int dsp_internal_set_vm_lds(int lds_bytes);
+int dsp_internal_launch_stream_read(const void* src, int64_t bytes, uint32_t* sink, int blocks, hipStream_t stream);
+int dsp_internal_launch_synth(void* wf, int out_dtype, int64_t n_wf, int wf_len, int64_t row_stride, float* baseline, float* t_pick, uint64_t seed,
+                              int64_t first_row, float tau, float sigma, float pick_offset, float bl_lo, float bl_hi, float amp_lo, float amp_hi,
+                              float rise_lo, float rise_hi, hipStream_t stream);
+// dsp_fit.hip
+int dsp_internal_launch_fit_rows(const FitArgs* A, int wf_dtype, int compute_dtype, hipStream_t stream);
+// dsp_energy.hip (npf: 16-byte loads per lane that cover a waveform; S: replay sub-chains, plan[S - 1]) and its second unit dsp_energy_h.hip
+int dsp_internal_launch_energy(const EnergyArgs* A, int trap_opcode, int npf, int64_t n_wf, int* err, int blocks, int threads, int lds_bytes,
+                               hipStream_t stream);
+int dsp_internal_set_energy_lds(int trap_opcode, int npf, int lds_bytes);
+int dsp_internal_launch_energy_rr(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype, int64_t n_wf, int* err,
+                                  int blocks, int threads, int lds_bytes, hipStream_t stream);
+int dsp_internal_launch_energy_rr_h(const EnergyArgs* A, const EnergyPlan* PL, int trap_opcode, int npf, int S, int wf_dtype, int64_t n_wf, int* err,
+                                    int blocks, int threads, int lds_bytes, hipStream_t stream);
+// dsp_rows.hip, dsp_pz.hip, dsp_reduce.hip
+int dsp_internal_launch_rows(const RowsArgs* A, int64_t n_wf, int* err, int lds_bytes, hipStream_t stream);
+int dsp_internal_set_rows_lds(int lds_bytes);
+int dsp_internal_launch_pz_rows(const PzArgs* A, int64_t n_wf, int* err, hipStream_t stream);
+int dsp_internal_launch_reduce(const ReduceArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+// dsp_scalar.hip (type: 0 float32, 1 float64, 2 int64 registers)
+int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);
+int dsp_internal_set_scalar_lds(int lds_bytes);
+// dsp_current.hip, dsp_fir_runs.hip
+int dsp_internal_launch_current(const CurrentArgs* A, int64_t n_wf, int blocks, int lds_bytes, hipStream_t stream);
+int dsp_internal_set_current_lds(int lds_bytes);
+int dsp_internal_launch_fir_runs(const FirRunsArgs* A, FirRunsTable* table, int64_t n_wf, int blocks, int* err, hipStream_t stream);
+// dsp_fir_mfma.hip (dsp_internal_fir_fixup: the rows-with-a-NaN-or-an-infinity pass alone, also behind the float16 kept-output form)
+int dsp_internal_launch_fir_mfma(const FirArgs* A, int64_t n_wf, int lds_bytes, hipStream_t stream);
+int dsp_internal_set_fir_mfma_lds(int lds_bytes);
+int dsp_internal_launch_fir_store(const FirArgs* A, int64_t n_wf, int lds_bytes, hipStream_t stream);
+int dsp_internal_set_fir_store_lds(int lds_bytes);
+int dsp_internal_fir_fixup(const FirArgs* A, int64_t n_wf, hipStream_t stream);
+// dsp_fir_f16.hip
+int dsp_internal_launch_fir_f16(const FirArgs* A, const FirF16Taps* T, int64_t n_wf, int lds_bytes, hipStream_t stream);
+int dsp_internal_set_fir_f16_lds(int lds_bytes);
+}

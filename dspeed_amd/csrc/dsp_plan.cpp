@@ -424,7 +424,7 @@ static bool match_current_shape(const PlanCtx& c) {
     }
     A.scratch_per_wave = (int64_t)(A.n_c + 2 * (A.n_up / 16)) * 64;
     ch->cio_wf = ld.io;
-    ch->cur_lds_bytes = dsp_internal_current_lds_bytes(A.ma_len);
+    ch->cur_lds_bytes = dsp_current::lds_bytes(A.ma_len);
     return true;
 }
 
@@ -497,7 +497,7 @@ static bool match_fir_shape(const PlanCtx& c) {
     A.scan_before = ld.ip[0];
     A.scan_after = ld.ip[1];
     ch->fio_wf = ld.io;
-    ch->fir_lds_bytes = dsp_internal_fir_mfma_lds_bytes(kend);
+    ch->fir_lds_bytes = dsp_fir_mfma::lds_bytes(kend);
     return ch->fir_lds_bytes <= 80 * 1024;
 }
 
@@ -560,7 +560,7 @@ static bool match_fir_store_shape(const PlanCtx& c) {
     ch->fio_wf = ld.io;
     ch->fio_taps[0] = o.io;
     ch->fio_out[0] = st.io;
-    ch->fir_lds_bytes = dsp_internal_fir_store_lds_bytes(A.kend);
+    ch->fir_lds_bytes = dsp_fir_mfma::store_lds_bytes(A.kend);
     return ch->fir_lds_bytes <= 80 * 1024;
 }
 
@@ -722,16 +722,16 @@ static bool match_rows_shape(const PlanCtx& c) {
     int maxlag = 0;
     for (int k = 0; k < 3; ++k) {
         A.lag[k] = dtr.ic[k];
-        if (A.lag[k] < 8) {
+        if (A.lag[k] < dsp_rows::RB) {
             note(ch, "a trapezoid with a rise or flat top of %d samples: the lane-per-waveform rows kernel takes 8 and more", A.lag[k]);
             return false;
         }
         if (A.lag[k] > maxlag) maxlag = A.lag[k];
     }
-    const int R = ((maxlag + 8 + 7) / 8) * 8;  // R > largest lag + 7, a whole number of blocks
-    if ((R + 8) * 256 > LDS_BYTES_PER_CU / 2) return false;
+    const int R = dsp_rows::ring_entries(maxlag);
+    if (dsp_rows::lds_bytes(R) > LDS_BYTES_PER_CU / 2) return false;
     A.ring_entries = R;
-    ch->rows_lds_bytes = (R + 8) * 256;
+    ch->rows_lds_bytes = dsp_rows::lds_bytes(R);
     A.trap_all_nan = dtr.ic[9];
     A.rr = dtr.fc[0];
     A.ll = dtr.fc[1];
@@ -1496,14 +1496,10 @@ static void plan_energy_rr(PlanCtx& c, const DevOp& dtp) {
     I.C = Ci;
     I.pitch = Ci;
     I.invC = 1.0f / (float)Ci;
-    int guard = 2 * Ci + 8;  // zeros below the image: lagged reads before sample 0 (an odd lag's pairs start one element lower: covered)
-    guard = ((guard + 3) / 4) * 4;  // (the image stays 16-byte aligned)
-    I.slot_off = guard;
-    const int ng1 = (Ci - 2) / 8 + 1, auxp = ng1 <= 9 ? 9 : (ng1 | 1);
-    int elems = guard + 64 * Ci + 16 + 64 * auxp + 32;  // image, tail, per-lane side array (auxp per lane), capture buffer (2 x 16)
-    elems = ((elems + 3) / 4) * 4;
-    I.lds_elems_per_wave = elems;
-    ch->rr_lds_bytes = elems * 4;
+    const dsp_energy_rr::Layout L = dsp_energy_rr::layout(Ci);  // (the kernel addresses the region by the same)
+    I.slot_off = L.slot_off;
+    I.lds_elems_per_wave = L.elems;
+    ch->rr_lds_bytes = L.elems * 4;
     for (int k = 0; k < 3; ++k) {
         I.q[k] = dtp.ic[k];  // the lags themselves
         I.rho[k] = 0;
@@ -1613,7 +1609,7 @@ static void choose_fir_f16(PlanCtx& c) {
     if (!(f32 && f32[0] == '1') && (w.row_stride * es) % 16 == 0 && (w.offset * es) % 16 == 0 &&
         ((n_slice & 7) == 0 || w.offset + ((n_slice + 7) & ~7) <= w.row_stride)) {
         ch->fir_f16 = true;
-        ch->f16.tz = dsp_internal_fir_f16_tz(ch->fir.kend);
+        ch->f16.tz = dsp_fir_f16::tz(ch->fir.kend);
     }
 }
 
@@ -1907,21 +1903,7 @@ dsp_route dsp_plan_route(const ChainPlan* ch) {
 }
 
 const char* dsp_plan_route_kernel_name(dsp_route route) {
-    switch (route) {
-        case DSP_ROUTE_SCALAR: return dsp_internal_scalar_kernel_name();
-        case DSP_ROUTE_PZ_ROWS: return dsp_internal_pz_rows_kernel_name();
-        case DSP_ROUTE_REDUCE: return dsp_internal_reduce_kernel_name();
-        case DSP_ROUTE_FIR_RUNS: return dsp_internal_fir_runs_kernel_name();
-        case DSP_ROUTE_CURRENT: return dsp_internal_current_kernel_name();
-        case DSP_ROUTE_FIR_F16: return dsp_internal_fir_f16_kernel_name();
-        case DSP_ROUTE_FIR_STORE: return dsp_internal_fir_store_kernel_name();
-        case DSP_ROUTE_FIR_MFMA: return dsp_internal_fir_mfma_kernel_name();
-        case DSP_ROUTE_ROWS: return dsp_internal_rows_kernel_name();
-        case DSP_ROUTE_ENERGY_RR: return dsp_internal_energy_rr_kernel_name();
-        case DSP_ROUTE_ENERGY: return dsp_internal_energy_kernel_name();
-        case DSP_ROUTE_VM: break;
-    }
-    return dsp_internal_vm_kernel_name();
+    return dsp_route_kernel_names[route >= DSP_ROUTE_SCALAR && route <= DSP_ROUTE_VM ? route : DSP_ROUTE_VM];
 }
 
 const char* dsp_plan_kernel_name(const ChainPlan* ch) { return dsp_plan_route_kernel_name(dsp_plan_route(ch)); }

@@ -4,78 +4,21 @@
 // reference evaluates once per call, packs the waveform slots into LDS by lifetime, matches the program against the specialised kernels'
 // shapes and picks the launch geometry.  It makes no HIP call and includes no HIP header: the same translation unit is compiled for the
 // CPU with -fsanitize=address,undefined and fuzzed there (tests/test_planner_fuzz.py, tests/planner_fuzz.cpp).  dsp_host.cpp puts the
-// device resources on top (struct dsp_chain : ChainPlan).  Internal header; the public contract is include/dspeed_hip.h.
+// device resources on top (struct dsp_chain : ChainPlan).  The argument blocks it fills are dsp_program.h's, the kernels' LDS geometry and
+// the routes dsp_kernels.h's: nothing of the kernels' side is declared here.  Internal header; the public contract is include/dspeed_hip.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include <string>
 
+#include "dsp_kernels.h"
 #include "dsp_program.h"
 
 constexpr int LDS_BYTES_PER_CU = 160 * 1024;
 
-// mirror of the struct in dsp_energy.hip
-struct EnergyArgs {
-    const void* wf;
-    int64_t wf_stride;
-    int32_t wf_offset;
-    int32_t len;
-    const float* bl;
-    int64_t bl_stride;
-    float bl_const;
-    int32_t has_bl;
-    const float* tp;
-    int64_t tp_stride;
-    float tp_const;
-    int32_t mode;
-    float* out;
-    int64_t out_stride;
-    double c;
-    double rr, ll;
-    int32_t tau_nan;
-    int32_t all_nan;
-    int32_t C, pitch;
-    float invC;
-    int32_t q[3], rho[3];
-    int32_t lds_elems_per_wave;
-    int32_t slot_off;
-    const float* tau;
-    int64_t tau_stride;
-    int32_t ablate;
-};
-
-struct EnergyPlan {  // [lag][replay sub-chain]
-    int32_t shift[3][4];
-    int32_t cs[3][4];
-    int32_t local[3][4];
-    int32_t grp[3][4];
-    int32_t side[3][4];
-    int32_t pn[3][4];
-};
 // (dsp_plan.cpp; exported for the CPU tests)
 extern "C" void dsp_internal_plan_energy_carries(int Ci, int S, const int32_t* lags, EnergyPlan* plan);
-
-// geometry of the kernels, defined beside them (host arithmetic on their tile constants: dsp_current.hip, dsp_fir_mfma.hip, dsp_fir_f16.hip)
-extern "C" int dsp_internal_current_lds_bytes(int ma_len);
-extern "C" int dsp_internal_fir_mfma_lds_bytes(int kend);
-extern "C" int dsp_internal_fir_store_lds_bytes(int kend);
-extern "C" int dsp_internal_fir_f16_tz(int kend);
-extern "C" size_t dsp_internal_fir_f16_taps_bytes(int kend);
-extern "C" int dsp_internal_fir_f16_lds_bytes();
-extern "C" const char* dsp_internal_vm_kernel_name();
-extern "C" const char* dsp_internal_energy_kernel_name();
-extern "C" const char* dsp_internal_energy_rr_kernel_name();
-extern "C" const char* dsp_internal_rows_kernel_name();
-extern "C" const char* dsp_internal_pz_rows_kernel_name();
-extern "C" const char* dsp_internal_reduce_kernel_name();
-extern "C" const char* dsp_internal_scalar_kernel_name();
-extern "C" const char* dsp_internal_current_kernel_name();
-extern "C" const char* dsp_internal_fir_f16_kernel_name();
-extern "C" const char* dsp_internal_fir_mfma_kernel_name();
-extern "C" const char* dsp_internal_fir_store_kernel_name();
-extern "C" const char* dsp_internal_fir_runs_kernel_name();
-extern "C" int dsp_internal_fir_runs_lds_bytes(int m);
 
 // thread-local text behind dsp_last_error(); dsp_fail formats it and hands `code` back
 int dsp_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -152,16 +95,9 @@ struct ChainPlan {
 // 0 or the DSP_ERR_* / DSP_E_* code (text in dsp_plan_last_error()); `ch` must be a freshly constructed plan
 int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_io, const int32_t* slot_len, int n_slots,
                    int n_sregs, int compute_dtype);
-// The kernels a chain can run on, in their order of precedence: a program that has the shape of several (the *_ok flags) runs on the first
-// whose switch is on.  dsp_plan_route is the one place that holds this order for everything that reports a plan (kernel name, note,
-// geometry); dsp_chain_execute walks the same list with the alignment of the pointers it is handed and may fall through to a later entry.
-enum dsp_route {
-    DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
-    DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
-};
 // the route a planned chain takes on rows that keep 16-byte alignment (fused_on and variant included; null: the interpreter)
 dsp_route dsp_plan_route(const ChainPlan* ch);
-// its kernel (what rocprofv3 --kernel-trace lists)
+// its kernel: dsp_route_kernel_names (dsp_kernels.h)
 const char* dsp_plan_route_kernel_name(dsp_route route);
 const char* dsp_plan_kernel_name(const ChainPlan* ch);
 // does a specialised kernel's shape stand behind the chain (its note is then not shown)?  The route, but for one case: the classic energy

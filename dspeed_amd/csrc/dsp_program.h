@@ -1,5 +1,6 @@
-// dsp_program.h -- device-side program representation shared by the host translator (dsp_host.cpp)
-// and the waveform VM kernel (dsp_vm.hip).  Internal: the public contract is include/dspeed_hip.h.
+// dsp_program.h -- everything that crosses from the planner and the host (dsp_plan.cpp, dsp_host.cpp) to a kernel by value: the device-side
+// program of the waveform VM (dsp_vm.hip) and the argument block of every specialised kernel, each defined here and nowhere else.  No HIP:
+// the planner fills these on the CPU.  Internal: the public contract is include/dspeed_hip.h.
 #pragma once
 #include <stdint.h>
 
@@ -88,6 +89,51 @@ struct FitArgs {
     void* out;  // [n_fits][4][n_wf] of the compute type: mean, stdev, slope, intercept
 };
 
+// arguments of the energy-chain kernels (dsp_energy.hip), filled by the planner when a program has that shape:
+//   LOAD [-> BL_SUBTRACT] -> POLE_ZERO -> TRAP_PICKOFF -> STORE_SCALAR
+struct EnergyArgs {
+    const void* wf;        // waveform rows
+    int64_t wf_stride;     // elements between rows
+    int32_t wf_offset;     // first sample used
+    int32_t len;           // samples per waveform
+    const float* bl;       // per-waveform baseline column, or nullptr
+    int64_t bl_stride;
+    float bl_const;
+    int32_t has_bl;        // 0: the chain has no bl_subtract (bl_const is then 0: x - 0 == x exactly)
+    const float* tp;       // per-waveform pick-off time column, or nullptr
+    int64_t tp_stride;
+    float tp_const;
+    int32_t mode;          // pick-off mode char
+    float* out;
+    int64_t out_stride;
+    double c;              // exp(-1/tau)
+    double rr, ll;         // rise, fall as float64
+    int32_t tau_nan;
+    int32_t all_nan;       // trap_filter with rise == 0
+    int32_t C, pitch;      // samples per lane, C + 1
+    float invC;
+    int32_t q[3], rho[3];  // lag = q*C + rho
+    int32_t lds_elems_per_wave;
+    int32_t slot_off;      // element offset of the slot inside the wave's region (2*pitch guard below it)
+    const float* tau;      // or null: the pole-zero time constant per event (a column) instead of c / tau_nan -- the TAU builds of the register-resident kernel
+    int64_t tau_stride;
+    int32_t ablate;        // diagnostic build only (-DDSPEED_HIP_DIAG, libdspeed_hip_diag.so): bit 0/1/2 = skip pass 1/2/3 (results are then
+                           // wrong), bit 3 = per-phase cycle stamps.  The product library ignores the field: ABLATE in dsp_energy.hip is a constant 0.
+};
+
+// Carry plan of the register-resident energy kernel's pad-free layout (C = len/64 + 2 samples per lane, sample i at LDS element i): for lag
+// k and replay sub-chain s the speculative carry needs the float32 prefix sum of the first r samples of the chunk of the lane `shift` below.
+// The prefix is the side array's group-end sum in front of the 8-sample group that holds sample r - 1, plus the first pn samples of that
+// group.  Row-invariant, built by the planner (dsp_internal_plan_energy_carries in dsp_plan.cpp, which the CPU can test) in the form the
+// kernel uses as it stands.
+struct EnergyPlan {       // [lag][replay sub-chain]
+    int32_t shift[3][4];  // lane distance
+    int32_t cs[3][4];     // sub-chain that holds the capture point, and ...
+    int32_t local[3][4];  // ... the samples of it in front of the point (the plan as the planner's checks read it; the kernel uses the form below)
+    int32_t grp[3][4];    // element offset, from the start of the lane's chunk, of the group's four pairs (8 * group; group NG: the two-sample tail)
+    int32_t side[3][4];   // element of the lane's side array that holds the sum of the groups in front, -1: none (group 0), read a word that holds 0.0f
+    int32_t pn[3][4];     // samples of the group in front of the capture point, 0 .. 8
+};
 
 // arguments of the lane-per-waveform chain kernel (dsp_rows.hip), filled by dsp_chain_execute when a program has that shape
 struct RowsArgs {

@@ -11,7 +11,7 @@
 // within the filter bar of the oracle like every scan formulation of this recurrence here.
 #include <hip/hip_runtime.h>
 
-#include "dsp_program.h"
+#include "dsp_launch.h"
 #include "dsp_reduce_tail.h"
 #include "dsp_wave.h"
 
@@ -237,5 +237,3 @@ extern "C" int dsp_internal_launch_pz_rows(const PzArgs* A, int64_t n_wf, int* e
     }
     return (int)hipGetLastError();
 }
-
-extern "C" const char* dsp_internal_pz_rows_kernel_name() { return "dsp_pz_rows_kernel"; }

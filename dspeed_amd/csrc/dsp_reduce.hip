@@ -9,7 +9,7 @@
 // (value, index) of its first minimum and maximum; one exchange across the wavefront at the end.  HBM-bound: the row is read once.
 #include <hip/hip_runtime.h>
 
-#include "dsp_program.h"
+#include "dsp_launch.h"
 #include "dsp_reduce_tail.h"
 #include "dsp_wave.h"
 
@@ -107,5 +107,3 @@ extern "C" int dsp_internal_launch_reduce(const ReduceArgs* A, int64_t n_wf, int
         launch_reduce<uint16_t>(A, n_wf, vec, err, stream);
     return (int)hipGetLastError();
 }
-
-extern "C" const char* dsp_internal_reduce_kernel_name() { return "dsp_reduce_kernel"; }

@@ -31,7 +31,8 @@
 
 #include <type_traits>
 
-#include "dsp_program.h"
+#include "dsp_kernels.h"
+#include "dsp_launch.h"
 #include "dsp_wave.h"
 
 #define ROWS_LDS __attribute__((address_space(3)))
@@ -40,7 +41,7 @@
 
 namespace {
 
-constexpr int RB = 8;  // samples per block (= per barrier)
+using namespace dsp_rows;  // RB: samples per block (= per barrier)
 
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -456,5 +457,3 @@ extern "C" int dsp_internal_set_rows_lds(int lds_bytes) {
     if (rc) return rc;
     return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&dsp_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
 }
-
-extern "C" const char* dsp_internal_rows_kernel_name() { return "dsp_rows_kernel"; }

@@ -10,7 +10,7 @@
 // processing_chain.py:832-947, or a coordinate conversion, unit_conversion.py:16-79).  Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
-#include "dsp_program.h"
+#include "dsp_launch.h"
 #include "dsp_wave.h"
 
 #define SC_PROG __attribute__((address_space(4)))
@@ -213,5 +213,3 @@ extern "C" int dsp_internal_set_scalar_lds(int lds_bytes) {
     if (rc) return rc;
     return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&dsp_scalar_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
 }
-
-extern "C" const char* dsp_internal_scalar_kernel_name() { return "dsp_scalar_kernel"; }

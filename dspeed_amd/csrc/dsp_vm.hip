@@ -19,7 +19,7 @@
 
 #include <type_traits>
 
-#include "dsp_program.h"
+#include "dsp_launch.h"
 #include "dsp_wave.h"
 
 // pointers into device memory (the program, I/O buffers) carry their address space in the type, see Ctx
@@ -2600,8 +2600,6 @@ extern "C" int dsp_internal_set_vm_lds(int lds_bytes) {
     }
     return 0;
 }
-
-extern "C" const char* dsp_internal_vm_kernel_name() { return "dsp_vm_kernel<float>"; }
 
 extern "C" int dsp_internal_launch_synth(void* wf, int out_dtype, int64_t n_wf, int wf_len, int64_t row_stride, float* baseline,
                                          float* t_pick, uint64_t seed, int64_t first_row, float tau, float sigma, float pick_offset,

@@ -15,19 +15,6 @@
 
 #include "../dspeed_amd/csrc/dsp_plan.h"
 
-// the kernels' geometry functions live beside the kernels; the planner needs them to link, this program never plans their chains
-extern "C" int dsp_internal_current_lds_bytes(int) { return 0; }
-extern "C" int dsp_internal_fir_mfma_lds_bytes(int) { return 0; }
-extern "C" int dsp_internal_fir_store_lds_bytes(int) { return 0; }
-extern "C" int dsp_internal_fir_f16_tz(int) { return 0; }
-extern "C" size_t dsp_internal_fir_f16_taps_bytes(int) { return 0; }
-extern "C" int dsp_internal_fir_f16_lds_bytes() { return 0; }
-extern "C" int dsp_internal_fir_runs_lds_bytes(int) { return 0; }
-#define NAME(fn) extern "C" const char* fn() { return #fn; }
-NAME(dsp_internal_vm_kernel_name) NAME(dsp_internal_energy_kernel_name) NAME(dsp_internal_energy_rr_kernel_name) NAME(dsp_internal_rows_kernel_name)
-NAME(dsp_internal_pz_rows_kernel_name) NAME(dsp_internal_reduce_kernel_name) NAME(dsp_internal_scalar_kernel_name) NAME(dsp_internal_current_kernel_name)
-NAME(dsp_internal_fir_f16_kernel_name) NAME(dsp_internal_fir_mfma_kernel_name) NAME(dsp_internal_fir_store_kernel_name) NAME(dsp_internal_fir_runs_kernel_name)
-
 static long checked = 0;
 
 static bool check(int C, int S, const int32_t lags[3]) {

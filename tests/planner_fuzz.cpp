@@ -27,28 +27,6 @@
 
 #include "../dspeed_amd/csrc/dsp_plan.h"
 
-// ---- the kernels' side of the planner's interface: tile geometry and names (the library links the .hip files' own; these follow them)
-extern "C" int dsp_internal_current_lds_bytes(int ma_len) { return (ma_len / 16 + 1) * 16 * 64 * 4; }
-extern "C" int dsp_internal_fir_mfma_lds_bytes(int kend) { return (((320 + kend + 3) & ~3) + 2 * 64 * 36 + 64 * 4 * 2) * 4; }
-extern "C" int dsp_internal_fir_store_lds_bytes(int kend) { return (((320 + kend + 3) & ~3) + 2 * 64 * 36) * 4; }
-extern "C" int dsp_internal_fir_f16_tz(int kend) { return ((kend + 8 + 63) / 64) * 64 + 400 + 16; }
-extern "C" size_t dsp_internal_fir_f16_taps_bytes(int kend) { return (size_t)16 * dsp_internal_fir_f16_tz(kend) * 2 + 16; }
-extern "C" int dsp_internal_fir_f16_lds_bytes() { return 84 * 1024; }
-#define NAME(fn, text) extern "C" const char* fn() { return text; }
-NAME(dsp_internal_vm_kernel_name, "dsp_vm_kernel<float>")
-NAME(dsp_internal_energy_kernel_name, "dsp_energy_kernel")
-NAME(dsp_internal_energy_rr_kernel_name, "dsp_energy_rr_kernel")
-NAME(dsp_internal_rows_kernel_name, "dsp_rows_kernel")
-NAME(dsp_internal_pz_rows_kernel_name, "dsp_pz_rows_kernel")
-NAME(dsp_internal_reduce_kernel_name, "dsp_reduce_kernel")
-NAME(dsp_internal_scalar_kernel_name, "dsp_scalar_kernel")
-NAME(dsp_internal_current_kernel_name, "dsp_current_kernel")
-NAME(dsp_internal_fir_f16_kernel_name, "dsp_fir_f16_kernel")
-NAME(dsp_internal_fir_mfma_kernel_name, "dsp_fir_mfma_kernel")
-NAME(dsp_internal_fir_store_kernel_name, "dsp_fir_store_kernel")
-NAME(dsp_internal_fir_runs_kernel_name, "dsp_fir_runs_kernel")
-extern "C" int dsp_internal_fir_runs_lds_bytes(int m) { return (4 * ((((m + 63) & ~63) + 512) * 9 / 8) + 64) * 8; }
-
 namespace {
 
 std::mt19937_64 rng;

@@ -110,3 +110,40 @@ def test_abort_trace_uninstall_restores_the_previous_disposition():
     )
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60)
     assert r.returncode == -signal.SIGABRT and "native call stack" not in r.stderr
+
+
+def _internal_interface():
+    """every dsp_internal_* prototype (ends in ';') and definition (opens a body) under dspeed_amd/csrc and tests/*.cpp, and the
+    definitions of the energy kernels' argument blocks: {name: [files]} each"""
+    import glob
+
+    files = sorted(glob.glob(os.path.join(ROOT, "dspeed_amd", "csrc", "*")) + glob.glob(os.path.join(ROOT, "tests", "*.cpp")))
+    files = [f for f in files if f.endswith((".h", ".hip", ".cpp"))]
+    # a return type in front of the name tells a prototype or definition from a call ("return f(..);", "x = f(..);", "(cast)f(..)")
+    func = re.compile(r"(?<![\w)=?:(,])\s*\b(?!return\b)[A-Za-z_]\w*[\s*]+(dsp_internal_\w+)\s*\(([^;{}()]|\([^()]*\))*\)\s*(;|\{)")
+    declared, defined, structs = {}, {}, {}
+    for path in files:
+        text = open(path).read()
+        text = re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)  # (whichever opens first: a line comment may hold "/*")
+        rel = os.path.relpath(path, ROOT)
+        for m in func.finditer(text):
+            (declared if m.group(3) == ";" else defined).setdefault(m.group(1), set()).add(rel)
+        for name in re.findall(r"\bstruct\s+(EnergyArgs|EnergyPlan)\s*\{", text):
+            structs.setdefault(name, []).append(rel)
+    return declared, defined, structs
+
+
+def test_internal_interface_is_declared_once():
+    """The contract between host, planner and kernels has one copy the compiler checks: every dsp_internal_* function is declared in
+    exactly one file, a header that its definition and its callers include; the CPU test programs define none (they see the real
+    geometry through dsp_kernels.h, not stand-ins); the energy kernels' argument blocks have one definition."""
+    declared, defined, structs = _internal_interface()
+    assert len(defined) >= 20 and "dsp_internal_plan_energy_carries" in defined and "dsp_internal_launch_vm_f32" in defined  # (the scan sees them)
+    assert sorted(set(defined) - set(declared)) == [], "defined without a prototype in a header"
+    many = {n: sorted(f) for n, f in declared.items() if len(f) != 1}
+    assert not many, f"declared in more than one file: {many}"
+    not_header = {n: sorted(f) for n, f in declared.items() if not all(p.endswith(".h") for p in f)}
+    assert not not_header, f"declared outside a header: {not_header}"
+    in_tests = {n: sorted(f) for n, f in defined.items() if any(p.startswith("tests" + os.sep) for p in f)}
+    assert not in_tests, f"a test program defines its own: {in_tests}"
+    assert {n: len(f) for n, f in structs.items()} == {"EnergyArgs": 1, "EnergyPlan": 1}, structs
