@@ -347,6 +347,11 @@ __global__ void __launch_bounds__(256, 2) dsp_energy_kernel(EnergyArgs A, int64_
 //     pass 3 (trapezoid replay); only the three lagged streams of the replay come from LDS, loaded PD stages ahead;
 //   * bl_subtract happens in the staging stores; the result of row r is stored behind the prefetch of row r + 2 (vmcnt
 //     counts stores: a store at the end of the loop body would sit in front of the next staging's s_waitcnt vmcnt(0));
+//     the row loads are non-temporal (a launch streams every byte once, past every cache: + 1.8 % alone), and in the build for
+//     4096-sample float32 rows they are issued behind pass 2, which lends their registers to 32 float64 images that pass 2 then
+//     does not convert again (KD below).  The sample in front of a lane's chunk comes from the lane below by DPP, not from LDS;
+//     the replay's group-start states are stored by the 4-point build alone, which is the one that reads them; lanes whose lagged
+//     window lies wholly below sample 0 read the guard at addresses of their own banks.  Figures: profiles/r07_headline_trims.md.
 //   * what must be picked out at a run-time position is never tested per sample: the float32 prefix sum at each 8-sample
 //     group end and the replay state at each group start go to a 9-entry per-lane LDS side array (a run-time group number is
 //     then an address); the two trapezoid samples every pick-off mode needs are copied out of a 16-sample register window
@@ -404,18 +409,20 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
     // (9 for up to 4096 samples, 17 for 8192).  The region's layout is the planner's, which sizes it and sets slot_off: dsp_kernels.h
     constexpr int AUXP = dsp_energy_rr::layout(C).side_pitch, GUARD = dsp_energy_rr::layout(C).guard, TAIL = dsp_energy_rr::layout(C).tail;
     static_assert(NG + 1 <= AUXP && S * NGS + 1 <= AUXP && (AUXP & 1) == 1, "side array too small");
-    static_assert(GUARD >= 2 * C + 8 && dsp_energy_rr::layout(C).slot_off >= GUARD, "lagged reads before sample 0 stay inside the guard");
+    static_assert(GUARD >= 2 * C + 8 && GUARD >= C + 64 + dsp_energy_rr::WINDOW_SPAN_EXTRA && dsp_energy_rr::layout(C).slot_off >= GUARD,
+                  "lagged reads before sample 0 stay inside the guard");
     float* aux = slot + 64 * C + TAIL + lane * AUXP;
     // the lagged window of the lane starts at element lane*C - lag: 8-byte aligned for an even lag; for an odd one the aligned pairs
-    // start one element lower and step t takes element t + 1 of them.  lagb[] is that aligned start (windows wholly below sample 0
-    // read the zero guard, whatever the parity), lagpar[] the wave-uniform, row-invariant parity of each lag
+    // start one element lower and step t takes element t + 1 of them.  lagb[] is that aligned start, lagpar[] the wave-uniform,
+    // row-invariant parity of each lag.  A window wholly below sample 0 reads zeros of the guard, at the guard address that equals its
+    // natural one modulo 64 elements (dsp_kernels.h: one address for all such lanes shares a bank pair with a lane that reads the image,
+    // in every access of the replay -- 68 conflict cycles a row at the benchmark's lags)
     const float* lagb[3];
     int lagpar[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         lagpar[k] = A.q[k] & 1;                           // q[] carries the lags
-        const int pos0 = lane * C - A.q[k] - lagpar[k];  // >= -C - 1: inside the guard
-        lagb[k] = (pos0 + lagpar[k] >= -C) ? slot + pos0 : slot - GUARD;
+        lagb[k] = slot + dsp_energy_rr::lag_window_start(C, GUARD, lane, A.q[k]);
     }
     // the carry plan as addresses of this lane (row-invariant): the capture group's pairs and the side-array element in front of it.  A
     // capture in group 0 has nothing in front: it reads the first word above the image, which nothing ever writes (0.0f since the clear)
@@ -445,12 +452,21 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     constexpr int NLD = IN == 0 ? NPF : NPF / 2;  // 16-byte loads per lane and waveform: 4 float32 or 8 16-bit samples each
     static_assert(IN == 0 || NPF % 2 == 0, "16-bit rows: an even number of 4-sample groups per lane");
+    // Pass 2 needs the float64 image of every sample pass 1 has just formed; all C of them are 2 C registers the kernel does not have,
+    // so pass 2 converts again.  The 4 NPF registers of the next row's prefetch are the largest block that can be had: where KD > 0 the
+    // prefetch (and the pending result store with it) is issued behind pass 2 instead of behind the staging, the loads then have the
+    // carries, pass 3 and the tail to arrive in (about half a row: enough, measured), and the first KD images of pass 1 are kept for
+    // pass 2 -- the same conversions of the same values.  KD = 32 is the measured best of 16 / 24 / 32 for 4096-sample float32 rows
+    // with one time constant (237 VGPRs, no scratch, no AGPR copies, two wavefronts per SIMD); the other builds keep the early prefetch.
+    constexpr int KD = (NPF == 16 && S == 1 && IN == 0 && !TAU) ? 32 : 0;
+    constexpr bool LATE = KD > 0;
     u4 pf[NLD];
     float pf_bl = 0.0f, pf_tp = 0.0f;
     auto prefetch = [&](int64_t r) {
         const char* g = (const char*)A.wf + (r * A.wf_stride + A.wf_offset) * (IN == 0 ? 4 : 2);
 #pragma unroll
-        for (int b = 0; b < NLD; ++b) pf[b] = reinterpret_cast<const u4*>(g)[b * 64 + lane];
+        for (int b = 0; b < NLD; ++b)  // (non-temporal: every byte of a row is read once per launch, and a launch's rows do not fit any cache)
+            pf[b] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(g) + b * 64 + lane);
         // (address space 1 spelled out: a pointer that went through a null test is otherwise loaded with flat_load, whose
         // out-of-order return forces every LDS wait that follows it down to lgkmcnt(0))
         typedef const __attribute__((address_space(1))) float* gptr;
@@ -503,10 +519,14 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
         reinterpret_cast<f2*>(slot + len)[lane] = f2{0.0f, 0.0f};
         const float t_in = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pf_tp)));
         const int64_t next = row + stride_rows;
-        __builtin_amdgcn_sched_barrier(0);
-        if (next < n_wf) prefetch(next);
-        if (pend_row >= 0 && lane == 0) A.out[pend_row * A.out_stride] = pend_result;
-        __builtin_amdgcn_sched_barrier(0);
+        auto fetch_next = [&]() __attribute__((always_inline)) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (next < n_wf) prefetch(next);
+            if (pend_row >= 0 && lane == 0) A.out[pend_row * A.out_stride] = pend_result;
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        bool fetched = false;
+        if constexpr (!LATE) fetch_next();
         wave_sync();
         PHASE(0)
         RR_PRIO_AT(0)
@@ -521,15 +541,21 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
             xr[2 * j] = v.x;
             xr[2 * j + 1] = v.y;
         }
-        const float xprev = (lane > 0) ? mine[-1] : 0.0f;
+        const float xprev = wave_prev(xr[C - 1]);  // the sample in front of the chunk is the lane below's last (lane 0: 0.0f)
         // ---- pass 1: float64 sum of x over the chunk
         // (four partial sums: the float64 sum of 66 float32 samples is exact for one waveform's dynamic range, so the order is free,
         // and one chain of dependent float64 adds would cost their full latency 66 times)
         double Xp[4] = {0.0, 0.0, 0.0, 0.0};
+        double xd[KD > 0 ? KD : 1];
 #pragma unroll
         for (int t = 0; t < C; ++t) {
             if ((t & 7) == 0) __builtin_amdgcn_sched_barrier(0);  // (keeps the float64 conversions from being hoisted: registers)
-            Xp[t & 3] += (double)xr[t];
+            if (t < KD) {
+                xd[t] = (double)xr[t];
+                Xp[t & 3] += xd[t];
+            } else {
+                Xp[t & 3] += (double)xr[t];
+            }
         }
         const double X = (Xp[0] + Xp[1]) + (Xp[2] + Xp[3]);
         double c_row = A.c;
@@ -547,7 +573,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
         }
         PHASE(1)
         RR_PRIO_AT(1)
-        // the float64 images of the samples are cheaper to recompute in pass 2 than to keep (130 registers): hide the reuse
+        // the float64 images of the samples past the first KD are cheaper to recompute in pass 2 than to keep (130 registers): hide the reuse
 #pragma unroll
         for (int t = 0; t < C; ++t) asm volatile("" : "+v"(xr[t]));
         if (!in_nan) {
@@ -559,7 +585,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
 #pragma unroll
             for (int t = 0; t < C; ++t) {
                 if ((t & 7) == 0) __builtin_amdgcn_sched_barrier(0);
-                const double x = (double)xr[t];
+                const double x = t < KD ? xd[t] : (double)xr[t];
                 // acc_k = acc_{k-1} + (x_k - c x_{k-1}); the float64 association differs from the reference's (acc + x) - xp*c by
                 // <= 1 ulp of a double (the chunk carry already does), invisible after the float32 store; the chain is one add long
                 acc += __builtin_fma(-c, xp, x);
@@ -575,6 +601,10 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 if ((t & 7) == 7) aux[t >> 3] = run;
             }
             wave_sync();
+            if constexpr (LATE) {
+                fetch_next();
+                fetched = true;
+            }
             PHASE(2)
         RR_PRIO_AT(2)
             bool pz_nan = false;
@@ -632,7 +662,11 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 PHASE(3)
         RR_PRIO_AT(3)
                 // ---- pass 3: replay; own samples from registers, the three lagged streams software-pipelined PD stages of GL = 4 samples ahead
-                wave_sync();  // the prefix sums in aux are consumed; aux now receives the replay state at every group start
+                // Only the 4-point mode reads the replay's state at the group starts (its two 8-sample re-runs): that build writes them into
+                // aux, behind the carries' reads of the prefix sums there.  The two-point build writes nothing into aux in the replay and
+                // needs no ordering point here: the replay's lagged reads of other lanes' pass-2 output are behind the wave_sync() that
+                // closes pass 2, and its capture-buffer stores are behind the last row's capture reads by the wave_sync() that ends a row.
+                if constexpr (WIDE) wave_sync();
                 // the two samples every pick-off mode needs (floor and ceil of the time point) are caught on the fly: stage numbers
                 const int i0 = (int)t_in;
                 int capst[2], capoff[2], caplane[2];
@@ -689,7 +723,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                     for (int gl = 0; gl < NL; ++gl) {
                         __builtin_amdgcn_sched_barrier(0);
                         load_stage(gl + PD);  // (nothing past stage NL)
-                        if ((gl * GL) % 8 == 0) {
+                        if (WIDE && (gl * GL) % 8 == 0) {  // (the re-runs' start states)
 #pragma unroll
                             for (int s = 0; s < S; ++s) aux[s * NGS + (gl * GL) / 8] = y[s];
                         }
@@ -717,7 +751,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                             }
                         }
                     }
-                    aux[S * NGS] = y[S - 1];  // state before the two-sample tail (it extends the last chain)
+                    if (WIDE) aux[S * NGS] = y[S - 1];  // state before the two-sample tail (it extends the last chain)
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
                         y[S - 1] = trap_step_r<float, KIND>(y[S - 1], xr[C - 2 + u], lagged(0, S - 1, CS + u), lagged(1, S - 1, CS + u), lagged(2, S - 1, CS + u),
@@ -828,6 +862,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 }
             }
         }
+        if (LATE && !fetched) fetch_next();  // a NaN row: it did not reach the prefetch behind pass 2
         pend_result = result;
         pend_row = row;
         wave_sync();

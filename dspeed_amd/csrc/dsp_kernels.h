@@ -73,14 +73,30 @@ constexpr int lds_bytes(int R) { return (R + RB) * 64 * 4; }                    
 // The register-resident energy kernel's LDS region of one wavefront (dsp_energy.hip), in float32 elements, for C samples per lane: `guard`
 // zeros below the image (lagged reads before sample 0; an odd lag's pairs start one element lower: covered), the image of 64 C elements at
 // slot_off (16-byte aligned), `tail` elements above it, a side array of side_pitch (odd) elements per lane for the (C - 2) / 8 + 1 group
-// sums, a capture buffer of 2 x 16.
+// sums, a capture buffer of 2 x 16.  The guard holds 2 C + 8 elements for the windows that straddle sample 0 and at least C + 72 for
+// the ones wholly below it (lag_window_start): 1024 and 2048 samples get 46 and 30 elements more than 2 C + 8 for that.
 namespace dsp_energy_rr {
 struct Layout {
     int guard, slot_off, tail, side_pitch, elems;
 };
+constexpr int WINDOW_SPAN_EXTRA = 8;  // a lane reads C + 2 elements from its window's aligned start (an odd lag's extra pair, the tail's), the 4-point re-run up to C + 7
 constexpr Layout layout(int C) {
-    const int guard = 2 * C + 8, slot_off = (guard + 3) / 4 * 4, tail = 16, ng1 = (C - 2) / 8 + 1;
+    const int guard = 2 * C + 8 > C + 72 ? 2 * C + 8 : C + 72, slot_off = (guard + 3) / 4 * 4, tail = 16, ng1 = (C - 2) / 8 + 1;
     const int side_pitch = ng1 <= 9 ? 9 : (ng1 | 1);  // (9 for up to 4096 samples, 17 for 8192)
     return {guard, slot_off, tail, side_pitch, (slot_off + 64 * C + tail + 64 * side_pitch + 2 * 16 + 3) / 4 * 4};
+}
+// Where lane `lane` starts to read the stream that lags by `lag` samples, as an element of the image (sample i at element i; negative:
+// the guard), always even.  Its window is samples lane C - lag .. lane C - lag + C - 1, read as aligned pairs from `natural` = that start
+// minus the lag's parity.  A window that holds a sample >= 0 keeps its natural start.  One wholly below sample 0 reads zeros wherever it
+// reads them, and if all such lanes read one address that address shares a bank pair with one of the reading lanes in every access.  So
+// each reads at the guard address that equals its natural one modulo 64 elements (the 64 banks of an 8-byte access of 32 lanes): natural
+// plus the smallest multiple of 64, of either sign, that brings it to -guard or above.  That is below -guard + 64, so the C +
+// WINDOW_SPAN_EXTRA elements from it end at or below element 0 when guard >= C + 72.  Natural starts of the 32 lanes of a half are C
+// apart, C / 2 is odd: 32 different pairs of banks, redirected or not.
+constexpr int lag_window_start(int C, int guard, int lane, int lag) {
+    const int natural = lane * C - lag - (lag & 1);
+    if (lane * C - lag + C > 0) return natural;
+    const int d = -guard - natural;  // > 0: natural lies that far below the guard, up by the next multiple of 64; < 0: that far inside or above it, down by whole 64s
+    return natural + (d >= 0 ? (d + 63) / 64 * 64 : -((-d) / 64 * 64));
 }
 }  // namespace dsp_energy_rr
