@@ -456,7 +456,11 @@ __device__ __forceinline__ void op_min_max_norm(Ctx<T>& cx, const DSP_PROG DevOp
         nan |= (v != v);
         pd[t] = v;
     }
-    cx.set_nan(op.dst, wave_any(nan));
+    // (inf / inf with an infinite bound: NaN in those samples alone, like the reference's division -- the slot holds real content beside them)
+    if (wave_any(nan))
+        cx.set_some_nan(op.dst);
+    else
+        cx.set_nan(op.dst, false);
     wave_sync();
 }
 
@@ -500,20 +504,30 @@ __device__ __forceinline__ void op_pole_zero(Ctx<T>& cx, const DSP_PROG DevOp& o
     double acc = E - c * (E - xprev);
     double xp = xprev;
     bool nan = false;
-    for (int t0 = 0; t0 < C; t0 += 8) {  // (loads of a batch ahead of its stores, as in bl_subtract: the filter usually runs in place)
-        T xs[8];
+    // A row that does not fill its chunks: behind an infinite last sample the recurrence runs on as inf - inf through the pads of the
+    // partial last chunk -- no samples of the output, so no "NaN in output", and the pads stay finite for the ops that read them.
+    // (Rows that fill their chunks -- 1024, 4096, 8192 samples -- keep the loop without the test per sample.)
+    auto run = [&](auto partial) {
+        const int n_row = ss.len - lane_id() * C;  // samples of this lane's chunk that belong to the row
+        for (int t0 = 0; t0 < C; t0 += 8) {  // (loads of a batch ahead of its stores, as in bl_subtract: the filter usually runs in place)
+            T xs[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) xs[k] = ps[t0 + k];
+            for (int k = 0; k < 8; ++k) xs[k] = ps[t0 + k];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const double x = (double)xs[k];
-            acc = (acc + x) - xp * c;
-            const T y = (T)acc;
-            nan |= (y != y);
-            pd[t0 + k] = y;
-            xp = x;
+            for (int k = 0; k < 8; ++k) {
+                const double x = (double)xs[k];
+                acc = (acc + x) - xp * c;
+                const T y = (!decltype(partial)::value || t0 + k < n_row) ? (T)acc : (T)0;
+                nan |= (y != y);
+                pd[t0 + k] = y;
+                xp = x;
+            }
         }
-    }
+    };
+    if (ss.len == 64 * C)
+        run(std::false_type{});
+    else
+        run(std::true_type{});
     if (wave_any(nan)) {  // pole_zero.py:76-77: NaN out of non-NaN input (inf - inf)
         cx.fatal(DSP_E_PZ_NAN);
         cx.set_nan(op.dst, true);
@@ -629,11 +643,14 @@ __device__ __forceinline__ void op_double_pole_zero(Ctx<T>& cx, const DSP_PROG D
         pd[0] = a;
         pd[1] = b;
     }
+    // (as in pole_zero: behind an infinite last sample the recursion runs on as inf - inf through the pads of a partial last chunk; they are
+    // no samples of the output and stay finite)
+    const int n_row = ss.len - lane * C;
 #pragma unroll 4
     for (int t = t_begin; t < C; ++t) {
         const double x = (double)ps[t];
         const double y2 = (((x + n1 * xm1) + n2 * xm2) - d1 * y1) - d2 * y0;
-        const T y = (T)y2;
+        const T y = t < n_row ? (T)y2 : (T)0;
         nan |= (y != y);
         pd[t] = y;
         y0 = y1;
@@ -662,6 +679,9 @@ __device__ __forceinline__ void op_double_pole_zero(Ctx<T>& cx, const DSP_PROG D
 // ------------------------------------------------------------------------------------------------
 #ifndef VM_FULL_AMAX
 #define VM_FULL_AMAX 1  // (0: A/B builds without the maximum-only replay of full rows)
+#endif
+#ifndef VM_TRAP_SECOND_GO
+#define VM_TRAP_SECOND_GO 1  // (0: A/B builds without the second replay of rows whose first one overflowed)
 #endif
 constexpr int TRAP_NCAP = 4;
 __device__ __forceinline__ float keep_larger(float a, float b) { return __builtin_fmaxf(a, b); }
@@ -733,7 +753,9 @@ __device__ __forceinline__ bool trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, 
     else
         G = (E - A[0]) / rr - (A[1] - A[2]) / ll;
     T g = (lane == 0) ? (T)-0.0 : (T)G;
-    const bool nonfinite = wave_any(!__builtin_isfinite(run));
+    // (also taken, at a second go below, by a row of finite samples whose replay leaves the finite numbers: w[i] - w[i - L] of samples
+    // near the largest float is an infinity in the reference's float arithmetic too, and inf - inf a few samples on)
+    bool nonfinite = wave_any(!__builtin_isfinite(run));
 
     // ---- pass B: replay the reference's rounding sequence from the speculative carry
     // lagged sample i - L_k lives in chunk (lane - q_k - 1) at offset C - rho_k + t, one element further once t >= rho_k
@@ -759,7 +781,10 @@ __device__ __forceinline__ bool trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, 
     typename Ctx<T>::LT* __restrict__ pd = STORE ? cx.chunk(sd) : nullptr;  // (another slot than the ones the steps read: loads may pass stores)
     const int n_valid = ss.len, i_first = lane * C;
     bool nan_made = false;
-    if (nonfinite) {  // true carries, one lane at a time (rows with an infinite sample only)
+    T y, vmin, vmax;
+    int imin, imax;
+  for (;;) {
+    if (nonfinite) {  // true carries, one lane at a time (rows with an infinite sample, or whose replay made one, only)
         T carry = (T)-0.0, yend = (T)0, ylast = (T)0;
         for (int d = 0; d < 64; ++d) {
             if (lane == d) {
@@ -776,9 +801,9 @@ __device__ __forceinline__ bool trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, 
         }
         nan_made = wave_any(ylast != ylast);
     }
-    T y = g;
-    T vmin = __builtin_huge_val(), vmax = -__builtin_huge_val();
-    int imin = 0x7fffffff, imax = 0x7fffffff;
+    y = g;
+    vmin = __builtin_huge_val(), vmax = -__builtin_huge_val();
+    imin = 0x7fffffff, imax = 0x7fffffff;
     {
         int t = 0;
         while (t < C) {
@@ -815,6 +840,9 @@ __device__ __forceinline__ bool trap_core(Ctx<T>& cx, const DSP_PROG DevOp& op, 
                 if (t == cap_off[c] + 1) capv[c] = y;
         }
     }
+    if (!VM_TRAP_SECOND_GO || nonfinite || !wave_any(!__builtin_isfinite(y))) break;  // (one wave vote per row; an infinity or NaN, once made, stays to the chunk's end)
+    nonfinite = true;
+  }
     // ---- true carries: exact scan of the per-chunk increments
     const double D = (double)y - (double)g;
     const double tstart = wave_exscan_add(D);
@@ -1049,6 +1077,16 @@ __device__ __attribute__((noinline)) T pickoff_spline(const typename Ctx<T>::LT*
     const int i0 = (int)t_in;  // 0 <= i0 <= n - 2: the caller handles integer t_in
     const double t0 = (double)t_in - (double)i0, t1 = 1.0 - t0;
     auto X = [&](int i) -> double { return (double)lds[padded_index(ss, i)]; };
+    // An infinite sample anywhere in the row reaches every second derivative in the reference's sweeps (u alternates +-inf from it to the
+    // row's end, the back substitution carries that down to i0) and the two of them that are read have opposite signs: NaN, however far
+    // from t_in the sample lies -- which the window below cannot see.  (t_in in the last interval reads one of them only: an infinity
+    // there, NaN here.)
+    bool nonfinite = false;
+    for (int i = lane; i < n; i += 64) {
+        const double v = X(i);
+        nonfinite |= !((v - v) == 0.0);
+    }
+    if (wave_any(nonfinite)) return quiet_nan<T>();
     constexpr int WARM = 48;
     constexpr double W2_FIX = -0.2679491924311227;
     const int j = i0 + lane;
