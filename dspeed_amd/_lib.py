@@ -23,7 +23,7 @@ ARG_CONST, ARG_INPUT, ARG_REG = range(3)
 (OP_LOAD, OP_STORE, OP_STORE_SCALAR, OP_BL_SUBTRACT, OP_POLE_ZERO, OP_DOUBLE_POLE_ZERO, OP_TRAP_FILTER, OP_TRAP_NORM,
  OP_ASYM_TRAP, OP_PICKOFF, OP_TIME_POINT_THRESH, OP_MIN_MAX, OP_DWT_HAAR, OP_CONVOLVE, OP_COPY, OP_TRAP_PICKOFF, OP_AMAX,
  OP_SCALAR_AFFINE, OP_MEAN_BELOW, OP_CONVOLVE_AMAX, OP_WINDOWER, OP_AVG_CURRENT, OP_TRAP_WINDOW_PICKOFF, OP_TRAP_REDUCE, OP_UPSAMPLER, OP_MOVING_WINDOW_MULTI, OP_LINEAR_SLOPE_FIT,
- OP_SCALAR_CONVERT, OP_SCALAR_DIV, OP_INTERP_TIME_POINT_THRESH, OP_MIN_MAX_NORM, OP_ELEMENTWISE, OP_SCALAR_FUNC) = range(1, 34)
+ OP_SCALAR_CONVERT, OP_SCALAR_DIV, OP_INTERP_TIME_POINT_THRESH, OP_MIN_MAX_NORM, OP_ELEMENTWISE, OP_SCALAR_FUNC, OP_MULTI_EXTREMA) = range(1, 35)
 (FN_ADD, FN_SUB, FN_MUL, FN_DIV, FN_LT, FN_LE, FN_GT, FN_GE, FN_EQ, FN_NE, FN_WHERE, FN_ISNAN, FN_ISFINITE, FN_NEG, FN_COPY, FN_FLOORDIV,
  FN_IADD, FN_ISUB, FN_IMUL, FN_IFLOORDIV, FN_ICAST, FN_LOR, FN_LAND, FN_RINT, FN_FLOOR, FN_CEIL, FN_TRUNC) = range(27)
 
@@ -143,6 +143,7 @@ def lib():
         "dsp_trap_pickoff_f32": [vp, C.c_int, i64, i32, i64, i32, i32, vp, f32, vp, vp, pi64],
         "dsp_dwt_haar_f32": [vp, C.c_int, i64, i32, i64, i32, i32, vp, i32, i64, vp, pi64],
         "dsp_convolve_wf_f32": [vp, C.c_int, i64, i32, i64, vp, i32, i32, vp, i32, i64, vp, pi64],
+        "dsp_get_multi_local_extrema_f32": [vp, C.c_int, i64, i32, i64, vp, f32, vp, f32, i32, vp, f32, vp, f32, vp, vp, i32, i64, vp, vp, vp, pi64],
         "dsp_synth_waveforms": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_synth_pulses": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_stream_read": [vp, i64, vp, vp],
@@ -184,7 +185,7 @@ EXPORTS = [
     "dsp_moving_window_multi_f32", "dsp_moving_window_multi_f64", "dsp_linear_slope_fit_f32", "dsp_linear_slope_fit_f64", "dsp_dwt_haar_f32", "dsp_convolve_wf_f32", "dsp_synth_waveforms", "dsp_synth_pulses", "dsp_stream_read",
     "dsp_bl_subtract_f64", "dsp_pole_zero_f64", "dsp_double_pole_zero_f64", "dsp_trap_filter_f64", "dsp_trap_norm_f64",
     "dsp_asym_trap_filter_f64", "dsp_fixed_time_pickoff_f64", "dsp_time_point_thresh_f64", "dsp_min_max_f64", "dsp_dwt_haar_f64",
-    "dsp_convolve_wf_f64", "dsp_linear_slope_fit_rows",
+    "dsp_convolve_wf_f64", "dsp_linear_slope_fit_rows", "dsp_get_multi_local_extrema_f32", "dsp_get_multi_local_extrema_f64",
 ]
 
 

@@ -363,7 +363,7 @@ class _ChunkWorker:
         chain = self.chain
         _set_buffer_len(chain, self.buffer_len, columns, self.mask, n)
         out = {name[4:] if name.startswith("out:") else name:
-               np.empty((n,) if length is None else (n, length), dtype=getattr(var, "dtype", None) or chain.loop_dtype)
+               np.empty((n,) if length is None else (n, length), dtype=getattr(var, "table_dtype", None) or getattr(var, "dtype", None) or chain.loop_dtype)
                for name, (var, length) in chain._out_vars.items()}
         try:
             chain(columns, out)
@@ -373,8 +373,12 @@ class _ChunkWorker:
         for c in chain._copy_pars:
             if c in columns:
                 out[c] = np.asarray(_values(columns[c]))
-        # variable-length outputs (declared with vector_len=len(<input>)) leave as VectorOfVectors: padded rows + their lengths
-        lens = {k: np.asarray(columns[src]) for k, src in chain.vector_lens.items() if k in out and src in columns}
+        # variable-length outputs (declared with vector_len=len(<input>), or with a per-event value the recipe computes: the count of
+        # get_multi_local_extrema) leave as VectorOfVectors: padded rows + their lengths, from the input table or from the results
+        lens = {k: np.asarray(columns[src] if src in columns else out[src]) for k, src in chain.vector_lens.items()
+                if k in out and (src in columns or src in out)}
+        for name in getattr(chain, "hidden_outputs", ()):
+            out.pop(name, None)
         return out, lens
 
 

@@ -31,6 +31,7 @@ from .language import (Grid, Quantity, SExpr, Var, _Builder, _GENERATORS, _MODUL
 
 # processors whose output waveform has the input's dimension name in the gufunc signature ("(n),...->(n)") and therefore its
 # coordinate grid (reference :1601-1619, 1700); the others' outputs have no grid unless the recipe declares one
+_MULTI_EXTREMA = "get_multi_local_extrema"
 _SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi")
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
@@ -125,6 +126,15 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
                 a.length = src_len
             a.dtype = np.dtype(np.float32)
             a.is_coord = False
+    if function == _MULTI_EXTREMA:
+        # its lists hold sample indices of the input: with a time unit they are coordinates on its grid, written in that unit like tp_max of
+        # min_max (reference :1990-2014); its counts are uint32 (the gufunc's "II")
+        for a in args[6:8]:
+            if isinstance(a, Var) and _time_unit_ns(a.unit) is not None and _grid_of(args[0]) is not None:
+                a.is_coord, a.grid = True, _grid_of(args[0])
+        for a in args[8:10]:
+            if isinstance(a, Var):
+                a.out_dtype = np.dtype(np.uint32)
     args = [_as_taps(b, a, function) if r == "t" else a for a, r in zip(args, roles)]
     args = [_group_constant(b, a, function, key) if r == "i" and isinstance(a, (Var, SExpr)) else a for a, r in zip(args, roles)]
     _, args = _resolve(b, roles, args, same_dim_out=function in _SAME_DIM)
@@ -393,6 +403,8 @@ class _Stager:
     def plain_scalar(x) -> bool:  # a constant, a per-event input column or a fit / stage result: in HBM before the stage runs
         if isinstance(x, Var):
             return x.kind == "scalar" and x.sreg is None and ((x.is_input and x.source is not None) or getattr(x, "ext_key", None) is not None)
+        if isinstance(x, SExpr):  # (an expression a stage of its own has evaluated: stage_expression)
+            return x.op == "ext" and getattr(x, "ext_key", None) is not None
         return _is_number(x)
 
     @staticmethod
@@ -445,10 +457,12 @@ class _Stager:
                     and (_is_integral(start) or any(start is o for o in extremes)))
         return False
 
-    def stage(self, group, scalars, what, wf=None, drop=None):
+    def stage(self, group, scalars, what, wf=None, drop=None, wfs=(), rows_first=False):
         """Compile the steps ``group`` (on copies of the variables) into a program of its own that writes the per-event values ``scalars``
-        and the waveform ``wf``; from here on these are columns / rows in HBM, and the steps ``drop`` (default: the group) leave the program."""
-        b, outs = self.b, list(scalars) + ([wf] if wf is not None else [])
+        and the waveforms ``wf`` / ``wfs`` (stored ahead of the per-event values with ``rows_first``); from here on these are columns / rows
+        in HBM, and the steps ``drop`` (default: the group) leave the program.  A per-event value with an ``out_dtype`` travels in that type."""
+        rows = ([wf] if wf is not None else []) + list(wfs)
+        b, outs = self.b, (rows + list(scalars)) if rows_first else (list(scalars) + rows)
         vars2, steps2 = copy.deepcopy((b.vars, group))
         b2 = copy.copy(b)
         b2.vars, b2.steps, b2._conversions, b2.stage_ft = vars2, list(steps2), {}, self.ft
@@ -457,7 +471,8 @@ class _Stager:
                 v.aux_io = None  # (an index into the main program's bindings; the stage binds the fit's column by its name)
         pc, _tb = _compile(b2, [o.name for o in outs], self.n_rows, [], stage_mode=True)
         self.stages.append(_stage_record(what, pc._program, pc._consts, pc._in_vars, pc._ext_alias,
-                                         [(f"out:{o.name}", f"in:{o.name}", o.length if o.kind == "wf" else None) for o in outs]))
+                                         [(f"out:{o.name}", f"in:{o.name}", o.length if o.kind == "wf" else None) for o in outs],
+                                         out_dtypes={f"in:{o.name}": o.out_dtype for o in outs if getattr(o, "out_dtype", None) is not None}))
         for o in outs:
             if o.kind == "wf":  # pole_zero returns an all-NaN waveform for an input with a NaN and DSPFatal for a NaN of its own making
                 made_by = self.producer_of(o)
@@ -467,7 +482,20 @@ class _Stager:
                 o.ext_len, o.offset, o.dtype = o.length, 0, np.dtype(np.float32)
         for o in scalars:
             o.kind = "scalar"
+            if getattr(o, "out_dtype", None) is not None:
+                o.ext_dtype = o.out_dtype
         self.steps = _without(self.steps, group if drop is None else drop)
+
+    def stage_expression(self, a, what):
+        """A per-event operand of a kernel that reads its operands as float32 columns, evaluated by a small program of its own: an expression
+        between values that are in HBM (0.5 * bl_std), or a column of another type.  Returns the operand as the kernel's stage reads it."""
+        if not isinstance(a, SExpr):
+            a = SExpr("func", (_lib.FN_COPY, a), f"float32({a.name})", a.unit, a.is_coord, a.grid)
+        self.b.vars[a.name] = a  # (an output of the small program, by its name)
+        self.stage([], [a], what)
+        del self.b.vars[a.name]
+        a.op, a.args, a.ext_dtype, a.io = "ext", (), self.ft, None
+        return a
 
     def move_ahead(self, operands) -> bool:
         """What computes these per-event operands from rows in HBM (min_max of the t0-filtered waveform, the t0 estimate) moves ahead of the
@@ -635,6 +663,54 @@ def _stage_row_reductions(cx: _Stager):
         cx.stage(group, [o for g in group for o in _outputs_of(g)], f"per-event values of {v.name} off its rows")
 
 
+def _stage_multi_extrema(cx: _Stager):
+    """``get_multi_local_extrema`` runs on dsp_extrema.hip and nowhere else (the interpreter has no such op), on rows in HBM: this stage is
+    mandatory.  Rows that are chain inputs or a stage's waveform are read as they are; any other source is written to HBM first by a small
+    program of its own, as a long filter's input is.  Per-event operands: constants, float32 columns of the input table, fit and stage
+    results; what the program would compute off rows in HBM moves ahead of it (``move_ahead``); expressions of those and columns of other
+    types go through a small program of their own (``stage_expression``)."""
+    fn = _MULTI_EXTREMA
+    for st in list(cx.steps):
+        if st[0] != fn or not cx.has(st):
+            continue
+        args, key = list(st[1]), st[2]
+        src, direction, lists, counts = args[0], args[3], args[6:8], args[8:10]
+        if not _is_integral(direction):
+            raise NotImplementedError(f"{fn} ({key}): search_direction must be a constant integer")
+        if int(direction) == 2:
+            raise NotImplementedError(f"{fn} ({key}): search_direction 2 (extrema found in both directions) is not implemented: the reference's "
+                                      "branch reads the maxima with the minima's mask and defines no result to agree with")
+        if not all(isinstance(v, Var) and v.kind == "wf" and v.length for v in lists) or not all(isinstance(v, Var) for v in counts):
+            raise ProcessingChainError(f"{fn} ({key}): declare the lists as name(length) and name the counts")
+        if int(direction) == 3 and lists[0].length > 64:
+            raise NotImplementedError(f"{fn} ({key}): search_direction 3 takes lists of at most 64 entries ({lists[0].length} declared)")
+        base = _base_of(src)
+        if base is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        if not cx.row_input(base):
+            anc = cx.ancestors(base)
+            if not anc:
+                raise NotImplementedError(f"{fn} ({key}): its source '{base.name}' cannot be written to rows in memory")
+            cx.stage(anc, [], f"{base.name} -> HBM", wf=base, drop=[])
+        for k in (1, 2, 4, 5):
+            a = args[k]
+            if not isinstance(a, (Var, SExpr)):
+                if isinstance(a, (tuple, Grid)) or not (_is_number(a) or isinstance(a, Quantity)):
+                    raise NotImplementedError(f"{fn} ({key}): operand {a!r} is neither a number nor a per-event value")
+                continue
+            for leaf in _leaves(a, []):  # what the program would compute off rows in HBM moves ahead of it
+                if not cx.plain_scalar(leaf) and not (leaf.kind == "scalar" and cx.move_ahead([leaf])):
+                    raise NotImplementedError(f"{fn} ({key}): operand '{a.name}' depends on '{leaf.name}', which is neither a constant, an input column, "
+                                              "a fit or stage result nor computed off rows in memory")
+            is_f32_column = isinstance(a, Var) and (getattr(a, "ext_key", None) is not None
+                                                    or np.dtype(_column(cx.b.tb_in, a.source).dtype) == np.dtype(np.float32))
+            if not is_f32_column and not (isinstance(a, SExpr) and cx.plain_scalar(a)):
+                args[k] = cx.stage_expression(a, f"{a.name} for {fn} {key}")
+        step = (fn, args, key)
+        cx.steps = [step if x is st else x for x in cx.steps]
+        cx.stage([step], counts, f"{fn} {key} on rows", wfs=lists, rows_first=True)
+
+
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     """Long FIRs leave the program: each ``convolve_wf`` with a constant kernel of STAGE_MIN_TAPS or more taps becomes a launch of the
     matrix-core FIR kernels ahead of the program (one waveform per wavefront is the wrong shape for 133 x 8192 or 5792 x 301
@@ -649,14 +725,18 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
         return steps, []  # the program is nothing but filters (BASELINE configs[2]): dsp_chain_create gives it the FIR kernel as a whole
     cx = _Stager(b, steps, out_pars, n_rows, ft)
     _stage_long_firs(cx)
-    if not cx.stages:
+    fir_staged = bool(cx.stages)
+    has_peaks = any(st[0] == _MULTI_EXTREMA for st in cx.steps)
+    if not cx.stages and not has_peaks:
         return cx.steps, cx.stages
-    _stage_short_traps(cx)
-    _stage_current_branch(cx)
+    if fir_staged:  # (the optional families follow the long filters, as before; the peak finder's stage is made with or without them)
+        _stage_short_traps(cx)
+        _stage_current_branch(cx)
+    _stage_multi_extrema(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and getattr(v, "ext_key", None) is not None and getattr(v, "aux_io", None) is None}
     cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
-    if ft == np.dtype(np.float32) and os.environ.get("DSPEED_HIP_NO_ROW_REDUCTIONS") != "1":
+    if ft == np.dtype(np.float32) and os.environ.get("DSPEED_HIP_NO_ROW_REDUCTIONS") != "1" and fir_staged:
         _stage_row_reductions(cx)
     return cx.steps, cx.stages
 
@@ -1104,7 +1184,7 @@ class _Emitter:
                 if getattr(a, "aux_io", None) is not None:  # a fit done ahead of the chain
                     return Scalar.input(a.aux_io)
                 if getattr(a, "ext_key", None) is not None:  # a fit or a stage ahead of this program
-                    return self.column(a, f"in:{a.name}", self.ft, buffer=a.ext_key)
+                    return self.column(a, f"in:{a.name}", getattr(a, "ext_dtype", self.ft), buffer=a.ext_key)
                 if a.is_input:
                     return self.column(a, f"in:{a.name}", _column(self.b.tb_in, a.source).dtype, var=a)
                 raise ProcessingChainError(f"scalar '{a.name}' is used before it is computed")
@@ -1220,6 +1300,23 @@ class _Emitter:
         for v in srcs:
             if v is not dead and v.slot != dst.slot:
                 self.release(v, si)
+
+    def multi_extrema(self, si, fn, args, what):
+        """the whole program of the peak finder's stage: LOAD, MULTI_EXTREMA; the stores of its lists and counts follow (``_emit_outputs``)"""
+        src = self.ensure_loaded(args[0], si)
+        sp = tuple(self.scalar_operand(args[k], args, what=what) for k in (1, 2, 4, 5))
+        direction = self.scalar_operand(args[3], args, integer=True, what=what)
+        vt_max, vt_min = self.out_wf(args[6], None, fn), self.out_wf(args[7], None, fn)
+        if vt_max.length != vt_min.length:
+            raise ProcessingChainError(f"{what}: the two lists share one length ({vt_max.length} and {vt_min.length} declared)")
+        vt_max.slot, vt_min.slot = self.new_slot(vt_max.length), self.new_slot(vt_min.length)
+        first = self.p.add_sregs(2)
+        for k, a in enumerate(args[8:10]):
+            if not isinstance(a, Var):
+                raise ProcessingChainError(f"{what}: the counts must be variable names")
+            a.kind, a.sreg = "scalar", first + k
+        self.p.add_op(_lib.OP_MULTI_EXTREMA, dst=vt_max.slot, src=src.slot, ip=(direction, vt_min.slot, first), sp=sp)
+        self.release(src, si)
 
     def copy_slice(self, si, fn, args, what):
         src = self.ensure_loaded(args[0], si)
@@ -1397,7 +1494,7 @@ _READ_OFF = {
 _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OPS, _Emitter.trapezoid), **dict.fromkeys(_WINDOW_OPS, _Emitter.window),
          "slice": _Emitter.copy_slice, "min_max": _Emitter.four_values, "linear_slope_fit": _Emitter.four_values,
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
-         "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve}
+         "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema}
 
 
 def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
@@ -1429,14 +1526,28 @@ def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
             if v.slot is None:
                 raise ProcessingChainError(f"output waveform '{o}' was never computed")
             odt = np.dtype(np.bool_) if v.dtype == np.dtype(np.bool_) else ft
+            unit_ns = _time_unit_ns(v.unit)
+            src_slot = v.slot
+            if v.is_coord is True and v.grid is not None and unit_ns is not None and not stage_mode:
+                # a list of sample indices (get_multi_local_extrema) written in its time unit: (index + grid offset) * period, sample by sample,
+                # in the chain's float type (exact while the times are integers below 2^24; the reference forms them in float64)
+                off_in = b.offset_in_periods(v.grid, v.grid.period)
+                off_in = e.scalar_operand(off_in, [], what=f"output {o}") if isinstance(off_in, (Var, SExpr)) else Scalar.const(float(off_in))
+                src_slot = e.new_slot(v.length)
+                p.add_op(_lib.OP_ELEMENTWISE, dst=src_slot, src=v.slot, ip=(_lib.FN_ADD, -1, -1), sp=(Scalar.const(0.0), off_in, Scalar.const(0.0)))
+                p.add_op(_lib.OP_ELEMENTWISE, dst=src_slot, src=src_slot, ip=(_lib.FN_MUL, -1, -1),
+                         sp=(Scalar.const(0.0), Scalar.const(v.grid.period / unit_ns), Scalar.const(0.0)))
             io = p.add_io(f"out:{o}", _lib.IO_WF_OUT, odt, v.length)
-            p.add_op(_lib.OP_STORE, src=v.slot, io=io)
+            p.add_op(_lib.OP_STORE, src=src_slot, io=io)
             out_bind[f"out:{o}"] = (SimpleNamespace(name=o, dtype=odt), v.length)
             if getattr(v, "vector_len", None) is not None:
                 vl = v.vector_len
-                if not (isinstance(vl, Var) and vl.is_input):
-                    raise NotImplementedError(f"output '{o}': vector_len must be the length of an input array (len(<input>))")
-                vector_lens[o] = vl.source
+                if isinstance(vl, Var) and vl.is_input and vl.source is not None:
+                    vector_lens[o] = vl.source  # a column of the input table
+                elif isinstance(vl, Var) and vl.name in out_pars:
+                    vector_lens[o] = vl.name    # a per-event value the recipe computes: an output (a hidden one if the recipe does not ask for it)
+                else:
+                    raise NotImplementedError(f"output '{o}': vector_len must be the length of an input array or a per-event variable the recipe computes")
             tb_out[o] = np.empty((n_rows, v.length), dtype=v.dtype if _is_int_dtype(v) and v.dtype.kind != "b" else odt)
             continue
         # a time coordinate is written in its unit, not in samples: (index + grid offset) * period (reference :1990-2014, get_buffer(unit))
@@ -1454,10 +1565,13 @@ def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
             raise ProcessingChainError(f"output '{o}' was never computed")
         reg = e.scalar_operand(v, [], what=f"output {o}")
         odt = np.dtype(np.bool_) if getattr(v, "dtype", None) == np.dtype(np.bool_) else ft
+        as_dt = getattr(v, "out_dtype", None)  # (a count of get_multi_local_extrema: uint32 -- as its stage writes it, and as the table holds it)
+        if stage_mode and as_dt is not None:
+            odt = np.dtype(as_dt)
         io = p.add_io(f"out:{o}", _lib.IO_SCALAR_OUT, odt)
         p.add_op(_lib.OP_STORE_SCALAR, io=io, ip=(reg.index,))
-        out_bind[f"out:{o}"] = (SimpleNamespace(name=o, dtype=odt), None)
-        tb_out[o] = np.empty(n_rows, dtype=v.dtype if isinstance(v, SExpr) and _is_int_dtype(v) and v.dtype.kind != "b" else odt)
+        out_bind[f"out:{o}"] = (SimpleNamespace(name=o, dtype=odt, table_dtype=None if stage_mode or as_dt is None else np.dtype(as_dt)), None)
+        tb_out[o] = np.empty(n_rows, dtype=v.dtype if isinstance(v, SExpr) and _is_int_dtype(v) and v.dtype.kind != "b" else (as_dt or odt))
     return tb_out, out_bind, vector_lens
 
 
@@ -1494,6 +1608,19 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
     main = not stage_mode
     off = lambda switch: os.environ.get(switch) == "1"  # noqa: E731
     steps = b.steps
+    hidden = []
+    if main:
+        out_pars = list(out_pars)
+        for o in list(out_pars):  # the computed length of a variable-length output leaves with it: a hidden output if the recipe does not ask for it
+            vl = getattr(b.vars.get(o), "vector_len", None)
+            if isinstance(vl, Var) and not vl.is_input and vl.name not in out_pars and b.vars.get(vl.name) is vl:
+                out_pars.append(vl.name)
+                hidden.append(vl.name)
+        if any(st[0] == _MULTI_EXTREMA for st in steps):
+            if off("DSPEED_HIP_NO_STAGES"):
+                raise NotImplementedError(f"{_MULTI_EXTREMA} runs as a stage ahead of the program, on a kernel of its own: not with DSPEED_HIP_NO_STAGES=1")
+            if ft != np.dtype(np.float32):
+                raise NotImplementedError(f"{_MULTI_EXTREMA} in a recipe whose loop type is {ft}: the stages ahead of the program hand on float32 rows")
     island, island_out = _int_island(b, steps, out_pars, ft) if main else (None, {})
     aux, stages = [], []
     if main and not off("DSPEED_HIP_FIT_IN_CHAIN"):
@@ -1528,7 +1655,8 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
     from .processing_chain import ProcessingChain  # (the runtime imports this module)
 
     chain = ProcessingChain(p, e.in_bind, out_bind, e.consts, n_rows, proc_strings, ft, aux_desc, stages=stages, ext_alias=e.ext_alias, tail=tail, walks=walks)
-    chain.vector_lens = vector_lens  # variable-length outputs -> the input column that holds their per-event lengths
+    chain.vector_lens = vector_lens  # variable-length outputs -> the input column, or the output, that holds their per-event lengths
+    chain.hidden_outputs = hidden    # outputs the recipe did not ask for: the computed lengths of variable-length outputs
     return chain, tb_out
 
 

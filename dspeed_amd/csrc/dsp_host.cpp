@@ -361,7 +361,7 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     HIP_TRY(hipMalloc((void**)&ch->dev_err, DSP_ERR_WORDS * sizeof(int)));
     HIP_TRY(hipMemset(ch->dev_err, 0, DSP_ERR_WORDS * sizeof(int)));
     const int block_lds = ch->lds_bytes_per_wave * ch->waves_per_block, classic_lds = ch->lds_bytes_per_wave * ch->classic_wpb;
-    int rc = raise_lds(true, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
+    int rc = raise_lds(!ch->ext_ok, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
     if (!rc) rc = raise_lds(ch->fused_ok, classic_lds, 64 * 1024, "energy kernel, %d", [&](int n) { return dsp_internal_set_energy_lds(ch->fused_trap, ch->fused_npf, n); });
     if (!rc) rc = raise_lds(ch->fir_f16, dsp_fir_f16::lds_bytes(), 64 * 1024, "float16 FIR kernel", dsp_internal_set_fir_f16_lds);
     if (!rc) rc = raise_lds(ch->fir_ok, ch->fir_lds_bytes, 64 * 1024, "FIR kernel, %d", ch->fir.store ? dsp_internal_set_fir_store_lds : dsp_internal_set_fir_mfma_lds);
@@ -382,6 +382,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // Does the kernel of a route run THIS launch?  The program has its shape, the specialised kernels are on, and the buffers of this call keep
 // the 16-byte alignment its wide loads need (the plan vouches for strides and offsets, nobody for the pointers).  dsp_chain_execute asks
 // in the order of dsp_plan_route; a launch whose planned route does not apply runs on the next that does.
+static bool extrema_applies(const dsp_chain* ch, void* const*) { return ch->ext_ok; }  // (always: the program runs nowhere else; unaligned rows: its scalar loads)
 static bool scalar_applies(const dsp_chain* ch, void* const*) { return ch->scalar_ok && ch->fused_on; }
 static bool pz_rows_applies(const dsp_chain* ch, void* const* io_ptrs) {
     return ch->pz_ok && ch->fused_on && aligned16(io_ptrs[ch->pio_wf]) && aligned16(io_at(ch, io_ptrs, ch->pio_out));
@@ -534,6 +535,20 @@ static void bind_reductions(const dsp_chain* ch, void* const* io_ptrs, ReduceArg
 static int launched(dsp_chain* ch, void* stream, hipError_t e, const char* what) {
     if (e != hipSuccess) return fail(DSP_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     return post_err(ch, stream);
+}
+
+static int launch_extrema(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    ExtremaArgs A = ch->ext;
+    A.wf = io_ptrs[ch->xio_wf];
+    for (int k = 0; k < 4; ++k) A.par[k] = at(ch->xio_par[k]);
+    for (int k = 0; k < 2; ++k) {
+        A.vt_out[k] = at(ch->xio_vt[k]);
+        A.n_out[k] = (uint32_t*)at(ch->xio_n[k]);
+    }
+    const int vec = ch->ext_vec && aligned16(A.wf);
+    hipError_t e = (hipError_t)dsp_internal_launch_extrema(&A, n_wf, ch->ext_dtype, vec, ch->dev_err, (hipStream_t)stream);
+    return launched(ch, stream, e, "extrema kernel launch");
 }
 
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
@@ -718,6 +733,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (!on_chain_device.ok) return fail(DSP_ERR_HIP, "hipSetDevice(%d) failed", ch->device);
     (void)hipGetLastError();  // launch checks below report this launch, not a stale error of an unrelated earlier call
     // the first kernel, in the order of dsp_plan_route, that takes this launch's pointers
+    if (extrema_applies(ch, io_ptrs)) return launch_extrema(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -809,6 +825,7 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
         case DSP_ROUTE_SCALAR:
             lds = ch->host.n_sregs * 64 * ((ch->f64 || ch->i64) ? 8 : 4), wpb = 1, b = (int)((n_wf + 63) / 64);
             break;
+        case DSP_ROUTE_EXTREMA:
         case DSP_ROUTE_PZ_ROWS:
         case DSP_ROUTE_REDUCE: lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4); break;
         case DSP_ROUTE_FIR_RUNS: lds = dsp_fir_runs::lds_bytes(ch->runs.m) / 4, wpb = 4, b = runs_blocks(ch, n_wf); break;
@@ -1182,9 +1199,37 @@ int g_min_max(int ty, const WfIn& in, void* t_min, void* t_max, void* a_min, voi
     return m.run(in.n_wf, st, er);
 }
 
+int g_multi_extrema(int ty, const WfIn& in, const void* const* cols, const double* consts, int32_t direction, void* vt_max, void* vt_min, int32_t out_len,
+                    int64_t out_stride, uint32_t* n_max, uint32_t* n_min, void* st, int64_t* er) {
+    if (in.n_wf <= 0) return DSP_OK;
+    Mini m(ty);
+    m.n_sregs = 2;
+    const int s_in = m.add_slot(in.len), s_max = m.add_slot(out_len), s_min = m.add_slot(out_len);
+    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
+    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
+    dsp_scalar_arg sp[4];
+    for (int k = 0; k < 4; ++k) sp[k] = m.scalar(cols[k], consts[k]);
+    {
+        dsp_op& o = m.add_op(DSP_OP_MULTI_EXTREMA, s_max, s_in, 0);
+        o.ip[0] = direction;
+        o.ip[1] = s_min;
+        o.ip[2] = 0;
+        for (int k = 0; k < 4; ++k) o.sp[k] = sp[k];
+    }
+    m.add_op(DSP_OP_STORE, 0, s_max, m.add_io(DSP_IO_WF_OUT, ty, out_len, out_stride, vt_max));
+    m.add_op(DSP_OP_STORE, 0, s_min, m.add_io(DSP_IO_WF_OUT, ty, out_len, out_stride, vt_min));
+    void* counts[2] = {n_max, n_min};
+    for (int k = 0; k < 2; ++k) {
+        const int io_out = m.add_io(DSP_IO_SCALAR_OUT, DSP_U32, 1, 1, counts[k]);
+        dsp_op& sto = m.add_op(DSP_OP_STORE_SCALAR, 0, 0, io_out);
+        sto.ip[0] = k;
+    }
+    return m.run(in.n_wf, st, er);
+}
+
 }  // namespace
 
-#define DSP_GUFUNCS(SFX, TY, FT)                                                                                                              \
+#define DSP_GUFUNCS(SFX, TY, FT)                                                                                                             \
     int dsp_bl_subtract_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* baseline_dev,          \
                               FT baseline, FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                                     \
         return g_bl_subtract(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, baseline_dev, (double)baseline, out, out_stride, stream,        \
@@ -1287,6 +1332,16 @@ int g_min_max(int ty, const WfIn& in, void* t_min, void* t_max, void* a_min, voi
                               int64_t* err_row) {                                                                                             \
         return g_convolve(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, kernel_dev, kernel_len, mode_char, out, out_len, out_stride,       \
                           stream, err_row);                                                                                                   \
+    }                                                                                                                                        \
+    int dsp_get_multi_local_extrema_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride,                     \
+                                          const FT* a_delta_max_dev, FT a_delta_max, const FT* a_delta_min_dev, FT a_delta_min,              \
+                                          int32_t search_direction, const FT* a_abs_max_dev, FT a_abs_max, const FT* a_abs_min_dev,          \
+                                          FT a_abs_min, FT* vt_max_out, FT* vt_min_out, int32_t out_len, int64_t out_stride,                 \
+                                          uint32_t* n_max_out, uint32_t* n_min_out, void* stream, int64_t* err_row) {                        \
+        const void* cols[4] = {a_delta_max_dev, a_delta_min_dev, a_abs_max_dev, a_abs_min_dev};                                              \
+        const double consts[4] = {(double)a_delta_max, (double)a_delta_min, (double)a_abs_max, (double)a_abs_min};                           \
+        return g_multi_extrema(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, cols, consts, search_direction, vt_max_out, vt_min_out,      \
+                               out_len, out_stride, n_max_out, n_min_out, stream, err_row);                                                  \
     }
 
 DSP_GUFUNCS(f32, DSP_F32, float)

@@ -32,6 +32,8 @@ int dsp_internal_launch_rows(const RowsArgs* A, int64_t n_wf, int* err, int lds_
 int dsp_internal_set_rows_lds(int lds_bytes);
 int dsp_internal_launch_pz_rows(const PzArgs* A, int64_t n_wf, int* err, hipStream_t stream);
 int dsp_internal_launch_reduce(const ReduceArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+// dsp_extrema.hip (dtype: the rows'; vec: rows start on 16-byte boundaries and hold whole 16-byte vectors)
+int dsp_internal_launch_extrema(const ExtremaArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_scalar.hip (type: 0 float32, 1 float64, 2 int64 registers)
 int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);
 int dsp_internal_set_scalar_lds(int lds_bytes);

@@ -68,6 +68,9 @@ extern "C" const char* dsp_fatal_message(int code) {
         case DSP_E_MW_NUM_INT: return "The number of moving windows must be an integer";
         case DSP_E_MW_LEN_RANGE: return "The length of the moving window is out of range";
         case DSP_E_MW_NUM_NEG: return "The number of moving windows much be positive";
+        case DSP_E_EXTREMA_LEN: return "The length of your return array must be smaller than the length of your waveform";
+        case DSP_E_EXTREMA_DELTA: return "Delta must be positive";
+        case DSP_E_EXTREMA_DIR: return "search direction type not found.";
         default: return "";
     }
 }
@@ -97,6 +100,7 @@ struct PlanCtx {
     int n_slots, n_sregs, compute_dtype;
     ChainPlan* ch;
     bool f64 = false, i64 = false;
+    bool has_extrema = false;  // a MULTI_EXTREMA among the ops: its counts are the one kind of DSP_U32 output
     int esz = 4;  // bytes of an LDS element
     // FIR inputs (laid out without the chunk pad); slots that share their LDS region with another
     bool linear[DSP_MAX_SLOTS] = {false}, shares[DSP_MAX_SLOTS] = {false};
@@ -340,6 +344,64 @@ static bool match_reduce_shape(const PlanCtx& c) {
     ch->red_dtype = w.dtype;
     ch->red_vec = (w.row_stride * es) % 16 == 0 && (w.offset * es) % 16 == 0 && (w.len * es) % 16 == 0;
     ch->dio_wf = ld.io;
+    return true;
+}
+
+static double op_const(const PlanCtx& c, const dsp_op& o, int k);
+
+// Is the program the peak finder's (dsp_extrema.hip)?
+//   LOAD s;  MULTI_EXTREMA of s;  STORE of its two lists;  STORE_SCALAR of its two counts into DSP_U32 columns
+// The parameters are constants or columns of the loop's type.  Why not, otherwise: `why` (a program that holds the op runs nowhere else).
+static bool match_extrema_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    *why = "the program must be exactly LOAD, MULTI_EXTREMA, STORE, STORE, STORE_SCALAR, STORE_SCALAR";
+    if (c.n_ops != 6 || c.n_slots != 3 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_MULTI_EXTREMA || ops[2].opcode != DSP_OP_STORE ||
+        ops[3].opcode != DSP_OP_STORE || ops[4].opcode != DSP_OP_STORE_SCALAR || ops[5].opcode != DSP_OP_STORE_SCALAR)
+        return false;
+    const dsp_op &ld = ops[0], &ex = ops[1];
+    const dsp_io_desc& w = io[ld.io];
+    if (ex.src != ld.dst || ld.ip[0] != 0 || ld.ip[1] != 0 || w.len != c.slot_len[ld.dst]) return false;
+    *why = "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64, int32 or uint32 rows";
+    if (c.f64 ? (w.dtype != DSP_F64 && w.dtype != DSP_I32 && w.dtype != DSP_U32) : (w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16)) return false;
+    ExtremaArgs& A = ch->ext;
+    memset(&A, 0, sizeof A);
+    *why = "the two lists are stored once each, the two counts once each into DSP_U32 columns";
+    for (int k = 0; k < 2; ++k) ch->xio_vt[k] = ch->xio_n[k] = -1;
+    for (int i = 2; i < 4; ++i) {
+        const int which = ops[i].src == ex.dst ? 0 : (ops[i].src == ex.ip[1] ? 1 : -1);
+        if (which < 0 || ch->xio_vt[which] >= 0) return false;
+        ch->xio_vt[which] = ops[i].io;
+        A.vt_stride[which] = io[ops[i].io].row_stride;
+    }
+    for (int i = 4; i < 6; ++i) {
+        const int which = ops[i].ip[0] - ex.ip[2];
+        if (which < 0 || which > 1 || ch->xio_n[which] >= 0 || io[ops[i].io].dtype != DSP_U32) return false;
+        ch->xio_n[which] = ops[i].io;
+        A.n_stride[which] = io[ops[i].io].row_stride;
+    }
+    *why = "a parameter is a constant or a per-event column of the loop's type";
+    for (int k = 0; k < 4; ++k) {
+        ch->xio_par[k] = -1;
+        if (ex.sp[k].kind == DSP_ARG_INPUT && io[ex.sp[k].index].dtype == c.compute_dtype) {
+            ch->xio_par[k] = ex.sp[k].index;
+            A.par_stride[k] = io[ex.sp[k].index].row_stride;
+        } else if (ex.sp[k].kind == DSP_ARG_CONST) {
+            A.par_const[k] = op_const(c, ex, k);
+        } else {
+            return false;
+        }
+    }
+    A.wf_stride = w.row_stride;
+    A.wf_offset = w.offset;
+    A.len = w.len;
+    A.m = c.slot_len[ex.dst];
+    A.direction = ex.ip[0];
+    const int es = elem_size(w.dtype);
+    ch->ext_dtype = w.dtype;
+    ch->ext_vec = (w.row_stride * es) % 16 == 0 && ((int64_t)w.offset * es) % 16 == 0 && ((int64_t)w.len * es) % 16 == 0;
+    ch->xio_wf = ld.io;
     return true;
 }
 
@@ -871,6 +933,7 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_UPSAMPLER:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
         case DSP_OP_DWT_HAAR: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[2]; return 3;
+        case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
         case DSP_OP_MOVING_WINDOW_MULTI:
             out[0] = o.src;
             out[1] = o.dst;
@@ -917,6 +980,7 @@ static int check_call(PlanCtx& c) {
     P.n_sregs = n_sregs;
     c.ch->f64 = c.f64;
     c.ch->i64 = c.i64;
+    for (int i = 0; i < n_ops; ++i) c.has_extrema |= c.ops[i].opcode == DSP_OP_MULTI_EXTREMA;
     return DSP_OK;
 }
 
@@ -1038,7 +1102,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.has_extrema)  // (MULTI_EXTREMA: its only kernel streams the row through registers, nothing lives in LDS)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1088,7 +1152,8 @@ static int bind_io(PlanCtx& c) {
         if (a.kind == DSP_IO_WF_IN && !f64 && (a.dtype == DSP_I32 || a.dtype == DSP_U32 || a.dtype == DSP_F64))
             return fail(DSP_ERR_ARG, "io %d: int32/uint32/float64 rows select the float64 loop (compute_dtype DSP_F64)", k);
         const bool is_out = a.kind == DSP_IO_WF_OUT || a.kind == DSP_IO_SCALAR_OUT;
-        if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT))
+        if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT) &&
+            !(c.has_extrema && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32))  // (the counts of MULTI_EXTREMA: match_extrema_shape sees to the rest)
             return fail(DSP_ERR_ARG, "io %d: outputs have the chain's compute type or DSP_BOOL, taps the compute type", k);
         if ((a.dtype == DSP_BOOL || a.dtype == DSP_I64 || a.dtype == DSP_U64) && a.kind != DSP_IO_SCALAR_IN && a.kind != DSP_IO_SCALAR_OUT && !(a.dtype == DSP_BOOL && is_out))
             return fail(DSP_ERR_ARG, "io %d: DSP_BOOL / DSP_I64 / DSP_U64 are types of per-event columns (DSP_BOOL also of waveform outputs)", k);
@@ -1357,6 +1422,23 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
         case DSP_OP_AMAX:
             if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs) return fail(DSP_ERR_ARG, "op %d: bad AMAX", i);
             break;
+        case DSP_OP_MULTI_EXTREMA: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || !check_slot(P, o.ip[1]) || o.dst == o.src || o.ip[1] == o.src || o.dst == o.ip[1] ||
+                slot_len[o.dst] != slot_len[o.ip[1]] || o.ip[2] < 0 || o.ip[2] > n_sregs - 2)
+                return fail(DSP_ERR_ARG, "op %d: bad MULTI_EXTREMA (dst, ip[1]: two slots of one length for the lists; ip[2]: two registers for the counts)", i);
+            // the reference's checks in its order (get_multi_local_extrema.py:126-131, 305-306), for everything that is a constant
+            if (slot_len[o.dst] >= slot_len[o.src]) return fail(DSP_E_EXTREMA_LEN, "%s", dsp_fatal_message(DSP_E_EXTREMA_LEN));
+            for (int k = 0; k < 2; ++k)
+                if (o.sp[k].kind == DSP_ARG_CONST && op_const(c, o, k) < 0) return fail(DSP_E_EXTREMA_DELTA, "%s", dsp_fatal_message(DSP_E_EXTREMA_DELTA));
+            if (o.ip[0] < 0 || o.ip[0] > 3) return fail(DSP_E_EXTREMA_DIR, "%s", dsp_fatal_message(DSP_E_EXTREMA_DIR));
+            if (o.ip[0] == 2)
+                return fail(DSP_ERR_UNSUPPORTED, "get_multi_local_extrema: search_direction 2 (extrema found in both directions) is not implemented: the reference's "
+                                                 "branch reads the maxima with the minima's mask and defines no result to agree with");
+            if (o.ip[0] == 3 && slot_len[o.dst] > DSP_EXTREMA_UNION_MAX)
+                return fail(DSP_ERR_UNSUPPORTED, "get_multi_local_extrema: search_direction 3 takes lists of at most %d entries (%d asked for)", DSP_EXTREMA_UNION_MAX,
+                            slot_len[o.dst]);
+            break;
+        }
         case DSP_OP_DWT_HAAR: {
             if (!check_slot(P, o.src) || !check_slot(P, o.dst) || !check_slot(P, o.ip[2]) || o.dst == o.src || o.dst == o.ip[2])
                 return fail(DSP_ERR_ARG, "op %d: bad DWT_HAAR slots", i);
@@ -1881,6 +1963,12 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
     if (const int rc = bind_io(c)) return rc;
     if (const int rc = lower_ops(c)) return rc;
     fold_load_bl_subtract(c);
+    if (c.has_extrema) {  // no interpreter op behind it: its own kernel or nothing
+        const char* why = "";
+        ch->ext_ok = match_extrema_shape(c, &why);
+        if (!ch->ext_ok)
+            return fail(DSP_ERR_UNSUPPORTED, "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only, on rows in memory: %s", why);
+    }
     match_shapes(c);
     fold_scaled_thresholds(c);
     form_teams(c);
@@ -1890,6 +1978,7 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
 }
 
 dsp_route dsp_plan_route(const ChainPlan* ch) {
+    if (ch && ch->ext_ok) return DSP_ROUTE_EXTREMA;  // (whatever the switches say: the interpreter has no such op)
     if (!ch || !ch->fused_on) return DSP_ROUTE_VM;
     if (ch->scalar_ok) return DSP_ROUTE_SCALAR;
     if (ch->pz_ok) return DSP_ROUTE_PZ_ROWS;
@@ -1903,7 +1992,7 @@ dsp_route dsp_plan_route(const ChainPlan* ch) {
 }
 
 const char* dsp_plan_route_kernel_name(dsp_route route) {
-    return dsp_route_kernel_names[route >= DSP_ROUTE_SCALAR && route <= DSP_ROUTE_VM ? route : DSP_ROUTE_VM];
+    return dsp_route_kernel_names[route >= DSP_ROUTE_EXTREMA && route <= DSP_ROUTE_VM ? route : DSP_ROUTE_VM];
 }
 
 const char* dsp_plan_kernel_name(const ChainPlan* ch) { return dsp_plan_route_kernel_name(dsp_plan_route(ch)); }

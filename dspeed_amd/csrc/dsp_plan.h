@@ -82,6 +82,10 @@ struct ChainPlan {
     int dio_walk[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1}, dio_walk_thr[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1},
         dio_walk_ts[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1};
     bool red_vec = false;  // rows keep 16-byte alignment and hold whole 16-byte vectors
+    // the peak finder (dsp_extrema.hip): the one kernel a program with MULTI_EXTREMA runs on
+    bool ext_ok = false, ext_vec = false;
+    ExtremaArgs ext{};
+    int xio_wf = -1, xio_par[4] = {-1, -1, -1, -1}, xio_vt[2] = {-1, -1}, xio_n[2] = {-1, -1}, ext_dtype = DSP_F32;
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};

@@ -261,6 +261,24 @@ struct ReduceArgs {
     int32_t need_stream;  // 0: nothing asks for the whole row (walks only, on rows that are NaN from the first sample on or NaN-free: LOAD ip[2])
 };
 
+// arguments of the peak finder (dsp_extrema.hip), filled by the planner when a program has the shape
+//   LOAD -> MULTI_EXTREMA -> STORE, STORE, STORE_SCALAR, STORE_SCALAR
+#define DSP_EXTREMA_UNION_MAX 64 /* search_direction 3 keeps a sweep's tags one per lane: the longest list it takes */
+struct ExtremaArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 / int32 / uint32 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples
+    int32_t m;               // length of vt_max_out / vt_min_out
+    int32_t direction;       // search_direction: 0 forward, 1 backward, 3 the union of both
+    const void* par[4];      // a_delta_max_in, a_delta_min_in, a_abs_max_in, a_abs_min_in: a column of the loop's type, or null: par_const
+    int64_t par_stride[4];
+    double par_const[4];
+    void* vt_out[2];         // vt_max_out, vt_min_out: rows of m values of the loop's type
+    int64_t vt_stride[2];
+    uint32_t* n_out[2];      // n_max_out, n_min_out
+    int64_t n_stride[2];
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

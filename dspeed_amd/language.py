@@ -148,6 +148,7 @@ _SIGS = {
     "discrete_wavelet_transform": "wiccW", "convolve_wf": "wtcW", "fft_convolve_wf": "wtcW", "amax": "wiS",
     "mean_below_threshold": "wsS", "windower": "wsW", "avg_current": "wsW", "trap_pickoff": "wiisS",
     "upsampler": "wsW", "moving_window_multi": "wsiiW", "numpy_subtract": "wsW", "numpy_add": "wsW", "min_max_norm": "wssW", "linear_slope_fit": "wSSSS",
+    "get_multi_local_extrema": "wssissWWSS",  # (w_in, a_delta_max_in, a_delta_min_in, search_direction, a_abs_max_in, a_abs_min_in, two lists, two counts)
 }
 _SIGS.update({"sample": "wiS", "slice": "wiiW", "get": "wsS"})  # wf[i], wf[lo:hi:step], wf[variable] (reference :948-1071)
 
@@ -578,7 +579,7 @@ class _Builder:
                         v.dtype = v.dtype if v.dtype is not None else np.dtype(np.float32)
                 if "vector_len" in kw:
                     vl = kw["vector_len"]
-                    if not _is_scalar(vl):
+                    if not _is_scalar(vl) and not (isinstance(vl, Var) and vl.kind is None and vl.name in new):  # (or a count this processor makes)
                         raise ProcessingChainError(f"vector_len in '{src}' must be a per-event variable")
                     v.vector_len = vl
                 if "dtype" in kw:

@@ -82,7 +82,8 @@ class ProcessingChain:
         self._stage_key, self._stage = None, []  # page-locked staging buffers (one set per piece slot)
         self._timing = {"h2d": 0.0, "kernel": 0.0, "d2h": 0.0}
         self._copy_pars = []      # outputs that are input columns handed through
-        self.vector_lens = {}     # variable-length outputs -> input column with their per-event lengths
+        self.vector_lens = {}     # variable-length outputs -> the input column, or the output, with their per-event lengths
+        self.hidden_outputs = []  # outputs the recipe did not ask for (a computed vector_len): in the output table, not in what build_dsp delivers
         self.output_attrs = {}    # output -> attributes of its LGDO column (units, lh5_attrs, description)
         self.proc_strings = proc_strings
         self.device = None        # GPU ordinal the chain is bound to (None: the current device of the thread that first executes it)

@@ -260,6 +260,33 @@ def _windower(g, *args):
         st.release()
 
 
+def _get_multi_local_extrema(g, *args):
+    if len(args) not in (8, 10):
+        raise TypeError("get_multi_local_extrema(w_in, a_delta_max_in, a_delta_min_in, search_direction, a_abs_max_in, a_abs_min_in, vt_max_out, "
+                        "vt_min_out[, n_max_out, n_min_out]): vt_max_out and vt_min_out must be passed (their length is the number of extrema kept)")
+    w_in, d_max, d_min, direction, a_max, a_min, vt_max, vt_min = args[:8]
+    n_max, n_min = args[8:] if len(args) == 10 else (None, None)
+    st = Staging()
+    try:
+        ptr, code, n_wf, n, stride, one_d = st.wf_in(w_in)
+        sfx = loop_suffix(_dtype_of(w_in))
+        ft = _F[sfx]
+        m = vt_max.shape[-1]
+        if vt_min.shape[-1] != m:
+            raise ValueError("get_multi_local_extrema: vt_max_out and vt_min_out share the dimension m")
+        cols = [st.scalar_in(v, n_wf, ft) for v in (d_max, d_min, a_max, a_min)]
+        pmax, rmax = st.out(vt_max, (m,) if one_d else (n_wf, m), ft)
+        pmin, rmin = st.out(vt_min, (m,) if one_d else (n_wf, m), ft)
+        pnmax, rnmax = st.out(n_max, () if one_d else (n_wf,), np.uint32)
+        pnmin, rnmin = st.out(n_min, () if one_d else (n_wf,), np.uint32)
+        run(entry("get_multi_local_extrema", sfx), g.__name__, ptr, code, n_wf, n, stride, *cols[0], *cols[1], _as_int(direction, g.__name__), *cols[2],
+            *cols[3], pmax, pmin, m, m, pnmax, pnmin)
+        st.finish()
+        return tuple(r[()] if isinstance(r, np.ndarray) and r.ndim == 0 else r for r in (rmax, rmin, rnmax, rnmin))
+    finally:
+        st.release()
+
+
 def _avg_current(g, *args):
     if len(args) != 3:
         raise TypeError("avg_current(w_in, length, w_out): w_out must be passed (len(w_in) - int(length) samples)")
@@ -425,6 +452,9 @@ def _zac_filter(g, sigma, flat, decay, kernel):
 
 windower = HipGUFunc("windower", "(n),(),(m)", ["fff", "ddd"], _windower,
                      "window of len(w_out) samples starting at int(t0_in), NaN outside the input (reference processors/windower.py:12-54)")
+get_multi_local_extrema = HipGUFunc("get_multi_local_extrema", "(n),(),(),(),(),(),(m),(m),(),()", ["ffffffffII", "ddddddddII"], _get_multi_local_extrema,
+                                    "lists of the local maxima and minima, len(vt_max_out) of each at most, NaN-padded, and their counts; search_direction 0, 1 "
+                                    "or 3 (reference processors/get_multi_local_extrema.py:12-306)")
 avg_current = HipGUFunc("avg_current", "(n),(),(m)", ["fff", "ddd"], _avg_current,
                         "(w_in[L:] - w_in[:-L]) / length (reference processors/moving_windows.py:206-249)")
 upsampler = HipGUFunc("upsampler", "(n),(),(m)", ["fff", "ddd"], _upsampler,
@@ -474,4 +504,4 @@ zac_filter = HipGUFunc("zac_filter", "(),(),(),(n)", ["ffff", "dddd"], _zac_filt
                        "zero-area CUSP kernel generator, host, once (reference processors/energy_kernels.py:76-157)")
 
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
-           "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope"]
+           "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema"]

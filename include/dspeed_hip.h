@@ -66,6 +66,9 @@ extern "C" {
 #define DSP_E_MW_NUM_INT 23    /* moving_windows.py:170-171 */
 #define DSP_E_MW_LEN_RANGE 24  /* moving_windows.py:173-174 */
 #define DSP_E_MW_NUM_NEG 25    /* moving_windows.py:176-177 */
+#define DSP_E_EXTREMA_LEN 26   /* get_multi_local_extrema.py:126-129 */
+#define DSP_E_EXTREMA_DELTA 27 /* get_multi_local_extrema.py:130-131   data dependent for a delta per event */
+#define DSP_E_EXTREMA_DIR 28   /* get_multi_local_extrema.py:305-306 */
 
 /* ---- element types -------------------------------------------------------------------------- */
 #define DSP_F32 0
@@ -218,6 +221,15 @@ typedef struct dsp_scalar_arg {
                                  * operand A = waveform slot src if src >= 0 else sp[0], B = slot ip[1] if >= 0 else sp[1], C = slot ip[2] if >= 0
                                  * else sp[2] (at least one operand is a slot; all of the length of dst); truth values are 0 / 1 in the loop type */
 #define DSP_OP_SCALAR_FUNC 33    /* the same functions between per-event values: sreg[dst] <- f(sp[0], sp[1], sp[2]); ip[0] = DSP_FN_* */
+#define DSP_OP_MULTI_EXTREMA 34   /* get_multi_local_extrema.py:12-306: the local maxima / minima of src as lists.  dst / ip[1] = the slots of vt_max_out /
+                                 * vt_min_out (both of m samples, m < len(src)), sreg[ip[2]], sreg[ip[2] + 1] <- n_max_out, n_min_out; ip[0] =
+                                 * search_direction (0, 1 or 3; 2 is refused: the reference's own branch defines nothing), sp[0..3] = a_delta_max_in,
+                                 * a_delta_min_in, a_abs_max_in, a_abs_min_in, each a constant or a per-event column of the loop's type.
+                                 * The waveform interpreter has no such op: it runs on dsp_extrema_kernel only, in a program of exactly
+                                 * LOAD, MULTI_EXTREMA, STORE of dst, STORE of ip[1], STORE_SCALAR of ip[2], STORE_SCALAR of ip[2] + 1, the
+                                 * two counts into DSP_U32 columns (the one program whose outputs have that type); search_direction 3 takes
+                                 * m <= 64.  Constant parameters are checked at chain creation whatever the rows hold (the reference lets an
+                                 * all-NaN row return ahead of its checks) */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -438,6 +450,13 @@ int dsp_dwt_haar_f32(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len,
 int dsp_convolve_wf_f32(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const float* kernel_dev,
                         int32_t kernel_len, int32_t mode_char, float* out, int32_t out_len, int64_t out_stride, void* stream,
                         int64_t* err_row);
+/* "(n),(),(),(),(),(),(m),(m),(),()": vt_max_out / vt_min_out are rows of out_len = m values out_stride apart, n_max_out / n_min_out one
+ * uint32 per waveform; search_direction is a constant of the call */
+int dsp_get_multi_local_extrema_f32(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const float* a_delta_max_dev,
+                                    float a_delta_max, const float* a_delta_min_dev, float a_delta_min, int32_t search_direction,
+                                    const float* a_abs_max_dev, float a_abs_max, const float* a_abs_min_dev, float a_abs_min, float* vt_max_out,
+                                    float* vt_min_out, int32_t out_len, int64_t out_stride, uint32_t* n_max_out, uint32_t* n_min_out, void* stream,
+                                    int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
@@ -483,6 +502,11 @@ int dsp_dwt_haar_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len,
 int dsp_convolve_wf_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* kernel_dev,
                         int32_t kernel_len, int32_t mode_char, double* out, int32_t out_len, int64_t out_stride, void* stream,
                         int64_t* err_row);
+int dsp_get_multi_local_extrema_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* a_delta_max_dev,
+                                    double a_delta_max, const double* a_delta_min_dev, double a_delta_min, int32_t search_direction,
+                                    const double* a_abs_max_dev, double a_abs_max, const double* a_abs_min_dev, double a_abs_min,
+                                    double* vt_max_out, double* vt_min_out, int32_t out_len, int64_t out_stride, uint32_t* n_max_out,
+                                    uint32_t* n_min_out, void* stream, int64_t* err_row);
 
 /* ---- synthetic batches generated on the device (bench.py) ---------------------------------
  * wf[r][i] = B_r + A_r*exp(-(i-t0_r)/tau)*[i>=t0_r] + sigma*n(r,i), counter-based hash noise;  also writes the
