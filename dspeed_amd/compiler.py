@@ -26,12 +26,14 @@ from . import _lib
 from .chain import Program, Scalar
 from .device import dtype_code
 from .errors import DSPFatal, ProcessingChainError
-from .language import (Grid, Quantity, SExpr, Var, _Builder, _GENERATORS, _MODULES, _NUMPY_BINARY, _SIGS, _column, _grid_of, _is_int_dtype, _is_scalar,
+from .language import (Grid, Quantity, SExpr, Var, _Builder, _GENERATORS, _NUMPY_BINARY, module_accepted, _SIGS, _column, _grid_of, _is_int_dtype, _is_scalar,
                        _is_wf, _resolve, _roles, _time_unit_ns, _wf_len)
 
 # processors whose output waveform has the input's dimension name in the gufunc signature ("(n),...->(n)") and therefore its
 # coordinate grid (reference :1601-1619, 1700); the others' outputs have no grid unless the recipe declares one
 _MULTI_EXTREMA = "get_multi_local_extrema"
+_HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS)  # processors that run as stages ahead of the program, on kernels of their own
 _SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi")
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
@@ -53,7 +55,7 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         else:
             b.vars[new_vars[0]] = Var(new_vars[0], "const", const=val)
         return
-    if module not in _MODULES:
+    if not module_accepted(module, function):
         raise NotImplementedError(f"module '{module}' is not available on the device path (processor {module}.{function})")
     if module in ("numpy", "np") and function == "copyto":
         # numpy.copyto(dst, src) as a processor: the copy of a (variable-length) array into a declared output (reference
@@ -684,31 +686,88 @@ def _stage_multi_extrema(cx: _Stager):
             raise ProcessingChainError(f"{fn} ({key}): declare the lists as name(length) and name the counts")
         if int(direction) == 3 and lists[0].length > 64:
             raise NotImplementedError(f"{fn} ({key}): search_direction 3 takes lists of at most 64 entries ({lists[0].length} declared)")
-        base = _base_of(src)
-        if base is None:
-            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
-        if not cx.row_input(base):
-            anc = cx.ancestors(base)
-            if not anc:
-                raise NotImplementedError(f"{fn} ({key}): its source '{base.name}' cannot be written to rows in memory")
-            cx.stage(anc, [], f"{base.name} -> HBM", wf=base, drop=[])
+        _rows_in_memory(cx, src, fn, key)
         for k in (1, 2, 4, 5):
-            a = args[k]
-            if not isinstance(a, (Var, SExpr)):
-                if isinstance(a, (tuple, Grid)) or not (_is_number(a) or isinstance(a, Quantity)):
-                    raise NotImplementedError(f"{fn} ({key}): operand {a!r} is neither a number nor a per-event value")
-                continue
-            for leaf in _leaves(a, []):  # what the program would compute off rows in HBM moves ahead of it
-                if not cx.plain_scalar(leaf) and not (leaf.kind == "scalar" and cx.move_ahead([leaf])):
-                    raise NotImplementedError(f"{fn} ({key}): operand '{a.name}' depends on '{leaf.name}', which is neither a constant, an input column, "
-                                              "a fit or stage result nor computed off rows in memory")
-            is_f32_column = isinstance(a, Var) and (getattr(a, "ext_key", None) is not None
-                                                    or np.dtype(_column(cx.b.tb_in, a.source).dtype) == np.dtype(np.float32))
-            if not is_f32_column and not (isinstance(a, SExpr) and cx.plain_scalar(a)):
-                args[k] = cx.stage_expression(a, f"{a.name} for {fn} {key}")
+            args[k] = _operand_in_memory(cx, args[k], fn, key)
         step = (fn, args, key)
         cx.steps = [step if x is st else x for x in cx.steps]
         cx.stage([step], counts, f"{fn} {key} on rows", wfs=lists, rows_first=True)
+
+
+def _operand_in_memory(cx: _Stager, a, fn, key):
+    """A per-event operand of a kernel that reads its operands as constants or float32 columns (``_stage_multi_extrema`` says which it
+    takes): returns it as the kernel's stage reads it, after moving ahead or evaluating what has to be."""
+    if not isinstance(a, (Var, SExpr)):
+        if isinstance(a, (tuple, Grid)) or not (_is_number(a) or isinstance(a, Quantity)):
+            raise NotImplementedError(f"{fn} ({key}): operand {a!r} is neither a number nor a per-event value")
+        return a
+    for leaf in _leaves(a, []):  # what the program would compute off rows in HBM moves ahead of it
+        if not cx.plain_scalar(leaf) and not (leaf.kind == "scalar" and cx.move_ahead([leaf])):
+            raise NotImplementedError(f"{fn} ({key}): operand '{a.name}' depends on '{leaf.name}', which is neither a constant, an input column, "
+                                      "a fit or stage result nor computed off rows in memory")
+    is_f32_column = isinstance(a, Var) and (getattr(a, "ext_key", None) is not None
+                                            or np.dtype(_column(cx.b.tb_in, a.source).dtype) == np.dtype(np.float32))
+    if not is_f32_column and not (isinstance(a, SExpr) and cx.plain_scalar(a)):
+        return cx.stage_expression(a, f"{a.name} for {fn} {key}")
+    return a
+
+
+def _rows_in_memory(cx: _Stager, src, fn, key):
+    """the source of a kernel that reads rows in HBM: a chain input or a stage's waveform as it is, anything else written there first"""
+    base = _base_of(src)
+    if base is None:
+        raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+    if not cx.row_input(base):
+        anc = cx.ancestors(base)
+        if not anc:
+            raise NotImplementedError(f"{fn} ({key}): its source '{base.name}' cannot be written to rows in memory")
+        cx.stage(anc, [], f"{base.name} -> HBM", wf=base, drop=[])
+
+
+def _stage_histogram(cx: _Stager):
+    """``histogram`` and ``histogram_stats`` run on dsp_hist.hip and nowhere else, on rows in HBM: mandatory stages, like the peak finder's.
+    A ``histogram_stats`` that reads exactly a histogram's weights and borders joins its launch; weights and borders are then written only
+    if something else reads them or the recipe asks for them.  Any other ``histogram_stats`` reads weights and edges as rows in memory."""
+    for st in list(cx.steps):
+        if st[0] != _HISTOGRAM or not cx.has(st):
+            continue
+        args, key = list(st[1]), st[2]
+        weights, borders = args[1:3]
+        if not all(isinstance(v, Var) and v.kind == "wf" and v.length for v in (weights, borders)):
+            raise ProcessingChainError(f"{_HISTOGRAM} ({key}): declare the outputs as name(length): weights(bins), borders(bins + 1)")
+        if borders.length != weights.length + 1:
+            raise DSPFatal("length borders_out must be exactly 1 + length of weights_out")
+        if weights.length > _lib.HIST_MAX_BINS:
+            raise NotImplementedError(f"{_HISTOGRAM} ({key}): at most {_lib.HIST_MAX_BINS} bins ({weights.length} declared)")
+        _rows_in_memory(cx, args[0], _HISTOGRAM, key)
+        stats = next((x for x in cx.steps if x[0] == _HISTOGRAM_STATS and x[1][0] is weights and x[1][1] is borders), None)
+        group, scalars = [st], []
+        if stats is not None:
+            sargs = list(stats[1])
+            sargs[5] = _operand_in_memory(cx, sargs[5], _HISTOGRAM_STATS, stats[2])
+            fused = (_HISTOGRAM_STATS, sargs, stats[2])
+            cx.steps = [fused if x is stats else x for x in cx.steps]
+            group, scalars = [st, fused], sargs[2:5]
+            if not all(isinstance(v, Var) for v in scalars):
+                raise ProcessingChainError(f"{_HISTOGRAM_STATS} ({stats[2]}): name the three outputs")
+        rows_wanted = any(v.name in cx.out_names or [u for u in cx.users_of(v) if not any(u is g for g in group)] for v in (weights, borders))
+        cx.stage(group, scalars, f"{_HISTOGRAM} {key}" + (f" + {_HISTOGRAM_STATS} {stats[2]} in one launch" if stats is not None else "") + " on rows",
+                 wfs=[weights, borders] if rows_wanted or stats is None else [], rows_first=True)
+    for st in list(cx.steps):
+        if st[0] != _HISTOGRAM_STATS or not cx.has(st):
+            continue
+        args, key = list(st[1]), st[2]
+        for a in args[:2]:
+            if not (isinstance(a, Var) and a.kind == "wf" and a.length):
+                raise ProcessingChainError(f"{_HISTOGRAM_STATS} ({key}): weights_in and edges_in are whole arrays of a declared length")
+        if args[1].length != args[0].length + 1:
+            raise DSPFatal("length edges_in must be exactly 1 + length of weights_in")
+        for a in args[:2]:
+            _rows_in_memory(cx, a, _HISTOGRAM_STATS, key)
+        args[5] = _operand_in_memory(cx, args[5], _HISTOGRAM_STATS, key)
+        step = (_HISTOGRAM_STATS, args, key)
+        cx.steps = [step if x is st else x for x in cx.steps]
+        cx.stage([step], args[2:5], f"{_HISTOGRAM_STATS} {key} on rows")
 
 
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
@@ -726,12 +785,13 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     cx = _Stager(b, steps, out_pars, n_rows, ft)
     _stage_long_firs(cx)
     fir_staged = bool(cx.stages)
-    has_peaks = any(st[0] == _MULTI_EXTREMA for st in cx.steps)
+    has_peaks = any(st[0] in _OWN_KERNEL for st in cx.steps)
     if not cx.stages and not has_peaks:
         return cx.steps, cx.stages
     if fir_staged:  # (the optional families follow the long filters, as before; the peak finder's stage is made with or without them)
         _stage_short_traps(cx)
         _stage_current_branch(cx)
+    _stage_histogram(cx)  # (ahead of the peak finder: its thresholds may be arithmetic of these results, "3*fwhm")
     _stage_multi_extrema(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and getattr(v, "ext_key", None) is not None and getattr(v, "aux_io", None) is None}
@@ -1318,6 +1378,25 @@ class _Emitter:
         self.p.add_op(_lib.OP_MULTI_EXTREMA, dst=vt_max.slot, src=src.slot, ip=(direction, vt_min.slot, first), sp=sp)
         self.release(src, si)
 
+    def histogram(self, si, fn, args, what):
+        """LOAD, HISTOGRAM of the histogram's stage; a fused histogram_stats and the stores follow"""
+        src = self.ensure_loaded(args[0], si)
+        weights, borders = self.out_wf(args[1], None, fn), self.out_wf(args[2], None, fn)
+        weights.slot, borders.slot = self.new_slot(weights.length), self.new_slot(borders.length)
+        self.p.add_op(_lib.OP_HISTOGRAM, dst=weights.slot, src=src.slot, ip=(borders.slot,))
+        self.release(src, si)
+
+    def histogram_stats(self, si, fn, args, what):
+        """HISTOGRAM_STATS on the slots of a histogram in the same program, or on weights and edges loaded from rows in memory"""
+        weights, edges = self.ensure_loaded(args[0], si), self.ensure_loaded(args[1], si)
+        max_in = self.scalar_operand(args[5], args, what=what)
+        first = self.p.add_sregs(3)
+        for k, a in enumerate(args[2:5]):
+            if not isinstance(a, Var):
+                raise ProcessingChainError(f"{what}: mode_out, max_out and fwhm_out must be variable names")
+            a.kind, a.sreg = "scalar", first + k
+        self.p.add_op(_lib.OP_HISTOGRAM_STATS, src=weights.slot, ip=(edges.slot, first), sp=(max_in,))
+
     def copy_slice(self, si, fn, args, what):
         src = self.ensure_loaded(args[0], si)
         dst = args[3]
@@ -1494,7 +1573,8 @@ _READ_OFF = {
 _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OPS, _Emitter.trapezoid), **dict.fromkeys(_WINDOW_OPS, _Emitter.window),
          "slice": _Emitter.copy_slice, "min_max": _Emitter.four_values, "linear_slope_fit": _Emitter.four_values,
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
-         "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema}
+         "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
+         _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats}
 
 
 def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
@@ -1616,11 +1696,13 @@ def _compile(b: _Builder, out_pars, n_rows, proc_strings, stage_mode=False):
             if isinstance(vl, Var) and not vl.is_input and vl.name not in out_pars and b.vars.get(vl.name) is vl:
                 out_pars.append(vl.name)
                 hidden.append(vl.name)
-        if any(st[0] == _MULTI_EXTREMA for st in steps):
+        for own in _OWN_KERNEL:
+            if not any(st[0] == own for st in steps):
+                continue
             if off("DSPEED_HIP_NO_STAGES"):
-                raise NotImplementedError(f"{_MULTI_EXTREMA} runs as a stage ahead of the program, on a kernel of its own: not with DSPEED_HIP_NO_STAGES=1")
+                raise NotImplementedError(f"{own} runs as a stage ahead of the program, on a kernel of its own: not with DSPEED_HIP_NO_STAGES=1")
             if ft != np.dtype(np.float32):
-                raise NotImplementedError(f"{_MULTI_EXTREMA} in a recipe whose loop type is {ft}: the stages ahead of the program hand on float32 rows")
+                raise NotImplementedError(f"{own} in a recipe whose loop type is {ft}: the stages ahead of the program hand on float32 rows")
     island, island_out = _int_island(b, steps, out_pars, ft) if main else (None, {})
     aux, stages = [], []
     if main and not off("DSPEED_HIP_FIT_IN_CHAIN"):

@@ -361,7 +361,7 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     HIP_TRY(hipMalloc((void**)&ch->dev_err, DSP_ERR_WORDS * sizeof(int)));
     HIP_TRY(hipMemset(ch->dev_err, 0, DSP_ERR_WORDS * sizeof(int)));
     const int block_lds = ch->lds_bytes_per_wave * ch->waves_per_block, classic_lds = ch->lds_bytes_per_wave * ch->classic_wpb;
-    int rc = raise_lds(!ch->ext_ok, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
+    int rc = raise_lds(!ch->ext_ok && !ch->hist_ok, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
     if (!rc) rc = raise_lds(ch->fused_ok, classic_lds, 64 * 1024, "energy kernel, %d", [&](int n) { return dsp_internal_set_energy_lds(ch->fused_trap, ch->fused_npf, n); });
     if (!rc) rc = raise_lds(ch->fir_f16, dsp_fir_f16::lds_bytes(), 64 * 1024, "float16 FIR kernel", dsp_internal_set_fir_f16_lds);
     if (!rc) rc = raise_lds(ch->fir_ok, ch->fir_lds_bytes, 64 * 1024, "FIR kernel, %d", ch->fir.store ? dsp_internal_set_fir_store_lds : dsp_internal_set_fir_mfma_lds);
@@ -383,6 +383,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // the 16-byte alignment its wide loads need (the plan vouches for strides and offsets, nobody for the pointers).  dsp_chain_execute asks
 // in the order of dsp_plan_route; a launch whose planned route does not apply runs on the next that does.
 static bool extrema_applies(const dsp_chain* ch, void* const*) { return ch->ext_ok; }  // (always: the program runs nowhere else; unaligned rows: its scalar loads)
+static bool hist_applies(const dsp_chain* ch, void* const*) { return ch->hist_ok; }        // (likewise)
 static bool scalar_applies(const dsp_chain* ch, void* const*) { return ch->scalar_ok && ch->fused_on; }
 static bool pz_rows_applies(const dsp_chain* ch, void* const* io_ptrs) {
     return ch->pz_ok && ch->fused_on && aligned16(io_ptrs[ch->pio_wf]) && aligned16(io_at(ch, io_ptrs, ch->pio_out));
@@ -549,6 +550,22 @@ static int launch_extrema(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, voi
     const int vec = ch->ext_vec && aligned16(A.wf);
     hipError_t e = (hipError_t)dsp_internal_launch_extrema(&A, n_wf, ch->ext_dtype, vec, ch->dev_err, (hipStream_t)stream);
     return launched(ch, stream, e, "extrema kernel launch");
+}
+
+static int launch_hist(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    HistArgs A = ch->hist;
+    auto raw = [&](int k) -> void* { return k < 0 ? nullptr : io_ptrs[k]; };  // (the inputs' offsets travel in the arguments)
+    A.wf = raw(ch->hio_wf);
+    A.w_in = raw(ch->hio_w_in);
+    A.e_in = raw(ch->hio_e_in);
+    A.w_out = at(ch->hio_w);
+    A.b_out = at(ch->hio_b);
+    A.max_in = at(ch->hio_max_in);
+    for (int k = 0; k < 3; ++k) A.s_out[k] = at(ch->hio_s[k]);
+    const int vec = ch->hist_vec && aligned16(A.wf);
+    hipError_t e = (hipError_t)dsp_internal_launch_hist(&A, n_wf, ch->hist_dtype, vec, ch->dev_err, (hipStream_t)stream);
+    return launched(ch, stream, e, "histogram kernel launch");
 }
 
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
@@ -734,6 +751,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     (void)hipGetLastError();  // launch checks below report this launch, not a stale error of an unrelated earlier call
     // the first kernel, in the order of dsp_plan_route, that takes this launch's pointers
     if (extrema_applies(ch, io_ptrs)) return launch_extrema(ch, io_ptrs, n_wf, stream);
+    if (hist_applies(ch, io_ptrs)) return launch_hist(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -825,6 +843,7 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
         case DSP_ROUTE_SCALAR:
             lds = ch->host.n_sregs * 64 * ((ch->f64 || ch->i64) ? 8 : 4), wpb = 1, b = (int)((n_wf + 63) / 64);
             break;
+        case DSP_ROUTE_HIST: lds = dsp_hist::lds_bytes(ch->hist.m) / 4, wpb = 4, b = (int)((n_wf + 3) / 4); break;
         case DSP_ROUTE_EXTREMA:
         case DSP_ROUTE_PZ_ROWS:
         case DSP_ROUTE_REDUCE: lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4); break;
@@ -1227,6 +1246,40 @@ int g_multi_extrema(int ty, const WfIn& in, const void* const* cols, const doubl
     return m.run(in.n_wf, st, er);
 }
 
+int g_histogram(int ty, const WfIn& in, void* weights, int32_t n_bins, int64_t w_stride, void* borders, int32_t borders_len, int64_t b_stride, void* st,
+                int64_t* er) {
+    if (in.n_wf <= 0) return DSP_OK;
+    if (n_bins <= 0 || borders_len <= 0) return dsp_fail(DSP_ERR_ARG, "histogram: weights_out and borders_out hold at least one value");
+    Mini m(ty);
+    const int s_in = m.add_slot(in.len), s_w = m.add_slot(n_bins), s_b = m.add_slot(borders_len);
+    m.add_op(DSP_OP_LOAD, s_in, 0, m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr));
+    m.add_op(DSP_OP_HISTOGRAM, s_w, s_in, 0).ip[0] = s_b;
+    m.add_op(DSP_OP_STORE, 0, s_w, m.add_io(DSP_IO_WF_OUT, ty, n_bins, w_stride, weights));
+    m.add_op(DSP_OP_STORE, 0, s_b, m.add_io(DSP_IO_WF_OUT, ty, borders_len, b_stride, borders));
+    return m.run(in.n_wf, st, er);
+}
+
+int g_histogram_stats(int ty, const void* weights, int64_t n_wf, int32_t n_bins, int64_t w_stride, const void* edges, int32_t edges_len, int64_t e_stride,
+                      const void* max_in_dev, double max_in, void* mode_out, void* max_out, void* fwhm_out, void* st, int64_t* er) {
+    if (n_wf <= 0) return DSP_OK;
+    if (n_bins <= 0 || edges_len <= 0) return dsp_fail(DSP_ERR_ARG, "histogram_stats: weights_in and edges_in hold at least one value");
+    Mini m(ty);
+    m.n_sregs = 3;
+    const int s_w = m.add_slot(n_bins), s_e = m.add_slot(edges_len);
+    m.add_op(DSP_OP_LOAD, s_w, 0, m.add_io(DSP_IO_WF_IN, ty, n_bins, w_stride, weights));
+    m.add_op(DSP_OP_LOAD, s_e, 0, m.add_io(DSP_IO_WF_IN, ty, edges_len, e_stride, edges));
+    const dsp_scalar_arg mi = m.scalar(max_in_dev, max_in);
+    {
+        dsp_op& o = m.add_op(DSP_OP_HISTOGRAM_STATS, 0, s_w, 0);
+        o.ip[0] = s_e;
+        o.ip[1] = 0;
+        o.sp[0] = mi;
+    }
+    void* outs[3] = {mode_out, max_out, fwhm_out};
+    for (int k = 0; k < 3; ++k) m.add_op(DSP_OP_STORE_SCALAR, 0, 0, m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, outs[k])).ip[0] = k;
+    return m.run(n_wf, st, er);
+}
+
 }  // namespace
 
 #define DSP_GUFUNCS(SFX, TY, FT)                                                                                                             \
@@ -1342,6 +1395,18 @@ int g_multi_extrema(int ty, const WfIn& in, const void* const* cols, const doubl
         const double consts[4] = {(double)a_delta_max, (double)a_delta_min, (double)a_abs_max, (double)a_abs_min};                           \
         return g_multi_extrema(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, cols, consts, search_direction, vt_max_out, vt_min_out,      \
                                out_len, out_stride, n_max_out, n_min_out, stream, err_row);                                                  \
+    }                                                                                                                                        \
+    int dsp_histogram_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT* weights_out, int32_t n_bins,  \
+                            int64_t weights_stride, FT* borders_out, int32_t borders_len, int64_t borders_stride, void* stream,              \
+                            int64_t* err_row) {                                                                                              \
+        return g_histogram(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, weights_out, n_bins, weights_stride, borders_out, borders_len,   \
+                           borders_stride, stream, err_row);                                                                                 \
+    }                                                                                                                                        \
+    int dsp_histogram_stats_##SFX(const FT* weights_in, int64_t n_wf, int32_t n_bins, int64_t weights_stride, const FT* edges_in,            \
+                                  int32_t edges_len, int64_t edges_stride, const FT* max_in_dev, FT max_in, FT* mode_out, FT* max_out,       \
+                                  FT* fwhm_out, void* stream, int64_t* err_row) {                                                            \
+        return g_histogram_stats(TY, weights_in, n_wf, n_bins, weights_stride, edges_in, edges_len, edges_stride, max_in_dev,                \
+                                 (double)max_in, mode_out, max_out, fwhm_out, stream, err_row);                                              \
     }
 
 DSP_GUFUNCS(f32, DSP_F32, float)

@@ -34,6 +34,8 @@ int dsp_internal_launch_pz_rows(const PzArgs* A, int64_t n_wf, int* err, hipStre
 int dsp_internal_launch_reduce(const ReduceArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_extrema.hip (dtype: the rows'; vec: rows start on 16-byte boundaries and hold whole 16-byte vectors)
 int dsp_internal_launch_extrema(const ExtremaArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+// dsp_hist.hip (A->wf null: histogram_stats alone, dtype then the loop's type; LDS: dsp_hist::lds_bytes(A->m), below the 64 KiB that need no opt-in)
+int dsp_internal_launch_hist(const HistArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_scalar.hip (type: 0 float32, 1 float64, 2 int64 registers)
 int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);
 int dsp_internal_set_scalar_lds(int lds_bytes);

@@ -71,6 +71,8 @@ extern "C" const char* dsp_fatal_message(int code) {
         case DSP_E_EXTREMA_LEN: return "The length of your return array must be smaller than the length of your waveform";
         case DSP_E_EXTREMA_DELTA: return "Delta must be positive";
         case DSP_E_EXTREMA_DIR: return "search direction type not found.";
+        case DSP_E_HIST_LEN: return "length borders_out must be exactly 1 + length of weights_out";
+        case DSP_E_HIST_STATS_LEN: return "length edges_in must be exactly 1 + length of weights_in";
         default: return "";
     }
 }
@@ -101,6 +103,7 @@ struct PlanCtx {
     ChainPlan* ch;
     bool f64 = false, i64 = false;
     bool has_extrema = false;  // a MULTI_EXTREMA among the ops: its counts are the one kind of DSP_U32 output
+    bool has_hist = false;     // a HISTOGRAM or HISTOGRAM_STATS among the ops
     int esz = 4;  // bytes of an LDS element
     // FIR inputs (laid out without the chunk pad); slots that share their LDS region with another
     bool linear[DSP_MAX_SLOTS] = {false}, shares[DSP_MAX_SLOTS] = {false};
@@ -402,6 +405,100 @@ static bool match_extrema_shape(const PlanCtx& c, const char** why) {
     ch->ext_dtype = w.dtype;
     ch->ext_vec = (w.row_stride * es) % 16 == 0 && ((int64_t)w.offset * es) % 16 == 0 && ((int64_t)w.len * es) % 16 == 0;
     ch->xio_wf = ld.io;
+    return true;
+}
+
+// Is the program one of the histogram kernel's (dsp_hist.hip)?
+//   LOAD s;  HISTOGRAM of s;  STORE of its weights and of its borders
+//   LOAD s;  HISTOGRAM of s;  HISTOGRAM_STATS of its two slots;  [STORE, STORE;]  STORE_SCALAR of the three registers
+//   LOAD weights;  LOAD edges;  HISTOGRAM_STATS of them;  STORE_SCALAR of the three registers
+// max_in is a constant or a column of the loop's type.  Why not, otherwise: `why` (a program that holds either op runs nowhere else).
+static bool match_hist_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int n = c.n_ops;
+    *why = "the program must be exactly LOAD, HISTOGRAM, STORE, STORE; or LOAD, HISTOGRAM, HISTOGRAM_STATS, [STORE, STORE,] STORE_SCALAR x 3; or "
+           "LOAD, LOAD, HISTOGRAM_STATS, STORE_SCALAR x 3";
+    auto is = [&](int i, int opcode) { return i < n && ops[i].opcode == opcode; };
+    const bool alone = n == 6 && is(0, DSP_OP_LOAD) && is(1, DSP_OP_LOAD) && is(2, DSP_OP_HISTOGRAM_STATS);
+    const bool hist = n >= 4 && is(0, DSP_OP_LOAD) && is(1, DSP_OP_HISTOGRAM);
+    const bool fused = hist && is(2, DSP_OP_HISTOGRAM_STATS);
+    if (!alone && !hist) return false;
+    const int n_stores = alone ? 0 : (fused ? n - 6 : 2), first_store = fused ? 3 : 2, first_scalar = alone ? 3 : first_store + n_stores;
+    if (c.n_slots != (alone ? 2 : 3) || (n_stores != 0 && n_stores != 2) || n != first_scalar + ((alone || fused) ? 3 : 0)) return false;
+    for (int i = first_store; i < first_store + n_stores; ++i)
+        if (!is(i, DSP_OP_STORE)) return false;
+    for (int i = first_scalar; i < n; ++i)
+        if (!is(i, DSP_OP_STORE_SCALAR)) return false;
+    HistArgs& A = ch->hist;
+    memset(&A, 0, sizeof A);
+    ch->hio_wf = ch->hio_w = ch->hio_b = ch->hio_w_in = ch->hio_e_in = ch->hio_max_in = -1;
+    for (int k = 0; k < 3; ++k) ch->hio_s[k] = -1;
+    const dsp_op* st = nullptr;
+    if (alone) {
+        st = &ops[2];
+        const dsp_op* lw = ops[0].dst == st->src ? &ops[0] : (ops[1].dst == st->src ? &ops[1] : nullptr);
+        const dsp_op* le = ops[0].dst == st->ip[0] ? &ops[0] : (ops[1].dst == st->ip[0] ? &ops[1] : nullptr);
+        if (!lw || !le || lw == le) return false;
+        *why = "histogram_stats alone reads weights and edges as rows of the loop's type";
+        for (const dsp_op* l : {lw, le})
+            if (l->ip[0] != 0 || l->ip[1] != 0 || io[l->io].dtype != c.compute_dtype) return false;
+        ch->hio_w_in = lw->io;
+        ch->hio_e_in = le->io;
+        A.w_in_stride = io[lw->io].row_stride;
+        A.w_in_offset = io[lw->io].offset;
+        A.e_in_stride = io[le->io].row_stride;
+        A.e_in_offset = io[le->io].offset;
+        A.m = c.slot_len[st->src];
+        ch->hist_dtype = c.compute_dtype;
+    } else {
+        const dsp_op &ld = ops[0], &hi = ops[1];
+        const dsp_io_desc& w = io[ld.io];
+        if (hi.src != ld.dst || ld.ip[0] != 0 || ld.ip[1] != 0 || w.len != c.slot_len[ld.dst]) return false;
+        *why = "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows";
+        if (c.f64 ? w.dtype != DSP_F64 : (w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16)) return false;
+        *why = "histogram_stats in the same program reads exactly the histogram's weights and borders";
+        if (fused) {
+            st = &ops[2];
+            if (st->src != hi.dst || st->ip[0] != hi.ip[0]) return false;
+        }
+        *why = "the weights and the borders are stored once each";
+        for (int i = first_store; i < first_store + n_stores; ++i) {
+            int& slot = ops[i].src == hi.dst ? ch->hio_w : ch->hio_b;
+            if ((ops[i].src != hi.dst && ops[i].src != hi.ip[0]) || slot >= 0) return false;
+            slot = ops[i].io;
+            (ops[i].src == hi.dst ? A.w_stride : A.b_stride) = io[ops[i].io].row_stride;
+        }
+        A.wf_stride = w.row_stride;
+        A.wf_offset = w.offset;
+        A.len = w.len;
+        A.m = c.slot_len[hi.dst];
+        A.max_blocks = hi.ip[1];
+        const int es = elem_size(w.dtype);
+        ch->hist_dtype = w.dtype;
+        ch->hist_vec = (w.row_stride * es) % 16 == 0 && ((int64_t)w.offset * es) % 16 == 0 && ((int64_t)w.len * es) % 16 == 0;
+        ch->hio_wf = ld.io;
+    }
+    if (st) {
+        *why = "mode_out, max_out and fwhm_out are stored once each, in the loop's type";
+        for (int i = first_scalar; i < n; ++i) {
+            const int which = ops[i].ip[0] - st->ip[1];
+            if (which < 0 || which > 2 || ch->hio_s[which] >= 0 || io[ops[i].io].dtype != c.compute_dtype) return false;
+            ch->hio_s[which] = ops[i].io;
+            A.s_stride[which] = io[ops[i].io].row_stride;
+        }
+        *why = "max_in is a constant or a per-event column of the loop's type";
+        if (st->sp[0].kind == DSP_ARG_INPUT && io[st->sp[0].index].dtype == c.compute_dtype) {
+            ch->hio_max_in = st->sp[0].index;
+            A.max_in_stride = io[st->sp[0].index].row_stride;
+        } else if (st->sp[0].kind == DSP_ARG_CONST) {
+            A.max_in_const = op_const(c, *st, 0);
+        } else {
+            return false;
+        }
+        A.stats = 1;
+    }
     return true;
 }
 
@@ -934,6 +1031,8 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
         case DSP_OP_DWT_HAAR: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[2]; return 3;
         case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
+        case DSP_OP_HISTOGRAM: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[0]; return 3;
+        case DSP_OP_HISTOGRAM_STATS: out[0] = o.src; out[1] = o.ip[0]; return 2;
         case DSP_OP_MOVING_WINDOW_MULTI:
             out[0] = o.src;
             out[1] = o.dst;
@@ -981,6 +1080,7 @@ static int check_call(PlanCtx& c) {
     c.ch->f64 = c.f64;
     c.ch->i64 = c.i64;
     for (int i = 0; i < n_ops; ++i) c.has_extrema |= c.ops[i].opcode == DSP_OP_MULTI_EXTREMA;
+    for (int i = 0; i < n_ops; ++i) c.has_hist |= c.ops[i].opcode == DSP_OP_HISTOGRAM || c.ops[i].opcode == DSP_OP_HISTOGRAM_STATS;
     return DSP_OK;
 }
 
@@ -1102,7 +1202,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.has_extrema)  // (MULTI_EXTREMA: its only kernel streams the row through registers, nothing lives in LDS)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.has_extrema && !c.has_hist)  // (MULTI_EXTREMA, HISTOGRAM: their kernels stream the row through registers, no row lives in LDS)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1437,6 +1537,25 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
             if (o.ip[0] == 3 && slot_len[o.dst] > DSP_EXTREMA_UNION_MAX)
                 return fail(DSP_ERR_UNSUPPORTED, "get_multi_local_extrema: search_direction 3 takes lists of at most %d entries (%d asked for)", DSP_EXTREMA_UNION_MAX,
                             slot_len[o.dst]);
+            break;
+        }
+        case DSP_OP_HISTOGRAM: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || !check_slot(P, o.ip[0]) || o.dst == o.src || o.ip[0] == o.src || o.dst == o.ip[0])
+                return fail(DSP_ERR_ARG, "op %d: bad HISTOGRAM (dst: the slot of the weights, ip[0]: the slot of the borders)", i);
+            if (o.ip[1] < 0) return fail(DSP_ERR_ARG, "op %d: HISTOGRAM ip[1] (the most workgroups the rows are dealt out to, 0: no cap of the program's) is negative", i);
+            if (slot_len[o.ip[0]] != slot_len[o.dst] + 1) return fail(DSP_E_HIST_LEN, "%s", dsp_fatal_message(DSP_E_HIST_LEN));
+            if (slot_len[o.dst] > DSP_HIST_MAX_BINS)
+                return fail(DSP_ERR_UNSUPPORTED, "histogram: at most %d bins (%d asked for): a wavefront keeps a counter per bin in LDS", DSP_HIST_MAX_BINS, slot_len[o.dst]);
+            if (!f64 && slot_len[o.src] > (1 << 24))
+                return fail(DSP_ERR_UNSUPPORTED, "histogram: the float32 loop takes rows of at most 2^24 samples (%d): a weight counts them exactly", slot_len[o.src]);
+            break;
+        }
+        case DSP_OP_HISTOGRAM_STATS: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.ip[0]) || o.src == o.ip[0] || o.ip[1] < 0 || o.ip[1] > n_sregs - 3)
+                return fail(DSP_ERR_ARG, "op %d: bad HISTOGRAM_STATS (src, ip[0]: the slots of weights and edges; ip[1]: three registers for mode, max, fwhm)", i);
+            if (slot_len[o.ip[0]] != slot_len[o.src] + 1) return fail(DSP_E_HIST_STATS_LEN, "%s", dsp_fatal_message(DSP_E_HIST_STATS_LEN));
+            if (slot_len[o.src] > DSP_HIST_MAX_BINS)
+                return fail(DSP_ERR_UNSUPPORTED, "histogram_stats: at most %d bins (%d given)", DSP_HIST_MAX_BINS, slot_len[o.src]);
             break;
         }
         case DSP_OP_DWT_HAAR: {
@@ -1969,6 +2088,12 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
         if (!ch->ext_ok)
             return fail(DSP_ERR_UNSUPPORTED, "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only, on rows in memory: %s", why);
     }
+    if (c.has_hist) {  // nor behind these two
+        const char* why = "";
+        ch->hist_ok = match_hist_shape(c, &why);
+        if (!ch->hist_ok)
+            return fail(DSP_ERR_UNSUPPORTED, "DSP_OP_HISTOGRAM / DSP_OP_HISTOGRAM_STATS (histogram, histogram_stats) run on dsp_hist_kernel only, on rows in memory: %s", why);
+    }
     match_shapes(c);
     fold_scaled_thresholds(c);
     form_teams(c);
@@ -1979,6 +2104,7 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
 
 dsp_route dsp_plan_route(const ChainPlan* ch) {
     if (ch && ch->ext_ok) return DSP_ROUTE_EXTREMA;  // (whatever the switches say: the interpreter has no such op)
+    if (ch && ch->hist_ok) return DSP_ROUTE_HIST;
     if (!ch || !ch->fused_on) return DSP_ROUTE_VM;
     if (ch->scalar_ok) return DSP_ROUTE_SCALAR;
     if (ch->pz_ok) return DSP_ROUTE_PZ_ROWS;

@@ -86,6 +86,10 @@ struct ChainPlan {
     bool ext_ok = false, ext_vec = false;
     ExtremaArgs ext{};
     int xio_wf = -1, xio_par[4] = {-1, -1, -1, -1}, xio_vt[2] = {-1, -1}, xio_n[2] = {-1, -1}, ext_dtype = DSP_F32;
+    // histogram and histogram_stats (dsp_hist.hip): the one kernel a program with HISTOGRAM or HISTOGRAM_STATS runs on
+    bool hist_ok = false, hist_vec = false;
+    HistArgs hist{};
+    int hio_wf = -1, hio_w = -1, hio_b = -1, hio_w_in = -1, hio_e_in = -1, hio_max_in = -1, hio_s[3] = {-1, -1, -1}, hist_dtype = DSP_F32;
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};

@@ -279,6 +279,34 @@ struct ExtremaArgs {
     int64_t n_stride[2];
 };
 
+// arguments of the histogram kernel (dsp_hist.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> HISTOGRAM -> STORE, STORE
+//   LOAD -> HISTOGRAM -> HISTOGRAM_STATS [-> STORE, STORE] -> STORE_SCALAR x 3
+//   LOAD, LOAD -> HISTOGRAM_STATS -> STORE_SCALAR x 3          (weights and edges read from memory)
+// A wavefront keeps a uint32 counter per bin in its own LDS region, four regions to a workgroup: 2048 bins are 32 KiB a workgroup, five
+// workgroups (20 wavefronts, five per SIMD) in a CU's 160 KiB; 100 bins leave the register file as the only bound.
+#define DSP_HIST_MAX_BINS 2048
+struct HistArgs {
+    const void* wf;          // histogram: float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop); null: stats alone
+    int64_t wf_stride;
+    int32_t wf_offset, len;
+    int32_t m;               // bins: len(weights); the borders are m + 1
+    int32_t stats;           // histogram_stats runs on the counters (fused) or on w_in / e_in (alone)
+    int32_t max_blocks;      // histogram: rows are dealt out to at most this many workgroups (0: up to 8192)
+    void* w_out;             // weights_out rows, or null: not stored
+    void* b_out;             // borders_out rows, or null
+    int64_t w_stride, b_stride;
+    const void* w_in;        // stats alone: weights_in / edges_in rows of the loop's type
+    const void* e_in;
+    int64_t w_in_stride, e_in_stride;
+    int32_t w_in_offset, e_in_offset;
+    const void* max_in;      // a column of the loop's type, or null: max_in_const
+    int64_t max_in_stride;
+    double max_in_const;
+    void* s_out[3];          // mode_out, max_out, fwhm_out
+    int64_t s_stride[3];
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

@@ -148,6 +148,7 @@ _SIGS = {
     "discrete_wavelet_transform": "wiccW", "convolve_wf": "wtcW", "fft_convolve_wf": "wtcW", "amax": "wiS",
     "mean_below_threshold": "wsS", "windower": "wsW", "avg_current": "wsW", "trap_pickoff": "wiisS",
     "upsampler": "wsW", "moving_window_multi": "wsiiW", "numpy_subtract": "wsW", "numpy_add": "wsW", "min_max_norm": "wssW", "linear_slope_fit": "wSSSS",
+    "histogram": "wWW", "histogram_stats": "wwSSSs",  # (w_in, weights_out, borders_out); (weights_in, edges_in, mode_out, max_out, fwhm_out, max_in)
     "get_multi_local_extrema": "wssissWWSS",  # (w_in, a_delta_max_in, a_delta_min_in, search_direction, a_abs_max_in, a_abs_min_in, two lists, two counts)
 }
 _SIGS.update({"sample": "wiS", "slice": "wiiW", "get": "wsS"})  # wf[i], wf[lo:hi:step], wf[variable] (reference :948-1071)
@@ -220,6 +221,28 @@ _WHERE_LOOPS = "BHILbhiq"  # processors/where.py:11-20: u1 u2 u4 u8 i1 i2 i4 i8 
 
 _GENERATORS = ("cusp_filter", "zac_filter", "t0_filter", "moving_slope")
 _MODULES = ("dspeed.processors", "dspeed_amd.processors", "numpy", "np")
+# ``dspeed.processors.<file>``: the reference file that defines each processor of the registry (recipes name either the package or the file;
+# histogram_stats is also written as living in histogram)
+_PROCESSOR_FILES = {
+    "bl_subtract": ("bl_subtract",), "pole_zero": ("pole_zero",), "double_pole_zero": ("pole_zero",), "trap_filter": ("trap_filters",),
+    "trap_norm": ("trap_filters",), "asym_trap_filter": ("trap_filters",), "trap_pickoff": ("trap_filters",), "fixed_time_pickoff": ("fixed_time_pickoff",),
+    "time_point_thresh": ("time_point_thresh",), "interpolated_time_point_thresh": ("time_point_thresh",), "min_max": ("min_max",),
+    "min_max_norm": ("min_max",), "linear_slope_fit": ("linear_slope_fit",), "mean_below_threshold": ("arithmetic",), "windower": ("windower",),
+    "avg_current": ("moving_windows",), "moving_window_multi": ("moving_windows",), "upsampler": ("upsampler",), "discrete_wavelet_transform": ("dwt",),
+    "convolve_wf": ("convolutions",), "fft_convolve_wf": ("convolutions",), "cusp_filter": ("energy_kernels",), "zac_filter": ("energy_kernels",),
+    "t0_filter": ("kernels",), "moving_slope": ("kernels",), "get_multi_local_extrema": ("get_multi_local_extrema",), "histogram": ("histogram",),
+    "histogram_stats": ("histogram_stats", "histogram"),
+}
+
+
+def module_accepted(module, function) -> bool:
+    """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
+    if module in _MODULES:
+        return True
+    pre = "dspeed.processors."
+    return isinstance(module, str) and module.startswith(pre) and module[len(pre):] in _PROCESSOR_FILES.get(function, ())
+
+
 _NUMPY_BINARY = {"add": ast.Add, "subtract": ast.Sub, "multiply": ast.Mult, "divide": ast.Div, "true_divide": ast.Div}
 _ROUND_MODES = {"round": 1, "floor": 2, "ceil": 3, "trunc": 4}
 

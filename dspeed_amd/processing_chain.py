@@ -17,7 +17,8 @@ What is kept from the reference (so existing LEGEND recipes for the energy chain
 * units and coordinate grids (:67-144, :1556-1732, :1806-1908): a waveform has a grid (period, offset) -- the input's from
   ``WaveformInput(values, dt, t0)`` --, a processor works on the grid of its first waveform argument, per-event variables with a
   time unit are sample indices on that grid, converted when another grid reads them and written in their unit;
-* the literal module string ``dspeed.processors`` (and ``numpy`` for ``amax`` / ``add``) resolves to this package's registry.
+* the literal module string ``dspeed.processors``, or ``dspeed.processors.<file>`` for the reference file that defines the processor
+  (and ``numpy`` for ``amax`` / ``add``), resolves to this package's registry.
 
 What is different by design: instead of calling one gufunc per processor per 16-row block, the resolved processor
 list is translated into ONE device program (``dsp_chain_create``) that keeps every intermediate waveform in LDS, and

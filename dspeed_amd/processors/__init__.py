@@ -287,6 +287,51 @@ def _get_multi_local_extrema(g, *args):
         st.release()
 
 
+def _histogram(g, *args):
+    if len(args) != 3:
+        raise TypeError("histogram(w_in, weights_out, borders_out): both outputs must be passed (len(weights_out) is the number of bins)")
+    w_in, weights, borders = args
+    st = Staging()
+    try:
+        ptr, code, n_wf, n, stride, one_d = st.wf_in(w_in)
+        sfx = loop_suffix(_dtype_of(w_in))
+        if sfx == "f64" and np.dtype(_dtype_of(w_in)) != np.dtype(np.float64):
+            raise NotImplementedError("histogram: the float64 loop takes float64 rows on the device")
+        ft = _F[sfx]
+        m, p = weights.shape[-1], borders.shape[-1]
+        pw, rw = st.out(weights, (m,) if one_d else (n_wf, m), ft)
+        pb, rb = st.out(borders, (p,) if one_d else (n_wf, p), ft)
+        run(entry("histogram", sfx), g.__name__, ptr, code, n_wf, n, stride, pw, m, m, pb, p, p)
+        st.finish()
+        return rw, rb
+    finally:
+        st.release()
+
+
+def _histogram_stats(g, *args):
+    if len(args) != 6:
+        raise TypeError("histogram_stats(weights_in, edges_in, mode_out, max_out, fwhm_out, max_in): the three outputs stand in the middle, "
+                        "as in the reference; pass None to have them allocated")
+    weights, edges, mode_out, max_out, fwhm_out, max_in = args
+    st = Staging()
+    try:
+        if np.dtype(_dtype_of(weights)) not in (np.dtype(np.float32), np.dtype(np.float64)) or _dtype_of(edges) != _dtype_of(weights):
+            raise TypeError("histogram_stats: weights_in and edges_in are float32 (the float32 loop) or float64 rows of one type")
+        sfx = "f32" if np.dtype(_dtype_of(weights)) == np.dtype(np.float32) else "f64"
+        ft = _F[sfx]
+        pw, _, n_wf, m, w_stride, one_d = st.wf_in(weights)
+        pe, _, n_e, p, e_stride, _ = st.wf_in(edges)
+        if n_e != n_wf:
+            raise ValueError("histogram_stats: weights_in and edges_in hold the same number of rows")
+        col = st.scalar_in(max_in, n_wf, ft)
+        outs = [st.out(o, () if one_d else (n_wf,), ft) for o in (mode_out, max_out, fwhm_out)]
+        run(entry("histogram_stats", sfx), g.__name__, pw, n_wf, m, w_stride, pe, p, e_stride, *col, *[o[0] for o in outs])
+        st.finish()
+        return tuple(r[()] if isinstance(r, np.ndarray) and r.ndim == 0 else r for _, r in outs)
+    finally:
+        st.release()
+
+
 def _avg_current(g, *args):
     if len(args) != 3:
         raise TypeError("avg_current(w_in, length, w_out): w_out must be passed (len(w_in) - int(length) samples)")
@@ -455,6 +500,12 @@ windower = HipGUFunc("windower", "(n),(),(m)", ["fff", "ddd"], _windower,
 get_multi_local_extrema = HipGUFunc("get_multi_local_extrema", "(n),(),(),(),(),(),(m),(m),(),()", ["ffffffffII", "ddddddddII"], _get_multi_local_extrema,
                                     "lists of the local maxima and minima, len(vt_max_out) of each at most, NaN-padded, and their counts; search_direction 0, 1 "
                                     "or 3 (reference processors/get_multi_local_extrema.py:12-306)")
+histogram = HipGUFunc("histogram", "(n),(m),(p)", ["fff", "ddd"], _histogram,
+                      "histogram of the row between its extremes: len(weights_out) bins, len(weights_out) + 1 borders; the maximum is not counted "
+                      "(reference processors/histogram.py:14-89)")
+histogram_stats = HipGUFunc("histogram_stats", "(n),(m),(),(),(),()", ["ffffff", "dddddd"], _histogram_stats,
+                            "index and left edge of a histogram's mode (or of the edge nearest max_in) and the half width at half maximum "
+                            "(reference processors/histogram_stats.py:157-261)")
 avg_current = HipGUFunc("avg_current", "(n),(),(m)", ["fff", "ddd"], _avg_current,
                         "(w_in[L:] - w_in[:-L]) / length (reference processors/moving_windows.py:206-249)")
 upsampler = HipGUFunc("upsampler", "(n),(),(m)", ["fff", "ddd"], _upsampler,
@@ -504,4 +555,4 @@ zac_filter = HipGUFunc("zac_filter", "(),(),(),(n)", ["ffff", "dddd"], _zac_filt
                        "zero-area CUSP kernel generator, host, once (reference processors/energy_kernels.py:76-157)")
 
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
-           "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema"]
+           "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats"]

@@ -69,6 +69,8 @@ extern "C" {
 #define DSP_E_EXTREMA_LEN 26   /* get_multi_local_extrema.py:126-129 */
 #define DSP_E_EXTREMA_DELTA 27 /* get_multi_local_extrema.py:130-131   data dependent for a delta per event */
 #define DSP_E_EXTREMA_DIR 28   /* get_multi_local_extrema.py:305-306 */
+#define DSP_E_HIST_LEN 29      /* histogram.py:61-62 */
+#define DSP_E_HIST_STATS_LEN 30 /* histogram_stats.py:227-228 */
 
 /* ---- element types -------------------------------------------------------------------------- */
 #define DSP_F32 0
@@ -230,6 +232,19 @@ typedef struct dsp_scalar_arg {
                                  * two counts into DSP_U32 columns (the one program whose outputs have that type); search_direction 3 takes
                                  * m <= 64.  Constant parameters are checked at chain creation whatever the rows hold (the reference lets an
                                  * all-NaN row return ahead of its checks) */
+#define DSP_OP_HISTOGRAM 35       /* histogram.py:14-89: the histogram of src between its own extremes.  dst = the slot of weights_out (m samples, m <=
+                                 * 2048), ip[0] = the slot of borders_out (m + 1 samples), ip[1] = the most workgroups the rows are
+                                 * dealt out to (four rows at a time each; 0: as many as the rows need, up to 8192).  Float32 / int16 / uint16 rows of at most 2^24 samples
+                                 * in the float32 loop, float64 rows in the float64 loop.  A sample whose bin index reaches m is dropped (the
+                                 * reference stores past the end there); an infinite sample makes the row a NaN row */
+#define DSP_OP_HISTOGRAM_STATS 36 /* histogram_stats.py:157-261 on the weights in slot src and the edges in slot ip[0] (one sample more):
+                                 * sreg[ip[1]], sreg[ip[1] + 1], sreg[ip[1] + 2] <- mode_out, max_out, fwhm_out; sp[0] = max_in, a constant or a
+                                 * per-event column of the loop's type.
+                                 * The waveform interpreter has neither op: they run on dsp_hist_kernel only, in a program of exactly
+                                 *   LOAD, HISTOGRAM, STORE of dst, STORE of ip[0]
+                                 *   LOAD, HISTOGRAM, HISTOGRAM_STATS of its two slots, [STORE, STORE,] STORE_SCALAR x 3   (one launch; without
+                                 *                                                           the STOREs no weight or border is written)
+                                 *   LOAD weights, LOAD edges, HISTOGRAM_STATS, STORE_SCALAR x 3   (rows of the loop's type in memory) */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -457,6 +472,14 @@ int dsp_get_multi_local_extrema_f32(const void* in, int in_dtype, int64_t n_wf, 
                                     const float* a_abs_max_dev, float a_abs_max, const float* a_abs_min_dev, float a_abs_min, float* vt_max_out,
                                     float* vt_min_out, int32_t out_len, int64_t out_stride, uint32_t* n_max_out, uint32_t* n_min_out, void* stream,
                                     int64_t* err_row);
+/* "(n),(m),(p)": weights_out rows of n_bins values weights_stride apart, borders_out rows of n_bins + 1 values borders_stride apart
+ * (borders_len is checked against n_bins + 1 as the reference checks it) */
+int dsp_histogram_f32(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, float* weights_out, int32_t n_bins,
+                      int64_t weights_stride, float* borders_out, int32_t borders_len, int64_t borders_stride, void* stream, int64_t* err_row);
+/* "(n),(m),(),(),(),()": weights_in / edges_in rows of the loop's type on the device; mode_out, max_out, fwhm_out one value per row */
+int dsp_histogram_stats_f32(const float* weights_in, int64_t n_wf, int32_t n_bins, int64_t weights_stride, const float* edges_in,
+                            int32_t edges_len, int64_t edges_stride, const float* max_in_dev, float max_in, float* mode_out, float* max_out,
+                            float* fwhm_out, void* stream, int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
@@ -507,6 +530,11 @@ int dsp_get_multi_local_extrema_f64(const void* in, int in_dtype, int64_t n_wf, 
                                     const double* a_abs_max_dev, double a_abs_max, const double* a_abs_min_dev, double a_abs_min,
                                     double* vt_max_out, double* vt_min_out, int32_t out_len, int64_t out_stride, uint32_t* n_max_out,
                                     uint32_t* n_min_out, void* stream, int64_t* err_row);
+int dsp_histogram_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, double* weights_out, int32_t n_bins,
+                      int64_t weights_stride, double* borders_out, int32_t borders_len, int64_t borders_stride, void* stream, int64_t* err_row);
+int dsp_histogram_stats_f64(const double* weights_in, int64_t n_wf, int32_t n_bins, int64_t weights_stride, const double* edges_in,
+                            int32_t edges_len, int64_t edges_stride, const double* max_in_dev, double max_in, double* mode_out,
+                            double* max_out, double* fwhm_out, void* stream, int64_t* err_row);
 
 /* ---- synthetic batches generated on the device (bench.py) ---------------------------------
  * wf[r][i] = B_r + A_r*exp(-(i-t0_r)/tau)*[i>=t0_r] + sigma*n(r,i), counter-based hash noise;  also writes the
