@@ -428,7 +428,7 @@ def test_stage_buffers_are_bounded_and_pieces_give_the_same_results():
     chain.execute()
     ref = {k: np.array(v) for k, v in out.items()}
     per_row = sum(4 * (1 if ln is None else ln) for st in chain._stages for _o, _k, ln in st["outs"])
-    chain.stage_bytes = 40 * per_row  # -> 4 pieces of 38 rows
+    chain.stage_bytes = 40 * per_row  # -> pieces of at most 38 rows: host-resident rows start and end with short ones, [9, 19, 38, 38, 27, 19]
     for v in out.values():
         v[...] = 0
     chain.execute()

@@ -479,6 +479,54 @@ def test_host_buffers_stream_through_in_overlapped_pieces():
     assert ei.value.wf_range == range(777, 778)
 
 
+_PICKOFF_AT_INTEGERS = {"outputs": ["e"], "processors": {
+    "wf_t": "dspeed.processors.trap_filter(waveform, 100, 10, wf_t)",
+    "e": "dspeed.processors.fixed_time_pickoff(wf_t, t_pick, 'i', e)"}}
+
+
+def _rows_with_integer_pickoffs(n=1000):
+    x, _bl, t0 = _synth(np.random.default_rng(15), n, 4096)
+    return x.astype(np.float32), np.floor(t0 + 625 + 150.4).astype(np.float32)
+
+
+def test_a_chain_runs_again_after_a_failed_pass_over_pieces():
+    """what the cleanup of a failed pass leaves behind: with the bad row mended in the linked column the same chain runs, raises nothing and
+    gives a fresh chain's output bit for bit (no error word, transfer or kernel of the abandoned pieces meets the next pass)"""
+    from dspeed_amd.errors import DSPFatal
+    from dspeed_amd.processing_chain import build_processing_chain
+
+    wf, tpi = _rows_with_integer_pickoffs()
+    good = tpi[777]
+    tpi[777] += 0.5
+    tb = {"waveform": wf, "t_pick": tpi}
+    ci, _, out = build_processing_chain(_PICKOFF_AT_INTEGERS, tb)
+    ci.pipeline_bytes = 100 * 4096 * 4
+    with pytest.raises(DSPFatal) as ei:
+        ci.execute()
+    assert ei.value.wf_range == range(777, 778)
+    tpi[777] = good
+    out["e"][:] = 0
+    ci.execute()
+    fresh, _, want = build_processing_chain(_PICKOFF_AT_INTEGERS, tb)
+    fresh.execute()
+    assert np.array_equal(out["e"], want["e"], equal_nan=True) and np.isfinite(want["e"]).all()
+
+
+def test_the_first_bad_row_in_table_order_is_the_one_reported():
+    """two bad rows in different pieces: the pieces are finished in order, so the DSPFatal names the earlier row"""
+    from dspeed_amd.errors import DSPFatal
+    from dspeed_amd.processing_chain import build_processing_chain
+
+    wf, tpi = _rows_with_integer_pickoffs()
+    tpi[777] += 0.5
+    tpi[123] += 0.5
+    ci, _, _ = build_processing_chain(_PICKOFF_AT_INTEGERS, {"waveform": wf, "t_pick": tpi})
+    ci.pipeline_bytes = 100 * 4096 * 4
+    with pytest.raises(DSPFatal) as ei:
+        ci.execute()
+    assert ei.value.wf_range == range(123, 124)
+
+
 def test_fatal_from_recipe_carries_processor_context():
     from dspeed_amd.errors import DSPFatal
     from dspeed_amd.processing_chain import build_processing_chain

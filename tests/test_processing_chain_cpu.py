@@ -159,6 +159,51 @@ def test_shard_rows_partitions_the_event_axis():
             assert max(sizes) - min(sizes) <= 1
 
 
+@pytest.mark.parametrize("args,piece,sizes", [
+    ((1000, 4, 400), 100, [25, 50] + [100] * 8 + [75, 50]),
+    ((1042, 4, 400), 100, [25, 50] + [100] * 9 + [67]),
+    ((1100, 4, 400), 100, [25, 50] + [100] * 9 + [75, 50]),
+    ((1000, 16388, 1638400), 99, [24, 49] + [99] * 8 + [86, 49]),
+    ((150, 0, 1, 33000, 40 * 33000), 38, [38, 38, 38, 36]),           # device-resident rows: equal pieces under the stages' bound
+    ((150, 8196, 256 << 20, 33000, 40 * 33000), 38, [9, 19, 38, 38, 27, 19]),  # the same rows in host memory: with the ramp
+    ((9, 4, 12), 3, [3, 3, 3]),
+    ((8, 4, 12), 3, [3, 3, 2]),
+    ((7, 4, 16), 4, [4, 3]),
+    ((1, 4, 1), 1, [1]),
+])
+def test_piece_sizes_of_a_batch(args, piece, sizes):
+    """(n, row_bytes, pipeline_bytes[, stage_row_bytes, stage_bytes]) -> rows of a full piece, rows of every piece: the values the runtime
+    computed before the sizing became a function of its own"""
+    from dspeed_amd.processing_chain import _piece_sizes
+
+    assert _piece_sizes(*args) == (piece, sizes)
+
+
+def test_piece_sizes_cover_the_batch_with_pieces_of_bounded_length():
+    from dspeed_amd.processing_chain import _piece_sizes
+
+    for n in range(1, 400):
+        for rows in range(1, 60):
+            piece, sizes = _piece_sizes(n, 4, 4 * rows)
+            assert piece == min(n, rows) and sum(sizes) == n and min(sizes) > 0 and max(sizes) <= piece + piece // 2, (n, rows, sizes)
+
+
+def test_stage_plan_keeps_every_reader_behind_what_it_reads():
+    """the plan of the stages on side streams (ProcessingChain.concurrent_stages) is a function of the stage records alone: what the GPU test
+    of the side streams asserts of it, without a device"""
+    rng = np.random.default_rng(17)
+    tb = {"waveform": WaveformInput(rng.integers(9000, 11000, (8, 8192)).astype(np.uint16), 16.0, 48000.0), "baseline": np.full(8, 1e4, np.float32)}
+    chain, _, _ = build_processing_chain(recipes.ICPC, tb)
+    plan = chain._stage_plan()
+    assert chain._chain is None and chain._lanes == []  # (nothing was created on a device)
+    assert plan["n_side"] >= 2 and all(i < j for j, d in enumerate(plan["deps"]) for i in d)
+    what = [st["what"] for st in chain._stages]
+    pzs, t0f = what.index("wf_pz -> HBM + min_max of waveform"), what.index("convolve_wf wf_t0_filter on prefix sums + per-event values of wf_t0_filter")
+    assert pzs in plan["deps"][t0f] and t0f in plan["deps"][what.index("asym_trap_filter wf_atrap on rows")]
+    assert plan["stream_of"][what.index("fft_convolve_wf wf_cusp")] != plan["stream_of"][t0f]
+    assert chain._stage_plan() is plan
+
+
 def test_t0_and_slope_kernel_generators_match_the_reference_fixtures():
     """host-side generators (reference processors/kernels.py:12-98), bit for bit against fixtures made from the reference bodies"""
     from golden_util import cases
