@@ -352,10 +352,15 @@ __global__ void __launch_bounds__(256, 2) dsp_energy_kernel(EnergyArgs A, int64_
 //     does not convert again (KD below).  The sample in front of a lane's chunk comes from the lane below by DPP, not from LDS;
 //     the replay's group-start states are stored by the 4-point build alone, which is the one that reads them; lanes whose lagged
 //     window lies wholly below sample 0 read the guard at addresses of their own banks.  Figures: profiles/r07_headline_trims.md.
-//   * what must be picked out at a run-time position is never tested per sample: the float32 prefix sum at each 8-sample
-//     group end and the replay state at each group start go to a 9-entry per-lane LDS side array (a run-time group number is
-//     then an address); the two trapezoid samples every pick-off mode needs are copied out of a 16-sample register window
-//     by one uniform branch per 16 samples (a not-taken branch costs tens of cycles; 32 of them cost more than they saved).
+//   * what must be picked out at a run-time position is never tested per sample, and where the position is wave-uniform and the
+//     values are the lane's own registers it does not go through LDS either: the float32 prefix sums at the 8-sample group ends are a
+//     register vector that the carries index (s_set_gpr_idx_on, one v_mov_b32); the two trapezoid samples every pick-off mode needs
+//     are indexed out of a 16-sample register window under one uniform branch per 16 samples (a not-taken branch costs tens of
+//     cycles; 32 of them cost more than they saved), by every lane -- the tail's readlane names the owner.  The replay state at each
+//     group start goes to a 9-entry per-lane LDS side array in the 4-point build, which re-runs a group from it (a run-time group
+//     number is then an address for the samples too).  The carries' capture groups are still read from LDS: xr is 66 registers, an
+//     indexed move reaches 32, and two uniform branches and eight indexed moves a lag cost more than the 12 pipelined reads
+//     they replace (built and measured: 3 % slower).  Figures: profiles/r10_headline_register_picks.md.
 //   * the LDS array serves a ds_read_b64 in 2 cycles and a ds_read2_b32 -- the same 8 bytes a lane -- in 4, and the array was busy
 //     two thirds of the kernel's time.  So the lane pitch is even, C = len/64 + 2: every lane's chunk starts 8-byte aligned, the
 //     chunk is NG = (C - 2) / 8 groups of 8 samples and a two-sample tail (the tail extends the last replay chain; where the
@@ -371,8 +376,8 @@ __global__ void __launch_bounds__(256, 2) dsp_energy_kernel(EnergyArgs A, int64_
 //     4 bytes at a run-time position and needs no parity case.  Figures: profiles/r05_headline_lds.md.
 //   * a wavefront issues at most one instruction per four cycles and the kernel's two wavefronts per SIMD saturate no pipe: outside the
 //     sample passes every instruction, scalar ones included, costs its four cycles, a branch tens.  So what a row does not need to work
-//     out is not worked out per row.  The carries take their plan from the host as it is used (EnergyPlan: pair address, side-array
-//     element, count; a capture in group 0 reads a word that holds 0.0f instead of selecting), held as lane addresses and one packed
+//     out is not worked out per row.  The carries take their plan from the host as it is used (EnergyPlan: pair address, side
+//     element, count; a capture in group 0 picks an element that holds 0.0f instead of selecting), held as lane addresses and one packed
 //     scalar across the row loop, and sum "the first pn of 8 samples" as all eight running prefixes and one indexed register move
 //     (s_set_gpr_idx_on with the wave-uniform pn) instead of eight masked additions.  The pick-off mode is a build of the kernel
 //     (WIDE): the two-point modes n f c l i end in straight-line selects, and only the build for the 4-point mode h holds the two
@@ -404,9 +409,11 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
     float* slot = lds + A.slot_off;
     float* mine = slot + lane * C;
     f2* mine2 = reinterpret_cast<f2*>(mine);  // (the wave's region, slot_off and lane * C are all even numbers of elements)
-    // per-lane side array (pitch 9, odd): group-end prefix sums of pass 2, later the group-start states of the replay.  Kept in
-    // LDS so that "the value of group gi" with a run-time gi is an address, not a register select chain
-    // (9 for up to 4096 samples, 17 for 8192).  The region's layout is the planner's, which sizes it and sets slot_off: dsp_kernels.h
+    // per-lane side array (pitch 9, odd): the group-start states of the replay, which the 4-point build alone stores and reads.  Kept in
+    // LDS so that "the state of group gi" with a run-time gi is an address, and its eight-sample re-run reads samples at one too
+    // (9 for up to 4096 samples, 17 for 8192).  The group-end prefix sums of pass 2 lived here once; they stay in registers now, and so do
+    // the two pick-off samples, whose 2 x 16-float capture buffer above the side arrays is still part of the layout, unused.
+    // The region's layout is the planner's, which sizes it and sets slot_off: dsp_kernels.h
     constexpr int AUXP = dsp_energy_rr::layout(C).side_pitch, GUARD = dsp_energy_rr::layout(C).guard, TAIL = dsp_energy_rr::layout(C).tail;
     static_assert(NG + 1 <= AUXP && S * NGS + 1 <= AUXP && (AUXP & 1) == 1, "side array too small");
     static_assert(GUARD >= 2 * C + 8 && GUARD >= C + 64 + dsp_energy_rr::WINDOW_SPAN_EXTRA && dsp_energy_rr::layout(C).slot_off >= GUARD,
@@ -424,25 +431,24 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
         lagpar[k] = A.q[k] & 1;                           // q[] carries the lags
         lagb[k] = slot + dsp_energy_rr::lag_window_start(C, GUARD, lane, A.q[k]);
     }
-    // the carry plan as addresses of this lane (row-invariant): the capture group's pairs and the side-array element in front of it.  A
-    // capture in group 0 has nothing in front: it reads the first word above the image, which nothing ever writes (0.0f since the clear)
+    // the carry plan (row-invariant): the capture group's pairs as an address of this lane ...
     const f2* capp[3][S];
-    const float* sidep[3][S];
 #pragma unroll
     for (int k = 0; k < 3; ++k)
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-            capp[k][s] = mine2 + (PL.grp[k][s] >> 1);
-            sidep[k][s] = PL.side[k][s] >= 0 ? aux + PL.side[k][s] : slot + 64 * C;
-        }
-    // ... and the three counts pn of a sub-chain in one scalar, opaque to the optimiser: it is then one live register, not three words
-    // of the kernel's arguments loaded again in every row (the kernel is at its scalar-register limit)
+        for (int s = 0; s < S; ++s) capp[k][s] = mine2 + (PL.grp[k][s] >> 1);
+    // ... and the three counts pn of a sub-chain and the three group-end sums in front of the capture groups in one scalar, opaque to the
+    // optimiser: it is then one live register, not six words of the kernel's arguments loaded again in every row (the kernel is at its
+    // scalar-register limit).  Bits 4 k .. 4 k + 3: pn of lag k; bits 12 + 5 k .. 16 + 5 k: 1 + the plan's side element, 0 = a capture in
+    // group 0, nothing in front (element 0 of pass 2's vector of group-end sums holds 0.0f)
     float zero = 0.0f;  // P[0] of the prefixes, as a register (a constant element makes the compiler fill the vector from scalars first)
     asm volatile("" : "+v"(zero));
+    static_assert(NG + 1 <= 32, "a side element and its + 1 fit 5 bits");
     int pnpack[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-        pnpack[s] = PL.pn[0][s] | (PL.pn[1][s] << 4) | (PL.pn[2][s] << 8);
+        pnpack[s] = PL.pn[0][s] | (PL.pn[1][s] << 4) | (PL.pn[2][s] << 8) | ((PL.side[0][s] + 1) << 12) | ((PL.side[1][s] + 1) << 17) |
+                    ((PL.side[2][s] + 1) << 22);
         asm volatile("" : "+s"(pnpack[s]));
     }
 
@@ -582,6 +588,11 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
             const double c = c_row;
             double xp = (double)xprev, acc = E - c * (E - xp);
             float run = 0.0f;
+            // the float32 prefix sum at every group end stays in registers, element 1 + group; element 0: nothing in front.  The carries
+            // pick three of them at the plan's wave-uniform positions by indexed register moves
+            typedef float fside __attribute__((ext_vector_type(NG + 1)));
+            fside gend;
+            gend[0] = zero;
 #pragma unroll
             for (int t = 0; t < C; ++t) {
                 if ((t & 7) == 0) __builtin_amdgcn_sched_barrier(0);
@@ -598,7 +609,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 }
                 xp = x;
                 run += y;
-                if ((t & 7) == 7) aux[t >> 3] = run;
+                if ((t & 7) == 7) gend[(t >> 3) + 1] = run;
             }
             wave_sync();
             if constexpr (LATE) {
@@ -626,7 +637,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                     float pbase[3], pv[3][8];
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
-                        pbase[k] = *sidep[k][s];
+                        pbase[k] = gend[(pnpack[s] >> (12 + 5 * k)) & 31];
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {  // (reads at most 6 past the chunk: inside the slot tail)
                             const f2 v = capp[k][s][u];
@@ -648,7 +659,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                         const float part = P[(pnpack[s] >> (4 * k)) & 15];
                         Ak[k] = wave_shift_up(Ep + (double)(pbase[k] + part), PL.shift[k][s]);
                     }
-                    const double own = Ep + (s ? (double)aux[s * NGS - 1] : 0.0);
+                    const double own = Ep + (s ? (double)gend[s * NGS] : 0.0);
                     double Gd;
                     if (KIND == TRAP_FILTER)
                         Gd = ((own - Ak[0]) - Ak[1]) + Ak[2];
@@ -663,10 +674,9 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
         RR_PRIO_AT(3)
                 // ---- pass 3: replay; own samples from registers, the three lagged streams software-pipelined PD stages of GL = 4 samples ahead
                 // Only the 4-point mode reads the replay's state at the group starts (its two 8-sample re-runs): that build writes them into
-                // aux, behind the carries' reads of the prefix sums there.  The two-point build writes nothing into aux in the replay and
-                // needs no ordering point here: the replay's lagged reads of other lanes' pass-2 output are behind the wave_sync() that
-                // closes pass 2, and its capture-buffer stores are behind the last row's capture reads by the wave_sync() that ends a row.
-                if constexpr (WIDE) wave_sync();
+                // aux, which nothing else uses (the carries take pass 2's prefix sums from registers); the last row's re-runs read aux in
+                // front of the wave_sync() that ends a row.  No build needs an ordering point here: the replay's lagged reads of other
+                // lanes' pass-2 output are behind the wave_sync() that closes pass 2, and the pick-off samples it catches stay in registers.
                 // the two samples every pick-off mode needs (floor and ceil of the time point) are caught on the fly: stage numbers
                 const int i0 = (int)t_in;
                 int capst[2], capoff[2], caplane[2];
@@ -682,7 +692,13 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 int capmask = (capst[0] >= 0 ? 1 << capst[0] : 0) | (capst[1] >= 0 ? 1 << capst[1] : 0);
                 const bool ok1 = capst[1] >= 0;  // (sample i0 itself always exists here: 0 <= t_in <= len - 1)
                 asm volatile("" : "+s"(capmask));  // one live scalar, not a recomputation at each test
-                float* capbuf = slot + 64 * C + TAIL + 64 * AUXP;  // 2 x 16 floats per wavefront, written by the lane that owns the sample
+                // ... and every lane keeps element capoff % BS of its own window of that block: a wave-uniform index, one indexed register move;
+                // the tail's readlane at caplane[] then names the lane that owns the sample (no lane test, no trip through LDS)
+                typedef float fbs __attribute__((ext_vector_type(BS)));
+                // (readfirstlane: where the compiler had moved the index arithmetic to the vector unit -- the 2048-sample build -- it indexed
+                // with sixteen compares and selects a pick instead)
+                const int capidx[2] = {__builtin_amdgcn_readfirstlane(capoff[0] % BS), __builtin_amdgcn_readfirstlane(capoff[1] % BS)};
+                float capv[2] = {0.0f, 0.0f};
                 float ytail[2];  // the replay's output at the two samples of the tail
                 // The lagged streams are read as aligned 8-byte pairs.  With the parity par[k] of lag k a compile-time constant, "element
                 // t + par[k] of the pair sequence" names a register in this straight-line code: one copy of the replay per parity case,
@@ -697,7 +713,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                     constexpr int NPS = CS / 2 + 2;      // pairs a sub-chain can need: CS / 2, one more for an odd lag, one more for the tail
                     f2 lp[3][S][NPS];
                     const f2* lagb2[3] = {reinterpret_cast<const f2*>(lagb[0]), reinterpret_cast<const f2*>(lagb[1]), reinterpret_cast<const f2*>(lagb[2])};
-                    float ysb[S][BS];
+                    fbs ysb[S];
                     // stage st of sub-chain s consumes elements 4 st + par .. 4 st + 3 + par: an odd lag's stage ends in the first half of the
                     // pair after it, so its loads are the pairs [rr_pair_lo(st), rr_pair_lo(st + 1)) -- two per stage and stream either way, the
                     // first stage one more, stage NL (the tail, last sub-chain only) the one pair that is left
@@ -743,10 +759,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                                 if (capmask & (1 << q)) {  // uniform, taken at most twice per waveform
 #pragma unroll
                                     for (int k = 0; k < 2; ++k)
-                                        if (capst[k] == q && lane == caplane[k]) {
-#pragma unroll
-                                            for (int u = 0; u < BS; ++u) capbuf[k * 16 + u] = ysb[s][u];
-                                        }
+                                        if (capst[k] == q) capv[k] = ysb[s][capidx[k]];
                                 }
                             }
                         }
@@ -799,7 +812,7 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
                 float w4[4];
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    float v = capbuf[k * 16 + (capoff[k] % BS)];  // (stale when the sample is in the tail or out of range: not used then)
+                    float v = capv[k];  // (0.0f when the sample is in the tail or out of range: not used then)
                     v = capoff[k] >= C - 2 ? (capoff[k] == C - 2 ? ytail[0] : ytail[1]) : v;
                     double delta = T0 - (double)g[0];
 #pragma unroll
@@ -865,6 +878,8 @@ __global__ void __launch_bounds__(256, NPF >= 32 ? 1 : 2) dsp_energy_rr_kernel(E
         if (LATE && !fetched) fetch_next();  // a NaN row: it did not reach the prefetch behind pass 2
         pend_result = result;
         pend_row = row;
+        // keeps the next row's staging stores (and, in the 4-point build, its replay's stores into aux) behind this row's lagged reads and
+        // re-runs: all it orders since the pick-off samples stay in registers.  (dsp_wave.h: a fence for the compiler)
         wave_sync();
         PHASE(5)
         RR_PRIO_AT(5)

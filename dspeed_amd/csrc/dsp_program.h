@@ -123,7 +123,7 @@ struct EnergyArgs {
 
 // Carry plan of the register-resident energy kernel's pad-free layout (C = len/64 + 2 samples per lane, sample i at LDS element i): for lag
 // k and replay sub-chain s the speculative carry needs the float32 prefix sum of the first r samples of the chunk of the lane `shift` below.
-// The prefix is the side array's group-end sum in front of the 8-sample group that holds sample r - 1, plus the first pn samples of that
+// The prefix is pass 2's group-end sum in front of the 8-sample group that holds sample r - 1, plus the first pn samples of that
 // group.  Row-invariant, built by the planner (dsp_internal_plan_energy_carries in dsp_plan.cpp, which the CPU can test) in the form the
 // kernel uses as it stands.
 struct EnergyPlan {       // [lag][replay sub-chain]
@@ -131,7 +131,7 @@ struct EnergyPlan {       // [lag][replay sub-chain]
     int32_t cs[3][4];     // sub-chain that holds the capture point, and ...
     int32_t local[3][4];  // ... the samples of it in front of the point (the plan as the planner's checks read it; the kernel uses the form below)
     int32_t grp[3][4];    // element offset, from the start of the lane's chunk, of the group's four pairs (8 * group; group NG: the two-sample tail)
-    int32_t side[3][4];   // element of the lane's side array that holds the sum of the groups in front, -1: none (group 0), read a word that holds 0.0f
+    int32_t side[3][4];   // group whose end sum is the sum of the groups in front (the kernel keeps the group-end sums in registers), -1: none (group 0), 0.0f
     int32_t pn[3][4];     // samples of the group in front of the capture point, 0 .. 8
 };
 
