@@ -33,7 +33,8 @@ from .language import (Grid, Quantity, SExpr, Var, _Builder, _GENERATORS, _NUMPY
 # coordinate grid (reference :1601-1619, 1700); the others' outputs have no grid unless the recipe declares one
 _MULTI_EXTREMA = "get_multi_local_extrema"
 _HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS)  # processors that run as stages ahead of the program, on kernels of their own
+_MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER)  # processors that run as stages ahead of the program, on kernels of their own
 _SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi")
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
@@ -137,6 +138,16 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         for a in args[8:10]:
             if isinstance(a, Var):
                 a.out_dtype = np.dtype(np.uint32)
+    if function == _MULTI_TPT:
+        # its thresholds are one constant list, or a list per event read from rows in memory; its times are sample indices of the input:
+        # with a time unit they are coordinates on its grid, written in that unit like the peak finder's lists
+        args[1] = _as_threshold_list(b, args[1], key)
+        t_out = args[5]
+        if isinstance(t_out, Var) and t_out.kind == "wf":
+            if t_out.length is None:
+                t_out.length = _wf_len(args[1]) if _is_wf(args[1]) else args[1].length
+            if _time_unit_ns(t_out.unit) is not None and _grid_of(args[0]) is not None:
+                t_out.is_coord, t_out.grid = True, _grid_of(args[0])
     args = [_as_taps(b, a, function) if r == "t" else a for a, r in zip(args, roles)]
     args = [_group_constant(b, a, function, key) if r == "i" and isinstance(a, (Var, SExpr)) else a for a, r in zip(args, roles)]
     _, args = _resolve(b, roles, args, same_dim_out=function in _SAME_DIM)
@@ -185,6 +196,27 @@ def _as_taps(b: _Builder, a, function):
     b._anon += 1
     name = a.name if isinstance(a, Var) else f"kernel#{b._anon}"
     return Var(name, "taps", int(arr.size), np.float32, const=np.ascontiguousarray(arr, dtype=np.float32))
+
+
+def _as_threshold_list(b: _Builder, a, key):
+    """The thresholds of ``multi_time_point_thresh``: a constant array (a list literal, a database array, loadlh5(...), or a recipe entry
+    holding one) becomes one list for every row, in the loop's float32; a two-dimensional input column or a stage's waveform stays what it
+    is: a list per event, in memory.  (The reference hands a float64 list to the float64 loop of the gufunc: here the list is cast.)"""
+    fn = _MULTI_TPT
+    arr = a.const if isinstance(a, Var) and a.kind in ("const", "taps") and isinstance(a.const, np.ndarray) else a
+    if isinstance(arr, np.ndarray):
+        if arr.ndim != 1 or arr.size < 1 or arr.dtype.kind not in "fiu":
+            raise ProcessingChainError(f"{fn} ({key}): the thresholds are a one-dimensional array of numbers, not {arr.dtype.name} of shape {arr.shape}")
+        if arr.size > _lib.THRESH_MAX:
+            raise NotImplementedError(f"{fn} ({key}): at most {_lib.THRESH_MAX} thresholds ({arr.size} given): a wavefront keeps one per lane")
+        b._anon += 1
+        name = a.name if isinstance(a, Var) else f"thresholds#{b._anon}"
+        return Var(name, "taps", int(arr.size), np.float32, const=np.ascontiguousarray(arr, dtype=np.float32))
+    if _is_wf(a):
+        if _wf_len(a) > _lib.THRESH_MAX:
+            raise NotImplementedError(f"{fn} ({key}): at most {_lib.THRESH_MAX} thresholds ({_wf_len(a)} given): a wavefront keeps one per lane")
+        return a
+    raise ProcessingChainError(f"{fn} ({key}): the thresholds are a constant array or an array per event, not {a!r}")
 
 
 def _fold_generator(b: _Builder, function, args, new_vars):
@@ -770,6 +802,69 @@ def _stage_histogram(cx: _Stager):
         cx.stage([step], args[2:5], f"{_HISTOGRAM_STATS} {key} on rows")
 
 
+def _operand_written_first(cx: _Stager, a, fn, key):
+    """``_operand_in_memory`` for the threshold kernel's operands, with one more source: a per-event value that the program would read off a
+    waveform it computes itself (the maximum of the baseline-subtracted waveform, for a threshold at half of it) is written to HBM first,
+    with the other results of its processor, by a small program of its own -- as a source waveform is."""
+    if isinstance(a, (Var, SExpr)):
+        for leaf in _leaves(a, []):
+            pst = cx.producer_of(leaf) if isinstance(leaf, Var) and leaf.kind == "scalar" and not cx.plain_scalar(leaf) else None
+            if pst is None or any(isinstance(x, Var) and cx.row_input(x) for x in _inputs_of(pst)):
+                continue  # (in memory already, or read off rows in memory: ``move_ahead`` takes it)
+            outs = _outputs_of(pst)
+            if all(isinstance(o, Var) and o.kind == "scalar" for o in outs):
+                cx.stage(cx.ancestors(leaf), outs, f"{leaf.name} -> HBM", drop=[])
+    return _operand_in_memory(cx, a, fn, key)
+
+
+def _stage_thresholds(cx: _Stager):
+    """``multi_time_point_thresh`` and ``time_over_threshold`` run on dsp_thresh.hip and nowhere else, on rows in HBM: mandatory stages, like
+    the peak finder's.  Polarity and mode are constants, checked here for every row; t_start and time_over_threshold's threshold are
+    per-event operands (``_operand_in_memory``); the thresholds are one constant list or rows in memory -- a two-dimensional input column
+    or a stage's waveform --, not something the program would compute per event."""
+    for st in list(cx.steps):
+        if st[0] != _MULTI_TPT or not cx.has(st):
+            continue
+        fn, args, key = st[0], list(st[1]), st[2]
+        src, thr, _t_start, polarity, mode, t_out = args
+        if isinstance(polarity, Var) and polarity.kind == "const":
+            polarity = polarity.const
+        if not _is_number(polarity):
+            raise NotImplementedError(f"{fn} ({key}): the polarity is a constant of the kernel, not a per-event value")
+        if not (polarity > 0 or polarity < 0):
+            raise DSPFatal("polarity cannot be 0")
+        if not (isinstance(mode, tuple) and mode and mode[0] == "char") and not isinstance(mode, (int, np.integer)):
+            raise NotImplementedError(f"{fn} ({key}): the interpolation mode is a constant of the kernel, not a per-event value")
+        code = _Emitter.char_of(mode)
+        if not 0 < code < 128 or chr(code) not in "iafbcrnl":
+            raise DSPFatal("Unrecognized interpolation mode")
+        m = thr.length if isinstance(thr, Var) else _wf_len(thr)
+        if not (isinstance(t_out, Var) and t_out.kind == "wf" and t_out.length == m):
+            raise ProcessingChainError(f"{fn} ({key}): t_out holds a time per threshold: declare it as name({m})")
+        _rows_in_memory(cx, src, fn, key)
+        if not (isinstance(thr, Var) and thr.kind == "taps"):
+            base = _base_of(thr)
+            if base is None or not cx.row_input(base):
+                raise NotImplementedError(f"{fn} ({key}): a threshold list computed per event inside the recipe is not supported: the thresholds "
+                                          "are a constant array, a two-dimensional input column or a stage's waveform")
+        args[2] = _operand_written_first(cx, args[2], fn, key)
+        args[3] = float(polarity)
+        step = (fn, args, key)
+        cx.steps = [step if x is st else x for x in cx.steps]
+        cx.stage([step], [], f"{fn} {key} on rows", wfs=[t_out], rows_first=True)
+    for st in list(cx.steps):
+        if st[0] != _TIME_OVER or not cx.has(st):
+            continue
+        fn, args, key = st[0], list(st[1]), st[2]
+        if not isinstance(args[2], Var):
+            raise ProcessingChainError(f"{fn} ({key}): name the output")
+        _rows_in_memory(cx, args[0], fn, key)
+        args[1] = _operand_written_first(cx, args[1], fn, key)
+        step = (fn, args, key)
+        cx.steps = [step if x is st else x for x in cx.steps]
+        cx.stage([step], [args[2]], f"{fn} {key} on rows")
+
+
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     """Long FIRs leave the program: each ``convolve_wf`` with a constant kernel of STAGE_MIN_TAPS or more taps becomes a launch of the
     matrix-core FIR kernels ahead of the program (one waveform per wavefront is the wrong shape for 133 x 8192 or 5792 x 301
@@ -793,6 +888,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
         _stage_current_branch(cx)
     _stage_histogram(cx)  # (ahead of the peak finder: its thresholds may be arithmetic of these results, "3*fwhm")
     _stage_multi_extrema(cx)
+    _stage_thresholds(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and getattr(v, "ext_key", None) is not None and getattr(v, "aux_io", None) is None}
     cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
@@ -1397,6 +1493,24 @@ class _Emitter:
             a.kind, a.sreg = "scalar", first + k
         self.p.add_op(_lib.OP_HISTOGRAM_STATS, src=weights.slot, ip=(edges.slot, first), sp=(max_in,))
 
+    def multi_time_point_thresh(self, si, fn, args, what):
+        """the whole program of the stage: LOAD, [LOAD of a list per event,] MULTI_TIME_POINT_THRESH; the store of t_out follows"""
+        src, thr = self.ensure_loaded(args[0], si), args[1]
+        if isinstance(thr, Var) and thr.kind == "taps":  # one list for every row: a constant vector of the program
+            if thr.io is None:
+                thr.io = self.p.add_io(f"taps:{thr.name}", _lib.IO_TAPS, self.ft, thr.length, 0, 0)
+                self.consts[f"taps:{thr.name}"] = thr.const.astype(self.ft)
+            io, lists, m = thr.io, -1, thr.length
+        else:
+            tv = self.ensure_loaded(thr, si)
+            io, lists, m = 0, tv.slot, tv.length
+        t_start = self.scalar_operand(args[2], args, what=what)
+        t_out = self.out_wf(args[5], m, fn)
+        t_out.slot = self.new_slot(m)
+        self.p.add_op(_lib.OP_MULTI_TIME_POINT_THRESH, dst=t_out.slot, src=src.slot, io=io, ip=(self.char_of(args[4]), lists),
+                      sp=(t_start, Scalar.const(float(args[3]))))
+        self.release(src, si)
+
     def copy_slice(self, si, fn, args, what):
         src = self.ensure_loaded(args[0], si)
         dst = args[3]
@@ -1567,6 +1681,7 @@ _READ_OFF = {
         (e.char_of(a[4]),), (so(a[1]), so(a[2]), Scalar.const(float(so(a[3], integer=True))))), True),
     "amax": (_lib.OP_AMAX, 2, lambda e, a, so: ((), ()), False),
     "mean_below_threshold": (_lib.OP_MEAN_BELOW, 2, lambda e, a, so: ((), (so(a[1]),)), False),
+    _TIME_OVER: (_lib.OP_TIME_OVER_THRESHOLD, 2, lambda e, a, so: ((), (so(a[1]),)), False),
     "trap_pickoff": (_lib.OP_TRAP_WINDOW_PICKOFF, 4, lambda e, a, so: (tuple(so(x, integer=True) for x in a[1:3]), (so(a[3]),)), False),
 }
 #: the other processors -> the method of ``_Emitter`` that emits their family
@@ -1574,7 +1689,7 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          "slice": _Emitter.copy_slice, "min_max": _Emitter.four_values, "linear_slope_fit": _Emitter.four_values,
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
          "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
-         _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats}
+         _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh}
 
 
 def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):

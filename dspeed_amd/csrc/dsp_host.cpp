@@ -361,7 +361,7 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     HIP_TRY(hipMalloc((void**)&ch->dev_err, DSP_ERR_WORDS * sizeof(int)));
     HIP_TRY(hipMemset(ch->dev_err, 0, DSP_ERR_WORDS * sizeof(int)));
     const int block_lds = ch->lds_bytes_per_wave * ch->waves_per_block, classic_lds = ch->lds_bytes_per_wave * ch->classic_wpb;
-    int rc = raise_lds(!ch->ext_ok && !ch->hist_ok, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
+    int rc = raise_lds(!ch->ext_ok && !ch->hist_ok && !ch->thresh_ok, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
     if (!rc) rc = raise_lds(ch->fused_ok, classic_lds, 64 * 1024, "energy kernel, %d", [&](int n) { return dsp_internal_set_energy_lds(ch->fused_trap, ch->fused_npf, n); });
     if (!rc) rc = raise_lds(ch->fir_f16, dsp_fir_f16::lds_bytes(), 64 * 1024, "float16 FIR kernel", dsp_internal_set_fir_f16_lds);
     if (!rc) rc = raise_lds(ch->fir_ok, ch->fir_lds_bytes, 64 * 1024, "FIR kernel, %d", ch->fir.store ? dsp_internal_set_fir_store_lds : dsp_internal_set_fir_mfma_lds);
@@ -384,6 +384,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // in the order of dsp_plan_route; a launch whose planned route does not apply runs on the next that does.
 static bool extrema_applies(const dsp_chain* ch, void* const*) { return ch->ext_ok; }  // (always: the program runs nowhere else; unaligned rows: its scalar loads)
 static bool hist_applies(const dsp_chain* ch, void* const*) { return ch->hist_ok; }        // (likewise)
+static bool thresh_applies(const dsp_chain* ch, void* const*) { return ch->thresh_ok; }    // (likewise)
 static bool scalar_applies(const dsp_chain* ch, void* const*) { return ch->scalar_ok && ch->fused_on; }
 static bool pz_rows_applies(const dsp_chain* ch, void* const* io_ptrs) {
     return ch->pz_ok && ch->fused_on && aligned16(io_ptrs[ch->pio_wf]) && aligned16(io_at(ch, io_ptrs, ch->pio_out));
@@ -566,6 +567,17 @@ static int launch_hist(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* 
     const int vec = ch->hist_vec && aligned16(A.wf);
     hipError_t e = (hipError_t)dsp_internal_launch_hist(&A, n_wf, ch->hist_dtype, vec, ch->dev_err, (hipStream_t)stream);
     return launched(ch, stream, e, "histogram kernel launch");
+}
+
+static int launch_thresh(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    ThreshArgs A = ch->thresh;
+    A.wf = io_ptrs[ch->tio_wf];  // (the inputs' offsets travel in the arguments)
+    A.thr = ch->tio_thr < 0 ? nullptr : io_ptrs[ch->tio_thr];
+    A.ts = io_at(ch, io_ptrs, ch->tio_ts);
+    A.out = io_at(ch, io_ptrs, ch->tio_out);
+    const int vec = ch->thresh_vec && aligned16(A.wf);
+    hipError_t e = (hipError_t)dsp_internal_launch_thresh(&A, n_wf, ch->thresh_dtype, vec, ch->dev_err, (hipStream_t)stream);
+    return launched(ch, stream, e, "threshold kernel launch");
 }
 
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
@@ -752,6 +764,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     // the first kernel, in the order of dsp_plan_route, that takes this launch's pointers
     if (extrema_applies(ch, io_ptrs)) return launch_extrema(ch, io_ptrs, n_wf, stream);
     if (hist_applies(ch, io_ptrs)) return launch_hist(ch, io_ptrs, n_wf, stream);
+    if (thresh_applies(ch, io_ptrs)) return launch_thresh(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -845,6 +858,7 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             break;
         case DSP_ROUTE_HIST: lds = dsp_hist::lds_bytes(ch->hist.m) / 4, wpb = 4, b = (int)((n_wf + 3) / 4); break;
         case DSP_ROUTE_EXTREMA:
+        case DSP_ROUTE_THRESH:
         case DSP_ROUTE_PZ_ROWS:
         case DSP_ROUTE_REDUCE: lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4); break;
         case DSP_ROUTE_FIR_RUNS: lds = dsp_fir_runs::lds_bytes(ch->runs.m) / 4, wpb = 4, b = runs_blocks(ch, n_wf); break;
@@ -1280,6 +1294,44 @@ int g_histogram_stats(int ty, const void* weights, int64_t n_wf, int32_t n_bins,
     return m.run(n_wf, st, er);
 }
 
+int g_multi_tpt(int ty, const WfIn& in, const void* thr_dev, int32_t n_thr, int64_t thr_stride, const void* ts_dev, double ts, double polarity,
+                int32_t mode, void* t_out, int64_t out_stride, void* st, int64_t* er) {
+    if (in.n_wf <= 0 || n_thr == 0) return DSP_OK;  // (no threshold: an empty result)
+    if (n_thr < 0 || !thr_dev) return dsp_fail(DSP_ERR_ARG, "multi_time_point_thresh: a_threshold_dev holds the thresholds on the device");
+    Mini m(ty);
+    const int s_in = m.add_slot(in.len), s_out = m.add_slot(n_thr);
+    m.add_op(DSP_OP_LOAD, s_in, 0, m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr));
+    int s_thr = -1, io_thr = 0;
+    if (thr_stride != 0) {
+        s_thr = m.add_slot(n_thr);
+        m.add_op(DSP_OP_LOAD, s_thr, 0, m.add_io(DSP_IO_WF_IN, ty, n_thr, thr_stride, thr_dev));
+    } else {
+        io_thr = m.add_io(DSP_IO_TAPS, ty, n_thr, 0, thr_dev);
+    }
+    const dsp_scalar_arg a = m.scalar(ts_dev, ts), b = m.scalar(nullptr, polarity);
+    {
+        dsp_op& o = m.add_op(DSP_OP_MULTI_TIME_POINT_THRESH, s_out, s_in, io_thr);
+        o.ip[0] = mode;
+        o.ip[1] = s_thr;
+        o.sp[0] = a;
+        o.sp[1] = b;
+    }
+    m.add_op(DSP_OP_STORE, 0, s_out, m.add_io(DSP_IO_WF_OUT, ty, n_thr, out_stride, t_out));
+    return m.run(in.n_wf, st, er);
+}
+
+int g_time_over_threshold(int ty, const WfIn& in, const void* thr_dev, double thr, void* out, void* st, int64_t* er) {
+    if (in.n_wf <= 0) return DSP_OK;
+    Mini m(ty);
+    m.n_sregs = 1;
+    const int s_in = m.add_slot(in.len);
+    m.add_op(DSP_OP_LOAD, s_in, 0, m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr));
+    const dsp_scalar_arg a = m.scalar(thr_dev, thr);
+    m.add_op(DSP_OP_TIME_OVER_THRESHOLD, 0, s_in, 0).sp[0] = a;
+    m.add_op(DSP_OP_STORE_SCALAR, 0, 0, m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, out)).ip[0] = 0;
+    return m.run(in.n_wf, st, er);
+}
+
 }  // namespace
 
 #define DSP_GUFUNCS(SFX, TY, FT)                                                                                                             \
@@ -1407,6 +1459,18 @@ int g_histogram_stats(int ty, const void* weights, int64_t n_wf, int32_t n_bins,
                                   FT* fwhm_out, void* stream, int64_t* err_row) {                                                            \
         return g_histogram_stats(TY, weights_in, n_wf, n_bins, weights_stride, edges_in, edges_len, edges_stride, max_in_dev,                \
                                  (double)max_in, mode_out, max_out, fwhm_out, stream, err_row);                                              \
+    }                                                                                                                                        \
+    int dsp_multi_time_point_thresh_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride,                     \
+                                          const FT* a_threshold_dev, int32_t n_thresholds, int64_t threshold_stride, const FT* t_start_dev,  \
+                                          FT t_start, FT polarity, int32_t mode_in, FT* t_out, int64_t out_stride, void* stream,             \
+                                          int64_t* err_row) {                                                                                \
+        return g_multi_tpt(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, a_threshold_dev, n_thresholds, threshold_stride, t_start_dev,    \
+                           (double)t_start, (double)polarity, mode_in, t_out, out_stride, stream, err_row);                                  \
+    }                                                                                                                                        \
+    int dsp_time_over_threshold_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride,                         \
+                                      const FT* a_threshold_dev, FT a_threshold, FT* n_samples_out, void* stream, int64_t* err_row) {        \
+        return g_time_over_threshold(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, a_threshold_dev, (double)a_threshold, n_samples_out,   \
+                                     stream, err_row);                                                                                       \
     }
 
 DSP_GUFUNCS(f32, DSP_F32, float)

@@ -11,6 +11,7 @@
 enum dsp_route {
     DSP_ROUTE_EXTREMA,  // (the one route that is no optimisation: the interpreter has no MULTI_EXTREMA, so no switch turns it off)
     DSP_ROUTE_HIST,     // (nor this one: HISTOGRAM and HISTOGRAM_STATS have no interpreter case either)
+    DSP_ROUTE_THRESH,   // (nor this: MULTI_TIME_POINT_THRESH and TIME_OVER_THRESHOLD)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -18,6 +19,7 @@ enum dsp_route {
 inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_extrema_kernel",
     "dsp_hist_kernel",
+    "dsp_thresh_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");

@@ -36,6 +36,8 @@ int dsp_internal_launch_reduce(const ReduceArgs* A, int64_t n_wf, int dtype, int
 int dsp_internal_launch_extrema(const ExtremaArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_hist.hip (A->wf null: histogram_stats alone, dtype then the loop's type; LDS: dsp_hist::lds_bytes(A->m), below the 64 KiB that need no opt-in)
 int dsp_internal_launch_hist(const HistArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+// dsp_thresh.hip (dtype: the rows'; vec as above; A->m 0: time_over_threshold, else multi_time_point_thresh with m thresholds)
+int dsp_internal_launch_thresh(const ThreshArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_scalar.hip (type: 0 float32, 1 float64, 2 int64 registers)
 int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);
 int dsp_internal_set_scalar_lds(int lds_bytes);

@@ -73,6 +73,8 @@ extern "C" const char* dsp_fatal_message(int code) {
         case DSP_E_EXTREMA_DIR: return "search direction type not found.";
         case DSP_E_HIST_LEN: return "length borders_out must be exactly 1 + length of weights_out";
         case DSP_E_HIST_STATS_LEN: return "length edges_in must be exactly 1 + length of weights_in";
+        case DSP_E_MTPT_POLARITY: return "polarity cannot be 0";
+        case DSP_E_MTPT_MODE: return "Unrecognized interpolation mode";
         default: return "";
     }
 }
@@ -104,6 +106,7 @@ struct PlanCtx {
     bool f64 = false, i64 = false;
     bool has_extrema = false;  // a MULTI_EXTREMA among the ops: its counts are the one kind of DSP_U32 output
     bool has_hist = false;     // a HISTOGRAM or HISTOGRAM_STATS among the ops
+    bool has_thresh = false;   // a MULTI_TIME_POINT_THRESH or TIME_OVER_THRESHOLD among the ops
     int esz = 4;  // bytes of an LDS element
     // FIR inputs (laid out without the chunk pad); slots that share their LDS region with another
     bool linear[DSP_MAX_SLOTS] = {false}, shares[DSP_MAX_SLOTS] = {false};
@@ -351,6 +354,7 @@ static bool match_reduce_shape(const PlanCtx& c) {
 }
 
 static double op_const(const PlanCtx& c, const dsp_op& o, int k);
+static bool need_io(const PlanCtx& c, const dsp_op& o, int kind);
 
 // Is the program the peak finder's (dsp_extrema.hip)?
 //   LOAD s;  MULTI_EXTREMA of s;  STORE of its two lists;  STORE_SCALAR of its two counts into DSP_U32 columns
@@ -499,6 +503,79 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
         }
         A.stats = 1;
     }
+    return true;
+}
+
+// Is the program one of the threshold kernel's (dsp_thresh.hip)?
+//   LOAD s;  MULTI_TIME_POINT_THRESH of s, its thresholds one list for every row (the op's DSP_IO_TAPS binding);  STORE of t_out
+//   LOAD s;  LOAD of the thresholds, a list per row;  MULTI_TIME_POINT_THRESH of s and of them;  STORE of t_out
+//   LOAD s;  TIME_OVER_THRESHOLD of s;  STORE_SCALAR of its register
+// t_start and time_over_threshold's threshold are constants or columns of the loop's type.  Why not, otherwise: `why`.
+static bool match_thresh_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int n = c.n_ops;
+    *why = "the program must be exactly LOAD, [LOAD of the thresholds,] MULTI_TIME_POINT_THRESH, STORE; or LOAD, TIME_OVER_THRESHOLD, STORE_SCALAR";
+    auto is = [&](int i, int opcode) { return i < n && ops[i].opcode == opcode; };
+    const bool tot = n == 3 && c.n_slots == 1 && is(0, DSP_OP_LOAD) && is(1, DSP_OP_TIME_OVER_THRESHOLD) && is(2, DSP_OP_STORE_SCALAR);
+    const bool one_list = n == 3 && c.n_slots == 2 && is(0, DSP_OP_LOAD) && is(1, DSP_OP_MULTI_TIME_POINT_THRESH) && is(2, DSP_OP_STORE);
+    const bool lists = n == 4 && c.n_slots == 3 && is(0, DSP_OP_LOAD) && is(1, DSP_OP_LOAD) && is(2, DSP_OP_MULTI_TIME_POINT_THRESH) && is(3, DSP_OP_STORE);
+    if (!tot && !one_list && !lists) return false;
+    const dsp_op& op = ops[lists ? 2 : 1];
+    const dsp_op* ld = ops[0].dst == op.src ? &ops[0] : (lists && ops[1].dst == op.src ? &ops[1] : nullptr);
+    if (!ld || ld->ip[0] != 0 || ld->ip[1] != 0) return false;
+    const dsp_io_desc& w = io[ld->io];
+    *why = "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows";
+    if (c.f64 ? w.dtype != DSP_F64 : (w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16)) return false;
+    ThreshArgs& A = ch->thresh;
+    memset(&A, 0, sizeof A);
+    ch->tio_wf = ch->tio_thr = ch->tio_ts = ch->tio_out = -1;
+    auto operand = [&](const dsp_scalar_arg& a, int& binding, int64_t& stride, double& value, int k) {
+        if (a.kind == DSP_ARG_INPUT && io[a.index].dtype == c.compute_dtype) {
+            binding = a.index;
+            stride = io[a.index].row_stride;
+        } else if (a.kind == DSP_ARG_CONST) {
+            value = op_const(c, op, k);
+        } else {
+            return false;
+        }
+        return true;
+    };
+    const dsp_op& st = ops[n - 1];
+    if (tot) {
+        *why = "the threshold is a constant or a per-event column of the loop's type; the count is stored once, in the loop's type";
+        if (!operand(op.sp[0], ch->tio_thr, A.thr_stride, A.thr_const, 0) || st.ip[0] != op.dst || io[st.io].dtype != c.compute_dtype) return false;
+        A.m = 0;
+    } else {
+        *why = "the thresholds are one list for every row (the op's DSP_IO_TAPS binding, ip[1] < 0) or a list per row, loaded into slot ip[1], in the loop's type";
+        if (lists) {
+            const dsp_op* lt = ld == &ops[0] ? &ops[1] : &ops[0];
+            if (op.ip[1] != lt->dst || lt->dst == op.src || lt->ip[0] != 0 || lt->ip[1] != 0 || io[lt->io].dtype != c.compute_dtype) return false;
+            ch->tio_thr = lt->io;
+            A.thr_stride = io[lt->io].row_stride;
+            A.thr_offset = io[lt->io].offset;
+        } else {
+            if (op.ip[1] >= 0 || !need_io(c, op, DSP_IO_TAPS) || io[op.io].len != c.slot_len[op.dst]) return false;
+            ch->tio_thr = op.io;
+            A.thr_stride = 0;
+            A.thr_offset = io[op.io].offset;
+        }
+        *why = "t_start is a constant or a per-event column of the loop's type; t_out is stored once, in the loop's type";
+        if (!operand(op.sp[0], ch->tio_ts, A.ts_stride, A.ts_const, 0) || st.src != op.dst || io[st.io].dtype != c.compute_dtype) return false;
+        A.m = c.slot_len[op.dst];
+        A.polarity = op_const(c, op, 1) > 0 ? 1 : -1;
+        A.mode = op.ip[0];
+    }
+    ch->tio_out = st.io;
+    A.out_stride = io[st.io].row_stride;
+    A.wf_stride = w.row_stride;
+    A.wf_offset = w.offset;
+    A.len = w.len;
+    const int es = elem_size(w.dtype);
+    ch->thresh_dtype = w.dtype;
+    ch->thresh_vec = (w.row_stride * es) % 16 == 0 && ((int64_t)w.offset * es) % 16 == 0 && ((int64_t)w.len * es) % 16 == 0;
+    ch->tio_wf = ld->io;
     return true;
 }
 
@@ -1033,6 +1110,15 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
         case DSP_OP_HISTOGRAM: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[0]; return 3;
         case DSP_OP_HISTOGRAM_STATS: out[0] = o.src; out[1] = o.ip[0]; return 2;
+        case DSP_OP_MULTI_TIME_POINT_THRESH:
+            out[0] = o.src;
+            out[1] = o.dst;
+            if (o.ip[1] >= 0) {
+                out[2] = o.ip[1];
+                return 3;
+            }
+            return 2;
+        case DSP_OP_TIME_OVER_THRESHOLD: out[0] = o.src; return 1;
         case DSP_OP_MOVING_WINDOW_MULTI:
             out[0] = o.src;
             out[1] = o.dst;
@@ -1081,6 +1167,7 @@ static int check_call(PlanCtx& c) {
     c.ch->i64 = c.i64;
     for (int i = 0; i < n_ops; ++i) c.has_extrema |= c.ops[i].opcode == DSP_OP_MULTI_EXTREMA;
     for (int i = 0; i < n_ops; ++i) c.has_hist |= c.ops[i].opcode == DSP_OP_HISTOGRAM || c.ops[i].opcode == DSP_OP_HISTOGRAM_STATS;
+    for (int i = 0; i < n_ops; ++i) c.has_thresh |= c.ops[i].opcode == DSP_OP_MULTI_TIME_POINT_THRESH || c.ops[i].opcode == DSP_OP_TIME_OVER_THRESHOLD;
     return DSP_OK;
 }
 
@@ -1202,7 +1289,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.has_extrema && !c.has_hist)  // (MULTI_EXTREMA, HISTOGRAM: their kernels stream the row through registers, no row lives in LDS)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.has_extrema && !c.has_hist && !c.has_thresh)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1556,6 +1643,32 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
             if (slot_len[o.ip[0]] != slot_len[o.src] + 1) return fail(DSP_E_HIST_STATS_LEN, "%s", dsp_fatal_message(DSP_E_HIST_STATS_LEN));
             if (slot_len[o.src] > DSP_HIST_MAX_BINS)
                 return fail(DSP_ERR_UNSUPPORTED, "histogram_stats: at most %d bins (%d given)", DSP_HIST_MAX_BINS, slot_len[o.src]);
+            break;
+        }
+        case DSP_OP_MULTI_TIME_POINT_THRESH: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src || (o.ip[1] >= 0 && (!check_slot(P, o.ip[1]) || o.ip[1] == o.src || o.ip[1] == o.dst)))
+                return fail(DSP_ERR_ARG, "op %d: bad MULTI_TIME_POINT_THRESH (dst: the slot of t_out; ip[1]: the slot of a list of thresholds per row, or < 0: one list, the op's DSP_IO_TAPS binding)", i);
+            if (o.ip[1] >= 0 ? slot_len[o.ip[1]] != slot_len[o.dst] : (need_io(c, o, DSP_IO_TAPS) && io[o.io].len != slot_len[o.dst]))
+                return fail(DSP_ERR_ARG, "op %d: MULTI_TIME_POINT_THRESH writes a time per threshold (%d thresholds, %d times)", i,
+                            o.ip[1] >= 0 ? slot_len[o.ip[1]] : io[o.io].len, slot_len[o.dst]);
+            // polarity and mode: constants, checked for every row (the reference raises only on rows that get that far)
+            if (o.sp[1].kind != DSP_ARG_CONST)
+                return fail(DSP_ERR_UNSUPPORTED, "multi_time_point_thresh: the polarity is a constant of the program, not a per-event value");
+            if (!(op_const(c, o, 1) > 0) && !(op_const(c, o, 1) < 0)) return fail(DSP_E_MTPT_POLARITY, "%s", dsp_fatal_message(DSP_E_MTPT_POLARITY));
+            if (o.ip[0] <= 0 || o.ip[0] > 127 || !strchr("iafbcrnl", o.ip[0])) return fail(DSP_E_MTPT_MODE, "%s", dsp_fatal_message(DSP_E_MTPT_MODE));
+            if (slot_len[o.dst] > DSP_THRESH_MAX)
+                return fail(DSP_ERR_UNSUPPORTED, "multi_time_point_thresh: at most %d thresholds (%d given): a wavefront keeps one per lane", DSP_THRESH_MAX, slot_len[o.dst]);
+            if (slot_len[o.src] < 2)
+                return fail(DSP_ERR_UNSUPPORTED, "multi_time_point_thresh: rows of at least 2 samples (%d): the walks compare neighbours", slot_len[o.src]);
+            if (!f64 && slot_len[o.src] > (1 << 24))
+                return fail(DSP_ERR_UNSUPPORTED, "multi_time_point_thresh: the float32 loop takes rows of at most 2^24 samples (%d): a time counts them exactly", slot_len[o.src]);
+            break;
+        }
+        case DSP_OP_TIME_OVER_THRESHOLD: {
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs)
+                return fail(DSP_ERR_ARG, "op %d: bad TIME_OVER_THRESHOLD (src: the slot of the row; dst: the register of the count)", i);
+            if (!f64 && slot_len[o.src] > (1 << 24))
+                return fail(DSP_ERR_UNSUPPORTED, "time_over_threshold: the float32 loop takes rows of at most 2^24 samples (%d): the count is exact", slot_len[o.src]);
             break;
         }
         case DSP_OP_DWT_HAAR: {
@@ -2094,6 +2207,12 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
         if (!ch->hist_ok)
             return fail(DSP_ERR_UNSUPPORTED, "DSP_OP_HISTOGRAM / DSP_OP_HISTOGRAM_STATS (histogram, histogram_stats) run on dsp_hist_kernel only, on rows in memory: %s", why);
     }
+    if (c.has_thresh) {  // nor these
+        const char* why = "";
+        ch->thresh_ok = match_thresh_shape(c, &why);
+        if (!ch->thresh_ok)
+            return fail(DSP_ERR_UNSUPPORTED, "DSP_OP_MULTI_TIME_POINT_THRESH / DSP_OP_TIME_OVER_THRESHOLD (multi_time_point_thresh, time_over_threshold) run on dsp_thresh_kernel only, on rows in memory: %s", why);
+    }
     match_shapes(c);
     fold_scaled_thresholds(c);
     form_teams(c);
@@ -2105,6 +2224,7 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
 dsp_route dsp_plan_route(const ChainPlan* ch) {
     if (ch && ch->ext_ok) return DSP_ROUTE_EXTREMA;  // (whatever the switches say: the interpreter has no such op)
     if (ch && ch->hist_ok) return DSP_ROUTE_HIST;
+    if (ch && ch->thresh_ok) return DSP_ROUTE_THRESH;
     if (!ch || !ch->fused_on) return DSP_ROUTE_VM;
     if (ch->scalar_ok) return DSP_ROUTE_SCALAR;
     if (ch->pz_ok) return DSP_ROUTE_PZ_ROWS;

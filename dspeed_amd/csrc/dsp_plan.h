@@ -90,6 +90,10 @@ struct ChainPlan {
     bool hist_ok = false, hist_vec = false;
     HistArgs hist{};
     int hio_wf = -1, hio_w = -1, hio_b = -1, hio_w_in = -1, hio_e_in = -1, hio_max_in = -1, hio_s[3] = {-1, -1, -1}, hist_dtype = DSP_F32;
+    // multi_time_point_thresh and time_over_threshold (dsp_thresh.hip): the one kernel a program with either op runs on
+    bool thresh_ok = false, thresh_vec = false;
+    ThreshArgs thresh{};
+    int tio_wf = -1, tio_thr = -1, tio_ts = -1, tio_out = -1, thresh_dtype = DSP_F32;
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};

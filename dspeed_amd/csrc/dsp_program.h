@@ -307,6 +307,29 @@ struct HistArgs {
     int64_t s_stride[3];
 };
 
+// arguments of the threshold kernel (dsp_thresh.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> [LOAD of the thresholds ->] MULTI_TIME_POINT_THRESH -> STORE
+//   LOAD -> TIME_OVER_THRESHOLD -> STORE_SCALAR
+// A wavefront keeps the row's thresholds one per lane (ranked, then in ascending order) and a result per lane: nothing lives in LDS.
+#define DSP_THRESH_MAX 64 /* thresholds of one multi_time_point_thresh */
+struct ThreshArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples (multi_time_point_thresh: at least 2)
+    int32_t m;               // thresholds of multi_time_point_thresh; 0: time_over_threshold
+    int32_t polarity;        // +1 or -1
+    int32_t mode;            // interpolation mode, a character of "iafbcrnl"
+    const void* thr;         // multi_time_point_thresh: lists of m values of the loop's type, thr_stride apart (0: one list for every row);
+    int64_t thr_stride;      //   time_over_threshold: a column of the loop's type, or null: thr_const
+    int32_t thr_offset;
+    double thr_const;
+    const void* ts;          // t_start: a column of the loop's type, or null: ts_const
+    int64_t ts_stride;
+    double ts_const;
+    void* out;               // t_out rows of m values, or the count, one value per row; the loop's type
+    int64_t out_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

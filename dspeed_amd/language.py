@@ -149,6 +149,7 @@ _SIGS = {
     "mean_below_threshold": "wsS", "windower": "wsW", "avg_current": "wsW", "trap_pickoff": "wiisS",
     "upsampler": "wsW", "moving_window_multi": "wsiiW", "numpy_subtract": "wsW", "numpy_add": "wsW", "min_max_norm": "wssW", "linear_slope_fit": "wSSSS",
     "histogram": "wWW", "histogram_stats": "wwSSSs",  # (w_in, weights_out, borders_out); (weights_in, edges_in, mode_out, max_out, fwhm_out, max_in)
+    "multi_time_point_thresh": "wtsscW", "time_over_threshold": "wsS",  # (w_in, a_threshold[m], t_start, polarity, mode_in, t_out[m]); (w_in, a_threshold, n_samples)
     "get_multi_local_extrema": "wssissWWSS",  # (w_in, a_delta_max_in, a_delta_min_in, search_direction, a_abs_max_in, a_abs_min_in, two lists, two counts)
 }
 _SIGS.update({"sample": "wiS", "slice": "wiiW", "get": "wsS"})  # wf[i], wf[lo:hi:step], wf[variable] (reference :948-1071)
@@ -231,7 +232,8 @@ _PROCESSOR_FILES = {
     "avg_current": ("moving_windows",), "moving_window_multi": ("moving_windows",), "upsampler": ("upsampler",), "discrete_wavelet_transform": ("dwt",),
     "convolve_wf": ("convolutions",), "fft_convolve_wf": ("convolutions",), "cusp_filter": ("energy_kernels",), "zac_filter": ("energy_kernels",),
     "t0_filter": ("kernels",), "moving_slope": ("kernels",), "get_multi_local_extrema": ("get_multi_local_extrema",), "histogram": ("histogram",),
-    "histogram_stats": ("histogram_stats", "histogram"),
+    "histogram_stats": ("histogram_stats", "histogram"), "multi_time_point_thresh": ("time_point_thresh",),
+    "time_over_threshold": ("time_over_threshold",),
 }
 
 

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .. import _lib
 from ..device import DeviceArray
 from ..errors import DSPFatal
 from ..gufunc import HipGUFunc, Staging, entry, loop_suffix, run
@@ -160,6 +161,77 @@ def _interpolated_time_point_thresh(g, *args):
         st.release()
 
 
+def _constant_of_call(v, what, name):
+    a = np.asarray(v)
+    if a.size != 1:
+        raise NotImplementedError(f"{what}: {name} is a constant of the call on the device, not a per-event value")
+    return a.reshape(-1)[0]
+
+
+def _multi_time_point_thresh(g, *args):
+    ins, outs = _split(g, args)
+    w_in, a_threshold, t_start, polarity, mode_in = ins
+    what = g.__name__
+    # polarity and mode are constants, checked for every row (the reference raises on the rows that get that far)
+    pol = float(_constant_of_call(polarity, what, "polarity"))
+    if not (pol > 0 or pol < 0):
+        raise DSPFatal("polarity cannot be 0")
+    mode = _mode_char(_constant_of_call(mode_in, what, "mode_in"))
+    if not 0 < mode < 128 or chr(mode) not in "iafbcrnl":
+        raise DSPFatal("Unrecognized interpolation mode")
+    st = Staging()
+    try:
+        ptr, code, n_wf, n, stride, one_d = st.wf_in(w_in)
+        sfx = loop_suffix(_dtype_of(w_in))
+        if sfx == "f64" and np.dtype(_dtype_of(w_in)) != np.dtype(np.float64):
+            raise NotImplementedError(f"{what}: the float64 loop takes float64 rows on the device")
+        ft = _F[sfx]
+        if isinstance(a_threshold, DeviceArray):
+            if a_threshold.dtype != np.dtype(ft):
+                raise TypeError(f"{what}: thresholds on the device have the loop's type, {np.dtype(ft)}")
+            thr, shape = a_threshold, tuple(a_threshold.shape)
+        else:
+            host = np.ascontiguousarray(np.asarray(a_threshold), dtype=ft)
+            shape = host.shape
+            thr = None
+        if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] != n_wf):
+            raise ValueError(f"{what}: a_threshold has shape {shape}, expected (m,) or ({n_wf}, m)")
+        m = int(shape[-1])
+        if m > _lib.THRESH_MAX:
+            raise NotImplementedError(f"{what}: at most {_lib.THRESH_MAX} thresholds ({m} given): a wavefront keeps one per lane")
+        oshape = (m,) if one_d else (n_wf, m)
+        if m == 0:
+            return outs[0] if outs[0] is not None else np.empty(oshape, dtype=ft)
+        if thr is None:
+            thr = DeviceArray.from_numpy(host)
+            st.keep.append(thr)
+        tp, tv = st.scalar_in(t_start, n_wf, ft)
+        optr, res = st.out(outs[0], oshape, ft)
+        run(entry("multi_time_point_thresh", sfx), what, ptr, code, n_wf, n, stride, thr.ptr, m, m if len(shape) == 2 else 0, tp, tv, pol, mode, optr, m)
+        st.finish()
+        return res
+    finally:
+        st.release()
+
+
+def _time_over_threshold(g, *args):
+    ins, outs = _split(g, args)
+    st = Staging()
+    try:
+        ptr, code, n_wf, n, stride, one_d = st.wf_in(ins[0])
+        sfx = loop_suffix(_dtype_of(ins[0]))
+        if sfx == "f64" and np.dtype(_dtype_of(ins[0])) != np.dtype(np.float64):
+            raise NotImplementedError(f"{g.__name__}: the float64 loop takes float64 rows on the device")
+        ft = _F[sfx]
+        ap, av = st.scalar_in(ins[1], n_wf, ft)
+        optr, res = st.out(outs[0], () if one_d else (n_wf,), ft)
+        run(entry("time_over_threshold", sfx), g.__name__, ptr, code, n_wf, n, stride, ap, av, optr)
+        st.finish()
+        return res[()] if isinstance(res, np.ndarray) and res.ndim == 0 else res
+    finally:
+        st.release()
+
+
 def _linear_slope_fit(g, *args):
     ins, outs = _split(g, args)
     st = Staging()
@@ -212,6 +284,12 @@ time_point_thresh = HipGUFunc("time_point_thresh", "(n),(),(),()->()", ["ffff->f
                               "first threshold crossing walking forward/backward (reference processors/time_point_thresh.py:12-92)")
 interpolated_time_point_thresh = HipGUFunc("interpolated_time_point_thresh", "(n),(),(),(),()->()", ["ffflb->f", "dddlb->d"], _interpolated_time_point_thresh,
                                            "threshold crossing placed between samples, modes i b c a f r n l (reference processors/time_point_thresh.py:95-222)")
+multi_time_point_thresh = HipGUFunc("multi_time_point_thresh", "(n),(m),(),(),()->(m)", ["ffffb->f", "ddddb->d"], _multi_time_point_thresh,
+                                    "the times at which a row crosses m thresholds (m <= 64), found from one starting sample: upwards with the polarity, "
+                                    "downwards against it; modes i a f b c r n l; polarity and mode are constants of the call "
+                                    "(reference processors/time_point_thresh.py:225-401)")
+time_over_threshold = HipGUFunc("time_over_threshold", "(n),()->()", ["ff->f", "dd->d"], _time_over_threshold,
+                                "the number of samples above a threshold (reference processors/time_over_threshold.py:11-48)")
 linear_slope_fit = HipGUFunc("linear_slope_fit", "(n)->(),(),(),()", ["f->ffff", "d->dddd"], _linear_slope_fit,
                              "Welford mean / standard deviation and least-squares slope / intercept (reference processors/linear_slope_fit.py:11-91)")
 mean_below_threshold = HipGUFunc("mean_below_threshold", "(n),()->()", ["ff->f", "dd->d"], _mean_below_threshold,
@@ -555,4 +633,4 @@ zac_filter = HipGUFunc("zac_filter", "(),(),(),(n)", ["ffff", "dddd"], _zac_filt
                        "zero-area CUSP kernel generator, host, once (reference processors/energy_kernels.py:76-157)")
 
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
-           "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats"]
+           "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

@@ -71,6 +71,8 @@ extern "C" {
 #define DSP_E_EXTREMA_DIR 28   /* get_multi_local_extrema.py:305-306 */
 #define DSP_E_HIST_LEN 29      /* histogram.py:61-62 */
 #define DSP_E_HIST_STATS_LEN 30 /* histogram_stats.py:227-228 */
+#define DSP_E_MTPT_POLARITY 31 /* time_point_thresh.py:313-314   checked at chain creation: polarity is a constant */
+#define DSP_E_MTPT_MODE 32     /* time_point_thresh.py:357-358   likewise */
 
 /* ---- element types -------------------------------------------------------------------------- */
 #define DSP_F32 0
@@ -245,6 +247,19 @@ typedef struct dsp_scalar_arg {
                                  *   LOAD, HISTOGRAM, HISTOGRAM_STATS of its two slots, [STORE, STORE,] STORE_SCALAR x 3   (one launch; without
                                  *                                                           the STOREs no weight or border is written)
                                  *   LOAD weights, LOAD edges, HISTOGRAM_STATS, STORE_SCALAR x 3   (rows of the loop's type in memory) */
+#define DSP_OP_MULTI_TIME_POINT_THRESH 37 /* time_point_thresh.py:225-401: the times at which src crosses m thresholds, found from one starting sample.
+                                 * dst = the slot of t_out (m samples, m <= 64); the thresholds are one list for every row (io = a DSP_IO_TAPS
+                                 * binding of m values, ip[1] < 0) or a list per row (ip[1] = a slot of m samples, loaded from rows of the loop's
+                                 * type); ip[0] = the interpolation mode, a character of "iafbcrnl"; sp[0] = t_start, a constant or a per-event
+                                 * column of the loop's type; sp[1] = polarity, a constant.  Polarity 0 and an unknown mode are refused at chain
+                                 * creation whatever the rows hold.  Float32 / int16 / uint16 rows of 2 to 2^24 samples in the float32 loop, float64
+                                 * rows in the float64 loop.  Negative sample indices wrap as NumPy's do (w[-1], w[-2]) */
+#define DSP_OP_TIME_OVER_THRESHOLD 38 /* time_over_threshold.py:11-48: sreg[dst] <- the number of samples of src above sp[0] (a constant or a per-event
+                                 * column of the loop's type), NaN if a sample or the threshold is NaN.
+                                 * The waveform interpreter has neither op: they run on dsp_thresh_kernel only, in a program of exactly
+                                 *   LOAD, MULTI_TIME_POINT_THRESH, STORE of dst                 (one list of thresholds)
+                                 *   LOAD, LOAD of the thresholds, MULTI_TIME_POINT_THRESH, STORE of dst
+                                 *   LOAD, TIME_OVER_THRESHOLD, STORE_SCALAR of dst */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -481,6 +496,16 @@ int dsp_histogram_stats_f32(const float* weights_in, int64_t n_wf, int32_t n_bin
                             int32_t edges_len, int64_t edges_stride, const float* max_in_dev, float max_in, float* mode_out, float* max_out,
                             float* fwhm_out, void* stream, int64_t* err_row);
 
+/* "(n),(m),(),(),()->(m)": a_threshold_dev holds lists of n_thresholds values threshold_stride apart (0: one list for every row); t_start is a
+ * column or a constant; polarity (its sign) and mode_in (a character of "iafbcrnl") are constants of the call, checked before the launch;
+ * t_out rows of n_thresholds values out_stride apart */
+int dsp_multi_time_point_thresh_f32(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const float* a_threshold_dev,
+                                    int32_t n_thresholds, int64_t threshold_stride, const float* t_start_dev, float t_start, float polarity,
+                                    int32_t mode_in, float* t_out, int64_t out_stride, void* stream, int64_t* err_row);
+/* "(n),()->()": the number of samples above a_threshold (a column or a constant), one value per row */
+int dsp_time_over_threshold_f32(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const float* a_threshold_dev,
+                                float a_threshold, float* n_samples_out, void* stream, int64_t* err_row);
+
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
                         double baseline, double* out, int64_t out_stride, void* stream, int64_t* err_row);
@@ -535,6 +560,11 @@ int dsp_histogram_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len
 int dsp_histogram_stats_f64(const double* weights_in, int64_t n_wf, int32_t n_bins, int64_t weights_stride, const double* edges_in,
                             int32_t edges_len, int64_t edges_stride, const double* max_in_dev, double max_in, double* mode_out,
                             double* max_out, double* fwhm_out, void* stream, int64_t* err_row);
+int dsp_multi_time_point_thresh_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* a_threshold_dev,
+                                    int32_t n_thresholds, int64_t threshold_stride, const double* t_start_dev, double t_start, double polarity,
+                                    int32_t mode_in, double* t_out, int64_t out_stride, void* stream, int64_t* err_row);
+int dsp_time_over_threshold_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* a_threshold_dev,
+                                double a_threshold, double* n_samples_out, void* stream, int64_t* err_row);
 
 /* ---- synthetic batches generated on the device (bench.py) ---------------------------------
  * wf[r][i] = B_r + A_r*exp(-(i-t0_r)/tau)*[i>=t0_r] + sigma*n(r,i), counter-based hash noise;  also writes the
