@@ -70,21 +70,10 @@ class PlanInfo(C.Structure):  # dsp_plan_info
                 ("slot_pitch", C.c_int32 * MAX_SLOTS), ("slot_chunk", C.c_int32 * MAX_SLOTS)]
 
 
-_lib = None
-
-
-def lib():
-    """Load (once) and return the shared library; raises if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m dspeed_amd.build` (hipcc, gfx950). "
-                           "dspeed_amd has no CPU fallback.")
-    L = C.CDLL(LIB_PATH)
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    pi64 = C.POINTER(C.c_int64)
-    sig = {
+# ---- the functions of include/dspeed_hip.h.  SIG: argument types of those that return an int status
+vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
+pi64 = C.POINTER(C.c_int64)
+SIG = {
         "dsp_device_count": [C.POINTER(C.c_int)],
         "dsp_set_device": [C.c_int],
         "dsp_get_device": [C.POINTER(C.c_int)],
@@ -119,6 +108,7 @@ def lib():
         "dsp_chain_geometry": [vp, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
         "dsp_chain_set_fused": [vp, C.c_int],
         "dsp_chain_set_async_check": [vp, C.c_int],
+        "dsp_chain_share_row_scales": [vp, vp],
         "dsp_bl_subtract_f32": [vp, C.c_int, i64, i32, i64, vp, f32, vp, i64, vp, pi64],
         "dsp_pole_zero_f32": [vp, C.c_int, i64, i32, i64, f32, vp, i64, vp, pi64],
         "dsp_double_pole_zero_f32": [vp, C.c_int, i64, i32, i64, f32, f32, f32, vp, i64, vp, pi64],
@@ -156,46 +146,38 @@ def lib():
         "dsp_stream_read": [vp, i64, vp, vp],
         "dsp_linear_slope_fit_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
                                       C.POINTER(FitWindow), C.c_int, vp, vp],
-    }
-    f64 = C.c_double
-    for name in list(sig):  # the float64 loops: same argument order, double scalars
-        if name.endswith("_f32") and name not in ("dsp_synth_waveforms", "dsp_synth_pulses"):
-            sig[name[:-4] + "_f64"] = [f64 if t is f32 else t for t in sig[name]]
-    for name, argtypes in sig.items():
-        fn = getattr(L, name)
-        fn.argtypes = argtypes
-        fn.restype = C.c_int
-    for name in ("dsp_last_error", "dsp_version"):
-        getattr(L, name).restype = C.c_char_p
-        getattr(L, name).argtypes = []
-    L.dsp_fatal_message.restype = C.c_char_p
-    L.dsp_fatal_message.argtypes = [C.c_int]
-    L.dsp_chain_kernel_name.restype = C.c_char_p
-    L.dsp_chain_kernel_name.argtypes = [vp]
-    L.dsp_chain_kernel_note.restype = C.c_char_p
-    L.dsp_chain_kernel_note.argtypes = [vp]
-    L.dsp_chain_share_row_scales.restype = C.c_int
-    L.dsp_chain_share_row_scales.argtypes = [vp, vp]
+}
+for _name in list(SIG):  # the float64 loops: same argument order, double scalars
+    if _name.endswith("_f32") and _name not in ("dsp_synth_waveforms", "dsp_synth_pulses"):
+        SIG[_name[:-4] + "_f64"] = [f64 if t is f32 else t for t in SIG[_name]]
+# ... and those that do not: (result type, argument types)
+OTHER = {
+    "dsp_last_error": (C.c_char_p, []),
+    "dsp_version": (C.c_char_p, []),
+    "dsp_fatal_message": (C.c_char_p, [C.c_int]),
+    "dsp_chain_kernel_name": (C.c_char_p, [vp]),
+    "dsp_chain_kernel_note": (C.c_char_p, [vp]),
+}
+EXPORTS = list(SIG) + list(OTHER)  # every function the header declares (tests/test_c_abi.py)
+
+_lib = None
+
+
+def lib():
+    """Load (once) and return the shared library; raises if it has not been built."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m dspeed_amd.build` (hipcc, gfx950). "
+                           "dspeed_amd has no CPU fallback.")
+    L = C.CDLL(LIB_PATH)
+    for name, argtypes in SIG.items():
+        getattr(L, name).argtypes, getattr(L, name).restype = argtypes, C.c_int
+    for name, (restype, argtypes) in OTHER.items():
+        getattr(L, name).argtypes, getattr(L, name).restype = argtypes, restype
     _lib = L
     return L
-
-
-EXPORTS = [
-    "dsp_device_count", "dsp_set_device", "dsp_get_device", "dsp_device_info", "dsp_malloc", "dsp_free", "dsp_host_alloc", "dsp_host_register", "dsp_host_unregister", "dsp_stream_wait_event",
-    "dsp_host_free", "dsp_memset", "dsp_h2d", "dsp_d2h", "dsp_h2d_async", "dsp_d2h_async", "dsp_stream_create", "dsp_stream_destroy",
-    "dsp_stream_sync", "dsp_sync", "dsp_event_create", "dsp_event_destroy", "dsp_event_record", "dsp_event_sync",
-    "dsp_event_elapsed_ms", "dsp_last_error", "dsp_fatal_message", "dsp_version", "dsp_chain_create", "dsp_chain_plan", "dsp_chain_execute",
-    "dsp_chain_check", "dsp_chain_destroy", "dsp_chain_geometry", "dsp_chain_kernel_name", "dsp_chain_kernel_note", "dsp_chain_share_row_scales", "dsp_chain_set_fused", "dsp_chain_set_async_check", "dsp_bl_subtract_f32", "dsp_pole_zero_f32",
-    "dsp_double_pole_zero_f32", "dsp_pole_zero_col_f32", "dsp_double_pole_zero_col_f32", "dsp_pole_zero_col_f64", "dsp_double_pole_zero_col_f64", "dsp_trap_filter_f32", "dsp_trap_norm_f32", "dsp_asym_trap_filter_f32", "dsp_fixed_time_pickoff_f32",
-    "dsp_install_abort_trace", "dsp_uninstall_abort_trace", "dsp_chain_profile", "dsp_chain_profile_read", "dsp_min_max_norm_f32", "dsp_min_max_norm_f64", "dsp_time_point_thresh_f32", "dsp_interpolated_time_point_thresh_f32", "dsp_interpolated_time_point_thresh_f64", "dsp_min_max_f32", "dsp_mean_below_threshold_f32", "dsp_mean_below_threshold_f64", "dsp_windower_f32", "dsp_windower_f64", "dsp_avg_current_f32",
-    "dsp_avg_current_f64", "dsp_trap_pickoff_f32", "dsp_trap_pickoff_f64", "dsp_upsampler_f32", "dsp_upsampler_f64",
-    "dsp_moving_window_multi_f32", "dsp_moving_window_multi_f64", "dsp_linear_slope_fit_f32", "dsp_linear_slope_fit_f64", "dsp_dwt_haar_f32", "dsp_convolve_wf_f32", "dsp_synth_waveforms", "dsp_synth_pulses", "dsp_stream_read",
-    "dsp_bl_subtract_f64", "dsp_pole_zero_f64", "dsp_double_pole_zero_f64", "dsp_trap_filter_f64", "dsp_trap_norm_f64",
-    "dsp_asym_trap_filter_f64", "dsp_fixed_time_pickoff_f64", "dsp_time_point_thresh_f64", "dsp_min_max_f64", "dsp_dwt_haar_f64",
-    "dsp_convolve_wf_f64", "dsp_linear_slope_fit_rows", "dsp_get_multi_local_extrema_f32", "dsp_get_multi_local_extrema_f64",
-    "dsp_histogram_f32", "dsp_histogram_f64", "dsp_histogram_stats_f32", "dsp_histogram_stats_f64",
-    "dsp_multi_time_point_thresh_f32", "dsp_multi_time_point_thresh_f64", "dsp_time_over_threshold_f32", "dsp_time_over_threshold_f64",
-]
 
 
 def last_error() -> str:

@@ -3,8 +3,9 @@
 //   * device/memory/stream helpers (thin wrappers so that a host needs nothing but this library);
 //   * chain translation: validates a dsp_op program, evaluates every constant the reference evaluates once per
 //     call in float64 on the host (exp(-1/tau) through libm exactly as numba/LLVM does, IIR coefficients, lag
-//     splits), lays the waveform slots out in LDS and picks the launch geometry;
-//   * the single-processor entry points (dsp_<name>_f32), which are tiny cached chains.
+//     splits), lays the waveform slots out in LDS and picks the launch geometry.
+//
+// The single-processor entry points (dsp_<name>_f32 / _f64: tiny cached chains) are clients of this file, in dsp_gufuncs.cpp.
 //
 // Reference behaviour mirrored here: constant-only DSPFatal conditions are raised at chain creation with the
 // reference's own codes/messages (processors/*.py, cited in include/dspeed_hip.h).
@@ -20,12 +21,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "dsp_gufuncs.h"
 #include "dsp_launch.h"
 #include "dsp_plan.h"
 
@@ -129,6 +130,19 @@ static hipError_t staged_d2h(void* host, const void* dev, size_t bytes) {
         if (e == hipSuccess) memcpy((char*)host + o, g_stage, n);
     }
     return e;
+}
+
+// the HIP side of the single-processor entry points (dsp_gufuncs.h)
+int dsp_gufunc_current_device() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return dev;
+}
+int dsp_gufunc_read_back(void* host, const void* dev, size_t bytes) {
+    const hipError_t e = staged_d2h(host, dev, bytes);
+    if (e == hipSuccess) return DSP_OK;
+    (void)hipGetLastError();  // (the text is what the copy reported when it stood in g_convolve)
+    return fail(DSP_ERR_HIP, "staged_d2h(taps.data(), kernel_dev, taps.size()) failed: %s", hipGetErrorString(e));
 }
 
 // a kernel the chain is planned for that needs more dynamic LDS than a launch gets unasked is told so once, at chain creation
@@ -915,567 +929,6 @@ int dsp_chain_set_fused(dsp_chain* ch, int enable) {
     ch->variant = (v == 7 || !ch->rr_ok) ? 1 : 6;
     return dsp_plan_specialised(ch) ? 1 : 0;
 }
-
-// ------------------------------------------------------------------------------------------------ single processors
-// One implementation per processor, generic in the loop type TY (DSP_F32 / DSP_F64); the exported dsp_<name>_f32 / _f64
-// functions below only fix the scalar C types.
-namespace {
-
-struct MiniKey {
-    std::vector<int64_t> v;
-    bool operator<(const MiniKey& o) const { return v < o.v; }
-};
-std::map<MiniKey, dsp_chain*> g_cache;
-std::mutex g_cache_mu;
-
-int64_t dbits(double f) {
-    int64_t i;
-    memcpy(&i, &f, 8);
-    return i;
-}
-
-struct Mini {
-    int ty;  // DSP_F32 or DSP_F64: the gufunc loop
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<void*> ptrs;
-    std::vector<int32_t> slots;
-    int n_sregs = 0;
-    MiniKey key;
-
-    explicit Mini(int ty_) : ty(ty_) { key.v.push_back(ty_); }
-
-    int add_io(int kind, int dtype, int len, int64_t stride, const void* p) {
-        dsp_io_desc d{kind, dtype, len, 0, stride};
-        io.push_back(d);
-        ptrs.push_back(const_cast<void*>(p));
-        key.v.insert(key.v.end(), {kind, dtype, len, stride});
-        return (int)io.size() - 1;
-    }
-    int add_slot(int len) {
-        key.v.push_back(len);
-        slots.push_back(len);
-        return (int)slots.size() - 1;
-    }
-    dsp_op& add_op(int opcode, int dst, int src, int io_idx) {
-        dsp_op o;
-        memset(&o, 0, sizeof o);
-        o.opcode = opcode;
-        o.dst = dst;
-        o.src = src;
-        o.io = io_idx;
-        ops.push_back(o);
-        key.v.insert(key.v.end(), {opcode, dst, src, io_idx});
-        return ops.back();
-    }
-    // scalar gufunc argument: device column (of the loop type) if given, else broadcast constant
-    dsp_scalar_arg scalar(const void* dev, double value) {
-        dsp_scalar_arg a{DSP_ARG_CONST, 0, value};
-        if (dev) {
-            a.kind = DSP_ARG_INPUT;
-            a.index = add_io(DSP_IO_SCALAR_IN, ty, 1, 1, dev);
-        } else {
-            key.v.push_back(dbits(value));
-        }
-        return a;
-    }
-    int run(int64_t n_wf, void* stream, int64_t* err_row) {
-        for (auto& o : ops) {
-            for (int k = 0; k < 4; ++k) key.v.push_back(o.ip[k]);
-            key.v.push_back(o.io);
-        }
-        // The cached chains carry one device error word each and are destroyed when the cache is emptied: look-up, creation, execution and
-        // the check of the error word happen under the cache's lock, so the dsp_<name>_f32/_f64 entry points are serialised within a
-        // process (threads that want concurrency build their own chains with dsp_chain_create).
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        key.v.push_back(dev);
-        dsp_chain* ch = nullptr;
-        auto it = g_cache.find(key);
-        if (it != g_cache.end()) ch = it->second;
-        if (!ch) {
-            int rc = dsp_chain_create(ops.data(), (int)ops.size(), io.data(), (int)io.size(), slots.data(), (int)slots.size(), n_sregs, ty,
-                                      &ch);
-            if (rc) return rc;
-            if (g_cache.size() > 256) {  // (nobody is inside a cached chain: we hold the lock)
-                for (auto& kv : g_cache) dsp_chain_destroy(kv.second);
-                g_cache.clear();
-            }
-            g_cache[key] = ch;
-        }
-        int rc = dsp_chain_execute(ch, ptrs.data(), n_wf, stream);
-        if (rc) return rc;
-        return dsp_chain_check(ch, stream, err_row);
-    }
-};
-
-struct WfIn {
-    const void* ptr;
-    int dtype;
-    int64_t n_wf;
-    int32_t len;
-    int64_t stride;
-};
-
-// waveform -> waveform processors
-int wf2wf(int ty, int opcode, const WfIn& in, void* out, int32_t out_len, int64_t out_stride, const int32_t* ip, int n_ip,
-          const double* consts, int n_c, const void* col0, void* stream, int64_t* err_row, const void* const* cols = nullptr) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    // the per-sample and scan filters work in place: one LDS slot, so a wavefront holds a waveform twice as long (about 38 k float32
-    // samples instead of 19 k for the filters that need source and destination side by side)
-    const bool in_place = (opcode == DSP_OP_BL_SUBTRACT || opcode == DSP_OP_POLE_ZERO || opcode == DSP_OP_DOUBLE_POLE_ZERO) && out_len == in.len;
-    const int s_in = m.add_slot(in.len), s_out = in_place ? s_in : m.add_slot(out_len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_scalar_arg sp[3];
-    memset(sp, 0, sizeof sp);
-    for (int k = 0; k < n_c; ++k) sp[k] = m.scalar(cols ? cols[k] : (k == 0 ? col0 : nullptr), consts[k]);  // device column or constant
-    dsp_op& o = m.add_op(opcode, s_out, s_in, 0);
-    for (int k = 0; k < n_ip; ++k) o.ip[k] = ip[k];
-    for (int k = 0; k < n_c; ++k) o.sp[k] = sp[k];
-    const int io_out = m.add_io(DSP_IO_WF_OUT, ty, out_len, out_stride, out);
-    m.add_op(DSP_OP_STORE, 0, s_out, io_out);
-    return m.run(in.n_wf, stream, err_row);
-}
-
-int g_bl_subtract(int ty, const WfIn& in, const void* bl_dev, double bl, void* out, int64_t out_stride, void* st, int64_t* er) {
-    const double c[1] = {bl};
-    return wf2wf(ty, DSP_OP_BL_SUBTRACT, in, out, in.len, out_stride, nullptr, 0, c, 1, bl_dev, st, er);
-}
-int g_min_max_norm(int ty, const WfIn& in, const void* lo_dev, double lo, const void* hi_dev, double hi, void* out, int64_t out_stride, void* st,
-                   int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    const int s_in = m.add_slot(in.len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_scalar_arg a = m.scalar(lo_dev, lo), b = m.scalar(hi_dev, hi);
-    dsp_op& o = m.add_op(DSP_OP_MIN_MAX_NORM, s_in, s_in, 0);  // in place
-    o.sp[0] = a;
-    o.sp[1] = b;
-    const int io_out = m.add_io(DSP_IO_WF_OUT, ty, in.len, out_stride, out);
-    m.add_op(DSP_OP_STORE, 0, s_in, io_out);
-    return m.run(in.n_wf, st, er);
-}
-int g_pole_zero(int ty, const WfIn& in, const void* tau_dev, double tau, void* out, int64_t out_stride, void* st, int64_t* er) {
-    const double c[1] = {tau};
-    return wf2wf(ty, DSP_OP_POLE_ZERO, in, out, in.len, out_stride, nullptr, 0, c, 1, tau_dev, st, er);
-}
-int g_double_pole_zero(int ty, const WfIn& in, const void* const* cols, double tau1, double tau2, double frac, void* out, int64_t out_stride, void* st,
-                       int64_t* er) {
-    const double c[3] = {tau1, tau2, frac};
-    return wf2wf(ty, DSP_OP_DOUBLE_POLE_ZERO, in, out, in.len, out_stride, nullptr, 0, c, 3, cols ? cols[0] : nullptr, st, er, cols);
-}
-int g_trap(int ty, int opcode, const WfIn& in, int32_t rise, int32_t flat, int32_t fall, void* out, int64_t out_stride, void* st, int64_t* er) {
-    const int32_t ip[3] = {rise, flat, fall};
-    return wf2wf(ty, opcode, in, out, in.len, out_stride, ip, 3, nullptr, 0, nullptr, st, er);
-}
-int g_dwt(int ty, const WfIn& in, int32_t level, int32_t coeff, void* out, int32_t out_len, int64_t out_stride, void* st, int64_t* er) {
-    const int32_t ip[3] = {level, coeff, 0};  // scratch = the input slot itself (dead after the transform)
-    return wf2wf(ty, DSP_OP_DWT_HAAR, in, out, out_len, out_stride, ip, 3, nullptr, 0, nullptr, st, er);
-}
-int g_convolve(int ty, const WfIn& in, const void* kernel_dev, int32_t kernel_len, int32_t mode, void* out, int32_t out_len, int64_t out_stride,
-               void* st, int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    if (kernel_len <= 0) return fail(DSP_ERR_ARG, "empty kernel");
-    // NaN among the taps -> NaN output (convolutions.py:45-46): look at them once on the host
-    const size_t esz = ty == DSP_F64 ? 8 : 4;
-    std::vector<unsigned char> taps(esz * (size_t)kernel_len);
-    HIP_TRY(staged_d2h(taps.data(), kernel_dev, taps.size()));
-    int has_nan = 0;  // bit 0: a NaN among the taps, bit 1: an infinity
-    for (int k = 0; k < kernel_len; ++k) {
-        const double v = ty == DSP_F64 ? ((const double*)taps.data())[k] : (double)((const float*)taps.data())[k];
-        has_nan |= std::isnan(v) ? 1 : (std::isinf(v) ? 2 : 0);
-    }
-    Mini m(ty);
-    const int s_in = m.add_slot(in.len), s_out = m.add_slot(out_len > 0 ? out_len : 1);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    const int io_k = m.add_io(DSP_IO_TAPS, ty, kernel_len, 0, kernel_dev);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_op& o = m.add_op(DSP_OP_CONVOLVE, s_out, s_in, io_k);
-    o.ip[0] = mode;
-    o.ip[1] = has_nan;
-    const int io_out = m.add_io(DSP_IO_WF_OUT, ty, out_len > 0 ? out_len : 1, out_stride, out);
-    m.add_op(DSP_OP_STORE, 0, s_out, io_out);
-    return m.run(in.n_wf, st, er);
-}
-int g_pickoff(int ty, const WfIn& in, const void* t_dev, double t_in, int32_t mode, void* out, void* st, int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    m.n_sregs = 1;
-    const int s_in = m.add_slot(in.len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_scalar_arg t = m.scalar(t_dev, t_in);
-    dsp_op& o = m.add_op(DSP_OP_PICKOFF, 0, s_in, 0);
-    o.ip[0] = mode;
-    o.sp[0] = t;
-    const int io_out = m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, out);
-    dsp_op& sto = m.add_op(DSP_OP_STORE_SCALAR, 0, 0, io_out);
-    sto.ip[0] = 0;
-    return m.run(in.n_wf, st, er);
-}
-// mode_char 0: time_point_thresh; otherwise interpolated_time_point_thresh with that interpolation mode
-int g_tpt(int ty, const WfIn& in, const void* thr_dev, double thr, const void* ts_dev, double ts, double walk, void* out, void* st, int64_t* er,
-          int mode_char = 0) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    m.n_sregs = 1;
-    const int s_in = m.add_slot(in.len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_scalar_arg a = m.scalar(thr_dev, thr), b = m.scalar(ts_dev, ts), c = m.scalar(nullptr, walk);
-    dsp_op& o = m.add_op(mode_char ? DSP_OP_INTERP_TIME_POINT_THRESH : DSP_OP_TIME_POINT_THRESH, 0, s_in, 0);
-    o.ip[0] = mode_char;
-    o.sp[0] = a;
-    o.sp[1] = b;
-    o.sp[2] = c;
-    const int io_out = m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, out);
-    dsp_op& sto = m.add_op(DSP_OP_STORE_SCALAR, 0, 0, io_out);
-    sto.ip[0] = 0;
-    return m.run(in.n_wf, st, er);
-}
-int g_windower(int ty, const WfIn& in, const void* t0_dev, double t0, void* out, int32_t out_len, int64_t out_stride, void* st, int64_t* er) {
-    const double c[1] = {t0};
-    return wf2wf(ty, DSP_OP_WINDOWER, in, out, out_len, out_stride, nullptr, 0, c, 1, t0_dev, st, er);
-}
-int g_avg_current(int ty, const WfIn& in, double length, void* out, int32_t out_len, int64_t out_stride, void* st, int64_t* er) {
-    const double c[1] = {length};
-    return wf2wf(ty, DSP_OP_AVG_CURRENT, in, out, out_len, out_stride, nullptr, 0, c, 1, nullptr, st, er);
-}
-int g_trap_window_pickoff(int ty, const WfIn& in, int32_t rise, int32_t flat, const void* tp_dev, double tp, void* out, void* st, int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    m.n_sregs = 1;
-    const int s_in = m.add_slot(in.len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_scalar_arg a = m.scalar(tp_dev, tp);
-    dsp_op& o = m.add_op(DSP_OP_TRAP_WINDOW_PICKOFF, 0, s_in, 0);
-    o.ip[0] = rise;
-    o.ip[1] = flat;
-    o.sp[0] = a;
-    const int io_out = m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, out);
-    dsp_op& sto = m.add_op(DSP_OP_STORE_SCALAR, 0, 0, io_out);
-    sto.ip[0] = 0;
-    return m.run(in.n_wf, st, er);
-}
-int g_upsampler(int ty, const WfIn& in, double up, void* out, int32_t out_len, int64_t out_stride, void* st, int64_t* er) {
-    const double c[1] = {up};
-    return wf2wf(ty, DSP_OP_UPSAMPLER, in, out, out_len, out_stride, nullptr, 0, c, 1, nullptr, st, er);
-}
-int g_moving_window_multi(int ty, const WfIn& in, double length, double num_mw, int32_t mw_type, void* out, int64_t out_stride, void* st,
-                          int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    if (floor(num_mw) != num_mw) return fail(DSP_E_MW_NUM_INT, "%s", dsp_fatal_message(DSP_E_MW_NUM_INT));
-    Mini m(ty);
-    const int s_in = m.add_slot(in.len), s_out = m.add_slot(in.len);
-    const int s_tmp = num_mw > 1 ? m.add_slot(in.len) : 0;
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_op& o = m.add_op(DSP_OP_MOVING_WINDOW_MULTI, s_out, s_in, 0);
-    o.ip[0] = mw_type;
-    o.ip[1] = (int32_t)num_mw;
-    o.ip[2] = s_tmp;
-    o.sp[0] = m.scalar(nullptr, length);
-    const int io_out = m.add_io(DSP_IO_WF_OUT, ty, in.len, out_stride, out);
-    m.add_op(DSP_OP_STORE, 0, s_out, io_out);
-    return m.run(in.n_wf, st, er);
-}
-int g_linear_slope_fit(int ty, const WfIn& in, void* mean, void* stdev, void* slope, void* intercept, void* st, int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    m.n_sregs = 4;
-    const int s_in = m.add_slot(in.len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    m.add_op(DSP_OP_LINEAR_SLOPE_FIT, 0, s_in, 0);
-    void* outs[4] = {mean, stdev, slope, intercept};
-    for (int k = 0; k < 4; ++k) {
-        const int io_out = m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, outs[k]);
-        dsp_op& sto = m.add_op(DSP_OP_STORE_SCALAR, 0, 0, io_out);
-        sto.ip[0] = k;
-    }
-    return m.run(in.n_wf, st, er);
-}
-int g_mean_below(int ty, const WfIn& in, const void* thr_dev, double thr, void* out, void* st, int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    m.n_sregs = 1;
-    const int s_in = m.add_slot(in.len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_scalar_arg a = m.scalar(thr_dev, thr);
-    dsp_op& o = m.add_op(DSP_OP_MEAN_BELOW, 0, s_in, 0);
-    o.sp[0] = a;
-    const int io_out = m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, out);
-    dsp_op& sto = m.add_op(DSP_OP_STORE_SCALAR, 0, 0, io_out);
-    sto.ip[0] = 0;
-    return m.run(in.n_wf, st, er);
-}
-int g_min_max(int ty, const WfIn& in, void* t_min, void* t_max, void* a_min, void* a_max, void* st, int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    m.n_sregs = 4;
-    const int s_in = m.add_slot(in.len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    m.add_op(DSP_OP_MIN_MAX, 0, s_in, 0);
-    void* outs[4] = {t_min, t_max, a_min, a_max};
-    for (int k = 0; k < 4; ++k) {
-        const int io_out = m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, outs[k]);
-        dsp_op& sto = m.add_op(DSP_OP_STORE_SCALAR, 0, 0, io_out);
-        sto.ip[0] = k;
-    }
-    return m.run(in.n_wf, st, er);
-}
-
-int g_multi_extrema(int ty, const WfIn& in, const void* const* cols, const double* consts, int32_t direction, void* vt_max, void* vt_min, int32_t out_len,
-                    int64_t out_stride, uint32_t* n_max, uint32_t* n_min, void* st, int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    m.n_sregs = 2;
-    const int s_in = m.add_slot(in.len), s_max = m.add_slot(out_len), s_min = m.add_slot(out_len);
-    const int io_in = m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, io_in);
-    dsp_scalar_arg sp[4];
-    for (int k = 0; k < 4; ++k) sp[k] = m.scalar(cols[k], consts[k]);
-    {
-        dsp_op& o = m.add_op(DSP_OP_MULTI_EXTREMA, s_max, s_in, 0);
-        o.ip[0] = direction;
-        o.ip[1] = s_min;
-        o.ip[2] = 0;
-        for (int k = 0; k < 4; ++k) o.sp[k] = sp[k];
-    }
-    m.add_op(DSP_OP_STORE, 0, s_max, m.add_io(DSP_IO_WF_OUT, ty, out_len, out_stride, vt_max));
-    m.add_op(DSP_OP_STORE, 0, s_min, m.add_io(DSP_IO_WF_OUT, ty, out_len, out_stride, vt_min));
-    void* counts[2] = {n_max, n_min};
-    for (int k = 0; k < 2; ++k) {
-        const int io_out = m.add_io(DSP_IO_SCALAR_OUT, DSP_U32, 1, 1, counts[k]);
-        dsp_op& sto = m.add_op(DSP_OP_STORE_SCALAR, 0, 0, io_out);
-        sto.ip[0] = k;
-    }
-    return m.run(in.n_wf, st, er);
-}
-
-int g_histogram(int ty, const WfIn& in, void* weights, int32_t n_bins, int64_t w_stride, void* borders, int32_t borders_len, int64_t b_stride, void* st,
-                int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    if (n_bins <= 0 || borders_len <= 0) return dsp_fail(DSP_ERR_ARG, "histogram: weights_out and borders_out hold at least one value");
-    Mini m(ty);
-    const int s_in = m.add_slot(in.len), s_w = m.add_slot(n_bins), s_b = m.add_slot(borders_len);
-    m.add_op(DSP_OP_LOAD, s_in, 0, m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr));
-    m.add_op(DSP_OP_HISTOGRAM, s_w, s_in, 0).ip[0] = s_b;
-    m.add_op(DSP_OP_STORE, 0, s_w, m.add_io(DSP_IO_WF_OUT, ty, n_bins, w_stride, weights));
-    m.add_op(DSP_OP_STORE, 0, s_b, m.add_io(DSP_IO_WF_OUT, ty, borders_len, b_stride, borders));
-    return m.run(in.n_wf, st, er);
-}
-
-int g_histogram_stats(int ty, const void* weights, int64_t n_wf, int32_t n_bins, int64_t w_stride, const void* edges, int32_t edges_len, int64_t e_stride,
-                      const void* max_in_dev, double max_in, void* mode_out, void* max_out, void* fwhm_out, void* st, int64_t* er) {
-    if (n_wf <= 0) return DSP_OK;
-    if (n_bins <= 0 || edges_len <= 0) return dsp_fail(DSP_ERR_ARG, "histogram_stats: weights_in and edges_in hold at least one value");
-    Mini m(ty);
-    m.n_sregs = 3;
-    const int s_w = m.add_slot(n_bins), s_e = m.add_slot(edges_len);
-    m.add_op(DSP_OP_LOAD, s_w, 0, m.add_io(DSP_IO_WF_IN, ty, n_bins, w_stride, weights));
-    m.add_op(DSP_OP_LOAD, s_e, 0, m.add_io(DSP_IO_WF_IN, ty, edges_len, e_stride, edges));
-    const dsp_scalar_arg mi = m.scalar(max_in_dev, max_in);
-    {
-        dsp_op& o = m.add_op(DSP_OP_HISTOGRAM_STATS, 0, s_w, 0);
-        o.ip[0] = s_e;
-        o.ip[1] = 0;
-        o.sp[0] = mi;
-    }
-    void* outs[3] = {mode_out, max_out, fwhm_out};
-    for (int k = 0; k < 3; ++k) m.add_op(DSP_OP_STORE_SCALAR, 0, 0, m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, outs[k])).ip[0] = k;
-    return m.run(n_wf, st, er);
-}
-
-int g_multi_tpt(int ty, const WfIn& in, const void* thr_dev, int32_t n_thr, int64_t thr_stride, const void* ts_dev, double ts, double polarity,
-                int32_t mode, void* t_out, int64_t out_stride, void* st, int64_t* er) {
-    if (in.n_wf <= 0 || n_thr == 0) return DSP_OK;  // (no threshold: an empty result)
-    if (n_thr < 0 || !thr_dev) return dsp_fail(DSP_ERR_ARG, "multi_time_point_thresh: a_threshold_dev holds the thresholds on the device");
-    Mini m(ty);
-    const int s_in = m.add_slot(in.len), s_out = m.add_slot(n_thr);
-    m.add_op(DSP_OP_LOAD, s_in, 0, m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr));
-    int s_thr = -1, io_thr = 0;
-    if (thr_stride != 0) {
-        s_thr = m.add_slot(n_thr);
-        m.add_op(DSP_OP_LOAD, s_thr, 0, m.add_io(DSP_IO_WF_IN, ty, n_thr, thr_stride, thr_dev));
-    } else {
-        io_thr = m.add_io(DSP_IO_TAPS, ty, n_thr, 0, thr_dev);
-    }
-    const dsp_scalar_arg a = m.scalar(ts_dev, ts), b = m.scalar(nullptr, polarity);
-    {
-        dsp_op& o = m.add_op(DSP_OP_MULTI_TIME_POINT_THRESH, s_out, s_in, io_thr);
-        o.ip[0] = mode;
-        o.ip[1] = s_thr;
-        o.sp[0] = a;
-        o.sp[1] = b;
-    }
-    m.add_op(DSP_OP_STORE, 0, s_out, m.add_io(DSP_IO_WF_OUT, ty, n_thr, out_stride, t_out));
-    return m.run(in.n_wf, st, er);
-}
-
-int g_time_over_threshold(int ty, const WfIn& in, const void* thr_dev, double thr, void* out, void* st, int64_t* er) {
-    if (in.n_wf <= 0) return DSP_OK;
-    Mini m(ty);
-    m.n_sregs = 1;
-    const int s_in = m.add_slot(in.len);
-    m.add_op(DSP_OP_LOAD, s_in, 0, m.add_io(DSP_IO_WF_IN, in.dtype, in.len, in.stride, in.ptr));
-    const dsp_scalar_arg a = m.scalar(thr_dev, thr);
-    m.add_op(DSP_OP_TIME_OVER_THRESHOLD, 0, s_in, 0).sp[0] = a;
-    m.add_op(DSP_OP_STORE_SCALAR, 0, 0, m.add_io(DSP_IO_SCALAR_OUT, ty, 1, 1, out)).ip[0] = 0;
-    return m.run(in.n_wf, st, er);
-}
-
-}  // namespace
-
-#define DSP_GUFUNCS(SFX, TY, FT)                                                                                                             \
-    int dsp_bl_subtract_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* baseline_dev,          \
-                              FT baseline, FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                                     \
-        return g_bl_subtract(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, baseline_dev, (double)baseline, out, out_stride, stream,        \
-                             err_row);                                                                                                        \
-    }                                                                                                                                         \
-    int dsp_pole_zero_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT tau, FT* out,                   \
-                            int64_t out_stride, void* stream, int64_t* err_row) {                                                             \
-        return g_pole_zero(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, nullptr, (double)tau, out, out_stride, stream, err_row);          \
-    }                                                                                                                                         \
-    int dsp_pole_zero_col_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* tau_dev, FT tau,      \
-                                FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                                                \
-        return g_pole_zero(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, tau_dev, (double)tau, out, out_stride, stream, err_row);          \
-    }                                                                                                                                         \
-    int dsp_double_pole_zero_col_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* tau1_dev,     \
-                                       FT tau1, const FT* tau2_dev, FT tau2, const FT* frac_dev, FT frac, FT* out, int64_t out_stride,        \
-                                       void* stream, int64_t* err_row) {                                                                      \
-        const void* cols[3] = {tau1_dev, tau2_dev, frac_dev};                                                                                 \
-        return g_double_pole_zero(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, cols, (double)tau1, (double)tau2, (double)frac, out,      \
-                                  out_stride, stream, err_row);                                                                              \
-    }                                                                                                                                         \
-    int dsp_double_pole_zero_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT tau1, FT tau2, FT frac,  \
-                                   FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                                             \
-        return g_double_pole_zero(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, nullptr, (double)tau1, (double)tau2, (double)frac, out,   \
-                                  out_stride, stream, err_row);                                                                              \
-    }                                                                                                                                         \
-    int dsp_trap_filter_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int32_t rise, int32_t flat,      \
-                              FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                                                  \
-        return g_trap(TY, DSP_OP_TRAP_FILTER, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, rise, flat, 0, out, out_stride, stream, err_row);  \
-    }                                                                                                                                         \
-    int dsp_trap_norm_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int32_t rise, int32_t flat,        \
-                            FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                                                    \
-        return g_trap(TY, DSP_OP_TRAP_NORM, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, rise, flat, 0, out, out_stride, stream, err_row);    \
-    }                                                                                                                                         \
-    int dsp_asym_trap_filter_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int32_t rise, int32_t flat, \
-                                   int32_t fall, FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                               \
-        return g_trap(TY, DSP_OP_ASYM_TRAP, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, rise, flat, fall, out, out_stride, stream, err_row); \
-    }                                                                                                                                         \
-    int dsp_fixed_time_pickoff_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* t_in_dev,       \
-                                     FT t_in, int32_t mode_char, FT* out, void* stream, int64_t* err_row) {                                   \
-        return g_pickoff(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, t_in_dev, (double)t_in, mode_char, out, stream, err_row);           \
-    }                                                                                                                                         \
-    int dsp_time_point_thresh_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* threshold_dev,   \
-                                    FT threshold, const FT* t_start_dev, FT t_start, FT walk_forward, FT* out, void* stream,                  \
-                                    int64_t* err_row) {                                                                                       \
-        return g_tpt(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, threshold_dev, (double)threshold, t_start_dev, (double)t_start,         \
-                     (double)walk_forward, out, stream, err_row);                                                                             \
-    }                                                                                                                                         \
-    int dsp_interpolated_time_point_thresh_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride,              \
-                                                 const FT* threshold_dev, FT threshold, const FT* t_start_dev, FT t_start,                  \
-                                                 int64_t walk_forward, int32_t mode_char, FT* out, void* stream, int64_t* err_row) {       \
-        if (mode_char <= 0 || mode_char > 127) return fail(DSP_ERR_ARG, "interpolated_time_point_thresh: mode must be a character");       \
-        return g_tpt(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, threshold_dev, (double)threshold, t_start_dev, (double)t_start,         \
-                     (double)walk_forward, out, stream, err_row, mode_char);                                                                \
-    }                                                                                                                                         \
-    int dsp_min_max_norm_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* a_min_dev, FT a_min,  \
-                               const FT* a_max_dev, FT a_max, FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                \
-        return g_min_max_norm(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, a_min_dev, (double)a_min, a_max_dev, (double)a_max, out,       \
-                              out_stride, stream, err_row);                                                                                  \
-    }                                                                                                                                         \
-    int dsp_windower_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* t0_dev, FT t0, FT* out,   \
-                           int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row) {                                             \
-        return g_windower(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, t0_dev, (double)t0, out, out_len, out_stride, stream, err_row);    \
-    }                                                                                                                                         \
-    int dsp_avg_current_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT length, FT* out,              \
-                              int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row) {                                          \
-        return g_avg_current(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, (double)length, out, out_len, out_stride, stream, err_row);     \
-    }                                                                                                                                         \
-    int dsp_trap_pickoff_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int32_t rise, int32_t flat,     \
-                               const FT* t_pickoff_dev, FT t_pickoff, FT* out, void* stream, int64_t* err_row) {                              \
-        return g_trap_window_pickoff(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, rise, flat, t_pickoff_dev, (double)t_pickoff, out,      \
-                                     stream, err_row);                                                                                       \
-    }                                                                                                                                         \
-    int dsp_upsampler_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT upsample, FT* out,              \
-                            int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row) {                                            \
-        return g_upsampler(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, (double)upsample, out, out_len, out_stride, stream, err_row);     \
-    }                                                                                                                                         \
-    int dsp_moving_window_multi_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT length, FT num_mw,    \
-                                      int32_t mw_type, FT* out, int64_t out_stride, void* stream, int64_t* err_row) {                         \
-        return g_moving_window_multi(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, (double)length, (double)num_mw, mw_type, out,          \
-                                     out_stride, stream, err_row);                                                                           \
-    }                                                                                                                                         \
-    int dsp_linear_slope_fit_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT* mean, FT* stdev,       \
-                                   FT* slope, FT* intercept, void* stream, int64_t* err_row) {                                                \
-        return g_linear_slope_fit(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, mean, stdev, slope, intercept, stream, err_row);           \
-    }                                                                                                                                         \
-    int dsp_mean_below_threshold_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride,                        \
-                                       const FT* threshold_dev, FT threshold, FT* out, void* stream, int64_t* err_row) {                      \
-        return g_mean_below(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, threshold_dev, (double)threshold, out, stream, err_row);         \
-    }                                                                                                                                         \
-    int dsp_min_max_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT* t_min, FT* t_max, FT* a_min,     \
-                          FT* a_max, void* stream, int64_t* err_row) {                                                                        \
-        return g_min_max(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, t_min, t_max, a_min, a_max, stream, err_row);                       \
-    }                                                                                                                                         \
-    int dsp_dwt_haar_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int32_t level, int32_t coeff_char,  \
-                           FT* out, int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row) {                                    \
-        return g_dwt(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, level, coeff_char, out, out_len, out_stride, stream, err_row);          \
-    }                                                                                                                                         \
-    int dsp_convolve_wf_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const FT* kernel_dev,            \
-                              int32_t kernel_len, int32_t mode_char, FT* out, int32_t out_len, int64_t out_stride, void* stream,              \
-                              int64_t* err_row) {                                                                                             \
-        return g_convolve(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, kernel_dev, kernel_len, mode_char, out, out_len, out_stride,       \
-                          stream, err_row);                                                                                                   \
-    }                                                                                                                                        \
-    int dsp_get_multi_local_extrema_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride,                     \
-                                          const FT* a_delta_max_dev, FT a_delta_max, const FT* a_delta_min_dev, FT a_delta_min,              \
-                                          int32_t search_direction, const FT* a_abs_max_dev, FT a_abs_max, const FT* a_abs_min_dev,          \
-                                          FT a_abs_min, FT* vt_max_out, FT* vt_min_out, int32_t out_len, int64_t out_stride,                 \
-                                          uint32_t* n_max_out, uint32_t* n_min_out, void* stream, int64_t* err_row) {                        \
-        const void* cols[4] = {a_delta_max_dev, a_delta_min_dev, a_abs_max_dev, a_abs_min_dev};                                              \
-        const double consts[4] = {(double)a_delta_max, (double)a_delta_min, (double)a_abs_max, (double)a_abs_min};                           \
-        return g_multi_extrema(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, cols, consts, search_direction, vt_max_out, vt_min_out,      \
-                               out_len, out_stride, n_max_out, n_min_out, stream, err_row);                                                  \
-    }                                                                                                                                        \
-    int dsp_histogram_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, FT* weights_out, int32_t n_bins,  \
-                            int64_t weights_stride, FT* borders_out, int32_t borders_len, int64_t borders_stride, void* stream,              \
-                            int64_t* err_row) {                                                                                              \
-        return g_histogram(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, weights_out, n_bins, weights_stride, borders_out, borders_len,   \
-                           borders_stride, stream, err_row);                                                                                 \
-    }                                                                                                                                        \
-    int dsp_histogram_stats_##SFX(const FT* weights_in, int64_t n_wf, int32_t n_bins, int64_t weights_stride, const FT* edges_in,            \
-                                  int32_t edges_len, int64_t edges_stride, const FT* max_in_dev, FT max_in, FT* mode_out, FT* max_out,       \
-                                  FT* fwhm_out, void* stream, int64_t* err_row) {                                                            \
-        return g_histogram_stats(TY, weights_in, n_wf, n_bins, weights_stride, edges_in, edges_len, edges_stride, max_in_dev,                \
-                                 (double)max_in, mode_out, max_out, fwhm_out, stream, err_row);                                              \
-    }                                                                                                                                        \
-    int dsp_multi_time_point_thresh_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride,                     \
-                                          const FT* a_threshold_dev, int32_t n_thresholds, int64_t threshold_stride, const FT* t_start_dev,  \
-                                          FT t_start, FT polarity, int32_t mode_in, FT* t_out, int64_t out_stride, void* stream,             \
-                                          int64_t* err_row) {                                                                                \
-        return g_multi_tpt(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, a_threshold_dev, n_thresholds, threshold_stride, t_start_dev,    \
-                           (double)t_start, (double)polarity, mode_in, t_out, out_stride, stream, err_row);                                  \
-    }                                                                                                                                        \
-    int dsp_time_over_threshold_##SFX(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride,                         \
-                                      const FT* a_threshold_dev, FT a_threshold, FT* n_samples_out, void* stream, int64_t* err_row) {        \
-        return g_time_over_threshold(TY, WfIn{in, in_dtype, n_wf, wf_len, in_stride}, a_threshold_dev, (double)a_threshold, n_samples_out,   \
-                                     stream, err_row);                                                                                       \
-    }
-
-DSP_GUFUNCS(f32, DSP_F32, float)
-DSP_GUFUNCS(f64, DSP_F64, double)
-#undef DSP_GUFUNCS
 
 int dsp_stream_read(const void* src, int64_t bytes, void* sink, void* stream) {
     if (!src || !sink || bytes < 16) return fail(DSP_ERR_ARG, "dsp_stream_read: need a source of at least 16 bytes and a 4-byte sink");

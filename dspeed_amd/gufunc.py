@@ -10,6 +10,7 @@ There is no CPU implementation behind these objects: without the library or a GP
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import re
 
@@ -201,3 +202,68 @@ def run(fn, what, *cargs):
     row = C.c_int64(-1)
     rc = fn(*cargs, None, C.byref(row))
     _lib.check(rc, row=row.value if row.value >= 0 else None, what=what)
+
+
+def dtype_of(x):
+    return x.dtype if hasattr(x, "dtype") else np.asarray(x).dtype
+
+
+class DeviceCall:
+    """The frame of one processor call on the device (``device_call``): the staging buffers and their lifetime, the rows and the loop they
+    select, the outputs, the launch of ``dsp_<name>_<loop>`` and what the call returns."""
+
+    LOOP_TYPES = {"f32": np.float32, "f64": np.float64}
+
+    def __init__(self, what):
+        self.what = what  # the processor's name, for error texts
+        self.st = Staging()
+        self.results = []
+
+    def rows(self, a, f64_rows_only=False):
+        """the waveform argument: on the device; its type selects the loop (``sfx``, ``ft``)"""
+        self.ptr, self.code, self.n_wf, self.n, self.stride, self.one_d = self.st.wf_in(a)
+        self.sfx = loop_suffix(dtype_of(a))
+        if f64_rows_only and self.sfx == "f64" and np.dtype(dtype_of(a)) != np.dtype(np.float64):
+            raise NotImplementedError(f"{self.what}: the float64 loop takes float64 rows on the device")
+        self.ft = self.LOOP_TYPES[self.sfx]
+
+    @property
+    def rows_args(self):
+        """what every entry point takes first"""
+        return self.ptr, self.code, self.n_wf, self.n, self.stride
+
+    def col(self, v):
+        """a '()' argument -> (device column or None, broadcast value)"""
+        return self.st.scalar_in(v, self.n_wf, self.ft)
+
+    def out(self, given, rule="", dtype=None):
+        """An output -- the caller's array or a new one -- by its shape rule: "" a value per row, "n" a row as long as the input's, "m" a row as
+        long as the array that has to be passed for it.  Returns its C arguments: the pointer, then the length for "n" (which is also the
+        stride), length and stride for "m"."""
+        m = {"": None, "n": self.n, "m": given.shape[-1] if rule == "m" else None}[rule]
+        shape = () if m is None else (m,)
+        ptr, res = self.st.out(given, shape if self.one_d else (self.n_wf, *shape), dtype or self.ft)
+        self.results.append(res)
+        return [ptr] + {"": [], "n": [m], "m": [m, m]}[rule]
+
+    def launch(self, name, *cargs):
+        """run the entry point, bring the outputs back and return them: one or a tuple, a 0-d array as its scalar"""
+        run(entry(name, self.sfx), self.what, *cargs)
+        self.st.finish()
+        res = [r[()] if isinstance(r, np.ndarray) and r.ndim == 0 else r for r in self.results]
+        return res[0] if len(res) == 1 else tuple(res)
+
+
+_LATER = object()  # (device_call: the body calls c.rows itself)
+
+
+@contextlib.contextmanager
+def device_call(what, rows=_LATER, f64_rows_only=False):
+    """``with device_call(name, w_in) as c:`` -- whatever happens inside, the staging buffers are released"""
+    c = DeviceCall(what)
+    try:
+        if rows is not _LATER:
+            c.rows(rows, f64_rows_only)
+        yield c
+    finally:
+        c.st.release()
