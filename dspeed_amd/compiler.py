@@ -420,6 +420,17 @@ class _Stager:
     def has(self, st) -> bool:
         return any(st is x for x in self.steps)
 
+    def steps_of(self, fn):
+        """the steps of processor ``fn`` that are still in the program when their turn comes (an earlier one's stage may have taken them)"""
+        for st in list(self.steps):
+            if st[0] == fn and self.has(st):
+                yield st
+
+    def replace(self, old, new):
+        """the step ``new`` in the place of ``old``; returns it"""
+        self.steps = [new if x is old else x for x in self.steps]
+        return new
+
     def producer_of(self, v):
         for st in self.steps:
             if any(a is v for a in _outputs_of(st)):
@@ -704,9 +715,7 @@ def _stage_multi_extrema(cx: _Stager):
     results; what the program would compute off rows in HBM moves ahead of it (``move_ahead``); expressions of those and columns of other
     types go through a small program of their own (``stage_expression``)."""
     fn = _MULTI_EXTREMA
-    for st in list(cx.steps):
-        if st[0] != fn or not cx.has(st):
-            continue
+    for st in cx.steps_of(fn):
         args, key = list(st[1]), st[2]
         src, direction, lists, counts = args[0], args[3], args[6:8], args[8:10]
         if not _is_integral(direction):
@@ -721,18 +730,27 @@ def _stage_multi_extrema(cx: _Stager):
         _rows_in_memory(cx, src, fn, key)
         for k in (1, 2, 4, 5):
             args[k] = _operand_in_memory(cx, args[k], fn, key)
-        step = (fn, args, key)
-        cx.steps = [step if x is st else x for x in cx.steps]
+        step = cx.replace(st, (fn, args, key))
         cx.stage([step], counts, f"{fn} {key} on rows", wfs=lists, rows_first=True)
 
 
-def _operand_in_memory(cx: _Stager, a, fn, key):
+def _operand_in_memory(cx: _Stager, a, fn, key, written_first=False):
     """A per-event operand of a kernel that reads its operands as constants or float32 columns (``_stage_multi_extrema`` says which it
-    takes): returns it as the kernel's stage reads it, after moving ahead or evaluating what has to be."""
+    takes): returns it as the kernel's stage reads it, after moving ahead or evaluating what has to be.  ``written_first`` (the threshold
+    kernel's operands) admits one more source: a per-event value that the program would read off a waveform it computes itself (the maximum
+    of the baseline-subtracted waveform, for a threshold at half of it) is written to HBM first, with the other results of its processor,
+    by a small program of its own -- as a source waveform is."""
     if not isinstance(a, (Var, SExpr)):
         if isinstance(a, (tuple, Grid)) or not (_is_number(a) or isinstance(a, Quantity)):
             raise NotImplementedError(f"{fn} ({key}): operand {a!r} is neither a number nor a per-event value")
         return a
+    for leaf in _leaves(a, []) if written_first else ():
+        pst = cx.producer_of(leaf) if isinstance(leaf, Var) and leaf.kind == "scalar" and not cx.plain_scalar(leaf) else None
+        if pst is None or any(isinstance(x, Var) and cx.row_input(x) for x in _inputs_of(pst)):
+            continue  # (in memory already, or read off rows in memory: ``move_ahead`` takes it)
+        outs = _outputs_of(pst)
+        if all(isinstance(o, Var) and o.kind == "scalar" for o in outs):
+            cx.stage(cx.ancestors(leaf), outs, f"{leaf.name} -> HBM", drop=[])
     for leaf in _leaves(a, []):  # what the program would compute off rows in HBM moves ahead of it
         if not cx.plain_scalar(leaf) and not (leaf.kind == "scalar" and cx.move_ahead([leaf])):
             raise NotImplementedError(f"{fn} ({key}): operand '{a.name}' depends on '{leaf.name}', which is neither a constant, an input column, "
@@ -760,9 +778,7 @@ def _stage_histogram(cx: _Stager):
     """``histogram`` and ``histogram_stats`` run on dsp_hist.hip and nowhere else, on rows in HBM: mandatory stages, like the peak finder's.
     A ``histogram_stats`` that reads exactly a histogram's weights and borders joins its launch; weights and borders are then written only
     if something else reads them or the recipe asks for them.  Any other ``histogram_stats`` reads weights and edges as rows in memory."""
-    for st in list(cx.steps):
-        if st[0] != _HISTOGRAM or not cx.has(st):
-            continue
+    for st in cx.steps_of(_HISTOGRAM):
         args, key = list(st[1]), st[2]
         weights, borders = args[1:3]
         if not all(isinstance(v, Var) and v.kind == "wf" and v.length for v in (weights, borders)):
@@ -777,17 +793,14 @@ def _stage_histogram(cx: _Stager):
         if stats is not None:
             sargs = list(stats[1])
             sargs[5] = _operand_in_memory(cx, sargs[5], _HISTOGRAM_STATS, stats[2])
-            fused = (_HISTOGRAM_STATS, sargs, stats[2])
-            cx.steps = [fused if x is stats else x for x in cx.steps]
+            fused = cx.replace(stats, (_HISTOGRAM_STATS, sargs, stats[2]))
             group, scalars = [st, fused], sargs[2:5]
             if not all(isinstance(v, Var) for v in scalars):
                 raise ProcessingChainError(f"{_HISTOGRAM_STATS} ({stats[2]}): name the three outputs")
         rows_wanted = any(v.name in cx.out_names or [u for u in cx.users_of(v) if not any(u is g for g in group)] for v in (weights, borders))
         cx.stage(group, scalars, f"{_HISTOGRAM} {key}" + (f" + {_HISTOGRAM_STATS} {stats[2]} in one launch" if stats is not None else "") + " on rows",
                  wfs=[weights, borders] if rows_wanted or stats is None else [], rows_first=True)
-    for st in list(cx.steps):
-        if st[0] != _HISTOGRAM_STATS or not cx.has(st):
-            continue
+    for st in cx.steps_of(_HISTOGRAM_STATS):
         args, key = list(st[1]), st[2]
         for a in args[:2]:
             if not (isinstance(a, Var) and a.kind == "wf" and a.length):
@@ -797,24 +810,8 @@ def _stage_histogram(cx: _Stager):
         for a in args[:2]:
             _rows_in_memory(cx, a, _HISTOGRAM_STATS, key)
         args[5] = _operand_in_memory(cx, args[5], _HISTOGRAM_STATS, key)
-        step = (_HISTOGRAM_STATS, args, key)
-        cx.steps = [step if x is st else x for x in cx.steps]
+        step = cx.replace(st, (_HISTOGRAM_STATS, args, key))
         cx.stage([step], args[2:5], f"{_HISTOGRAM_STATS} {key} on rows")
-
-
-def _operand_written_first(cx: _Stager, a, fn, key):
-    """``_operand_in_memory`` for the threshold kernel's operands, with one more source: a per-event value that the program would read off a
-    waveform it computes itself (the maximum of the baseline-subtracted waveform, for a threshold at half of it) is written to HBM first,
-    with the other results of its processor, by a small program of its own -- as a source waveform is."""
-    if isinstance(a, (Var, SExpr)):
-        for leaf in _leaves(a, []):
-            pst = cx.producer_of(leaf) if isinstance(leaf, Var) and leaf.kind == "scalar" and not cx.plain_scalar(leaf) else None
-            if pst is None or any(isinstance(x, Var) and cx.row_input(x) for x in _inputs_of(pst)):
-                continue  # (in memory already, or read off rows in memory: ``move_ahead`` takes it)
-            outs = _outputs_of(pst)
-            if all(isinstance(o, Var) and o.kind == "scalar" for o in outs):
-                cx.stage(cx.ancestors(leaf), outs, f"{leaf.name} -> HBM", drop=[])
-    return _operand_in_memory(cx, a, fn, key)
 
 
 def _stage_thresholds(cx: _Stager):
@@ -822,9 +819,7 @@ def _stage_thresholds(cx: _Stager):
     the peak finder's.  Polarity and mode are constants, checked here for every row; t_start and time_over_threshold's threshold are
     per-event operands (``_operand_in_memory``); the thresholds are one constant list or rows in memory -- a two-dimensional input column
     or a stage's waveform --, not something the program would compute per event."""
-    for st in list(cx.steps):
-        if st[0] != _MULTI_TPT or not cx.has(st):
-            continue
+    for st in cx.steps_of(_MULTI_TPT):
         fn, args, key = st[0], list(st[1]), st[2]
         src, thr, _t_start, polarity, mode, t_out = args
         if isinstance(polarity, Var) and polarity.kind == "const":
@@ -847,21 +842,17 @@ def _stage_thresholds(cx: _Stager):
             if base is None or not cx.row_input(base):
                 raise NotImplementedError(f"{fn} ({key}): a threshold list computed per event inside the recipe is not supported: the thresholds "
                                           "are a constant array, a two-dimensional input column or a stage's waveform")
-        args[2] = _operand_written_first(cx, args[2], fn, key)
+        args[2] = _operand_in_memory(cx, args[2], fn, key, written_first=True)
         args[3] = float(polarity)
-        step = (fn, args, key)
-        cx.steps = [step if x is st else x for x in cx.steps]
+        step = cx.replace(st, (fn, args, key))
         cx.stage([step], [], f"{fn} {key} on rows", wfs=[t_out], rows_first=True)
-    for st in list(cx.steps):
-        if st[0] != _TIME_OVER or not cx.has(st):
-            continue
+    for st in cx.steps_of(_TIME_OVER):
         fn, args, key = st[0], list(st[1]), st[2]
         if not isinstance(args[2], Var):
             raise ProcessingChainError(f"{fn} ({key}): name the output")
         _rows_in_memory(cx, args[0], fn, key)
-        args[1] = _operand_written_first(cx, args[1], fn, key)
-        step = (fn, args, key)
-        cx.steps = [step if x is st else x for x in cx.steps]
+        args[1] = _operand_in_memory(cx, args[1], fn, key, written_first=True)
+        step = cx.replace(st, (fn, args, key))
         cx.stage([step], [args[2]], f"{fn} {key} on rows")
 
 

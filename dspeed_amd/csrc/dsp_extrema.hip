@@ -1,7 +1,7 @@
 // dsp_extrema.hip -- get_multi_local_extrema (processors/get_multi_local_extrema.py:12-306): the lists of local maxima and minima of a row,
 // found by a hysteresis state machine over its samples.  The only processor here whose result is a list.
 //
-// A wavefront per row, four to a workgroup, the row streamed through registers as dsp_reduce.hip streams it (16 bytes per lane and load,
+// A wavefront per row, four to a workgroup, the row streamed through registers as dsp_row_stream.h lays it out (16 bytes per lane and load,
 // four loads in flight, non-temporal; a sample per lane where start, stride or length are not whole 16-byte vectors).  The machine looks
 // sequential -- "the sample is more than delta below the running maximum: tag that maximum, look for a minimum from here" -- but between
 // two transitions it is a prefix maximum (or minimum) and a comparison per sample.  One sweep, in sweep order (forward: sample p;
@@ -27,42 +27,10 @@
 #include <hip/hip_runtime.h>
 
 #include "dsp_launch.h"
+#include "dsp_row_stream.h"
 #include "dsp_wave.h"
 
 namespace {
-
-template <typename IN>
-struct ExtVec;  // 16 bytes of a row
-template <>
-struct ExtVec<float> {
-    static constexpr int N = 4;
-    typedef float vec __attribute__((ext_vector_type(4)));
-};
-template <>
-struct ExtVec<int16_t> {
-    static constexpr int N = 8;
-    typedef short vec __attribute__((ext_vector_type(8)));
-};
-template <>
-struct ExtVec<uint16_t> {
-    static constexpr int N = 8;
-    typedef unsigned short vec __attribute__((ext_vector_type(8)));
-};
-template <>
-struct ExtVec<double> {
-    static constexpr int N = 2;
-    typedef double vec __attribute__((ext_vector_type(2)));
-};
-template <>
-struct ExtVec<int32_t> {
-    static constexpr int N = 4;
-    typedef int vec __attribute__((ext_vector_type(4)));
-};
-template <>
-struct ExtVec<uint32_t> {
-    static constexpr int N = 4;
-    typedef unsigned int vec __attribute__((ext_vector_type(4)));
-};
 
 // lanes without a source keep their own value: combining a value with itself changes nothing in a running maximum
 template <int CTRL, int ROW_MASK>
@@ -201,7 +169,7 @@ __device__ __forceinline__ void extrema_group(Sweep<T>& S, const T (&x)[N], int 
 template <typename T, typename IN, int N>
 __device__ __forceinline__ void extrema_sweep(Sweep<T>& S, const IN* w, int n, int m, bool back, T dmax, T dmin, T amax, T amin, bool keep, T* out_max,
                                               T* out_min, int lane) {
-    typedef typename ExtVec<IN>::vec vec;
+    typedef typename RowVec<IN>::vec vec;
     S.mx = true;
     S.rv = (T)w[back ? n - 1 : 0];
     S.rp = 0;
@@ -312,9 +280,9 @@ __global__ void __launch_bounds__(256) dsp_extrema_kernel(ExtremaArgs A, int64_t
 
 template <typename T, typename IN>
 void launch_extrema(const ExtremaArgs* A, int64_t n_wf, int vec, int* err, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((n_wf + 3) / 4);  // a wavefront per row, four to a workgroup
+    const unsigned blocks = row_blocks(n_wf);
     if (vec)
-        hipLaunchKernelGGL((dsp_extrema_kernel<T, IN, ExtVec<IN>::N>), dim3(blocks), dim3(256), 0, stream, *A, n_wf, err);
+        hipLaunchKernelGGL((dsp_extrema_kernel<T, IN, RowVec<IN>::N>), dim3(blocks), dim3(256), 0, stream, *A, n_wf, err);
     else
         hipLaunchKernelGGL((dsp_extrema_kernel<T, IN, 1>), dim3(blocks), dim3(256), 0, stream, *A, n_wf, err);
 }

@@ -2,7 +2,7 @@
 // row between its own extremes, and the mode, its left edge and the half width at half maximum read off a histogram.  The first
 // scatter-shaped workload here: a pass for the row's extremes, a second with a data-dependent increment per sample.
 //
-// A wavefront per row, four to a workgroup, rows dealt out workgroup by workgroup; the row is streamed as dsp_reduce.hip streams it (16
+// A wavefront per row, four to a workgroup, rows dealt out workgroup by workgroup; the row is streamed as dsp_row_stream.h lays it out (16
 // bytes per lane and load, four loads in flight; a sample per lane where start, stride or length are not whole 16-byte vectors).
 //   pass 1   minimum, maximum, "a NaN" of the row: per lane, then one exchange across the wavefront.  Pass 2 reads the row again, past the caches this
 //            time: keeping a short row (four groups of loads, 1024 float32 samples) in registers instead measured 6 - 7 % slower at either
@@ -25,32 +25,10 @@
 
 #include "dsp_kernels.h"
 #include "dsp_launch.h"
+#include "dsp_row_stream.h"
 #include "dsp_wave.h"
 
 namespace {
-
-template <typename IN>
-struct HistVec;  // 16 bytes of a row
-template <>
-struct HistVec<float> {
-    static constexpr int N = 4;
-    typedef float vec __attribute__((ext_vector_type(4)));
-};
-template <>
-struct HistVec<int16_t> {
-    static constexpr int N = 8;
-    typedef short vec __attribute__((ext_vector_type(8)));
-};
-template <>
-struct HistVec<uint16_t> {
-    static constexpr int N = 8;
-    typedef unsigned short vec __attribute__((ext_vector_type(8)));
-};
-template <>
-struct HistVec<double> {
-    static constexpr int N = 2;
-    typedef double vec __attribute__((ext_vector_type(2)));
-};
 
 __device__ __forceinline__ float absv(float v) { return __builtin_fabsf(v); }
 __device__ __forceinline__ double absv(double v) { return __builtin_fabs(v); }
@@ -155,7 +133,7 @@ __device__ __forceinline__ T max_in_of(const HistArgs& A, int64_t row) {
 template <typename T, typename IN, int N>
 __global__ void __launch_bounds__(256) dsp_hist_kernel(HistArgs A, int64_t n_wf, int* err) {
     extern __shared__ uint32_t hist_counters[];  // [4][mp]: a region per wavefront
-    typedef typename HistVec<IN>::vec vec;
+    typedef typename RowVec<IN>::vec vec;
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const int n = A.len, m = A.m, mp = (m + 63) & ~63;
     uint32_t* cnt = hist_counters + wave * mp;
@@ -178,7 +156,7 @@ __global__ void __launch_bounds__(256) dsp_hist_kernel(HistArgs A, int64_t n_wf,
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int at = (g0 + k) * per_group + lane * N;
-                    if (at < n) v[k] = stream ? __builtin_nontemporal_load(wv + ((g0 + k) * 64 + lane)) : wv[(g0 + k) * 64 + lane];  // (a vector that starts inside the row lies inside it whole)
+                    if (at < n) v[k] = stream ? __builtin_nontemporal_load(wv + ((g0 + k) * 64 + lane)) : wv[(g0 + k) * 64 + lane];  // (whole vectors: dsp_row_stream.h)
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
@@ -279,7 +257,7 @@ __global__ void __launch_bounds__(256) dsp_hist_stats_kernel(HistArgs A, int64_t
 // rows are dealt out to at most this many workgroups: 8192, or the program's own cap (DSP_OP_HISTOGRAM ip[1])
 unsigned hist_blocks(int64_t n_wf, int32_t max_blocks = 0) {
     const int64_t cap = max_blocks >= 1 && max_blocks < 8192 ? max_blocks : 8192;
-    const int64_t blocks = (n_wf + 3) / 4;
+    const int64_t blocks = row_blocks(n_wf);
     return (unsigned)(blocks < cap ? blocks : cap);
 }
 
@@ -287,7 +265,7 @@ template <typename T, typename IN>
 void launch_hist(const HistArgs* A, int64_t n_wf, int vec, int* err, hipStream_t stream) {
     const unsigned lds = (unsigned)dsp_hist::lds_bytes(A->m);
     if (vec)
-        hipLaunchKernelGGL((dsp_hist_kernel<T, IN, HistVec<IN>::N>), dim3(hist_blocks(n_wf, A->max_blocks)), dim3(256), lds, stream, *A, n_wf, err);
+        hipLaunchKernelGGL((dsp_hist_kernel<T, IN, RowVec<IN>::N>), dim3(hist_blocks(n_wf, A->max_blocks)), dim3(256), lds, stream, *A, n_wf, err);
     else
         hipLaunchKernelGGL((dsp_hist_kernel<T, IN, 1>), dim3(hist_blocks(n_wf, A->max_blocks)), dim3(256), lds, stream, *A, n_wf, err);
 }

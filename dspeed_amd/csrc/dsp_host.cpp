@@ -375,7 +375,7 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     HIP_TRY(hipMalloc((void**)&ch->dev_err, DSP_ERR_WORDS * sizeof(int)));
     HIP_TRY(hipMemset(ch->dev_err, 0, DSP_ERR_WORDS * sizeof(int)));
     const int block_lds = ch->lds_bytes_per_wave * ch->waves_per_block, classic_lds = ch->lds_bytes_per_wave * ch->classic_wpb;
-    int rc = raise_lds(!ch->ext_ok && !ch->hist_ok && !ch->thresh_ok, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
+    int rc = raise_lds(ch->kernel_only == DSP_ROUTE_VM, block_lds, 64 * 1024, "MaxDynamicSharedMemorySize=%d", dsp_internal_set_vm_lds);
     if (!rc) rc = raise_lds(ch->fused_ok, classic_lds, 64 * 1024, "energy kernel, %d", [&](int n) { return dsp_internal_set_energy_lds(ch->fused_trap, ch->fused_npf, n); });
     if (!rc) rc = raise_lds(ch->fir_f16, dsp_fir_f16::lds_bytes(), 64 * 1024, "float16 FIR kernel", dsp_internal_set_fir_f16_lds);
     if (!rc) rc = raise_lds(ch->fir_ok, ch->fir_lds_bytes, 64 * 1024, "FIR kernel, %d", ch->fir.store ? dsp_internal_set_fir_store_lds : dsp_internal_set_fir_mfma_lds);
@@ -396,9 +396,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // Does the kernel of a route run THIS launch?  The program has its shape, the specialised kernels are on, and the buffers of this call keep
 // the 16-byte alignment its wide loads need (the plan vouches for strides and offsets, nobody for the pointers).  dsp_chain_execute asks
 // in the order of dsp_plan_route; a launch whose planned route does not apply runs on the next that does.
-static bool extrema_applies(const dsp_chain* ch, void* const*) { return ch->ext_ok; }  // (always: the program runs nowhere else; unaligned rows: its scalar loads)
-static bool hist_applies(const dsp_chain* ch, void* const*) { return ch->hist_ok; }        // (likewise)
-static bool thresh_applies(const dsp_chain* ch, void* const*) { return ch->thresh_ok; }    // (likewise)
+static bool kernel_only_applies(const dsp_chain* ch, dsp_route route) { return ch->kernel_only == route; }  // (always: the program runs nowhere else; unaligned rows: the kernel's scalar loads)
 static bool scalar_applies(const dsp_chain* ch, void* const*) { return ch->scalar_ok && ch->fused_on; }
 static bool pz_rows_applies(const dsp_chain* ch, void* const* io_ptrs) {
     return ch->pz_ok && ch->fused_on && aligned16(io_ptrs[ch->pio_wf]) && aligned16(io_at(ch, io_ptrs, ch->pio_out));
@@ -553,45 +551,48 @@ static int launched(dsp_chain* ch, void* stream, hipError_t e, const char* what)
     return post_err(ch, stream);
 }
 
+// the shared ending of the kernels that stream rows (dsp_row_stream.h): 16-byte loads where the plan vouches for strides, offsets and length
+// and this call's pointer for the alignment
+extern "C++" template <typename Args, typename Launcher>
+static int launch_on_rows(dsp_chain* ch, int64_t n_wf, void* stream, const Args& A, const RowSource& src, Launcher launcher, const char* what) {
+    const int vec = src.vec && aligned16(A.wf);
+    hipError_t e = (hipError_t)launcher(&A, n_wf, src.dtype, vec, ch->dev_err, (hipStream_t)stream);
+    return launched(ch, stream, e, what);
+}
+
 static int launch_extrema(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
     auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
     ExtremaArgs A = ch->ext;
-    A.wf = io_ptrs[ch->xio_wf];
+    A.wf = io_ptrs[ch->ext_src.io];
     for (int k = 0; k < 4; ++k) A.par[k] = at(ch->xio_par[k]);
     for (int k = 0; k < 2; ++k) {
         A.vt_out[k] = at(ch->xio_vt[k]);
         A.n_out[k] = (uint32_t*)at(ch->xio_n[k]);
     }
-    const int vec = ch->ext_vec && aligned16(A.wf);
-    hipError_t e = (hipError_t)dsp_internal_launch_extrema(&A, n_wf, ch->ext_dtype, vec, ch->dev_err, (hipStream_t)stream);
-    return launched(ch, stream, e, "extrema kernel launch");
+    return launch_on_rows(ch, n_wf, stream, A, ch->ext_src, dsp_internal_launch_extrema, "extrema kernel launch");
 }
 
 static int launch_hist(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
     auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
     HistArgs A = ch->hist;
     auto raw = [&](int k) -> void* { return k < 0 ? nullptr : io_ptrs[k]; };  // (the inputs' offsets travel in the arguments)
-    A.wf = raw(ch->hio_wf);
+    A.wf = raw(ch->hist_src.io);
     A.w_in = raw(ch->hio_w_in);
     A.e_in = raw(ch->hio_e_in);
     A.w_out = at(ch->hio_w);
     A.b_out = at(ch->hio_b);
     A.max_in = at(ch->hio_max_in);
     for (int k = 0; k < 3; ++k) A.s_out[k] = at(ch->hio_s[k]);
-    const int vec = ch->hist_vec && aligned16(A.wf);
-    hipError_t e = (hipError_t)dsp_internal_launch_hist(&A, n_wf, ch->hist_dtype, vec, ch->dev_err, (hipStream_t)stream);
-    return launched(ch, stream, e, "histogram kernel launch");
+    return launch_on_rows(ch, n_wf, stream, A, ch->hist_src, dsp_internal_launch_hist, "histogram kernel launch");
 }
 
 static int launch_thresh(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
     ThreshArgs A = ch->thresh;
-    A.wf = io_ptrs[ch->tio_wf];  // (the inputs' offsets travel in the arguments)
+    A.wf = io_ptrs[ch->thresh_src.io];  // (the inputs' offsets travel in the arguments)
     A.thr = ch->tio_thr < 0 ? nullptr : io_ptrs[ch->tio_thr];
     A.ts = io_at(ch, io_ptrs, ch->tio_ts);
     A.out = io_at(ch, io_ptrs, ch->tio_out);
-    const int vec = ch->thresh_vec && aligned16(A.wf);
-    hipError_t e = (hipError_t)dsp_internal_launch_thresh(&A, n_wf, ch->thresh_dtype, vec, ch->dev_err, (hipStream_t)stream);
-    return launched(ch, stream, e, "threshold kernel launch");
+    return launch_on_rows(ch, n_wf, stream, A, ch->thresh_src, dsp_internal_launch_thresh, "threshold kernel launch");
 }
 
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
@@ -643,11 +644,9 @@ static int launch_pz_rows(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, voi
 
 static int launch_reduce(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
     ReduceArgs A = ch->red;
-    A.wf = io_ptrs[ch->dio_wf];
+    A.wf = io_ptrs[ch->red_src.io];
     bind_reductions(ch, io_ptrs, A);
-    const int vec = ch->red_vec && (reinterpret_cast<uintptr_t>(A.wf) & 15u) == 0;
-    hipError_t e = (hipError_t)dsp_internal_launch_reduce(&A, n_wf, ch->red_dtype, vec, ch->dev_err, (hipStream_t)stream);
-    return launched(ch, stream, e, "reduce kernel launch");
+    return launch_on_rows(ch, n_wf, stream, A, ch->red_src, dsp_internal_launch_reduce, "reduce kernel launch");
 }
 
 static int launch_fir_runs(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
@@ -776,9 +775,9 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (!on_chain_device.ok) return fail(DSP_ERR_HIP, "hipSetDevice(%d) failed", ch->device);
     (void)hipGetLastError();  // launch checks below report this launch, not a stale error of an unrelated earlier call
     // the first kernel, in the order of dsp_plan_route, that takes this launch's pointers
-    if (extrema_applies(ch, io_ptrs)) return launch_extrema(ch, io_ptrs, n_wf, stream);
-    if (hist_applies(ch, io_ptrs)) return launch_hist(ch, io_ptrs, n_wf, stream);
-    if (thresh_applies(ch, io_ptrs)) return launch_thresh(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_EXTREMA)) return launch_extrema(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_HIST)) return launch_hist(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_THRESH)) return launch_thresh(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);

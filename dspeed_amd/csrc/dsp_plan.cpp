@@ -94,6 +94,27 @@ static void note(ChainPlan* ch, const char* fmt, ...) {
     ch->note = buf;
 }
 
+struct PlanCtx;
+// The routes that are no optimisation: ops the interpreter has no case for.  A program that holds one of `opcodes` has the shape `match`
+// accepts, or is refused with `refusal` and the matcher's reason.  (A program never matches two: every shape is exact.)
+struct KernelOnlyRoute {
+    dsp_route route;
+    int opcodes[2];
+    bool (*match)(const PlanCtx& c, const char** why);
+    const char* refusal;
+};
+static bool match_extrema_shape(const PlanCtx& c, const char** why);
+static bool match_hist_shape(const PlanCtx& c, const char** why);
+static bool match_thresh_shape(const PlanCtx& c, const char** why);
+static const KernelOnlyRoute kernel_only_routes[] = {
+    {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
+     "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
+    {DSP_ROUTE_HIST, {DSP_OP_HISTOGRAM, DSP_OP_HISTOGRAM_STATS}, match_hist_shape,
+     "DSP_OP_HISTOGRAM / DSP_OP_HISTOGRAM_STATS (histogram, histogram_stats) run on dsp_hist_kernel only"},
+    {DSP_ROUTE_THRESH, {DSP_OP_MULTI_TIME_POINT_THRESH, DSP_OP_TIME_OVER_THRESHOLD}, match_thresh_shape,
+     "DSP_OP_MULTI_TIME_POINT_THRESH / DSP_OP_TIME_OVER_THRESHOLD (multi_time_point_thresh, time_over_threshold) run on dsp_thresh_kernel only"},
+};
+
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
 struct PlanCtx {
     const dsp_op* ops;
@@ -104,9 +125,7 @@ struct PlanCtx {
     int n_slots, n_sregs, compute_dtype;
     ChainPlan* ch;
     bool f64 = false, i64 = false;
-    bool has_extrema = false;  // a MULTI_EXTREMA among the ops: its counts are the one kind of DSP_U32 output
-    bool has_hist = false;     // a HISTOGRAM or HISTOGRAM_STATS among the ops
-    bool has_thresh = false;   // a MULTI_TIME_POINT_THRESH or TIME_OVER_THRESHOLD among the ops
+    const KernelOnlyRoute* only = nullptr;  // the first route of kernel_only_routes that one of the ops belongs to
     int esz = 4;  // bytes of an LDS element
     // FIR inputs (laid out without the chunk pad); slots that share their LDS region with another
     bool linear[DSP_MAX_SLOTS] = {false}, shares[DSP_MAX_SLOTS] = {false};
@@ -211,10 +230,9 @@ static bool match_pz_rows_shape(const PlanCtx& c) {
 //   LOAD s;  then any of  MIN_MAX of s (once),  AMAX of s (once),  PICKOFF of s at a constant integral time (fixed_time_pickoff, or the plain
 //   sample wf[k]; up to DSP_REDUCE_PICKS),  TIME_POINT_THRESH of s from a constant sample or from MIN_MAX's t_min / t_max (up to
 //   DSP_REDUCE_WALKS);  then STORE_SCALARs of the registers those made, float32 columns
-// The reductions themselves: ops[first ..] on waveform slot `slot` of `len` samples, then the stores; fills A and ch->dio_* (dsp_fir_runs.hip
-// runs the same on the waveform it has just filtered)
+// The reductions themselves: ops[first ..] on waveform slot `slot` of `len` samples, then the stores; fills A, which the caller has cleared, and
+// ch->dio_* (dsp_fir_runs.hip runs the same on the waveform it has just filtered)
 static bool match_reduce_ops(ChainPlan* ch, const dsp_op* ops, int first, int n_ops, int slot, int len, const dsp_io_desc* io, ReduceArgs& A) {
-    memset(&A, 0, sizeof A);
     int reg_of_out[5] = {-1, -1, -1, -1, -1}, reg_of_pick[DSP_REDUCE_PICKS] = {-1, -1, -1, -1};
     int reg_of_walk[DSP_REDUCE_WALKS], walk_thr_io[DSP_REDUCE_WALKS], walk_ts_io[DSP_REDUCE_WALKS];
     for (int k = 0; k < DSP_REDUCE_WALKS; ++k) reg_of_walk[k] = walk_thr_io[k] = walk_ts_io[k] = -1;
@@ -334,27 +352,58 @@ static bool match_reduce_ops(ChainPlan* ch, const dsp_op* ops, int first, int n_
     return true;
 }
 
+static double op_const(const PlanCtx& c, const dsp_op& o, int k);
+static bool need_io(const PlanCtx& c, const dsp_op& o, int kind);
+
+// ---- what the matchers of the kernels that stream rows from memory share (dsp_row_stream.h)
+constexpr unsigned ROWS_F32_LOOP = 1u << DSP_F32 | 1u << DSP_I16 | 1u << DSP_U16, ROWS_F64 = 1u << DSP_F64, ROWS_F64_LOOP = ROWS_F64 | 1u << DSP_I32 | 1u << DSP_U32;
+
+// The rows such a kernel reads: LOAD `ld` takes them whole, as they lie in memory (nothing screened), and their type is one of `f32_loop` /
+// `f64_loop` (bits 1 << DSP_*) for the program's loop.  Fills the block's wf_stride / wf_offset / len and `src`; 16-byte loads where stride,
+// offset and length are whole vectors.  `type_why`: the reason from the type test on.
+template <typename Args>
+static bool bind_rows(const PlanCtx& c, const dsp_op& ld, unsigned f32_loop, unsigned f64_loop, Args& A, RowSource& src, const char** why = nullptr,
+                      const char* type_why = nullptr) {
+    const dsp_io_desc& w = c.io[ld.io];
+    if (ld.ip[0] != 0 || ld.ip[1] != 0 || w.len != c.slot_len[ld.dst]) return false;
+    if (why) *why = type_why;
+    if (!((c.f64 ? f64_loop : f32_loop) >> w.dtype & 1u)) return false;
+    const int64_t es = elem_size(w.dtype);
+    A.wf_stride = w.row_stride;
+    A.wf_offset = w.offset;
+    A.len = w.len;
+    src.io = ld.io;
+    src.dtype = w.dtype;
+    src.vec = (w.row_stride * es) % 16 == 0 && (w.offset * es) % 16 == 0 && (w.len * es) % 16 == 0;
+    return true;
+}
+
+// Operand k of `o`, a per-event value: a constant (`value`, as the loop receives it) or a column of the loop's type (`binding`, `stride`)
+static bool bind_operand(const PlanCtx& c, const dsp_op& o, int k, int& binding, int64_t& stride, double& value) {
+    const dsp_scalar_arg& a = o.sp[k];
+    if (a.kind == DSP_ARG_INPUT && c.io[a.index].dtype == c.compute_dtype) {
+        binding = a.index;
+        stride = c.io[a.index].row_stride;
+    } else if (a.kind == DSP_ARG_CONST) {
+        value = op_const(c, o, k);
+    } else {
+        return false;
+    }
+    return true;
+}
+
 static bool match_reduce_shape(const PlanCtx& c) {
     ChainPlan* ch = c.ch;
     if (c.f64 || c.n_ops < 3 || c.ops[0].opcode != DSP_OP_LOAD) return false;
     const dsp_op& ld = c.ops[0];
-    const dsp_io_desc& w = c.io[ld.io];
-    if ((w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16) || ld.ip[0] != 0 || ld.ip[1] != 0 || w.len < 1 || c.slot_len[ld.dst] != w.len)
-        return false;
     ReduceArgs& A = ch->red;
-    if (!match_reduce_ops(ch, c.ops, 1, c.n_ops, ld.dst, w.len, c.io, A)) return false;
-    if (!(ld.ip[2] & 1) && w.dtype == DSP_F32) A.need_stream = 1;  // (float rows without the promise of LOAD ip[2]: a NaN may sit anywhere)
-    const int es = w.dtype == DSP_F32 ? 4 : 2;
-    A.wf_stride = w.row_stride;
-    A.wf_offset = w.offset;
-    ch->red_dtype = w.dtype;
-    ch->red_vec = (w.row_stride * es) % 16 == 0 && (w.offset * es) % 16 == 0 && (w.len * es) % 16 == 0;
-    ch->dio_wf = ld.io;
+    memset(&A, 0, sizeof A);
+    RowSource src;
+    if (!bind_rows(c, ld, ROWS_F32_LOOP, 0, A, src) || !match_reduce_ops(ch, c.ops, 1, c.n_ops, ld.dst, A.len, c.io, A)) return false;
+    if (!(ld.ip[2] & 1) && src.dtype == DSP_F32) A.need_stream = 1;  // (float rows without the promise of LOAD ip[2]: a NaN may sit anywhere)
+    ch->red_src = src;  // (only now: what a refused shape leaves behind is nobody's)
     return true;
 }
-
-static double op_const(const PlanCtx& c, const dsp_op& o, int k);
-static bool need_io(const PlanCtx& c, const dsp_op& o, int kind);
 
 // Is the program the peak finder's (dsp_extrema.hip)?
 //   LOAD s;  MULTI_EXTREMA of s;  STORE of its two lists;  STORE_SCALAR of its two counts into DSP_U32 columns
@@ -368,12 +417,11 @@ static bool match_extrema_shape(const PlanCtx& c, const char** why) {
         ops[3].opcode != DSP_OP_STORE || ops[4].opcode != DSP_OP_STORE_SCALAR || ops[5].opcode != DSP_OP_STORE_SCALAR)
         return false;
     const dsp_op &ld = ops[0], &ex = ops[1];
-    const dsp_io_desc& w = io[ld.io];
-    if (ex.src != ld.dst || ld.ip[0] != 0 || ld.ip[1] != 0 || w.len != c.slot_len[ld.dst]) return false;
-    *why = "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64, int32 or uint32 rows";
-    if (c.f64 ? (w.dtype != DSP_F64 && w.dtype != DSP_I32 && w.dtype != DSP_U32) : (w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16)) return false;
     ExtremaArgs& A = ch->ext;
     memset(&A, 0, sizeof A);
+    if (ex.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64_LOOP, A, ch->ext_src, why,
+                                       "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64, int32 or uint32 rows"))
+        return false;
     *why = "the two lists are stored once each, the two counts once each into DSP_U32 columns";
     for (int k = 0; k < 2; ++k) ch->xio_vt[k] = ch->xio_n[k] = -1;
     for (int i = 2; i < 4; ++i) {
@@ -391,24 +439,10 @@ static bool match_extrema_shape(const PlanCtx& c, const char** why) {
     *why = "a parameter is a constant or a per-event column of the loop's type";
     for (int k = 0; k < 4; ++k) {
         ch->xio_par[k] = -1;
-        if (ex.sp[k].kind == DSP_ARG_INPUT && io[ex.sp[k].index].dtype == c.compute_dtype) {
-            ch->xio_par[k] = ex.sp[k].index;
-            A.par_stride[k] = io[ex.sp[k].index].row_stride;
-        } else if (ex.sp[k].kind == DSP_ARG_CONST) {
-            A.par_const[k] = op_const(c, ex, k);
-        } else {
-            return false;
-        }
+        if (!bind_operand(c, ex, k, ch->xio_par[k], A.par_stride[k], A.par_const[k])) return false;
     }
-    A.wf_stride = w.row_stride;
-    A.wf_offset = w.offset;
-    A.len = w.len;
     A.m = c.slot_len[ex.dst];
     A.direction = ex.ip[0];
-    const int es = elem_size(w.dtype);
-    ch->ext_dtype = w.dtype;
-    ch->ext_vec = (w.row_stride * es) % 16 == 0 && ((int64_t)w.offset * es) % 16 == 0 && ((int64_t)w.len * es) % 16 == 0;
-    ch->xio_wf = ld.io;
     return true;
 }
 
@@ -437,7 +471,7 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
         if (!is(i, DSP_OP_STORE_SCALAR)) return false;
     HistArgs& A = ch->hist;
     memset(&A, 0, sizeof A);
-    ch->hio_wf = ch->hio_w = ch->hio_b = ch->hio_w_in = ch->hio_e_in = ch->hio_max_in = -1;
+    ch->hio_w = ch->hio_b = ch->hio_w_in = ch->hio_e_in = ch->hio_max_in = -1;
     for (int k = 0; k < 3; ++k) ch->hio_s[k] = -1;
     const dsp_op* st = nullptr;
     if (alone) {
@@ -455,13 +489,12 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
         A.e_in_stride = io[le->io].row_stride;
         A.e_in_offset = io[le->io].offset;
         A.m = c.slot_len[st->src];
-        ch->hist_dtype = c.compute_dtype;
+        ch->hist_src.dtype = c.compute_dtype;
     } else {
         const dsp_op &ld = ops[0], &hi = ops[1];
-        const dsp_io_desc& w = io[ld.io];
-        if (hi.src != ld.dst || ld.ip[0] != 0 || ld.ip[1] != 0 || w.len != c.slot_len[ld.dst]) return false;
-        *why = "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows";
-        if (c.f64 ? w.dtype != DSP_F64 : (w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16)) return false;
+        if (hi.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->hist_src, why,
+                                           "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+            return false;
         *why = "histogram_stats in the same program reads exactly the histogram's weights and borders";
         if (fused) {
             st = &ops[2];
@@ -474,15 +507,8 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
             slot = ops[i].io;
             (ops[i].src == hi.dst ? A.w_stride : A.b_stride) = io[ops[i].io].row_stride;
         }
-        A.wf_stride = w.row_stride;
-        A.wf_offset = w.offset;
-        A.len = w.len;
         A.m = c.slot_len[hi.dst];
         A.max_blocks = hi.ip[1];
-        const int es = elem_size(w.dtype);
-        ch->hist_dtype = w.dtype;
-        ch->hist_vec = (w.row_stride * es) % 16 == 0 && ((int64_t)w.offset * es) % 16 == 0 && ((int64_t)w.len * es) % 16 == 0;
-        ch->hio_wf = ld.io;
     }
     if (st) {
         *why = "mode_out, max_out and fwhm_out are stored once each, in the loop's type";
@@ -493,14 +519,7 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
             A.s_stride[which] = io[ops[i].io].row_stride;
         }
         *why = "max_in is a constant or a per-event column of the loop's type";
-        if (st->sp[0].kind == DSP_ARG_INPUT && io[st->sp[0].index].dtype == c.compute_dtype) {
-            ch->hio_max_in = st->sp[0].index;
-            A.max_in_stride = io[st->sp[0].index].row_stride;
-        } else if (st->sp[0].kind == DSP_ARG_CONST) {
-            A.max_in_const = op_const(c, *st, 0);
-        } else {
-            return false;
-        }
+        if (!bind_operand(c, *st, 0, ch->hio_max_in, A.max_in_stride, A.max_in_const)) return false;
         A.stats = 1;
     }
     return true;
@@ -524,28 +543,16 @@ static bool match_thresh_shape(const PlanCtx& c, const char** why) {
     if (!tot && !one_list && !lists) return false;
     const dsp_op& op = ops[lists ? 2 : 1];
     const dsp_op* ld = ops[0].dst == op.src ? &ops[0] : (lists && ops[1].dst == op.src ? &ops[1] : nullptr);
-    if (!ld || ld->ip[0] != 0 || ld->ip[1] != 0) return false;
-    const dsp_io_desc& w = io[ld->io];
-    *why = "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows";
-    if (c.f64 ? w.dtype != DSP_F64 : (w.dtype != DSP_F32 && w.dtype != DSP_I16 && w.dtype != DSP_U16)) return false;
     ThreshArgs& A = ch->thresh;
     memset(&A, 0, sizeof A);
-    ch->tio_wf = ch->tio_thr = ch->tio_ts = ch->tio_out = -1;
-    auto operand = [&](const dsp_scalar_arg& a, int& binding, int64_t& stride, double& value, int k) {
-        if (a.kind == DSP_ARG_INPUT && io[a.index].dtype == c.compute_dtype) {
-            binding = a.index;
-            stride = io[a.index].row_stride;
-        } else if (a.kind == DSP_ARG_CONST) {
-            value = op_const(c, op, k);
-        } else {
-            return false;
-        }
-        return true;
-    };
+    ch->tio_thr = ch->tio_ts = ch->tio_out = -1;
+    if (!ld || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, ch->thresh_src, why,
+                          "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
     const dsp_op& st = ops[n - 1];
     if (tot) {
         *why = "the threshold is a constant or a per-event column of the loop's type; the count is stored once, in the loop's type";
-        if (!operand(op.sp[0], ch->tio_thr, A.thr_stride, A.thr_const, 0) || st.ip[0] != op.dst || io[st.io].dtype != c.compute_dtype) return false;
+        if (!bind_operand(c, op, 0, ch->tio_thr, A.thr_stride, A.thr_const) || st.ip[0] != op.dst || io[st.io].dtype != c.compute_dtype) return false;
         A.m = 0;
     } else {
         *why = "the thresholds are one list for every row (the op's DSP_IO_TAPS binding, ip[1] < 0) or a list per row, loaded into slot ip[1], in the loop's type";
@@ -562,20 +569,13 @@ static bool match_thresh_shape(const PlanCtx& c, const char** why) {
             A.thr_offset = io[op.io].offset;
         }
         *why = "t_start is a constant or a per-event column of the loop's type; t_out is stored once, in the loop's type";
-        if (!operand(op.sp[0], ch->tio_ts, A.ts_stride, A.ts_const, 0) || st.src != op.dst || io[st.io].dtype != c.compute_dtype) return false;
+        if (!bind_operand(c, op, 0, ch->tio_ts, A.ts_stride, A.ts_const) || st.src != op.dst || io[st.io].dtype != c.compute_dtype) return false;
         A.m = c.slot_len[op.dst];
         A.polarity = op_const(c, op, 1) > 0 ? 1 : -1;
         A.mode = op.ip[0];
     }
     ch->tio_out = st.io;
     A.out_stride = io[st.io].row_stride;
-    A.wf_stride = w.row_stride;
-    A.wf_offset = w.offset;
-    A.len = w.len;
-    const int es = elem_size(w.dtype);
-    ch->thresh_dtype = w.dtype;
-    ch->thresh_vec = (w.row_stride * es) % 16 == 0 && ((int64_t)w.offset * es) % 16 == 0 && ((int64_t)w.len * es) % 16 == 0;
-    ch->tio_wf = ld->io;
     return true;
 }
 
@@ -1165,9 +1165,9 @@ static int check_call(PlanCtx& c) {
     P.n_sregs = n_sregs;
     c.ch->f64 = c.f64;
     c.ch->i64 = c.i64;
-    for (int i = 0; i < n_ops; ++i) c.has_extrema |= c.ops[i].opcode == DSP_OP_MULTI_EXTREMA;
-    for (int i = 0; i < n_ops; ++i) c.has_hist |= c.ops[i].opcode == DSP_OP_HISTOGRAM || c.ops[i].opcode == DSP_OP_HISTOGRAM_STATS;
-    for (int i = 0; i < n_ops; ++i) c.has_thresh |= c.ops[i].opcode == DSP_OP_MULTI_TIME_POINT_THRESH || c.ops[i].opcode == DSP_OP_TIME_OVER_THRESHOLD;
+    for (const KernelOnlyRoute& r : kernel_only_routes)
+        for (int i = 0; i < n_ops && !c.only; ++i)
+            if (c.ops[i].opcode == r.opcodes[0] || c.ops[i].opcode == r.opcodes[1]) c.only = &r;
     return DSP_OK;
 }
 
@@ -1289,7 +1289,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.has_extrema && !c.has_hist && !c.has_thresh)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1340,7 +1340,7 @@ static int bind_io(PlanCtx& c) {
             return fail(DSP_ERR_ARG, "io %d: int32/uint32/float64 rows select the float64 loop (compute_dtype DSP_F64)", k);
         const bool is_out = a.kind == DSP_IO_WF_OUT || a.kind == DSP_IO_SCALAR_OUT;
         if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT) &&
-            !(c.has_extrema && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32))  // (the counts of MULTI_EXTREMA: match_extrema_shape sees to the rest)
+            !(c.only && c.only->route == DSP_ROUTE_EXTREMA && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32))  // (the counts of MULTI_EXTREMA: match_extrema_shape sees to the rest)
             return fail(DSP_ERR_ARG, "io %d: outputs have the chain's compute type or DSP_BOOL, taps the compute type", k);
         if ((a.dtype == DSP_BOOL || a.dtype == DSP_I64 || a.dtype == DSP_U64) && a.kind != DSP_IO_SCALAR_IN && a.kind != DSP_IO_SCALAR_OUT && !(a.dtype == DSP_BOOL && is_out))
             return fail(DSP_ERR_ARG, "io %d: DSP_BOOL / DSP_I64 / DSP_U64 are types of per-event columns (DSP_BOOL also of waveform outputs)", k);
@@ -2195,23 +2195,10 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
     if (const int rc = bind_io(c)) return rc;
     if (const int rc = lower_ops(c)) return rc;
     fold_load_bl_subtract(c);
-    if (c.has_extrema) {  // no interpreter op behind it: its own kernel or nothing
+    if (c.only) {  // no interpreter op behind it: its own kernel or nothing
         const char* why = "";
-        ch->ext_ok = match_extrema_shape(c, &why);
-        if (!ch->ext_ok)
-            return fail(DSP_ERR_UNSUPPORTED, "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only, on rows in memory: %s", why);
-    }
-    if (c.has_hist) {  // nor behind these two
-        const char* why = "";
-        ch->hist_ok = match_hist_shape(c, &why);
-        if (!ch->hist_ok)
-            return fail(DSP_ERR_UNSUPPORTED, "DSP_OP_HISTOGRAM / DSP_OP_HISTOGRAM_STATS (histogram, histogram_stats) run on dsp_hist_kernel only, on rows in memory: %s", why);
-    }
-    if (c.has_thresh) {  // nor these
-        const char* why = "";
-        ch->thresh_ok = match_thresh_shape(c, &why);
-        if (!ch->thresh_ok)
-            return fail(DSP_ERR_UNSUPPORTED, "DSP_OP_MULTI_TIME_POINT_THRESH / DSP_OP_TIME_OVER_THRESHOLD (multi_time_point_thresh, time_over_threshold) run on dsp_thresh_kernel only, on rows in memory: %s", why);
+        if (!c.only->match(c, &why)) return fail(DSP_ERR_UNSUPPORTED, "%s, on rows in memory: %s", c.only->refusal, why);
+        ch->kernel_only = c.only->route;
     }
     match_shapes(c);
     fold_scaled_thresholds(c);
@@ -2222,9 +2209,7 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
 }
 
 dsp_route dsp_plan_route(const ChainPlan* ch) {
-    if (ch && ch->ext_ok) return DSP_ROUTE_EXTREMA;  // (whatever the switches say: the interpreter has no such op)
-    if (ch && ch->hist_ok) return DSP_ROUTE_HIST;
-    if (ch && ch->thresh_ok) return DSP_ROUTE_THRESH;
+    if (ch && ch->kernel_only != DSP_ROUTE_VM) return ch->kernel_only;  // (whatever the switches say: the interpreter has no such op)
     if (!ch || !ch->fused_on) return DSP_ROUTE_VM;
     if (ch->scalar_ok) return DSP_ROUTE_SCALAR;
     if (ch->pz_ok) return DSP_ROUTE_PZ_ROWS;

@@ -17,6 +17,14 @@
 
 constexpr int LDS_BYTES_PER_CU = 160 * 1024;
 
+// Where a kernel that streams rows from memory (dsp_row_stream.h) finds them: the binding of the rows, their type, and whether strides, offsets
+// and length are whole 16-byte vectors (the launch adds the alignment of the pointer it is handed)
+struct RowSource {
+    int io = -1;
+    int dtype = DSP_F32;
+    bool vec = false;
+};
+
 // (dsp_plan.cpp; exported for the CPU tests)
 extern "C" void dsp_internal_plan_energy_carries(int Ci, int S, const int32_t* lags, EnergyPlan* plan);
 
@@ -78,22 +86,25 @@ struct ChainPlan {
     // streaming reductions of rows (dsp_reduce.hip)
     bool red_ok = false;
     ReduceArgs red{};
-    int dio_wf = -1, dio_out[5] = {-1, -1, -1, -1, -1}, dio_pick[DSP_REDUCE_PICKS] = {-1, -1, -1, -1}, red_dtype = DSP_F32;
+    RowSource red_src{};
+    int dio_out[5] = {-1, -1, -1, -1, -1}, dio_pick[DSP_REDUCE_PICKS] = {-1, -1, -1, -1};
     int dio_walk[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1}, dio_walk_thr[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1},
         dio_walk_ts[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1};
-    bool red_vec = false;  // rows keep 16-byte alignment and hold whole 16-byte vectors
+    // The ops no interpreter case stands behind: a program that holds one runs on that op's kernel or is refused (the table of these routes
+    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST or DSP_ROUTE_THRESH; DSP_ROUTE_VM: the program holds none.
+    dsp_route kernel_only = DSP_ROUTE_VM;
     // the peak finder (dsp_extrema.hip): the one kernel a program with MULTI_EXTREMA runs on
-    bool ext_ok = false, ext_vec = false;
     ExtremaArgs ext{};
-    int xio_wf = -1, xio_par[4] = {-1, -1, -1, -1}, xio_vt[2] = {-1, -1}, xio_n[2] = {-1, -1}, ext_dtype = DSP_F32;
+    RowSource ext_src{};
+    int xio_par[4] = {-1, -1, -1, -1}, xio_vt[2] = {-1, -1}, xio_n[2] = {-1, -1};
     // histogram and histogram_stats (dsp_hist.hip): the one kernel a program with HISTOGRAM or HISTOGRAM_STATS runs on
-    bool hist_ok = false, hist_vec = false;
     HistArgs hist{};
-    int hio_wf = -1, hio_w = -1, hio_b = -1, hio_w_in = -1, hio_e_in = -1, hio_max_in = -1, hio_s[3] = {-1, -1, -1}, hist_dtype = DSP_F32;
+    RowSource hist_src{};  // (io < 0: histogram_stats alone, on weights and edges read from rows; dtype: the loop's)
+    int hio_w = -1, hio_b = -1, hio_w_in = -1, hio_e_in = -1, hio_max_in = -1, hio_s[3] = {-1, -1, -1};
     // multi_time_point_thresh and time_over_threshold (dsp_thresh.hip): the one kernel a program with either op runs on
-    bool thresh_ok = false, thresh_vec = false;
     ThreshArgs thresh{};
-    int tio_wf = -1, tio_thr = -1, tio_ts = -1, tio_out = -1, thresh_dtype = DSP_F32;
+    RowSource thresh_src{};
+    int tio_thr = -1, tio_ts = -1, tio_out = -1;
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};

@@ -11,27 +11,10 @@
 
 #include "dsp_launch.h"
 #include "dsp_reduce_tail.h"
+#include "dsp_row_stream.h"
 #include "dsp_wave.h"
 
 namespace {
-
-template <typename IN>
-struct RowVec;  // 16 bytes of a row
-template <>
-struct RowVec<float> {
-    static constexpr int N = 4;
-    typedef float vec __attribute__((ext_vector_type(4)));
-};
-template <>
-struct RowVec<int16_t> {
-    static constexpr int N = 8;
-    typedef short vec __attribute__((ext_vector_type(8)));
-};
-template <>
-struct RowVec<uint16_t> {
-    static constexpr int N = 8;
-    typedef unsigned short vec __attribute__((ext_vector_type(8)));
-};
 
 // VEC: row starts, stride and length are whole 16-byte vectors (every Ge waveform is); otherwise a sample per lane and load
 template <typename IN, bool VEC>
@@ -59,7 +42,7 @@ __global__ void __launch_bounds__(256) dsp_reduce_kernel(ReduceArgs A, int64_t n
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int at = (g0 + k) * per_group + lane * N;
-                if (at < n) x[k] = __builtin_nontemporal_load(wv + ((g0 + k) * 64 + lane));  // (a vector that starts inside the row lies inside it whole)
+                if (at < n) x[k] = __builtin_nontemporal_load(wv + ((g0 + k) * 64 + lane));  // (whole vectors: dsp_row_stream.h)
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -90,7 +73,7 @@ __global__ void __launch_bounds__(256) dsp_reduce_kernel(ReduceArgs A, int64_t n
 
 template <typename IN>
 static void launch_reduce(const ReduceArgs* A, int64_t n_wf, int vec, int* err, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((n_wf + 3) / 4);  // a wavefront per row, four to a workgroup
+    const unsigned blocks = row_blocks(n_wf);
     if (vec)
         hipLaunchKernelGGL((dsp_reduce_kernel<IN, true>), dim3(blocks), dim3(256), 0, stream, *A, n_wf, err);
     else

@@ -2,8 +2,8 @@
 // from one starting sample; and time_over_threshold (processors/time_over_threshold.py:11-48): the number of samples above a threshold.
 //
 // A wavefront per row, four to a workgroup, nothing in LDS.
-//   pass 1   the row is streamed as dsp_reduce.hip streams it (16 bytes per lane and load, four loads in flight; a sample per lane, eight in
-//            flight, where start, stride or length are not whole 16-byte vectors): "a NaN" of the row, which both processors need, and the
+//   pass 1   the row is streamed through registers (dsp_row_stream.h: 16 bytes per lane and load, four loads in flight; a sample per lane,
+//            eight in flight, where start, stride or length are not whole 16-byte vectors): "a NaN" of the row, which both processors need, and the
 //            count of samples above the threshold, which is time_over_threshold whole.
 //   ranking  a threshold per lane (m <= 64); its rank is the number of thresholds below it (or equal with a lower index); one
 //            forward permute puts thresholds and their indices in ascending order, one per lane.  The first one >= w[t_start] splits them.
@@ -21,40 +21,10 @@
 #include <hip/hip_runtime.h>
 
 #include "dsp_launch.h"
+#include "dsp_row_stream.h"
 #include "dsp_wave.h"
 
 namespace {
-
-template <typename IN>
-struct ThreshVec;  // 16 bytes of a row
-template <>
-struct ThreshVec<float> {
-    static constexpr int N = 4;
-    typedef float vec __attribute__((ext_vector_type(4)));
-};
-template <>
-struct ThreshVec<int16_t> {
-    static constexpr int N = 8;
-    typedef short vec __attribute__((ext_vector_type(8)));
-};
-template <>
-struct ThreshVec<uint16_t> {
-    static constexpr int N = 8;
-    typedef unsigned short vec __attribute__((ext_vector_type(8)));
-};
-template <>
-struct ThreshVec<double> {
-    static constexpr int N = 2;
-    typedef double vec __attribute__((ext_vector_type(2)));
-};
-
-// the value of lane `to`'s sender: every lane sends v to lane `to` (a permutation of the lanes)
-__device__ __forceinline__ int wave_send(int v, int to) { return __builtin_amdgcn_ds_permute(to << 2, v); }
-__device__ __forceinline__ float wave_send(float v, int to) { return __int_as_float(wave_send(__float_as_int(v), to)); }
-__device__ __forceinline__ double wave_send(double v, int to) {
-    const int lo = wave_send(__double2loint(v), to), hi = wave_send(__double2hiint(v), to);
-    return __hiloint2double(hi, lo);
-}
 
 // the time of a crossing between w[i] = wi and w[i + pol] = wn (time_point_thresh.py:335-358)
 template <typename T>
@@ -74,7 +44,6 @@ __device__ __forceinline__ T crossing_time(int mode, int pol, int i, T wi, T wn,
 // N: samples per lane and load (1, or those of a 16-byte vector: rows then start on 16-byte boundaries and hold whole vectors)
 template <typename T, typename IN, int N>
 __global__ void __launch_bounds__(256) dsp_thresh_kernel(ThreshArgs A, int64_t n_wf, int* err) {
-    typedef typename ThreshVec<IN>::vec vec;
     constexpr int K = N > 1 ? 4 : 8;  // loads in flight
     const int lane = lane_id();
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -85,37 +54,18 @@ __global__ void __launch_bounds__(256) dsp_thresh_kernel(ThreshArgs A, int64_t n
     // time_over_threshold's threshold (multi_time_point_thresh counts nothing)
     const T above = m == 0 ? (A.thr ? ((const T*)A.thr)[row * A.thr_stride] : (T)A.thr_const) : (T)0;
 
-    // pass 1: samples [g * 64 N + lane * N, + N) of group g, K groups requested before the first is looked at
-    const int per_group = 64 * N, n_groups = (n + per_group - 1) / per_group;
+    // pass 1
     bool bad = false;
     int count = 0;
-    for (int g0 = 0; g0 < n_groups; g0 += K) {
+    for (int g0 = 0; g0 < row_groups<N>(n); g0 += K) {
         T x[K][N];
-        if constexpr (N > 1) {
-            const vec* wv = (const vec*)w;
-            vec v[K] = {};
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const int at = (g0 + k) * per_group + lane * N;
-                if (at < n) v[k] = __builtin_nontemporal_load(wv + ((g0 + k) * 64 + lane));  // (a vector that starts inside the row lies inside it whole)
-            }
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int j = 0; j < N; ++j) x[k][j] = (T)v[k][j];
-        } else {
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const int at = (g0 + k) * 64 + lane;
-                x[k][0] = at < n ? (T)w[at] : (T)0;
-            }
-        }
+        load_row_groups<T, IN, N, K>(x, w, n, g0, lane);
 #pragma unroll
         for (int k = 0; k < K; ++k)
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 const T v = x[k][j];
-                const bool in = (g0 + k) * per_group + lane * N + j < n;
+                const bool in = in_row<N>(g0, k, j, lane) < n;
                 bad |= in && v != v;
                 count += (in && v > above) ? 1 : 0;
             }
@@ -192,9 +142,9 @@ __global__ void __launch_bounds__(256) dsp_thresh_kernel(ThreshArgs A, int64_t n
 
 template <typename T, typename IN>
 void launch_thresh(const ThreshArgs* A, int64_t n_wf, int vec, int* err, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((n_wf + 3) / 4);  // a wavefront per row, four to a workgroup
+    const unsigned blocks = row_blocks(n_wf);
     if (vec)
-        hipLaunchKernelGGL((dsp_thresh_kernel<T, IN, ThreshVec<IN>::N>), dim3(blocks), dim3(256), 0, stream, *A, n_wf, err);
+        hipLaunchKernelGGL((dsp_thresh_kernel<T, IN, RowVec<IN>::N>), dim3(blocks), dim3(256), 0, stream, *A, n_wf, err);
     else
         hipLaunchKernelGGL((dsp_thresh_kernel<T, IN, 1>), dim3(blocks), dim3(256), 0, stream, *A, n_wf, err);
 }

@@ -85,6 +85,14 @@ __device__ __forceinline__ bool wave_any(bool p) { return __any(p) != 0; }
 
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// the value of lane `to`'s sender: every lane sends v to lane `to` (a permutation of the lanes)
+__device__ __forceinline__ int wave_send(int v, int to) { return __builtin_amdgcn_ds_permute(to << 2, v); }
+__device__ __forceinline__ float wave_send(float v, int to) { return __int_as_float(wave_send(__float_as_int(v), to)); }
+__device__ __forceinline__ double wave_send(double v, int to) {
+    const int lo = wave_send(__double2loint(v), to), hi = wave_send(__double2hiint(v), to);
+    return __hiloint2double(hi, lo);
+}
+
 // LDS element index of sample e of a slot (e / C via a float reciprocal: exact for e < 2^20, C % 8 == 0)
 template <typename SlotRef>  // (DevSlot in any address space)
 __device__ __forceinline__ int padded_index(const SlotRef& s, int e) {

@@ -5,7 +5,8 @@
 //
 // Two kinds of programs: (1) op lists drawn from every opcode with operands that are valid most of the time (so that the validation, the
 // constant evaluation and the LDS packing behind it are reached) and garbage some of the time (so that the validation itself is); (2) the
-// shapes of the specialised kernels (energy chain, lane-per-waveform rows, matrix-core FIR, pole-zero rows, reductions, current branch)
+// shapes of the specialised kernels (energy chain, lane-per-waveform rows, matrix-core FIR, pole-zero rows, reductions, current branch, the
+// peak finder, the histogram and the threshold kernels)
 // with random lengths, offsets, strides and one field mutated.  A program the planner accepts must satisfy its invariants:
 //   * LDS: every slot's region inside the wavefront's slot area, regions of slots alive at the same time disjoint, sample 0 behind its
 //     zero guard, the register file and the scratch area behind the slots, the whole at most a CU's 160 kB;
@@ -599,6 +600,124 @@ Prog scalar_shape() {
     return p;
 }
 
+// ---- the kernels that stream rows from memory and have no interpreter op behind them (dsp_extrema.hip, dsp_hist.hip, dsp_thresh.hip)
+// a per-event operand: a constant, or a column of the loop's type -- or, now and then, of another
+dsp_scalar_arg loop_arg(Prog& p, double lo = 0.0) {
+    if (chance(0.5)) return cst(pick({lo, 1.0, 12.5, 100.0, 4000.0}));
+    if (chance(0.15)) return sarg(p);
+    dsp_scalar_arg a{};
+    a.kind = DSP_ARG_INPUT;
+    a.index = add_io(p, DSP_IO_SCALAR_IN, chance(0.85) ? p.dtype : pick({DSP_F32, DSP_F64, DSP_I16, DSP_U32}), 1, chance(0.1) ? rnd(0, 3) : 0, pick({1, 1, 1, 0, 2}));
+    return a;
+}
+// LOAD of a fresh slot from rows with a random start and stride: whole 16-byte vectors half of the time
+int load_rows(Prog& p, int len, int dtype) {
+    const int s = new_slot(p, len);
+    const int off = pick({0, 0, 0, 8, 16, 3, rnd(0, 40)}), stride = off + len + pick({0, 0, 0, 8, 16, 1, rnd(0, 40)});
+    dsp_op o = op0(DSP_OP_LOAD);
+    o.dst = s, o.io = add_io(p, DSP_IO_WF_IN, dtype, len, off, chance(0.05) ? 0 : stride);
+    if (chance(0.05)) o.ip[0] = rnd(0, off), o.ip[1] = rnd(0, stride - off - len);
+    p.ops.push_back(o);
+    return s;
+}
+int rows_out(Prog& p, int slot) {
+    const int off = pick({0, 0, 4, 1});
+    dsp_op st = op0(DSP_OP_STORE);
+    st.src = slot, st.io = add_io(p, DSP_IO_WF_OUT, chance(0.05) ? DSP_BOOL : p.dtype, p.slots[slot], off, off + p.slots[slot] + pick({0, 0, 4, 3}));
+    p.ops.push_back(st);
+    return st.io;
+}
+void store_regs(Prog& p, int first, int n, int dtype) {
+    for (int k = 0; k < n; ++k) {
+        dsp_op st = op0(DSP_OP_STORE_SCALAR);
+        st.io = chance(0.9) ? add_io(p, DSP_IO_SCALAR_OUT, dtype, 1, chance(0.1) ? rnd(0, 3) : 0, pick({1, 1, 2})) : scalar_out(p);
+        st.ip[0] = first + k;
+        p.ops.push_back(st);
+    }
+}
+
+// LOAD, MULTI_EXTREMA, STORE of the two lists, STORE_SCALAR of the two counts (match_extrema_shape)
+Prog extrema_shape() {
+    Prog p;
+    p.dtype = chance(0.3) ? DSP_F64 : DSP_F32;
+    const int len = some_len(), m = chance(0.9) ? rnd(1, len > 64 ? 64 : (len > 1 ? len - 1 : 1)) : some_len();
+    const int s = load_rows(p, len, in_dtype(p)), a = new_slot(p, m), b = new_slot(p, m), r = new_sregs(p, 2);
+    dsp_op ex = op0(DSP_OP_MULTI_EXTREMA);
+    ex.src = s, ex.dst = a, ex.ip[1] = b, ex.ip[2] = r, ex.ip[0] = pick({0, 0, 1, 3, 3, 2});
+    for (int k = 0; k < 4; ++k) ex.sp[k] = loop_arg(p);
+    p.ops.push_back(ex);
+    const bool swap = chance(0.3);
+    rows_out(p, swap ? b : a);
+    rows_out(p, chance(0.95) ? (swap ? a : b) : a);
+    store_regs(p, r, 2, DSP_U32);
+    if (chance(0.2)) std::swap(p.ops[4], p.ops[5]);
+    return p;
+}
+
+// the three shapes of match_hist_shape: histogram stored; histogram with histogram_stats on its counters; histogram_stats alone
+Prog hist_shape() {
+    Prog p;
+    p.dtype = chance(0.3) ? DSP_F64 : DSP_F32;
+    const int m = pick({1, 4, 64, 100, 2048, 2049, rnd(1, 300)}), form = rnd(0, 2);
+    if (form == 2) {  // LOAD weights, LOAD edges (either first), HISTOGRAM_STATS, STORE_SCALAR x 3
+        const bool edges_first = chance(0.3);
+        const int wrong = chance(0.1) ? in_dtype(p) : p.dtype;
+        const int x = load_rows(p, edges_first ? m + 1 : m, chance(0.5) ? wrong : p.dtype), y = load_rows(p, edges_first ? m : m + 1, p.dtype), r = new_sregs(p, 3);
+        dsp_op st = op0(DSP_OP_HISTOGRAM_STATS);
+        st.src = edges_first ? y : x, st.ip[0] = edges_first ? x : y, st.ip[1] = r, st.sp[0] = loop_arg(p);
+        p.ops.push_back(st);
+        store_regs(p, r, 3, p.dtype);
+        return p;
+    }
+    const int s = load_rows(p, some_len(), in_dtype(p)), w = new_slot(p, m), b = new_slot(p, chance(0.95) ? m + 1 : m);
+    dsp_op hi = op0(DSP_OP_HISTOGRAM);
+    hi.src = s, hi.dst = w, hi.ip[0] = b, hi.ip[1] = pick({0, 0, 0, 1, 64, 9000, -1});
+    p.ops.push_back(hi);
+    int r = -1;
+    if (form == 1) {
+        r = new_sregs(p, 3);
+        dsp_op st = op0(DSP_OP_HISTOGRAM_STATS);
+        st.src = chance(0.95) ? w : s, st.ip[0] = b, st.ip[1] = r, st.sp[0] = loop_arg(p);
+        p.ops.push_back(st);
+    }
+    if (form == 0 || chance(0.5)) {
+        const bool swap = chance(0.3);
+        rows_out(p, swap ? b : w);
+        rows_out(p, chance(0.95) ? (swap ? w : b) : w);
+    }
+    if (form == 1) store_regs(p, r, 3, p.dtype);
+    return p;
+}
+
+// the three shapes of match_thresh_shape: time_over_threshold; multi_time_point_thresh with one list of thresholds, or a list per row
+Prog thresh_shape() {
+    Prog p;
+    p.dtype = chance(0.3) ? DSP_F64 : DSP_F32;
+    const int len = some_len(), form = rnd(0, 2);
+    if (form == 0) {  // LOAD, TIME_OVER_THRESHOLD, STORE_SCALAR
+        const int s = load_rows(p, len, in_dtype(p)), r = new_sregs(p, 1);
+        dsp_op o = op0(DSP_OP_TIME_OVER_THRESHOLD);
+        o.src = s, o.dst = r, o.sp[0] = loop_arg(p);
+        p.ops.push_back(o);
+        store_regs(p, r, 1, p.dtype);
+        return p;
+    }
+    const int m = pick({1, 3, 64, 65, rnd(1, 64)});
+    const bool lists = form == 2, list_first = lists && chance(0.3);
+    int thr = -1;
+    if (list_first) thr = load_rows(p, m, chance(0.9) ? p.dtype : in_dtype(p));
+    const int s = load_rows(p, len, in_dtype(p));
+    if (lists && !list_first) thr = load_rows(p, chance(0.95) ? m : m + 1, chance(0.9) ? p.dtype : in_dtype(p));
+    const int t = new_slot(p, m);
+    dsp_op o = op0(DSP_OP_MULTI_TIME_POINT_THRESH);
+    o.src = s, o.dst = t, o.ip[0] = pick({'i', 'a', 'f', 'b', 'c', 'r', 'n', 'l', 'l', 'z'}), o.ip[1] = lists ? thr : -1;
+    if (!lists) o.io = add_io(p, DSP_IO_TAPS, chance(0.95) ? p.dtype : DSP_F32, chance(0.95) ? m : m + 1, pick({0, 0, 2}), 0);
+    o.sp[0] = loop_arg(p), o.sp[1] = chance(0.95) ? cst(pick({1.0, -1.0, 2.5, 0.0})) : loop_arg(p);
+    p.ops.push_back(o);
+    rows_out(p, t);
+    return p;
+}
+
 void mutate(Prog& p) {
     if (p.ops.empty()) return;
     dsp_op& o = p.ops[rnd(0, (int)p.ops.size() - 1)];
@@ -666,7 +785,7 @@ bool check(const Prog& p, const ChainPlan& c) {
             if (p.io[k].kind == DSP_IO_SCALAR_IN) REQUIRE(p.io[k].dtype != DSP_F32 && p.io[k].dtype != DSP_F64, "integer program reads a float column");
     } else {
         for (size_t k = 0; k < p.io.size(); ++k)
-            if (p.io[k].kind == DSP_IO_SCALAR_OUT || p.io[k].kind == DSP_IO_WF_OUT) REQUIRE(p.io[k].dtype == p.dtype || p.io[k].dtype == DSP_BOOL, "output %zu of type %d in a chain of type %d", k, p.io[k].dtype, p.dtype);
+            if (p.io[k].kind == DSP_IO_SCALAR_OUT || p.io[k].kind == DSP_IO_WF_OUT) REQUIRE(p.io[k].dtype == p.dtype || p.io[k].dtype == DSP_BOOL || (c.kernel_only == DSP_ROUTE_EXTREMA && p.io[k].kind == DSP_IO_SCALAR_OUT && p.io[k].dtype == DSP_U32), "output %zu of type %d in a chain of type %d", k, p.io[k].dtype, p.dtype);
     }
     REQUIRE(P.n_ops >= 1 && P.n_ops <= DSP_MAX_OPS + DSP_MAX_SLOTS, "device ops %d", P.n_ops);
     REQUIRE(P.team >= 1 && P.team <= 3, "team %d", P.team);
@@ -712,8 +831,8 @@ bool check(const Prog& p, const ChainPlan& c) {
             if (c.pio_mm[k] >= 0) REQUIRE(c.pz.mm_on && io_ok(c.pio_mm[k], DSP_IO_SCALAR_OUT) && c.pz.mm_stride[k] == p.io[c.pio_mm[k]].row_stride, "pole-zero rows: min_max output %d", k);
     }
     if (c.red_ok) {
-        REQUIRE(io_ok(c.dio_wf, DSP_IO_WF_IN), "reduce kernel: row binding");
-        REQUIRE(c.red.wf_offset == p.io[c.dio_wf].offset && c.red.wf_stride == p.io[c.dio_wf].row_stride && c.red.len == p.io[c.dio_wf].len, "reduce kernel: the row binding's offset / stride / length");
+        REQUIRE(io_ok(c.red_src.io, DSP_IO_WF_IN), "reduce kernel: row binding");
+        REQUIRE(c.red.wf_offset == p.io[c.red_src.io].offset && c.red.wf_stride == p.io[c.red_src.io].row_stride && c.red.len == p.io[c.red_src.io].len, "reduce kernel: the row binding's offset / stride / length");
         for (int k = 0; k < DSP_REDUCE_PICKS; ++k)
             if (c.dio_pick[k] >= 0) REQUIRE(c.red.pick_at[k] >= -1 && c.red.pick_at[k] < c.red.len, "reduce kernel: pick-off at %d of %d", c.red.pick_at[k], c.red.len);
         for (int k = 0; k < DSP_REDUCE_WALKS; ++k)
@@ -725,7 +844,7 @@ bool check(const Prog& p, const ChainPlan& c) {
             if (from == 3) REQUIRE(io_ok(c.dio_walk_ts[k], DSP_IO_SCALAR_IN) && p.io[c.dio_walk_ts[k]].dtype == DSP_F32 && c.red.walk_ts_stride[k] == p.io[c.dio_walk_ts[k]].row_stride, "reduce kernel: walk %d's start column", k);
             if (c.red.walk_thr_scaled[k]) REQUIRE(io_ok(c.dio_walk_thr[k], DSP_IO_SCALAR_IN), "reduce kernel: walk %d scales no column", k);
         }
-        if (!c.red.need_stream) REQUIRE(c.dio_out[0] < 0 && c.dio_out[4] < 0 && (p.io[c.dio_wf].dtype != DSP_F32 || (p.ops[0].ip[2] & 1)), "reduce kernel: no pass over rows that need one");
+        if (!c.red.need_stream) REQUIRE(c.dio_out[0] < 0 && c.dio_out[4] < 0 && (p.io[c.red_src.io].dtype != DSP_F32 || (p.ops[0].ip[2] & 1)), "reduce kernel: no pass over rows that need one");
     }
     if (c.runs_ok) {
         REQUIRE(!c.red_ok && !c.fir_ok, "run-length FIR beside another kernel of the same program");
@@ -751,6 +870,66 @@ bool check(const Prog& p, const ChainPlan& c) {
         REQUIRE(c.cur.win_len < c.cur.n_in && c.cur.n_c == c.cur.win_len - c.cur.ac_lag && c.cur.n_up % 16 == 0 && c.cur.ma_len % 16 == 0 && c.cur.ma_len <= 112 && c.cur.up_shift >= 0 && c.cur.up_shift <= 4,
                 "current kernel geometry");
         REQUIRE(c.cur_lds_bytes > 0 && c.cur_lds_bytes <= LDS_BYTES_PER_CU, "current kernel LDS %d", c.cur_lds_bytes);
+    }
+    // the kernels that stream rows from memory: the row binding, the per-event operands, the outputs
+    auto rows_vec = [&](int k) {
+        const int64_t es = dsp_elem_size(p.io[k].dtype);
+        return (p.io[k].row_stride * es) % 16 == 0 && ((int64_t)p.io[k].offset * es) % 16 == 0 && ((int64_t)p.io[k].len * es) % 16 == 0;
+    };
+    auto column_ok = [&](int k, int64_t stride) { return io_ok(k, DSP_IO_SCALAR_IN) && p.io[k].dtype == p.dtype && stride == p.io[k].row_stride; };
+    auto out_ok = [&](int k, int kind, int64_t stride) { return io_ok(k, kind) && stride == p.io[k].row_stride; };
+    if (c.kernel_only == DSP_ROUTE_EXTREMA) {
+        const ExtremaArgs& A = c.ext;
+        REQUIRE(io_ok(c.ext_src.io, DSP_IO_WF_IN), "extrema kernel: row binding");
+        REQUIRE(A.wf_offset == p.io[c.ext_src.io].offset && A.wf_stride == p.io[c.ext_src.io].row_stride && A.len == p.io[c.ext_src.io].len, "extrema kernel: the row binding's offset / stride / length");
+        for (int k = 0; k < 4; ++k)
+            if (c.xio_par[k] >= 0) REQUIRE(column_ok(c.xio_par[k], A.par_stride[k]), "extrema kernel: parameter column %d", k);
+        for (int k = 0; k < 2; ++k) {
+            REQUIRE(out_ok(c.xio_vt[k], DSP_IO_WF_OUT, A.vt_stride[k]) && p.io[c.xio_vt[k]].len == A.m, "extrema kernel: list %d", k);
+            REQUIRE(out_ok(c.xio_n[k], DSP_IO_SCALAR_OUT, A.n_stride[k]) && p.io[c.xio_n[k]].dtype == DSP_U32, "extrema kernel: count %d", k);
+        }
+        REQUIRE(A.m >= 1 && A.m < A.len && A.direction >= 0 && A.direction <= 3 && A.direction != 2, "extrema kernel: lists of %d from rows of %d, direction %d", A.m, A.len, A.direction);
+        if (c.ext_src.vec) REQUIRE(rows_vec(c.ext_src.io), "extrema kernel: vector loads on rows that are not whole 16-byte vectors");
+    }
+    if (c.kernel_only == DSP_ROUTE_HIST) {
+        const HistArgs& A = c.hist;
+        REQUIRE(A.m >= 1 && A.m <= DSP_HIST_MAX_BINS, "histogram kernel: %d bins", A.m);
+        if (c.hist_src.io >= 0) {
+            REQUIRE(io_ok(c.hist_src.io, DSP_IO_WF_IN), "histogram kernel: row binding");
+            REQUIRE(A.wf_offset == p.io[c.hist_src.io].offset && A.wf_stride == p.io[c.hist_src.io].row_stride && A.len == p.io[c.hist_src.io].len, "histogram kernel: the row binding's offset / stride / length");
+            REQUIRE(c.hio_w_in < 0 && c.hio_e_in < 0, "histogram kernel: a row and weights read from memory");
+            if (c.hist_src.vec) REQUIRE(rows_vec(c.hist_src.io), "histogram kernel: vector loads on rows that are not whole 16-byte vectors");
+        } else {
+            REQUIRE(A.stats && !c.hist_src.vec, "histogram kernel: neither a row nor histogram_stats alone");
+            REQUIRE(io_ok(c.hio_w_in, DSP_IO_WF_IN) && p.io[c.hio_w_in].dtype == p.dtype && A.w_in_stride == p.io[c.hio_w_in].row_stride && A.w_in_offset == p.io[c.hio_w_in].offset && p.io[c.hio_w_in].len == A.m,
+                    "histogram_stats alone: the weights' rows");
+            REQUIRE(io_ok(c.hio_e_in, DSP_IO_WF_IN) && p.io[c.hio_e_in].dtype == p.dtype && A.e_in_stride == p.io[c.hio_e_in].row_stride && A.e_in_offset == p.io[c.hio_e_in].offset && p.io[c.hio_e_in].len == A.m + 1,
+                    "histogram_stats alone: the edges' rows");
+        }
+        if (c.hio_w >= 0 || !A.stats) REQUIRE(out_ok(c.hio_w, DSP_IO_WF_OUT, A.w_stride) && p.io[c.hio_w].len == A.m, "histogram kernel: weights_out");
+        if (c.hio_b >= 0 || !A.stats) REQUIRE(out_ok(c.hio_b, DSP_IO_WF_OUT, A.b_stride) && p.io[c.hio_b].len == A.m + 1, "histogram kernel: borders_out");
+        if (A.stats) {
+            for (int k = 0; k < 3; ++k) REQUIRE(out_ok(c.hio_s[k], DSP_IO_SCALAR_OUT, A.s_stride[k]), "histogram kernel: histogram_stats output %d", k);
+            if (c.hio_max_in >= 0) REQUIRE(column_ok(c.hio_max_in, A.max_in_stride), "histogram kernel: max_in column");
+        }
+    }
+    if (c.kernel_only == DSP_ROUTE_THRESH) {
+        const ThreshArgs& A = c.thresh;
+        REQUIRE(io_ok(c.thresh_src.io, DSP_IO_WF_IN), "threshold kernel: row binding");
+        REQUIRE(A.wf_offset == p.io[c.thresh_src.io].offset && A.wf_stride == p.io[c.thresh_src.io].row_stride && A.len == p.io[c.thresh_src.io].len, "threshold kernel: the row binding's offset / stride / length");
+        REQUIRE(A.m >= 0 && A.m <= DSP_THRESH_MAX && A.len >= (A.m > 0 ? 2 : 1), "threshold kernel: %d thresholds on rows of %d", A.m, A.len);
+        REQUIRE(out_ok(c.tio_out, A.m > 0 ? DSP_IO_WF_OUT : DSP_IO_SCALAR_OUT, A.out_stride), "threshold kernel: output");
+        if (A.m > 0) {
+            REQUIRE((A.polarity == 1 || A.polarity == -1) && strchr("iafbcrnl", A.mode) && p.io[c.tio_out].len == A.m, "threshold kernel: polarity %d, mode %d", A.polarity, A.mode);
+            REQUIRE(c.tio_thr >= 0 && c.tio_thr < (int)p.io.size() && p.io[c.tio_thr].dtype == p.dtype && p.io[c.tio_thr].len == A.m && A.thr_offset == p.io[c.tio_thr].offset &&
+                        (p.io[c.tio_thr].kind == DSP_IO_WF_IN ? A.thr_stride == p.io[c.tio_thr].row_stride : (p.io[c.tio_thr].kind == DSP_IO_TAPS && A.thr_stride == 0)),
+                    "threshold kernel: the thresholds' binding");
+            if (c.tio_ts >= 0) REQUIRE(column_ok(c.tio_ts, A.ts_stride), "threshold kernel: t_start column");
+        } else {
+            REQUIRE(c.tio_ts < 0, "time_over_threshold with a t_start");
+            if (c.tio_thr >= 0) REQUIRE(column_ok(c.tio_thr, A.thr_stride), "threshold kernel: threshold column");
+        }
+        if (c.thresh_src.vec) REQUIRE(rows_vec(c.thresh_src.io), "threshold kernel: vector loads on rows that are not whole 16-byte vectors");
     }
     return true;
 }
@@ -805,10 +984,10 @@ void digest_plan(Digest& H, const ChainPlan& c, int n_slots) {
     H(c.fused_ok), H(c.rr_ok), H(c.rows_ok), H(c.fir_ok), H(c.scalar_ok), H(c.cur_ok), H(c.pz_ok), H(c.red_ok), H(c.runs_ok);
     H((bool)(c.fused_on && any_ok));  // (the switch alone, on a program no kernel takes, shows through no accessor)
     H(c.variant), H(c.fused_trap), H(c.fused_npf), H(c.wf_dtype), H(c.rr_lds_bytes), H(c.rows_lds_bytes), H(c.fir_lds_bytes), H(c.cur_lds_bytes), H(c.fir_f16), H(c.f16.tz);
-    H(c.red_dtype), H(c.red_vec);
+    H(c.red_src.dtype), H(c.red_src.vec);
     H(c.io_wf), H(c.io_bl), H(c.io_tp), H(c.io_out), H(c.io_tau), H(c.rio_wf), H(c.rio_bl), H(c.rio_thr), H(c.rio_ts), H(c.rio_mm), H(c.rio_tpt), H(c.rio_dwt);
     H(c.fio_wf), H(c.fio_bl), H(c.fio_taps), H(c.fio_out), H(c.cio_wf), H(c.cio_t0), H(c.cio_out), H(c.pio_wf), H(c.pio_bl), H(c.pio_out), H(c.pio_tau), H(c.pio_mm);
-    H(c.dio_wf), H(c.dio_out), H(c.dio_pick), H(c.dio_walk), H(c.dio_walk_thr), H(c.dio_walk_ts), H(c.uio_wf), H(c.uio_taps), H(c.uio_out);
+    H(c.red_src.io), H(c.dio_out), H(c.dio_pick), H(c.dio_walk), H(c.dio_walk_thr), H(c.dio_walk_ts), H(c.uio_wf), H(c.uio_taps), H(c.uio_out);
     for (int S = 0; S < 2; ++S)
         for (int k = 0; k < 3; ++k) H(c.plan[S].shift[k]), H(c.plan[S].cs[k]), H(c.plan[S].local[k]);
     H(c.slot_base), H(c.slot_foot), H(c.slot_first_op), H(c.slot_last_op), H(c.slot_shares);
@@ -851,6 +1030,23 @@ void digest_plan(Digest& H, const ChainPlan& c, int n_slots) {
         H(A.wf_stride), H(A.wf_offset), H(A.n), H(A.m), H(A.p), H(A.start), H(A.keep), H(A.out_stride), H(A.has_red);
         if (A.has_red) digest_reduce(H, A.red);
     }
+    // the kernels that stream rows from memory and have no interpreter op behind them
+    H(c.kernel_only == DSP_ROUTE_EXTREMA), H(c.ext_src.dtype), H(c.ext_src.vec), H(c.ext_src.io), H(c.xio_par), H(c.xio_vt), H(c.xio_n);
+    H(c.kernel_only == DSP_ROUTE_HIST), H(c.hist_src.dtype), H(c.hist_src.vec), H(c.hist_src.io), H(c.hio_w), H(c.hio_b), H(c.hio_w_in), H(c.hio_e_in), H(c.hio_max_in), H(c.hio_s);
+    H(c.kernel_only == DSP_ROUTE_THRESH), H(c.thresh_src.dtype), H(c.thresh_src.vec), H(c.thresh_src.io), H(c.tio_thr), H(c.tio_ts), H(c.tio_out);
+    if (c.kernel_only == DSP_ROUTE_EXTREMA) {
+        const ExtremaArgs& A = c.ext;
+        H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.m), H(A.direction), H(A.par_stride), H(A.par_const), H(A.vt_stride), H(A.n_stride);
+    }
+    if (c.kernel_only == DSP_ROUTE_HIST) {
+        const HistArgs& A = c.hist;
+        H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.m), H(A.stats), H(A.max_blocks), H(A.w_stride), H(A.b_stride), H(A.w_in_stride), H(A.e_in_stride), H(A.w_in_offset), H(A.e_in_offset);
+        H(A.max_in_stride), H(A.max_in_const), H(A.s_stride);
+    }
+    if (c.kernel_only == DSP_ROUTE_THRESH) {
+        const ThreshArgs& A = c.thresh;
+        H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.m), H(A.polarity), H(A.mode), H(A.thr_stride), H(A.thr_offset), H(A.thr_const), H(A.ts_stride), H(A.ts_const), H(A.out_stride);
+    }
 }
 
 }  // namespace
@@ -861,11 +1057,11 @@ int main(int argc, char** argv) {
     const bool with_digest = argc > 3 && !strcmp(argv[3], "digest");
     Digest digest;
     rng.seed(seed);
-    long accepted = 0, by_kind[9] = {0}, n_integer = 0;
-    long kernels[11] = {0};
+    long accepted = 0, by_kind[12] = {0}, n_integer = 0;
+    long kernels[14] = {0};
     for (long it = 0; it < n_programs; ++it) {
         Prog p;
-        const int kind = rnd(0, 14);
+        const int kind = rnd(0, 20);
         switch (kind) {
             case 0: p = energy_shape(); break;
             case 1: p = rows_shape(); break;
@@ -875,10 +1071,13 @@ int main(int argc, char** argv) {
             case 5: p = current_shape(); break;
             case 6: p = scalar_shape(); break;
             case 7: p = fir_runs_shape(); break;
+            case 8: p = extrema_shape(); break;
+            case 9: p = hist_shape(); break;
+            case 10: p = thresh_shape(); break;
             default: p = random_program();
         }
-        if (kind <= 7 && chance(0.3)) mutate(p);
-        if (kind > 7 && chance(0.05)) mutate(p);
+        if (kind <= 10 && chance(0.3)) mutate(p);
+        if (kind > 10 && chance(0.05)) mutate(p);
         if (p.slots.size() > DSP_MAX_SLOTS && chance(0.9)) p.slots.resize(DSP_MAX_SLOTS);
         std::unique_ptr<ChainPlan> plan(new ChainPlan());
         const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(), p.n_sregs, p.dtype);
@@ -893,7 +1092,7 @@ int main(int argc, char** argv) {
         }
         if (with_digest) digest(rc), digest_plan(digest, *plan, (int)p.slots.size());
         ++accepted;
-        ++by_kind[kind <= 7 ? kind : 8];
+        ++by_kind[kind <= 10 ? kind : 11];
         n_integer += plan->i64 ? 1 : 0;
         switch (dsp_plan_route(plan.get())) {  // (the summary's buckets: the three FIR kernels as one, the interpreter's teams apart)
             case DSP_ROUTE_SCALAR: kernels[0]++; break;
@@ -905,6 +1104,9 @@ int main(int argc, char** argv) {
             case DSP_ROUTE_ROWS: kernels[5]++; break;
             case DSP_ROUTE_ENERGY_RR: kernels[6]++; break;
             case DSP_ROUTE_ENERGY: kernels[7]++; break;
+            case DSP_ROUTE_EXTREMA: kernels[11]++; break;
+            case DSP_ROUTE_HIST: kernels[12]++; break;
+            case DSP_ROUTE_THRESH: kernels[13]++; break;
             case DSP_ROUTE_VM: kernels[plan->host.team >= 2 ? 8 : 9]++; break;
         }
         if (!check(p, *plan)) {
@@ -913,10 +1115,10 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    printf("{\"programs\": %ld, \"accepted\": %ld, \"accepted_by_generator\": {\"energy\": %ld, \"rows\": %ld, \"fir\": %ld, \"pz\": %ld, \"reduce\": %ld, \"current\": %ld, \"scalar\": %ld, \"fir_runs\": %ld, \"random\": %ld}, "
-           "\"kernels\": {\"scalar\": %ld, \"pz_rows\": %ld, \"reduce\": %ld, \"current\": %ld, \"fir\": %ld, \"rows\": %ld, \"energy_rr\": %ld, \"energy\": %ld, \"vm_team\": %ld, \"vm\": %ld, \"fir_runs\": %ld}, \"integer_programs\": %ld",
-           n_programs, accepted, by_kind[0], by_kind[1], by_kind[2], by_kind[3], by_kind[4], by_kind[5], by_kind[6], by_kind[7], by_kind[8], kernels[0], kernels[1], kernels[2], kernels[3], kernels[4], kernels[5],
-           kernels[6], kernels[7], kernels[8], kernels[9], kernels[10], n_integer);
+    printf("{\"programs\": %ld, \"accepted\": %ld, \"accepted_by_generator\": {\"energy\": %ld, \"rows\": %ld, \"fir\": %ld, \"pz\": %ld, \"reduce\": %ld, \"current\": %ld, \"scalar\": %ld, \"fir_runs\": %ld, \"extrema\": %ld, \"hist\": %ld, \"thresh\": %ld, \"random\": %ld}, "
+           "\"kernels\": {\"scalar\": %ld, \"pz_rows\": %ld, \"reduce\": %ld, \"current\": %ld, \"fir\": %ld, \"rows\": %ld, \"energy_rr\": %ld, \"energy\": %ld, \"vm_team\": %ld, \"vm\": %ld, \"fir_runs\": %ld, \"extrema\": %ld, \"hist\": %ld, \"thresh\": %ld}, \"integer_programs\": %ld",
+           n_programs, accepted, by_kind[0], by_kind[1], by_kind[2], by_kind[3], by_kind[4], by_kind[5], by_kind[6], by_kind[7], by_kind[8], by_kind[9], by_kind[10], by_kind[11], kernels[0], kernels[1], kernels[2], kernels[3], kernels[4], kernels[5],
+           kernels[6], kernels[7], kernels[8], kernels[9], kernels[10], kernels[11], kernels[12], kernels[13], n_integer);
     if (with_digest) printf(", \"digest\": \"0x%016llx\"", (unsigned long long)digest.h);
     printf("}\n");
     return 0;
