@@ -127,6 +127,7 @@ struct Mini {
         // process (threads that want concurrency build their own chains with dsp_chain_create).
         std::lock_guard<std::mutex> lk(g_cache_mu);
         key.v.push_back(dsp_gufunc_current_device());
+        key.v.push_back((int64_t)dsp_plan_switches());  // (a chain planned under other routing switches is another chain)
         dsp_chain* ch = nullptr;
         auto it = g_cache.find(key);
         if (it != g_cache.end()) ch = it->second;

@@ -1938,6 +1938,18 @@ static bool match_scalar_shape(const PlanCtx& c) {
     return only_scalar && c.n_dev_ops == c.n_ops;
 }
 
+uint64_t dsp_plan_switches() {
+    static const char* const names[] = {"DSPEED_HIP_VARIANT", "DSPEED_HIP_ABLATE", "DSPEED_HIP_FIR_F32", "DSPEED_HIP_NO_FUSED", "DSPEED_HIP_NO_FIR_RUNS",
+                                        "DSPEED_HIP_NO_THRESHOLD_FOLD", "DSPEED_HIP_NO_TEAMS", "DSPEED_HIP_TEAM_MAX", "DSPEED_HIP_TEAM_WPB"};
+    uint64_t h = 1469598103934665603ull;  // (FNV-1a over the values, a separator behind each)
+    for (const char* name : names) {
+        const char* v = getenv(name);
+        for (const char* p = v ? v : ""; *p; ++p) h = (h ^ (unsigned char)*p) * 1099511628211ull;
+        h = (h ^ 0xffu) * 1099511628211ull;
+    }
+    return h;
+}
+
 // Every specialised kernel's shape against the program: the *_ok flags, the kernels' argument blocks and binding indices.  Several may
 // hold at once; which kernel runs is dsp_plan_route's business (and, with the pointers of a launch in hand, dsp_chain_execute's).
 static void match_shapes(PlanCtx& c) {

@@ -126,3 +126,6 @@ const char* dsp_plan_kernel_name(const ChainPlan* ch);
 // does a specialised kernel's shape stand behind the chain (its note is then not shown)?  The route, but for one case: the classic energy
 // kernel asked for (variant 1) on a program only the register-resident one takes runs on the interpreter and still counts
 bool dsp_plan_specialised(const ChainPlan* ch);
+// a digest of every environment switch dsp_plan_build reads (DSPEED_HIP_FIR_F32, DSPEED_HIP_NO_FUSED, ...): a plan stands for the program
+// AND these, so whoever keeps planned chains by their program (dsp_gufuncs.cpp) keys on it as well
+uint64_t dsp_plan_switches();
