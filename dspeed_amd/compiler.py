@@ -26,8 +26,8 @@ from . import _lib
 from .chain import Program, Scalar
 from .device import dtype_code
 from .errors import DSPFatal, ProcessingChainError
-from .language import (Grid, Quantity, SExpr, Var, _Builder, _GENERATORS, _NUMPY_BINARY, module_accepted, _SIGS, _column, _grid_of, _is_int_dtype, _is_scalar,
-                       _is_wf, _resolve, _roles, _time_unit_ns, _wf_len)
+from .language import (Char, Grid, Quantity, SExpr, Var, View, _Builder, _GENERATORS, _NUMPY_BINARY, module_accepted, _SIGS, _column, _grid_of, _is_int_dtype,
+                       _is_scalar, _is_wf, _resolve, _roles, _time_unit_ns)
 
 # processors whose output waveform has the input's dimension name in the gufunc signature ("(n),...->(n)") and therefore its
 # coordinate grid (reference :1601-1619, 1700); the others' outputs have no grid unless the recipe declares one
@@ -45,10 +45,10 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
     b.cur_key = key
     if module is None:  # inline expression: alias / constant / the result of operators and functions of the language (reference :2676-2696)
         val = b.eval_arg(node["args"][0])
-        if isinstance(val, tuple) and not _is_wf(val):
+        if isinstance(val, Char):
             raise ProcessingChainError(f"'{key}': {val!r} is not a value")
-        if isinstance(val, (Var, SExpr, tuple)):
-            if isinstance(val, (Var, SExpr)) and "#" in val.name and not getattr(val, "is_input", False):
+        if isinstance(val, (Var, SExpr, View)):
+            if isinstance(val, (Var, SExpr)) and "#" in val.name and not val.is_input:
                 val.name = new_vars[0]  # (an expression's result takes the name the recipe gives it)
             if "unit" in node and isinstance(val, (Var, SExpr)) and val.unit is None and isinstance(node["unit"], str):
                 val.unit = node["unit"]
@@ -65,11 +65,12 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         if len(args) != 2 or not isinstance(args[0], Var) or args[0].length is None or not _is_wf(args[1]):
             raise ProcessingChainError(f"numpy.copyto takes a declared output array and an array for parameter {key}")
         dst, src = args
-        if _wf_len(src) < dst.length:
-            raise ProcessingChainError(f"numpy.copyto for parameter {key}: the output holds {dst.length} samples, the source only {_wf_len(src)}")
+        if src.length < dst.length:
+            raise ProcessingChainError(f"numpy.copyto for parameter {key}: the output holds {dst.length} samples, the source only {src.length}")
         dst.kind = "wf"
         dst.dtype = dst.dtype if dst.dtype is not None else np.dtype(np.float32)
-        b._step("slice", [src if _wf_len(src) == dst.length else ("slice", *( (src[1], src[2], src[2] + dst.length) if isinstance(src, tuple) else (src, 0, dst.length))), 0, 1, dst], "wiiW")
+        lo = src.lo if isinstance(src, View) else 0
+        b._step("slice", [src if src.length == dst.length else View(src.base, lo, lo + dst.length), 0, 1, dst], "wiiW")
         return
     if module in ("numpy", "np") and function not in ("amax",) + tuple(_NUMPY_BINARY):
         raise NotImplementedError(f"numpy.{function} is not available on the device path")
@@ -89,10 +90,9 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         if len(args) != 3 or not isinstance(args[2], Var):
             raise ProcessingChainError(f"numpy.{function} takes two operands and an output variable for parameter {key}")
         x, y, out = args
-        is_wf = lambda v: (isinstance(v, Var) and v.kind == "wf") or (isinstance(v, tuple) and v and v[0] == "slice")  # noqa: E731
-        if is_wf(x) and not is_wf(y) and function in ("subtract", "add"):
+        if _is_wf(x) and not _is_wf(y) and function in ("subtract", "add"):
             function = "numpy_subtract" if function == "subtract" else "numpy_add"
-        elif is_wf(x) or is_wf(y):
+        elif _is_wf(x) or _is_wf(y):
             # the ufunc on waveforms, as the operator of the language makes it (one NumPy loop per sample); the declared output names the result
             val = b._wf_binop(_NUMPY_BINARY[function](), x, y, f"numpy.{function}({', '.join(map(str, node['args']))})")
             if out.length is not None and out.length != val.length:
@@ -116,11 +116,8 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
     # give the variables this processor creates their type now, so later recipe entries can slice / measure them
     src_len = None
     for a, r in zip(args, roles):
-        if r == "w":
-            if isinstance(a, tuple) and a[0] == "slice":
-                src_len = a[3] - a[2]
-            elif isinstance(a, Var):
-                src_len = a.length
+        if r == "w" and isinstance(a, (Var, View)):
+            src_len = a.length
     for a, r in zip(args, roles):
         if r == "W" and isinstance(a, Var):
             if a.kind is None:
@@ -145,7 +142,7 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         t_out = args[5]
         if isinstance(t_out, Var) and t_out.kind == "wf":
             if t_out.length is None:
-                t_out.length = _wf_len(args[1]) if _is_wf(args[1]) else args[1].length
+                t_out.length = args[1].length
             if _time_unit_ns(t_out.unit) is not None and _grid_of(args[0]) is not None:
                 t_out.is_coord, t_out.grid = True, _grid_of(args[0])
     args = [_as_taps(b, a, function) if r == "t" else a for a, r in zip(args, roles)]
@@ -171,7 +168,7 @@ def _group_constant(b: _Builder, a, function, key):
     chain is for, or reported to ``build_processing_chain``, which then returns a GroupedProcessingChain."""
     if isinstance(a, Var) and a.kind == "const":
         return a.const
-    if not (isinstance(a, Var) and a.kind == "scalar" and a.is_input and a.source is not None and getattr(a, "ext_key", None) is None):
+    if not (isinstance(a, Var) and a.kind == "scalar" and a.is_input and a.source is not None and a.ext_key is None):
         raise NotImplementedError(f"{function} ({key}): the integer parameter '{a.name}' is computed per event inside the recipe; the device "
                                   "programs take integer parameters as constants or as columns of the input table (rows grouped by value)")
     if not np.can_cast(a.dtype, np.int32):  # ("fii->f" and the like: the column must cast to the signature's 'i', reference :1565-1572)
@@ -213,8 +210,8 @@ def _as_threshold_list(b: _Builder, a, key):
         name = a.name if isinstance(a, Var) else f"thresholds#{b._anon}"
         return Var(name, "taps", int(arr.size), np.float32, const=np.ascontiguousarray(arr, dtype=np.float32))
     if _is_wf(a):
-        if _wf_len(a) > _lib.THRESH_MAX:
-            raise NotImplementedError(f"{fn} ({key}): at most {_lib.THRESH_MAX} thresholds ({_wf_len(a)} given): a wavefront keeps one per lane")
+        if a.length > _lib.THRESH_MAX:
+            raise NotImplementedError(f"{fn} ({key}): at most {_lib.THRESH_MAX} thresholds ({a.length} given): a wavefront keeps one per lane")
         return a
     raise ProcessingChainError(f"{fn} ({key}): the thresholds are a constant array or an array per event, not {a!r}")
 
@@ -234,7 +231,7 @@ def _fold_generator(b: _Builder, function, args, new_vars):
             if period is None:
                 raise ProcessingChainError(f"{function}: time quantity without a sampling period")
             s = float(s) / period
-        if isinstance(s, (Var, tuple)):
+        if isinstance(s, (Var, View, Char)):
             raise NotImplementedError(f"{function} with per-event arguments is not supported")
         vals.append(float(s))
     k = np.zeros(out.length, dtype=np.float32)
@@ -276,20 +273,14 @@ def _leaves(a, acc):
     if isinstance(a, SExpr):
         for x in a.args:
             _leaves(x, acc)
-    elif isinstance(a, Var):
-        acc.append(a)
-    elif isinstance(a, tuple) and a and a[0] == "slice":
-        acc.append(a[1])
+    elif isinstance(a, (Var, View)):
+        acc.append(a.base)
     return acc
 
 
 def _base_of(a):
     """the waveform variable of an argument, whole or under a slice (None: not a waveform argument)"""
-    if isinstance(a, Var):
-        return a
-    if isinstance(a, tuple) and a and a[0] == "slice":
-        return a[1]
-    return None
+    return a.base if isinstance(a, (Var, View)) else None
 
 
 def _outputs_of(step):
@@ -447,14 +438,14 @@ class _Stager:
     @staticmethod
     def plain_scalar(x) -> bool:  # a constant, a per-event input column or a fit / stage result: in HBM before the stage runs
         if isinstance(x, Var):
-            return x.kind == "scalar" and x.sreg is None and ((x.is_input and x.source is not None) or getattr(x, "ext_key", None) is not None)
+            return x.kind == "scalar" and x.sreg is None and ((x.is_input and x.source is not None) or x.ext_key is not None)
         if isinstance(x, SExpr):  # (an expression a stage of its own has evaluated: stage_expression)
-            return x.op == "ext" and getattr(x, "ext_key", None) is not None
+            return x.op == "ext" and x.ext_key is not None
         return _is_number(x)
 
     @staticmethod
     def row_input(v) -> bool:  # rows of the input table or of an earlier stage
-        return isinstance(v, Var) and v.kind == "wf" and ((v.is_input and v.source is not None) or getattr(v, "ext_key", None) is not None)
+        return isinstance(v, Var) and v.kind == "wf" and ((v.is_input and v.source is not None) or v.ext_key is not None)
 
     def ancestors(self, v):
         """steps that compute v from inputs and earlier results, in order"""
@@ -482,7 +473,7 @@ class _Stager:
             ins, outs = _inputs_of(st), _outputs_of(st)
             if not outs or "W" in _roles(st[0]) or not any(a is v for a in ins if isinstance(a, Var)):
                 continue
-            others = [a for a in ins if a is not v and isinstance(a, (Var, SExpr, tuple)) and not (isinstance(a, tuple) and a and a[0] == "char")]
+            others = [a for a in ins if a is not v and isinstance(a, (Var, SExpr, View))]
             if all(isinstance(a, Var) and (self.plain_scalar(a) or id(a) in made) for a in others) and all(isinstance(o, Var) for o in outs):
                 picked.append(st)
                 made.update(id(o) for o in outs)
@@ -512,12 +503,12 @@ class _Stager:
         b2 = copy.copy(b)
         b2.vars, b2.steps, b2._conversions, b2.stage_ft = vars2, list(steps2), {}, self.ft
         for v in vars2.values():
-            if isinstance(v, Var) and getattr(v, "aux_io", None) is not None:
+            if isinstance(v, Var) and v.aux_io is not None:
                 v.aux_io = None  # (an index into the main program's bindings; the stage binds the fit's column by its name)
         pc, _tb = _compile(b2, [o.name for o in outs], self.n_rows, [], stage_mode=True)
         self.stages.append(_stage_record(what, pc._program, pc._consts, pc._in_vars, pc._ext_alias,
                                          [(f"out:{o.name}", f"in:{o.name}", o.length if o.kind == "wf" else None) for o in outs],
-                                         out_dtypes={f"in:{o.name}": o.out_dtype for o in outs if getattr(o, "out_dtype", None) is not None}))
+                                         out_dtypes={f"in:{o.name}": o.out_dtype for o in outs if o.out_dtype is not None}))
         for o in outs:
             if o.kind == "wf":  # pole_zero returns an all-NaN waveform for an input with a NaN and DSPFatal for a NaN of its own making
                 made_by = self.producer_of(o)
@@ -527,7 +518,7 @@ class _Stager:
                 o.ext_len, o.offset, o.dtype = o.length, 0, np.dtype(np.float32)
         for o in scalars:
             o.kind = "scalar"
-            if getattr(o, "out_dtype", None) is not None:
+            if o.out_dtype is not None:
                 o.ext_dtype = o.out_dtype
         self.steps = _without(self.steps, group if drop is None else drop)
 
@@ -596,10 +587,10 @@ def _stage_long_firs(cx: _Stager):
         if not (isinstance(taps, Var) and taps.kind == "taps" and taps.const is not None and isinstance(out, Var) and out.length):
             continue
         m = int(taps.length)
-        base, n_in = _base_of(args[0]), _wf_len(args[0])
+        base, n_in = _base_of(args[0]), args[0].length
         if base is None or n_in is None or m < STAGE_MIN_TAPS or m > n_in or not np.isfinite(taps.const).all():
             continue
-        mode = args[2][1][0] if isinstance(args[2], tuple) and args[2][0] == "char" else (chr(args[2]) if isinstance(args[2], (int, np.integer)) else None)
+        mode = args[2].value[0] if isinstance(args[2], Char) else (chr(args[2]) if isinstance(args[2], (int, np.integer)) else None)
         want_len = {"v": n_in - m + 1, "s": n_in, "f": n_in + m - 1}.get(mode)
         if want_len is None or want_len != out.length:
             continue  # (the program's own op reports it)
@@ -741,7 +732,7 @@ def _operand_in_memory(cx: _Stager, a, fn, key, written_first=False):
     of the baseline-subtracted waveform, for a threshold at half of it) is written to HBM first, with the other results of its processor,
     by a small program of its own -- as a source waveform is."""
     if not isinstance(a, (Var, SExpr)):
-        if isinstance(a, (tuple, Grid)) or not (_is_number(a) or isinstance(a, Quantity)):
+        if not (_is_number(a) or isinstance(a, Quantity)):
             raise NotImplementedError(f"{fn} ({key}): operand {a!r} is neither a number nor a per-event value")
         return a
     for leaf in _leaves(a, []) if written_first else ():
@@ -755,7 +746,7 @@ def _operand_in_memory(cx: _Stager, a, fn, key, written_first=False):
         if not cx.plain_scalar(leaf) and not (leaf.kind == "scalar" and cx.move_ahead([leaf])):
             raise NotImplementedError(f"{fn} ({key}): operand '{a.name}' depends on '{leaf.name}', which is neither a constant, an input column, "
                                       "a fit or stage result nor computed off rows in memory")
-    is_f32_column = isinstance(a, Var) and (getattr(a, "ext_key", None) is not None
+    is_f32_column = isinstance(a, Var) and (a.ext_key is not None
                                             or np.dtype(_column(cx.b.tb_in, a.source).dtype) == np.dtype(np.float32))
     if not is_f32_column and not (isinstance(a, SExpr) and cx.plain_scalar(a)):
         return cx.stage_expression(a, f"{a.name} for {fn} {key}")
@@ -828,12 +819,12 @@ def _stage_thresholds(cx: _Stager):
             raise NotImplementedError(f"{fn} ({key}): the polarity is a constant of the kernel, not a per-event value")
         if not (polarity > 0 or polarity < 0):
             raise DSPFatal("polarity cannot be 0")
-        if not (isinstance(mode, tuple) and mode and mode[0] == "char") and not isinstance(mode, (int, np.integer)):
+        if not isinstance(mode, (Char, int, np.integer)):
             raise NotImplementedError(f"{fn} ({key}): the interpolation mode is a constant of the kernel, not a per-event value")
         code = _Emitter.char_of(mode)
         if not 0 < code < 128 or chr(code) not in "iafbcrnl":
             raise DSPFatal("Unrecognized interpolation mode")
-        m = thr.length if isinstance(thr, Var) else _wf_len(thr)
+        m = thr.length
         if not (isinstance(t_out, Var) and t_out.kind == "wf" and t_out.length == m):
             raise ProcessingChainError(f"{fn} ({key}): t_out holds a time per threshold: declare it as name({m})")
         _rows_in_memory(cx, src, fn, key)
@@ -881,7 +872,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_multi_extrema(cx)
     _stage_thresholds(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
-    staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and getattr(v, "ext_key", None) is not None and getattr(v, "aux_io", None) is None}
+    staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and v.ext_key is not None and v.aux_io is None}
     cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
     if ft == np.dtype(np.float32) and os.environ.get("DSPEED_HIP_NO_ROW_REDUCTIONS") != "1" and fir_staged:
         _stage_row_reductions(cx)
@@ -903,7 +894,7 @@ def _int_dtype_of(x):
 
 
 def _is_table_column(x) -> bool:  # a column of the input table: in HBM before any program runs
-    return isinstance(x, Var) and x.kind == "scalar" and x.is_input and x.source is not None and x.sreg is None and getattr(x, "ext_key", None) is None
+    return isinstance(x, Var) and x.kind == "scalar" and x.is_input and x.source is not None and x.sreg is None and x.ext_key is None
 
 
 def _expressions(b: _Builder, steps, out_pars):
@@ -1055,7 +1046,7 @@ def _extract_fits(b: _Builder, steps, out_pars, p: Program, ft):
         tau = None
         if not v.is_input and v.name in producer and producer[v.name][0] == "pole_zero":
             _fn, a = producer[v.name]
-            if not isinstance(a[0], Var) or isinstance(a[1], (Var, SExpr, Quantity, tuple)):
+            if not isinstance(a[0], Var) or isinstance(a[1], (Var, SExpr, Quantity, View, Char)):
                 return None
             tau, v = float(a[1]), a[0]
         sub, mode = None, 0
@@ -1068,8 +1059,8 @@ def _extract_fits(b: _Builder, steps, out_pars, p: Program, ft):
                 return None
             sub, mode, src = a[1], (1 if fn2 == "bl_subtract" else 2), a[0]
         lo, n = 0, None
-        if isinstance(src, tuple) and src[0] == "slice":
-            src, lo, n = src[1], src[2], src[3] - src[2]
+        if isinstance(src, View):
+            src, lo, n = src.base, src.lo, src.length
         if not (isinstance(src, Var) and src.is_input and src.kind == "wf" and src.offset == 0):
             return None
         return src, lo, (src.length if n is None else n), sub, mode, tau
@@ -1081,8 +1072,8 @@ def _extract_fits(b: _Builder, steps, out_pars, p: Program, ft):
         if fn != "linear_slope_fit" or not all(isinstance(a, Var) for a in args[1:5]):
             continue
         a0, first, count = args[0], 0, None
-        if isinstance(a0, tuple) and a0[0] == "slice":
-            a0, first, count = a0[1], a0[2], a0[3] - a0[2]
+        if isinstance(a0, View):
+            a0, first, count = a0.base, a0.lo, a0.length
         pl = pipeline_of(a0) if isinstance(a0, Var) else None
         if pl is None:
             continue
@@ -1122,7 +1113,7 @@ def _push_down_slices(steps, out_names):
         if fn != "bl_subtract" or not isinstance(args[0], Var) or not isinstance(args[-1], Var) or args[-1].name in out_names:
             continue
         src_v, dst_v = args[0], args[-1]
-        found = {(x[2], x[3]) for _fn, a2, _k in steps for x in a2 if isinstance(x, tuple) and x[0] == "slice" and x[1] is dst_v}
+        found = {(x.lo, x.hi) for _fn, a2, _k in steps for x in a2 if isinstance(x, View) and x.base is dst_v}
         uses_of_dst = sum(1 for _fn, a2, _k in steps for x in a2 if x is dst_v)  # the producing step itself counts once
         if len(found) != 1 or uses_of_dst != 1 or not src_v.is_input or src_v.kind != "wf":
             continue
@@ -1131,16 +1122,17 @@ def _push_down_slices(steps, out_names):
             continue
         # ... except for bl_subtract's NaN rule, which looks at the WHOLE waveform (bl_subtract.py:41-44): the load of the slice also screens
         # the samples outside it (LOAD ip[0..1]); another processor reading the same slice of the input as a plain view must not see that
-        if any(isinstance(x, tuple) and x[0] == "slice" and x[1] is src_v and (x[2], x[3]) == (lo, hi) for _f, a2, _k in steps for x in a2):
+        pushed = View(src_v, lo, hi)
+        if any(isinstance(x, View) and x == pushed for _f, a2, _k in steps for x in a2):
             continue
-        whole_nan_rule[f"{src_v.name}[{lo}:{hi}]"] = (lo, src_v.length - hi)
+        whole_nan_rule[pushed.name] = (lo, src_v.length - hi)
         new_args = list(args)
-        new_args[0] = ("slice", src_v, lo, hi)
+        new_args[0] = pushed
         steps[si] = (fn, new_args, key)
         dst_v.length = hi - lo
         for sj, (fn2, a2, k2) in enumerate(steps):
             if sj != si:
-                steps[sj] = (fn2, [dst_v if (isinstance(x, tuple) and x[0] == "slice" and x[1] is dst_v) else x for x in a2], k2)
+                steps[sj] = (fn2, [dst_v if (isinstance(x, View) and x.base is dst_v) else x for x in a2], k2)
     return whole_nan_rule
 
 
@@ -1154,7 +1146,7 @@ def _last_uses(b: _Builder, steps, out_pars):
                 last_use[v.name] = si
     for o in out_pars:  # (a variable may be known by another name than the output's: an alias, a named slice)
         last_use[o] = len(steps) + 1
-        v = _base_of(b.vars.get(o)) if isinstance(b.vars.get(o), (Var, tuple)) else None
+        v = _base_of(b.vars.get(o))
         if v is not None:
             last_use[v.name] = len(steps) + 1
     return last_use
@@ -1226,28 +1218,25 @@ class _Emitter:
     def ensure_loaded(self, a, si):
         """Waveform operand -> slot.  Chain inputs are loaded on first use (a constant slice of an input is free)."""
         b, p = self.b, self.p
-        if isinstance(a, tuple) and a[0] == "slice":
-            _, base, lo, hi = a
-            key = f"{base.name}[{lo}:{hi}]"
+        if isinstance(a, View):
+            base, lo, hi, key = a.base, a.lo, a.hi, a.name
             v = b.vars.get(key)
             if base.is_input:
                 if v is None:
-                    v = Var(key, "wf", hi - lo, base.dtype, source=base.source, offset=lo, grid=_grid_of(a), is_coord=False)
+                    v = Var(key, "wf", hi - lo, base.dtype, source=base.source, offset=lo, grid=a.grid, is_coord=False)
                     v.is_input = True
-                    if getattr(base, "ext_key", None) is not None:  # (a waveform a stage wrote: same buffer, first sample lo)
-                        v.ext_key, v.ext_len = base.ext_key, getattr(base, "ext_len", base.length)
+                    v.ext_key, v.ext_len = base.ext_key, base.ext_len  # (a waveform a stage wrote: same buffer, first sample lo)
                     b.vars[key] = v
                     self.last_use[key] = self.last_use.get(base.name, si)
                 return self.ensure_loaded(v, si)
             if v is not None and v.slot is not None:
                 return v  # the same slice was materialised for an earlier processor and is still alive
             src = self.ensure_loaded(base, si)
-            v = Var(key, "wf", hi - lo, np.float32, grid=_grid_of(a), is_coord=False)
+            v = Var(key, "wf", hi - lo, np.float32, grid=a.grid, is_coord=False)
             v.slot = self.new_slot(v.length)
             p.add_op(_lib.OP_COPY, dst=v.slot, src=src.slot, ip=(lo,))
             b.vars[key] = v
-            self.last_use[key] = max((sj for sj, (_, a2, _k) in enumerate(self.steps)
-                                      for x in a2 if isinstance(x, tuple) and x[0] == "slice" and x[1] is base and x[2] == lo and x[3] == hi), default=si)
+            self.last_use[key] = max((sj for sj, (_, a2, _k) in enumerate(self.steps) for x in a2 if isinstance(x, View) and x == a), default=si)
             return v
         v = a
         if v.kind != "wf":
@@ -1255,8 +1244,8 @@ class _Emitter:
         if v.slot is None:
             if not v.is_input:
                 raise ProcessingChainError(f"waveform '{v.name}' is used before it is computed")
-            if getattr(v, "ext_key", None) is not None:  # written by a stage ahead of the program: float32 rows of the variable's length
-                io = p.add_io(f"in:{v.name}", _lib.IO_WF_IN, np.float32, v.length, v.offset, getattr(v, "ext_len", v.length))
+            if v.ext_key is not None:  # written by a stage ahead of the program: float32 rows of the variable's length
+                io = p.add_io(f"in:{v.name}", _lib.IO_WF_IN, np.float32, v.length, v.offset, v.ext_len)
                 self.ext_alias[f"in:{v.name}"] = v.ext_key
             else:
                 col = _column(b.tb_in, v.source)
@@ -1264,7 +1253,7 @@ class _Emitter:
                 self.in_bind[f"in:{v.name}"] = v
             v.slot = self.new_slot(v.length)
             screens = self.whole_nan_rule.get(v.name, ())
-            if getattr(v, "nan_uniform", False):  # rows a stage wrote with pole_zero's rule: all NaN or free of NaN (DSP_OP_LOAD ip[2])
+            if v.nan_uniform:  # rows a stage wrote with pole_zero's rule: all NaN or free of NaN (DSP_OP_LOAD ip[2])
                 screens = (*(screens or (0, 0)), 1)
             p.add_op(_lib.OP_LOAD, dst=v.slot, io=io, ip=screens)
         return v
@@ -1284,7 +1273,7 @@ class _Emitter:
             p.add_op(_lib.OP_SCALAR_AFFINE if a.op == "affine" else _lib.OP_SCALAR_DIV, dst=r, sp=tuple(opnd(x) for x in a.args))
         elif a.op == "func":
             code, *xs = a.args
-            if code == _lib.FN_COPY and getattr(a, "want_dtype", None) not in (None, ft):
+            if code == _lib.FN_COPY and a.want_dtype not in (None, ft):
                 raise NotImplementedError(f"{what}: astype to {a.want_dtype} in a chain whose loop type is {ft}")
             if (code >> 8) & 0xff == 32 and ft != np.dtype(np.float64):
                 # a 32-bit integer loop between per-event values of a float32 chain (len(v) // 2, eventnumber + 1): the registers are
@@ -1317,7 +1306,7 @@ class _Emitter:
     def scalar_operand(self, a, args, integer=False, what=""):
         """Scalar argument -> Scalar (const / input column / register)."""
         if isinstance(a, SExpr) and a.op == "ext":  # a column the integer program ahead of this one wrote (_int_island)
-            if getattr(a, "ext_key", None) is None:
+            if a.ext_key is None:
                 raise ProcessingChainError(f"{what}: '{a.name}' is written by the integer program as an output only")
             return self.column(a, a.ext_key, a.ext_dtype, buffer=a.ext_key)
         if isinstance(a, SExpr):
@@ -1328,10 +1317,10 @@ class _Emitter:
             elif a.kind == "scalar":
                 if a.sreg is not None:
                     return Scalar.reg(a.sreg)
-                if getattr(a, "aux_io", None) is not None:  # a fit done ahead of the chain
+                if a.aux_io is not None:  # a fit done ahead of the chain
                     return Scalar.input(a.aux_io)
-                if getattr(a, "ext_key", None) is not None:  # a fit or a stage ahead of this program
-                    return self.column(a, f"in:{a.name}", getattr(a, "ext_dtype", self.ft), buffer=a.ext_key)
+                if a.ext_key is not None:  # a fit or a stage ahead of this program
+                    return self.column(a, f"in:{a.name}", self.ft if a.ext_dtype is None else a.ext_dtype, buffer=a.ext_key)
                 if a.is_input:
                     return self.column(a, f"in:{a.name}", _column(self.b.tb_in, a.source).dtype, var=a)
                 raise ProcessingChainError(f"scalar '{a.name}' is used before it is computed")
@@ -1342,7 +1331,7 @@ class _Emitter:
             if per is None:
                 raise ProcessingChainError(f"{what}: time quantity without a sampling period (wrap the input in WaveformInput)")
             a = float(a) / per
-        if isinstance(a, (tuple, Grid)):
+        if isinstance(a, (View, Char, Grid)):
             raise ProcessingChainError(f"{what}: expected a number or a per-event variable, got {a!r}")
         if integer:  # reference :1767-1768: integer parameters are rounded after the unit conversion
             return int(a) if isinstance(a, (int, np.integer)) else int(np.rint(float(a)))
@@ -1350,8 +1339,8 @@ class _Emitter:
 
     @staticmethod
     def char_of(a):
-        if isinstance(a, tuple) and a[0] == "char":
-            return ord(a[1][0])
+        if isinstance(a, Char):
+            return ord(a.value[0])
         if isinstance(a, (int, np.integer)):
             return int(a)
         raise ProcessingChainError(f"expected a character argument, got {a!r}")
@@ -1381,12 +1370,12 @@ class _Emitter:
             a.sreg = self.p.add_sregs(1)
         return a
 
-    def out_four(self, outs, name):
-        """four registers in a row for the results of min_max / linear_slope_fit"""
-        first = self.p.add_sregs(4)
+    def out_row(self, outs, refusal):
+        """registers in a row for the named results of one op: min_max, linear_slope_fit, the peak finder's counts, histogram_stats"""
+        first = self.p.add_sregs(len(outs))
         for k, a in enumerate(outs):
             if not isinstance(a, Var):
-                raise ProcessingChainError(f"{name} outputs must be variable names")
+                raise ProcessingChainError(refusal)
             a.kind, a.sreg = "scalar", first + k
         return first
 
@@ -1426,7 +1415,7 @@ class _Emitter:
 
     def elementwise(self, si, fn, args, what):
         code, *opn, dst = args
-        if code == _lib.FN_COPY and getattr(dst, "want_dtype", None) not in (None, self.ft):
+        if code == _lib.FN_COPY and dst.want_dtype not in (None, self.ft):
             raise NotImplementedError(f"{what}: astype to {dst.want_dtype} in a chain whose loop type is {self.ft}")
         if (code >> 8) & 0xff == 32 and self.ft != np.dtype(np.float64):
             raise NotImplementedError(f"{what}: a 32-bit integer loop on waveforms in a chain whose loop type is {self.ft} (its values do not hold every "
@@ -1457,11 +1446,7 @@ class _Emitter:
         if vt_max.length != vt_min.length:
             raise ProcessingChainError(f"{what}: the two lists share one length ({vt_max.length} and {vt_min.length} declared)")
         vt_max.slot, vt_min.slot = self.new_slot(vt_max.length), self.new_slot(vt_min.length)
-        first = self.p.add_sregs(2)
-        for k, a in enumerate(args[8:10]):
-            if not isinstance(a, Var):
-                raise ProcessingChainError(f"{what}: the counts must be variable names")
-            a.kind, a.sreg = "scalar", first + k
+        first = self.out_row(args[8:10], f"{what}: the counts must be variable names")
         self.p.add_op(_lib.OP_MULTI_EXTREMA, dst=vt_max.slot, src=src.slot, ip=(direction, vt_min.slot, first), sp=sp)
         self.release(src, si)
 
@@ -1477,11 +1462,7 @@ class _Emitter:
         """HISTOGRAM_STATS on the slots of a histogram in the same program, or on weights and edges loaded from rows in memory"""
         weights, edges = self.ensure_loaded(args[0], si), self.ensure_loaded(args[1], si)
         max_in = self.scalar_operand(args[5], args, what=what)
-        first = self.p.add_sregs(3)
-        for k, a in enumerate(args[2:5]):
-            if not isinstance(a, Var):
-                raise ProcessingChainError(f"{what}: mode_out, max_out and fwhm_out must be variable names")
-            a.kind, a.sreg = "scalar", first + k
+        first = self.out_row(args[2:5], f"{what}: mode_out, max_out and fwhm_out must be variable names")
         self.p.add_op(_lib.OP_HISTOGRAM_STATS, src=weights.slot, ip=(edges.slot, first), sp=(max_in,))
 
     def multi_time_point_thresh(self, si, fn, args, what):
@@ -1534,7 +1515,7 @@ class _Emitter:
         pick_ok = all(char_of(steps[sj][1][2]) != ord("s") for sj in users if steps[sj][0] == "fixed_time_pickoff")
         if (users and plain and pick_ok and dst.name not in self.out_names
                 and sorted(kinds) in (["min_max"], ["time_point_thresh"], ["min_max", "time_point_thresh"], ["amax"], ["amax", "fixed_time_pickoff"])
-                and not any(isinstance(x, tuple) and x[0] == "slice" and x[1] is dst for _f, a2, _k in steps for x in a2)):
+                and not any(isinstance(x, View) and x.base is dst for _f, a2, _k in steps for x in a2)):
             self.pending_reduce[dst.name] = {"src": src, "ints": ints, "kind": _TRAP_OPS[fn], "emit_at": max(users), "mm_first": -1}
             last_use[src.name] = max(last_use.get(src.name, si), max(users))
             return
@@ -1555,7 +1536,7 @@ class _Emitter:
                 raise ProcessingChainError("numpy.amax output must be a variable name")
             args[2].kind, args[2].sreg = "scalar", pr["mm_first"] + 3
         elif fn == "min_max":
-            pr["mm_first"] = self.out_four(args[1:5], "min_max")
+            pr["mm_first"] = self.out_row(args[1:5], "min_max outputs must be variable names")
         else:
             pr["tpt"] = (tuple(self.scalar_operand(a, args, what=what) for a in args[1:4]), self.out_scalar(args[4]))
         if si == pr["emit_at"]:
@@ -1575,10 +1556,10 @@ class _Emitter:
         a0, view = args[0], ()
         if fn == "linear_slope_fit":
             view = (0, 0)
-            if isinstance(a0, tuple) and a0[0] == "slice" and not a0[1].is_input:  # a window of an intermediate: read in place
-                a0, view = a0[1], (a0[2], a0[3] - a0[2])
+            if isinstance(a0, View) and not a0.is_input:  # a window of an intermediate: read in place
+                a0, view = a0.base, (a0.lo, a0.length)
         src = self.ensure_loaded(a0, si)
-        first = self.out_four(args[1:5], fn)
+        first = self.out_row(args[1:5], f"{fn} outputs must be variable names")
         self.p.add_op(_lib.OP_MIN_MAX if fn == "min_max" else _lib.OP_LINEAR_SLOPE_FIT, dst=first, src=src.slot, ip=view)
         self.release(src, si)
 
@@ -1695,7 +1676,7 @@ def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
             out_bind[f"out:{o}"] = (SimpleNamespace(name=o, dtype=col_dt), None)
             tb_out[o] = np.empty(n_rows, dtype=nat)
             continue
-        if _is_wf(v) and isinstance(v, tuple):  # a named slice: of an input it is read straight from the rows, else copied out of its waveform
+        if isinstance(v, View):  # a named slice: of an input it is read straight from the rows, else copied out of its waveform
             v = e.ensure_loaded(v, len(e.steps))
         if v is None or v.kind in (None,):
             raise ProcessingChainError(f"output '{o}' was never computed")
@@ -1726,7 +1707,7 @@ def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
             io = p.add_io(f"out:{o}", _lib.IO_WF_OUT, odt, v.length)
             p.add_op(_lib.OP_STORE, src=src_slot, io=io)
             out_bind[f"out:{o}"] = (SimpleNamespace(name=o, dtype=odt), v.length)
-            if getattr(v, "vector_len", None) is not None:
+            if v.vector_len is not None:
                 vl = v.vector_len
                 if isinstance(vl, Var) and vl.is_input and vl.source is not None:
                     vector_lens[o] = vl.source  # a column of the input table
@@ -1740,7 +1721,7 @@ def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
         unit_ns = _time_unit_ns(v.unit)
         if v.is_coord is True and v.grid is not None and unit_ns is not None and not stage_mode:  # (a stage hands on sample indices)
             v = b.converted(v, Grid(unit_ns))
-        if isinstance(v, Var) and v.sreg is None and (getattr(v, "aux_io", None) is not None or getattr(v, "ext_key", None) is not None):
+        if isinstance(v, Var) and v.sreg is None and (v.aux_io is not None or v.ext_key is not None):
             src_op = e.scalar_operand(v, [], what=f"output {o}")  # (stores read registers)
             v.sreg = p.add_sregs(1)
             p.add_op(_lib.OP_SCALAR_FUNC, dst=v.sreg, ip=(_lib.FN_COPY,), sp=(src_op, Scalar.const(0.0), Scalar.const(0.0)))
@@ -1751,7 +1732,7 @@ def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
             raise ProcessingChainError(f"output '{o}' was never computed")
         reg = e.scalar_operand(v, [], what=f"output {o}")
         odt = np.dtype(np.bool_) if getattr(v, "dtype", None) == np.dtype(np.bool_) else ft
-        as_dt = getattr(v, "out_dtype", None)  # (a count of get_multi_local_extrema: uint32 -- as its stage writes it, and as the table holds it)
+        as_dt = v.out_dtype  # (a count of get_multi_local_extrema: uint32 -- as its stage writes it, and as the table holds it)
         if stage_mode and as_dt is not None:
             odt = np.dtype(as_dt)
         io = p.add_io(f"out:{o}", _lib.IO_SCALAR_OUT, odt)

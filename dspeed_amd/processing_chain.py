@@ -43,7 +43,7 @@ from .chain import Chain, Program
 from .compiler import _PerEventInteger, _add_step, _compile
 from .device import DeviceArray, Event, HostPin, PinnedArray, Stream, dtype_code, set_device
 from .errors import DSPFatal, ProcessingChainError
-from .language import Grid, Quantity, SExpr, Var, WaveformInput, _Builder, _column, _int_loop_const, _int_loop_of, log  # noqa: F401  (re-exported)
+from .language import Char, Grid, Quantity, SExpr, Var, View, WaveformInput, _Builder, _column, _int_loop_const, _int_loop_of, log  # noqa: F401  (re-exported)
 from .recipe import Recipe
 
 
@@ -970,7 +970,7 @@ def _build_chain(processors, tb_in, db_dict, outputs, block_width, device, group
     chain.output_attrs = {}
     for o in out_pars:
         v, entry, a = b.vars.get(o), book.defined_by.get(o), {}
-        unit = getattr(v, "unit", None)
+        unit = None if isinstance(v, View) else getattr(v, "unit", None)  # (a named slice leaves without its waveform's unit, as it always has)
         if isinstance(unit, str):
             a["units"] = unit
         if entry is not None:

@@ -140,13 +140,13 @@ def test_per_event_time_expression():
 
 
 def test_quantity_arithmetic():
-    from dspeed_amd.processing_chain import _Builder
+    from dspeed_amd.processing_chain import Char, _Builder
 
     b = _Builder({"w": WaveformInput(np.zeros((2, 8192), dtype=np.float32), dt=16.0)}, {})
     assert b.eval_arg("round((128*ns+2*us)/w.period)") == 133
     assert b.eval_arg("len(w)-(33.6*us/w.period)-(4.8*us/w.period)") == pytest.approx(8192 - 2100 - 300)
     assert isinstance(b.eval_arg("10*us"), Quantity) and float(b.eval_arg("10*us")) == 10000.0
-    assert b.eval_arg("'l'") == ("char", "l")
+    assert b.eval_arg("'l'") == Char("l") and b.eval_arg("'l'").value == "l"
 
 
 def test_shard_rows_partitions_the_event_axis():
