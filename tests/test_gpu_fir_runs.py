@@ -17,7 +17,9 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-6
 
 
-def _program(n, offset, stride, taps, mode, keep=True, reductions=True, hint=1, walk_from=("t_max", 100), picks=(0, 57)):
+def _program(n, offset, stride, taps, mode, keep=True, reductions=True, hint=1, walk_from=("t_max", 100), picks=(0, 57), out_offset=0, out_stride=None, dtype=np.float32):
+    """``out_offset`` / ``out_stride``: where the kept output lies in its buffer (elements; a row of P + 8 from element 0 unless given);
+    ``dtype``: the rows' type"""
     from dspeed_amd import _lib
     from dspeed_amd.chain import Program, Scalar
 
@@ -25,14 +27,14 @@ def _program(n, offset, stride, taps, mode, keep=True, reductions=True, hint=1, 
     P = {"v": n - m + 1, "s": n, "f": n + m - 1}[mode]
     p = Program()
     p.slots = [n, P]
-    wf = p.add_io("wf", _lib.IO_WF_IN, np.float32, n, offset, stride)
+    wf = p.add_io("wf", _lib.IO_WF_IN, dtype, n, offset, stride)
     padded = -(-m // 16) * 16
     tp = p.add_io("taps", _lib.IO_TAPS, np.float32, padded, 0, 0)
     p.add_op(_lib.OP_LOAD, dst=0, io=wf)
     p.add_op(_lib.OP_CONVOLVE, dst=1, src=0, io=tp, ip=(ord(mode), 0, hint, m))
     outs = []
     if keep:
-        o = p.add_io("filtered", _lib.IO_WF_OUT, np.float32, P, 0, P + 8)
+        o = p.add_io("filtered", _lib.IO_WF_OUT, np.float32, P, out_offset, P + 8 if out_stride is None else out_stride)
         p.add_op(_lib.OP_STORE, src=1, io=o)
     if reductions:
         thr = p.add_io("thr", _lib.IO_SCALAR_IN, np.float32)
@@ -73,7 +75,7 @@ def _taps(which, rng):
         return np.array([1.0] * 5 + [-1.0] * 7, np.float32)
     if which == "one":
         return np.array([-2.5], np.float32)
-    if which == "runs24":  # as many runs as the kernel takes, zeros in front, in the middle and at the end
+    if which == "runs24":  # 23 breakpoints (the kernel takes 25: tests/fir_runs_cases.py), zeros in front, in the middle and at the end
         v = rng.uniform(-1, 1, 24).astype(np.float32)
         v[[0, 11, 23]] = 0.0
         v[12] = v[10]
@@ -83,7 +85,9 @@ def _taps(which, rng):
     raise KeyError(which)
 
 
-def _execute(prog, outs, P, w, taps, thr, fused, keep):
+def _execute(prog, outs, P, w, taps, thr, fused, keep, out_offset=0, out_stride=None, fill=None, geometry=None):
+    """``fill``: what the kept output's buffer holds before the launch (zeros unless given); the whole buffer then comes back as
+    ``filtered_buffer``.  ``geometry``: a dict that receives ``Chain.geometry`` of the launch"""
     from dspeed_amd.chain import Chain
     from dspeed_amd.device import DeviceArray
 
@@ -94,15 +98,21 @@ def _execute(prog, outs, P, w, taps, thr, fused, keep):
     bufs = {"wf": DeviceArray.from_numpy(w), "taps": DeviceArray.from_numpy(np.concatenate([taps, np.zeros(padded - len(taps), np.float32)]))}
     if outs:
         bufs["thr"] = DeviceArray.from_numpy(thr)
+    pitch = P + 8 if out_stride is None else out_stride
     if keep:
-        bufs["filtered"] = DeviceArray.zeros((n_rows, P + 8), np.float32)
+        bufs["filtered"] = DeviceArray.zeros((n_rows, pitch), np.float32) if fill is None else DeviceArray.from_numpy(np.full((n_rows, pitch), fill, np.float32))
     for name in outs:
         bufs[name] = DeviceArray.zeros((n_rows,), np.float32)
+    if geometry is not None:
+        geometry.update(ch.geometry(n_rows))
     ch.execute(bufs, n_rows)
     ch.check()
     got = {name: bufs[name].to_numpy() for name in outs}
     if keep:
-        got["filtered"] = bufs["filtered"].to_numpy()[:, :P]
+        whole = bufs["filtered"].to_numpy()
+        got["filtered"] = whole[:, out_offset:out_offset + P]
+        if fill is not None:
+            got["filtered_buffer"] = whole
     return ch.kernel_name, got
 
 
