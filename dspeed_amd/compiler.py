@@ -34,7 +34,8 @@ from .language import (Char, Grid, Quantity, SExpr, Var, View, _Builder, _GENERA
 _MULTI_EXTREMA = "get_multi_local_extrema"
 _HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
 _MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER)  # processors that run as stages ahead of the program, on kernels of their own
+_PSD = "psd"
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD)  # processors that run as stages ahead of the program, on kernels of their own
 _SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi")
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
@@ -108,6 +109,9 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
     if function in _GENERATORS:
         _fold_generator(b, function, args, new_vars)
         return
+    if function == "fft":
+        raise NotImplementedError(f"processor 'fft' ({key}): complex variables are not in the recipe language; the gufunc dspeed_amd.processors.fft "
+                                  "and the C entry dsp_fft are the interface (psd runs in recipes)")
     if function not in _SIGS:
         raise NotImplementedError(f"processor '{function}' is not implemented on the device path")
     roles = _SIGS[function]
@@ -847,6 +851,28 @@ def _stage_thresholds(cx: _Stager):
         cx.stage([step], [args[2]], f"{fn} {key} on rows")
 
 
+def _stage_spectrum(cx: _Stager):
+    """``psd`` runs on dsp_spectrum.hip and nowhere else, on rows in HBM: a mandatory stage, like the peak finder's.  The source is a chain
+    input, a stage's waveform, a slice of either, or a waveform the program computes, written to HBM first; the spectrum is an ordinary
+    waveform variable of the program."""
+    from .processors import check_spectrum_length
+
+    fn = _PSD
+    for st in cx.steps_of(fn):
+        args, key = list(st[1]), st[2]
+        src, out = args
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        m = src.length // 2 + 1
+        if not (isinstance(out, Var) and out.kind == "wf" and out.length):
+            raise ProcessingChainError(f"{fn} ({key}): declare the output as name(len(w_in)//2+1): {m} bins")
+        if out.length != m:
+            raise DSPFatal(f"Size of psd must be len(w_in)//2+1 = {m}")
+        check_spectrum_length(f"{fn} ({key})", src.length, np.float32)
+        _rows_in_memory(cx, src, fn, key)
+        cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+
+
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     """Long FIRs leave the program: each ``convolve_wf`` with a constant kernel of STAGE_MIN_TAPS or more taps becomes a launch of the
     matrix-core FIR kernels ahead of the program (one waveform per wavefront is the wrong shape for 133 x 8192 or 5792 x 301
@@ -871,6 +897,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_histogram(cx)  # (ahead of the peak finder: its thresholds may be arithmetic of these results, "3*fwhm")
     _stage_multi_extrema(cx)
     _stage_thresholds(cx)
+    _stage_spectrum(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and v.ext_key is not None and v.aux_io is None}
     cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
@@ -1483,6 +1510,14 @@ class _Emitter:
                       sp=(t_start, Scalar.const(float(args[3]))))
         self.release(src, si)
 
+    def psd(self, si, fn, args, what):
+        """the whole program of the stage: LOAD, PSD; the store of the spectrum follows"""
+        src = self.ensure_loaded(args[0], si)
+        out = self.out_wf(args[1], src.length // 2 + 1, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_PSD, dst=out.slot, src=src.slot)
+        self.release(src, si)
+
     def copy_slice(self, si, fn, args, what):
         src = self.ensure_loaded(args[0], si)
         dst = args[3]
@@ -1661,7 +1696,8 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          "slice": _Emitter.copy_slice, "min_max": _Emitter.four_values, "linear_slope_fit": _Emitter.four_values,
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
          "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
-         _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh}
+         _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
+         _PSD: _Emitter.psd}
 
 
 def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):

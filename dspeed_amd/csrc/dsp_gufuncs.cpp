@@ -406,6 +406,20 @@ extern "C" {
 DSP_GUFUNCS(f32, DSP_F32, float)
 DSP_GUFUNCS(f64, DSP_F64, double)
 #undef DSP_GUFUNCS
+
+// psd and fft: one entry for both loops (compute_dtype), rows of n_bins values -- (re, im) pairs for fft -- out_stride values of the loop's type apart
+static int spectrum(int opcode, const WfIn& in, int compute_dtype, void* out, int32_t n_bins, int64_t out_stride, void* st, int64_t* er) {
+    const char* name = opcode == DSP_OP_FFT ? "fft" : "psd";
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "%s: compute_dtype is DSP_F32 or DSP_F64", name);
+    if (n_bins < 1 || n_bins > (1 << 19)) return dsp_fail(DSP_ERR_ARG, "%s: the output holds at least one bin", name);
+    return wf2wf(compute_dtype, opcode, in, {}, {}, {out, opcode == DSP_OP_FFT ? 2 * n_bins : n_bins, out_stride}, st, er);
+}
+int dsp_psd(ROWS, int compute_dtype, void* psd_out, int32_t n_bins, int64_t out_stride, TAIL) {
+    return spectrum(DSP_OP_PSD, IN, compute_dtype, psd_out, n_bins, out_stride, TAIL_ARGS);
+}
+int dsp_fft(ROWS, int compute_dtype, void* dft_out, int32_t n_bins, int64_t out_stride, TAIL) {
+    return spectrum(DSP_OP_FFT, IN, compute_dtype, dft_out, n_bins, out_stride, TAIL_ARGS);
+}
 #undef ROWS
 #undef IN
 #undef TAIL

@@ -29,6 +29,7 @@
 #include "dsp_gufuncs.h"
 #include "dsp_launch.h"
 #include "dsp_plan.h"
+#include "dsp_spectrum_tables.h"
 
 #define fail dsp_fail
 #define elem_size dsp_elem_size
@@ -78,6 +79,7 @@ struct dsp_chain : ChainPlan {
     int cur_blocks_cap = 0;
     FirRunsTable* runs_table = nullptr;  // (run-length FIR) the kernel's breakpoints, rewritten by every launch; allocated at the first
     float* runs_scratch = nullptr;       // a row per resident wavefront for a filtered waveform that nothing keeps
+    void* spec_tables = nullptr;         // (psd, fft) twiddles, unpacking twiddles or chirp, filter: written once by dsp_chain_create, only read after
     // the error word handed to the host by a copy that is part of the launch (dsp_chain_set_async_check): dsp_chain_check then needs no
     // transfer of its own -- one issued while a large host-to-device copy of the next buffer is in flight queues up behind it
     int* err_mirror = nullptr;  // page-locked
@@ -95,6 +97,7 @@ struct dsp_chain : ChainPlan {
         if (cur_scratch) (void)hipFree(cur_scratch);
         if (runs_table) (void)hipFree(runs_table);
         if (runs_scratch) (void)hipFree(runs_scratch);
+        if (spec_tables) (void)hipFree(spec_tables);
         for (int k = 0; k < DSP_FIR_MAXK; ++k)
             if (f16.taps16[k]) (void)hipFree(const_cast<void*>(f16.taps16[k]));
         if (f16.row_scale) (void)hipFree(const_cast<void*>(f16.row_scale));
@@ -346,6 +349,32 @@ const char* dsp_last_error(void) { return dsp_plan_last_error(); }
 const char* dsp_version(void) { return "dspeed_hip 0.1 (gfx950)"; }
 
 
+// The tables of the spectrum kernel (dsp_spectrum_tables.h), float64 on the host, rounded once to the loop's type, in one device block: the
+// transform's twiddles, then the unpacking twiddles (a power-of-two row) or the chirp and the filter (Bluestein).  No launch writes them.
+static int spectrum_tables(dsp_chain* ch) {
+    namespace tb = dsp_spectrum_tables;
+    SpectrumArgs& A = ch->spec;
+    std::vector<double> all = tb::twiddle(A.points);
+    const size_t at_aux = all.size();
+    const std::vector<double> aux = A.bluestein ? tb::chirp(A.len) : tb::unpack(A.len);
+    all.insert(all.end(), aux.begin(), aux.end());
+    const size_t at_filter = all.size();
+    if (A.bluestein) {
+        const std::vector<double> f = tb::filter(A.len, A.points, A.log2_points);
+        all.insert(all.end(), f.begin(), f.end());
+    }
+    const size_t esz = ch->f64 ? 8 : 4;
+    std::vector<float> narrow;
+    if (!ch->f64) narrow.assign(all.begin(), all.end());
+    HIP_TRY(hipMalloc(&ch->spec_tables, all.size() * esz));
+    HIP_TRY(staged_h2d(ch->spec_tables, ch->f64 ? (const void*)all.data() : (const void*)narrow.data(), all.size() * esz));
+    const char* base = (const char*)ch->spec_tables;
+    A.twiddle = base;
+    A.aux = base + at_aux * esz;
+    A.filter = A.bluestein ? base + at_filter * esz : nullptr;
+    return DSP_OK;
+}
+
 int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_io, const int32_t* slot_len, int n_slots,
                      int n_sregs, int compute_dtype, dsp_chain** out) {
     if (out) *out = nullptr;
@@ -363,6 +392,8 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
             HIP_TRY(hipMalloc(&buf, dsp_fir_f16::taps_bytes(ch->fir.kend)));
             ch->f16.taps16[k] = buf;
         }
+    if (ch->kernel_only == DSP_ROUTE_SPECTRUM)
+        if (const int rc = spectrum_tables(ch.get())) return rc;
     HIP_TRY(hipGetDevice(&ch->device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, ch->device));
@@ -382,6 +413,9 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     if (!rc) rc = raise_lds(ch->scalar_ok, n_sregs * 64 * esz, 48 * 1024, "scalar kernel", dsp_internal_set_scalar_lds);
     if (!rc) rc = raise_lds(ch->cur_ok, ch->cur_lds_bytes, 64 * 1024, "current kernel, %d", dsp_internal_set_current_lds);
     if (!rc) rc = raise_lds(ch->rows_ok, ch->rows_lds_bytes, 64 * 1024, "rows kernel, %d", dsp_internal_set_rows_lds);
+    if (!rc)
+        rc = raise_lds(ch->kernel_only == DSP_ROUTE_SPECTRUM, dsp_spectrum::lds_bytes(ch->spec.len, esz), 64 * 1024, "spectrum kernel, %d",
+                       [&](int n) { return dsp_internal_set_spectrum_lds(ch->spec_src.dtype, n); });
     if (rc) return rc;
     *out = ch.release();
     return DSP_OK;
@@ -595,6 +629,13 @@ static int launch_thresh(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void
     return launch_on_rows(ch, n_wf, stream, A, ch->thresh_src, dsp_internal_launch_thresh, "threshold kernel launch");
 }
 
+static int launch_spectrum(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    SpectrumArgs A = ch->spec;  // (its table pointers are the chain's)
+    A.wf = io_ptrs[ch->spec_src.io];
+    A.out = io_at(ch, io_ptrs, ch->sio_out);
+    return launch_on_rows(ch, n_wf, stream, A, ch->spec_src, dsp_internal_launch_spectrum, "spectrum kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -778,6 +819,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_EXTREMA)) return launch_extrema(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_HIST)) return launch_hist(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_THRESH)) return launch_thresh(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_SPECTRUM)) return launch_spectrum(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -870,6 +912,12 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             lds = ch->host.n_sregs * 64 * ((ch->f64 || ch->i64) ? 8 : 4), wpb = 1, b = (int)((n_wf + 63) / 64);
             break;
         case DSP_ROUTE_HIST: lds = dsp_hist::lds_bytes(ch->hist.m) / 4, wpb = 4, b = (int)((n_wf + 3) / 4); break;
+        case DSP_ROUTE_SPECTRUM: {
+            const int n = ch->spec.len, es = ch->f64 ? 8 : 4;
+            const bool wide = dsp_spectrum::wide(n, es);
+            lds = dsp_spectrum::row_bytes(n, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
+            break;
+        }
         case DSP_ROUTE_EXTREMA:
         case DSP_ROUTE_THRESH:
         case DSP_ROUTE_PZ_ROWS:

@@ -12,6 +12,7 @@ enum dsp_route {
     DSP_ROUTE_EXTREMA,  // (the one route that is no optimisation: the interpreter has no MULTI_EXTREMA, so no switch turns it off)
     DSP_ROUTE_HIST,     // (nor this one: HISTOGRAM and HISTOGRAM_STATS have no interpreter case either)
     DSP_ROUTE_THRESH,   // (nor this: MULTI_TIME_POINT_THRESH and TIME_OVER_THRESHOLD)
+    DSP_ROUTE_SPECTRUM, // (nor this: PSD and FFT)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -20,6 +21,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_extrema_kernel",
     "dsp_hist_kernel",
     "dsp_thresh_kernel",
+    "dsp_spectrum_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -28,6 +30,24 @@ namespace dsp_hist {  // dsp_hist.hip: a uint32 counter per bin (rounded up to w
 constexpr int WAVES = 4;
 constexpr int lds_bytes(int m) { return WAVES * ((m + 63) & ~63) * 4; }
 }  // namespace dsp_hist
+
+namespace dsp_spectrum {  // dsp_spectrum.hip: a row's transform as (re, im) pairs of the loop's type in LDS
+// complex points of the transform of a row of n samples: n / 2 for a power of two (the real row packed in pairs; 1 for n <= 2), else
+// Bluestein's padded length, the power of two >= 2 n - 1
+constexpr bool pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+constexpr int points(int n) {
+    if (pow2(n)) return n >= 2 ? n / 2 : 1;
+    int m = 1;
+    while (m < 2 * n - 1) m *= 2;
+    return m;
+}
+constexpr int row_bytes(int n, int esz) { return points(n) * 2 * esz; }
+// the geometry: rows whose transform fills at most this much LDS get a wavefront each, four to a workgroup (32 KiB); longer ones a
+// workgroup of 256 (up to 64 KiB), with 16 bytes behind the transform for the word its wavefronts agree through
+constexpr int WAVE_ROW_BYTES = 8 * 1024;
+constexpr bool wide(int n, int esz) { return row_bytes(n, esz) > WAVE_ROW_BYTES; }
+constexpr int lds_bytes(int n, int esz) { return wide(n, esz) ? row_bytes(n, esz) + 16 : 4 * row_bytes(n, esz); }
+}  // namespace dsp_spectrum
 
 namespace dsp_current {  // dsp_current.hip
 constexpr int CB = 16;   // samples per block (= per checkpoint)

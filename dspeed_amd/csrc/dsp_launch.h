@@ -38,6 +38,9 @@ int dsp_internal_launch_extrema(const ExtremaArgs* A, int64_t n_wf, int dtype, i
 int dsp_internal_launch_hist(const HistArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_thresh.hip (dtype: the rows'; vec as above; A->m 0: time_over_threshold, else multi_time_point_thresh with m thresholds)
 int dsp_internal_launch_thresh(const ThreshArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+// dsp_spectrum.hip (dtype: the rows'; vec as above; the tables of A are the chain's; LDS: dsp_spectrum::lds_bytes, 16 bytes past 64 KiB for the longest rows)
+int dsp_internal_launch_spectrum(const SpectrumArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+int dsp_internal_set_spectrum_lds(int dtype, int lds_bytes);
 // dsp_scalar.hip (type: 0 float32, 1 float64, 2 int64 registers)
 int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);
 int dsp_internal_set_scalar_lds(int lds_bytes);

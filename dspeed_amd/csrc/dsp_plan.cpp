@@ -75,6 +75,8 @@ extern "C" const char* dsp_fatal_message(int code) {
         case DSP_E_HIST_STATS_LEN: return "length edges_in must be exactly 1 + length of weights_in";
         case DSP_E_MTPT_POLARITY: return "polarity cannot be 0";
         case DSP_E_MTPT_MODE: return "Unrecognized interpolation mode";
+        case DSP_E_FFT_LEN: return "Size of fft must be len(w_in)//2+1";  // (raised with the length behind it, as the reference formats it)
+        case DSP_E_PSD_LEN: return "Size of psd must be len(w_in)//2+1";
         default: return "";
     }
 }
@@ -106,6 +108,7 @@ struct KernelOnlyRoute {
 static bool match_extrema_shape(const PlanCtx& c, const char** why);
 static bool match_hist_shape(const PlanCtx& c, const char** why);
 static bool match_thresh_shape(const PlanCtx& c, const char** why);
+static bool match_spectrum_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -113,6 +116,7 @@ static const KernelOnlyRoute kernel_only_routes[] = {
      "DSP_OP_HISTOGRAM / DSP_OP_HISTOGRAM_STATS (histogram, histogram_stats) run on dsp_hist_kernel only"},
     {DSP_ROUTE_THRESH, {DSP_OP_MULTI_TIME_POINT_THRESH, DSP_OP_TIME_OVER_THRESHOLD}, match_thresh_shape,
      "DSP_OP_MULTI_TIME_POINT_THRESH / DSP_OP_TIME_OVER_THRESHOLD (multi_time_point_thresh, time_over_threshold) run on dsp_thresh_kernel only"},
+    {DSP_ROUTE_SPECTRUM, {DSP_OP_PSD, DSP_OP_FFT}, match_spectrum_shape, "DSP_OP_PSD / DSP_OP_FFT (psd, fft) run on dsp_spectrum_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -576,6 +580,37 @@ static bool match_thresh_shape(const PlanCtx& c, const char** why) {
     }
     ch->tio_out = st.io;
     A.out_stride = io[st.io].row_stride;
+    return true;
+}
+
+// Is the program one of the spectrum kernel's (dsp_spectrum.hip)?
+//   LOAD s;  PSD of s;  STORE of its n / 2 + 1 bins
+//   LOAD s;  FFT of s;  STORE of its 2 (n / 2 + 1) values, (re, im) pairs
+// Lengths and limits are lower_op's business (every program that holds either op passes there first).  Why not, otherwise: `why`.
+static bool match_spectrum_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    *why = "the program must be exactly LOAD, PSD, STORE or LOAD, FFT, STORE";
+    if (c.n_ops != 3 || c.n_slots != 2 || ops[0].opcode != DSP_OP_LOAD || (ops[1].opcode != DSP_OP_PSD && ops[1].opcode != DSP_OP_FFT) ||
+        ops[2].opcode != DSP_OP_STORE)
+        return false;
+    const dsp_op &ld = ops[0], &op = ops[1], &st = ops[2];
+    SpectrumArgs& A = ch->spec;
+    memset(&A, 0, sizeof A);
+    ch->sio_out = -1;
+    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->spec_src, why,
+                                       "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
+    *why = "the spectrum is stored once, in the loop's type";
+    if (st.src != op.dst || c.io[st.io].dtype != c.compute_dtype) return false;
+    A.m = A.len / 2 + 1;
+    A.complex_out = op.opcode == DSP_OP_FFT ? 1 : 0;
+    A.points = dsp_spectrum::points(A.len);
+    for (A.log2_points = 0; (1 << A.log2_points) < A.points; ++A.log2_points) {}
+    A.bluestein = dsp_spectrum::pow2(A.len) ? 0 : 1;
+    A.wide = dsp_spectrum::wide(A.len, c.esz) ? 1 : 0;
+    ch->sio_out = st.io;
+    A.out_stride = c.io[st.io].row_stride;
     return true;
 }
 
@@ -1105,6 +1140,8 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_WINDOWER:
         case DSP_OP_AVG_CURRENT:
         case DSP_OP_UPSAMPLER:
+        case DSP_OP_PSD:
+        case DSP_OP_FFT:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
         case DSP_OP_DWT_HAAR: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[2]; return 3;
         case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
@@ -1289,7 +1326,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT: their own layout and limits)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1669,6 +1706,22 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
                 return fail(DSP_ERR_ARG, "op %d: bad TIME_OVER_THRESHOLD (src: the slot of the row; dst: the register of the count)", i);
             if (!f64 && slot_len[o.src] > (1 << 24))
                 return fail(DSP_ERR_UNSUPPORTED, "time_over_threshold: the float32 loop takes rows of at most 2^24 samples (%d): the count is exact", slot_len[o.src]);
+            break;
+        }
+        case DSP_OP_PSD:
+        case DSP_OP_FFT: {
+            const bool cplx = o.opcode == DSP_OP_FFT;
+            const char* name = cplx ? "fft" : "psd";
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad %s (src: the slot of the row; dst: the slot of the spectrum%s)", i, cplx ? "FFT" : "PSD",
+                            cplx ? ", (re, im) pairs" : "");
+            const int n = slot_len[o.src], m = n / 2 + 1;
+            // the reference's check, first (fft.py:39-40, 119-120)
+            if (slot_len[o.dst] != (cplx ? 2 * m : m)) return fail(cplx ? DSP_E_FFT_LEN : DSP_E_PSD_LEN, "Size of %s must be len(w_in)//2+1 = %d", name, m);
+            const int pow2_max = DSP_SPECTRUM_F32_POW2_MAX / (f64 ? 2 : 1), any_max = DSP_SPECTRUM_F32_ANY_MAX / (f64 ? 2 : 1);
+            if (dsp_spectrum::pow2(n) ? n > pow2_max : n > any_max)
+                return fail(DSP_ERR_UNSUPPORTED, "%s: the %s loop takes rows of a power of two up to %d samples and of any other length up to %d (%d given): a row's transform lives in 64 KiB of LDS",
+                            name, f64 ? "float64" : "float32", pow2_max, any_max, n);
             break;
         }
         case DSP_OP_DWT_HAAR: {

@@ -330,6 +330,30 @@ struct ThreshArgs {
     int64_t out_stride;
 };
 
+// arguments of the spectrum kernel (dsp_spectrum.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> PSD -> STORE
+//   LOAD -> FFT -> STORE
+// One row is one transform of `points` complex points (a power of two) held in LDS: a power-of-two row packed as len / 2 points and unpacked
+// behind the transform, any other row Bluestein's convolution of the next power of two >= 2 len - 1.  The tables are the chain's, written
+// once when it is created (dsp_spectrum_tables.h); (re, im) pairs of the loop's type.
+#define DSP_SPECTRUM_F32_POW2_MAX 16384 /* samples of a power-of-two row, float32 loop (the float64 loop: half): 64 KiB of LDS a row */
+#define DSP_SPECTRUM_F32_ANY_MAX 4096   /* samples of any other row, float32 loop (the float64 loop: half) */
+struct SpectrumArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples
+    int32_t m;               // bins: len / 2 + 1
+    int32_t complex_out;     // 1: fft (2 m values a row), 0: psd
+    int32_t points, log2_points;  // the transform in LDS
+    int32_t bluestein;       // 0: len is a power of two
+    int32_t wide;            // 1: a workgroup of 256 per row, 0: a wavefront per row, four rows to a workgroup
+    const void* twiddle;     // exp(-2 pi i k / points), k < points / 2
+    const void* aux;         // power of two: exp(-2 pi i k / len), k <= len / 2 (the unpacking step); Bluestein: the chirp exp(-i pi j^2 / len), j < len
+    const void* filter;      // Bluestein: the spectrum of the conjugate chirp over `points`, in bit-reversed order
+    void* out;
+    int64_t out_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

@@ -43,6 +43,15 @@ class Quantity(float):
         return f"{float(self):g}*ns"
 
 
+class Frequency(float):
+    """The reciprocal of a time, in 1 / ns: what ``1/wf.period/len(wf)`` is, the spacing of a spectrum's bins (the ``period=`` of a psd's
+    declaration, reference processors/fft.py:117).  It exists inside the ``period=`` / ``offset=`` of a declaration only; plain numbers
+    scale it, nothing else combines with it."""
+
+    def __repr__(self):
+        return f"{float(self):g}/ns"
+
+
 class WaveformInput:
     """Input column with sampling information, the role of ``lgdo.WaveformTable`` (values, dt, t0) in the reference
     (processing_chain.py:2263-2360).  ``dt`` and ``t0`` in nanoseconds; ``t0`` is one number or one value per row (an ndarray or
@@ -67,7 +76,7 @@ class Grid:
         self.period, self.offset, self.offset_var = float(period), float(offset), offset_var
 
     def __eq__(self, other):  # (a variable offset compares by identity, reference :107-113)
-        return (isinstance(other, Grid) and self.period == other.period and self.offset == other.offset
+        return (type(other) is type(self) and self.period == other.period and self.offset == other.offset
                 and self.offset_var is other.offset_var)
 
     __hash__ = None
@@ -77,11 +86,21 @@ class Grid:
 
     def shifted(self, first_sample: int, step: int = 1) -> "Grid":
         """grid of wf[first_sample::step] (reference :1032-1054)"""
-        return Grid(self.period * step, self.offset + first_sample * self.period, self.offset_var)
+        return type(self)(self.period * step, self.offset + first_sample * self.period, self.offset_var)
 
     def __repr__(self):
         off = f"{self.offset:g}" + (f"+{self.offset_var.name}" if self.offset_var is not None else "")
         return f"({self.period:g}*ns,{off})"
+
+
+class FrequencyGrid(Grid):
+    """The grid of a spectrum: period and offset in 1 / ns (bin spacing, frequency of bin 0).  It is kept with the variable, shifted by its
+    slices and is no other grid's equal: a time is never converted onto it."""
+
+    __slots__ = ()
+
+    def __repr__(self):
+        return f"({self.period:g}/ns,{self.offset:g})"
 
 
 def _time_unit_ns(unit):
@@ -219,6 +238,7 @@ _SIGS = {
     "upsampler": "wsW", "moving_window_multi": "wsiiW", "numpy_subtract": "wsW", "numpy_add": "wsW", "min_max_norm": "wssW", "linear_slope_fit": "wSSSS",
     "histogram": "wWW", "histogram_stats": "wwSSSs",  # (w_in, weights_out, borders_out); (weights_in, edges_in, mode_out, max_out, fwhm_out, max_in)
     "multi_time_point_thresh": "wtsscW", "time_over_threshold": "wsS",  # (w_in, a_threshold[m], t_start, polarity, mode_in, t_out[m]); (w_in, a_threshold, n_samples)
+    "psd": "wW",  # (w_in, psd_out[len(w_in) // 2 + 1])
     "get_multi_local_extrema": "wssissWWSS",  # (w_in, a_delta_max_in, a_delta_min_in, search_direction, a_abs_max_in, a_abs_min_in, two lists, two counts)
 }
 _SIGS.update({"sample": "wiS", "slice": "wiiW", "get": "wsS"})  # wf[i], wf[lo:hi:step], wf[variable] (reference :948-1071)
@@ -321,10 +341,16 @@ _PROCESSOR_FILES = {
 }
 
 
+# the spectral processors (processors.SPECTRAL) and their file, beside the table above: that one is compared name by name with the registry's
+# __all__ (tests/test_histogram_plan_cpu.py), where these two are not
+_SPECTRAL_FILES = {"psd": ("fft",), "fft": ("fft",)}
+
+
 def module_accepted(module, function) -> bool:
     """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
     pre = "dspeed.processors."
-    return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in _PROCESSOR_FILES.get(function, ()))
+    files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ())
+    return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in files)
 
 
 _NUMPY_BINARY = {"add": ast.Add, "subtract": ast.Sub, "multiply": ast.Mult, "divide": ast.Div, "true_divide": ast.Div}
@@ -345,6 +371,7 @@ class _Builder:
         self.vars: dict[str, Var] = {}
         self.steps = []  # (function name, [operands], recipe key)
         self.default_period = next((col.dt for col in self.tb_in.values() if isinstance(col, WaveformInput)), None)
+        self._frequencies = False  # (inside the period= / offset= of a declaration: number / time is a frequency there)
         self.cur_key = None   # recipe entry being added (the expression steps it creates carry its name)
         self._anon = 0        # counter behind the names of expression results
         self._conversions = {}  # (id(value), target grid key, rounding) -> SExpr: one conversion per variable and grid (reference :303-313)
@@ -507,6 +534,8 @@ class _Builder:
             raise ProcessingChainError(f"'{base.name}' has no coordinate grid (wrap the input in WaveformInput, or declare grid=/period=)")
         if n.attr == "grid":
             return grid
+        if isinstance(grid, FrequencyGrid):
+            return Frequency(grid.period if n.attr == "period" else grid.offset)
         if n.attr == "period":
             return Quantity(grid.period)
         if grid.offset_var is None:
@@ -654,7 +683,13 @@ class _Builder:
                 v.dtype = np.dtype(_text(self._eval(n.args[1], src, new)))
         elif not n.args and not n.keywords:
             raise ProcessingChainError(f"declaration '{src}' needs a shape")
-        kw = {k.arg: self._eval(k.value, src, new) for k in n.keywords}
+        kw = {}
+        for k in n.keywords:
+            self._frequencies = k.arg in ("period", "offset")
+            try:
+                kw[k.arg] = self._eval(k.value, src, new)
+            finally:
+                self._frequencies = False
         for k in kw:
             if k not in ("unit", "period", "offset", "grid", "dtype", "is_coord", "shape", "vector_len"):
                 raise ProcessingChainError(f"unknown keyword '{k}' in declaration '{src}'")
@@ -688,6 +723,11 @@ class _Builder:
                 v.grid = kw["grid"]
             elif "period" in kw:
                 per, off = kw["period"], kw.get("offset", 0.0)
+                if isinstance(per, Frequency):  # a spectrum: bins 1 / time apart, bin 0 at frequency 0 unless said otherwise
+                    if not isinstance(off, (int, float)) or isinstance(off, Quantity):
+                        raise ProcessingChainError(f"offset= in '{src}' beside a period in 1 / time is a frequency or a number of bins")
+                    v.grid = FrequencyGrid(float(per), float(off) if isinstance(off, Frequency) else float(off) * float(per))
+                    return v
                 if not isinstance(per, Quantity):
                     raise ProcessingChainError(f"period= in '{src}' must be a time")
                 if _is_scalar(off) and (off.is_coord is not True or off.grid is None):
@@ -769,12 +809,25 @@ class _Builder:
                 raise ProcessingChainError("unsupported operator in argument expression")
             return fn(a, b)
         qa, qb = isinstance(a, Quantity), isinstance(b, Quantity)
+        if isinstance(a, Frequency) or isinstance(b, Frequency) or (isinstance(op, ast.Div) and qb and not qa):
+            # number / time is a frequency, in the period= / offset= of a declaration and nowhere else; plain numbers scale one
+            # (1/wf.period/len(wf): a spectrum's bin spacing)
+            if not self._frequencies:
+                raise ProcessingChainError("number / time is not supported")
+            plain = lambda x: not isinstance(x, (Quantity, Frequency))  # noqa: E731
+            if isinstance(op, ast.Div) and plain(b) and float(b) != 0:
+                return Frequency(float(a) / float(b))
+            if isinstance(op, ast.Div) and qb and plain(a) and float(b) != 0:
+                return Frequency(float(a) / float(b))
+            if isinstance(op, ast.Mult) and (plain(a) or plain(b)):
+                return Frequency(float(a) * float(b))
+            raise ProcessingChainError(f"a frequency (number / time) in '{src}' is scaled by plain numbers only")
         fa, fb = float(a), float(b)
         # by operator: (the operation, is the result a time?, why it is refused)
         rules = {ast.Add: (operator.add, qa or qb, qa != qb and "adding a time to a plain number"),
                  ast.Sub: (operator.sub, qa or qb, qa != qb and "subtracting a time and a plain number"),
                  ast.Mult: (operator.mul, qa != qb, qa and qb and "time * time is not a time"),
-                 ast.Div: (operator.truediv, qa and not qb, qb and not qa and "number / time is not supported"),
+                 ast.Div: (operator.truediv, qa and not qb, False),
                  ast.FloorDiv: (operator.floordiv, qa and not qb, False)}
         if type(op) not in rules:
             raise ProcessingChainError("unsupported operator in argument expression")

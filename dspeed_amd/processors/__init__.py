@@ -16,7 +16,7 @@ import numpy as np
 from .. import _lib
 from ..device import DeviceArray
 from ..errors import DSPFatal
-from ..gufunc import HipGUFunc, device_call, dtype_of
+from ..gufunc import HipGUFunc, device_call, dtype_of, run
 
 
 def _split(g, args):
@@ -370,6 +370,61 @@ cusp_filter = HipGUFunc("cusp_filter", "(),(),(),(n)", ["ffff", "dddd"], _cusp_f
                         "CUSP kernel generator, evaluated once on the host at chain build (reference processors/energy_kernels.py:12-73)")
 zac_filter = HipGUFunc("zac_filter", "(),(),(),(n)", ["ffff", "dddd"], _zac_filter,
                        "zero-area CUSP kernel generator, host, once (reference processors/energy_kernels.py:76-157)")
+
+# --------------------------------------------------------------------------------------------------- spectra
+def spectrum_limits(loop_dtype):
+    """(longest power-of-two row, longest row of any other length) of psd / fft in a loop: the transform lives in 64 KiB of LDS"""
+    half = 2 if np.dtype(loop_dtype) == np.dtype(np.float64) else 1
+    return _lib.SPECTRUM_F32_POW2_MAX // half, _lib.SPECTRUM_F32_ANY_MAX // half
+
+
+def check_spectrum_length(what, n, loop_dtype):
+    pow2_max, any_max = spectrum_limits(loop_dtype)
+    if n > (pow2_max if n & (n - 1) == 0 else any_max):
+        raise NotImplementedError(f"{what}: the {np.dtype(loop_dtype).name} loop takes rows of a power of two up to {pow2_max} samples and of any other "
+                                  f"length up to {any_max} ({n} given): a row's transform lives in 64 KiB of LDS")
+
+
+def _spectrum(complex_out):
+    """psd / fft: one C entry for both loops (``dsp_psd`` / ``dsp_fft`` take the loop's type).  fft's output is complex64 / complex128 to the
+    caller and (re, im) pairs of the loop's type to the device: the same bytes."""
+
+    def impl(g, *args):
+        name = g.__name__
+        if len(args) != 2 or args[1] is None:
+            raise TypeError(f"{name}(w_in, {name}_out): {name}_out must be passed (len(w_in)//2 + 1 bins)")
+        w_in, out = args
+        with device_call(name, w_in, f64_rows_only=True) as c:
+            m = c.n // 2 + 1
+            ct = np.dtype(np.complex64 if c.ft is np.float32 else np.complex128) if complex_out else np.dtype(c.ft)
+            if not isinstance(out, (np.ndarray, DeviceArray)):
+                raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+            if out.shape[-1] != m:
+                raise DSPFatal(f"Size of {name} must be len(w_in)//2+1 = {m}")
+            if np.dtype(out.dtype) != ct:
+                raise TypeError(f"{name}: {name}_out is {ct.name} in the {np.dtype(c.ft).name} loop ({np.dtype(out.dtype).name} given)")
+            check_spectrum_length(name, c.n, c.ft)
+            ptr, res = c.st.out(out, (m,) if c.one_d else (c.n_wf, m), ct)
+            c.results.append(res)
+            width = 2 * m if complex_out else m
+            run(getattr(_lib.lib(), f"dsp_{name}"), name, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, ptr, m, width)
+            c.st.finish()
+            return res
+
+    return impl
+
+
+psd = HipGUFunc("psd", "(n),(m)", ["ff", "dd"], _spectrum(False),
+                "power spectrum (re^2 + im^2) / n of a real row, len(w_in)//2 + 1 bins; a row with a NaN or an infinity: NaN bins "
+                "(reference processors/fft.py:92-126)")
+fft = HipGUFunc("fft", "(n),(m)", ["fF", "dD"], _spectrum(True),
+                "spectrum of a real row, NumPy's rfft: len(w_in)//2 + 1 complex bins; a row with a NaN or an infinity: bins NaN + 0j "
+                "(reference processors/fft.py:12-46)")
+
+# The spectral processors are attributes of this module -- "module": "dspeed.processors" resolves them -- and are listed here, not in
+# __all__: tests/test_gufunc_calls_cpu.py holds a call record for every name of __all__, and these two have theirs in a file of their own
+# (tests/test_spectrum_plan_cpu.py).
+SPECTRAL = ("fft", "psd")
 
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

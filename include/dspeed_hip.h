@@ -73,6 +73,8 @@ extern "C" {
 #define DSP_E_HIST_STATS_LEN 30 /* histogram_stats.py:227-228 */
 #define DSP_E_MTPT_POLARITY 31 /* time_point_thresh.py:313-314   checked at chain creation: polarity is a constant */
 #define DSP_E_MTPT_MODE 32     /* time_point_thresh.py:357-358   likewise */
+#define DSP_E_FFT_LEN 33       /* fft.py:39-40    "Size of fft must be len(w_in)//2+1 = ..." (the text carries the length: dsp_last_error) */
+#define DSP_E_PSD_LEN 34       /* fft.py:119-120  "Size of psd must be len(w_in)//2+1 = ..." */
 
 /* ---- element types -------------------------------------------------------------------------- */
 #define DSP_F32 0
@@ -260,6 +262,14 @@ typedef struct dsp_scalar_arg {
                                  *   LOAD, MULTI_TIME_POINT_THRESH, STORE of dst                 (one list of thresholds)
                                  *   LOAD, LOAD of the thresholds, MULTI_TIME_POINT_THRESH, STORE of dst
                                  *   LOAD, TIME_OVER_THRESHOLD, STORE_SCALAR of dst */
+#define DSP_OP_PSD 39           /* fft.py:92-126 psd: dst (n / 2 + 1 samples) <- (re^2 + im^2) / n of the real spectrum of src (n samples), in the loop's type */
+#define DSP_OP_FFT 40           /* fft.py:12-46 fft: dst (2 (n / 2 + 1) samples: re, im interleaved) <- sum_j src[j] exp(-2 pi i j k / n), k = 0 .. n / 2
+                                 * (NumPy's rfft: no normalisation).  A row with a NaN or an infinity: every bin NaN (fft: real part NaN, imaginary part 0).
+                                 * Float32 / int16 / uint16 rows in the float32 loop (powers of two up to 16384 samples, any other length up to 4096),
+                                 * float64 rows in the float64 loop (half of each).
+                                 * The waveform interpreter has neither op: they run on dsp_spectrum_kernel only, in a program of exactly
+                                 *   LOAD, PSD, STORE of dst
+                                 *   LOAD, FFT, STORE of dst */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -505,6 +515,14 @@ int dsp_multi_time_point_thresh_f32(const void* in, int in_dtype, int64_t n_wf, 
 /* "(n),()->()": the number of samples above a_threshold (a column or a constant), one value per row */
 int dsp_time_over_threshold_f32(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const float* a_threshold_dev,
                                 float a_threshold, float* n_samples_out, void* stream, int64_t* err_row);
+
+/* "(n),(m)" psd and fft (fft.py:92-126, 12-46), m == wf_len / 2 + 1 bins.  One entry for both loops, which compute_dtype names (DSP_F32:
+ * float32 / int16 / uint16 rows, float outputs; DSP_F64: float64 rows, double outputs).  dsp_fft writes bins as (re, im) pairs: rows of
+ * 2 n_bins values of the loop's type, out_stride of them apart. */
+int dsp_psd(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, void* psd_out, int32_t n_bins,
+            int64_t out_stride, void* stream, int64_t* err_row);
+int dsp_fft(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, void* dft_out, int32_t n_bins,
+            int64_t out_stride, void* stream, int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
