@@ -34,9 +34,9 @@ from .language import (Char, Grid, Quantity, SExpr, Var, View, _Builder, _GENERA
 _MULTI_EXTREMA = "get_multi_local_extrema"
 _HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
 _MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
-_PSD = "psd"
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD)  # processors that run as stages ahead of the program, on kernels of their own
-_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi")
+_PSD, _SORT = "psd", "sort"
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT)  # processors that run as stages ahead of the program, on kernels of their own
+_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
 
@@ -873,6 +873,27 @@ def _stage_spectrum(cx: _Stager):
         cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
 
 
+def _stage_sort(cx: _Stager):
+    """``sort`` runs on dsp_sort.hip and nowhere else, on rows in HBM: a mandatory stage, like the spectrum's.  The source is a chain input,
+    a stage's waveform, a slice of either, or a waveform the program computes, written to HBM first; the sorted row is an ordinary waveform
+    variable of the program, with the source's length and grid."""
+    from .processors import check_sort_length
+
+    fn = _SORT
+    for st in cx.steps_of(fn):
+        args, key = list(st[1]), st[2]
+        src, out = args
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        if not (isinstance(out, Var) and out.kind == "wf" and out.length):
+            raise ProcessingChainError(f"{fn} ({key}): the output is a waveform variable")
+        if out.length != src.length:
+            raise ProcessingChainError(f"{fn} ({key}): '{out.name}' holds {out.length} samples, the source {src.length}")
+        check_sort_length(f"{fn} ({key})", src.length, np.float32)
+        _rows_in_memory(cx, src, fn, key)
+        cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+
+
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     """Long FIRs leave the program: each ``convolve_wf`` with a constant kernel of STAGE_MIN_TAPS or more taps becomes a launch of the
     matrix-core FIR kernels ahead of the program (one waveform per wavefront is the wrong shape for 133 x 8192 or 5792 x 301
@@ -898,6 +919,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_multi_extrema(cx)
     _stage_thresholds(cx)
     _stage_spectrum(cx)
+    _stage_sort(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and v.ext_key is not None and v.aux_io is None}
     cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
@@ -1518,6 +1540,14 @@ class _Emitter:
         self.p.add_op(_lib.OP_PSD, dst=out.slot, src=src.slot)
         self.release(src, si)
 
+    def sort(self, si, fn, args, what):
+        """the whole program of the stage: LOAD, SORT; the store of the sorted row follows"""
+        src = self.ensure_loaded(args[0], si)
+        out = self.out_wf(args[1], src.length, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_SORT, dst=out.slot, src=src.slot)
+        self.release(src, si)
+
     def copy_slice(self, si, fn, args, what):
         src = self.ensure_loaded(args[0], si)
         dst = args[3]
@@ -1697,7 +1727,7 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
          "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
          _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
-         _PSD: _Emitter.psd}
+         _PSD: _Emitter.psd, _SORT: _Emitter.sort}
 
 
 def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):

@@ -420,6 +420,11 @@ int dsp_psd(ROWS, int compute_dtype, void* psd_out, int32_t n_bins, int64_t out_
 int dsp_fft(ROWS, int compute_dtype, void* dft_out, int32_t n_bins, int64_t out_stride, TAIL) {
     return spectrum(DSP_OP_FFT, IN, compute_dtype, dft_out, n_bins, out_stride, TAIL_ARGS);
 }
+// sort: one entry for both loops too (compute_dtype), rows of wf_len values out_stride values of the loop's type apart
+int dsp_sort_rows(ROWS, int compute_dtype, void* sorted_out, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "sort: compute_dtype is DSP_F32 or DSP_F64");
+    return wf2wf(compute_dtype, DSP_OP_SORT, IN, {}, {}, {sorted_out, wf_len, out_stride}, TAIL_ARGS);
+}
 #undef ROWS
 #undef IN
 #undef TAIL

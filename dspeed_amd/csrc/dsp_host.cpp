@@ -416,6 +416,9 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     if (!rc)
         rc = raise_lds(ch->kernel_only == DSP_ROUTE_SPECTRUM, dsp_spectrum::lds_bytes(ch->spec.len, esz), 64 * 1024, "spectrum kernel, %d",
                        [&](int n) { return dsp_internal_set_spectrum_lds(ch->spec_src.dtype, n); });
+    if (!rc)
+        rc = raise_lds(ch->kernel_only == DSP_ROUTE_SORT, dsp_sort::lds_bytes(ch->sort.len, esz), 64 * 1024, "sort kernel, %d",
+                       [&](int n) { return dsp_internal_set_sort_lds(ch->sort_src.dtype, n); });
     if (rc) return rc;
     *out = ch.release();
     return DSP_OK;
@@ -636,6 +639,13 @@ static int launch_spectrum(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, vo
     return launch_on_rows(ch, n_wf, stream, A, ch->spec_src, dsp_internal_launch_spectrum, "spectrum kernel launch");
 }
 
+static int launch_sort(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    SortArgs A = ch->sort;
+    A.wf = io_ptrs[ch->sort_src.io];
+    A.out = io_at(ch, io_ptrs, ch->oio_out);
+    return launch_on_rows(ch, n_wf, stream, A, ch->sort_src, dsp_internal_launch_sort, "sort kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -820,6 +830,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_HIST)) return launch_hist(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_THRESH)) return launch_thresh(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_SPECTRUM)) return launch_spectrum(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_SORT)) return launch_sort(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -916,6 +927,12 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             const int n = ch->spec.len, es = ch->f64 ? 8 : 4;
             const bool wide = dsp_spectrum::wide(n, es);
             lds = dsp_spectrum::row_bytes(n, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
+            break;
+        }
+        case DSP_ROUTE_SORT: {
+            const int n = ch->sort.len, es = ch->f64 ? 8 : 4;
+            const bool wide = dsp_sort::wide(n);
+            lds = dsp_sort::padded(n) * es / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
             break;
         }
         case DSP_ROUTE_EXTREMA:

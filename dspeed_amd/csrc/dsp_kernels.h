@@ -4,6 +4,7 @@
 // cannot link a .hip file, see the same arithmetic.  No HIP: plain C++17.  Internal header; the public contract is include/dspeed_hip.h.
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
 
 // The kernels a chain can run on, in their order of precedence: a program that has the shape of several (the *_ok flags) runs on the first
 // whose switch is on.  dsp_plan_route is the one place that holds this order for everything that reports a plan (kernel name, note,
@@ -13,6 +14,7 @@ enum dsp_route {
     DSP_ROUTE_HIST,     // (nor this one: HISTOGRAM and HISTOGRAM_STATS have no interpreter case either)
     DSP_ROUTE_THRESH,   // (nor this: MULTI_TIME_POINT_THRESH and TIME_OVER_THRESHOLD)
     DSP_ROUTE_SPECTRUM, // (nor this: PSD and FFT)
+    DSP_ROUTE_SORT,     // (nor this: SORT)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -22,6 +24,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_hist_kernel",
     "dsp_thresh_kernel",
     "dsp_spectrum_kernel",
+    "dsp_sort_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -48,6 +51,65 @@ constexpr int WAVE_ROW_BYTES = 8 * 1024;
 constexpr bool wide(int n, int esz) { return row_bytes(n, esz) > WAVE_ROW_BYTES; }
 constexpr int lds_bytes(int n, int esz) { return wide(n, esz) ? row_bytes(n, esz) + 16 : 4 * row_bytes(n, esz); }
 }  // namespace dsp_spectrum
+
+namespace dsp_sort {  // dsp_sort.hip: a row as order-preserving unsigned keys in LDS, sorted by a bitonic network over the padded length P
+// ---- keys.  The bits of a sample map to an unsigned key whose integer order is the samples' order: all bits of a negative value flipped,
+// the sign bit of any other set.  -0.0 lands just below +0.0, -inf .. +inf fill [KEY_NEG_INF, KEY_POS_INF], and every NaN lies outside
+// that range on one side or the other: one unsigned comparison finds it.
+constexpr uint32_t key_of(uint32_t bits) { return bits & 0x80000000u ? ~bits : bits | 0x80000000u; }
+constexpr uint64_t key_of(uint64_t bits) { return bits & 0x8000000000000000ull ? ~bits : bits | 0x8000000000000000ull; }
+constexpr uint32_t bits_of(uint32_t key) { return key & 0x80000000u ? key & 0x7fffffffu : ~key; }
+constexpr uint64_t bits_of(uint64_t key) { return key & 0x8000000000000000ull ? key & 0x7fffffffffffffffull : ~key; }
+constexpr uint32_t KEY_NEG_INF32 = 0x007fffffu, KEY_POS_INF32 = 0xff800000u;
+constexpr uint64_t KEY_NEG_INF64 = 0x000fffffffffffffull, KEY_POS_INF64 = 0xfff0000000000000ull;
+constexpr bool key_is_nan(uint32_t key) { return (uint32_t)(key - KEY_NEG_INF32) > KEY_POS_INF32 - KEY_NEG_INF32; }
+constexpr bool key_is_nan(uint64_t key) { return (uint64_t)(key - KEY_NEG_INF64) > KEY_POS_INF64 - KEY_NEG_INF64; }
+
+// ---- geometry.  A lane holds CHUNK neighbouring keys in registers, a wavefront a TILE of 64 chunks.  A row of n samples is padded with
+// +inf keys to P = padded(n): the power of two >= n, and at least a chunk.  Rows of P <= NARROW_MAX get a wavefront each, four rows to a
+// workgroup; longer rows a workgroup of 256, with 16 bytes behind the keys for the word its wavefronts agree on "a NaN" through.
+constexpr int CHUNK = 8, TILE = 64 * CHUNK;
+constexpr int NARROW_MAX = 2048;
+constexpr int padded(int n) {
+    int p = CHUNK;
+    while (p < n) p *= 2;
+    return p;
+}
+constexpr bool wide(int n) { return padded(n) > NARROW_MAX; }
+constexpr int lds_bytes(int n, int esz) { return wide(n) ? padded(n) * esz + 16 : 4 * padded(n) * esz; }
+
+// ---- schedule.  Stage k = 2, 4 .. P merges bitonic runs of k keys with the steps j = k / 2, k / 4 .. 1; step (k, j) compares key i with
+// key i ^ j and leaves the smaller at the lower index where bit k of i is clear (the run ascends), the larger where it is set.  The last
+// stage's k is P, which no index has: everything ascends.  A step's stride says where its two keys meet: inside a lane's chunk, in two
+// lanes of a wavefront's tile, or only in LDS.
+struct Step {
+    int k, j;
+};
+constexpr int log2_of(int p) {
+    int l = 0;
+    while ((1 << l) < p) ++l;
+    return l;
+}
+constexpr int steps(int P) { return log2_of(P) * (log2_of(P) + 1) / 2; }
+constexpr Step step(int P, int s) {  // the s-th of steps(P), in the order they run
+    (void)P;
+    int stage = 1;
+    while (s >= stage) s -= stage, ++stage;
+    return {1 << stage, 1 << (stage - 1 - s)};
+}
+constexpr int partner(int i, int j) { return i ^ j; }
+constexpr bool ascends(int i, int k) { return (i & k) == 0; }
+constexpr bool keeps_min(int i, int k, int j) { return ((i & j) == 0) == ascends(i, k); }
+enum Kind { REGISTER, CROSS_LANE, LDS };
+constexpr Kind kind(int j) { return j < CHUNK ? REGISTER : j < TILE ? CROSS_LANE : LDS; }
+// LDS passes over a row behind the staging: one that runs stages 2 .. min(P, TILE) on a tile in registers, then per longer stage one per
+// LDS step and one for the steps below TILE
+constexpr int lds_passes(int P) {
+    int passes = 1;
+    for (int k = 2 * TILE; k <= P; k *= 2) passes += log2_of(k / TILE) + 1;
+    return passes;
+}
+}  // namespace dsp_sort
 
 namespace dsp_current {  // dsp_current.hip
 constexpr int CB = 16;   // samples per block (= per checkpoint)

@@ -109,6 +109,7 @@ static bool match_extrema_shape(const PlanCtx& c, const char** why);
 static bool match_hist_shape(const PlanCtx& c, const char** why);
 static bool match_thresh_shape(const PlanCtx& c, const char** why);
 static bool match_spectrum_shape(const PlanCtx& c, const char** why);
+static bool match_sort_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -117,6 +118,7 @@ static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_THRESH, {DSP_OP_MULTI_TIME_POINT_THRESH, DSP_OP_TIME_OVER_THRESHOLD}, match_thresh_shape,
      "DSP_OP_MULTI_TIME_POINT_THRESH / DSP_OP_TIME_OVER_THRESHOLD (multi_time_point_thresh, time_over_threshold) run on dsp_thresh_kernel only"},
     {DSP_ROUTE_SPECTRUM, {DSP_OP_PSD, DSP_OP_FFT}, match_spectrum_shape, "DSP_OP_PSD / DSP_OP_FFT (psd, fft) run on dsp_spectrum_kernel only"},
+    {DSP_ROUTE_SORT, {DSP_OP_SORT, DSP_OP_SORT}, match_sort_shape, "DSP_OP_SORT (sort) runs on dsp_sort_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -611,6 +613,31 @@ static bool match_spectrum_shape(const PlanCtx& c, const char** why) {
     A.wide = dsp_spectrum::wide(A.len, c.esz) ? 1 : 0;
     ch->sio_out = st.io;
     A.out_stride = c.io[st.io].row_stride;
+    return true;
+}
+
+// Is the program the sorting kernel's (dsp_sort.hip)?
+//   LOAD s;  SORT of s;  STORE of its n samples
+// Lengths and limits are lower_op's business (every program that holds the op passes there first).  Why not, otherwise: `why`.
+static bool match_sort_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    *why = "the program must be exactly LOAD, SORT, STORE";
+    if (c.n_ops != 3 || c.n_slots != 2 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_SORT || ops[2].opcode != DSP_OP_STORE) return false;
+    const dsp_op &ld = ops[0], &op = ops[1], &st = ops[2];
+    SortArgs& A = ch->sort;
+    memset(&A, 0, sizeof A);
+    ch->oio_out = -1;
+    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->sort_src, why,
+                                       "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
+    *why = "the sorted row is stored once, whole, in the loop's type";
+    const dsp_io_desc& o = c.io[st.io];
+    if (st.src != op.dst || o.dtype != c.compute_dtype || o.len != A.len) return false;
+    A.padded = dsp_sort::padded(A.len);
+    A.wide = dsp_sort::wide(A.len) ? 1 : 0;
+    ch->oio_out = st.io;
+    A.out_stride = o.row_stride;
     return true;
 }
 
@@ -1142,6 +1169,7 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_UPSAMPLER:
         case DSP_OP_PSD:
         case DSP_OP_FFT:
+        case DSP_OP_SORT:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
         case DSP_OP_DWT_HAAR: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[2]; return 3;
         case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
@@ -1326,7 +1354,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT: their own layout and limits)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT: their own layout and limits)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1722,6 +1750,16 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
             if (dsp_spectrum::pow2(n) ? n > pow2_max : n > any_max)
                 return fail(DSP_ERR_UNSUPPORTED, "%s: the %s loop takes rows of a power of two up to %d samples and of any other length up to %d (%d given): a row's transform lives in 64 KiB of LDS",
                             name, f64 ? "float64" : "float32", pow2_max, any_max, n);
+            break;
+        }
+        case DSP_OP_SORT: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad SORT (src: the slot of the row; dst: another slot, for the sorted row)", i);
+            const int n = slot_len[o.src], n_max = DSP_SORT_F32_MAX / (f64 ? 2 : 1);
+            if (slot_len[o.dst] != n) return fail(DSP_ERR_ARG, "op %d: SORT: the sorted row has the row's length (%d; %d given)", i, n, slot_len[o.dst]);
+            if (n > n_max)
+                return fail(DSP_ERR_UNSUPPORTED, "sort: rows of up to %d samples in the float32 loop and %d in the float64 loop (%d given): a row's keys live in 64 KiB of LDS",
+                            DSP_SORT_F32_MAX, DSP_SORT_F32_MAX / 2, n);
             break;
         }
         case DSP_OP_DWT_HAAR: {

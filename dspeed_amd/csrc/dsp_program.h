@@ -354,6 +354,20 @@ struct SpectrumArgs {
     int64_t out_stride;
 };
 
+// arguments of the sorting kernel (dsp_sort.hip), filled by the planner when a program has the shape
+//   LOAD -> SORT -> STORE
+// One row is `padded` order-preserving unsigned keys in LDS (dsp_kernels.h, dsp_sort), the keys past `len` +inf's.
+#define DSP_SORT_F32_MAX 16384 /* samples of a row, float32 loop (the float64 loop: half): 64 KiB of LDS a row */
+struct SortArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples
+    int32_t padded;          // dsp_sort::padded(len): the power of two the network runs over
+    int32_t wide;            // 1: a workgroup of 256 per row, 0: a wavefront per row, four rows to a workgroup
+    void* out;               // rows of len samples of the loop's type
+    int64_t out_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

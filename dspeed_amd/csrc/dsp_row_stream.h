@@ -1,6 +1,6 @@
 // dsp_row_stream.h -- how a wavefront streams a row from memory through its registers: shared by the kernels that give a row to a wavefront,
-// four rows to a workgroup (dsp_reduce.hip, dsp_thresh.hip, dsp_hist.hip, dsp_extrema.hip; dsp_spectrum.hip stages rows into LDS through the same
-// loader, a wavefront or the four wavefronts of a workgroup per row).  Internal header.
+// four rows to a workgroup (dsp_reduce.hip, dsp_thresh.hip, dsp_hist.hip, dsp_extrema.hip; dsp_spectrum.hip and dsp_sort.hip stage rows into LDS
+// through the same loader, a wavefront or the four wavefronts of a workgroup per row).  Internal header.
 //
 // A row of n samples is read in groups of 64 N: lane l holds samples [g 64 N + l N, + N) of group g.  N is the number of samples in 16
 // bytes (RowVec) where row starts, stride and length are whole 16-byte vectors -- the planner's rule and the pointer's alignment: `vec` of

@@ -426,5 +426,36 @@ fft = HipGUFunc("fft", "(n),(m)", ["fF", "dD"], _spectrum(True),
 # (tests/test_spectrum_plan_cpu.py).
 SPECTRAL = ("fft", "psd")
 
+
+# --------------------------------------------------------------------------------------------------- order statistics
+def sort_limit(loop_dtype):
+    """longest row of sort in a loop: the row's keys live in 64 KiB of LDS"""
+    return _lib.SORT_F32_MAX // (2 if np.dtype(loop_dtype) == np.dtype(np.float64) else 1)
+
+
+def check_sort_length(what, n, loop_dtype):
+    """(both limits are named whichever loop runs: the planner's text)"""
+    if n > sort_limit(loop_dtype):
+        raise NotImplementedError(f"{what}: rows of up to {_lib.SORT_F32_MAX} samples in the float32 loop and {_lib.SORT_F32_MAX // 2} in the float64 loop "
+                                  f"({n} given): a row's keys live in 64 KiB of LDS")
+
+
+def _sort(g, *args):
+    """one C entry for both loops, like psd's (``dsp_sort_rows`` takes the loop's type); the output may be left out"""
+    (w_in,), (out,) = _split(g, args)
+    with device_call(g.__name__, w_in, f64_rows_only=True) as c:
+        check_sort_length(g.__name__, c.n, c.ft)
+        ptr, stride = c.out(out, "n")
+        run(getattr(_lib.lib(), "dsp_sort_rows"), g.__name__, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, ptr, stride)
+        c.st.finish()
+        return c.results[0]
+
+
+sort = HipGUFunc("sort", "(n)->(n)", ["f->f", "d->d"], _sort,
+                 "rows in ascending order, -inf first and +inf last, -0.0 before +0.0; a row with a NaN: NaNs (reference processors/sort.py:10-42)")
+
+# Listed here and not in __all__, like the spectral processors: its call record is tests/test_sort_plan_cpu.py's.
+ORDER = ("sort",)
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

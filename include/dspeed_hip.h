@@ -270,6 +270,11 @@ typedef struct dsp_scalar_arg {
                                  * The waveform interpreter has neither op: they run on dsp_spectrum_kernel only, in a program of exactly
                                  *   LOAD, PSD, STORE of dst
                                  *   LOAD, FFT, STORE of dst */
+#define DSP_OP_SORT 41          /* sort.py:36-42 sort: dst (n samples, another slot than src) <- src in ascending order, -inf first and +inf last (infinities
+                                 * are ordinary values here); -0.0 before +0.0 (the total order of the bit patterns).  A row with a NaN: every sample NaN.
+                                 * Float32 / int16 / uint16 rows of up to 16384 samples in the float32 loop, float64 rows of up to 8192 in the float64 loop.
+                                 * The waveform interpreter has no such op: it runs on dsp_sort_kernel only, in a program of exactly
+                                 *   LOAD, SORT, STORE of dst */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -523,6 +528,12 @@ int dsp_psd(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t 
             int64_t out_stride, void* stream, int64_t* err_row);
 int dsp_fft(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, void* dft_out, int32_t n_bins,
             int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n)->(n)" sort (sort.py:36-42): every row in ascending order, a row with a NaN as NaNs (DSP_OP_SORT).  One entry for both loops, like
+ * dsp_psd: compute_dtype names the loop (DSP_F32: float32 / int16 / uint16 rows of up to 16384 samples, float output; DSP_F64: float64 rows of
+ * up to 8192 samples, double output).  sorted_out: rows of wf_len values of the loop's type, out_stride of them apart. */
+int dsp_sort_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, void* sorted_out,
+                  int64_t out_stride, void* stream, int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
