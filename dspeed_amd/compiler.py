@@ -34,8 +34,8 @@ from .language import (Char, Grid, Quantity, SExpr, Var, View, _Builder, _GENERA
 _MULTI_EXTREMA = "get_multi_local_extrema"
 _HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
 _MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
-_PSD, _SORT = "psd", "sort"
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT)  # processors that run as stages ahead of the program, on kernels of their own
+_PSD, _SORT, _INTERP = "psd", "sort", "interpolating_upsampler"
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP)  # processors that run as stages ahead of the program, on kernels of their own
 _SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
@@ -894,6 +894,28 @@ def _stage_sort(cx: _Stager):
         cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
 
 
+def _stage_interp_upsampler(cx: _Stager):
+    """``interpolating_upsampler`` runs on dsp_interp.hip and nowhere else, on rows in HBM: a mandatory stage, like sort's.  The source is
+    a chain input, a stage's waveform, a slice of either, or a waveform the program computes, written to HBM first; the resampled row is an
+    ordinary waveform variable of the program, declared with its length (and ``period=``: the finer grid).  The mode is a constant of the
+    kernel, checked here for every row."""
+    from .processors import check_interp
+
+    fn = _INTERP
+    for st in cx.steps_of(fn):
+        args, key = list(st[1]), st[2]
+        src, mode, out = args
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        if not isinstance(mode, (Char, int, np.integer)):
+            raise NotImplementedError(f"{fn} ({key}): the interpolation mode is a constant of the kernel, not a per-event value")
+        if not (isinstance(out, Var) and out.kind == "wf" and out.length):
+            raise ProcessingChainError(f"{fn} ({key}): declare the output with its length, as in wf_up(len(wf)*10, period=wf.period/10)")
+        check_interp(f"{fn} ({key})", _Emitter.char_of(mode), src.length, out.length, np.float32)
+        _rows_in_memory(cx, src, fn, key)
+        cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+
+
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     """Long FIRs leave the program: each ``convolve_wf`` with a constant kernel of STAGE_MIN_TAPS or more taps becomes a launch of the
     matrix-core FIR kernels ahead of the program (one waveform per wavefront is the wrong shape for 133 x 8192 or 5792 x 301
@@ -920,6 +942,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_thresholds(cx)
     _stage_spectrum(cx)
     _stage_sort(cx)
+    _stage_interp_upsampler(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and v.ext_key is not None and v.aux_io is None}
     cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
@@ -1548,6 +1571,14 @@ class _Emitter:
         self.p.add_op(_lib.OP_SORT, dst=out.slot, src=src.slot)
         self.release(src, si)
 
+    def interpolating_upsampler(self, si, fn, args, what):
+        """the whole program of the stage: LOAD, INTERP_UPSAMPLE; the store of the resampled row follows"""
+        src = self.ensure_loaded(args[0], si)
+        out = self.out_wf(args[2], None, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_INTERP_UPSAMPLE, dst=out.slot, src=src.slot, ip=(self.char_of(args[1]),))
+        self.release(src, si)
+
     def copy_slice(self, si, fn, args, what):
         src = self.ensure_loaded(args[0], si)
         dst = args[3]
@@ -1727,7 +1758,7 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
          "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
          _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
-         _PSD: _Emitter.psd, _SORT: _Emitter.sort}
+         _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler}
 
 
 def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):

@@ -425,6 +425,13 @@ int dsp_sort_rows(ROWS, int compute_dtype, void* sorted_out, int64_t out_stride,
     if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "sort: compute_dtype is DSP_F32 or DSP_F64");
     return wf2wf(compute_dtype, DSP_OP_SORT, IN, {}, {}, {sorted_out, wf_len, out_stride}, TAIL_ARGS);
 }
+// interpolating_upsampler: one entry for both loops too; the ratio is out_len / wf_len, the mode a constant of the call
+int dsp_interp_upsample_rows(ROWS, int compute_dtype, int32_t mode, void* out, int32_t out_len, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64)
+        return dsp_fail(DSP_ERR_ARG, "interpolating_upsampler: compute_dtype is DSP_F32 or DSP_F64");
+    if (out_len < 1) return dsp_fail(DSP_ERR_ARG, "interpolating_upsampler: the output holds at least one sample (%d given)", out_len);
+    return wf2wf(compute_dtype, DSP_OP_INTERP_UPSAMPLE, IN, {mode}, {}, {out, out_len, out_stride}, TAIL_ARGS);
+}
 #undef ROWS
 #undef IN
 #undef TAIL

@@ -419,6 +419,9 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     if (!rc)
         rc = raise_lds(ch->kernel_only == DSP_ROUTE_SORT, dsp_sort::lds_bytes(ch->sort.len, esz), 64 * 1024, "sort kernel, %d",
                        [&](int n) { return dsp_internal_set_sort_lds(ch->sort_src.dtype, n); });
+    if (!rc)
+        rc = raise_lds(ch->kernel_only == DSP_ROUTE_INTERP, dsp_interp::lds_bytes(ch->interp.mode, ch->interp.len, esz), 64 * 1024, "interp kernel, %d",
+                       [&](int n) { return dsp_internal_set_interp_lds(ch->interp_src.dtype, n); });
     if (rc) return rc;
     *out = ch.release();
     return DSP_OK;
@@ -646,6 +649,15 @@ static int launch_sort(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* 
     return launch_on_rows(ch, n_wf, stream, A, ch->sort_src, dsp_internal_launch_sort, "sort kernel launch");
 }
 
+static int launch_interp(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    InterpArgs A = ch->interp;
+    A.wf = io_ptrs[ch->interp_src.io];
+    A.out = io_at(ch, io_ptrs, ch->iuo_out);
+    // 16-byte stores: launch_on_rows' rule for the loads, on the output side (the plan vouches for the stride, this call's pointer for the start)
+    A.out_vec = (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
+    return launch_on_rows(ch, n_wf, stream, A, ch->interp_src, dsp_internal_launch_interp, "interp kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -831,6 +843,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_THRESH)) return launch_thresh(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_SPECTRUM)) return launch_spectrum(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_SORT)) return launch_sort(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_INTERP)) return launch_interp(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -933,6 +946,12 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             const int n = ch->sort.len, es = ch->f64 ? 8 : 4;
             const bool wide = dsp_sort::wide(n);
             lds = dsp_sort::padded(n) * es / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
+            break;
+        }
+        case DSP_ROUTE_INTERP: {
+            const int n = ch->interp.len, mode = ch->interp.mode, es = ch->f64 ? 8 : 4;
+            const bool wide = dsp_interp::wide(mode, n, es);
+            lds = dsp_interp::row_bytes(mode, n, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
             break;
         }
         case DSP_ROUTE_EXTREMA:

@@ -15,6 +15,7 @@ enum dsp_route {
     DSP_ROUTE_THRESH,   // (nor this: MULTI_TIME_POINT_THRESH and TIME_OVER_THRESHOLD)
     DSP_ROUTE_SPECTRUM, // (nor this: PSD and FFT)
     DSP_ROUTE_SORT,     // (nor this: SORT)
+    DSP_ROUTE_INTERP,   // (nor this: INTERP_UPSAMPLE)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -25,6 +26,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_thresh_kernel",
     "dsp_spectrum_kernel",
     "dsp_sort_kernel",
+    "dsp_interp_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -110,6 +112,78 @@ constexpr int lds_passes(int P) {
     return passes;
 }
 }  // namespace dsp_sort
+
+namespace dsp_interp {  // dsp_interp.hip: interpolating_upsampler (upsampler.py:52-216), a row of n samples in LDS resampled to m outputs
+// ---- index rules.  The reference walks the INPUT samples and fills intervals of outputs whose bounds are float64 expressions of
+// u = m / n: one division, then one multiply with one rounding per bound -- not the rational ceil(m i / n), from which they differ (at
+// i = 7 for (n, m) = (14, 58)).  The kernel walks the OUTPUTS, so the rules are inverted here: a candidate floor(o / u), corrected by
+// evaluating the reference's own bound expression.  bound(mode, u, i) is the first output that input sample i does NOT fill:
+//   'n' ceil(u (i + 0.5))     'f' 'l' 'h' ceil(u (i + 1))     'c' floor(u i) + 1     's' ceil(u (i + 1)) + 1
+// ('s' writes each segment from its upper bound down to ceil(u i) inclusive, lower segments later: an output that is a segment bound
+// keeps the value of the lower segment, evaluated at t0 >= 1.)
+constexpr int64_t ceil_of(double x) {  // x >= 0, below 2^62
+    const int64_t k = (int64_t)x;
+    return k + ((double)k < x ? 1 : 0);
+}
+constexpr double ratio(int n, int64_t m) { return (double)m / (double)n; }
+constexpr int64_t bound(int mode, double u, int i) {
+    return mode == 'n' ? ceil_of(u * ((double)i + 0.5)) : mode == 'c' ? (int64_t)(u * (double)i) + 1 : ceil_of(u * (double)(i + 1)) + (mode == 's' ? 1 : 0);
+}
+enum Kind { VALUE, ZERO, TAIL, NONE };  // a segment's value / one of 'i's zeros / 'n' and 'c': w_in[n - 1] behind the last bound / left NaN
+struct Map {
+    int seg;  // the input sample (n f c i), the lower sample of the segment (l h s); TAIL: n - 1
+    Kind kind;
+};
+// the smallest i in [from, n) with o < bound(i), n if there is none; `from` is at most that i (bounds do not decrease with i)
+constexpr int advance(int mode, int n, double u, int64_t o, int from) {
+    int i = from;
+    while (i < n && !(o < bound(mode, u, i))) ++i;
+    return i;
+}
+constexpr int locate(int mode, int n, double u, int64_t o) {
+    const double q = (double)o / u;
+    int i = q < (double)(n - 1) ? (int)q : n - 1;
+    while (i > 0 && o < bound(mode, u, i - 1)) --i;
+    return advance(mode, n, u, o, i);
+}
+// what output o is made of, given i = locate(...) or advance(...) of it
+constexpr Map map_of(int mode, int n, int64_t m, int64_t o, int i) {
+    if (mode == 'i') {
+        const int64_t r = m / n;
+        return {(int)(o / r), o % r ? ZERO : VALUE};
+    }
+    if (mode == 'h' || mode == 's') return {i < n - 2 ? i : n - 2, n < 2 ? NONE : VALUE};  // ('h': the last segment extrapolates; 's' at n == 1: NaNs)
+    if (i < n) return {i, VALUE};
+    return {n - 1, mode == 'n' || mode == 'c' ? TAIL : NONE};
+}
+constexpr Map map(int mode, int n, int64_t m, int64_t o) { return map_of(mode, n, m, o, mode == 'i' ? 0 : locate(mode, n, ratio(n, m), o)); }
+constexpr bool mode_ok(int mode) { return mode == 'i' || mode == 'n' || mode == 'f' || mode == 'c' || mode == 'l' || mode == 'h' || mode == 's'; }
+
+// ---- the spline's sweeps.  The forward coefficient w2[i] = -0.5 / (0.5 w2[i - 1] + 2) is data independent and stationary in float64 from
+// i = STATIONARY on; both recurrences contract by 0.268 a step, so WARM samples of warm-up put a perturbation of 3e-28 ahead of the same
+// operations (pickoff_spline's argument, dsp_vm.hip).
+constexpr int WARM = 48, STATIONARY = 15;
+constexpr double W2_FIX = -0.2679491924311227;
+constexpr double forward_coef(int i) {  // w2[i] of the forward sweep, 1 <= i <= n - 2 (0 outside)
+    if (i >= STATIONARY) return W2_FIX;
+    double w = 0.0;
+    for (int k = 1; k <= i; ++k) w = -0.5 / (0.5 * w + 2.0);
+    return w;
+}
+
+// ---- geometry.  The row lives in LDS in the loop's type, the spline's second derivatives as float64 behind it.  Rows of up to
+// WAVE_ROW_BYTES get a wavefront each, four to a workgroup (no barrier); longer ones a workgroup of 256, with 16 bytes behind the row for
+// the word its wavefronts agree on "a NaN" / "an infinity" through.
+constexpr int WAVE_ROW_BYTES = 8 * 1024, LDS_MAX = 64 * 1024;
+constexpr int w2_offset(int n, int esz) { return (n * esz + 15) / 16 * 16; }  // bytes from the row to the second derivatives
+constexpr int row_bytes(int mode, int n, int esz) { return w2_offset(n, esz) + (mode == 's' ? (n * 8 + 15) / 16 * 16 : 0); }
+constexpr bool wide(int mode, int n, int esz) { return row_bytes(mode, n, esz) > WAVE_ROW_BYTES; }
+constexpr int lds_bytes(int mode, int n, int esz) { return wide(mode, n, esz) ? row_bytes(mode, n, esz) + 16 : 4 * row_bytes(mode, n, esz); }
+constexpr int SPLINE_F32_MAX = 5456, SPLINE_F64_MAX = 4096;  // (with LDS_MAX / esz for the other modes: DSP_INTERP_*_MAX of dsp_program.h)
+constexpr int max_len(int mode, int esz) { return mode == 's' ? (esz == 8 ? SPLINE_F64_MAX : SPLINE_F32_MAX) : LDS_MAX / esz; }
+static_assert(row_bytes('s', SPLINE_F32_MAX, 4) <= LDS_MAX && row_bytes('s', SPLINE_F32_MAX + 16, 4) > LDS_MAX, "the longest float32 spline row fills the LDS");
+static_assert(row_bytes('s', SPLINE_F64_MAX, 8) == LDS_MAX && row_bytes('l', max_len('l', 4), 4) == LDS_MAX, "and the others");
+}  // namespace dsp_interp
 
 namespace dsp_current {  // dsp_current.hip
 constexpr int CB = 16;   // samples per block (= per checkpoint)

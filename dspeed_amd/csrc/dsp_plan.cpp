@@ -110,6 +110,7 @@ static bool match_hist_shape(const PlanCtx& c, const char** why);
 static bool match_thresh_shape(const PlanCtx& c, const char** why);
 static bool match_spectrum_shape(const PlanCtx& c, const char** why);
 static bool match_sort_shape(const PlanCtx& c, const char** why);
+static bool match_interp_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -119,6 +120,8 @@ static const KernelOnlyRoute kernel_only_routes[] = {
      "DSP_OP_MULTI_TIME_POINT_THRESH / DSP_OP_TIME_OVER_THRESHOLD (multi_time_point_thresh, time_over_threshold) run on dsp_thresh_kernel only"},
     {DSP_ROUTE_SPECTRUM, {DSP_OP_PSD, DSP_OP_FFT}, match_spectrum_shape, "DSP_OP_PSD / DSP_OP_FFT (psd, fft) run on dsp_spectrum_kernel only"},
     {DSP_ROUTE_SORT, {DSP_OP_SORT, DSP_OP_SORT}, match_sort_shape, "DSP_OP_SORT (sort) runs on dsp_sort_kernel only"},
+    {DSP_ROUTE_INTERP, {DSP_OP_INTERP_UPSAMPLE, DSP_OP_INTERP_UPSAMPLE}, match_interp_shape,
+     "DSP_OP_INTERP_UPSAMPLE (interpolating_upsampler) runs on dsp_interp_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -637,6 +640,33 @@ static bool match_sort_shape(const PlanCtx& c, const char** why) {
     A.padded = dsp_sort::padded(A.len);
     A.wide = dsp_sort::wide(A.len) ? 1 : 0;
     ch->oio_out = st.io;
+    A.out_stride = o.row_stride;
+    return true;
+}
+
+// Is the program the resampling kernel's (dsp_interp.hip)?
+//   LOAD s;  INTERP_UPSAMPLE of s into a slot of m samples;  STORE of its m samples
+// Mode, lengths and limits are lower_op's business (every program that holds the op passes there first).  Why not, otherwise: `why`.
+static bool match_interp_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    *why = "the program must be exactly LOAD, INTERP_UPSAMPLE, STORE";
+    if (c.n_ops != 3 || c.n_slots != 2 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_INTERP_UPSAMPLE || ops[2].opcode != DSP_OP_STORE)
+        return false;
+    const dsp_op &ld = ops[0], &op = ops[1], &st = ops[2];
+    InterpArgs& A = ch->interp;
+    memset(&A, 0, sizeof A);
+    ch->iuo_out = -1;
+    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->interp_src, why,
+                                       "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
+    *why = "the resampled row is stored once, whole, in the loop's type";
+    const dsp_io_desc& o = c.io[st.io];
+    if (st.src != op.dst || o.dtype != c.compute_dtype || o.len != c.slot_len[op.dst]) return false;
+    A.out_len = o.len;
+    A.mode = op.ip[0];
+    A.wide = dsp_interp::wide(A.mode, A.len, c.esz) ? 1 : 0;
+    ch->iuo_out = st.io;
     A.out_stride = o.row_stride;
     return true;
 }
@@ -1170,6 +1200,7 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_PSD:
         case DSP_OP_FFT:
         case DSP_OP_SORT:
+        case DSP_OP_INTERP_UPSAMPLE:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
         case DSP_OP_DWT_HAAR: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[2]; return 3;
         case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
@@ -1354,7 +1385,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT: their own layout and limits)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE: their own layout and limits)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1760,6 +1791,28 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
             if (n > n_max)
                 return fail(DSP_ERR_UNSUPPORTED, "sort: rows of up to %d samples in the float32 loop and %d in the float64 loop (%d given): a row's keys live in 64 KiB of LDS",
                             DSP_SORT_F32_MAX, DSP_SORT_F32_MAX / 2, n);
+            break;
+        }
+        case DSP_OP_INTERP_UPSAMPLE: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad INTERP_UPSAMPLE (src: the slot of the row; dst: another slot, for the resampled row; ip[0]: the mode)", i);
+            const int n = slot_len[o.src], m = slot_len[o.dst], mode = o.ip[0], es = f64 ? 8 : 4;
+            static_assert(dsp_interp::max_len('l', 4) == DSP_INTERP_F32_MAX && dsp_interp::max_len('l', 8) == DSP_INTERP_F32_MAX / 2 &&
+                              dsp_interp::max_len('s', 4) == DSP_INTERP_SPLINE_F32_MAX && dsp_interp::max_len('s', 8) == DSP_INTERP_SPLINE_F64_MAX,
+                          "the limits the texts name are the geometry's");
+            if (n < 1 || m < 1) return fail(DSP_ERR_ARG, "op %d: INTERP_UPSAMPLE: the row and the resampled row hold at least one sample (%d and %d given)", i, n, m);
+            if (!dsp_interp::mode_ok(mode)) return fail(DSP_ERR_ARG, "interpolating_upsampler: Unrecognized interpolation mode (%d)", mode);
+            if (mode == 'i' && m % n != 0)
+                return fail(DSP_ERR_ARG, "interpolating_upsampler requires len(w_out) to be an integer multiple of len(w_in) for mode 'i' (%d and %d given)", m, n);
+            if (mode == 'h' && n < 2)
+                return fail(DSP_ERR_UNSUPPORTED, "interpolating_upsampler: mode 'h' takes rows of at least 2 samples (%d given): the reference reads an unbound variable there", n);
+            if (n > dsp_interp::max_len(mode, es)) {
+                if (mode == 's')
+                    return fail(DSP_ERR_UNSUPPORTED, "interpolating_upsampler: mode 's' takes rows of up to %d samples in the float32 loop and %d in the float64 loop (%d given): "
+                                "the row and its second derivatives live in 64 KiB of LDS", DSP_INTERP_SPLINE_F32_MAX, DSP_INTERP_SPLINE_F64_MAX, n);
+                return fail(DSP_ERR_UNSUPPORTED, "interpolating_upsampler: rows of up to %d samples in the float32 loop and %d in the float64 loop (%d given): a row lives in 64 KiB of LDS",
+                            DSP_INTERP_F32_MAX, DSP_INTERP_F32_MAX / 2, n);
+            }
             break;
         }
         case DSP_OP_DWT_HAAR: {

@@ -91,7 +91,7 @@ struct ChainPlan {
     int dio_walk[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1}, dio_walk_thr[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1},
         dio_walk_ts[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1};
     // The ops no interpreter case stands behind: a program that holds one runs on that op's kernel or is refused (the table of these routes
-    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM or DSP_ROUTE_SORT; DSP_ROUTE_VM: the program holds none.
+    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM, DSP_ROUTE_SORT or DSP_ROUTE_INTERP; DSP_ROUTE_VM: the program holds none.
     dsp_route kernel_only = DSP_ROUTE_VM;
     // the peak finder (dsp_extrema.hip): the one kernel a program with MULTI_EXTREMA runs on
     ExtremaArgs ext{};
@@ -113,6 +113,10 @@ struct ChainPlan {
     SortArgs sort{};
     RowSource sort_src{};
     int oio_out = -1;
+    // interpolating_upsampler (dsp_interp.hip): the one kernel a program with the op runs on
+    InterpArgs interp{};
+    RowSource interp_src{};
+    int iuo_out = -1;
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};

@@ -368,6 +368,24 @@ struct SortArgs {
     int64_t out_stride;
 };
 
+// arguments of the resampling kernel (dsp_interp.hip), filled by the planner when a program has the shape
+//   LOAD -> INTERP_UPSAMPLE -> STORE
+// The row lives in LDS in the loop's type; mode 's' keeps its second derivatives as float64 behind it (dsp_kernels.h, dsp_interp).
+#define DSP_INTERP_F32_MAX 16384       /* samples of a row, float32 loop (the float64 loop: half): 64 KiB of LDS a row */
+#define DSP_INTERP_SPLINE_F32_MAX 5456 /* mode 's', float32 loop: 12 bytes a sample */
+#define DSP_INTERP_SPLINE_F64_MAX 4096 /* mode 's', float64 loop: 16 bytes a sample */
+struct InterpArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples (n)
+    int32_t out_len;         // m: the resampling ratio is m / n, a float64
+    int32_t mode;            // 'i' 'n' 'f' 'c' 'l' 'h' 's'
+    int32_t wide;            // 1: a workgroup of 256 per row, 0: a wavefront per row, four rows to a workgroup
+    int32_t out_vec;         // 1: 16-byte stores (the output rows' start and stride are whole vectors: set per call)
+    void* out;               // rows of out_len samples of the loop's type
+    int64_t out_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

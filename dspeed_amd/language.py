@@ -240,6 +240,7 @@ _SIGS = {
     "multi_time_point_thresh": "wtsscW", "time_over_threshold": "wsS",  # (w_in, a_threshold[m], t_start, polarity, mode_in, t_out[m]); (w_in, a_threshold, n_samples)
     "psd": "wW",  # (w_in, psd_out[len(w_in) // 2 + 1])
     "sort": "wW",  # (w_in, w_out)
+    "interpolating_upsampler": "wcW",  # (w_in, mode_in, w_out[m]: any length)
     "get_multi_local_extrema": "wssissWWSS",  # (w_in, a_delta_max_in, a_delta_min_in, search_direction, a_abs_max_in, a_abs_min_in, two lists, two counts)
 }
 _SIGS.update({"sample": "wiS", "slice": "wiiW", "get": "wsS"})  # wf[i], wf[lo:hi:step], wf[variable] (reference :948-1071)
@@ -346,12 +347,13 @@ _PROCESSOR_FILES = {
 # __all__ (tests/test_histogram_plan_cpu.py), where these two are not
 _SPECTRAL_FILES = {"psd": ("fft",), "fft": ("fft",)}
 _ORDER_FILES = {"sort": ("sort",)}  # (processors.ORDER, likewise)
+_RESAMPLING_FILES = {"interpolating_upsampler": ("upsampler",)}  # (processors.RESAMPLING, likewise)
 
 
 def module_accepted(module, function) -> bool:
     """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
     pre = "dspeed.processors."
-    files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ()) + _ORDER_FILES.get(function, ())
+    files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ()) + _ORDER_FILES.get(function, ()) + _RESAMPLING_FILES.get(function, ())
     return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in files)
 
 

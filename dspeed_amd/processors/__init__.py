@@ -457,5 +457,66 @@ sort = HipGUFunc("sort", "(n)->(n)", ["f->f", "d->d"], _sort,
 # Listed here and not in __all__, like the spectral processors: its call record is tests/test_sort_plan_cpu.py's.
 ORDER = ("sort",)
 
+
+# --------------------------------------------------------------------------------------------------- resampling
+INTERP_MODES = "infclhs"
+
+
+def interp_limit(mode, loop_dtype):
+    """longest row of interpolating_upsampler in a mode and loop: the row (and the spline's second derivatives) live in 64 KiB of LDS"""
+    f64 = np.dtype(loop_dtype) == np.dtype(np.float64)
+    if mode == "s":
+        return _lib.INTERP_SPLINE_F64_MAX if f64 else _lib.INTERP_SPLINE_F32_MAX
+    return _lib.INTERP_F32_MAX // (2 if f64 else 1)
+
+
+def check_interp(what, mode, n, m, loop_dtype):
+    """what the planner checks, in its words (and the reference's, where it has them): ``mode`` is the character's code"""
+    if not 0 < mode < 128 or chr(mode) not in INTERP_MODES:
+        raise DSPFatal("Unrecognized interpolation mode")
+    mode = chr(mode)
+    if m < 1:
+        raise ValueError(f"{what}: the output holds at least one sample ({m} given)")
+    if mode == "i" and m % n:
+        raise DSPFatal("interpolating_upsampler requires len(w_out) to be an integer multiple of len(w_in) for mode 'i'")
+    if mode == "h" and n < 2:
+        raise NotImplementedError(f"{what}: mode 'h' takes rows of at least 2 samples ({n} given): the reference reads an unbound variable there")
+    if n > interp_limit(mode, loop_dtype):
+        if mode == "s":
+            raise NotImplementedError(f"{what}: mode 's' takes rows of up to {_lib.INTERP_SPLINE_F32_MAX} samples in the float32 loop and "
+                                      f"{_lib.INTERP_SPLINE_F64_MAX} in the float64 loop ({n} given): the row and its second derivatives live in 64 KiB of LDS")
+        raise NotImplementedError(f"{what}: rows of up to {_lib.INTERP_F32_MAX} samples in the float32 loop and {_lib.INTERP_F32_MAX // 2} in the float64 loop "
+                                  f"({n} given): a row lives in 64 KiB of LDS")
+
+
+def _interpolating_upsampler(g, *args):
+    """one C entry for both loops, like psd's (``dsp_interp_upsample_rows`` takes the loop's type).  The mode is a constant of the call,
+    checked here for every row (the reference raises on the rows that get that far)."""
+    what = g.__name__
+    if len(args) != 3 or args[2] is None:
+        raise TypeError(f"{what}(w_in, mode_in, w_out): w_out must be passed (its length is the output size)")
+    w_in, mode_in, w_out = args
+    mode = _mode_char(_constant_of_call(mode_in, what, "mode_in"))
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        if not isinstance(w_out, (np.ndarray, DeviceArray)):
+            raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+        if np.dtype(w_out.dtype) != np.dtype(c.ft):
+            raise TypeError(f"{what}: w_out is {np.dtype(c.ft).name} in the {np.dtype(c.ft).name} loop ({np.dtype(w_out.dtype).name} given)")
+        m = int(w_out.shape[-1]) if len(w_out.shape) else 0
+        check_interp(what, mode, c.n, m, c.ft)
+        ptr, res = c.st.out(w_out, (m,) if c.one_d else (c.n_wf, m), c.ft)
+        c.results.append(res)
+        run(getattr(_lib.lib(), "dsp_interp_upsample_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, mode, ptr, m, m)
+        c.st.finish()
+        return res
+
+
+interpolating_upsampler = HipGUFunc("interpolating_upsampler", "(n),(),(m)", ["fbf", "dbd"], _interpolating_upsampler,
+                                    "the row resampled to len(w_out) samples: 'i' zero-stuffing, 'n' nearest, 'f' floor, 'c' ceiling, 'l' linear, 'h' Hermite "
+                                    "cubic, 's' natural cubic spline; a row with a NaN: NaNs (reference processors/upsampler.py:52-216)")
+
+# Listed here and not in __all__, like the spectral processors and sort: its call record is tests/test_interp_plan_cpu.py's.
+RESAMPLING = ("interpolating_upsampler",)
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

@@ -275,6 +275,13 @@ typedef struct dsp_scalar_arg {
                                  * Float32 / int16 / uint16 rows of up to 16384 samples in the float32 loop, float64 rows of up to 8192 in the float64 loop.
                                  * The waveform interpreter has no such op: it runs on dsp_sort_kernel only, in a program of exactly
                                  *   LOAD, SORT, STORE of dst */
+#define DSP_OP_INTERP_UPSAMPLE 42 /* upsampler.py:52-216 interpolating_upsampler: dst (m samples, another slot than src) <- src (n samples) resampled by the
+                                 * rule ip[0]: 'i' zero-stuffing (m a multiple of n), 'n' nearest, 'f' floor, 'c' ceiling, 'l' linear, 'h' Hermite cubic
+                                 * (n >= 2), 's' natural cubic spline.  The ratio is the float64 m / n: any m >= 1, below n too.  A row with a NaN: every
+                                 * output NaN.  Rows of up to 16384 samples in the float32 loop (float32 / int16 / uint16 rows) and 8192 in the float64
+                                 * loop (float64 rows); mode 's' 5456 and 4096.  The waveform interpreter has no such op: it runs on dsp_interp_kernel
+                                 * only, in a program of exactly
+                                 *   LOAD, INTERP_UPSAMPLE, STORE of dst */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -534,6 +541,13 @@ int dsp_fft(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t 
  * up to 8192 samples, double output).  sorted_out: rows of wf_len values of the loop's type, out_stride of them apart. */
 int dsp_sort_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, void* sorted_out,
                   int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(),(m)" interpolating_upsampler (upsampler.py:52-216): every row resampled to out_len samples by the rule `mode` (DSP_OP_INTERP_UPSAMPLE).
+ * One entry for both loops, like dsp_psd: compute_dtype names the loop (DSP_F32: float32 / int16 / uint16 rows, float output; DSP_F64: float64
+ * rows, double output).  out: rows of out_len values of the loop's type, out_stride of them apart; 16-byte stores where out and out_stride
+ * are whole vectors. */
+int dsp_interp_upsample_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, int32_t mode,
+                             void* out, int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
