@@ -35,8 +35,11 @@ _MULTI_EXTREMA = "get_multi_local_extrema"
 _HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
 _MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
 _PSD, _SORT, _INTERP = "psd", "sort", "interpolating_upsampler"
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP)  # processors that run as stages ahead of the program, on kernels of their own
-_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT)
+_NORMALISE = "normalisation_layer"
+_DENSE_LAYERS = ("dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
+_ML = (_NORMALISE,) + _DENSE_LAYERS
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP) + _ML  # processors that run as stages ahead of the program, on kernels of their own
+_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
 
@@ -149,6 +152,8 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
                 t_out.length = args[1].length
             if _time_unit_ns(t_out.unit) is not None and _grid_of(args[0]) is not None:
                 t_out.is_coord, t_out.grid = True, _grid_of(args[0])
+    if function in _ML:
+        args = _layer_arguments(b, function, args, key)
     args = [_as_taps(b, a, function) if r == "t" else a for a, r in zip(args, roles)]
     args = [_group_constant(b, a, function, key) if r == "i" and isinstance(a, (Var, SExpr)) else a for a, r in zip(args, roles)]
     _, args = _resolve(b, roles, args, same_dim_out=function in _SAME_DIM)
@@ -218,6 +223,50 @@ def _as_threshold_list(b: _Builder, a, key):
             raise NotImplementedError(f"{fn} ({key}): at most {_lib.THRESH_MAX} thresholds ({a.length} given): a wavefront keeps one per lane")
         return a
     raise ProcessingChainError(f"{fn} ({key}): the thresholds are a constant array or an array per event, not {a!r}")
+
+
+def _layer_arguments(b: _Builder, function, args, key):
+    """The constant arrays of a neural-network layer (ml.py): weights, bias, means and variances are a ``db.`` value, a list literal,
+    loadlh5(...), or a recipe entry holding one -- one array for every row, cast to the loop's float32 once, here (the reference hands a
+    float64 array to the float64 loop of the gufunc, like a float64 threshold list).  The weights of a dense layer are two-dimensional and
+    give an undeclared output its length; a classification layer's are one-dimensional, its bias one number."""
+    classify = function.startswith("classification")
+    names = {_NORMALISE: ("means", "variances")}.get(function, ("kernel", "bias"))
+    dims = {_NORMALISE: (1, 1)}.get(function, (1 if classify else 2, 0 if classify else 1))
+    args = list(args)
+    for k, (name, ndim) in enumerate(zip(names, dims), start=1):
+        if _SIGS[function][k] != "a":
+            break
+        a = args[k]
+        arr = a.const if isinstance(a, Var) and a.kind in ("const", "taps") and a.const is not None else a
+        if isinstance(arr, (list, tuple)) or (ndim == 0 and _is_number(arr)):
+            arr = np.asarray(arr)
+        if not isinstance(arr, np.ndarray):
+            raise NotImplementedError(f"{function} ({key}): {name} is a constant array -- a db. value, a list, loadlh5(...) or a recipe entry holding "
+                                      f"one --, not a per-event value ({a!r})")
+        if arr.ndim != ndim or arr.size < 1 or arr.dtype.kind not in "fiu":
+            raise ProcessingChainError(f"{function} ({key}): {name} is {'a number' if ndim == 0 else f'a {ndim}-dimensional array of numbers'}, "
+                                       f"not {arr.dtype.name} of shape {arr.shape}")
+        b._anon += 1
+        args[k] = Var(a.name if isinstance(a, Var) else f"{name}#{b._anon}", "taps", int(arr.size), np.float32, const=np.ascontiguousarray(arr, dtype=np.float32))
+    src, out = args[0], args[-1]
+    if _is_wf(src):
+        n = src.length
+        if function == _NORMALISE:
+            wrong = next((f"{nm} holds {a.length} values" for nm, a in zip(names, args[1:3]) if a.length != n), None)
+        else:
+            wrong = None if args[1].const.shape[0] == n else f"kernel has shape {args[1].const.shape}"
+            if wrong is None and len(names) > 1 and _SIGS[function][2] == "a" and args[2].length != (1 if classify else args[1].const.shape[1]):
+                wrong = f"bias holds {args[2].length} values"
+        if wrong:
+            raise ProcessingChainError(f"{function} ({key}): '{src.name}' holds {n} samples, {wrong}")
+        if not classify and function != _NORMALISE and isinstance(out, Var) and out.kind in (None, "wf"):
+            m = int(args[1].const.shape[1])
+            if out.length is None:
+                out.kind, out.length = "wf", m
+            elif out.length != m:
+                raise ProcessingChainError(f"{function} ({key}): '{out.name}' holds {out.length} samples, the kernel has {m} columns")
+    return args
 
 
 def _fold_generator(b: _Builder, function, args, new_vars):
@@ -916,6 +965,51 @@ def _stage_interp_upsampler(cx: _Stager):
         cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
 
 
+def _stage_ml_layers(cx: _Stager):
+    """The neural-network layers (ml.py) run on dsp_dense.hip and nowhere else, on rows in HBM: mandatory stages, like sort's.  Each dense or
+    classification layer is a launch on rows in memory -- a chain input, a stage's waveform (the layer before it), or a waveform the program
+    computes, written to HBM first.  A ``normalisation_layer`` whose result only dense or classification layers read, and which is not an
+    output of the recipe, is folded into their loads (the kernel normalises while it stages a row); otherwise it is a launch of its own.
+    The activation is a constant of the kernel."""
+    from .processors import check_dense
+
+    def folded(st):  # a normalisation that only layers read
+        out = st[1][3]
+        users = cx.users_of(out)
+        return bool(users) and out.name not in cx.out_names and all(u[0] in _DENSE_LAYERS and u[1][0] is out for u in users)
+
+    for st in [x for x in cx.steps if x[0] in _ML]:
+        fn, args, key = st[0], list(st[1]), st[2]
+        src, out = args[0], args[-1]
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        if fn == _NORMALISE:
+            if not (isinstance(out, Var) and out.kind == "wf" and out.length == src.length):
+                raise ProcessingChainError(f"{fn} ({key}): the output is a waveform variable of the source's {src.length} samples")
+            check_dense(f"{fn} ({key})", src.length, 1)
+            if not folded(st):
+                _rows_in_memory(cx, src, fn, key)
+                cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+            continue
+        if not isinstance(args[-2], (Char, int, np.integer)):
+            raise NotImplementedError(f"{fn} ({key}): the activation function is a constant of the kernel, not a per-event value")
+        classify = fn.startswith("classification")
+        check_dense(f"{fn} ({key})", src.length, 1 if classify else int(args[1].const.shape[1]))
+        if not isinstance(out, Var) or (not classify and not (out.kind == "wf" and out.length)):
+            raise ProcessingChainError(f"{fn} ({key}): name the output")
+        norm = cx.producer_of(src) if isinstance(src, Var) else None
+        if norm is not None and norm[0] == _NORMALISE and cx.has(norm) and folded(norm):
+            _rows_in_memory(cx, norm[1][0], _NORMALISE, norm[2])
+            group, what = [norm, st], f"{_NORMALISE} {norm[2]} + {fn} {key} in one launch on rows"
+        else:
+            _rows_in_memory(cx, src, fn, key)
+            group, what = [st], f"{fn} {key} on rows"
+        if classify:
+            cx.stage(group, [out], what, drop=[st])
+        else:
+            cx.stage(group, [], what, wfs=[out], rows_first=True, drop=[st])
+
+
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     """Long FIRs leave the program: each ``convolve_wf`` with a constant kernel of STAGE_MIN_TAPS or more taps becomes a launch of the
     matrix-core FIR kernels ahead of the program (one waveform per wavefront is the wrong shape for 133 x 8192 or 5792 x 301
@@ -943,6 +1037,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_spectrum(cx)
     _stage_sort(cx)
     _stage_interp_upsampler(cx)
+    _stage_ml_layers(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and v.ext_key is not None and v.aux_io is None}
     cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
@@ -1579,6 +1674,37 @@ class _Emitter:
         self.p.add_op(_lib.OP_INTERP_UPSAMPLE, dst=out.slot, src=src.slot, ip=(self.char_of(args[1]),))
         self.release(src, si)
 
+    def taps_io(self, v):
+        """the binding of a constant array, made at its first use"""
+        if v.io is None:
+            v.io = self.p.add_io(f"taps:{v.name}", _lib.IO_TAPS, self.ft, v.length, 0, 0)
+            self.consts[f"taps:{v.name}"] = np.ascontiguousarray(v.const, dtype=self.ft).reshape(-1)
+        return v.io
+
+    def normalisation_layer(self, si, fn, args, what):
+        """LOAD, NORMALISE in place; a dense layer of the same stage or the store of the normalised row follows"""
+        src = self.ensure_loaded(args[0], si)
+        out = self.out_wf(args[3], src.length, fn)
+        out.slot = src.slot
+        self.p.add_op(_lib.OP_NORMALISE, dst=src.slot, src=src.slot, io=self.taps_io(args[1]), ip=(self.taps_io(args[2]),))
+
+    def dense_layer(self, si, fn, args, what):
+        """[LOAD,] DENSE; the store of the m outputs -- of the one value, for a classification layer -- follows"""
+        classify = fn.startswith("classification")
+        src = self.ensure_loaded(args[0], si)
+        io_w = self.taps_io(args[1])
+        io_b = self.taps_io(args[2]) if fn.endswith("with_bias") else -1
+        act = self.char_of(args[-2])
+        if classify:
+            o = self.out_scalar(args[-1])
+            self.p.add_op(_lib.OP_DENSE, dst=o.sreg, src=src.slot, io=io_w, ip=(act, io_b, src.length, 0))
+        else:
+            m = int(args[1].const.shape[1])
+            out = self.out_wf(args[-1], m, fn)
+            out.slot = self.new_slot(m)
+            self.p.add_op(_lib.OP_DENSE, dst=out.slot, src=src.slot, io=io_w, ip=(act, io_b, src.length, m))
+        self.release(src, si)
+
     def copy_slice(self, si, fn, args, what):
         src = self.ensure_loaded(args[0], si)
         dst = args[3]
@@ -1758,7 +1884,8 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
          "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
          _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
-         _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler}
+         _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler,
+         _NORMALISE: _Emitter.normalisation_layer, **dict.fromkeys(_DENSE_LAYERS, _Emitter.dense_layer)}
 
 
 def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):

@@ -432,6 +432,43 @@ int dsp_interp_upsample_rows(ROWS, int compute_dtype, int32_t mode, void* out, i
     if (out_len < 1) return dsp_fail(DSP_ERR_ARG, "interpolating_upsampler: the output holds at least one sample (%d given)", out_len);
     return wf2wf(compute_dtype, DSP_OP_INTERP_UPSAMPLE, IN, {mode}, {}, {out, out_len, out_stride}, TAIL_ARGS);
 }
+// dense_layer_* and, with out_len == 0, classification_layer_*: one entry for both loops; weights and bias are bound like a filter's taps
+int dsp_dense_rows(ROWS, int compute_dtype, const void* weights_dev, const void* bias_dev, int32_t activation, void* out, int32_t out_len,
+                   int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "dense_layer: compute_dtype is DSP_F32 or DSP_F64");
+    if (out_len < 0 || !weights_dev) return dsp_fail(DSP_ERR_ARG, "dense_layer: weights_dev holds the weights on the device; out_len is m, or 0 for one value per row");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        const int32_t cols = out_len > 0 ? out_len : 1;
+        if (wf_len > DSP_DENSE_N_MAX || cols > DSP_DENSE_M_MAX)  // (ahead of the product below)
+            return dsp_fail(DSP_ERR_UNSUPPORTED, "dense_layer: " DSP_DENSE_LIMITS_TEXT " (n = %d, m = %d given)", DSP_DENSE_N_MAX, DSP_DENSE_M_MAX, wf_len, cols);
+        const int s_in = m.load(IN);
+        const int io_w = m.add_io(DSP_IO_TAPS, compute_dtype, wf_len * cols, 0, weights_dev);
+        const int io_b = bias_dev ? m.add_io(DSP_IO_TAPS, compute_dtype, cols, 0, bias_dev) : -1;
+        if (out_len > 0) {
+            const int s_out = m.add_slot(out_len);
+            m.op(DSP_OP_DENSE, s_out, s_in, io_w, {activation, io_b, wf_len, out_len});
+            m.store(s_out, {out, out_len, out_stride});
+        } else {
+            m.n_sregs = 1;
+            m.op(DSP_OP_DENSE, 0, s_in, io_w, {activation, io_b, wf_len, 0});
+            m.store_scalar(0, out, compute_dtype);
+        }
+        return DSP_OK;
+    });
+}
+// normalisation_layer: means and variances are bound like a filter's taps; in place in its slot
+int dsp_normalisation_rows(ROWS, int compute_dtype, const void* means_dev, const void* variances_dev, void* out, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "normalisation_layer: compute_dtype is DSP_F32 or DSP_F64");
+    if (!means_dev || !variances_dev) return dsp_fail(DSP_ERR_ARG, "normalisation_layer: means_dev and variances_dev hold len(x_in) values each on the device");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        const int s = m.load(IN);
+        const int io_mean = m.add_io(DSP_IO_TAPS, compute_dtype, wf_len, 0, means_dev);
+        const int io_var = m.add_io(DSP_IO_TAPS, compute_dtype, wf_len, 0, variances_dev);
+        m.op(DSP_OP_NORMALISE, s, s, io_mean, {io_var});
+        m.store(s, {out, wf_len, out_stride});
+        return DSP_OK;
+    });
+}
 #undef ROWS
 #undef IN
 #undef TAIL

@@ -422,6 +422,9 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     if (!rc)
         rc = raise_lds(ch->kernel_only == DSP_ROUTE_INTERP, dsp_interp::lds_bytes(ch->interp.mode, ch->interp.len, esz), 64 * 1024, "interp kernel, %d",
                        [&](int n) { return dsp_internal_set_interp_lds(ch->interp_src.dtype, n); });
+    if (!rc)
+        rc = raise_lds(ch->kernel_only == DSP_ROUTE_DENSE, dsp_dense::lds_bytes(ch->dense.m, esz), 64 * 1024, "dense kernel, %d",
+                       [&](int n) { return dsp_internal_set_dense_lds(ch->dense_src.dtype, n); });
     if (rc) return rc;
     *out = ch.release();
     return DSP_OK;
@@ -658,6 +661,17 @@ static int launch_interp(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void
     return launch_on_rows(ch, n_wf, stream, A, ch->interp_src, dsp_internal_launch_interp, "interp kernel launch");
 }
 
+static int launch_dense(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    DenseArgs A = ch->dense;
+    A.wf = io_ptrs[ch->dense_src.io];
+    A.weights = io_at(ch, io_ptrs, ch->eio_w);
+    A.bias = io_at(ch, io_ptrs, ch->eio_b);
+    A.means = io_at(ch, io_ptrs, ch->eio_mean);
+    A.variances = io_at(ch, io_ptrs, ch->eio_var);
+    A.out = io_at(ch, io_ptrs, ch->eio_out);
+    return launch_on_rows(ch, n_wf, stream, A, ch->dense_src, dsp_internal_launch_dense, "dense kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -844,6 +858,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_SPECTRUM)) return launch_spectrum(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_SORT)) return launch_sort(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_INTERP)) return launch_interp(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_DENSE)) return launch_dense(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -954,6 +969,12 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             lds = dsp_interp::row_bytes(mode, n, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
             break;
         }
+        case DSP_ROUTE_DENSE:  // a tile of 64 rows per workgroup; the normalisation alone: a wavefront per row
+            if (ch->dense.m > 0)
+                lds = dsp_dense::lds_bytes(ch->dense.m, ch->f64 ? 8 : 4) / 4, wpb = 4, b = (int)dsp_dense::tiles(n_wf);
+            else
+                lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4);
+            break;
         case DSP_ROUTE_EXTREMA:
         case DSP_ROUTE_THRESH:
         case DSP_ROUTE_PZ_ROWS:

@@ -16,6 +16,7 @@ enum dsp_route {
     DSP_ROUTE_SPECTRUM, // (nor this: PSD and FFT)
     DSP_ROUTE_SORT,     // (nor this: SORT)
     DSP_ROUTE_INTERP,   // (nor this: INTERP_UPSAMPLE)
+    DSP_ROUTE_DENSE,    // (nor this: NORMALISE and DENSE)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -27,6 +28,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_spectrum_kernel",
     "dsp_sort_kernel",
     "dsp_interp_kernel",
+    "dsp_dense_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -184,6 +186,26 @@ constexpr int max_len(int mode, int esz) { return mode == 's' ? (esz == 8 ? SPLI
 static_assert(row_bytes('s', SPLINE_F32_MAX, 4) <= LDS_MAX && row_bytes('s', SPLINE_F32_MAX + 16, 4) > LDS_MAX, "the longest float32 spline row fills the LDS");
 static_assert(row_bytes('s', SPLINE_F64_MAX, 8) == LDS_MAX && row_bytes('l', max_len('l', 4), 4) == LDS_MAX, "and the others");
 }  // namespace dsp_interp
+
+namespace dsp_dense {  // dsp_dense.hip: the neural-network layers of ml.py, rows x an (n, m) weight matrix on the matrix cores
+// ---- geometry.  A workgroup of WAVES wavefronts takes TILE_ROWS rows and all m outputs; a wavefront WAVE_ROWS rows x m, m in blocks of BLOCK
+// columns, an accumulator tile of v_mfma_*_16x16x4 per block.  Rows and weights pass through LDS in chunks of 256 bytes a row along n:
+//   x  [TILE_ROWS][x_pitch]    the rows' chunk, zero beyond n and in the rows beyond the batch
+//   w  [chunk][w_pitch(m)]     the weights' chunk, zero beyond n and in the columns beyond m (0 x garbage may be NaN)
+// Pitches: the lanes of an operand read differ in row (l & 15, x) or column (l & 15, w) and in k (l >> 4); the pads put the four k of a
+// read into different banks.
+constexpr int WAVES = 4, WAVE_ROWS = 16, TILE_ROWS = WAVES * WAVE_ROWS, BLOCK = 16, DEPTH = 4;  // (DEPTH: the k of one instruction)
+constexpr int N_MAX = 16384, M_MAX = 256, BLOCKS_MAX = M_MAX / BLOCK;
+constexpr int chunk(int esz) { return 256 / esz; }
+constexpr int x_pitch(int esz) { return chunk(esz) + 16 / esz; }
+constexpr int blocks(int m) { return (m + BLOCK - 1) / BLOCK; }
+constexpr int w_pitch(int m) { return blocks(m) * BLOCK + (blocks(m) % 2 == 0 ? BLOCK : 0); }
+constexpr int lds_bytes(int m, int esz) { return m < 1 ? 0 : (chunk(esz) * w_pitch(m) + TILE_ROWS * x_pitch(esz)) * esz; }
+// the kernel is built for 1, 4 or BLOCKS_MAX column blocks a wavefront: the smallest that holds m
+constexpr int built_blocks(int m) { return blocks(m) <= 1 ? 1 : blocks(m) <= 4 ? 4 : BLOCKS_MAX; }
+constexpr int64_t tiles(int64_t n_wf) { return (n_wf + TILE_ROWS - 1) / TILE_ROWS; }
+static_assert(lds_bytes(M_MAX, 4) == 87040 && lds_bytes(M_MAX, 8) == 87040 && lds_bytes(1, 4) < 64 * 1024, "LDS of the widest layer: raised past 64 KiB (dsp_internal_set_dense_lds)");
+}  // namespace dsp_dense
 
 namespace dsp_current {  // dsp_current.hip
 constexpr int CB = 16;   // samples per block (= per checkpoint)

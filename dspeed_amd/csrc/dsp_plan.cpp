@@ -111,6 +111,7 @@ static bool match_thresh_shape(const PlanCtx& c, const char** why);
 static bool match_spectrum_shape(const PlanCtx& c, const char** why);
 static bool match_sort_shape(const PlanCtx& c, const char** why);
 static bool match_interp_shape(const PlanCtx& c, const char** why);
+static bool match_dense_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -122,6 +123,8 @@ static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_SORT, {DSP_OP_SORT, DSP_OP_SORT}, match_sort_shape, "DSP_OP_SORT (sort) runs on dsp_sort_kernel only"},
     {DSP_ROUTE_INTERP, {DSP_OP_INTERP_UPSAMPLE, DSP_OP_INTERP_UPSAMPLE}, match_interp_shape,
      "DSP_OP_INTERP_UPSAMPLE (interpolating_upsampler) runs on dsp_interp_kernel only"},
+    {DSP_ROUTE_DENSE, {DSP_OP_NORMALISE, DSP_OP_DENSE}, match_dense_shape,
+     "DSP_OP_NORMALISE / DSP_OP_DENSE (normalisation_layer, dense_layer_*, classification_layer_*) run on dsp_dense_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -671,6 +674,51 @@ static bool match_interp_shape(const PlanCtx& c, const char** why) {
     return true;
 }
 
+// Is the program one of the dense-layer kernel's (dsp_dense.hip)?
+//   LOAD s;  [NORMALISE of s, in place;]  DENSE of s into a slot of m samples;  STORE of its m samples
+//   LOAD s;  [NORMALISE of s, in place;]  DENSE of s into a scalar register (the classification form);  STORE_SCALAR of it
+//   LOAD s;  NORMALISE of s, in place;  STORE of its n samples
+// Operands and limits are lower_op's business (every program that holds either op passes there first).  Why not, otherwise: `why`.
+static bool match_dense_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const int n = c.n_ops;
+    *why = "the program must be exactly LOAD, [NORMALISE,] DENSE, STORE; LOAD, [NORMALISE,] DENSE, STORE_SCALAR; or LOAD, NORMALISE, STORE";
+    auto is = [&](int i, int opcode) { return i < n && ops[i].opcode == opcode; };
+    if (n < 3 || n > 4 || !is(0, DSP_OP_LOAD)) return false;
+    const dsp_op* norm = is(1, DSP_OP_NORMALISE) ? &ops[1] : nullptr;
+    const dsp_op* dense = is(norm ? 2 : 1, DSP_OP_DENSE) ? &ops[norm ? 2 : 1] : nullptr;
+    const dsp_op& st = ops[n - 1];
+    if (n != 2 + (norm ? 1 : 0) + (dense ? 1 : 0)) return false;
+    const bool classify = dense && dense->ip[3] == 0;
+    if (st.opcode != (classify ? DSP_OP_STORE_SCALAR : DSP_OP_STORE) || c.n_slots != (dense && !classify ? 2 : 1)) return false;
+    const dsp_op& ld = ops[0];
+    DenseArgs& A = ch->dense;
+    memset(&A, 0, sizeof A);
+    ch->eio_w = ch->eio_b = ch->eio_mean = ch->eio_var = ch->eio_out = -1;
+    if ((norm && norm->src != ld.dst) || (dense && dense->src != ld.dst) ||
+        !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->dense_src, why, "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
+    *why = "the result is stored once, whole, in the loop's type";
+    const dsp_io_desc& o = c.io[st.io];
+    if (o.dtype != c.compute_dtype) return false;
+    if (classify ? st.ip[0] != dense->dst : (st.src != (dense ? dense->dst : ld.dst) || o.len != (dense ? dense->ip[3] : A.len))) return false;
+    if (norm) {
+        A.normalise = 1;
+        ch->eio_mean = norm->io;
+        ch->eio_var = norm->ip[0];
+    }
+    if (dense) {
+        A.m = classify ? 1 : dense->ip[3];
+        A.activation = dense->ip[0];
+        ch->eio_w = dense->io;
+        ch->eio_b = dense->ip[1];
+    }
+    ch->eio_out = st.io;
+    A.out_stride = o.row_stride;
+    return true;
+}
+
 // Does the program have the shape of the current-branch kernel (dsp_current.hip)?
 //   LOAD s0;  WINDOWER s1 <- s0 (start: constant or float32 column);  AVG_CURRENT s2 <- s1;  UPSAMPLER s3 <- s2;
 //   MOVING_WINDOW_MULTI d <- s3 (3 windows, alternating);  MIN_MAX of d;  STORE_SCALARs of its four registers
@@ -1202,6 +1250,12 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_SORT:
         case DSP_OP_INTERP_UPSAMPLE:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
+        case DSP_OP_NORMALISE: out[0] = o.src; return 1;
+        case DSP_OP_DENSE:
+            out[0] = o.src;
+            if (o.ip[3] == 0) return 1;  // (the classification form: dst is a scalar register)
+            out[1] = o.dst;
+            return 2;
         case DSP_OP_DWT_HAAR: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[2]; return 3;
         case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
         case DSP_OP_HISTOGRAM: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[0]; return 3;
@@ -1385,7 +1439,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE: their own layout and limits)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE: their own layout and limits)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1813,6 +1867,32 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
                 return fail(DSP_ERR_UNSUPPORTED, "interpolating_upsampler: rows of up to %d samples in the float32 loop and %d in the float64 loop (%d given): a row lives in 64 KiB of LDS",
                             DSP_INTERP_F32_MAX, DSP_INTERP_F32_MAX / 2, n);
             }
+            break;
+        }
+        case DSP_OP_NORMALISE: {
+            if (!check_slot(P, o.src) || o.dst != o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad NORMALISE (src = dst: the slot of the row, normalised in place)", i);
+            const int n = slot_len[o.src];
+            if (n > DSP_DENSE_N_MAX)
+                return fail(DSP_ERR_UNSUPPORTED, "normalisation_layer: " DSP_DENSE_LIMITS_TEXT " (n = %d given)", DSP_DENSE_N_MAX, DSP_DENSE_M_MAX, n);
+            if (!need_io(c, o, DSP_IO_TAPS) || io[o.io].len != n || o.ip[0] < 0 || o.ip[0] >= c.n_io || io[o.ip[0]].kind != DSP_IO_TAPS || io[o.ip[0]].len != n)
+                return fail(DSP_ERR_ARG, "normalisation_layer: means (io) and variances (ip[0]) are DSP_IO_TAPS bindings of len(x_in) = %d values", n);
+            break;
+        }
+        case DSP_OP_DENSE: {
+            const bool classify = o.ip[3] == 0;
+            if (!check_slot(P, o.src) || (classify ? (o.dst < 0 || o.dst >= n_sregs) : (!check_slot(P, o.dst) || o.dst == o.src)))
+                return fail(DSP_ERR_ARG, "op %d: bad DENSE (src: the slot of the row; dst: another slot, of ip[3] = m samples, or with ip[3] = 0 a scalar register)", i);
+            static_assert(dsp_dense::N_MAX == DSP_DENSE_N_MAX && dsp_dense::M_MAX == DSP_DENSE_M_MAX, "the limits the text names are the geometry's");
+            const int n = slot_len[o.src], m = classify ? 1 : o.ip[3];
+            if (o.ip[2] != n || (!classify && (m < 1 || slot_len[o.dst] != m)))
+                return fail(DSP_ERR_ARG, "op %d: DENSE: ip[2] is the length of the row (%d), ip[3] that of the output slot or 0 (%d and %d given)", i, n, o.ip[2], o.ip[3]);
+            if (n > DSP_DENSE_N_MAX || m > DSP_DENSE_M_MAX)
+                return fail(DSP_ERR_UNSUPPORTED, "dense_layer: " DSP_DENSE_LIMITS_TEXT " (n = %d, m = %d given)", DSP_DENSE_N_MAX, DSP_DENSE_M_MAX, n, m);
+            if (!need_io(c, o, DSP_IO_TAPS) || (int64_t)io[o.io].len != (int64_t)n * m)
+                return fail(DSP_ERR_ARG, "dense_layer: the weights (io) are a DSP_IO_TAPS binding of n * m = %d * %d values, row-major", n, m);
+            if (o.ip[1] >= 0 && (o.ip[1] >= c.n_io || io[o.ip[1]].kind != DSP_IO_TAPS || io[o.ip[1]].len != m))
+                return fail(DSP_ERR_ARG, "dense_layer: the bias (ip[1]) is a DSP_IO_TAPS binding of m = %d values, or -1", m);
             break;
         }
         case DSP_OP_DWT_HAAR: {

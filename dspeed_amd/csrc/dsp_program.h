@@ -386,6 +386,28 @@ struct InterpArgs {
     int64_t out_stride;
 };
 
+// arguments of the dense-layer kernel (dsp_dense.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> [NORMALISE ->] DENSE -> STORE | STORE_SCALAR        LOAD -> NORMALISE -> STORE
+// Rows and weights pass through LDS in chunks along n (dsp_kernels.h, dsp_dense); the accumulators stay in registers.
+#define DSP_DENSE_N_MAX 16384 /* inputs of a layer */
+#define DSP_DENSE_M_MAX 256   /* outputs of a layer: 16 column blocks of accumulators a wavefront */
+#define DSP_DENSE_LIMITS_TEXT "layers of up to %d inputs and %d outputs"
+struct DenseArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples (n)
+    int32_t m;               // outputs (1: the classification form too); 0: no DENSE, the normalised row itself is stored
+    int32_t activation;      // the character; none of "srlmt": NaN outputs
+    int32_t normalise;       // 1: (x - means) / sqrt(variances) while a row is staged
+    int32_t pad_;
+    const void* weights;     // (n, m) row-major, the loop's type
+    const void* bias;        // m values or null
+    const void* means;       // n values each (normalise)
+    const void* variances;
+    void* out;               // rows of m values (of n: m == 0) of the loop's type
+    int64_t out_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

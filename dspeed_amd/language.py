@@ -228,7 +228,7 @@ def _text(a):
 
 # signatures of the supported processors: argument roles, in recipe order
 #   w = waveform in, W = waveform out, s = float scalar in (const or per-event), i = int const, c = char const,
-#   S = scalar out, t = taps in
+#   S = scalar out, t = taps in, a = a constant array of a neural-network layer (weights, bias, means, variances)
 _SIGS = {
     "bl_subtract": "wsW", "pole_zero": "wsW", "double_pole_zero": "wsssW", "trap_filter": "wiiW", "trap_norm": "wiiW",
     "asym_trap_filter": "wiiiW", "fixed_time_pickoff": "wscS", "time_point_thresh": "wsssS", "interpolated_time_point_thresh": "wssicS",
@@ -241,6 +241,9 @@ _SIGS = {
     "psd": "wW",  # (w_in, psd_out[len(w_in) // 2 + 1])
     "sort": "wW",  # (w_in, w_out)
     "interpolating_upsampler": "wcW",  # (w_in, mode_in, w_out[m]: any length)
+    # ml.py: (x_in, means, variances, x_out); (x_in, kernel[n, m], [bias[m],] activation_func, x_out[m]); (x_in, kernel[n], [bias,] activation_func, x_out)
+    "normalisation_layer": "waaW", "dense_layer_no_bias": "wacW", "dense_layer_with_bias": "waacW",
+    "classification_layer_no_bias": "wacS", "classification_layer_with_bias": "waacS",
     "get_multi_local_extrema": "wssissWWSS",  # (w_in, a_delta_max_in, a_delta_min_in, search_direction, a_abs_max_in, a_abs_min_in, two lists, two counts)
 }
 _SIGS.update({"sample": "wiS", "slice": "wiiW", "get": "wsS"})  # wf[i], wf[lo:hi:step], wf[variable] (reference :948-1071)
@@ -348,12 +351,15 @@ _PROCESSOR_FILES = {
 _SPECTRAL_FILES = {"psd": ("fft",), "fft": ("fft",)}
 _ORDER_FILES = {"sort": ("sort",)}  # (processors.ORDER, likewise)
 _RESAMPLING_FILES = {"interpolating_upsampler": ("upsampler",)}  # (processors.RESAMPLING, likewise)
+_ML_FILES = dict.fromkeys(("normalisation_layer", "dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias",
+                           "classification_layer_with_bias"), ("ml",))  # (processors.ML, likewise)
 
 
 def module_accepted(module, function) -> bool:
     """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
     pre = "dspeed.processors."
     files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ()) + _ORDER_FILES.get(function, ()) + _RESAMPLING_FILES.get(function, ())
+    files += _ML_FILES.get(function, ())
     return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in files)
 
 

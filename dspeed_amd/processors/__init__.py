@@ -518,5 +518,100 @@ interpolating_upsampler = HipGUFunc("interpolating_upsampler", "(n),(),(m)", ["f
 # Listed here and not in __all__, like the spectral processors and sort: its call record is tests/test_interp_plan_cpu.py's.
 RESAMPLING = ("interpolating_upsampler",)
 
+
+# --------------------------------------------------------------------------------------------------- neural-network layers
+ML_ACTIVATIONS = "srlmt"  # sigmoid, relu, leaky relu, softplus ("softmax" in the reference), tanh; any other character: NaN outputs, no error
+DENSE_LIMITS = f"layers of up to {_lib.DENSE_N_MAX} inputs and {_lib.DENSE_M_MAX} outputs"  # (DSP_DENSE_LIMITS_TEXT, dsp_program.h)
+
+
+def check_dense(what, n, m):
+    """what the planner checks, in its words"""
+    if n > _lib.DENSE_N_MAX or m > _lib.DENSE_M_MAX:
+        raise NotImplementedError(f"{what}: {DENSE_LIMITS} (n = {n}, m = {m} given)")
+
+
+def _layer_constant(c, v, what, name):
+    """weights, bias, means or variances: one constant array for every row, on the device in the loop's type -> (DeviceArray, shape)"""
+    if isinstance(v, DeviceArray):
+        if v.dtype != np.dtype(c.ft):
+            raise TypeError(f"{what}: {name} on the device has the loop's type, {np.dtype(c.ft)}")
+        return v, tuple(v.shape)
+    host = np.ascontiguousarray(np.asarray(v), dtype=c.ft)
+    if host.size < 1:
+        raise ValueError(f"{what}: {name} is empty")
+    d = DeviceArray.from_numpy(host if host.ndim else host.reshape(1))
+    c.st.keep.append(d)
+    return d, host.shape
+
+
+def _dense(classify, with_bias):
+    """dense_layer_* (an (n, m) kernel, m outputs a row) and classification_layer_* (an (n) kernel, one value a row): one C entry for both
+    loops, ``dsp_dense_rows``.  Kernel and bias are constants of the call; so is the activation."""
+
+    def impl(g, *args):
+        what = g.__name__
+        ins, outs = _split(g, args)
+        w_in, kernel, bias = ins[0], ins[1], ins[2] if with_bias else None
+        act = _mode_char(_constant_of_call(ins[-1], what, "activation_func"))
+        with device_call(what, w_in, f64_rows_only=True) as c:
+            wd, wshape = _layer_constant(c, kernel, what, "kernel")
+            if classify:
+                if wshape not in ((c.n,), (c.n, 1)):
+                    raise ValueError(f"{what}: kernel has shape {wshape}, expected ({c.n},)")
+                m = 1
+            else:
+                if len(wshape) != 2 or wshape[0] != c.n:
+                    raise ValueError(f"{what}: kernel has shape {wshape}, expected ({c.n}, m)")
+                m = int(wshape[1])
+            check_dense(what, c.n, m)
+            bptr = None
+            if with_bias:
+                bd, bshape = _layer_constant(c, bias, what, "bias")
+                if int(np.prod(bshape)) != m or len(bshape) > 1:
+                    raise (NotImplementedError(f"{what}: bias is a constant of the call on the device, not a per-event value") if classify else
+                           ValueError(f"{what}: bias has shape {bshape}, expected ({m},)"))
+                bptr = bd.ptr
+            shape = () if classify else (m,)
+            ptr, res = c.st.out(outs[0], shape if c.one_d else (c.n_wf, *shape), c.ft)
+            run(getattr(_lib.lib(), "dsp_dense_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, wd.ptr, bptr, act, ptr,
+                0 if classify else m, m)
+            c.st.finish()
+            return res[()] if isinstance(res, np.ndarray) and res.ndim == 0 else res
+
+    return impl
+
+
+def _normalisation_layer(g, *args):
+    what = g.__name__
+    (w_in, means, variances), outs = _split(g, args)
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        check_dense(what, c.n, 1)
+        consts = []
+        for v, name in ((means, "means"), (variances, "variances")):
+            d, shape = _layer_constant(c, v, what, name)
+            if shape != (c.n,):
+                raise ValueError(f"{what}: {name} has shape {shape}, expected ({c.n},)")
+            consts.append(d.ptr)
+        ptr, res = c.st.out(outs[0], (c.n,) if c.one_d else (c.n_wf, c.n), c.ft)
+        run(getattr(_lib.lib(), "dsp_normalisation_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, *consts, ptr, c.n)
+        c.st.finish()
+        return res
+
+
+_LAYER_DOC = ("activation(x_in . kernel{}) on the matrix cores, one fused multiply-add chain per output in ascending k; activations s r l m t as the "
+              "reference writes them, any other character: NaN outputs; a row with a NaN: NaN outputs (reference processors/ml.py:{})")
+normalisation_layer = HipGUFunc("normalisation_layer", "(n),(n),(n)->(n)", ["fff->f", "ddd->d"], _normalisation_layer,
+                                "(x_in - means) / sqrt(variances), every step in the loop's type (reference processors/ml.py:349-390)")
+dense_layer_no_bias = HipGUFunc("dense_layer_no_bias", "(n),(n,m),()->(m)", ["ffb->f", "ddb->d"], _dense(False, False), _LAYER_DOC.format("", "83-141"))
+dense_layer_with_bias = HipGUFunc("dense_layer_with_bias", "(n),(n,m),(m),()->(m)", ["fffb->f", "dddb->d"], _dense(False, True),
+                                  _LAYER_DOC.format(" + bias", "144-209"))
+classification_layer_no_bias = HipGUFunc("classification_layer_no_bias", "(n),(n),()->()", ["ffb->f", "ddb->d"], _dense(True, False),
+                                         _LAYER_DOC.format("", "212-274").replace("per output", "per row"))
+classification_layer_with_bias = HipGUFunc("classification_layer_with_bias", "(n),(n),(),()->()", ["fffb->f", "dddb->d"], _dense(True, True),
+                                           _LAYER_DOC.format(" + bias", "277-346").replace("per output", "per row"))
+
+# Listed here and not in __all__, like the spectral processors, sort and the resampler: their call records are tests/test_ml_plan_cpu.py's.
+ML = ("normalisation_layer", "dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

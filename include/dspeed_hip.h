@@ -282,6 +282,19 @@ typedef struct dsp_scalar_arg {
                                  * loop (float64 rows); mode 's' 5456 and 4096.  The waveform interpreter has no such op: it runs on dsp_interp_kernel
                                  * only, in a program of exactly
                                  *   LOAD, INTERP_UPSAMPLE, STORE of dst */
+#define DSP_OP_NORMALISE 43     /* ml.py:358-390 normalisation_layer: dst = src (in place), sample k <- (sample k - means[k]) / sqrt(variances[k]), every step
+                                 * in the loop's type, IEEE division and square root; no NaN rule.  io = the means, ip[0] = the io index of the variances:
+                                 * DSP_IO_TAPS bindings of n values of the loop's type.  Runs on dsp_dense_kernel only (see DSP_OP_DENSE). */
+#define DSP_OP_DENSE 44         /* ml.py:92-346 dense_layer_* / classification_layer_*: activation(src (n samples) . weights (n, m) [+ bias]).  io = the
+                                 * weights, a DSP_IO_TAPS binding of n * m values, row-major; ip[0] = the activation character ('s' sigmoid, 'r' relu,
+                                 * 'l' leaky relu, 'm' softplus, 't' tanh; any other: NaN outputs, as the reference leaves them); ip[1] = the io index of
+                                 * the bias (DSP_IO_TAPS, m values) or -1; ip[2] = n; ip[3] = m >= 1: dst is a slot of m samples, or 0: the classification
+                                 * form, one value (m = 1) into scalar register dst.  One float32 (float64) fused multiply-add chain per output in
+                                 * ascending k on the matrix cores, the bias added behind it; a row with a NaN: NaN outputs.  n up to 16384, m up to 256.
+                                 * The waveform interpreter has neither op: they run on dsp_dense_kernel only, in a program of exactly
+                                 *   LOAD, [NORMALISE,] DENSE, STORE of dst
+                                 *   LOAD, [NORMALISE,] DENSE, STORE_SCALAR of dst
+                                 *   LOAD, NORMALISE, STORE */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -548,6 +561,18 @@ int dsp_sort_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, in
  * are whole vectors. */
 int dsp_interp_upsample_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, int32_t mode,
                              void* out, int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(n,m)[,(m)],()->(m)" dense_layer_no_bias / dense_layer_with_bias and, with out_len == 0, "(n),(n)[,()],()->()" classification_layer_*
+ * (ml.py:92-346; DSP_OP_DENSE).  One entry for both loops, like dsp_psd.  weights_dev: wf_len * m values of the loop's type on the device,
+ * row-major (n, m), m = out_len (1 for out_len == 0); bias_dev: m values or NULL; activation: the character.  out: rows of out_len values
+ * out_stride apart, or with out_len == 0 a column of one value per row (out_stride is not read). */
+int dsp_dense_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, const void* weights_dev,
+                   const void* bias_dev, int32_t activation, void* out, int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(n),(n)->(n)" normalisation_layer (ml.py:358-390; DSP_OP_NORMALISE): (row - means) / sqrt(variances), means_dev and variances_dev
+ * wf_len values of the loop's type on the device.  One entry for both loops. */
+int dsp_normalisation_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype,
+                           const void* means_dev, const void* variances_dev, void* out, int64_t out_stride, void* stream, int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
