@@ -24,6 +24,8 @@ SPECTRUM_F32_POW2_MAX, SPECTRUM_F32_ANY_MAX = 16384, 4096
 SORT_F32_MAX = 16384  # DSP_SORT_F32_MAX (dsp_program.h): the longest row of sort in the float32 loop (float64: half)
 # DSP_INTERP_* (dsp_program.h): the longest rows of interpolating_upsampler in the float32 loop (float64: half), and in mode 's' in either loop
 INTERP_F32_MAX, INTERP_SPLINE_F32_MAX, INTERP_SPLINE_F64_MAX = 16384, 5456, 4096
+# DSP_REFLECT_* (dsp_program.h): the longest staged row of reflected_convolve_wf, len(w_in) + len(kernel) - 1, in the float32 and the float64 loop
+REFLECT_F32_MAX, REFLECT_F64_MAX = 16384, 8192
 DENSE_N_MAX, DENSE_M_MAX = 16384, 256  # DSP_DENSE_*_MAX (dsp_program.h): the inputs and outputs of a dense / classification / normalisation layer
 F32, F64, I16, U16, I32, U32, BOOL, I64, U64 = range(9)
 IO_WF_IN, IO_WF_OUT, IO_SCALAR_IN, IO_SCALAR_OUT, IO_TAPS = range(5)
@@ -32,7 +34,7 @@ ARG_CONST, ARG_INPUT, ARG_REG = range(3)
  OP_ASYM_TRAP, OP_PICKOFF, OP_TIME_POINT_THRESH, OP_MIN_MAX, OP_DWT_HAAR, OP_CONVOLVE, OP_COPY, OP_TRAP_PICKOFF, OP_AMAX,
  OP_SCALAR_AFFINE, OP_MEAN_BELOW, OP_CONVOLVE_AMAX, OP_WINDOWER, OP_AVG_CURRENT, OP_TRAP_WINDOW_PICKOFF, OP_TRAP_REDUCE, OP_UPSAMPLER, OP_MOVING_WINDOW_MULTI, OP_LINEAR_SLOPE_FIT,
  OP_SCALAR_CONVERT, OP_SCALAR_DIV, OP_INTERP_TIME_POINT_THRESH, OP_MIN_MAX_NORM, OP_ELEMENTWISE, OP_SCALAR_FUNC, OP_MULTI_EXTREMA, OP_HISTOGRAM,
- OP_HISTOGRAM_STATS, OP_MULTI_TIME_POINT_THRESH, OP_TIME_OVER_THRESHOLD, OP_PSD, OP_FFT, OP_SORT, OP_INTERP_UPSAMPLE, OP_NORMALISE, OP_DENSE) = range(1, 45)
+ OP_HISTOGRAM_STATS, OP_MULTI_TIME_POINT_THRESH, OP_TIME_OVER_THRESHOLD, OP_PSD, OP_FFT, OP_SORT, OP_INTERP_UPSAMPLE, OP_NORMALISE, OP_DENSE, OP_REFLECTED_CONVOLVE) = range(1, 46)
 (FN_ADD, FN_SUB, FN_MUL, FN_DIV, FN_LT, FN_LE, FN_GT, FN_GE, FN_EQ, FN_NE, FN_WHERE, FN_ISNAN, FN_ISFINITE, FN_NEG, FN_COPY, FN_FLOORDIV,
  FN_IADD, FN_ISUB, FN_IMUL, FN_IFLOORDIV, FN_ICAST, FN_LOR, FN_LAND, FN_RINT, FN_FLOOR, FN_CEIL, FN_TRUNC) = range(27)
 
@@ -153,6 +155,7 @@ SIG = {
         "dsp_interp_upsample_rows": [vp, C.c_int, i64, i32, i64, C.c_int, i32, vp, i32, i64, vp, pi64],
         "dsp_dense_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, vp, i32, vp, i32, i64, vp, pi64],
         "dsp_normalisation_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, vp, vp, i64, vp, pi64],
+        "dsp_reflected_convolve_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, vp, i64, vp, pi64],
         "dsp_synth_waveforms": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_synth_pulses": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_stream_read": [vp, i64, vp, vp],

@@ -34,12 +34,12 @@ from .language import (Char, Grid, Quantity, SExpr, Var, View, _Builder, _GENERA
 _MULTI_EXTREMA = "get_multi_local_extrema"
 _HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
 _MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
-_PSD, _SORT, _INTERP = "psd", "sort", "interpolating_upsampler"
+_PSD, _SORT, _INTERP, _REFLECT = "psd", "sort", "interpolating_upsampler", "reflected_convolve_wf"
 _NORMALISE = "normalisation_layer"
 _DENSE_LAYERS = ("dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
 _ML = (_NORMALISE,) + _DENSE_LAYERS
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP) + _ML  # processors that run as stages ahead of the program, on kernels of their own
-_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE)
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT) + _ML  # processors that run as stages ahead of the program, on kernels of their own
+_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
 
@@ -965,6 +965,43 @@ def _stage_interp_upsampler(cx: _Stager):
         cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
 
 
+def _stage_reflected_convolve(cx: _Stager):
+    """``reflected_convolve_wf`` runs on dsp_reflect.hip and nowhere else, on rows in HBM: a mandatory stage, like sort's, made ahead of the
+    others (the histogram and the peak finder of the SiPM recipes read what it feeds).  The source is a chain input, a stage's waveform, a
+    slice of either, or a waveform the program computes, written to HBM first; the kernel is constant taps in any form convolve_wf's takes;
+    the filtered row is an ordinary waveform variable of the program, with the source's length and grid.  An ``avg_current`` that reads
+    exactly the filtered waveform, with a constant length, joins the launch; the filtered waveform is then written only if something else
+    reads it or the recipe asks for it (``_stage_histogram``'s rule for weights and borders)."""
+    from .processors import check_reflect
+
+    fn = _REFLECT
+    for st in cx.steps_of(fn):
+        args, key = list(st[1]), st[2]
+        src, taps, out = args
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        if not (isinstance(taps, Var) and taps.kind == "taps"):
+            raise NotImplementedError(f"{fn} ({key}): the kernel is one constant array for every row (a database array, a list, loadlh5 or a kernel "
+                                      "generator's output), not a per-event value")
+        if not (isinstance(out, Var) and out.kind == "wf" and out.length):
+            raise ProcessingChainError(f"{fn} ({key}): the output is a waveform variable")
+        if out.length != src.length:
+            raise ValueError(f"{fn} ({key}): the output has the length of the input (len(w_in) = {src.length}, len(w_out) = {out.length})")
+        check_reflect(f"{fn} ({key})", src.length, taps.length, np.float32)
+        _rows_in_memory(cx, src, fn, key)
+        def joins(x):  # an avg_current of exactly the filtered row, with a constant length DSP_OP_AVG_CURRENT accepts
+            length = x[1][1].const if isinstance(x[1][1], Var) and x[1][1].kind == "const" else x[1][1]
+            return (x[0] == "avg_current" and x[1][0] is out and _is_number(length) and isinstance(x[1][2], Var) and bool(x[1][2].length)
+                    and 0 < int(length) < out.length and x[1][2].length == out.length - int(length))
+
+        cur = next((x for x in cx.users_of(out) if joins(x)), None)
+        if cur is None:
+            cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+            continue
+        row_wanted = out.name in cx.out_names or any(u is not cur for u in cx.users_of(out))
+        cx.stage([st, cur], [], f"{fn} {key} + avg_current {cur[2]} in one launch on rows", wfs=([out] if row_wanted else []) + [cur[1][2]], rows_first=True)
+
+
 def _stage_ml_layers(cx: _Stager):
     """The neural-network layers (ml.py) run on dsp_dense.hip and nowhere else, on rows in HBM: mandatory stages, like sort's.  Each dense or
     classification layer is a launch on rows in memory -- a chain input, a stage's waveform (the layer before it), or a waveform the program
@@ -1031,6 +1068,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     if fir_staged:  # (the optional families follow the long filters, as before; the peak finder's stage is made with or without them)
         _stage_short_traps(cx)
         _stage_current_branch(cx)
+    _stage_reflected_convolve(cx)  # (ahead of everything that may read the smoothed rows or their current)
     _stage_histogram(cx)  # (ahead of the peak finder: its thresholds may be arithmetic of these results, "3*fwhm")
     _stage_multi_extrema(cx)
     _stage_thresholds(cx)
@@ -1674,6 +1712,15 @@ class _Emitter:
         self.p.add_op(_lib.OP_INTERP_UPSAMPLE, dst=out.slot, src=src.slot, ip=(self.char_of(args[1]),))
         self.release(src, si)
 
+    def reflected_convolve(self, si, fn, args, what):
+        """the whole program of the stage: LOAD, REFLECTED_CONVOLVE; an avg_current of the filtered row may follow, then the stores"""
+        src = self.ensure_loaded(args[0], si)
+        taps = args[1]
+        out = self.out_wf(args[2], src.length, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_REFLECTED_CONVOLVE, dst=out.slot, src=src.slot, io=self.taps_io(taps), ip=(int(np.isnan(taps.const).any()),))
+        self.release(src, si)
+
     def taps_io(self, v):
         """the binding of a constant array, made at its first use"""
         if v.io is None:
@@ -1884,7 +1931,7 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
          "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
          _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
-         _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler,
+         _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler, _REFLECT: _Emitter.reflected_convolve,
          _NORMALISE: _Emitter.normalisation_layer, **dict.fromkeys(_DENSE_LAYERS, _Emitter.dense_layer)}
 
 

@@ -469,6 +469,26 @@ int dsp_normalisation_rows(ROWS, int compute_dtype, const void* means_dev, const
         return DSP_OK;
     });
 }
+// reflected_convolve_wf: one entry for both loops too; the kernel is bound like convolve_wf's and looked at once here: a NaN among the taps
+// makes every row NaN (convolutions.py:160-161)
+int dsp_reflected_convolve_rows(ROWS, int compute_dtype, const void* taps_dev, int32_t n_taps, void* out, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "reflected_convolve_wf: compute_dtype is DSP_F32 or DSP_F64");
+    if (n_taps < 1 || !taps_dev) return dsp_fail(DSP_ERR_ARG, "reflected_convolve_wf: taps_dev holds n_taps >= 1 values of the loop's type on the device");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (n_taps > wf_len) return dsp_fail(DSP_ERR_ARG, "The filter is longer than the input waveform (%d taps, %d samples)", n_taps, wf_len);  // (ahead of the read-back)
+        const size_t esz = compute_dtype == DSP_F64 ? 8 : 4;
+        std::vector<unsigned char> taps(esz * (size_t)n_taps);
+        if (int rc = dsp_gufunc_read_back(taps.data(), taps_dev, taps.size())) return rc;
+        int has_nan = 0;
+        for (int k = 0; k < n_taps; ++k)
+            has_nan |= std::isnan(compute_dtype == DSP_F64 ? ((const double*)taps.data())[k] : (double)((const float*)taps.data())[k]) ? 1 : 0;
+        const int s_in = m.load(IN), s_out = m.add_slot(wf_len);
+        const int io_k = m.add_io(DSP_IO_TAPS, compute_dtype, n_taps, 0, taps_dev);
+        m.op(DSP_OP_REFLECTED_CONVOLVE, s_out, s_in, io_k, {has_nan});
+        m.store(s_out, {out, wf_len, out_stride});
+        return DSP_OK;
+    });
+}
 #undef ROWS
 #undef IN
 #undef TAIL

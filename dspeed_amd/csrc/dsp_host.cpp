@@ -425,6 +425,9 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     if (!rc)
         rc = raise_lds(ch->kernel_only == DSP_ROUTE_DENSE, dsp_dense::lds_bytes(ch->dense.m, esz), 64 * 1024, "dense kernel, %d",
                        [&](int n) { return dsp_internal_set_dense_lds(ch->dense_src.dtype, n); });
+    if (!rc)
+        rc = raise_lds(ch->kernel_only == DSP_ROUTE_REFLECT, dsp_reflect::lds_bytes(ch->reflect.len, ch->reflect.n_taps, esz), 64 * 1024, "reflect kernel, %d",
+                       [&](int n) { return dsp_internal_set_reflect_lds(ch->reflect_src.dtype, n); });
     if (rc) return rc;
     *out = ch.release();
     return DSP_OK;
@@ -672,6 +675,17 @@ static int launch_dense(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void*
     return launch_on_rows(ch, n_wf, stream, A, ch->dense_src, dsp_internal_launch_dense, "dense kernel launch");
 }
 
+static int launch_reflect(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    ReflectArgs A = ch->reflect;
+    A.wf = io_ptrs[ch->reflect_src.io];
+    A.taps = io_at(ch, io_ptrs, ch->rio_taps);
+    A.out = io_at(ch, io_ptrs, ch->rio_out);
+    A.cur = io_at(ch, io_ptrs, ch->rio_cur);
+    // 16-byte stores: launch_interp's rule (the plan vouches for the stride, this call's pointer for the start)
+    A.out_vec = A.out && (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
+    return launch_on_rows(ch, n_wf, stream, A, ch->reflect_src, dsp_internal_launch_reflect, "reflect kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -859,6 +873,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_SORT)) return launch_sort(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_INTERP)) return launch_interp(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_DENSE)) return launch_dense(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_REFLECT)) return launch_reflect(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -967,6 +982,12 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             const int n = ch->interp.len, mode = ch->interp.mode, es = ch->f64 ? 8 : 4;
             const bool wide = dsp_interp::wide(mode, n, es);
             lds = dsp_interp::row_bytes(mode, n, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
+            break;
+        }
+        case DSP_ROUTE_REFLECT: {
+            const int n = ch->reflect.len, m = ch->reflect.n_taps, es = ch->f64 ? 8 : 4;
+            const bool wide = dsp_reflect::wide(n, m, es);
+            lds = dsp_reflect::row_bytes(n, m, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
             break;
         }
         case DSP_ROUTE_DENSE:  // a tile of 64 rows per workgroup; the normalisation alone: a wavefront per row

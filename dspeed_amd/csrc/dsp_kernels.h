@@ -17,6 +17,7 @@ enum dsp_route {
     DSP_ROUTE_SORT,     // (nor this: SORT)
     DSP_ROUTE_INTERP,   // (nor this: INTERP_UPSAMPLE)
     DSP_ROUTE_DENSE,    // (nor this: NORMALISE and DENSE)
+    DSP_ROUTE_REFLECT,  // (nor this: REFLECTED_CONVOLVE)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -29,6 +30,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_sort_kernel",
     "dsp_interp_kernel",
     "dsp_dense_kernel",
+    "dsp_reflect_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -206,6 +208,42 @@ constexpr int built_blocks(int m) { return blocks(m) <= 1 ? 1 : blocks(m) <= 4 ?
 constexpr int64_t tiles(int64_t n_wf) { return (n_wf + TILE_ROWS - 1) / TILE_ROWS; }
 static_assert(lds_bytes(M_MAX, 4) == 87040 && lds_bytes(M_MAX, 8) == 87040 && lds_bytes(1, 4) < 64 * 1024, "LDS of the widest layer: raised past 64 KiB (dsp_internal_set_dense_lds)");
 }  // namespace dsp_dense
+
+namespace dsp_reflect {  // dsp_reflect.hip: reflected_convolve_wf (convolutions.py:122-182), a FIR of m taps over a row of n samples with mirrored edges
+// ---- the rule.  np.convolve(np.pad(w, int(m/2) + 1, "reflect"), kernel, "same") cut back to n samples is, for 1 <= m <= n,
+//   out[i] = sum_k kernel[k] * w[reflect(i + centre(m) - k, n)]
+// the kernel flipped (a convolution), its centre at (m - 1) / 2 for even m too, the edge sample not repeated ("reflect", not "symmetric").
+// One reflection suffices because m <= n.
+constexpr int centre(int m) { return (m - 1) / 2; }
+constexpr int left(int m) { return m / 2; }         // mirrored samples ahead of the row: output 0 reaches centre(m) - (m - 1) = -left(m)
+constexpr int right(int m) { return (m - 1) / 2; }  // and behind it: output n - 1 reaches n - 1 + centre(m)
+constexpr int reflect(int t, int n) { return t < 0 ? -t : t > n - 1 ? 2 * (n - 1) - t : t; }
+// ---- the staged row.  staged(n, m) samples E[j] = w[source(j, n, m)], the margins materialised beside the row, so that
+//   out[i] = sum_k kernel[k] * E[i + m - 1 - k]
+// needs no branch.  A lane makes vec(esz) consecutive outputs and reads its samples 16 bytes at a time, V taps a step from tap 0 on: the
+// staged row starts pad(m, esz) samples into its LDS, so that these reads are whole vectors -- output i, taps k0 .. k0 + V - 1 (k0 a
+// multiple of V) read the vector at i + m + pad - k0 - V and, for its later outputs, those above; the last step of a kernel whose length
+// is no multiple of V starts at 0 and uses its upper m % V samples only.  elems(): the samples of LDS a row takes, the run of the last lane
+// included (what it reads past the staged row feeds outputs past the row, which are not stored).
+constexpr int staged(int n, int m) { return n + m - 1; }
+constexpr int source(int j, int n, int m) { return reflect(j - left(m), n); }
+constexpr int vec(int esz) { return 16 / esz; }
+constexpr int round_up(int x, int v) { return (x + v - 1) / v * v; }
+constexpr int pad(int m, int esz) { return round_up(m, vec(esz)) - m; }
+constexpr int elems(int n, int m, int esz) { return round_up(n, vec(esz)) + round_up(m, vec(esz)); }
+// ---- geometry and limits.  The staged row lives in 64 KiB of LDS: F32_MAX / F64_MAX staged samples (DSP_REFLECT_*_MAX of dsp_program.h);
+// the alignment above adds at most 28 bytes.  Rows that fill at most WAVE_ROW_BYTES staged get a wavefront each, four to a workgroup (no
+// barrier); longer ones a workgroup of 256, with 16 bytes behind the row for the word its wavefronts agree on "a NaN" through.
+constexpr int WAVE_ROW_BYTES = 8 * 1024, LDS_MAX = 64 * 1024;
+constexpr int F32_MAX = LDS_MAX / 4, F64_MAX = LDS_MAX / 8;
+constexpr int max_staged(int esz) { return esz == 8 ? F64_MAX : F32_MAX; }
+constexpr bool fits(int n, int m, int esz) { return (int64_t)n + m - 1 <= max_staged(esz); }
+constexpr int row_bytes(int n, int m, int esz) { return elems(n, m, esz) * esz; }
+constexpr bool wide(int n, int m, int esz) { return staged(n, m) * esz > WAVE_ROW_BYTES; }
+constexpr int lds_bytes(int n, int m, int esz) { return wide(n, m, esz) ? row_bytes(n, m, esz) + 16 : 4 * row_bytes(n, m, esz); }
+static_assert(left(1) == 0 && right(1) == 0 && left(4) == 2 && right(4) == 1 && left(4) + right(4) + 1 == 4, "the margins of a kernel");
+static_assert(lds_bytes(F32_MAX, 1, 4) == LDS_MAX + 16 + 16 && lds_bytes(F64_MAX - 1, 2, 8) <= LDS_MAX + 16 + 16, "the longest rows: raised past 64 KiB (dsp_internal_set_reflect_lds)");
+}  // namespace dsp_reflect
 
 namespace dsp_current {  // dsp_current.hip
 constexpr int CB = 16;   // samples per block (= per checkpoint)

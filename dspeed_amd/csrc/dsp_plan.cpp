@@ -112,6 +112,7 @@ static bool match_spectrum_shape(const PlanCtx& c, const char** why);
 static bool match_sort_shape(const PlanCtx& c, const char** why);
 static bool match_interp_shape(const PlanCtx& c, const char** why);
 static bool match_dense_shape(const PlanCtx& c, const char** why);
+static bool match_reflect_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -125,6 +126,8 @@ static const KernelOnlyRoute kernel_only_routes[] = {
      "DSP_OP_INTERP_UPSAMPLE (interpolating_upsampler) runs on dsp_interp_kernel only"},
     {DSP_ROUTE_DENSE, {DSP_OP_NORMALISE, DSP_OP_DENSE}, match_dense_shape,
      "DSP_OP_NORMALISE / DSP_OP_DENSE (normalisation_layer, dense_layer_*, classification_layer_*) run on dsp_dense_kernel only"},
+    {DSP_ROUTE_REFLECT, {DSP_OP_REFLECTED_CONVOLVE, DSP_OP_REFLECTED_CONVOLVE}, match_reflect_shape,
+     "DSP_OP_REFLECTED_CONVOLVE (reflected_convolve_wf) runs on dsp_reflect_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -719,6 +722,55 @@ static bool match_dense_shape(const PlanCtx& c, const char** why) {
     return true;
 }
 
+// Is the program one of the mirrored-edge FIR kernel's (dsp_reflect.hip)?
+//   LOAD s;  REFLECTED_CONVOLVE of s into a slot of as many samples;  STORE of them
+//   LOAD s;  REFLECTED_CONVOLVE of s;  AVG_CURRENT of the filtered row (a constant length);  STORE of the current [and of the filtered row]
+// Taps, lengths and limits are lower_op's business (every program that holds the op passes there first).  Why not, otherwise: `why`.
+static bool match_reflect_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const int n = c.n_ops;
+    *why = "the program must be exactly LOAD, REFLECTED_CONVOLVE, STORE; or LOAD, REFLECTED_CONVOLVE, AVG_CURRENT, STORE [, STORE]";
+    auto is = [&](int i, int opcode) { return i < n && ops[i].opcode == opcode; };
+    if (n < 3 || !is(0, DSP_OP_LOAD) || !is(1, DSP_OP_REFLECTED_CONVOLVE)) return false;
+    const bool fused = is(2, DSP_OP_AVG_CURRENT);
+    const int first_store = fused ? 3 : 2, n_stores = n - first_store;
+    if (n_stores < 1 || n_stores > (fused ? 2 : 1) || c.n_slots != (fused ? 3 : 2)) return false;
+    for (int i = first_store; i < n; ++i)
+        if (!is(i, DSP_OP_STORE)) return false;
+    const dsp_op &ld = ops[0], &op = ops[1];
+    ReflectArgs& A = ch->reflect;
+    memset(&A, 0, sizeof A);
+    ch->rio_taps = ch->rio_out = ch->rio_cur = -1;
+    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->reflect_src, why,
+                                       "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
+    if (fused) {
+        const dsp_op& ac = ops[2];
+        *why = "the avg_current in the same program reads exactly the filtered row, with a constant length";
+        int binding = -1;
+        int64_t stride = 0;
+        if (ac.src != op.dst || ac.dst == op.dst || ac.dst == ld.dst || !bind_operand(c, ac, 0, binding, stride, A.length) || binding >= 0) return false;
+        A.lag = (int)A.length;  // (0 < lag < n, and the current's slot holds n - lag samples: lower_op's DSP_OP_AVG_CURRENT)
+    }
+    *why = fused ? "the current is stored once, whole, in the loop's type, and the filtered row at most once" : "the filtered row is stored once, whole, in the loop's type";
+    for (int i = first_store; i < n; ++i) {
+        const dsp_op& st = ops[i];
+        const dsp_io_desc& o = c.io[st.io];
+        const bool current = fused && st.src == ops[2].dst;
+        int& slot = current ? ch->rio_cur : ch->rio_out;
+        if ((!current && st.src != op.dst) || slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        slot = st.io;
+        (current ? A.cur_stride : A.out_stride) = o.row_stride;
+    }
+    if (fused && ch->rio_cur < 0) return false;
+    A.n_taps = c.io[op.io].len;
+    A.taps_nan = op.ip[0] & 1;
+    A.wide = dsp_reflect::wide(A.len, A.n_taps, c.esz) ? 1 : 0;
+    ch->rio_taps = op.io;
+    return true;
+}
+
 // Does the program have the shape of the current-branch kernel (dsp_current.hip)?
 //   LOAD s0;  WINDOWER s1 <- s0 (start: constant or float32 column);  AVG_CURRENT s2 <- s1;  UPSAMPLER s3 <- s2;
 //   MOVING_WINDOW_MULTI d <- s3 (3 windows, alternating);  MIN_MAX of d;  STORE_SCALARs of its four registers
@@ -1249,6 +1301,7 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_FFT:
         case DSP_OP_SORT:
         case DSP_OP_INTERP_UPSAMPLE:
+        case DSP_OP_REFLECTED_CONVOLVE:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
         case DSP_OP_NORMALISE: out[0] = o.src; return 1;
         case DSP_OP_DENSE:
@@ -1439,7 +1492,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE: their own layout and limits)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1893,6 +1946,20 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
                 return fail(DSP_ERR_ARG, "dense_layer: the weights (io) are a DSP_IO_TAPS binding of n * m = %d * %d values, row-major", n, m);
             if (o.ip[1] >= 0 && (o.ip[1] >= c.n_io || io[o.ip[1]].kind != DSP_IO_TAPS || io[o.ip[1]].len != m))
                 return fail(DSP_ERR_ARG, "dense_layer: the bias (ip[1]) is a DSP_IO_TAPS binding of m = %d values, or -1", m);
+            break;
+        }
+        case DSP_OP_REFLECTED_CONVOLVE: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src || !need_io(c, o, DSP_IO_TAPS))
+                return fail(DSP_ERR_ARG, "op %d: bad REFLECTED_CONVOLVE (src: the slot of the row; dst: another slot, for the filtered row; io: the kernel, a DSP_IO_TAPS binding)", i);
+            static_assert(dsp_reflect::F32_MAX == DSP_REFLECT_F32_MAX && dsp_reflect::F64_MAX == DSP_REFLECT_F64_MAX, "the limits the text names are the geometry's");
+            const int n = slot_len[o.src], m = io[o.io].len;
+            if (n < 1 || m < 1) return fail(DSP_ERR_ARG, "op %d: REFLECTED_CONVOLVE: the row and the kernel hold at least one sample (%d and %d given)", i, n, m);
+            if (m > n) return fail(DSP_ERR_ARG, "The filter is longer than the input waveform (%d taps, %d samples)", m, n);
+            if (slot_len[o.dst] != n)
+                return fail(DSP_ERR_ARG, "reflected_convolve_wf: the output has the length of the input (len(w_in) = %d, len(w_out) = %d)", n, slot_len[o.dst]);
+            if (!dsp_reflect::fits(n, m, f64 ? 8 : 4))
+                return fail(DSP_ERR_UNSUPPORTED, "reflected_convolve_wf: " DSP_REFLECT_LIMITS_TEXT " (len(w_in) = %d, len(kernel) = %d given): a row and its mirrored margins live in 64 KiB of LDS",
+                            DSP_REFLECT_F32_MAX, DSP_REFLECT_F64_MAX, n, m);
             break;
         }
         case DSP_OP_DWT_HAAR: {

@@ -91,7 +91,7 @@ struct ChainPlan {
     int dio_walk[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1}, dio_walk_thr[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1},
         dio_walk_ts[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1};
     // The ops no interpreter case stands behind: a program that holds one runs on that op's kernel or is refused (the table of these routes
-    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM, DSP_ROUTE_SORT, DSP_ROUTE_INTERP or DSP_ROUTE_DENSE; DSP_ROUTE_VM: the program holds none.
+    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM, DSP_ROUTE_SORT, DSP_ROUTE_INTERP, DSP_ROUTE_DENSE or DSP_ROUTE_REFLECT; DSP_ROUTE_VM: the program holds none.
     dsp_route kernel_only = DSP_ROUTE_VM;
     // the peak finder (dsp_extrema.hip): the one kernel a program with MULTI_EXTREMA runs on
     ExtremaArgs ext{};
@@ -121,6 +121,10 @@ struct ChainPlan {
     DenseArgs dense{};
     RowSource dense_src{};
     int eio_w = -1, eio_b = -1, eio_mean = -1, eio_var = -1, eio_out = -1;
+    // reflected_convolve_wf, with an avg_current of its output or without (dsp_reflect.hip): the one kernel a program with the op runs on
+    ReflectArgs reflect{};
+    RowSource reflect_src{};
+    int rio_taps = -1, rio_out = -1, rio_cur = -1;
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};

@@ -408,6 +408,30 @@ struct DenseArgs {
     int64_t out_stride;
 };
 
+// arguments of the mirrored-edge FIR kernel (dsp_reflect.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> REFLECTED_CONVOLVE -> STORE        LOAD -> REFLECTED_CONVOLVE -> AVG_CURRENT -> STORE [of the filtered row too]
+// The row lives in LDS in the loop's type with its mirrored margins beside it (dsp_kernels.h, dsp_reflect).
+#define DSP_REFLECT_F32_MAX 16384 /* len + n_taps - 1, float32 loop: 64 KiB of LDS a staged row */
+#define DSP_REFLECT_F64_MAX 8192  /* float64 loop */
+#define DSP_REFLECT_LIMITS_TEXT "len(w_in) + len(kernel) - 1 of up to %d in the float32 loop and %d in the float64 loop"
+struct ReflectArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples (n)
+    int32_t n_taps;          // m <= n
+    int32_t taps_nan;        // 1: the caller found a NaN among the taps: every row comes out as NaNs
+    int32_t wide;            // 1: a workgroup of 256 per row, 0: a wavefront per row, four rows to a workgroup
+    int32_t out_vec;         // 1: 16-byte stores of the filtered row (the output rows' start and stride are whole vectors: set per call)
+    int32_t lag;             // the fused avg_current: int(length), 0: none
+    int32_t pad_;
+    double length;           // ... and its divisor, rounded to the loop's type
+    const void* taps;        // n_taps values of the loop's type
+    void* out;               // rows of len samples of the loop's type, or null: the filtered row is not stored (the fused form)
+    int64_t out_stride;
+    void* cur;               // rows of len - lag samples (the fused form) or null
+    int64_t cur_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

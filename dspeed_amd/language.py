@@ -241,6 +241,7 @@ _SIGS = {
     "psd": "wW",  # (w_in, psd_out[len(w_in) // 2 + 1])
     "sort": "wW",  # (w_in, w_out)
     "interpolating_upsampler": "wcW",  # (w_in, mode_in, w_out[m]: any length)
+    "reflected_convolve_wf": "wtW",  # (w_in, kernel[m], w_out)
     # ml.py: (x_in, means, variances, x_out); (x_in, kernel[n, m], [bias[m],] activation_func, x_out[m]); (x_in, kernel[n], [bias,] activation_func, x_out)
     "normalisation_layer": "waaW", "dense_layer_no_bias": "wacW", "dense_layer_with_bias": "waacW",
     "classification_layer_no_bias": "wacS", "classification_layer_with_bias": "waacS",
@@ -351,6 +352,7 @@ _PROCESSOR_FILES = {
 _SPECTRAL_FILES = {"psd": ("fft",), "fft": ("fft",)}
 _ORDER_FILES = {"sort": ("sort",)}  # (processors.ORDER, likewise)
 _RESAMPLING_FILES = {"interpolating_upsampler": ("upsampler",)}  # (processors.RESAMPLING, likewise)
+_SMOOTHING_FILES = {"reflected_convolve_wf": ("convolutions",)}  # (processors.SMOOTHING, likewise; gaussian_filter1d stays refused in recipes)
 _ML_FILES = dict.fromkeys(("normalisation_layer", "dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias",
                            "classification_layer_with_bias"), ("ml",))  # (processors.ML, likewise)
 
@@ -359,7 +361,7 @@ def module_accepted(module, function) -> bool:
     """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
     pre = "dspeed.processors."
     files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ()) + _ORDER_FILES.get(function, ()) + _RESAMPLING_FILES.get(function, ())
-    files += _ML_FILES.get(function, ())
+    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ())
     return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in files)
 
 

@@ -613,5 +613,86 @@ classification_layer_with_bias = HipGUFunc("classification_layer_with_bias", "(n
 # Listed here and not in __all__, like the spectral processors, sort and the resampler: their call records are tests/test_ml_plan_cpu.py's.
 ML = ("normalisation_layer", "dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
 
+
+# --------------------------------------------------------------------------------------------------- smoothing
+def reflect_limit(loop_dtype):
+    """longest staged row of reflected_convolve_wf in a loop, len(w_in) + len(kernel) - 1: the row and its mirrored margins live in 64 KiB of LDS"""
+    return _lib.REFLECT_F64_MAX if np.dtype(loop_dtype) == np.dtype(np.float64) else _lib.REFLECT_F32_MAX
+
+
+def check_reflect(what, n, m, loop_dtype):
+    """what the planner checks, in its words (and the reference's, where it has them).  A kernel longer than the rows is refused for the
+    whole call, even where every row holds a NaN (the reference raises on the rows that get that far)."""
+    if m < 1:
+        raise ValueError(f"{what}: the kernel holds at least one tap ({m} given)")
+    if m > n:
+        raise DSPFatal("The filter is longer than the input waveform")
+    if n + m - 1 > reflect_limit(loop_dtype):
+        raise NotImplementedError(f"{what}: len(w_in) + len(kernel) - 1 of up to {_lib.REFLECT_F32_MAX} in the float32 loop and {_lib.REFLECT_F64_MAX} in the "
+                                  f"float64 loop (len(w_in) = {n}, len(kernel) = {m} given): a row and its mirrored margins live in 64 KiB of LDS")
+
+
+def _reflected_convolve_wf(g, *args):
+    """one C entry for both loops, like psd's (``dsp_reflected_convolve_rows`` takes the loop's type).  The kernel is one constant array for
+    all rows, handled as convolve_wf's; ``w_out`` may be left out: its length is the input's."""
+    what = g.__name__
+    if len(args) not in (2, 3):
+        raise TypeError(f"{what}(w_in, kernel[, w_out]) takes 2 or 3 arguments ({len(args)} given)")
+    w_in, kernel = args[:2]
+    w_out = args[2] if len(args) == 3 else None
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        if isinstance(kernel, DeviceArray):
+            if np.dtype(kernel.dtype) != np.dtype(c.ft) or len(kernel.shape) != 1:
+                raise TypeError(f"{what}: a kernel on the device is one row of {np.dtype(c.ft).name} values in the {np.dtype(c.ft).name} loop")
+            kd = kernel
+        else:
+            k = np.ascontiguousarray(kernel, dtype=c.ft)
+            if k.ndim != 1:
+                raise NotImplementedError("per-waveform kernels are not supported")
+            kd = DeviceArray.from_numpy(k) if k.size else None
+            if kd is not None:
+                c.st.keep.append(kd)
+        m = int(kd.shape[-1]) if kd is not None else 0
+        if w_out is not None:
+            if not isinstance(w_out, (np.ndarray, DeviceArray)):
+                raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+            p = int(w_out.shape[-1]) if len(w_out.shape) else 0
+            if p != c.n:
+                raise ValueError(f"{what}: the output has the length of the input (len(w_in) = {c.n}, len(w_out) = {p})")
+        check_reflect(what, c.n, m, c.ft)
+        ptr, stride = c.out(w_out, "n")
+        run(getattr(_lib.lib(), "dsp_reflected_convolve_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, kd.ptr, m, ptr, stride)
+        c.st.finish()
+        return c.results[0]
+
+
+reflected_convolve_wf = HipGUFunc("reflected_convolve_wf", "(n),(m),(p)", ["fff", "ddd"], _reflected_convolve_wf,
+                                  "FIR filter with mirrored edges: np.convolve of the row padded by reflection, cut back to len(w_in) samples; float64 "
+                                  "accumulators; a row or a kernel with a NaN: NaNs (reference processors/convolutions.py:122-182)")
+
+
+def _gaussian_filter1d(g, sigma, truncate, weights):
+    """Gaussian weights exp(-x^2 / (2 sigma^2)) over x = -lw .. lw, lw = int(truncate * sigma + 0.5), normalised to sum 1: evaluated in
+    float64 and rounded once into the array (the reference's generator runs in object mode on Python floats,
+    processors/gaussian_filter1d.py:56-82).  Stricter than the reference in two places: it fails in NumPy's broadcast when the array has
+    another length than 2 lw + 1, and divides by zero for sigma == 0."""
+    sigma, truncate = _scalar_for(weights, sigma), _scalar_for(weights, truncate)
+    if not sigma > 0:
+        raise ValueError(f"gaussian_filter1d: sigma must be positive ({sigma} given)")
+    lw = int(truncate * sigma + 0.5)
+    if len(weights) != 2 * lw + 1:
+        raise ValueError(f"gaussian_filter1d: weights holds 2 * int(truncate * sigma + 0.5) + 1 = {2 * lw + 1} values ({len(weights)} given)")
+    x = np.arange(-lw, lw + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x**2)
+    weights[:] = phi / phi.sum()
+    return weights
+
+
+gaussian_filter1d = HipGUFunc("gaussian_filter1d", "(),(),(n)", ["fff", "ddd"], _gaussian_filter1d,
+                              "Gaussian kernel generator for reflected_convolve_wf, host, once (reference processors/gaussian_filter1d.py:56-82)")
+
+# Listed here and not in __all__, like the spectral processors and sort: their call records are tests/test_reflect_plan_cpu.py's.
+SMOOTHING = ("reflected_convolve_wf", "gaussian_filter1d")
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

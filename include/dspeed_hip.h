@@ -295,6 +295,16 @@ typedef struct dsp_scalar_arg {
                                  *   LOAD, [NORMALISE,] DENSE, STORE of dst
                                  *   LOAD, [NORMALISE,] DENSE, STORE_SCALAR of dst
                                  *   LOAD, NORMALISE, STORE */
+#define DSP_OP_REFLECTED_CONVOLVE 45 /* convolutions.py:122-182 reflected_convolve_wf: dst (n samples, another slot than src) <- src (n samples) convolved
+                                 * with the m <= n taps of io (a DSP_IO_TAPS binding of the loop's type), the row continued past both ends by its mirror
+                                 * image, the edge sample not repeated: dst[i] = sum_k taps[k] * src[r(i + (m-1)/2 - k)], r(t) = -t below 0,
+                                 * 2 (n - 1) - t above n - 1.  float64 accumulators, the taps in ascending order, one rounding at the store.  ip[0] & 1:
+                                 * the caller found a NaN among the taps: every row NaN; a row with a NaN: NaN.  n + m - 1 up to 16384 in the float32
+                                 * loop (float32 / int16 / uint16 rows) and 8192 in the float64 loop (float64 rows).  The waveform interpreter has no
+                                 * such op: it runs on dsp_reflect_kernel only, in a program of exactly
+                                 *   LOAD, REFLECTED_CONVOLVE, STORE of dst;  or
+                                 *   LOAD, REFLECTED_CONVOLVE, AVG_CURRENT of dst (a constant length), STORE of the current [, STORE of dst]
+                                 * where the filtered row goes to memory only if it is stored */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -573,6 +583,14 @@ int dsp_dense_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, i
  * wf_len values of the loop's type on the device.  One entry for both loops. */
 int dsp_normalisation_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype,
                            const void* means_dev, const void* variances_dev, void* out, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(m),(n)" reflected_convolve_wf (convolutions.py:122-182; DSP_OP_REFLECTED_CONVOLVE): every row convolved with the n_taps <= wf_len values
+ * at taps_dev (the loop's type, on the device; looked at once per call: a NaN among them makes every row NaN), mirrored edges, wf_len outputs.
+ * One entry for both loops, like dsp_psd: compute_dtype names the loop (DSP_F32: float32 / int16 / uint16 rows, float taps and output; DSP_F64:
+ * float64 rows, double taps and output).  wf_len + n_taps - 1 up to 16384 (DSP_F32) or 8192 (DSP_F64); n_taps > wf_len is an argument
+ * error with the reference's text.  16-byte stores where out and out_stride are whole vectors. */
+int dsp_reflected_convolve_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype,
+                                const void* taps_dev, int32_t n_taps, void* out, int64_t out_stride, void* stream, int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
