@@ -464,10 +464,11 @@ class _Stager:
     def has(self, st) -> bool:
         return any(st is x for x in self.steps)
 
-    def steps_of(self, fn):
-        """the steps of processor ``fn`` that are still in the program when their turn comes (an earlier one's stage may have taken them)"""
+    def steps_of(self, fn, only=None):
+        """the steps of processor ``fn`` that are still in the program when their turn comes (an earlier one's stage may have taken them, or
+        a reader of theirs that was staged first: ``_stage_producers``); ``only``: that step alone"""
         for st in list(self.steps):
-            if st[0] == fn and self.has(st):
+            if st[0] == fn and self.has(st) and (only is None or st is only):
                 yield st
 
     def replace(self, old, new):
@@ -608,6 +609,7 @@ def _fir_input_as_rows(cx: _Stager, base):
     """The FIR kernels read rows from HBM.  Returns what joins the filter's own stage ahead of it: nothing for a chain input or what a
     stage wrote (made here, if need be, by a small program that writes the filter's input to HBM), the bl_subtract of an input that is done
     while staging; None if the input cannot become rows."""
+    _stage_producers(cx, base)
     if cx.row_input(base):
         return []
     pst = cx.producer_of(base)
@@ -752,14 +754,14 @@ def _stage_row_reductions(cx: _Stager):
         cx.stage(group, [o for g in group for o in _outputs_of(g)], f"per-event values of {v.name} off its rows")
 
 
-def _stage_multi_extrema(cx: _Stager):
+def _stage_multi_extrema(cx: _Stager, only=None):
     """``get_multi_local_extrema`` runs on dsp_extrema.hip and nowhere else (the interpreter has no such op), on rows in HBM: this stage is
     mandatory.  Rows that are chain inputs or a stage's waveform are read as they are; any other source is written to HBM first by a small
     program of its own, as a long filter's input is.  Per-event operands: constants, float32 columns of the input table, fit and stage
     results; what the program would compute off rows in HBM moves ahead of it (``move_ahead``); expressions of those and columns of other
     types go through a small program of their own (``stage_expression``)."""
     fn = _MULTI_EXTREMA
-    for st in cx.steps_of(fn):
+    for st in cx.steps_of(fn, only):
         args, key = list(st[1]), st[2]
         src, direction, lists, counts = args[0], args[3], args[6:8], args[8:10]
         if not _is_integral(direction):
@@ -788,6 +790,8 @@ def _operand_in_memory(cx: _Stager, a, fn, key, written_first=False):
         if not (_is_number(a) or isinstance(a, Quantity)):
             raise NotImplementedError(f"{fn} ({key}): operand {a!r} is neither a number nor a per-event value")
         return a
+    for leaf in _leaves(a, []):
+        _stage_producers(cx, leaf)
     for leaf in _leaves(a, []) if written_first else ():
         pst = cx.producer_of(leaf) if isinstance(leaf, Var) and leaf.kind == "scalar" and not cx.plain_scalar(leaf) else None
         if pst is None or any(isinstance(x, Var) and cx.row_input(x) for x in _inputs_of(pst)):
@@ -806,11 +810,33 @@ def _operand_in_memory(cx: _Stager, a, fn, key, written_first=False):
     return a
 
 
+def _folded_normalisation(cx: _Stager, st) -> bool:
+    """a normalisation that only dense or classification layers read, and the recipe does not ask for: it runs inside their launches"""
+    out = st[1][3]
+    return out.name not in cx.out_names and all(u[0] in _DENSE_LAYERS and u[1][0] is out for u in cx.users_of(out))
+
+
+def _stage_producers(cx: _Stager, v):
+    """Stages are made in the order the data flows.  Whatever ``v`` is computed from that runs on a kernel of its own is staged here, by its
+    own family, before a reader of ``v`` is: the first such processor among ``v``'s ancestors has none above it, its stage takes it out of
+    the program and makes its result rows in memory, where ``ancestors`` ends -- so every one of them is staged once, a producer ahead of
+    its readers, and what is then left between them and ``v`` is work of the interpreter.  (A folded normalisation goes with its layer.)"""
+    while True:
+        own = next((a for a in cx.ancestors(v) if a[0] in _OWN_KERNEL and not (a[0] == _NORMALISE and _folded_normalisation(cx, a))), None)
+        if own is None:
+            return
+        _FAMILY_OF[own[0]](cx, only=own)
+        if cx.has(own):
+            raise NotImplementedError(f"{own[0]} ({own[2]}): cannot be staged ahead of what reads '{v.name}'")
+
+
 def _rows_in_memory(cx: _Stager, src, fn, key):
-    """the source of a kernel that reads rows in HBM: a chain input or a stage's waveform as it is, anything else written there first"""
+    """the source of a kernel that reads rows in HBM: a chain input or a stage's waveform as it is, anything else written there first --
+    behind the stages of the processors it comes from that own a kernel (``_stage_producers``)"""
     base = _base_of(src)
     if base is None:
         raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+    _stage_producers(cx, base)
     if not cx.row_input(base):
         anc = cx.ancestors(base)
         if not anc:
@@ -818,11 +844,11 @@ def _rows_in_memory(cx: _Stager, src, fn, key):
         cx.stage(anc, [], f"{base.name} -> HBM", wf=base, drop=[])
 
 
-def _stage_histogram(cx: _Stager):
+def _stage_histogram(cx: _Stager, only=None):
     """``histogram`` and ``histogram_stats`` run on dsp_hist.hip and nowhere else, on rows in HBM: mandatory stages, like the peak finder's.
     A ``histogram_stats`` that reads exactly a histogram's weights and borders joins its launch; weights and borders are then written only
     if something else reads them or the recipe asks for them.  Any other ``histogram_stats`` reads weights and edges as rows in memory."""
-    for st in cx.steps_of(_HISTOGRAM):
+    for st in cx.steps_of(_HISTOGRAM, only):
         args, key = list(st[1]), st[2]
         weights, borders = args[1:3]
         if not all(isinstance(v, Var) and v.kind == "wf" and v.length for v in (weights, borders)):
@@ -844,7 +870,7 @@ def _stage_histogram(cx: _Stager):
         rows_wanted = any(v.name in cx.out_names or [u for u in cx.users_of(v) if not any(u is g for g in group)] for v in (weights, borders))
         cx.stage(group, scalars, f"{_HISTOGRAM} {key}" + (f" + {_HISTOGRAM_STATS} {stats[2]} in one launch" if stats is not None else "") + " on rows",
                  wfs=[weights, borders] if rows_wanted or stats is None else [], rows_first=True)
-    for st in cx.steps_of(_HISTOGRAM_STATS):
+    for st in cx.steps_of(_HISTOGRAM_STATS, only):
         args, key = list(st[1]), st[2]
         for a in args[:2]:
             if not (isinstance(a, Var) and a.kind == "wf" and a.length):
@@ -858,12 +884,12 @@ def _stage_histogram(cx: _Stager):
         cx.stage([step], args[2:5], f"{_HISTOGRAM_STATS} {key} on rows")
 
 
-def _stage_thresholds(cx: _Stager):
+def _stage_thresholds(cx: _Stager, only=None):
     """``multi_time_point_thresh`` and ``time_over_threshold`` run on dsp_thresh.hip and nowhere else, on rows in HBM: mandatory stages, like
     the peak finder's.  Polarity and mode are constants, checked here for every row; t_start and time_over_threshold's threshold are
     per-event operands (``_operand_in_memory``); the thresholds are one constant list or rows in memory -- a two-dimensional input column
     or a stage's waveform --, not something the program would compute per event."""
-    for st in cx.steps_of(_MULTI_TPT):
+    for st in cx.steps_of(_MULTI_TPT, only):
         fn, args, key = st[0], list(st[1]), st[2]
         src, thr, _t_start, polarity, mode, t_out = args
         if isinstance(polarity, Var) and polarity.kind == "const":
@@ -890,7 +916,7 @@ def _stage_thresholds(cx: _Stager):
         args[3] = float(polarity)
         step = cx.replace(st, (fn, args, key))
         cx.stage([step], [], f"{fn} {key} on rows", wfs=[t_out], rows_first=True)
-    for st in cx.steps_of(_TIME_OVER):
+    for st in cx.steps_of(_TIME_OVER, only):
         fn, args, key = st[0], list(st[1]), st[2]
         if not isinstance(args[2], Var):
             raise ProcessingChainError(f"{fn} ({key}): name the output")
@@ -900,14 +926,14 @@ def _stage_thresholds(cx: _Stager):
         cx.stage([step], [args[2]], f"{fn} {key} on rows")
 
 
-def _stage_spectrum(cx: _Stager):
+def _stage_spectrum(cx: _Stager, only=None):
     """``psd`` runs on dsp_spectrum.hip and nowhere else, on rows in HBM: a mandatory stage, like the peak finder's.  The source is a chain
     input, a stage's waveform, a slice of either, or a waveform the program computes, written to HBM first; the spectrum is an ordinary
     waveform variable of the program."""
     from .processors import check_spectrum_length
 
     fn = _PSD
-    for st in cx.steps_of(fn):
+    for st in cx.steps_of(fn, only):
         args, key = list(st[1]), st[2]
         src, out = args
         if _base_of(src) is None:
@@ -922,14 +948,14 @@ def _stage_spectrum(cx: _Stager):
         cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
 
 
-def _stage_sort(cx: _Stager):
+def _stage_sort(cx: _Stager, only=None):
     """``sort`` runs on dsp_sort.hip and nowhere else, on rows in HBM: a mandatory stage, like the spectrum's.  The source is a chain input,
     a stage's waveform, a slice of either, or a waveform the program computes, written to HBM first; the sorted row is an ordinary waveform
     variable of the program, with the source's length and grid."""
     from .processors import check_sort_length
 
     fn = _SORT
-    for st in cx.steps_of(fn):
+    for st in cx.steps_of(fn, only):
         args, key = list(st[1]), st[2]
         src, out = args
         if _base_of(src) is None:
@@ -943,7 +969,7 @@ def _stage_sort(cx: _Stager):
         cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
 
 
-def _stage_interp_upsampler(cx: _Stager):
+def _stage_interp_upsampler(cx: _Stager, only=None):
     """``interpolating_upsampler`` runs on dsp_interp.hip and nowhere else, on rows in HBM: a mandatory stage, like sort's.  The source is
     a chain input, a stage's waveform, a slice of either, or a waveform the program computes, written to HBM first; the resampled row is an
     ordinary waveform variable of the program, declared with its length (and ``period=``: the finer grid).  The mode is a constant of the
@@ -951,7 +977,7 @@ def _stage_interp_upsampler(cx: _Stager):
     from .processors import check_interp
 
     fn = _INTERP
-    for st in cx.steps_of(fn):
+    for st in cx.steps_of(fn, only):
         args, key = list(st[1]), st[2]
         src, mode, out = args
         if _base_of(src) is None:
@@ -965,7 +991,7 @@ def _stage_interp_upsampler(cx: _Stager):
         cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
 
 
-def _stage_reflected_convolve(cx: _Stager):
+def _stage_reflected_convolve(cx: _Stager, only=None):
     """``reflected_convolve_wf`` runs on dsp_reflect.hip and nowhere else, on rows in HBM: a mandatory stage, like sort's, made ahead of the
     others (the histogram and the peak finder of the SiPM recipes read what it feeds).  The source is a chain input, a stage's waveform, a
     slice of either, or a waveform the program computes, written to HBM first; the kernel is constant taps in any form convolve_wf's takes;
@@ -975,7 +1001,7 @@ def _stage_reflected_convolve(cx: _Stager):
     from .processors import check_reflect
 
     fn = _REFLECT
-    for st in cx.steps_of(fn):
+    for st in cx.steps_of(fn, only):
         args, key = list(st[1]), st[2]
         src, taps, out = args
         if _base_of(src) is None:
@@ -1002,7 +1028,7 @@ def _stage_reflected_convolve(cx: _Stager):
         cx.stage([st, cur], [], f"{fn} {key} + avg_current {cur[2]} in one launch on rows", wfs=([out] if row_wanted else []) + [cur[1][2]], rows_first=True)
 
 
-def _stage_ml_layers(cx: _Stager):
+def _stage_ml_layers(cx: _Stager, only=None):
     """The neural-network layers (ml.py) run on dsp_dense.hip and nowhere else, on rows in HBM: mandatory stages, like sort's.  Each dense or
     classification layer is a launch on rows in memory -- a chain input, a stage's waveform (the layer before it), or a waveform the program
     computes, written to HBM first.  A ``normalisation_layer`` whose result only dense or classification layers read, and which is not an
@@ -1010,12 +1036,12 @@ def _stage_ml_layers(cx: _Stager):
     The activation is a constant of the kernel."""
     from .processors import check_dense
 
-    def folded(st):  # a normalisation that only layers read
-        out = st[1][3]
-        users = cx.users_of(out)
-        return bool(users) and out.name not in cx.out_names and all(u[0] in _DENSE_LAYERS and u[1][0] is out for u in users)
+    def folded(st):  # (a normalisation whose layers are all staged already has no reader left: it ran with them)
+        return _folded_normalisation(cx, st)
 
-    for st in [x for x in cx.steps if x[0] in _ML]:
+    for st in [x for x in cx.steps if x[0] in _ML and (only is None or x is only)]:
+        if not cx.has(st):
+            continue
         fn, args, key = st[0], list(st[1]), st[2]
         src, out = args[0], args[-1]
         if _base_of(src) is None:
@@ -1045,6 +1071,12 @@ def _stage_ml_layers(cx: _Stager):
             cx.stage(group, [out], what, drop=[st])
         else:
             cx.stage(group, [], what, wfs=[out], rows_first=True, drop=[st])
+
+
+#: the family that stages each processor with a kernel of its own (``_stage_producers`` asks it for one step)
+_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
+              _MULTI_EXTREMA: _stage_multi_extrema, _MULTI_TPT: _stage_thresholds, _TIME_OVER: _stage_thresholds, _PSD: _stage_spectrum,
+              _SORT: _stage_sort, _INTERP: _stage_interp_upsampler, **dict.fromkeys(_ML, _stage_ml_layers)}
 
 
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
