@@ -34,7 +34,7 @@ ARG_CONST, ARG_INPUT, ARG_REG = range(3)
  OP_ASYM_TRAP, OP_PICKOFF, OP_TIME_POINT_THRESH, OP_MIN_MAX, OP_DWT_HAAR, OP_CONVOLVE, OP_COPY, OP_TRAP_PICKOFF, OP_AMAX,
  OP_SCALAR_AFFINE, OP_MEAN_BELOW, OP_CONVOLVE_AMAX, OP_WINDOWER, OP_AVG_CURRENT, OP_TRAP_WINDOW_PICKOFF, OP_TRAP_REDUCE, OP_UPSAMPLER, OP_MOVING_WINDOW_MULTI, OP_LINEAR_SLOPE_FIT,
  OP_SCALAR_CONVERT, OP_SCALAR_DIV, OP_INTERP_TIME_POINT_THRESH, OP_MIN_MAX_NORM, OP_ELEMENTWISE, OP_SCALAR_FUNC, OP_MULTI_EXTREMA, OP_HISTOGRAM,
- OP_HISTOGRAM_STATS, OP_MULTI_TIME_POINT_THRESH, OP_TIME_OVER_THRESHOLD, OP_PSD, OP_FFT, OP_SORT, OP_INTERP_UPSAMPLE, OP_NORMALISE, OP_DENSE, OP_REFLECTED_CONVOLVE) = range(1, 46)
+ OP_HISTOGRAM_STATS, OP_MULTI_TIME_POINT_THRESH, OP_TIME_OVER_THRESHOLD, OP_PSD, OP_FFT, OP_SORT, OP_INTERP_UPSAMPLE, OP_NORMALISE, OP_DENSE, OP_REFLECTED_CONVOLVE, OP_RC_CR2, OP_BI_LEVEL_ZERO_CROSSING) = range(1, 48)
 (FN_ADD, FN_SUB, FN_MUL, FN_DIV, FN_LT, FN_LE, FN_GT, FN_GE, FN_EQ, FN_NE, FN_WHERE, FN_ISNAN, FN_ISFINITE, FN_NEG, FN_COPY, FN_FLOORDIV,
  FN_IADD, FN_ISUB, FN_IMUL, FN_IFLOORDIV, FN_ICAST, FN_LOR, FN_LAND, FN_RINT, FN_FLOOR, FN_CEIL, FN_TRUNC) = range(27)
 
@@ -156,6 +156,8 @@ SIG = {
         "dsp_dense_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, vp, i32, vp, i32, i64, vp, pi64],
         "dsp_normalisation_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, vp, vp, i64, vp, pi64],
         "dsp_reflected_convolve_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, vp, i64, vp, pi64],
+        "dsp_rc_cr2_rows": [vp, C.c_int, i64, i32, i64, C.c_int, C.c_double, vp, i64, vp, pi64],
+        "dsp_bi_level_zero_crossing_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, C.c_double, vp, C.c_double, vp, C.c_double, vp, C.c_double, vp, vp, vp, i32, i64, vp, pi64],
         "dsp_synth_waveforms": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_synth_pulses": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_stream_read": [vp, i64, vp, vp],

@@ -377,6 +377,8 @@ class _ChunkWorker:
         # get_multi_local_extrema) leave as VectorOfVectors: padded rows + their lengths, from the input table or from the results
         lens = {k: np.asarray(columns[src] if src in columns else out[src]) for k, src in chain.vector_lens.items()
                 if k in out and (src in columns or src in out)}
+        # (a count may go on past its lists' length -- bi_level_zero_crossing_time_points' does: the lists hold what was declared)
+        lens = {k: np.minimum(v, out[k].shape[1]) if out[k].ndim == 2 else v for k, v in lens.items()}
         for name in getattr(chain, "hidden_outputs", ()):
             out.pop(name, None)
         return out, lens

@@ -35,11 +35,12 @@ _MULTI_EXTREMA = "get_multi_local_extrema"
 _HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
 _MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
 _PSD, _SORT, _INTERP, _REFLECT = "psd", "sort", "interpolating_upsampler", "reflected_convolve_wf"
+_RC_CR2, _BI_LEVEL = "rc_cr2", "bi_level_zero_crossing_time_points"
 _NORMALISE = "normalisation_layer"
 _DENSE_LAYERS = ("dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
 _ML = (_NORMALISE,) + _DENSE_LAYERS
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT) + _ML  # processors that run as stages ahead of the program, on kernels of their own
-_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT)
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL) + _ML  # processors that run as stages ahead of the program, on kernels of their own
+_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT, _RC_CR2)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
 
@@ -142,6 +143,12 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         for a in args[8:10]:
             if isinstance(a, Var):
                 a.out_dtype = np.dtype(np.uint32)
+    if function == _BI_LEVEL:
+        # its times are sample indices of the input, like the peak finder's lists; its count is uint32 (the gufunc's "I")
+        if isinstance(args[7], Var) and _time_unit_ns(args[7].unit) is not None and _grid_of(args[0]) is not None:
+            args[7].is_coord, args[7].grid = True, _grid_of(args[0])
+        if isinstance(args[5], Var):
+            args[5].out_dtype = np.dtype(np.uint32)
     if function == _MULTI_TPT:
         # its thresholds are one constant list, or a list per event read from rows in memory; its times are sample indices of the input:
         # with a time unit they are coordinates on its grid, written in that unit like the peak finder's lists
@@ -1028,6 +1035,78 @@ def _stage_reflected_convolve(cx: _Stager, only=None):
         cx.stage([st, cur], [], f"{fn} {key} + avg_current {cur[2]} in one launch on rows", wfs=([out] if row_wanted else []) + [cur[1][2]], rows_first=True)
 
 
+def _pileup_rows(cx: _Stager, src, fn, key, reader):
+    """The rows the pile-up kernel reads: a chain input or a stage's waveform as it is (behind the stages of what it comes from).  A
+    ``bl_subtract`` of a chain input by a per-event value in memory, whose result only ``reader`` reads and the recipe does not ask for, joins
+    the launch -- one float subtraction as the rows are read, as ``_fir_input_as_rows`` has it for the long filters: returned, for the
+    stage's group.  Anything else is written to memory first."""
+    base = _base_of(src)
+    if base is None:
+        raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+    _stage_producers(cx, base)
+    pst = cx.producer_of(base) if not cx.row_input(base) else None
+    if (pst is not None and src is base and pst[0] == "bl_subtract" and isinstance(pst[1][0], Var) and cx.row_input(pst[1][0])
+            and base.name not in cx.out_names and all(u is reader for u in cx.users_of(base))
+            and (_is_number(pst[1][1]) or all(cx.plain_scalar(leaf) for leaf in _leaves(pst[1][1], [])))):
+        bargs = list(pst[1])
+        bargs[1] = _operand_in_memory(cx, bargs[1], "bl_subtract", pst[2])
+        return [cx.replace(pst, ("bl_subtract", bargs, pst[2]))]
+    _rows_in_memory(cx, src, fn, key)
+    return []
+
+
+def _stage_pileup(cx: _Stager, only=None):
+    """``rc_cr2`` and ``bi_level_zero_crossing_time_points`` run on dsp_pileup.hip and nowhere else, on rows in HBM: mandatory stages, like
+    the threshold kernel's.  A walk that reads exactly an ``rc_cr2``'s output takes the filter into its launch; the filtered waveform is then
+    written only if something else reads it or the recipe asks for it (``_stage_histogram``'s rule for weights and borders).  t_tau is a
+    constant -- the filter's coefficients are formed on the host --; thresholds, gate and start are per-event operands
+    (``_operand_in_memory``); the lists are declared with their length, ``name(20, vector_len=n_crossings)``."""
+    from .processors import check_bi_level_lists, check_rc_cr2
+
+    def filter_checked(st):
+        fn, (src, tau, out), key = st
+        if isinstance(tau, Var) and tau.kind == "const":
+            tau = tau.const
+        if not (_is_number(tau) or isinstance(tau, Quantity)):
+            raise NotImplementedError(f"{fn} ({key}): t_tau is a constant of the kernel, not a per-event value: its coefficients are formed on the host")
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        if not (isinstance(out, Var) and out.kind == "wf" and out.length):
+            raise ProcessingChainError(f"{fn} ({key}): the output is a waveform variable")
+        check_rc_cr2(f"{fn} ({key})", src.length, out.length)
+        return src, out
+
+    for st in cx.steps_of(_BI_LEVEL, only):
+        fn, args, key = st[0], list(st[1]), st[2]
+        src, gate, count, polarity, times = args[0], args[3], args[5], args[6], args[7]
+        if not all(isinstance(v, Var) and v.kind == "wf" and v.length for v in (polarity, times)) or not isinstance(count, Var):
+            raise ProcessingChainError(f"{fn} ({key}): declare the lists as name(length, vector_len=<the count>) and name the count")
+        check_bi_level_lists(f"{fn} ({key})", polarity.length, times.length)
+        if isinstance(gate, Var) and gate.kind == "const":
+            gate = gate.const
+        if _is_number(gate) and not np.isfinite(float(gate)):
+            raise ValueError(f"{fn} ({key}): gate_time_in is a finite number of samples")
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        flt = cx.producer_of(src) if isinstance(src, Var) else None
+        flt = flt if flt is not None and flt[0] == _RC_CR2 and cx.has(flt) else None
+        rows, out = filter_checked(flt) if flt is not None else (src, None)
+        pre = _pileup_rows(cx, rows, fn if flt is None else _RC_CR2, key if flt is None else flt[2], st if flt is None else flt)
+        for k in (1, 2, 3, 4):
+            args[k] = _operand_in_memory(cx, args[k], fn, key, written_first=True)
+        step = cx.replace(st, (fn, args, key))
+        if flt is None:
+            cx.stage(pre + [step], [count], f"{fn} {key} on rows", wfs=[polarity, times], rows_first=True)
+            continue
+        row_wanted = out.name in cx.out_names or any(u is not step for u in cx.users_of(out))
+        cx.stage(pre + [flt, step], [count], f"{_RC_CR2} {flt[2]} + {fn} {key} in one launch on rows", wfs=([out] if row_wanted else []) + [polarity, times],
+                 rows_first=True)
+    for st in cx.steps_of(_RC_CR2, only):
+        src, out = filter_checked(st)
+        pre = _pileup_rows(cx, src, st[0], st[2], st)
+        cx.stage(pre + [st], [], f"{st[0]} {st[2]} on rows", wfs=[out], rows_first=True)
+
+
 def _stage_ml_layers(cx: _Stager, only=None):
     """The neural-network layers (ml.py) run on dsp_dense.hip and nowhere else, on rows in HBM: mandatory stages, like sort's.  Each dense or
     classification layer is a launch on rows in memory -- a chain input, a stage's waveform (the layer before it), or a waveform the program
@@ -1074,7 +1153,7 @@ def _stage_ml_layers(cx: _Stager, only=None):
 
 
 #: the family that stages each processor with a kernel of its own (``_stage_producers`` asks it for one step)
-_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
+_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _RC_CR2: _stage_pileup, _BI_LEVEL: _stage_pileup, _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
               _MULTI_EXTREMA: _stage_multi_extrema, _MULTI_TPT: _stage_thresholds, _TIME_OVER: _stage_thresholds, _PSD: _stage_spectrum,
               _SORT: _stage_sort, _INTERP: _stage_interp_upsampler, **dict.fromkeys(_ML, _stage_ml_layers)}
 
@@ -1104,6 +1183,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_histogram(cx)  # (ahead of the peak finder: its thresholds may be arithmetic of these results, "3*fwhm")
     _stage_multi_extrema(cx)
     _stage_thresholds(cx)
+    _stage_pileup(cx)
     _stage_spectrum(cx)
     _stage_sort(cx)
     _stage_interp_upsampler(cx)
@@ -1753,6 +1833,24 @@ class _Emitter:
         self.p.add_op(_lib.OP_REFLECTED_CONVOLVE, dst=out.slot, src=src.slot, io=self.taps_io(taps), ip=(int(np.isnan(taps.const).any()),))
         self.release(src, si)
 
+    def rc_cr2(self, si, fn, args, what):
+        """LOAD, [BL_SUBTRACT,] RC_CR2 of the pile-up stage; the walk of the filtered row may follow, then the stores"""
+        src = self.ensure_loaded(args[0], si)
+        out = self.out_wf(args[2], src.length, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_RC_CR2, dst=out.slot, src=src.slot, sp=(self.scalar_operand(args[1], args, what=what),))
+        self.release(src, si)
+
+    def bi_level_zero_crossing(self, si, fn, args, what):
+        """BI_LEVEL_ZERO_CROSSING on the rows of the stage, or on the filtered row of the same program; the stores of its lists and count follow"""
+        src = self.ensure_loaded(args[0], si)
+        sp = tuple(self.scalar_operand(args[k], args, what=what) for k in (1, 2, 3, 4))
+        polarity, times = self.out_wf(args[6], None, fn), self.out_wf(args[7], None, fn)
+        polarity.slot, times.slot = self.new_slot(polarity.length), self.new_slot(times.length)
+        first = self.out_row(args[5:6], f"{what}: the count must be a variable name")
+        self.p.add_op(_lib.OP_BI_LEVEL_ZERO_CROSSING, dst=polarity.slot, src=src.slot, ip=(times.slot, first), sp=sp)
+        self.release(src, si)
+
     def taps_io(self, v):
         """the binding of a constant array, made at its first use"""
         if v.io is None:
@@ -1963,7 +2061,8 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          "moving_window_multi": _Emitter.moving_window_multi, "discrete_wavelet_transform": _Emitter.wavelet,
          "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
          _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
-         _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler, _REFLECT: _Emitter.reflected_convolve,
+         _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler, _REFLECT: _Emitter.reflected_convolve, _RC_CR2: _Emitter.rc_cr2,
+         _BI_LEVEL: _Emitter.bi_level_zero_crossing,
          _NORMALISE: _Emitter.normalisation_layer, **dict.fromkeys(_DENSE_LAYERS, _Emitter.dense_layer)}
 
 

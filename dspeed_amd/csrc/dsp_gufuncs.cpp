@@ -489,6 +489,33 @@ int dsp_reflected_convolve_rows(ROWS, int compute_dtype, const void* taps_dev, i
         return DSP_OK;
     });
 }
+// rc_cr2 and bi_level_zero_crossing_time_points: one entry each for both loops, like dsp_sort_rows
+int dsp_rc_cr2_rows(ROWS, int compute_dtype, double t_tau, void* out, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "rc_cr2: compute_dtype is DSP_F32 or DSP_F64");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        const int s_in = m.load(IN), s_out = m.add_slot(wf_len);
+        m.op(DSP_OP_RC_CR2, s_out, s_in, 0, {}, {{nullptr, t_tau}});
+        m.store(s_out, {out, wf_len, out_stride});
+        return DSP_OK;
+    });
+}
+int dsp_bi_level_zero_crossing_rows(ROWS, int compute_dtype, const void* a_pos_threshold_dev, double a_pos_threshold, const void* a_neg_threshold_dev,
+                                    double a_neg_threshold, const void* gate_time_dev, double gate_time, const void* t_start_dev, double t_start,
+                                    uint32_t* n_crossings_out, void* polarity_out, void* t_trig_times_out, int32_t out_len, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64)
+        return dsp_fail(DSP_ERR_ARG, "bi_level_zero_crossing_time_points: compute_dtype is DSP_F32 or DSP_F64");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (out_len < 1) return dsp_fail(DSP_ERR_ARG, "bi_level_zero_crossing_time_points: polarity_out and t_trig_times_out hold at least one entry");
+        m.n_sregs = 1;
+        const int s_in = m.load(IN), s_pol = m.add_slot(out_len), s_time = m.add_slot(out_len);
+        m.op(DSP_OP_BI_LEVEL_ZERO_CROSSING, s_pol, s_in, 0, {s_time, 0},
+             {{a_pos_threshold_dev, a_pos_threshold}, {a_neg_threshold_dev, a_neg_threshold}, {gate_time_dev, gate_time}, {t_start_dev, t_start}});
+        m.store(s_pol, {polarity_out, out_len, out_stride});
+        m.store(s_time, {t_trig_times_out, out_len, out_stride});
+        m.store_scalar(0, n_crossings_out, DSP_U32);
+        return DSP_OK;
+    });
+}
 #undef ROWS
 #undef IN
 #undef TAIL

@@ -686,6 +686,20 @@ static int launch_reflect(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, voi
     return launch_on_rows(ch, n_wf, stream, A, ch->reflect_src, dsp_internal_launch_reflect, "reflect kernel launch");
 }
 
+static int launch_pileup(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    PileupArgs A = ch->pileup;
+    A.wf = io_ptrs[ch->pileup_src.io];
+    for (int k = 0; k < 4; ++k) A.par[k] = at(ch->lio_par[k]);
+    A.out = at(ch->lio_out);
+    A.sub = at(ch->lio_sub);
+    for (int k = 0; k < 2; ++k) A.list[k] = at(ch->lio_list[k]);
+    A.n_out = (uint32_t*)at(ch->lio_n);
+    // 16-byte stores: launch_interp's rule (the plan vouches for the stride, this call's pointer for the start)
+    A.out_vec = A.out && (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
+    return launch_on_rows(ch, n_wf, stream, A, ch->pileup_src, dsp_internal_launch_pileup, "pile-up kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -874,6 +888,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_INTERP)) return launch_interp(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_DENSE)) return launch_dense(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_REFLECT)) return launch_reflect(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_PILEUP)) return launch_pileup(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -990,6 +1005,9 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             lds = dsp_reflect::row_bytes(n, m, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
             break;
         }
+        case DSP_ROUTE_PILEUP:  // a tile of 64 rows per wavefront, one wavefront a workgroup
+            lds = dsp_pileup::lds_bytes(ch->f64 ? 8 : 4), wpb = 1, b = (int)dsp_pileup::tiles(n_wf);
+            break;
         case DSP_ROUTE_DENSE:  // a tile of 64 rows per workgroup; the normalisation alone: a wavefront per row
             if (ch->dense.m > 0)
                 lds = dsp_dense::lds_bytes(ch->dense.m, ch->f64 ? 8 : 4) / 4, wpb = 4, b = (int)dsp_dense::tiles(n_wf);

@@ -18,6 +18,7 @@ enum dsp_route {
     DSP_ROUTE_INTERP,   // (nor this: INTERP_UPSAMPLE)
     DSP_ROUTE_DENSE,    // (nor this: NORMALISE and DENSE)
     DSP_ROUTE_REFLECT,  // (nor this: REFLECTED_CONVOLVE)
+    DSP_ROUTE_PILEUP,   // (nor this: RC_CR2 and BI_LEVEL_ZERO_CROSSING)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -31,6 +32,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_interp_kernel",
     "dsp_dense_kernel",
     "dsp_reflect_kernel",
+    "dsp_pileup_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -244,6 +246,17 @@ constexpr int lds_bytes(int n, int m, int esz) { return wide(n, m, esz) ? row_by
 static_assert(left(1) == 0 && right(1) == 0 && left(4) == 2 && right(4) == 1 && left(4) + right(4) + 1 == 4, "the margins of a kernel");
 static_assert(lds_bytes(F32_MAX, 1, 4) == LDS_MAX + 16 + 16 && lds_bytes(F64_MAX - 1, 2, 8) <= LDS_MAX + 16 + 16, "the longest rows: raised past 64 KiB (dsp_internal_set_reflect_lds)");
 }  // namespace dsp_reflect
+
+namespace dsp_pileup {  // dsp_pileup.hip: rc_cr2 and bi_level_zero_crossing_time_points, one waveform per lane
+// The 64 rows of a wavefront pass through one LDS tile of TS samples each: written along the rows, read along the columns -- lane l walks
+// row l of the tile --, and a filtered row goes back through the same tile.  With a pitch of TS + 1 elements the lanes of a column read hit
+// different banks in both loops (float32: bank (65 l) % 32 = l % 32 within a half of the wavefront; float64: dwords 130 l, 130 l + 1).
+constexpr int ROWS = 64, TS = 64, PITCH = TS + 1;
+constexpr int lds_bytes(int esz) { return ROWS * PITCH * esz; }
+constexpr int64_t tiles(int64_t n_wf) { return (n_wf + ROWS - 1) / ROWS; }
+constexpr int MIN_FILTER_LEN = 4;  // rc_cr2.py:51-54: more than 3 samples
+static_assert(lds_bytes(8) <= 64 * 1024, "a static LDS array");
+}  // namespace dsp_pileup
 
 namespace dsp_current {  // dsp_current.hip
 constexpr int CB = 16;   // samples per block (= per checkpoint)

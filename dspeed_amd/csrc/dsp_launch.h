@@ -53,6 +53,8 @@ int dsp_internal_set_dense_lds(int dtype, int lds_bytes);
 // dsp_reflect.hip (dtype: the rows'; vec as above, for the loads -- the stores' is A->out_vec; LDS: dsp_reflect::lds_bytes, up to 32 bytes past 64 KiB for the longest rows)
 int dsp_internal_launch_reflect(const ReflectArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 int dsp_internal_set_reflect_lds(int dtype, int lds_bytes);
+// dsp_pileup.hip (dtype: the rows'; vec as above, for the loads -- the stores' is A->out_vec; LDS: dsp_pileup::lds_bytes, static)
+int dsp_internal_launch_pileup(const PileupArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_scalar.hip (type: 0 float32, 1 float64, 2 int64 registers)
 int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);
 int dsp_internal_set_scalar_lds(int lds_bytes);

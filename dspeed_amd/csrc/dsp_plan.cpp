@@ -77,6 +77,7 @@ extern "C" const char* dsp_fatal_message(int code) {
         case DSP_E_MTPT_MODE: return "Unrecognized interpolation mode";
         case DSP_E_FFT_LEN: return "Size of fft must be len(w_in)//2+1";  // (raised with the length behind it, as the reference formats it)
         case DSP_E_PSD_LEN: return "Size of psd must be len(w_in)//2+1";
+        case DSP_E_RC_CR2_NAN: return "RC-CR^2 filter produced nans in output.";
         default: return "";
     }
 }
@@ -113,6 +114,7 @@ static bool match_sort_shape(const PlanCtx& c, const char** why);
 static bool match_interp_shape(const PlanCtx& c, const char** why);
 static bool match_dense_shape(const PlanCtx& c, const char** why);
 static bool match_reflect_shape(const PlanCtx& c, const char** why);
+static bool match_pileup_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -128,6 +130,8 @@ static const KernelOnlyRoute kernel_only_routes[] = {
      "DSP_OP_NORMALISE / DSP_OP_DENSE (normalisation_layer, dense_layer_*, classification_layer_*) run on dsp_dense_kernel only"},
     {DSP_ROUTE_REFLECT, {DSP_OP_REFLECTED_CONVOLVE, DSP_OP_REFLECTED_CONVOLVE}, match_reflect_shape,
      "DSP_OP_REFLECTED_CONVOLVE (reflected_convolve_wf) runs on dsp_reflect_kernel only"},
+    {DSP_ROUTE_PILEUP, {DSP_OP_RC_CR2, DSP_OP_BI_LEVEL_ZERO_CROSSING}, match_pileup_shape,
+     "DSP_OP_RC_CR2 / DSP_OP_BI_LEVEL_ZERO_CROSSING (rc_cr2, bi_level_zero_crossing_time_points) run on dsp_pileup_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -771,6 +775,85 @@ static bool match_reflect_shape(const PlanCtx& c, const char** why) {
     return true;
 }
 
+// Is the program one of the pile-up kernel's (dsp_pileup.hip)?
+//   LOAD s;  RC_CR2 of s into a slot of as many samples;  STORE of them
+//   LOAD s;  BI_LEVEL_ZERO_CROSSING of s;  STORE of its two lists;  STORE_SCALAR of its count into a DSP_U32 column
+//   LOAD s;  RC_CR2 of s;  BI_LEVEL_ZERO_CROSSING of the filtered row;  [STORE of the filtered row;]  STORE, STORE;  STORE_SCALAR
+// each with or without  BL_SUBTRACT s <- s  (bl_subtract.py, a constant or a column of the loop's type) behind the LOAD: done as the rows are read.
+// The walk's operands are constants or columns of the loop's type; t_tau, lengths and limits are lower_op's business (every program that holds
+// either op passes there first).  Why not, otherwise: `why`.
+static bool match_pileup_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int n = c.n_ops;
+    *why = "the program must be exactly LOAD, RC_CR2, STORE; or LOAD, BI_LEVEL_ZERO_CROSSING, STORE, STORE, STORE_SCALAR; or LOAD, RC_CR2, "
+           "BI_LEVEL_ZERO_CROSSING, [STORE of the filtered row,] STORE, STORE, STORE_SCALAR (a BL_SUBTRACT of the rows, in place, may follow the LOAD)";
+    auto is = [&](int i, int opcode) { return i >= 0 && i < n && ops[i].opcode == opcode; };
+    if (n < 3 || !is(0, DSP_OP_LOAD)) return false;
+    const int first = is(1, DSP_OP_BL_SUBTRACT) ? 2 : 1;
+    const bool filter = is(first, DSP_OP_RC_CR2), walk = is(filter ? first + 1 : first, DSP_OP_BI_LEVEL_ZERO_CROSSING);
+    if (!filter && !walk) return false;
+    const int first_store = first + (filter ? 1 : 0) + (walk ? 1 : 0);
+    const int n_stores = walk ? n - 1 - first_store : n - first_store;  // (behind them the walk's STORE_SCALAR)
+    if (c.n_slots != 1 + (filter ? 1 : 0) + (walk ? 2 : 0) || (walk ? (n_stores != 2 && !(filter && n_stores == 3)) || !is(n - 1, DSP_OP_STORE_SCALAR) : n_stores != 1))
+        return false;
+    for (int i = first_store; i < first_store + n_stores; ++i)
+        if (!is(i, DSP_OP_STORE)) return false;
+    const dsp_op& ld = ops[0];
+    const dsp_op* fi = filter ? &ops[first] : nullptr;
+    const dsp_op* wk = walk ? &ops[filter ? first + 1 : first] : nullptr;
+    PileupArgs& A = ch->pileup;
+    memset(&A, 0, sizeof A);
+    ch->lio_out = ch->lio_list[0] = ch->lio_list[1] = ch->lio_n = ch->lio_sub = -1;
+    for (int k = 0; k < 4; ++k) ch->lio_par[k] = -1;
+    if ((fi ? fi->src : wk->src) != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->pileup_src, why,
+                                                        "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
+    if (first == 2) {
+        const dsp_op& bs = ops[1];
+        *why = "the BL_SUBTRACT behind the LOAD works on the rows in place (bl_subtract, ip[0] = 0), its baseline a constant or a per-event column of the loop's type";
+        if (bs.dst != ld.dst || bs.src != ld.dst || bs.ip[0] != 0 || !bind_operand(c, bs, 0, ch->lio_sub, A.sub_stride, A.sub_const)) return false;
+        A.sub_mode = 1;
+    }
+    *why = "the walk in the same program reads exactly the filtered row";
+    if (fi && wk && (wk->src != fi->dst || wk->dst == ld.dst || wk->ip[0] == ld.dst)) return false;
+    *why = "the filtered row and the two lists are stored once each, whole, in the loop's type; the count once, into a DSP_U32 column";
+    for (int i = first_store; i < first_store + n_stores; ++i) {
+        const dsp_op& st = ops[i];
+        const dsp_io_desc& o = io[st.io];
+        int* slot = fi && st.src == fi->dst ? &ch->lio_out : (wk && st.src == wk->dst ? &ch->lio_list[0] : (wk && st.src == wk->ip[0] ? &ch->lio_list[1] : nullptr));
+        if (!slot || *slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        *slot = st.io;
+        if (slot == &ch->lio_out) A.out_stride = o.row_stride;
+        else A.list_stride[slot == &ch->lio_list[0] ? 0 : 1] = o.row_stride;
+    }
+    if (wk) {
+        const dsp_op& sc = ops[n - 1];
+        if (ch->lio_list[0] < 0 || ch->lio_list[1] < 0 || ch->lio_list[0] == ch->lio_list[1] || ch->lio_list[0] == ch->lio_out || ch->lio_list[1] == ch->lio_out ||
+            sc.ip[0] != wk->ip[1] || io[sc.io].dtype != DSP_U32)  // (every output its own binding)
+            return false;
+        ch->lio_n = sc.io;
+        A.n_stride = io[sc.io].row_stride;
+        *why = "a threshold, the gate and t_start are constants or per-event columns of the loop's type";
+        for (int k = 0; k < 4; ++k)
+            if (!bind_operand(c, *wk, k, ch->lio_par[k], A.par_stride[k], A.par_const[k])) return false;
+        A.m = c.slot_len[wk->dst];
+    } else if (ch->lio_out < 0) {
+        return false;
+    }
+    if (fi) {  // rc_cr2.py:66-71 with numba's typing: -1 / t_tau in float64 whatever the loop, the powers as products
+        const double tau = op_const(c, *fi, 0), a = exp(-1.0 / tau);
+        A.c1 = 3.0 * a;
+        A.c2 = 3.0 * (a * a);
+        A.c3 = a * (a * a);
+        A.tau_nan = std::isnan(tau) ? 1 : 0;
+    }
+    A.filter = fi ? 1 : 0;
+    A.walk = wk ? 1 : 0;
+    return true;
+}
+
 // Does the program have the shape of the current-branch kernel (dsp_current.hip)?
 //   LOAD s0;  WINDOWER s1 <- s0 (start: constant or float32 column);  AVG_CURRENT s2 <- s1;  UPSAMPLER s3 <- s2;
 //   MOVING_WINDOW_MULTI d <- s3 (3 windows, alternating);  MIN_MAX of d;  STORE_SCALARs of its four registers
@@ -1302,6 +1385,7 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_SORT:
         case DSP_OP_INTERP_UPSAMPLE:
         case DSP_OP_REFLECTED_CONVOLVE:
+        case DSP_OP_RC_CR2:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
         case DSP_OP_NORMALISE: out[0] = o.src; return 1;
         case DSP_OP_DENSE:
@@ -1311,6 +1395,7 @@ static int op_slots(const dsp_op& o, int out[4]) {
             return 2;
         case DSP_OP_DWT_HAAR: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[2]; return 3;
         case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
+        case DSP_OP_BI_LEVEL_ZERO_CROSSING:
         case DSP_OP_HISTOGRAM: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[0]; return 3;
         case DSP_OP_HISTOGRAM_STATS: out[0] = o.src; out[1] = o.ip[0]; return 2;
         case DSP_OP_MULTI_TIME_POINT_THRESH:
@@ -1492,7 +1577,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1543,7 +1628,7 @@ static int bind_io(PlanCtx& c) {
             return fail(DSP_ERR_ARG, "io %d: int32/uint32/float64 rows select the float64 loop (compute_dtype DSP_F64)", k);
         const bool is_out = a.kind == DSP_IO_WF_OUT || a.kind == DSP_IO_SCALAR_OUT;
         if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT) &&
-            !(c.only && c.only->route == DSP_ROUTE_EXTREMA && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32))  // (the counts of MULTI_EXTREMA: match_extrema_shape sees to the rest)
+            !(c.only && (c.only->route == DSP_ROUTE_EXTREMA || c.only->route == DSP_ROUTE_PILEUP) && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32))  // (the counts of MULTI_EXTREMA and BI_LEVEL_ZERO_CROSSING: their matchers see to the rest)
             return fail(DSP_ERR_ARG, "io %d: outputs have the chain's compute type or DSP_BOOL, taps the compute type", k);
         if ((a.dtype == DSP_BOOL || a.dtype == DSP_I64 || a.dtype == DSP_U64) && a.kind != DSP_IO_SCALAR_IN && a.kind != DSP_IO_SCALAR_OUT && !(a.dtype == DSP_BOOL && is_out))
             return fail(DSP_ERR_ARG, "io %d: DSP_BOOL / DSP_I64 / DSP_U64 are types of per-event columns (DSP_BOOL also of waveform outputs)", k);
@@ -1960,6 +2045,35 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
             if (!dsp_reflect::fits(n, m, f64 ? 8 : 4))
                 return fail(DSP_ERR_UNSUPPORTED, "reflected_convolve_wf: " DSP_REFLECT_LIMITS_TEXT " (len(w_in) = %d, len(kernel) = %d given): a row and its mirrored margins live in 64 KiB of LDS",
                             DSP_REFLECT_F32_MAX, DSP_REFLECT_F64_MAX, n, m);
+            break;
+        }
+        case DSP_OP_RC_CR2: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad RC_CR2 (src: the slot of the row; dst: another slot, for the filtered row; sp[0]: t_tau)", i);
+            if (o.sp[0].kind != DSP_ARG_CONST)
+                return fail(DSP_ERR_UNSUPPORTED, "rc_cr2: t_tau is a constant of the program, not a per-event value: its coefficients are formed on the host");
+            if (slot_len[o.src] < dsp_pileup::MIN_FILTER_LEN) return fail(DSP_E_DPZ_SHORT, "%s", dsp_fatal_message(DSP_E_DPZ_SHORT));
+            if (slot_len[o.dst] != slot_len[o.src])
+                return fail(DSP_ERR_ARG, "rc_cr2: the output has the length of the input (len(w_in) = %d, len(w_out) = %d)", slot_len[o.src], slot_len[o.dst]);
+            break;
+        }
+        case DSP_OP_BI_LEVEL_ZERO_CROSSING: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || !check_slot(P, o.ip[0]) || o.dst == o.src || o.ip[0] == o.src || o.dst == o.ip[0] || o.ip[1] < 0 ||
+                o.ip[1] >= n_sregs)
+                return fail(DSP_ERR_ARG, "op %d: bad BI_LEVEL_ZERO_CROSSING (dst, ip[0]: the slots of polarity_out and t_trig_times_out; ip[1]: the register of the count)", i);
+            if (slot_len[o.dst] != slot_len[o.ip[0]])
+                return fail(DSP_ERR_ARG, "bi_level_zero_crossing_time_points: the output arrays are of different lengths (%d and %d)", slot_len[o.dst], slot_len[o.ip[0]]);
+            if (slot_len[o.dst] < 1) return fail(DSP_ERR_ARG, "bi_level_zero_crossing_time_points: polarity_out and t_trig_times_out hold at least one entry");
+            if (o.sp[2].kind == DSP_ARG_CONST && !std::isfinite(o.sp[2].value))
+                return fail(DSP_ERR_ARG, "bi_level_zero_crossing_time_points: gate_time_in is a finite number of samples");
+            // t_start: the reference's checks in its order (time_point_thresh.py:479-483), for a constant
+            if (o.sp[3].kind == DSP_ARG_CONST && !std::isnan(o.sp[3].value)) {
+                const double t = op_const(c, o, 3);
+                if (floor(t) != t) return fail(DSP_E_TPT_START_INT, "%s", dsp_fatal_message(DSP_E_TPT_START_INT));
+                if (t < 0 || t >= slot_len[o.src]) return fail(DSP_E_TPT_RANGE, "%s", dsp_fatal_message(DSP_E_TPT_RANGE));
+            }
+            if (!f64 && slot_len[o.src] > (1 << 24))
+                return fail(DSP_ERR_UNSUPPORTED, "bi_level_zero_crossing_time_points: the float32 loop takes rows of at most 2^24 samples (%d): a time counts them exactly", slot_len[o.src]);
             break;
         }
         case DSP_OP_DWT_HAAR: {

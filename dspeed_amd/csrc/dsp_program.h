@@ -432,6 +432,36 @@ struct ReflectArgs {
     int64_t cur_stride;
 };
 
+// arguments of the pile-up kernel (dsp_pileup.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> RC_CR2 -> STORE
+//   LOAD -> BI_LEVEL_ZERO_CROSSING -> STORE, STORE, STORE_SCALAR
+//   LOAD -> RC_CR2 -> BI_LEVEL_ZERO_CROSSING [-> STORE of the filtered row] -> STORE, STORE, STORE_SCALAR
+// each with or without a BL_SUBTRACT of the rows, in place, behind the LOAD.  One waveform per lane; the rows pass through an LDS tile of 64 rows x 64 samples (dsp_kernels.h, dsp_pileup).
+struct PileupArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples (the filter: more than 3; the walk: at least 1)
+    int32_t filter;          // 1: rc_cr2 runs on the row
+    int32_t walk;            // 1: bi_level_zero_crossing_time_points runs on the row, or on the filtered row as stored
+    int32_t m;               // entries of each list
+    int32_t out_vec;         // 1: 16-byte stores of the filtered row (the output rows' start and stride are whole vectors: set per call)
+    int32_t tau_nan;         // 1: t_tau is a NaN: every filtered row NaN, no error
+    int32_t sub_mode;        // 1: the baseline is subtracted from every sample as it is read (bl_subtract)
+    const void* sub;         // the baseline: a column of the loop's type, or null: sub_const
+    int64_t sub_stride;
+    double sub_const;
+    double c1, c2, c3;       // 3a, 3(a a), a(a a) with a = exp(-1 / t_tau): float64, formed on the host
+    const void* par[4];      // a_pos_threshold_in, a_neg_threshold_in, gate_time_in, t_start_in: columns of the loop's type, or null: par_const
+    int64_t par_stride[4];
+    double par_const[4];
+    void* out;               // filtered rows of len samples of the loop's type, or null: not stored
+    int64_t out_stride;
+    void* list[2];           // polarity_out, t_trig_times_out: rows of m values of the loop's type
+    int64_t list_stride[2];
+    uint32_t* n_out;         // n_crossings_out
+    int64_t n_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

@@ -694,5 +694,75 @@ gaussian_filter1d = HipGUFunc("gaussian_filter1d", "(),(),(n)", ["fff", "ddd"], 
 # Listed here and not in __all__, like the spectral processors and sort: their call records are tests/test_reflect_plan_cpu.py's.
 SMOOTHING = ("reflected_convolve_wf", "gaussian_filter1d")
 
+
+# --------------------------------------------------------------------------------------------------- pile-up
+def check_rc_cr2(what, n, m=None):
+    """what the planner checks, in the reference's words where it has them"""
+    if n <= 3:
+        raise DSPFatal("The length of the waveform must be larger than 3 for the filter to work safely")
+    if m is not None and m != n:
+        raise ValueError(f"{what}: the output has the length of the input (len(w_in) = {n}, len(w_out) = {m})")
+
+
+def check_bi_level_lists(what, m_polarity, m_times):
+    if m_polarity != m_times:
+        raise ValueError(f"{what}: polarity_out and t_trig_times_out share the dimension m ({m_polarity} and {m_times} given)")
+    if m_polarity < 1:
+        raise ValueError(f"{what}: polarity_out and t_trig_times_out hold at least one entry")
+
+
+def _rc_cr2(g, *args):
+    """one C entry for both loops, like sort's (``dsp_rc_cr2_rows`` takes the loop's type).  t_tau is a constant of the call: the filter's
+    coefficients are formed on the host, in float64, from the value the loop receives; ``w_out`` may be left out."""
+    what = g.__name__
+    (w_in, t_tau), (out,) = _split(g, args)
+    tau = float(_constant_of_call(t_tau, what, "t_tau"))
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        if out is not None and not isinstance(out, (np.ndarray, DeviceArray)):
+            raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+        check_rc_cr2(what, c.n, None if out is None else (int(out.shape[-1]) if len(out.shape) else 0))
+        ptr, stride = c.out(out, "n")
+        run(getattr(_lib.lib(), "dsp_rc_cr2_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, tau, ptr, stride)
+        c.st.finish()
+        return c.results[0]
+
+
+def _bi_level_zero_crossing_time_points(g, *args):
+    """one C entry for both loops.  The two lists must be passed: their length is m; the count may be ``None``.  Thresholds, gate and start
+    are each one value or a value per row."""
+    what = g.__name__
+    if len(args) != 8:
+        raise TypeError(f"{what}(w_in, a_pos_threshold_in, a_neg_threshold_in, gate_time_in, t_start_in, n_crossings_out, polarity_out, "
+                        "t_trig_times_out): polarity_out and t_trig_times_out must be passed (their length is the number of crossings kept); "
+                        "n_crossings_out may be None")
+    w_in, pos, neg, gate, t_start, n_out, polarity, times = args
+    for o in (polarity, times):
+        if not isinstance(o, (np.ndarray, DeviceArray)):
+            raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        m = int(polarity.shape[-1]) if len(polarity.shape) else 0
+        check_bi_level_lists(what, m, int(times.shape[-1]) if len(times.shape) else 0)
+        if np.size(gate) == 1 and not isinstance(gate, DeviceArray) and not np.isfinite(float(np.asarray(gate).reshape(-1)[0])):
+            raise ValueError(f"{what}: gate_time_in is a finite number of samples")
+        cols = [c.col(v) for v in (pos, neg, gate, t_start)]
+        pn = c.out(n_out, "", np.uint32)[0]
+        pp, pt = c.out(polarity, "m")[0], c.out(times, "m")[0]
+        run(getattr(_lib.lib(), "dsp_bi_level_zero_crossing_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64,
+            *cols[0], *cols[1], *cols[2], *cols[3], pn, pp, pt, m, m)
+        c.st.finish()
+        return tuple(c.results)
+
+
+rc_cr2 = HipGUFunc("rc_cr2", "(n),()->(n)", ["ff->f", "dd->d"], _rc_cr2,
+                   "RC-CR^2 shaper with the time constant t_tau (a constant of the call): a third-order recursion with a float64 state, one "
+                   "rounding at the store; a row with a NaN: NaNs (reference processors/rc_cr2.py:12-94)")
+bi_level_zero_crossing_time_points = HipGUFunc("bi_level_zero_crossing_time_points", "(n),(),(),(),(),(),(m),(m)", ["fffffIff", "dddddIdd"],
+                                               _bi_level_zero_crossing_time_points,
+                                               "the zero crossings between a crossing of one threshold and, within the gate, of the other: count, "
+                                               "polarities and NaN-padded indices (reference processors/time_point_thresh.py:404-532)")
+
+# Listed here and not in __all__, like the smoothing processors: their call records are tests/test_pileup_plan_cpu.py's.
+PILEUP = ("rc_cr2", "bi_level_zero_crossing_time_points")
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

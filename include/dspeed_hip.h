@@ -75,6 +75,7 @@ extern "C" {
 #define DSP_E_MTPT_MODE 32     /* time_point_thresh.py:357-358   likewise */
 #define DSP_E_FFT_LEN 33       /* fft.py:39-40    "Size of fft must be len(w_in)//2+1 = ..." (the text carries the length: dsp_last_error) */
 #define DSP_E_PSD_LEN 34       /* fft.py:119-120  "Size of psd must be len(w_in)//2+1 = ..." */
+#define DSP_E_RC_CR2_NAN 35    /* rc_cr2.py:93-94          data dependent */
 
 /* ---- element types -------------------------------------------------------------------------- */
 #define DSP_F32 0
@@ -305,6 +306,24 @@ typedef struct dsp_scalar_arg {
                                  *   LOAD, REFLECTED_CONVOLVE, STORE of dst;  or
                                  *   LOAD, REFLECTED_CONVOLVE, AVG_CURRENT of dst (a constant length), STORE of the current [, STORE of dst]
                                  * where the filtered row goes to memory only if it is stored */
+#define DSP_OP_RC_CR2 46       /* rc_cr2.py:12-94: dst (n samples, another slot than src) <- src (n > 3 samples) through the RC-CR^2 shaper with the
+                                 * triple pole a = exp(-1 / sp[0]), sp[0] = t_tau, a constant of the program.  dst[0:3] = src[0:3]; from sample 3 on a
+                                 * float64 state w: w3 = 3a w2 - 3(a a) w1 + a(a a) w0 + src[i] - 2 src[i-1] + src[i-2], summed in that order, one
+                                 * rounding at the store; the three coefficients are formed on the host in float64.  A row with a NaN, and every row
+                                 * for a NaN t_tau: NaN, no error; a NaN of the filter's own making (an infinite sample): DSP_E_RC_CR2_NAN with the row.
+                                 * The waveform interpreter has no such op: it runs on dsp_pileup_kernel only (the shapes: below) */
+#define DSP_OP_BI_LEVEL_ZERO_CROSSING 47 /* time_point_thresh.py:404-532 bi_level_zero_crossing_time_points: the reference's state machine over
+                                 * i = t_start .. n - 2 of src.  dst / ip[0] = the slots of polarity_out / t_trig_times_out (both of m >= 1 values,
+                                 * NaN-padded), sreg[ip[1]] <- n_crossings_out (a DSP_U32 column; it counts on past m); sp[0..3] = a_pos_threshold_in,
+                                 * a_neg_threshold_in, gate_time_in, t_start_in, each a constant or a per-event column of the loop's type.  A row,
+                                 * threshold or t_start with a NaN, or a per-event gate that is not finite: NaN lists, count 0; a t_start that is not
+                                 * integral or outside the row: DSP_E_TPT_START_INT / DSP_E_TPT_RANGE with the row.  It runs on dsp_pileup_kernel
+                                 * only, one waveform per lane, in a program of exactly
+                                 *   LOAD, RC_CR2, STORE of the filtered row
+                                 *   LOAD, BI_LEVEL_ZERO_CROSSING, STORE, STORE of the two lists, STORE_SCALAR of the count
+                                 *   LOAD, RC_CR2, BI_LEVEL_ZERO_CROSSING of the filtered row, [STORE of the filtered row,] STORE, STORE, STORE_SCALAR
+                                 * where the walk tests the filtered value as stored (rounded to the loop's type) and the filtered row goes to
+                                 * memory only if it is stored */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -591,6 +610,21 @@ int dsp_normalisation_rows(const void* in, int in_dtype, int64_t n_wf, int32_t w
  * error with the reference's text.  16-byte stores where out and out_stride are whole vectors. */
 int dsp_reflected_convolve_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype,
                                 const void* taps_dev, int32_t n_taps, void* out, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),()->(n)" rc_cr2 (rc_cr2.py:12-94; DSP_OP_RC_CR2): every row through the RC-CR^2 shaper with the constant time constant t_tau (in
+ * samples), wf_len > 3 outputs.  One entry for both loops, like dsp_sort_rows: compute_dtype names the loop (DSP_F32: float32 / int16 / uint16
+ * rows, float output; DSP_F64: float64 rows, double output).  Returns DSP_E_RC_CR2_NAN with *err_row for a row the filter itself makes NaN. */
+int dsp_rc_cr2_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, double t_tau, void* out,
+                    int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(),(),(),(),(),(m),(m)" bi_level_zero_crossing_time_points (time_point_thresh.py:404-532; DSP_OP_BI_LEVEL_ZERO_CROSSING).  The four
+ * operands are columns of the loop's type on the device (*_dev) or, where that is null, the constant beside it.  polarity_out and
+ * t_trig_times_out: rows of out_len >= 1 values of the loop's type, out_stride apart, NaN-padded; n_crossings_out: a uint32 per row, which
+ * counts on past out_len. */
+int dsp_bi_level_zero_crossing_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype,
+                                    const void* a_pos_threshold_dev, double a_pos_threshold, const void* a_neg_threshold_dev, double a_neg_threshold,
+                                    const void* gate_time_dev, double gate_time, const void* t_start_dev, double t_start, uint32_t* n_crossings_out,
+                                    void* polarity_out, void* t_trig_times_out, int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
