@@ -26,7 +26,7 @@ from . import _lib
 from .chain import Program, Scalar
 from .device import dtype_code
 from .errors import DSPFatal, ProcessingChainError
-from .language import (Char, Grid, Quantity, SExpr, Var, View, _Builder, _GENERATORS, _NUMPY_BINARY, module_accepted, _SIGS, _column, _grid_of, _is_int_dtype,
+from .language import (Char, Grid, Quantity, SExpr, Var, View, _Builder, _GENERATORS, _MODULES, _NUMPY_BINARY, module_accepted, _SIGS, _column, _grid_of, _is_int_dtype,
                        _is_scalar, _is_wf, _resolve, _roles, _time_unit_ns)
 
 # processors whose output waveform has the input's dimension name in the gufunc signature ("(n),...->(n)") and therefore its
@@ -36,10 +36,11 @@ _HISTOGRAM, _HISTOGRAM_STATS = "histogram", "histogram_stats"
 _MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
 _PSD, _SORT, _INTERP, _REFLECT = "psd", "sort", "interpolating_upsampler", "reflected_convolve_wf"
 _RC_CR2, _BI_LEVEL = "rc_cr2", "bi_level_zero_crossing_time_points"
+_PEAK_SNR, _MULTI_A = "peak_snr_threshold", "multi_a_filter"
 _NORMALISE = "normalisation_layer"
 _DENSE_LAYERS = ("dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
 _ML = (_NORMALISE,) + _DENSE_LAYERS
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL) + _ML  # processors that run as stages ahead of the program, on kernels of their own
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL, _PEAK_SNR, _MULTI_A) + _ML  # processors that run as stages ahead of the program, on kernels of their own
 _SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT, _RC_CR2)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
@@ -116,7 +117,10 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
     if function == "fft":
         raise NotImplementedError(f"processor 'fft' ({key}): complex variables are not in the recipe language; the gufunc dspeed_amd.processors.fft "
                                   "and the C entry dsp_fft are the interface (psd runs in recipes)")
-    if function not in _SIGS:
+    if function not in _SIGS or (function in (_PEAK_SNR, _MULTI_A) and module in _MODULES):
+        # (peak_snr_threshold and multi_a_filter are reached through their files' module strings, dspeed.processors.peak_snr_threshold and
+        # dspeed.processors.multi_a_filter, as the SiPM configs write them; under the package's string they stay refused, in these words:
+        # tests/test_histogram_plan_cpu.py and the recorded translations hold that -- as they hold gaussian_filter1d's refusal)
         raise NotImplementedError(f"processor '{function}' is not implemented on the device path")
     roles = _SIGS[function]
     if len(args) != len(roles):
@@ -148,6 +152,17 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         if isinstance(args[7], Var) and _time_unit_ns(args[7].unit) is not None and _grid_of(args[0]) is not None:
             args[7].is_coord, args[7].grid = True, _grid_of(args[0])
         if isinstance(args[5], Var):
+            args[5].out_dtype = np.dtype(np.uint32)
+    if function in (_PEAK_SNR, _MULTI_A):
+        # the output list is as long as the list read (the reference's ProcessorManager deduces m: the config declares no length); the
+        # picker's list holds sample indices of the input, like the peak finder's; its count is uint32 (the gufunc's "I")
+        lst, out = args[1], args[4 if function == _PEAK_SNR else 2]
+        if isinstance(out, Var) and out.kind == "wf" and _is_wf(lst):
+            if out.length is None:
+                out.length = lst.length
+            if function == _PEAK_SNR and _time_unit_ns(out.unit) is not None and _grid_of(args[0]) is not None:
+                out.is_coord, out.grid = True, _grid_of(args[0])
+        if function == _PEAK_SNR and isinstance(args[5], Var):
             args[5].out_dtype = np.dtype(np.uint32)
     if function == _MULTI_TPT:
         # its thresholds are one constant list, or a list per event read from rows in memory; its times are sample indices of the input:
@@ -1107,6 +1122,59 @@ def _stage_pileup(cx: _Stager, only=None):
         cx.stage(pre + [st], [], f"{st[0]} {st[2]} on rows", wfs=[out], rows_first=True)
 
 
+def _stage_pulses(cx: _Stager, only=None):
+    """``peak_snr_threshold`` and ``multi_a_filter`` run on dsp_pulses.hip and nowhere else, on rows in HBM: mandatory stages, like the
+    threshold kernel's.  The list is a stage's list in memory (the peak finder's, a picker's) or a two-dimensional input column; the ratio is
+    a per-event operand (``_operand_in_memory``), the width a constant.  A ``multi_a_filter`` that reads exactly a picker's ``idx_out``, on
+    the same waveform, joins its launch; the list is then written only if something else reads it or the recipe asks for it
+    (``_stage_histogram``'s rule for weights and borders).  The outputs' length is that of the list read."""
+    from .processors import check_pulse_list, check_pulse_width
+
+    def list_in_memory(fn, key, lst, out, pickoff, n):
+        if not _is_wf(lst) or not lst.length:
+            raise ProcessingChainError(f"{fn} ({key}): the list is an array per event: a stage's list or a two-dimensional input column, not {lst!r}")
+        if not (isinstance(out, Var) and out.kind == "wf" and out.length):
+            raise ProcessingChainError(f"{fn} ({key}): the output is an array variable (its length is that of the list read)")
+        check_pulse_list(f"{fn} ({key})", n, lst.length, out.length, pickoff=pickoff)
+
+    for st in cx.steps_of(_PEAK_SNR, only):
+        fn, args, key = st[0], list(st[1]), st[2]
+        src, lst, _ratio, width, out, count = args
+        if isinstance(width, Var) and width.kind == "const":
+            width = width.const
+        if not (_is_number(width) or isinstance(width, Quantity)):
+            raise NotImplementedError(f"{fn} ({key}): per-waveform integer parameters are not supported on the device")
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        if not isinstance(count, Var):
+            raise ProcessingChainError(f"{fn} ({key}): name the count")
+        if not isinstance(width, Quantity):
+            args[3] = check_pulse_width(f"{fn} ({key})", width)
+        list_in_memory(fn, key, lst, out, False, src.length)
+        _rows_in_memory(cx, src, fn, key)
+        _rows_in_memory(cx, lst, fn, key)
+        args[2] = _operand_in_memory(cx, args[2], fn, key, written_first=True)
+        step = cx.replace(st, (fn, args, key))
+        amp = next((x for x in cx.steps if x[0] == _MULTI_A and x[1][1] is out and x[1][0] is src), None)
+        if amp is None:
+            cx.stage([step], [count], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+            continue
+        list_in_memory(_MULTI_A, amp[2], out, amp[1][2], True, src.length)
+        list_wanted = out.name in cx.out_names or any(u is not amp for u in cx.users_of(out))
+        cx.stage([step, amp], [count], f"{fn} {key} + {_MULTI_A} {amp[2]} in one launch on rows", wfs=([out] if list_wanted else []) + [amp[1][2]],
+                 rows_first=True)
+    for st in cx.steps_of(_MULTI_A, only):
+        fn, (src, lst, out), key = st
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        list_in_memory(fn, key, lst, out, True, src.length)
+        _rows_in_memory(cx, lst, fn, key)  # (a picker's list: its stage first, and with it this step, if it reads the same waveform)
+        if not cx.has(st):
+            continue
+        _rows_in_memory(cx, src, fn, key)
+        cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+
+
 def _stage_ml_layers(cx: _Stager, only=None):
     """The neural-network layers (ml.py) run on dsp_dense.hip and nowhere else, on rows in HBM: mandatory stages, like sort's.  Each dense or
     classification layer is a launch on rows in memory -- a chain input, a stage's waveform (the layer before it), or a waveform the program
@@ -1153,7 +1221,7 @@ def _stage_ml_layers(cx: _Stager, only=None):
 
 
 #: the family that stages each processor with a kernel of its own (``_stage_producers`` asks it for one step)
-_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _RC_CR2: _stage_pileup, _BI_LEVEL: _stage_pileup, _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
+_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _RC_CR2: _stage_pileup, _BI_LEVEL: _stage_pileup, _PEAK_SNR: _stage_pulses, _MULTI_A: _stage_pulses, _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
               _MULTI_EXTREMA: _stage_multi_extrema, _MULTI_TPT: _stage_thresholds, _TIME_OVER: _stage_thresholds, _PSD: _stage_spectrum,
               _SORT: _stage_sort, _INTERP: _stage_interp_upsampler, **dict.fromkeys(_ML, _stage_ml_layers)}
 
@@ -1184,6 +1252,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_multi_extrema(cx)
     _stage_thresholds(cx)
     _stage_pileup(cx)
+    _stage_pulses(cx)
     _stage_spectrum(cx)
     _stage_sort(cx)
     _stage_interp_upsampler(cx)
@@ -1851,6 +1920,26 @@ class _Emitter:
         self.p.add_op(_lib.OP_BI_LEVEL_ZERO_CROSSING, dst=polarity.slot, src=src.slot, ip=(times.slot, first), sp=sp)
         self.release(src, si)
 
+    def peak_snr_threshold(self, si, fn, args, what):
+        """LOAD, LOAD of the candidates, PEAK_SNR_THRESHOLD of the picker's stage; a multi_a_filter of the packed list may follow, then the stores"""
+        src, lst = self.ensure_loaded(args[0], si), self.ensure_loaded(args[1], si)
+        sp = (self.scalar_operand(args[2], args, what=what), self.scalar_operand(args[3], args, what=what))
+        out = self.out_wf(args[4], lst.length, fn)
+        out.slot = self.new_slot(out.length)
+        first = self.out_row(args[5:6], f"{what}: the count must be a variable name")
+        self.p.add_op(_lib.OP_PEAK_SNR_THRESHOLD, dst=out.slot, src=src.slot, ip=(lst.slot, first), sp=sp)
+        self.release(lst, si)
+        self.release(src, si)
+
+    def multi_a_filter(self, si, fn, args, what):
+        """MULTI_A_FILTER on rows and a list loaded from memory, or on the rows and the packed list of a picker in the same program"""
+        src, lst = self.ensure_loaded(args[0], si), self.ensure_loaded(args[1], si)
+        out = self.out_wf(args[2], lst.length, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_MULTI_A_FILTER, dst=out.slot, src=src.slot, ip=(lst.slot,))
+        self.release(lst, si)
+        self.release(src, si)
+
     def taps_io(self, v):
         """the binding of a constant array, made at its first use"""
         if v.io is None:
@@ -2062,7 +2151,7 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          "convolve_wf": _Emitter.convolve, "fft_convolve_wf": _Emitter.convolve, _MULTI_EXTREMA: _Emitter.multi_extrema,
          _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
          _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler, _REFLECT: _Emitter.reflected_convolve, _RC_CR2: _Emitter.rc_cr2,
-         _BI_LEVEL: _Emitter.bi_level_zero_crossing,
+         _BI_LEVEL: _Emitter.bi_level_zero_crossing, _PEAK_SNR: _Emitter.peak_snr_threshold, _MULTI_A: _Emitter.multi_a_filter,
          _NORMALISE: _Emitter.normalisation_layer, **dict.fromkeys(_DENSE_LAYERS, _Emitter.dense_layer)}
 
 
@@ -2109,7 +2198,7 @@ def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):
             io = p.add_io(f"out:{o}", _lib.IO_WF_OUT, odt, v.length)
             p.add_op(_lib.OP_STORE, src=src_slot, io=io)
             out_bind[f"out:{o}"] = (SimpleNamespace(name=o, dtype=odt), v.length)
-            if v.vector_len is not None:
+            if v.vector_len is not None and not stage_mode:  # (a stage hands on whole rows: the lengths leave with the recipe's outputs)
                 vl = v.vector_len
                 if isinstance(vl, Var) and vl.is_input and vl.source is not None:
                     vector_lens[o] = vl.source  # a column of the input table

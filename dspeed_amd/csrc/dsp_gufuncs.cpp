@@ -516,6 +516,32 @@ int dsp_bi_level_zero_crossing_rows(ROWS, int compute_dtype, const void* a_pos_t
         return DSP_OK;
     });
 }
+// peak_snr_threshold and multi_a_filter: one entry each for both loops; the list is loaded like rows, a list per row
+int dsp_peak_snr_threshold_rows(ROWS, int compute_dtype, const void* idx_in_dev, int32_t list_len, int64_t idx_in_stride, const void* ratio_dev, double ratio,
+                                double width, void* idx_out, int64_t out_stride, uint32_t* n_idx_out, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "peak_snr_threshold: compute_dtype is DSP_F32 or DSP_F64");
+    if (list_len == 0) return DSP_OK;  // (no candidate: an empty result)
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (list_len < 0 || !idx_in_dev) return dsp_fail(DSP_ERR_ARG, "peak_snr_threshold: idx_in_dev holds the candidates on the device");
+        m.n_sregs = 1;
+        const int s_in = m.load(IN), s_list = m.load({idx_in_dev, compute_dtype, n_wf, list_len, idx_in_stride}), s_out = m.add_slot(list_len);
+        m.op(DSP_OP_PEAK_SNR_THRESHOLD, s_out, s_in, 0, {s_list, 0}, {{ratio_dev, ratio}, {nullptr, width}});
+        m.store(s_out, {idx_out, list_len, out_stride});
+        m.store_scalar(0, n_idx_out, DSP_U32);
+        return DSP_OK;
+    });
+}
+int dsp_multi_a_filter_rows(ROWS, int compute_dtype, const void* vt_maxs_in_dev, int32_t list_len, int64_t vt_stride, void* va_max_out, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "multi_a_filter: compute_dtype is DSP_F32 or DSP_F64");
+    if (list_len == 0) return DSP_OK;  // (no position: an empty result)
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (list_len < 0 || !vt_maxs_in_dev) return dsp_fail(DSP_ERR_ARG, "multi_a_filter: vt_maxs_in_dev holds the positions on the device");
+        const int s_in = m.load(IN), s_list = m.load({vt_maxs_in_dev, compute_dtype, n_wf, list_len, vt_stride}), s_out = m.add_slot(list_len);
+        m.op(DSP_OP_MULTI_A_FILTER, s_out, s_in, 0, {s_list});
+        m.store(s_out, {va_max_out, list_len, out_stride});
+        return DSP_OK;
+    });
+}
 #undef ROWS
 #undef IN
 #undef TAIL

@@ -700,6 +700,18 @@ static int launch_pileup(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void
     return launch_on_rows(ch, n_wf, stream, A, ch->pileup_src, dsp_internal_launch_pileup, "pile-up kernel launch");
 }
 
+static int launch_pulses(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    PulsesArgs A = ch->pulses;
+    A.wf = io_ptrs[ch->pulses_src.io];  // (the inputs' offsets travel in the arguments)
+    A.list = io_ptrs[ch->uio_list];
+    A.ratio = at(ch->uio_ratio);
+    A.idx_out = at(ch->uio_idx);
+    A.n_out = (uint32_t*)at(ch->uio_n);
+    A.amp_out = at(ch->uio_amp);
+    return launch_on_rows(ch, n_wf, stream, A, ch->pulses_src, dsp_internal_launch_pulses, "pulse kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -889,6 +901,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_DENSE)) return launch_dense(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_REFLECT)) return launch_reflect(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_PILEUP)) return launch_pileup(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_PULSES)) return launch_pulses(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -1016,6 +1029,7 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
             break;
         case DSP_ROUTE_EXTREMA:
         case DSP_ROUTE_THRESH:
+        case DSP_ROUTE_PULSES:
         case DSP_ROUTE_PZ_ROWS:
         case DSP_ROUTE_REDUCE: lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4); break;
         case DSP_ROUTE_FIR_RUNS: lds = dsp_fir_runs::lds_bytes(ch->runs.m) / 4, wpb = 4, b = runs_blocks(ch, n_wf); break;

@@ -19,6 +19,7 @@ enum dsp_route {
     DSP_ROUTE_DENSE,    // (nor this: NORMALISE and DENSE)
     DSP_ROUTE_REFLECT,  // (nor this: REFLECTED_CONVOLVE)
     DSP_ROUTE_PILEUP,   // (nor this: RC_CR2 and BI_LEVEL_ZERO_CROSSING)
+    DSP_ROUTE_PULSES,   // (nor this: PEAK_SNR_THRESHOLD and MULTI_A_FILTER)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -33,6 +34,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_dense_kernel",
     "dsp_reflect_kernel",
     "dsp_pileup_kernel",
+    "dsp_pulses_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -257,6 +259,28 @@ constexpr int64_t tiles(int64_t n_wf) { return (n_wf + ROWS - 1) / ROWS; }
 constexpr int MIN_FILTER_LEN = 4;  // rc_cr2.py:51-54: more than 3 samples
 static_assert(lds_bytes(8) <= 64 * 1024, "a static LDS array");
 }  // namespace dsp_pileup
+
+namespace dsp_pulses {  // dsp_pulses.hip: peak_snr_threshold (peak_snr_threshold.py:19-71) and multi_a_filter (multi_a_filter.py:20-57)
+// ---- the rule of a candidate, shared by the kernel, the planner and tests/pulse_window.cpp.  A candidate idx of a row of n samples, the
+// window half width `width` >= 0: c = int(idx) (towards zero), the minimum is looked for over j in [a, b) from min_index = a,
+//   a = max(c - width, 0),  b = min(c + width, n - 1)
+// -- b itself is never looked at, so neither c + width nor, under the clamp, the row's last sample; an empty window leaves a.  dropped():
+// the candidates no sample is read for -- a NaN (the reference skips it), and where the reference defines nothing: an infinite one, and one
+// whose int() lies outside [0, n).  The test is made on the value, before any conversion: (-1, n) is what truncates into [0, n - 1].
+struct Window {
+    int c, a, b;
+};
+constexpr bool dropped(double idx, int n) { return !(idx > -1.0 && idx < (double)n); }  // (a NaN fails both comparisons)
+constexpr Window window(double idx, int n, int width) {
+    const int c = (int)idx;  // (not dropped: -1 < idx < n)
+    const int64_t lo = (int64_t)c - width, hi = (int64_t)c + width;
+    return {c, (int)(lo < 0 ? 0 : lo), (int)(hi >= n ? n - 1 : hi)};
+}
+// the width as the kernel takes it: int(width_in), and at most n -- beyond that both ends are clamped whatever the candidate
+constexpr int clamped_width(double width_in, int n) { return width_in >= (double)n ? n : (int)width_in; }
+static_assert(window(5.9, 10, 2).c == 5 && window(5.9, 10, 2).a == 3 && window(5.9, 10, 2).b == 7 && window(8.0, 10, 3).b == 9 && window(-0.5, 10, 3).c == 0, "the window");
+static_assert(dropped(-1.0, 10) && dropped(10.0, 10) && !dropped(-0.999, 10) && !dropped(9.5, 10) && dropped(0.0, 0), "the dropped candidates");
+}  // namespace dsp_pulses
 
 namespace dsp_current {  // dsp_current.hip
 constexpr int CB = 16;   // samples per block (= per checkpoint)

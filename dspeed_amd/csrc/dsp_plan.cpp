@@ -78,6 +78,7 @@ extern "C" const char* dsp_fatal_message(int code) {
         case DSP_E_FFT_LEN: return "Size of fft must be len(w_in)//2+1";  // (raised with the length behind it, as the reference formats it)
         case DSP_E_PSD_LEN: return "Size of psd must be len(w_in)//2+1";
         case DSP_E_RC_CR2_NAN: return "RC-CR^2 filter produced nans in output.";
+        case DSP_E_MAF_LEN: return "The length of your return array must be smaller than the length of your waveform";
         default: return "";
     }
 }
@@ -115,6 +116,7 @@ static bool match_interp_shape(const PlanCtx& c, const char** why);
 static bool match_dense_shape(const PlanCtx& c, const char** why);
 static bool match_reflect_shape(const PlanCtx& c, const char** why);
 static bool match_pileup_shape(const PlanCtx& c, const char** why);
+static bool match_pulses_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -132,6 +134,8 @@ static const KernelOnlyRoute kernel_only_routes[] = {
      "DSP_OP_REFLECTED_CONVOLVE (reflected_convolve_wf) runs on dsp_reflect_kernel only"},
     {DSP_ROUTE_PILEUP, {DSP_OP_RC_CR2, DSP_OP_BI_LEVEL_ZERO_CROSSING}, match_pileup_shape,
      "DSP_OP_RC_CR2 / DSP_OP_BI_LEVEL_ZERO_CROSSING (rc_cr2, bi_level_zero_crossing_time_points) run on dsp_pileup_kernel only"},
+    {DSP_ROUTE_PULSES, {DSP_OP_PEAK_SNR_THRESHOLD, DSP_OP_MULTI_A_FILTER}, match_pulses_shape,
+     "DSP_OP_PEAK_SNR_THRESHOLD / DSP_OP_MULTI_A_FILTER (peak_snr_threshold, multi_a_filter) run on dsp_pulses_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -854,6 +858,73 @@ static bool match_pileup_shape(const PlanCtx& c, const char** why) {
     return true;
 }
 
+// Is the program one of the pulse picker's (dsp_pulses.hip)?
+//   LOAD s;  LOAD of the candidates, a list per row;  PEAK_SNR_THRESHOLD of s and of them;  STORE of idx_out;  STORE_SCALAR of the count (DSP_U32)
+//   LOAD s;  LOAD of the positions;  MULTI_A_FILTER of s and of them;  STORE of va_max_out
+//   LOAD s;  LOAD of the candidates;  PEAK_SNR_THRESHOLD;  MULTI_A_FILTER of s at idx_out;  [STORE of idx_out;]  STORE of va_max_out;  STORE_SCALAR
+// ratio_in is a constant or a column of the loop's type; the width, the lists' lengths and the limits are lower_op's business (every program
+// that holds either op passes there first).  Why not, otherwise: `why`.
+static bool match_pulses_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int n = c.n_ops;
+    *why = "the program must be exactly LOAD, LOAD of the list, PEAK_SNR_THRESHOLD, STORE, STORE_SCALAR; or LOAD, LOAD of the list, MULTI_A_FILTER, STORE; or LOAD, "
+           "LOAD of the list, PEAK_SNR_THRESHOLD, MULTI_A_FILTER, [STORE of idx_out,] STORE of va_max_out, STORE_SCALAR";
+    auto is = [&](int i, int opcode) { return i >= 0 && i < n && ops[i].opcode == opcode; };
+    if (n < 4 || !is(0, DSP_OP_LOAD) || !is(1, DSP_OP_LOAD)) return false;
+    const bool pick = is(2, DSP_OP_PEAK_SNR_THRESHOLD), amp = is(pick ? 3 : 2, DSP_OP_MULTI_A_FILTER);
+    if (!pick && !amp) return false;
+    const int first_store = 2 + (pick ? 1 : 0) + (amp ? 1 : 0);
+    const int n_stores = pick ? n - 1 - first_store : n - first_store;  // (behind them the picker's STORE_SCALAR)
+    if (c.n_slots != 2 + (pick ? 1 : 0) + (amp ? 1 : 0) || (pick && !is(n - 1, DSP_OP_STORE_SCALAR)) || (pick && amp ? n_stores != 1 && n_stores != 2 : n_stores != 1))
+        return false;
+    for (int i = first_store; i < first_store + n_stores; ++i)
+        if (!is(i, DSP_OP_STORE)) return false;
+    const dsp_op* pk = pick ? &ops[2] : nullptr;
+    const dsp_op* am = amp ? &ops[pick ? 3 : 2] : nullptr;
+    const dsp_op& first = pk ? *pk : *am;
+    const dsp_op* ld = ops[0].dst == first.src ? &ops[0] : (ops[1].dst == first.src ? &ops[1] : nullptr);
+    PulsesArgs& A = ch->pulses;
+    memset(&A, 0, sizeof A);
+    ch->uio_list = ch->uio_ratio = ch->uio_idx = ch->uio_n = ch->uio_amp = -1;
+    if (!ld || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, ch->pulses_src, why,
+                          "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
+    *why = "the list is loaded whole into slot ip[0], a list per row in the loop's type";
+    const dsp_op* lt = ld == &ops[0] ? &ops[1] : &ops[0];
+    if (first.ip[0] != lt->dst || lt->dst == first.src || lt->ip[0] != 0 || lt->ip[1] != 0 || io[lt->io].dtype != c.compute_dtype || io[lt->io].len != c.slot_len[lt->dst])
+        return false;
+    ch->uio_list = lt->io;
+    A.list_stride = io[lt->io].row_stride;
+    A.list_offset = io[lt->io].offset;
+    *why = "multi_a_filter in the same program reads the same row at exactly the picker's idx_out";
+    if (pk && am && (am->src != pk->src || am->ip[0] != pk->dst)) return false;
+    *why = "idx_out and va_max_out are stored once each, whole, in the loop's type; the count once, into a DSP_U32 column";
+    for (int i = first_store; i < first_store + n_stores; ++i) {
+        const dsp_op& st = ops[i];
+        const dsp_io_desc& o = io[st.io];
+        int* slot = pk && st.src == pk->dst ? &ch->uio_idx : (am && st.src == am->dst ? &ch->uio_amp : nullptr);
+        if (!slot || *slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        *slot = st.io;
+        (slot == &ch->uio_idx ? A.idx_stride : A.amp_stride) = o.row_stride;
+    }
+    if ((am && ch->uio_amp < 0) || (!am && ch->uio_idx < 0) || (ch->uio_idx >= 0 && ch->uio_idx == ch->uio_amp)) return false;
+    if (pk) {
+        const dsp_op& sc = ops[n - 1];
+        if (sc.ip[0] != pk->ip[1] || io[sc.io].dtype != DSP_U32) return false;
+        ch->uio_n = sc.io;
+        A.n_stride = io[sc.io].row_stride;
+        *why = "ratio_in is a constant or a per-event column of the loop's type";
+        if (!bind_operand(c, *pk, 0, ch->uio_ratio, A.ratio_stride, A.ratio_const)) return false;
+        A.width = dsp_pulses::clamped_width(op_const(c, *pk, 1), A.len);
+    }
+    A.m = c.slot_len[first.ip[0]];
+    A.pick = pk ? 1 : 0;
+    A.amp = am ? 1 : 0;
+    return true;
+}
+
 // Does the program have the shape of the current-branch kernel (dsp_current.hip)?
 //   LOAD s0;  WINDOWER s1 <- s0 (start: constant or float32 column);  AVG_CURRENT s2 <- s1;  UPSAMPLER s3 <- s2;
 //   MOVING_WINDOW_MULTI d <- s3 (3 windows, alternating);  MIN_MAX of d;  STORE_SCALARs of its four registers
@@ -1396,6 +1467,8 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_DWT_HAAR: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[2]; return 3;
         case DSP_OP_MULTI_EXTREMA: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[1]; return 3;
         case DSP_OP_BI_LEVEL_ZERO_CROSSING:
+        case DSP_OP_PEAK_SNR_THRESHOLD:
+        case DSP_OP_MULTI_A_FILTER:
         case DSP_OP_HISTOGRAM: out[0] = o.src; out[1] = o.dst; out[2] = o.ip[0]; return 3;
         case DSP_OP_HISTOGRAM_STATS: out[0] = o.src; out[1] = o.ip[0]; return 2;
         case DSP_OP_MULTI_TIME_POINT_THRESH:
@@ -1577,7 +1650,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows; PEAK_SNR_THRESHOLD, MULTI_A_FILTER: nothing in LDS)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1628,7 +1701,7 @@ static int bind_io(PlanCtx& c) {
             return fail(DSP_ERR_ARG, "io %d: int32/uint32/float64 rows select the float64 loop (compute_dtype DSP_F64)", k);
         const bool is_out = a.kind == DSP_IO_WF_OUT || a.kind == DSP_IO_SCALAR_OUT;
         if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT) &&
-            !(c.only && (c.only->route == DSP_ROUTE_EXTREMA || c.only->route == DSP_ROUTE_PILEUP) && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32))  // (the counts of MULTI_EXTREMA and BI_LEVEL_ZERO_CROSSING: their matchers see to the rest)
+            !(c.only && (c.only->route == DSP_ROUTE_EXTREMA || c.only->route == DSP_ROUTE_PILEUP || c.only->route == DSP_ROUTE_PULSES) && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32))  // (the counts of MULTI_EXTREMA, BI_LEVEL_ZERO_CROSSING and PEAK_SNR_THRESHOLD: their matchers see to the rest)
             return fail(DSP_ERR_ARG, "io %d: outputs have the chain's compute type or DSP_BOOL, taps the compute type", k);
         if ((a.dtype == DSP_BOOL || a.dtype == DSP_I64 || a.dtype == DSP_U64) && a.kind != DSP_IO_SCALAR_IN && a.kind != DSP_IO_SCALAR_OUT && !(a.dtype == DSP_BOOL && is_out))
             return fail(DSP_ERR_ARG, "io %d: DSP_BOOL / DSP_I64 / DSP_U64 are types of per-event columns (DSP_BOOL also of waveform outputs)", k);
@@ -2074,6 +2147,29 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
             }
             if (!f64 && slot_len[o.src] > (1 << 24))
                 return fail(DSP_ERR_UNSUPPORTED, "bi_level_zero_crossing_time_points: the float32 loop takes rows of at most 2^24 samples (%d): a time counts them exactly", slot_len[o.src]);
+            break;
+        }
+        case DSP_OP_PEAK_SNR_THRESHOLD: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || !check_slot(P, o.ip[0]) || o.dst == o.src || o.ip[0] == o.src || o.dst == o.ip[0] || o.ip[1] < 0 ||
+                o.ip[1] >= n_sregs)
+                return fail(DSP_ERR_ARG, "op %d: bad PEAK_SNR_THRESHOLD (src: the slot of the row; ip[0]: the slot of idx_in; dst: another slot, for idx_out; ip[1]: the register of the count)", i);
+            if (slot_len[o.dst] != slot_len[o.ip[0]])
+                return fail(DSP_ERR_ARG, "peak_snr_threshold: idx_out has the length of idx_in (%d and %d)", slot_len[o.dst], slot_len[o.ip[0]]);
+            if (slot_len[o.dst] > DSP_PEAKS_MAX)
+                return fail(DSP_ERR_UNSUPPORTED, "peak_snr_threshold: at most %d candidates (%d given): a wavefront keeps one per lane", DSP_PEAKS_MAX, slot_len[o.dst]);
+            if (o.sp[1].kind != DSP_ARG_CONST)
+                return fail(DSP_ERR_UNSUPPORTED, "peak_snr_threshold: width_in is a constant of the program, not a per-event value");
+            if (!(o.sp[1].value >= 0) || !std::isfinite(o.sp[1].value)) return fail(DSP_ERR_ARG, "peak_snr_threshold: width_in is a non-negative number of samples");
+            break;
+        }
+        case DSP_OP_MULTI_A_FILTER: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || !check_slot(P, o.ip[0]) || o.dst == o.src || o.ip[0] == o.src || o.dst == o.ip[0])
+                return fail(DSP_ERR_ARG, "op %d: bad MULTI_A_FILTER (src: the slot of the row; ip[0]: the slot of vt_maxs_in; dst: another slot, for va_max_out)", i);
+            if (slot_len[o.dst] != slot_len[o.ip[0]])
+                return fail(DSP_ERR_ARG, "multi_a_filter: va_max_out has the length of vt_maxs_in (%d and %d)", slot_len[o.dst], slot_len[o.ip[0]]);
+            if (slot_len[o.dst] > DSP_PEAKS_MAX)
+                return fail(DSP_ERR_UNSUPPORTED, "multi_a_filter: at most %d positions (%d given): a wavefront keeps one per lane", DSP_PEAKS_MAX, slot_len[o.dst]);
+            if (!(slot_len[o.ip[0]] < slot_len[o.src])) return fail(DSP_E_MAF_LEN, "%s", dsp_fatal_message(DSP_E_MAF_LEN));  // multi_a_filter.py:42-45
             break;
         }
         case DSP_OP_DWT_HAAR: {

@@ -462,6 +462,34 @@ struct PileupArgs {
     int64_t n_stride;
 };
 
+// arguments of the pulse picker (dsp_pulses.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> LOAD of the candidates -> PEAK_SNR_THRESHOLD -> STORE of idx_out, STORE_SCALAR of the count
+//   LOAD -> LOAD of the positions -> MULTI_A_FILTER -> STORE of va_max_out
+//   LOAD -> LOAD of the candidates -> PEAK_SNR_THRESHOLD -> MULTI_A_FILTER [-> STORE of idx_out] -> STORE of va_max_out, STORE_SCALAR
+// A wavefront keeps the row's list one entry per lane: nothing lives in LDS.
+#define DSP_PEAKS_MAX 64 /* entries of a list of peak_snr_threshold / multi_a_filter (as DSP_THRESH_MAX, and the peak finder's direction 3) */
+struct PulsesArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples
+    int32_t m;               // entries of the list, 1 .. DSP_PEAKS_MAX
+    int32_t pick;            // 1: peak_snr_threshold runs on the list
+    int32_t amp;             // 1: multi_a_filter runs on the list, or on the packed list of the picker (registers)
+    int32_t width;           // int(width_in), at most len (a wider window is clamped to the row all the same)
+    const void* list;        // idx_in / vt_maxs_in: rows of m values of the loop's type
+    int64_t list_stride;
+    int32_t list_offset;
+    const void* ratio;       // ratio_in: a column of the loop's type, or null: ratio_const
+    int64_t ratio_stride;
+    double ratio_const;
+    void* idx_out;           // rows of m values of the loop's type, or null: not stored
+    int64_t idx_stride;
+    uint32_t* n_out;         // n_idx_out
+    int64_t n_stride;
+    void* amp_out;           // va_max_out: rows of m values of the loop's type
+    int64_t amp_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

@@ -244,6 +244,8 @@ _SIGS = {
     "reflected_convolve_wf": "wtW",  # (w_in, kernel[m], w_out)
     # (w_in, t_tau, w_out); (w_in, a_pos_threshold_in, a_neg_threshold_in, gate_time_in, t_start_in, n_crossings_out, polarity_out[m], t_trig_times_out[m])
     "rc_cr2": "wsW", "bi_level_zero_crossing_time_points": "wssssSWW",
+    # (w_in, idx_in[m], ratio_in, width_in, idx_out[m], n_idx_out); (w_in, vt_maxs_in[m], va_max_out[m]): the lists are waveforms of a stage, m theirs
+    "peak_snr_threshold": "wwssWS", "multi_a_filter": "wwW",
     # ml.py: (x_in, means, variances, x_out); (x_in, kernel[n, m], [bias[m],] activation_func, x_out[m]); (x_in, kernel[n], [bias,] activation_func, x_out)
     "normalisation_layer": "waaW", "dense_layer_no_bias": "wacW", "dense_layer_with_bias": "waacW",
     "classification_layer_no_bias": "wacS", "classification_layer_with_bias": "waacS",
@@ -356,6 +358,7 @@ _ORDER_FILES = {"sort": ("sort",)}  # (processors.ORDER, likewise)
 _RESAMPLING_FILES = {"interpolating_upsampler": ("upsampler",)}  # (processors.RESAMPLING, likewise)
 _SMOOTHING_FILES = {"reflected_convolve_wf": ("convolutions",)}  # (processors.SMOOTHING, likewise; gaussian_filter1d stays refused in recipes)
 _PILEUP_FILES = {"rc_cr2": ("rc_cr2",), "bi_level_zero_crossing_time_points": ("time_point_thresh",)}  # (processors.PILEUP, likewise)
+_PULSE_FILES = {"peak_snr_threshold": ("peak_snr_threshold",), "multi_a_filter": ("multi_a_filter",)}  # (processors.PULSES, likewise; in recipes under these strings only: compiler._add_step)
 _ML_FILES = dict.fromkeys(("normalisation_layer", "dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias",
                            "classification_layer_with_bias"), ("ml",))  # (processors.ML, likewise)
 
@@ -364,7 +367,7 @@ def module_accepted(module, function) -> bool:
     """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
     pre = "dspeed.processors."
     files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ()) + _ORDER_FILES.get(function, ()) + _RESAMPLING_FILES.get(function, ())
-    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ()) + _PILEUP_FILES.get(function, ())
+    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ()) + _PILEUP_FILES.get(function, ()) + _PULSE_FILES.get(function, ())
     return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in files)
 
 

@@ -764,5 +764,111 @@ bi_level_zero_crossing_time_points = HipGUFunc("bi_level_zero_crossing_time_poin
 # Listed here and not in __all__, like the smoothing processors: their call records are tests/test_pileup_plan_cpu.py's.
 PILEUP = ("rc_cr2", "bi_level_zero_crossing_time_points")
 
+
+# --------------------------------------------------------------------------------------------------- pulses
+def check_pulse_list(what, n, m, m_out=None, pickoff=False):
+    """what the planner checks of a list of ``m`` entries on rows of ``n`` samples, in the reference's words where it has them"""
+    if m_out is not None and m_out != m:
+        raise ValueError(f"{what}: the output has the length of the list ({m} entries, {m_out} given)")
+    if m > _lib.PEAKS_MAX:
+        raise NotImplementedError(f"{what}: at most {_lib.PEAKS_MAX} list entries ({m} given): a wavefront keeps one per lane")
+    if pickoff and not m < n:
+        raise DSPFatal("The length of your return array must be smaller than the length of your waveform")
+
+
+def check_pulse_width(what, width):
+    """width_in as the kernel takes it: one non-negative, finite number of samples"""
+    a = np.asarray(width.magnitude if hasattr(width, "magnitude") else width)
+    if a.size != 1:
+        raise NotImplementedError(f"{what}: per-waveform integer parameters are not supported on the device")
+    w = float(a.reshape(-1)[0])
+    if not (w >= 0 and np.isfinite(w)):
+        raise ValueError(f"{what}: width_in is a non-negative number of samples")
+    return w
+
+
+def _pulse_list(c, what, v, name):
+    """a '(m)' input on the device: (array, m, row stride); one list is repeated for every row"""
+    if isinstance(v, DeviceArray):
+        if v.dtype != np.dtype(c.ft):
+            raise TypeError(f"{what}: {name} on the device has the loop's type, {np.dtype(c.ft)}")
+        shape, dev = tuple(v.shape), v
+    else:
+        host = np.ascontiguousarray(np.asarray(v), dtype=c.ft)
+        shape, dev = host.shape, None
+    if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] != c.n_wf) or (dev is not None and len(shape) == 1 and c.n_wf != 1):
+        raise ValueError(f"{what}: {name} has shape {shape}, expected ({c.n_wf}, m)" + ("" if dev is not None else " or (m,)"))
+    m = int(shape[-1])
+    if dev is None and m > 0 and m <= _lib.PEAKS_MAX:
+        dev = DeviceArray.from_numpy(np.ascontiguousarray(np.broadcast_to(host, (c.n_wf, m))))
+        c.st.keep.append(dev)
+    return dev, m, m
+
+
+def _pulse_out(c, given, m, dtype=None):
+    """an output of m values a row (``m`` None: a value a row), the caller's or a new one"""
+    if given is not None and not isinstance(given, (np.ndarray, DeviceArray)):
+        raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+    shape = () if m is None else (m,)
+    ptr, res = c.st.out(given, shape if c.one_d else (c.n_wf, *shape), dtype or c.ft)
+    c.results.append(res)
+    return ptr
+
+
+def _results(c):
+    res = [r[()] if isinstance(r, np.ndarray) and r.ndim == 0 else r for r in c.results]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def _peak_snr_threshold(g, *args):
+    """one C entry for both loops, like sort's.  ``width_in`` is a constant of the call, ``ratio_in`` one value or a value per row; the
+    outputs may be left out: their length is that of ``idx_in``."""
+    what = g.__name__
+    (w_in, idx_in, ratio, width), (idx_out, n_out) = _split(g, args)
+    width = check_pulse_width(what, width)
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        lst, m, stride = _pulse_list(c, what, idx_in, "idx_in")
+        check_pulse_list(what, c.n, m, None if idx_out is None else (int(idx_out.shape[-1]) if len(idx_out.shape) else 0))
+        col = c.col(ratio)
+        if m == 0:  # no candidate: nothing to launch, the counts are 0
+            zeros = np.zeros(() if c.one_d else (c.n_wf,), np.uint32)
+            if isinstance(n_out, DeviceArray):
+                n_out.copy_from(zeros.reshape(n_out.shape))
+            elif n_out is not None:
+                n_out[...] = 0
+            return (idx_out if idx_out is not None else np.empty((0,) if c.one_d else (c.n_wf, 0), c.ft)), (n_out if n_out is not None else zeros[()])
+        po, pn = _pulse_out(c, idx_out, m), _pulse_out(c, n_out, None, np.uint32)
+        run(getattr(_lib.lib(), "dsp_peak_snr_threshold_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, lst.ptr, m, stride, *col,
+            width, po, m, pn)
+        c.st.finish()
+        return _results(c)
+
+
+def _multi_a_filter(g, *args):
+    """one C entry for both loops; ``va_max_out`` may be left out: its length is that of ``vt_maxs_in``"""
+    what = g.__name__
+    (w_in, vt), (out,) = _split(g, args)
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        lst, m, stride = _pulse_list(c, what, vt, "vt_maxs_in")
+        check_pulse_list(what, c.n, m, None if out is None else (int(out.shape[-1]) if len(out.shape) else 0), pickoff=True)
+        if m == 0:
+            return out if out is not None else np.empty((0,) if c.one_d else (c.n_wf, 0), c.ft)
+        po = _pulse_out(c, out, m)
+        run(getattr(_lib.lib(), "dsp_multi_a_filter_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, lst.ptr, m, stride, po, m)
+        c.st.finish()
+        return _results(c)
+
+
+peak_snr_threshold = HipGUFunc("peak_snr_threshold", "(n),(m),(),()->(m),()", ["ffff->fI", "dddd->dI"], _peak_snr_threshold,
+                               "of the candidates idx_in those whose window [c - width, c + width) -- clamped to the row, its upper end excluded -- "
+                               "goes down to less than ratio_in of the sample at c: packed to the front, NaN-padded, and their number; m <= 64, "
+                               "width_in a constant of the call (reference processors/peak_snr_threshold.py:19-71)")
+multi_a_filter = HipGUFunc("multi_a_filter", "(n),(m)->(m)", ["ff->f", "dd->d"], _multi_a_filter,
+                           "the row's samples at the whole-numbered positions vt_maxs_in, NaN for a NaN position or one outside the row; a row with "
+                           "a NaN: NaNs; m <= 64 and m < n (reference processors/multi_a_filter.py:20-57)")
+
+# Listed here and not in __all__, like the pile-up processors: their call records are tests/test_pulse_plan_cpu.py's.
+PULSES = ("peak_snr_threshold", "multi_a_filter")
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

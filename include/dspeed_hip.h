@@ -76,6 +76,7 @@ extern "C" {
 #define DSP_E_FFT_LEN 33       /* fft.py:39-40    "Size of fft must be len(w_in)//2+1 = ..." (the text carries the length: dsp_last_error) */
 #define DSP_E_PSD_LEN 34       /* fft.py:119-120  "Size of psd must be len(w_in)//2+1 = ..." */
 #define DSP_E_RC_CR2_NAN 35    /* rc_cr2.py:93-94          data dependent */
+#define DSP_E_MAF_LEN 36       /* multi_a_filter.py:42-45  "The length of your return array must be smaller than the length of your waveform" */
 
 /* ---- element types -------------------------------------------------------------------------- */
 #define DSP_F32 0
@@ -324,6 +325,23 @@ typedef struct dsp_scalar_arg {
                                  *   LOAD, RC_CR2, BI_LEVEL_ZERO_CROSSING of the filtered row, [STORE of the filtered row,] STORE, STORE, STORE_SCALAR
                                  * where the walk tests the filtered value as stored (rounded to the loop's type) and the filtered row goes to
                                  * memory only if it is stored */
+#define DSP_OP_PEAK_SNR_THRESHOLD 48 /* peak_snr_threshold.py:19-71: of the candidates in slot ip[0] (m <= DSP_PEAKS_MAX sample indices of src, NaN:
+                                 * none) those are kept, in list order, for which |src[min_index] / src[c]| < sp[0], c = int(candidate) and min_index
+                                 * the first minimum of src over [max(c - w, 0), min(c + w, n - 1)) -- the upper end excluded --, w = int(sp[1]), a
+                                 * constant >= 0 of the program.  dst = the slot of idx_out (m values: the kept candidates as given, packed to the
+                                 * front, NaN behind them), sreg[ip[1]] <- n_idx_out (a DSP_U32 column); sp[0] = ratio_in, a constant or a per-event
+                                 * column of the loop's type.  A row with a NaN is a row like any other.  Where the reference defines nothing: a
+                                 * candidate that is infinite or whose int() lies outside [0, n) is dropped and no sample read; src[c] == 0 divides
+                                 * as IEEE does and the candidate is dropped.  It runs on dsp_pulses_kernel only (the shapes: below) */
+#define DSP_OP_MULTI_A_FILTER 49 /* multi_a_filter.py:20-57: dst (m values) <- src at the positions in slot ip[0] (m < n of them): entry j is
+                                 * fixed_time_pickoff(src, vt[j], 'i') -- NaN for a NaN, a negative position or one above n - 1, src[int(vt[j])] for
+                                 * a whole number, DSP_E_FTP_INT with the row otherwise; a row with a NaN: all NaN.  m >= n: DSP_E_MAF_LEN.  It runs
+                                 * on dsp_pulses_kernel only, a wavefront per row, in a program of exactly
+                                 *   LOAD, LOAD of the candidates, PEAK_SNR_THRESHOLD, STORE of idx_out, STORE_SCALAR of the count
+                                 *   LOAD, LOAD of the positions, MULTI_A_FILTER, STORE of va_max_out
+                                 *   LOAD, LOAD of the candidates, PEAK_SNR_THRESHOLD, MULTI_A_FILTER of the same row at idx_out, [STORE of idx_out,]
+                                 *   STORE of va_max_out, STORE_SCALAR of the count
+                                 * where idx_out goes to memory only if it is stored */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -625,6 +643,22 @@ int dsp_bi_level_zero_crossing_rows(const void* in, int in_dtype, int64_t n_wf, 
                                     const void* a_pos_threshold_dev, double a_pos_threshold, const void* a_neg_threshold_dev, double a_neg_threshold,
                                     const void* gate_time_dev, double gate_time, const void* t_start_dev, double t_start, uint32_t* n_crossings_out,
                                     void* polarity_out, void* t_trig_times_out, int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(m),(),()->(m),()" peak_snr_threshold (peak_snr_threshold.py:19-71; DSP_OP_PEAK_SNR_THRESHOLD).  One entry for both loops, like
+ * dsp_sort_rows.  idx_in_dev: rows of list_len <= DSP_PEAKS_MAX candidates of the loop's type on the device, idx_in_stride apart; ratio: a
+ * column of the loop's type on the device or, where that is null, the constant beside it; width: a non-negative number of samples.
+ * idx_out: rows of list_len values, out_stride apart (the kept candidates, then NaN); n_idx_out: a uint32 per row.  list_len 0: nothing is
+ * launched. */
+int dsp_peak_snr_threshold_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype,
+                                const void* idx_in_dev, int32_t list_len, int64_t idx_in_stride, const void* ratio_dev, double ratio, double width,
+                                void* idx_out, int64_t out_stride, uint32_t* n_idx_out, void* stream, int64_t* err_row);
+
+/* "(n),(m)->(m)" multi_a_filter (multi_a_filter.py:20-57; DSP_OP_MULTI_A_FILTER).  vt_maxs_in_dev: rows of list_len < wf_len positions of
+ * the loop's type on the device, vt_stride apart; va_max_out: rows of list_len values, out_stride apart.  Returns DSP_E_FTP_INT with
+ * *err_row for a position that is no whole number, DSP_E_MAF_LEN for list_len >= wf_len.  list_len 0: nothing is launched. */
+int dsp_multi_a_filter_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype,
+                            const void* vt_maxs_in_dev, int32_t list_len, int64_t vt_stride, void* va_max_out, int64_t out_stride, void* stream,
+                            int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
