@@ -19,6 +19,7 @@ OK, ERR_HIP, ERR_ARG, ERR_UNSUPPORTED, ERR_TOO_LONG = 0, -1, -2, -3, -4
 E_ZERODIV = 17
 HIST_MAX_BINS = 2048  # DSP_HIST_MAX_BINS (dsp_program.h): the bins dsp_hist_kernel keeps counters for
 PEAKS_MAX = 64  # DSP_PEAKS_MAX (dsp_program.h): the entries of a list of peak_snr_threshold / multi_a_filter, one per lane of dsp_pulses_kernel
+POLY_MAX = 8  # DSP_POLY_MAX (dsp_program.h): the coefficients of poly_fit / poly_diff / poly_exp_rms, a float64 accumulator per lane of dsp_tailfit_kernel each
 THRESH_MAX = 64  # DSP_THRESH_MAX (dsp_program.h): the thresholds of one multi_time_point_thresh, one per lane of dsp_thresh_kernel
 # DSP_SPECTRUM_* (dsp_program.h): the longest rows of psd / fft in the float32 loop, a power of two / any other length (float64: half of each)
 SPECTRUM_F32_POW2_MAX, SPECTRUM_F32_ANY_MAX = 16384, 4096
@@ -36,7 +37,7 @@ ARG_CONST, ARG_INPUT, ARG_REG = range(3)
  OP_SCALAR_AFFINE, OP_MEAN_BELOW, OP_CONVOLVE_AMAX, OP_WINDOWER, OP_AVG_CURRENT, OP_TRAP_WINDOW_PICKOFF, OP_TRAP_REDUCE, OP_UPSAMPLER, OP_MOVING_WINDOW_MULTI, OP_LINEAR_SLOPE_FIT,
  OP_SCALAR_CONVERT, OP_SCALAR_DIV, OP_INTERP_TIME_POINT_THRESH, OP_MIN_MAX_NORM, OP_ELEMENTWISE, OP_SCALAR_FUNC, OP_MULTI_EXTREMA, OP_HISTOGRAM,
  OP_HISTOGRAM_STATS, OP_MULTI_TIME_POINT_THRESH, OP_TIME_OVER_THRESHOLD, OP_PSD, OP_FFT, OP_SORT, OP_INTERP_UPSAMPLE, OP_NORMALISE, OP_DENSE, OP_REFLECTED_CONVOLVE, OP_RC_CR2, OP_BI_LEVEL_ZERO_CROSSING,
- OP_PEAK_SNR_THRESHOLD, OP_MULTI_A_FILTER) = range(1, 50)
+ OP_PEAK_SNR_THRESHOLD, OP_MULTI_A_FILTER, OP_LOG_CHECK, OP_POLY_FIT, OP_POLY_DIFF, OP_POLY_EXP_RMS) = range(1, 54)
 (FN_ADD, FN_SUB, FN_MUL, FN_DIV, FN_LT, FN_LE, FN_GT, FN_GE, FN_EQ, FN_NE, FN_WHERE, FN_ISNAN, FN_ISFINITE, FN_NEG, FN_COPY, FN_FLOORDIV,
  FN_IADD, FN_ISUB, FN_IMUL, FN_IFLOORDIV, FN_ICAST, FN_LOR, FN_LAND, FN_RINT, FN_FLOOR, FN_CEIL, FN_TRUNC) = range(27)
 
@@ -162,6 +163,9 @@ SIG = {
         "dsp_bi_level_zero_crossing_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, C.c_double, vp, C.c_double, vp, C.c_double, vp, C.c_double, vp, vp, vp, i32, i64, vp, pi64],
         "dsp_peak_snr_threshold_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, i64, vp, C.c_double, C.c_double, vp, i64, vp, vp, pi64],
         "dsp_multi_a_filter_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, i64, vp, i64, vp, pi64],
+        "dsp_log_check_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i64, vp, pi64],
+        "dsp_poly_fit_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, vp, i64, vp, pi64],
+        "dsp_poly_residual_rows": [vp, C.c_int, i64, i32, i64, C.c_int, i32, vp, i32, i64, vp, vp, vp, pi64],
         "dsp_synth_waveforms": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_synth_pulses": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_stream_read": [vp, i64, vp, vp],

@@ -37,11 +37,13 @@ _MULTI_TPT, _TIME_OVER = "multi_time_point_thresh", "time_over_threshold"
 _PSD, _SORT, _INTERP, _REFLECT = "psd", "sort", "interpolating_upsampler", "reflected_convolve_wf"
 _RC_CR2, _BI_LEVEL = "rc_cr2", "bi_level_zero_crossing_time_points"
 _PEAK_SNR, _MULTI_A = "peak_snr_threshold", "multi_a_filter"
+_LOG_CHECK, _POLY_FIT, _POLY_DIFF, _POLY_EXP_RMS = "log_check", "poly_fit", "poly_diff", "poly_exp_rms"
+_TAILFIT = (_LOG_CHECK, _POLY_FIT, _POLY_DIFF, _POLY_EXP_RMS)
 _NORMALISE = "normalisation_layer"
 _DENSE_LAYERS = ("dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
 _ML = (_NORMALISE,) + _DENSE_LAYERS
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL, _PEAK_SNR, _MULTI_A) + _ML  # processors that run as stages ahead of the program, on kernels of their own
-_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT, _RC_CR2)
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL, _PEAK_SNR, _MULTI_A) + _TAILFIT + _ML  # processors that run as stages ahead of the program, on kernels of their own
+_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT, _RC_CR2, _LOG_CHECK)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
 
@@ -122,6 +124,8 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         # dspeed.processors.multi_a_filter, as the SiPM configs write them; under the package's string they stay refused, in these words:
         # tests/test_histogram_plan_cpu.py and the recorded translations hold that -- as they hold gaussian_filter1d's refusal)
         raise NotImplementedError(f"processor '{function}' is not implemented on the device path")
+    if "init_args" in node and function != _POLY_FIT:
+        raise NotImplementedError(f"{function} ({key}): init_args builds a processor from a factory; on the device path only poly_fit is one")
     roles = _SIGS[function]
     if len(args) != len(roles):
         raise ProcessingChainError(f"{function} takes {len(roles)} arguments ({len(args)} given) for parameter {key}")
@@ -164,6 +168,7 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
                 out.is_coord, out.grid = True, _grid_of(args[0])
         if function == _PEAK_SNR and isinstance(args[5], Var):
             args[5].out_dtype = np.dtype(np.uint32)
+    inverse = _poly_fit_inverse(b, node, args, key) if function == _POLY_FIT else None
     if function == _MULTI_TPT:
         # its thresholds are one constant list, or a list per event read from rows in memory; its times are sample indices of the input:
         # with a time unit they are coordinates on its grid, written in that unit like the peak finder's lists
@@ -179,8 +184,50 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
     args = [_as_taps(b, a, function) if r == "t" else a for a, r in zip(args, roles)]
     args = [_group_constant(b, a, function, key) if r == "i" and isinstance(a, (Var, SExpr)) else a for a, r in zip(args, roles)]
     _, args = _resolve(b, roles, args, same_dim_out=function in _SAME_DIM)
+    if inverse is not None:
+        args = list(args) + [inverse]  # (behind the arguments the roles name: a constant of the step)
     b.steps.append((function, args, key))
     proc_strings.append(f"{function}({', '.join(str(a.name if isinstance(a, (Var, SExpr)) else a) for a in args)})")
+
+
+def _poly_fit_inverse(b: _Builder, node, args, key):
+    """``poly_fit`` is a factory in the reference: ``init_args`` -- (length, deg), each an expression of the language, ``len(wf_logged)`` among
+    them -- builds the gufunc (processing_chain.py:2723-2773).  Both are constants of the chain; the inverted matrix is formed here, once, and
+    travels as a constant array behind the step's arguments: returned.  The coefficients are a row of ``deg + 1``: that is their length where the declaration
+    gives none, and must be where it gives one."""
+    from .processors import check_poly, check_poly_fit_init, poly_fit_inverse
+
+    what = f"{_POLY_FIT} ({key})"
+    init = node.get("init_args")
+    if not isinstance(init, (list, tuple)) or len(init) != 2:
+        raise ProcessingChainError(f"{what}: init_args holds length and deg, as the factory takes them")
+    vals = []
+    for name, a in zip(("length", "deg"), init):
+        v = b.eval_arg(a) if isinstance(a, str) else a
+        if isinstance(v, Var) and v.kind == "const":
+            v = v.const
+        if isinstance(v, (Var, SExpr, View)):
+            raise NotImplementedError(f"{what}: {name} is a constant of the call on the device, not a per-event value")
+        vals.append(v)
+    try:
+        length, deg = check_poly_fit_init(what, *vals)
+    except ValueError as e:
+        raise ProcessingChainError(str(e)) from None
+    src, out = args
+    if not _is_wf(src):
+        raise ProcessingChainError(f"{what}: '{src}' is not a waveform")
+    if not isinstance(out, Var):
+        raise ProcessingChainError(f"{what}: the coefficients are a variable name")
+    if out.length is None:
+        out.length = deg + 1
+    if out.length != deg + 1:
+        raise ProcessingChainError(f"{what}: poly_pars holds deg + 1 = {deg + 1} coefficients ({out.length} declared)")
+    check_poly(what, max(length, src.length), deg + 1)
+    try:
+        inv = poly_fit_inverse(length, deg)
+    except np.linalg.LinAlgError as e:  # (length <= deg: the reference's factory raises there too)
+        raise ProcessingChainError(f"{what}: the matrix of power sums over range({length}) cannot be inverted for deg = {deg} ({e})") from None
+    return Var(f"inv#{out.name}", "taps", (deg + 1) ** 2, np.float64, const=np.ascontiguousarray(inv, dtype=np.float64))
 
 
 class _PerEventInteger(Exception):
@@ -1052,7 +1099,8 @@ def _stage_reflected_convolve(cx: _Stager, only=None):
 
 def _pileup_rows(cx: _Stager, src, fn, key, reader):
     """The rows the pile-up kernel reads: a chain input or a stage's waveform as it is (behind the stages of what it comes from).  A
-    ``bl_subtract`` of a chain input by a per-event value in memory, whose result only ``reader`` reads and the recipe does not ask for, joins
+    ``bl_subtract`` of a chain input by a per-event value in memory, whose result only ``reader`` (a step, or a list of them: the steps of one
+    launch) reads and the recipe does not ask for, joins
     the launch -- one float subtraction as the rows are read, as ``_fir_input_as_rows`` has it for the long filters: returned, for the
     stage's group.  Anything else is written to memory first."""
     base = _base_of(src)
@@ -1061,7 +1109,7 @@ def _pileup_rows(cx: _Stager, src, fn, key, reader):
     _stage_producers(cx, base)
     pst = cx.producer_of(base) if not cx.row_input(base) else None
     if (pst is not None and src is base and pst[0] == "bl_subtract" and isinstance(pst[1][0], Var) and cx.row_input(pst[1][0])
-            and base.name not in cx.out_names and all(u is reader for u in cx.users_of(base))
+            and base.name not in cx.out_names and all(any(u is r for r in (reader if isinstance(reader, list) else [reader])) for u in cx.users_of(base))
             and (_is_number(pst[1][1]) or all(cx.plain_scalar(leaf) for leaf in _leaves(pst[1][1], [])))):
         bargs = list(pst[1])
         bargs[1] = _operand_in_memory(cx, bargs[1], "bl_subtract", pst[2])
@@ -1175,6 +1223,84 @@ def _stage_pulses(cx: _Stager, only=None):
         cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
 
 
+def _same_rows(a, b) -> bool:
+    """the same variable, or the same slice of the same variable"""
+    return a is b or (isinstance(a, View) and a == b)
+
+
+def _stage_tailfit(cx: _Stager, only=None):
+    """``log_check``, ``poly_fit``, ``poly_diff`` and ``poly_exp_rms`` run on dsp_tailfit.hip and nowhere else, on rows in HBM: mandatory stages,
+    like the pile-up kernel's.  Each owns one launch: a ``poly_diff`` / ``poly_exp_rms`` that reads exactly a ``poly_fit``'s coefficients, and
+    the rows that fit was made of (or their logarithm), takes the fit into its launch, and the fit a ``log_check`` whose result it reads; the
+    logged row and the coefficients are then written only if something else reads them or the recipe asks for them (``_stage_histogram``'s
+    rule for weights and borders).  A ``bl_subtract`` nothing else reads joins as in ``_pileup_rows``.  ``mean`` and ``rms`` are per-event
+    values, the coefficients a row of m."""
+    from .processors import check_poly
+
+    def producer(v, fn):
+        st = cx.producer_of(v) if isinstance(v, Var) else None
+        return st if st is not None and st[0] == fn and cx.has(st) else None
+
+    def fit_checked(st):
+        fn, (src, out, _inv), key = st
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        check_poly(f"{fn} ({key})", src.length, out.length)
+        return src, out
+
+    def log_checked(st):
+        fn, (src, out), key = st
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        if not (isinstance(out, Var) and out.kind == "wf" and out.length == src.length):
+            raise ProcessingChainError(f"{fn} ({key}): the output is a waveform variable of the source's {src.length} samples")
+        return src, out
+
+    def wanted(v, group):
+        return v.name in cx.out_names or any(not any(u is g for g in group) for u in cx.users_of(v))
+
+    def fit_group(ft):
+        """the fit with the log_check it reads, if there is one: (steps, rows, the logged row or None, the coefficients)"""
+        src, pars = fit_checked(ft)
+        lg = producer(src, _LOG_CHECK)
+        if lg is None:
+            return [ft], src, None, pars
+        rows, logged = log_checked(lg)
+        return [lg, ft], rows, logged, pars
+
+    for fn in (_POLY_DIFF, _POLY_EXP_RMS):
+        for st in cx.steps_of(fn, only):
+            (src, pars, mean, rms), key = st[1], st[2]
+            if _base_of(src) is None:
+                raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+            if not _is_wf(pars) or not pars.length:
+                raise ProcessingChainError(f"{fn} ({key}): the coefficients are an array per event: a poly_fit's or a two-dimensional input column, not {pars!r}")
+            if not (isinstance(mean, Var) and isinstance(rms, Var)):
+                raise ProcessingChainError(f"{fn} ({key}): name the two outputs")
+            check_poly(f"{fn} ({key})", src.length, pars.length)
+            ft = producer(pars, _POLY_FIT)
+            if ft is not None:
+                group, rows, logged, _ = fit_group(ft)
+                if _same_rows(src, rows) or (logged is not None and src is logged):
+                    group = group + [st]
+                    pre = _pileup_rows(cx, rows, group[0][0], group[0][2], group)
+                    wfs = ([logged] if logged is not None and wanted(logged, group) else []) + ([pars] if wanted(pars, group) else [])
+                    cx.stage(pre + group, [mean, rms], " + ".join(f"{g[0]} {g[2]}" for g in group) + " in one launch on rows", wfs=wfs, rows_first=True)
+                    continue
+            _rows_in_memory(cx, pars, fn, key)  # (a fit's coefficients: its stage first)
+            pre = _pileup_rows(cx, src, fn, key, st)
+            cx.stage(pre + [st], [mean, rms], f"{fn} {key} on rows", rows_first=True)
+    for st in cx.steps_of(_POLY_FIT, only):
+        group, rows, logged, pars = fit_group(st)
+        pre = _pileup_rows(cx, rows, group[0][0], group[0][2], group)
+        wfs = ([logged] if logged is not None and wanted(logged, group) else []) + [pars]
+        cx.stage(pre + group, [], " + ".join(f"{g[0]} {g[2]}" for g in group) + (" in one launch" if len(group) > 1 else "") + " on rows", wfs=wfs, rows_first=True)
+    for st in cx.steps_of(_LOG_CHECK, only):
+        src, out = log_checked(st)
+        pre = _pileup_rows(cx, src, st[0], st[2], st)
+        cx.stage(pre + [st], [], f"{st[0]} {st[2]} on rows", wfs=[out], rows_first=True)
+
+
 def _stage_ml_layers(cx: _Stager, only=None):
     """The neural-network layers (ml.py) run on dsp_dense.hip and nowhere else, on rows in HBM: mandatory stages, like sort's.  Each dense or
     classification layer is a launch on rows in memory -- a chain input, a stage's waveform (the layer before it), or a waveform the program
@@ -1221,7 +1347,7 @@ def _stage_ml_layers(cx: _Stager, only=None):
 
 
 #: the family that stages each processor with a kernel of its own (``_stage_producers`` asks it for one step)
-_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _RC_CR2: _stage_pileup, _BI_LEVEL: _stage_pileup, _PEAK_SNR: _stage_pulses, _MULTI_A: _stage_pulses, _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
+_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _RC_CR2: _stage_pileup, _BI_LEVEL: _stage_pileup, _PEAK_SNR: _stage_pulses, _MULTI_A: _stage_pulses, **dict.fromkeys(_TAILFIT, _stage_tailfit), _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
               _MULTI_EXTREMA: _stage_multi_extrema, _MULTI_TPT: _stage_thresholds, _TIME_OVER: _stage_thresholds, _PSD: _stage_spectrum,
               _SORT: _stage_sort, _INTERP: _stage_interp_upsampler, **dict.fromkeys(_ML, _stage_ml_layers)}
 
@@ -1253,6 +1379,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_thresholds(cx)
     _stage_pileup(cx)
     _stage_pulses(cx)
+    _stage_tailfit(cx)
     _stage_spectrum(cx)
     _stage_sort(cx)
     _stage_interp_upsampler(cx)
@@ -1940,6 +2067,34 @@ class _Emitter:
         self.release(lst, si)
         self.release(src, si)
 
+    def log_check(self, si, fn, args, what):
+        """LOAD, [BL_SUBTRACT,] LOG_CHECK of the tail-fit stage; a poly_fit of the logged row may follow, then the stores"""
+        src = self.ensure_loaded(args[0], si)
+        out = self.out_wf(args[1], src.length, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_LOG_CHECK, dst=out.slot, src=src.slot)
+        self.release(src, si)
+
+    def poly_fit(self, si, fn, args, what):
+        """POLY_FIT on the rows of the stage, or on the logged row of the same program; the inverted matrix is a float64 binding in both loops"""
+        src, inv = self.ensure_loaded(args[0], si), args[2]
+        out = self.out_wf(args[1], None, fn)
+        out.slot = self.new_slot(out.length)
+        if inv.io is None:
+            inv.io = self.p.add_io(f"taps:{inv.name}", _lib.IO_TAPS, np.float64, inv.length, 0, 0)
+            self.consts[f"taps:{inv.name}"] = np.ascontiguousarray(inv.const, dtype=np.float64).reshape(-1)
+        self.p.add_op(_lib.OP_POLY_FIT, dst=out.slot, src=src.slot, io=inv.io)
+        self.release(src, si)
+
+    def poly_residual(self, si, fn, args, what):
+        """POLY_DIFF / POLY_EXP_RMS on rows and coefficients loaded from memory, or on the rows (or the logged row) and the coefficients of a
+        poly_fit in the same program; the stores of its two results follow"""
+        src, pars = self.ensure_loaded(args[0], si), self.ensure_loaded(args[1], si)
+        first = self.out_row(args[2:4], f"{what}: mean and rms must be variable names")
+        self.p.add_op(_lib.OP_POLY_DIFF if fn == _POLY_DIFF else _lib.OP_POLY_EXP_RMS, dst=first, src=src.slot, ip=(pars.slot,))
+        self.release(pars, si)
+        self.release(src, si)
+
     def taps_io(self, v):
         """the binding of a constant array, made at its first use"""
         if v.io is None:
@@ -2152,6 +2307,7 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
          _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler, _REFLECT: _Emitter.reflected_convolve, _RC_CR2: _Emitter.rc_cr2,
          _BI_LEVEL: _Emitter.bi_level_zero_crossing, _PEAK_SNR: _Emitter.peak_snr_threshold, _MULTI_A: _Emitter.multi_a_filter,
+         _LOG_CHECK: _Emitter.log_check, _POLY_FIT: _Emitter.poly_fit, _POLY_DIFF: _Emitter.poly_residual, _POLY_EXP_RMS: _Emitter.poly_residual,
          _NORMALISE: _Emitter.normalisation_layer, **dict.fromkeys(_DENSE_LAYERS, _Emitter.dense_layer)}
 
 

@@ -542,6 +542,38 @@ int dsp_multi_a_filter_rows(ROWS, int compute_dtype, const void* vt_maxs_in_dev,
         return DSP_OK;
     });
 }
+// log_check, poly_fitter, poly_diff / poly_exp_rms: one entry each for both loops; the inverted matrix is bound like a filter's taps, float64 in
+// both loops, the coefficients of the residuals are loaded like rows, a row per event
+int dsp_log_check_rows(ROWS, int compute_dtype, void* out, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "log_check: compute_dtype is DSP_F32 or DSP_F64");
+    return wf2wf(compute_dtype, DSP_OP_LOG_CHECK, IN, {}, {}, {out, wf_len, out_stride}, TAIL_ARGS);
+}
+int dsp_poly_fit_rows(ROWS, int compute_dtype, const double* inv_dev, int32_t n_pars, void* poly_pars_out, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "poly_fit: compute_dtype is DSP_F32 or DSP_F64");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (n_pars < 1 || !inv_dev) return dsp_fail(DSP_ERR_ARG, "poly_fit: inv_dev holds the n_pars * n_pars >= 1 float64 values of the inverted matrix on the device");
+        if (n_pars > DSP_POLY_MAX) return dsp_fail(DSP_ERR_UNSUPPORTED, "poly_fit: " DSP_POLY_MAX_TEXT, DSP_POLY_MAX, n_pars);  // (ahead of the product below)
+        const int s_in = m.load(IN), s_out = m.add_slot(n_pars);
+        const int io_inv = m.add_io(DSP_IO_TAPS, DSP_F64, n_pars * n_pars, 0, inv_dev);
+        m.op(DSP_OP_POLY_FIT, s_out, s_in, io_inv);
+        m.store(s_out, {poly_pars_out, n_pars, out_stride});
+        return DSP_OK;
+    });
+}
+int dsp_poly_residual_rows(ROWS, int compute_dtype, int32_t exp_rms, const void* poly_pars_dev, int32_t n_pars, int64_t pars_stride, void* mean_out, void* rms_out,
+                           TAIL) {
+    const char* name = exp_rms ? "poly_exp_rms" : "poly_diff";
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "%s: compute_dtype is DSP_F32 or DSP_F64", name);
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (n_pars < 1 || !poly_pars_dev) return dsp_fail(DSP_ERR_ARG, "%s: poly_pars_dev holds n_pars >= 1 coefficients per row on the device", name);
+        m.n_sregs = 2;
+        const int s_in = m.load(IN), s_pars = m.load({poly_pars_dev, compute_dtype, n_wf, n_pars, pars_stride});
+        m.op(exp_rms ? DSP_OP_POLY_EXP_RMS : DSP_OP_POLY_DIFF, 0, s_in, 0, {s_pars});
+        m.store_scalar(0, mean_out, compute_dtype);
+        m.store_scalar(1, rms_out, compute_dtype);
+        return DSP_OK;
+    });
+}
 #undef ROWS
 #undef IN
 #undef TAIL

@@ -712,6 +712,22 @@ static int launch_pulses(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void
     return launch_on_rows(ch, n_wf, stream, A, ch->pulses_src, dsp_internal_launch_pulses, "pulse kernel launch");
 }
 
+static int launch_tailfit(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    TailfitArgs A = ch->tailfit;
+    A.wf = io_ptrs[ch->tailfit_src.io];  // (the inputs' offsets travel in the arguments)
+    A.pars = ch->aio_pars < 0 ? nullptr : io_ptrs[ch->aio_pars];
+    A.sub = at(ch->aio_sub);
+    A.inv = (const double*)at(ch->aio_inv);
+    A.out = at(ch->aio_out);
+    A.pars_out = at(ch->aio_pars_out);
+    A.mean_out = at(ch->aio_mean);
+    A.rms_out = at(ch->aio_rms);
+    // 16-byte stores: launch_interp's rule (the plan vouches for the stride, this call's pointer for the start)
+    A.out_vec = A.out && (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
+    return launch_on_rows(ch, n_wf, stream, A, ch->tailfit_src, dsp_internal_launch_tailfit, "tail-fit kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -902,6 +918,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_REFLECT)) return launch_reflect(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_PILEUP)) return launch_pileup(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_PULSES)) return launch_pulses(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_TAILFIT)) return launch_tailfit(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -1020,6 +1037,9 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
         }
         case DSP_ROUTE_PILEUP:  // a tile of 64 rows per wavefront, one wavefront a workgroup
             lds = dsp_pileup::lds_bytes(ch->f64 ? 8 : 4), wpb = 1, b = (int)dsp_pileup::tiles(n_wf);
+            break;
+        case DSP_ROUTE_TAILFIT:  // the same tile, and the table of powers beside it
+            lds = dsp_tailfit::lds_bytes(ch->f64 ? 8 : 4), wpb = 1, b = (int)dsp_tailfit::tiles(n_wf);
             break;
         case DSP_ROUTE_DENSE:  // a tile of 64 rows per workgroup; the normalisation alone: a wavefront per row
             if (ch->dense.m > 0)

@@ -20,6 +20,7 @@ enum dsp_route {
     DSP_ROUTE_REFLECT,  // (nor this: REFLECTED_CONVOLVE)
     DSP_ROUTE_PILEUP,   // (nor this: RC_CR2 and BI_LEVEL_ZERO_CROSSING)
     DSP_ROUTE_PULSES,   // (nor this: PEAK_SNR_THRESHOLD and MULTI_A_FILTER)
+    DSP_ROUTE_TAILFIT,  // (nor this: LOG_CHECK, POLY_FIT, POLY_DIFF and POLY_EXP_RMS)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -35,6 +36,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_reflect_kernel",
     "dsp_pileup_kernel",
     "dsp_pulses_kernel",
+    "dsp_tailfit_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -259,6 +261,19 @@ constexpr int64_t tiles(int64_t n_wf) { return (n_wf + ROWS - 1) / ROWS; }
 constexpr int MIN_FILTER_LEN = 4;  // rc_cr2.py:51-54: more than 3 samples
 static_assert(lds_bytes(8) <= 64 * 1024, "a static LDS array");
 }  // namespace dsp_pileup
+
+namespace dsp_tailfit {  // dsp_tailfit.hip: log_check, poly_fit, poly_diff and poly_exp_rms, one waveform per lane
+// The rows pass through the pile-up kernel's tile (dsp_lane_tiles.h), twice where the residuals follow the fit.  Beside it lies the table of
+// the powers of a tile's sample indices: float64(i**j) for the TS samples of the tile and j < POLY_MAX, which a lane forms for one sample
+// and all lanes read, every lane the same entry at a time (a broadcast).
+using dsp_pileup::PITCH;
+using dsp_pileup::ROWS;
+using dsp_pileup::tiles;
+using dsp_pileup::TS;
+constexpr int POLY_MAX = 8;  // DSP_POLY_MAX (dsp_program.h)
+constexpr int lds_bytes(int esz) { return dsp_pileup::lds_bytes(esz) + TS * POLY_MAX * 8; }
+static_assert(lds_bytes(8) <= 64 * 1024, "static LDS arrays");
+}  // namespace dsp_tailfit
 
 namespace dsp_pulses {  // dsp_pulses.hip: peak_snr_threshold (peak_snr_threshold.py:19-71) and multi_a_filter (multi_a_filter.py:20-57)
 // ---- the rule of a candidate, shared by the kernel, the planner and tests/pulse_window.cpp.  A candidate idx of a row of n samples, the

@@ -103,7 +103,7 @@ struct PlanCtx;
 // accepts, or is refused with `refusal` and the matcher's reason.  (A program never matches two: every shape is exact.)
 struct KernelOnlyRoute {
     dsp_route route;
-    int opcodes[2];
+    int opcodes[4];  // (0: none)
     bool (*match)(const PlanCtx& c, const char** why);
     const char* refusal;
 };
@@ -117,6 +117,7 @@ static bool match_dense_shape(const PlanCtx& c, const char** why);
 static bool match_reflect_shape(const PlanCtx& c, const char** why);
 static bool match_pileup_shape(const PlanCtx& c, const char** why);
 static bool match_pulses_shape(const PlanCtx& c, const char** why);
+static bool match_tailfit_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -136,6 +137,8 @@ static const KernelOnlyRoute kernel_only_routes[] = {
      "DSP_OP_RC_CR2 / DSP_OP_BI_LEVEL_ZERO_CROSSING (rc_cr2, bi_level_zero_crossing_time_points) run on dsp_pileup_kernel only"},
     {DSP_ROUTE_PULSES, {DSP_OP_PEAK_SNR_THRESHOLD, DSP_OP_MULTI_A_FILTER}, match_pulses_shape,
      "DSP_OP_PEAK_SNR_THRESHOLD / DSP_OP_MULTI_A_FILTER (peak_snr_threshold, multi_a_filter) run on dsp_pulses_kernel only"},
+    {DSP_ROUTE_TAILFIT, {DSP_OP_LOG_CHECK, DSP_OP_POLY_FIT, DSP_OP_POLY_DIFF, DSP_OP_POLY_EXP_RMS}, match_tailfit_shape,
+     "DSP_OP_LOG_CHECK / DSP_OP_POLY_FIT / DSP_OP_POLY_DIFF / DSP_OP_POLY_EXP_RMS (log_check, poly_fit, poly_diff, poly_exp_rms) run on dsp_tailfit_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -925,6 +928,97 @@ static bool match_pulses_shape(const PlanCtx& c, const char** why) {
     return true;
 }
 
+// Is the program one of the decay-tail fitter's (dsp_tailfit.hip)?
+//   LOAD s;  LOG_CHECK of s;  STORE of the logged row
+//   LOAD s;  POLY_FIT of s;  STORE of the coefficients
+//   LOAD s;  LOAD of the coefficients, a row of m per event;  POLY_DIFF | POLY_EXP_RMS of s and of them;  STORE_SCALAR, STORE_SCALAR
+//   LOAD s;  [LOG_CHECK of s;]  POLY_FIT of the logged row (of s);  [STORE of the logged row;]  STORE of the coefficients
+//   LOAD s;  [LOG_CHECK of s;]  POLY_FIT;  POLY_DIFF | POLY_EXP_RMS of s or of the logged row with the fitted coefficients;
+//            [STORE of the logged row;]  [STORE of the coefficients;]  STORE_SCALAR, STORE_SCALAR
+// each with or without  BL_SUBTRACT s <- s  (bl_subtract.py, a constant or a column of the loop's type) behind the LOAD of s: done as the rows
+// are read.  Lengths and limits are lower_op's business (every program that holds one of the ops passes there first).  Why not, otherwise: `why`.
+static bool match_tailfit_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int n = c.n_ops;
+    *why = "the program must be exactly LOAD, LOG_CHECK, STORE; or LOAD, POLY_FIT, STORE; or LOAD, LOAD of the coefficients, POLY_DIFF | POLY_EXP_RMS, STORE_SCALAR, "
+           "STORE_SCALAR; or LOAD, [LOG_CHECK,] POLY_FIT, [POLY_DIFF | POLY_EXP_RMS,] [STORE of the logged row,] [STORE of the coefficients,] [STORE_SCALAR, "
+           "STORE_SCALAR] (a BL_SUBTRACT of the rows, in place, may follow their LOAD)";
+    auto is = [&](int i, int opcode) { return i >= 0 && i < n && ops[i].opcode == opcode; };
+    if (n < 3 || !is(0, DSP_OP_LOAD)) return false;
+    // ---- behind the first LOAD: at most one more LOAD (the coefficients) and one BL_SUBTRACT, in either order
+    int at = 1;
+    const dsp_op *ld2 = nullptr, *bs = nullptr;
+    for (; at < n; ++at) {
+        if (is(at, DSP_OP_LOAD) && !ld2) ld2 = &ops[at];
+        else if (is(at, DSP_OP_BL_SUBTRACT) && !bs) bs = &ops[at];
+        else break;
+    }
+    const dsp_op* lg = is(at, DSP_OP_LOG_CHECK) ? &ops[at++] : nullptr;
+    const dsp_op* ft = is(at, DSP_OP_POLY_FIT) ? &ops[at++] : nullptr;
+    const dsp_op* rs = is(at, DSP_OP_POLY_DIFF) || is(at, DSP_OP_POLY_EXP_RMS) ? &ops[at++] : nullptr;
+    if ((!lg && !ft && !rs) || (lg && rs && !ft) || (ld2 != nullptr) != (rs && !ft)) return false;
+    const int first_store = at, n_stores = n - first_store - (rs ? 2 : 0);
+    if (n_stores < 0 || n_stores > (lg ? 1 : 0) + (ft ? 1 : 0) || c.n_slots != 1 + (ld2 ? 1 : 0) + (lg ? 1 : 0) + (ft ? 1 : 0)) return false;
+    for (int i = first_store; i < first_store + n_stores; ++i)
+        if (!is(i, DSP_OP_STORE)) return false;
+    if (rs && (!is(n - 2, DSP_OP_STORE_SCALAR) || !is(n - 1, DSP_OP_STORE_SCALAR))) return false;
+    // ---- the rows: the LOAD the first of the ops reads
+    const dsp_op& first = lg ? *lg : (ft ? *ft : *rs);
+    const dsp_op* ld = ops[0].dst == first.src ? &ops[0] : (ld2 && ld2->dst == first.src ? ld2 : nullptr);
+    const dsp_op* lp = ld2 ? (ld == &ops[0] ? ld2 : &ops[0]) : nullptr;
+    TailfitArgs& A = ch->tailfit;
+    memset(&A, 0, sizeof A);
+    ch->aio_sub = ch->aio_inv = ch->aio_pars = ch->aio_out = ch->aio_pars_out = ch->aio_mean = ch->aio_rms = -1;
+    if (!ld || (!ld2 && ld != &ops[0]) || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, ch->tailfit_src, why,
+                                                     "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        return false;
+    if (bs) {
+        *why = "the BL_SUBTRACT behind the LOAD works on the rows in place (bl_subtract, ip[0] = 0), its baseline a constant or a per-event column of the loop's type";
+        if (bs->dst != ld->dst || bs->src != ld->dst || bs->ip[0] != 0 || !bind_operand(c, *bs, 0, ch->aio_sub, A.sub_stride, A.sub_const)) return false;
+        A.sub_mode = 1;
+    }
+    *why = "poly_fit in the same program reads exactly the logged row; the residuals the row as loaded or the logged row, with exactly the fitted coefficients";
+    if (lg && ft && ft->src != lg->dst) return false;
+    if (ft && rs && (rs->ip[0] != ft->dst || (rs->src != ld->dst && !(lg && rs->src == lg->dst)))) return false;
+    if (lp) {
+        *why = "the coefficients are loaded whole into slot ip[0], a row of them per event in the loop's type";
+        if (rs->ip[0] != lp->dst || lp->dst == rs->src || lp->ip[0] != 0 || lp->ip[1] != 0 || io[lp->io].dtype != c.compute_dtype || io[lp->io].len != c.slot_len[lp->dst])
+            return false;
+        ch->aio_pars = lp->io;
+        A.pars_stride = io[lp->io].row_stride;
+        A.pars_offset = io[lp->io].offset;
+    }
+    *why = "the logged row and the coefficients are stored once each, whole, in the loop's type; the two results of the residuals once each, in the loop's type";
+    for (int i = first_store; i < first_store + n_stores; ++i) {
+        const dsp_op& st = ops[i];
+        const dsp_io_desc& o = io[st.io];
+        int* slot = lg && st.src == lg->dst ? &ch->aio_out : (ft && st.src == ft->dst ? &ch->aio_pars_out : nullptr);
+        if (!slot || *slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        *slot = st.io;
+        (slot == &ch->aio_out ? A.out_stride : A.pars_out_stride) = o.row_stride;
+    }
+    if ((lg && !ft && ch->aio_out < 0) || (ft && !rs && ch->aio_pars_out < 0) || (ch->aio_out >= 0 && ch->aio_out == ch->aio_pars_out)) return false;
+    if (rs) {
+        const dsp_op &s0 = ops[n - 2], &s1 = ops[n - 1];
+        const dsp_op* mean = s0.ip[0] == rs->dst ? &s0 : (s1.ip[0] == rs->dst ? &s1 : nullptr);
+        const dsp_op* rms = s0.ip[0] == rs->dst + 1 ? &s0 : (s1.ip[0] == rs->dst + 1 ? &s1 : nullptr);
+        if (!mean || !rms || mean == rms || mean->io == rms->io || io[mean->io].dtype != c.compute_dtype || io[rms->io].dtype != c.compute_dtype) return false;
+        ch->aio_mean = mean->io;
+        ch->aio_rms = rms->io;
+        A.mean_stride = io[mean->io].row_stride;
+        A.rms_stride = io[rms->io].row_stride;
+        A.resid = rs->opcode == DSP_OP_POLY_EXP_RMS ? 2 : 1;
+        A.resid_log = lg && rs->src == lg->dst ? 1 : 0;
+    }
+    if (ft) ch->aio_inv = ft->io;
+    A.m = ft ? c.slot_len[ft->dst] : (rs ? c.slot_len[rs->ip[0]] : 0);
+    A.log = lg ? 1 : 0;
+    A.fit = ft ? 1 : 0;
+    return true;
+}
+
 // Does the program have the shape of the current-branch kernel (dsp_current.hip)?
 //   LOAD s0;  WINDOWER s1 <- s0 (start: constant or float32 column);  AVG_CURRENT s2 <- s1;  UPSAMPLER s3 <- s2;
 //   MOVING_WINDOW_MULTI d <- s3 (3 windows, alternating);  MIN_MAX of d;  STORE_SCALARs of its four registers
@@ -1457,7 +1551,11 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_INTERP_UPSAMPLE:
         case DSP_OP_REFLECTED_CONVOLVE:
         case DSP_OP_RC_CR2:
+        case DSP_OP_LOG_CHECK:
+        case DSP_OP_POLY_FIT:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
+        case DSP_OP_POLY_DIFF:
+        case DSP_OP_POLY_EXP_RMS: out[0] = o.src; out[1] = o.ip[0]; return 2;
         case DSP_OP_NORMALISE: out[0] = o.src; return 1;
         case DSP_OP_DENSE:
             out[0] = o.src;
@@ -1528,7 +1626,8 @@ static int check_call(PlanCtx& c) {
     c.ch->i64 = c.i64;
     for (const KernelOnlyRoute& r : kernel_only_routes)
         for (int i = 0; i < n_ops && !c.only; ++i)
-            if (c.ops[i].opcode == r.opcodes[0] || c.ops[i].opcode == r.opcodes[1]) c.only = &r;
+            for (const int opcode : r.opcodes)
+                if (opcode != 0 && c.ops[i].opcode == opcode) c.only = &r;
     return DSP_OK;
 }
 
@@ -1650,7 +1749,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows; PEAK_SNR_THRESHOLD, MULTI_A_FILTER: nothing in LDS)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows; PEAK_SNR_THRESHOLD, MULTI_A_FILTER: nothing in LDS; LOG_CHECK, POLY_FIT, POLY_DIFF, POLY_EXP_RMS: a tile of 64 rows)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1701,7 +1800,8 @@ static int bind_io(PlanCtx& c) {
             return fail(DSP_ERR_ARG, "io %d: int32/uint32/float64 rows select the float64 loop (compute_dtype DSP_F64)", k);
         const bool is_out = a.kind == DSP_IO_WF_OUT || a.kind == DSP_IO_SCALAR_OUT;
         if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT) &&
-            !(c.only && (c.only->route == DSP_ROUTE_EXTREMA || c.only->route == DSP_ROUTE_PILEUP || c.only->route == DSP_ROUTE_PULSES) && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32))  // (the counts of MULTI_EXTREMA, BI_LEVEL_ZERO_CROSSING and PEAK_SNR_THRESHOLD: their matchers see to the rest)
+            !(c.only && (c.only->route == DSP_ROUTE_EXTREMA || c.only->route == DSP_ROUTE_PILEUP || c.only->route == DSP_ROUTE_PULSES) && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32) &&  // (the counts of MULTI_EXTREMA, BI_LEVEL_ZERO_CROSSING and PEAK_SNR_THRESHOLD: their matchers see to the rest)
+            !(c.only && c.only->route == DSP_ROUTE_TAILFIT && a.kind == DSP_IO_TAPS && a.dtype == DSP_F64))  // (POLY_FIT's inverted matrix: float64 in both loops)
             return fail(DSP_ERR_ARG, "io %d: outputs have the chain's compute type or DSP_BOOL, taps the compute type", k);
         if ((a.dtype == DSP_BOOL || a.dtype == DSP_I64 || a.dtype == DSP_U64) && a.kind != DSP_IO_SCALAR_IN && a.kind != DSP_IO_SCALAR_OUT && !(a.dtype == DSP_BOOL && is_out))
             return fail(DSP_ERR_ARG, "io %d: DSP_BOOL / DSP_I64 / DSP_U64 are types of per-event columns (DSP_BOOL also of waveform outputs)", k);
@@ -2170,6 +2270,34 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
             if (slot_len[o.dst] > DSP_PEAKS_MAX)
                 return fail(DSP_ERR_UNSUPPORTED, "multi_a_filter: at most %d positions (%d given): a wavefront keeps one per lane", DSP_PEAKS_MAX, slot_len[o.dst]);
             if (!(slot_len[o.ip[0]] < slot_len[o.src])) return fail(DSP_E_MAF_LEN, "%s", dsp_fatal_message(DSP_E_MAF_LEN));  // multi_a_filter.py:42-45
+            break;
+        }
+        case DSP_OP_LOG_CHECK: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad LOG_CHECK (src: the slot of the row; dst: another slot, for the logged row)", i);
+            if (slot_len[o.dst] != slot_len[o.src])
+                return fail(DSP_ERR_ARG, "log_check: the output has the length of the input (len(w_in) = %d, len(w_log) = %d)", slot_len[o.src], slot_len[o.dst]);
+            break;
+        }
+        case DSP_OP_POLY_FIT: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad POLY_FIT (src: the slot of the row; dst: another slot, for the coefficients; io: the inverted matrix)", i);
+            const int m = slot_len[o.dst];
+            if (m > DSP_POLY_MAX) return fail(DSP_ERR_UNSUPPORTED, "poly_fit: " DSP_POLY_MAX_TEXT, DSP_POLY_MAX, m);
+            if (!need_io(c, o, DSP_IO_TAPS) || c.io[o.io].dtype != DSP_F64 || c.io[o.io].len != m * m)
+                return fail(DSP_ERR_ARG, "poly_fit: io is a DSP_IO_TAPS binding of m * m = %d DSP_F64 values, the inverted matrix of power sums (both loops)", m * m);
+            if (!dsp_poly_powers_fit(slot_len[o.src], m)) return fail(DSP_ERR_UNSUPPORTED, "poly_fit: " DSP_POLY_POWER_TEXT, slot_len[o.src], m);
+            break;
+        }
+        case DSP_OP_POLY_DIFF:
+        case DSP_OP_POLY_EXP_RMS: {
+            const char* name = o.opcode == DSP_OP_POLY_DIFF ? "poly_diff" : "poly_exp_rms";
+            if (!check_slot(P, o.src) || !check_slot(P, o.ip[0]) || o.ip[0] == o.src || o.dst < 0 || o.dst + 1 >= n_sregs)
+                return fail(DSP_ERR_ARG, "op %d: bad %s (src: the slot of the row; ip[0]: the slot of the coefficients; dst, dst + 1: the registers of mean and rms)", i,
+                            o.opcode == DSP_OP_POLY_DIFF ? "POLY_DIFF" : "POLY_EXP_RMS");
+            const int m = slot_len[o.ip[0]];
+            if (m > DSP_POLY_MAX) return fail(DSP_ERR_UNSUPPORTED, "%s: " DSP_POLY_MAX_TEXT, name, DSP_POLY_MAX, m);
+            if (!dsp_poly_powers_fit(slot_len[o.src], m)) return fail(DSP_ERR_UNSUPPORTED, "%s: " DSP_POLY_POWER_TEXT, name, slot_len[o.src], m);
             break;
         }
         case DSP_OP_DWT_HAAR: {

@@ -490,6 +490,56 @@ struct PulsesArgs {
     int64_t amp_stride;
 };
 
+// arguments of the decay-tail fitter (dsp_tailfit.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> LOG_CHECK -> STORE
+//   LOAD -> POLY_FIT -> STORE of the coefficients
+//   LOAD -> LOAD of the coefficients -> POLY_DIFF | POLY_EXP_RMS -> STORE_SCALAR, STORE_SCALAR
+//   LOAD -> LOG_CHECK -> POLY_FIT [-> STORE of the logged row] -> STORE of the coefficients
+//   LOAD -> LOG_CHECK -> POLY_FIT -> POLY_DIFF | POLY_EXP_RMS [-> STORE of the logged row] [-> STORE of the coefficients] -> STORE_SCALAR, STORE_SCALAR
+// each with or without a BL_SUBTRACT of the rows, in place, behind their LOAD.  One waveform per lane; the rows pass through an LDS tile of
+// 64 rows x 64 samples (dsp_kernels.h, dsp_tailfit), twice where the residuals follow the fit.
+#define DSP_POLY_MAX 8 /* coefficients of poly_fit / poly_diff / poly_exp_rms: a lane keeps as many float64 accumulators */
+#define DSP_POLY_MAX_TEXT "at most %d coefficients (%d given): a lane keeps one float64 accumulator each"
+#define DSP_POLY_POWER_TEXT \
+    "(n - 1)**(m - 1) must stay below 2**63 (n = %d samples, m = %d coefficients): beyond it the reference's int64 power i**j wraps silently"
+// does i**j stay an int64 for every sample i < n and every power j < m?
+static inline bool dsp_poly_powers_fit(int64_t n, int m) {
+    const uint64_t b = n > 1 ? (uint64_t)(n - 1) : 0, top = ((uint64_t)1 << 63) - 1;
+    uint64_t p = 1;
+    for (int j = 1; j < m; ++j) {
+        if (b != 0 && p > top / b) return false;
+        p *= b;
+    }
+    return true;
+}
+struct TailfitArgs {
+    const void* wf;          // float32 / int16 / uint16 rows (the float32 loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples
+    int32_t log;             // 1: log_check runs on the row
+    int32_t fit;             // 1: poly_fit runs on the row, or on the logged row
+    int32_t resid;           // 0: none; 1: poly_diff; 2: poly_exp_rms -- with the coefficients of `pars`, or the fitted ones as stored
+    int32_t resid_log;       // 1: the residuals are those of the logged row (else of the row as loaded)
+    int32_t m;               // coefficients, 1 .. DSP_POLY_MAX (with fit or resid)
+    int32_t out_vec;         // 1: 16-byte stores of the logged row (the output rows' start and stride are whole vectors: set per call)
+    int32_t sub_mode;        // 1: the baseline is subtracted from every sample as it is read (bl_subtract)
+    const void* sub;         // the baseline: a column of the loop's type, or null: sub_const
+    int64_t sub_stride;
+    double sub_const;
+    const double* inv;       // poly_fit: m * m float64 values, row-major, whatever the loop
+    const void* pars;        // poly_diff / poly_exp_rms alone: rows of m coefficients of the loop's type
+    int64_t pars_stride;
+    int32_t pars_offset;
+    void* out;               // logged rows of len samples of the loop's type, or null: not stored
+    int64_t out_stride;
+    void* pars_out;          // rows of m fitted coefficients of the loop's type, or null: not stored
+    int64_t pars_out_stride;
+    void* mean_out;          // the two results of the residuals: a value of the loop's type per row
+    int64_t mean_stride;
+    void* rms_out;
+    int64_t rms_stride;
+};
+
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4
 struct FirArgs {

@@ -246,6 +246,8 @@ _SIGS = {
     "rc_cr2": "wsW", "bi_level_zero_crossing_time_points": "wssssSWW",
     # (w_in, idx_in[m], ratio_in, width_in, idx_out[m], n_idx_out); (w_in, vt_maxs_in[m], va_max_out[m]): the lists are waveforms of a stage, m theirs
     "peak_snr_threshold": "wwssWS", "multi_a_filter": "wwW",
+    # (w_in, w_log); (w_in, poly_pars[m]) with init_args (length, deg); (w_in, poly_pars[m], mean, rms) twice: the coefficients are a waveform of a stage, m theirs
+    "log_check": "wW", "poly_fit": "wW", "poly_diff": "wwSS", "poly_exp_rms": "wwSS",
     # ml.py: (x_in, means, variances, x_out); (x_in, kernel[n, m], [bias[m],] activation_func, x_out[m]); (x_in, kernel[n], [bias,] activation_func, x_out)
     "normalisation_layer": "waaW", "dense_layer_no_bias": "wacW", "dense_layer_with_bias": "waacW",
     "classification_layer_no_bias": "wacS", "classification_layer_with_bias": "waacS",
@@ -359,6 +361,7 @@ _RESAMPLING_FILES = {"interpolating_upsampler": ("upsampler",)}  # (processors.R
 _SMOOTHING_FILES = {"reflected_convolve_wf": ("convolutions",)}  # (processors.SMOOTHING, likewise; gaussian_filter1d stays refused in recipes)
 _PILEUP_FILES = {"rc_cr2": ("rc_cr2",), "bi_level_zero_crossing_time_points": ("time_point_thresh",)}  # (processors.PILEUP, likewise)
 _PULSE_FILES = {"peak_snr_threshold": ("peak_snr_threshold",), "multi_a_filter": ("multi_a_filter",)}  # (processors.PULSES, likewise; in recipes under these strings only: compiler._add_step)
+_TAILFIT_FILES = {"log_check": ("log_check",), "poly_fit": ("poly_fit",), "poly_diff": ("poly_fit",), "poly_exp_rms": ("poly_fit",)}  # (processors.TAILFIT, likewise)
 _ML_FILES = dict.fromkeys(("normalisation_layer", "dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias",
                            "classification_layer_with_bias"), ("ml",))  # (processors.ML, likewise)
 
@@ -367,7 +370,7 @@ def module_accepted(module, function) -> bool:
     """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
     pre = "dspeed.processors."
     files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ()) + _ORDER_FILES.get(function, ()) + _RESAMPLING_FILES.get(function, ())
-    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ()) + _PILEUP_FILES.get(function, ()) + _PULSE_FILES.get(function, ())
+    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ()) + _PILEUP_FILES.get(function, ()) + _PULSE_FILES.get(function, ()) + _TAILFIT_FILES.get(function, ())
     return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in files)
 
 

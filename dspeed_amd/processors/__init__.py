@@ -870,5 +870,140 @@ multi_a_filter = HipGUFunc("multi_a_filter", "(n),(m)->(m)", ["ff->f", "dd->d"],
 # Listed here and not in __all__, like the pile-up processors: their call records are tests/test_pulse_plan_cpu.py's.
 PULSES = ("peak_snr_threshold", "multi_a_filter")
 
+
+# --------------------------------------------------------------------------------------------------- decay-tail fit
+def check_poly(what, n, m):
+    """what the planner checks of ``m`` coefficients on rows of ``n`` samples, in its words"""
+    if m < 1:
+        raise ValueError(f"{what}: at least one coefficient")
+    if m > _lib.POLY_MAX:
+        raise NotImplementedError(f"{what}: at most {_lib.POLY_MAX} coefficients ({m} given): a lane keeps one float64 accumulator each")
+    if max(n - 1, 0) ** (m - 1) >= 2 ** 63:
+        raise NotImplementedError(f"{what}: (n - 1)**(m - 1) must stay below 2**63 (n = {n} samples, m = {m} coefficients): beyond it the "
+                                  "reference's int64 power i**j wraps silently")
+
+
+def check_poly_fit_init(what, length, deg):
+    """``init_args`` of poly_fit: two non-negative integer constants -> (length, deg)"""
+    out = []
+    for name, v in (("length", length), ("deg", deg)):
+        a = np.asarray(v.magnitude if hasattr(v, "magnitude") else v)
+        if a.size != 1:
+            raise NotImplementedError(f"{what}: {name} is a constant of the call on the device, not a per-event value")
+        f = float(a.reshape(-1)[0])
+        if not (f >= 0 and f == int(f)):
+            raise ValueError(f"{what}: {name} is a non-negative integer ({v} given)")
+        out.append(int(f))
+    return tuple(out)
+
+
+def poly_fit_inverse(length, deg):
+    """The factory's matrix (reference processors/poly_fit.py:50-61, as written): the power sums over ``range(length)`` in float64, inverted
+    once on the host with ``np.linalg.inv``.  A singular matrix (``length <= deg``) raises as it does there."""
+    vals_array = np.zeros(2 * deg + 1, dtype="float64")
+    for i in range(length):
+        for j in range(2 * deg + 1):
+            vals_array[j] += i**j
+    mat = np.zeros((deg + 1, deg + 1), dtype="float")
+    for i in range(deg + 1):
+        mat[i, :] = vals_array[i: deg + 1 + i]
+    return np.linalg.inv(mat)
+
+
+def _log_check(g, *args):
+    """one C entry for both loops, like sort's; ``w_log`` may be left out"""
+    what = g.__name__
+    (w_in,), (out,) = _split(g, args)
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        if out is not None and not isinstance(out, (np.ndarray, DeviceArray)):
+            raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+        if out is not None and (int(out.shape[-1]) if len(out.shape) else 0) != c.n:
+            raise ValueError(f"{what}: the output has the length of the input (len(w_in) = {c.n}, len(w_log) = {int(out.shape[-1]) if len(out.shape) else 0})")
+        ptr, stride = c.out(out, "n")
+        run(getattr(_lib.lib(), "dsp_log_check_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, ptr, stride)
+        c.st.finish()
+        return _results(c)
+
+
+def poly_fit(length, deg):
+    """The reference's factory (processors/poly_fit.py:35-71): the gufunc ``poly_fitter``, ``(n),(m)``, that fits rows to a polynomial of order
+    ``deg`` over ``range(length)``.  The inverted matrix is formed here, once, and travels with every call; ``poly_pars`` (``deg + 1``
+    coefficients a row) is written in place, or returned where it is left out."""
+    length, deg = check_poly_fit_init("poly_fit", length, deg)
+    check_poly("poly_fit", length, deg + 1)
+    inv = np.ascontiguousarray(poly_fit_inverse(length, deg), dtype=np.float64)
+    m = deg + 1
+
+    def impl(g, *args):
+        what = g.__name__
+        if len(args) not in (1, 2):
+            raise TypeError(f"{what}() takes w_in and poly_pars ({len(args)} given)")
+        w_in, out = args[0], (args[1] if len(args) == 2 else None)
+        with device_call(what, w_in, f64_rows_only=True) as c:
+            if out is not None and not isinstance(out, (np.ndarray, DeviceArray)):
+                raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+            m_out = m if out is None else (int(out.shape[-1]) if len(out.shape) else 0)
+            if m_out != m:
+                raise ValueError(f"{what}: poly_pars holds deg + 1 = {m} coefficients ({m_out} given)")
+            check_poly(what, c.n, m)
+            dev = DeviceArray.from_numpy(inv)
+            c.st.keep.append(dev)
+            po = _pulse_out(c, out, m)
+            run(getattr(_lib.lib(), "dsp_poly_fit_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, dev.ptr, m, po, m)
+            c.st.finish()
+            return _results(c)
+
+    g = HipGUFunc("poly_fitter", "(n),(m)", ["ff", "dd"], impl, f"Fit w_in to order {deg} polynomial.")
+    g.inv = inv
+    return g
+
+
+def _poly_pars(c, what, v):
+    """the '(m)' input of the residuals on the device: (array, m, row stride); one row of coefficients is repeated for every row"""
+    if isinstance(v, DeviceArray):
+        if v.dtype != np.dtype(c.ft):
+            raise TypeError(f"{what}: poly_pars on the device has the loop's type, {np.dtype(c.ft)}")
+        shape, dev = tuple(v.shape), v
+    else:
+        host = np.ascontiguousarray(np.asarray(v), dtype=c.ft)
+        shape, dev = host.shape, None
+    if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] != c.n_wf) or (dev is not None and len(shape) == 1 and c.n_wf != 1):
+        raise ValueError(f"{what}: poly_pars has shape {shape}, expected ({c.n_wf}, m)" + ("" if dev is not None else " or (m,)"))
+    m = int(shape[-1])
+    check_poly(what, c.n, m)
+    if dev is None:
+        dev = DeviceArray.from_numpy(np.ascontiguousarray(np.broadcast_to(host, (c.n_wf, m))))
+        c.st.keep.append(dev)
+    return dev, m, m
+
+
+def _poly_residual(exp_rms):
+    def impl(g, *args):
+        """one C entry for both processors and both loops; ``mean`` and ``rms`` may be left out"""
+        what = g.__name__
+        (w_in, pars), (mean, rms) = _split(g, args)
+        with device_call(what, w_in, f64_rows_only=True) as c:
+            dev, m, stride = _poly_pars(c, what, pars)
+            pm, pr = _pulse_out(c, mean, None), _pulse_out(c, rms, None)
+            run(getattr(_lib.lib(), "dsp_poly_residual_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, exp_rms, dev.ptr, m, stride, pm, pr)
+            c.st.finish()
+            return _results(c)
+
+    return impl
+
+
+log_check = HipGUFunc("log_check", "(n)->(n)", ["f->f", "d->d"], _log_check,
+                      "the logarithm of a row that is positive throughout; a row with a NaN or a sample <= 0: NaNs (reference "
+                      "processors/log_check.py:11-48)")
+poly_diff = HipGUFunc("poly_diff", "(n),(m)->(),()", ["ff->ff", "dd->dd"], _poly_residual(0),
+                      "of the residuals r_i = w_in[i] - sum_j poly_pars[j] i**j (float64): sum r_i / (i + 1) and sqrt(sum r_i^2 / (n - 1)), both "
+                      "rounded to the loop's type after every sample; m <= 8 (reference processors/poly_fit.py:74-108)")
+poly_exp_rms = HipGUFunc("poly_exp_rms", "(n),(m)->(),()", ["ff->ff", "dd->dd"], _poly_residual(1),
+                         "poly_diff against the exponential of the polynomial, r_i = w_in[i] - exp(sum_j poly_pars[j] i**j) (reference "
+                         "processors/poly_fit.py:111-141)")
+
+# Listed here and not in __all__, like the pulse picker's processors: their call records are tests/test_tailfit_plan_cpu.py's.
+TAILFIT = ("log_check", "poly_fit", "poly_diff", "poly_exp_rms")
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

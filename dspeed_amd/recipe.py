@@ -168,8 +168,11 @@ class Recipe:
         needs = fields.pop("prereqs", None)
         targets = defined_names(key)
         args = [self._with_database(a, fields.get("defaults")) for a in args]
+        if isinstance(fields.get("init_args"), (list, tuple)):  # (the arguments of a factory, poly_fit's: expressions of the same language)
+            fields["init_args"] = [self._with_database(a, fields.get("defaults")) for a in fields["init_args"]]
         if needs is None:
-            mentioned = (name for a in args if isinstance(a, str) for name in variables_in(a))
+            init = fields.get("init_args") if isinstance(fields.get("init_args"), (list, tuple)) else ()
+            mentioned = (name for a in (*args, *init) if isinstance(a, str) for name in variables_in(a))
             needs = [n for n in dict.fromkeys(mentioned) if n not in targets]
         return Entry(key, targets, function, module, args, list(needs), fields)
 

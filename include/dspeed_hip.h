@@ -342,6 +342,27 @@ typedef struct dsp_scalar_arg {
                                  *   LOAD, LOAD of the candidates, PEAK_SNR_THRESHOLD, MULTI_A_FILTER of the same row at idx_out, [STORE of idx_out,]
                                  *   STORE of va_max_out, STORE_SCALAR of the count
                                  * where idx_out goes to memory only if it is stored */
+#define DSP_OP_LOG_CHECK 50    /* log_check.py:11-48: dst (n samples, another slot than src) <- log(src) in the loop's type if no sample of src is a
+                                 * NaN or <= 0, else n NaNs.  It runs on dsp_tailfit_kernel only (the shapes: below DSP_OP_POLY_EXP_RMS) */
+#define DSP_OP_POLY_FIT 51     /* poly_fit.py:12-71, the gufunc poly_fit(length, deg) returns: dst (m = deg + 1 <= DSP_POLY_MAX coefficients) <- the
+                                 * least-squares polynomial of src (n samples at 0 .. n - 1).  io = a DSP_IO_TAPS binding of m * m DSP_F64 values in
+                                 * BOTH loops: the inverse of the matrix of power sums, row-major, inverted by the caller.  arr[j] = sum_i src[i] * i**j
+                                 * in float64 for ascending i, i**j an exact integer converted once; dst[k] = sum_j inv[k][j] * arr[j] for ascending
+                                 * j, rounded once.  A row with a NaN: NaN coefficients.  (n - 1)**(m - 1) < 2**63. */
+#define DSP_OP_POLY_DIFF 52    /* poly_fit.py:74-108: sreg[dst], sreg[dst + 1] <- "mean", rms of the residuals r_i = src[i] - sum_j p[j] * i**j, p =
+                                 * the m <= DSP_POLY_MAX coefficients in slot ip[0].  The polynomial and r_i in float64 (ascending j); mean += r_i /
+                                 * (i + 1) and rms += r_i * r_i add in float64 and round to the loop's type after every sample; rms = sqrt(rms /
+                                 * (n - 1)), n = 1 dividing by zero as IEEE does.  A NaN in the row or among the coefficients: NaN, NaN. */
+#define DSP_OP_POLY_EXP_RMS 53 /* poly_fit.py:111-141: as DSP_OP_POLY_DIFF with r_i = src[i] - exp(sum_j p[j] * i**j), the float64 exp.
+                                 * The four run on dsp_tailfit_kernel only, one waveform per lane, in a program of exactly
+                                 *   LOAD, LOG_CHECK, STORE of the logged row
+                                 *   LOAD, POLY_FIT, STORE of the coefficients
+                                 *   LOAD, LOAD of the coefficients (a row of m per event), POLY_DIFF | POLY_EXP_RMS, STORE_SCALAR, STORE_SCALAR
+                                 *   LOAD, LOG_CHECK, POLY_FIT of the logged row, [STORE of the logged row,] STORE of the coefficients
+                                 *   LOAD, LOG_CHECK, POLY_FIT of the logged row, POLY_DIFF | POLY_EXP_RMS of the loaded or the logged row with the
+                                 *   fitted coefficients as stored, [STORE of the logged row,] [STORE of the coefficients,] STORE_SCALAR, STORE_SCALAR
+                                 * each with or without a BL_SUBTRACT of the loaded rows, in place, behind their LOAD.  The logged row and, in the
+                                 * last shape, the coefficients go to memory only if they are stored */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -659,6 +680,24 @@ int dsp_peak_snr_threshold_rows(const void* in, int in_dtype, int64_t n_wf, int3
 int dsp_multi_a_filter_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype,
                             const void* vt_maxs_in_dev, int32_t list_len, int64_t vt_stride, void* va_max_out, int64_t out_stride, void* stream,
                             int64_t* err_row);
+
+/* "(n)->(n)" log_check (log_check.py:11-48; DSP_OP_LOG_CHECK).  One entry for both loops, like dsp_sort_rows: out holds rows of wf_len
+ * values of the loop's type, out_stride apart. */
+int dsp_log_check_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, void* out,
+                       int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(m)" poly_fitter, what poly_fit(length, deg) returns (poly_fit.py:12-71; DSP_OP_POLY_FIT).  inv_dev: the n_pars * n_pars float64 values
+ * of the inverted matrix of power sums on the device, row-major, in both loops; poly_pars_out: rows of n_pars <= DSP_POLY_MAX coefficients of
+ * the loop's type, out_stride apart. */
+int dsp_poly_fit_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, const double* inv_dev,
+                      int32_t n_pars, void* poly_pars_out, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(m)->(),()" poly_diff (exp_rms == 0; poly_fit.py:74-108; DSP_OP_POLY_DIFF) and poly_exp_rms (exp_rms != 0; poly_fit.py:111-141;
+ * DSP_OP_POLY_EXP_RMS).  poly_pars_dev: rows of n_pars <= DSP_POLY_MAX coefficients of the loop's type on the device, pars_stride apart;
+ * mean_out, rms_out: a value of the loop's type per row. */
+int dsp_poly_residual_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, int32_t exp_rms,
+                           const void* poly_pars_dev, int32_t n_pars, int64_t pars_stride, void* mean_out, void* rms_out, void* stream,
+                           int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
