@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("DSPEED_HIP_LIB") or os.path.join(_HERE, "libdspeed_hi
 # ---- constants of include/dspeed_hip.h
 OK, ERR_HIP, ERR_ARG, ERR_UNSUPPORTED, ERR_TOO_LONG = 0, -1, -2, -3, -4
 E_ZERODIV = 17
+E_INL_RANGE, E_ALIGN_CENTROID = 37, 38
 HIST_MAX_BINS = 2048  # DSP_HIST_MAX_BINS (dsp_program.h): the bins dsp_hist_kernel keeps counters for
 PEAKS_MAX = 64  # DSP_PEAKS_MAX (dsp_program.h): the entries of a list of peak_snr_threshold / multi_a_filter, one per lane of dsp_pulses_kernel
 POLY_MAX = 8  # DSP_POLY_MAX (dsp_program.h): the coefficients of poly_fit / poly_diff / poly_exp_rms, a float64 accumulator per lane of dsp_tailfit_kernel each
@@ -37,7 +38,8 @@ ARG_CONST, ARG_INPUT, ARG_REG = range(3)
  OP_SCALAR_AFFINE, OP_MEAN_BELOW, OP_CONVOLVE_AMAX, OP_WINDOWER, OP_AVG_CURRENT, OP_TRAP_WINDOW_PICKOFF, OP_TRAP_REDUCE, OP_UPSAMPLER, OP_MOVING_WINDOW_MULTI, OP_LINEAR_SLOPE_FIT,
  OP_SCALAR_CONVERT, OP_SCALAR_DIV, OP_INTERP_TIME_POINT_THRESH, OP_MIN_MAX_NORM, OP_ELEMENTWISE, OP_SCALAR_FUNC, OP_MULTI_EXTREMA, OP_HISTOGRAM,
  OP_HISTOGRAM_STATS, OP_MULTI_TIME_POINT_THRESH, OP_TIME_OVER_THRESHOLD, OP_PSD, OP_FFT, OP_SORT, OP_INTERP_UPSAMPLE, OP_NORMALISE, OP_DENSE, OP_REFLECTED_CONVOLVE, OP_RC_CR2, OP_BI_LEVEL_ZERO_CROSSING,
- OP_PEAK_SNR_THRESHOLD, OP_MULTI_A_FILTER, OP_LOG_CHECK, OP_POLY_FIT, OP_POLY_DIFF, OP_POLY_EXP_RMS) = range(1, 54)
+ OP_PEAK_SNR_THRESHOLD, OP_MULTI_A_FILTER, OP_LOG_CHECK, OP_POLY_FIT, OP_POLY_DIFF, OP_POLY_EXP_RMS,
+ OP_INL_CORRECTION, OP_WF_CENTROID, OP_WF_ALIGNMENT, OP_WF_CORRECTION) = range(1, 58)
 (FN_ADD, FN_SUB, FN_MUL, FN_DIV, FN_LT, FN_LE, FN_GT, FN_GE, FN_EQ, FN_NE, FN_WHERE, FN_ISNAN, FN_ISFINITE, FN_NEG, FN_COPY, FN_FLOORDIV,
  FN_IADD, FN_ISUB, FN_IMUL, FN_IFLOORDIV, FN_ICAST, FN_LOR, FN_LAND, FN_RINT, FN_FLOOR, FN_CEIL, FN_TRUNC) = range(27)
 
@@ -166,6 +168,10 @@ SIG = {
         "dsp_log_check_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i64, vp, pi64],
         "dsp_poly_fit_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, vp, i64, vp, pi64],
         "dsp_poly_residual_rows": [vp, C.c_int, i64, i32, i64, C.c_int, i32, vp, i32, i64, vp, vp, vp, pi64],
+        "dsp_inl_correction_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, vp, i64, vp, pi64],
+        "dsp_wf_centroid_rows": [vp, C.c_int, i64, i32, i64, C.c_int, C.c_double, vp, vp, pi64],
+        "dsp_wf_alignment_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, C.c_double, C.c_double, C.c_double, vp, i32, i64, vp, pi64],
+        "dsp_wf_correction_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, i32, i32, vp, i64, vp, pi64],
         "dsp_synth_waveforms": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_synth_pulses": [vp, C.c_int, i64, i32, i64, vp, vp, C.c_uint64, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp],
         "dsp_stream_read": [vp, i64, vp, vp],

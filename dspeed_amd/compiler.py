@@ -39,11 +39,13 @@ _RC_CR2, _BI_LEVEL = "rc_cr2", "bi_level_zero_crossing_time_points"
 _PEAK_SNR, _MULTI_A = "peak_snr_threshold", "multi_a_filter"
 _LOG_CHECK, _POLY_FIT, _POLY_DIFF, _POLY_EXP_RMS = "log_check", "poly_fit", "poly_diff", "poly_exp_rms"
 _TAILFIT = (_LOG_CHECK, _POLY_FIT, _POLY_DIFF, _POLY_EXP_RMS)
+_INL, _WF_CENTROID, _WF_ALIGN, _WF_CORR = "inl_correction", "get_wf_centroid", "wf_alignment", "wf_correction"
+_ALIGN = (_INL, _WF_CENTROID, _WF_ALIGN, _WF_CORR)
 _NORMALISE = "normalisation_layer"
 _DENSE_LAYERS = ("dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
 _ML = (_NORMALISE,) + _DENSE_LAYERS
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL, _PEAK_SNR, _MULTI_A) + _TAILFIT + _ML  # processors that run as stages ahead of the program, on kernels of their own
-_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT, _RC_CR2, _LOG_CHECK)
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL, _PEAK_SNR, _MULTI_A) + _TAILFIT + _ALIGN + _ML  # processors that run as stages ahead of the program, on kernels of their own
+_SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT, _RC_CR2, _LOG_CHECK, _INL, _WF_CORR)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
 
@@ -181,6 +183,10 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
                 t_out.is_coord, t_out.grid = True, _grid_of(args[0])
     if function in _ML:
         args = _layer_arguments(b, function, args, key)
+    if function in (_INL, _WF_CORR):
+        args = _table_argument(b, function, args, key)
+    if function == _WF_ALIGN:
+        _alignment_output(args, key)
     args = [_as_taps(b, a, function) if r == "t" else a for a, r in zip(args, roles)]
     args = [_group_constant(b, a, function, key) if r == "i" and isinstance(a, (Var, SExpr)) else a for a, r in zip(args, roles)]
     _, args = _resolve(b, roles, args, same_dim_out=function in _SAME_DIM)
@@ -336,6 +342,33 @@ def _layer_arguments(b: _Builder, function, args, key):
             elif out.length != m:
                 raise ProcessingChainError(f"{function} ({key}): '{out.name}' holds {out.length} samples, the kernel has {m} columns")
     return args
+
+
+def _table_argument(b: _Builder, function, args, key):
+    """The constant array of ``inl_correction`` (inl) and ``wf_correction`` (w_corr): a ``db.`` value, a list literal, loadlh5(...) or a recipe
+    entry holding one -- one array for every row, cast to the loop's float32 once, here, as the layers' weights are."""
+    name = "inl" if function == _INL else "w_corr"
+    args = list(args)
+    a = args[1]
+    arr = a.const if isinstance(a, Var) and a.kind in ("const", "taps") and a.const is not None else a
+    if isinstance(arr, (list, tuple)):
+        arr = np.asarray(arr)
+    if not isinstance(arr, np.ndarray):
+        raise NotImplementedError(f"{function} ({key}): {name} is one constant array of the call on the device, not an array per event ({a!r})")
+    if arr.ndim != 1 or arr.size < 1 or arr.dtype.kind not in "fiu":
+        raise ProcessingChainError(f"{function} ({key}): {name} is a one-dimensional array of numbers, not {arr.dtype.name} of shape {arr.shape}")
+    b._anon += 1
+    args[1] = Var(a.name if isinstance(a, Var) else f"{name}#{b._anon}", "taps", int(arr.size), np.float32, const=np.ascontiguousarray(arr, dtype=np.float32))
+    return args
+
+
+def _alignment_output(args, key):
+    """``wf_alignment`` writes ``size`` samples: that is the output's length where the declaration gives none"""
+    size, out = args[3], args[4]
+    if isinstance(size, Var) and size.kind == "const":
+        size = size.const
+    if isinstance(out, Var) and out.kind == "wf" and out.length is None and _is_number(size) and float(size) == int(float(size)) and size > 0:
+        out.length = int(size)
 
 
 def _fold_generator(b: _Builder, function, args, new_vars):
@@ -1301,6 +1334,93 @@ def _stage_tailfit(cx: _Stager, only=None):
         cx.stage(pre + [st], [], f"{st[0]} {st[2]} on rows", wfs=[out], rows_first=True)
 
 
+def _stage_align(cx: _Stager, only=None):
+    """``inl_correction``, ``get_wf_centroid``, ``wf_alignment`` and ``wf_correction`` run on dsp_align.hip and nowhere else, on rows in HBM:
+    mandatory stages, like the decay-tail fitter's.  Each owns one launch; a ``wf_correction`` that reads exactly a ``wf_alignment``'s output
+    takes it into its launch, and the aligned row is then written only if something else reads it or the recipe asks for it
+    (``_stage_histogram``'s rule for weights and borders).  ``shift``, ``size`` and the indices are constants, checked here for every row in
+    the reference's order and words; the centroid is a constant, an input column or a stage's result (``_operand_in_memory``); ``inl`` and
+    ``w_corr`` are constant arrays; ``inl_correction`` reads an integer input column."""
+    from .processors import check_alignment, check_centroid_shift, check_correction
+
+    def constant(what, name, v):
+        if isinstance(v, Var) and v.kind == "const":
+            v = v.const
+        if not _is_number(v):
+            raise NotImplementedError(f"{what}: {name} is a constant of the call on the device, not a per-event value")
+        return float(v)
+
+    def rows_out(what, src, out, length):
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{what}: '{src}' is not a waveform")
+        if not (isinstance(out, Var) and out.kind == "wf" and out.length):
+            raise ProcessingChainError(f"{what}: the output is a waveform variable" + ("" if length else ", declared with its length: name(size)"))
+        if length and out.length != length:
+            raise ProcessingChainError(f"{what}: '{out.name}' holds {out.length} samples, the source {length}")
+
+    def corr_checked(st):
+        fn, args, key = st[0], list(st[1]), st[2]
+        what = f"{fn} ({key})"
+        src, tpl, start, stop, out = args
+        rows_out(what, src, out, src.length if _base_of(src) is not None else None)
+        try:
+            args[2], args[3] = check_correction(what, src.length, tpl.length, constant(what, "start_idx", start), constant(what, "stop_idx", stop))
+        except ValueError as e:
+            raise ProcessingChainError(str(e)) from None
+        return cx.replace(st, (fn, args, key))
+
+    for st in cx.steps_of(_WF_ALIGN, only):
+        fn, args, key = st[0], list(st[1]), st[2]
+        what = f"{fn} ({key})"
+        src, centroid, shift, size, out = args
+        rows_out(what, src, out, None)
+        try:
+            args[2], args[3] = check_alignment(what, src.length, constant(what, "shift", shift), constant(what, "size", size), out.length)
+        except ValueError as e:
+            raise ProcessingChainError(str(e)) from None
+        if isinstance(centroid, Var) and centroid.kind == "const":
+            centroid = args[1] = centroid.const
+        if _is_number(centroid) and np.isnan(centroid):
+            raise DSPFatal("centroid is nan")
+        _rows_in_memory(cx, src, fn, key)
+        args[1] = _operand_in_memory(cx, args[1], fn, key, written_first=True)
+        step = cx.replace(st, (fn, args, key))
+        corr = next((x for x in cx.steps if x[0] == _WF_CORR and x[1][0] is out), None)
+        if corr is None:
+            cx.stage([step], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+            continue
+        corr = corr_checked(corr)
+        wanted = out.name in cx.out_names or any(u is not corr for u in cx.users_of(out))
+        cx.stage([step, corr], [], f"{fn} {key} + {_WF_CORR} {corr[2]} in one launch on rows", wfs=([out] if wanted else []) + [corr[1][4]], rows_first=True)
+    for st in cx.steps_of(_WF_CORR, only):
+        src = st[1][0]
+        if _base_of(src) is not None:
+            _rows_in_memory(cx, src, st[0], st[2])  # (an alignment's window: its stage first, and with it this step)
+        if not cx.has(st):
+            continue
+        st = corr_checked(st)
+        cx.stage([st], [], f"{st[0]} {st[2]} on rows", wfs=[st[1][4]], rows_first=True)
+    for st in cx.steps_of(_WF_CENTROID, only):
+        fn, args, key = st[0], list(st[1]), st[2]
+        what = f"{fn} ({key})"
+        src, shift, out = args
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{what}: '{src}' is not a waveform")
+        if not isinstance(out, Var):
+            raise ProcessingChainError(f"{what}: name the centroid")
+        args[1] = check_centroid_shift(what, src.length, constant(what, "shift", shift))
+        _rows_in_memory(cx, src, fn, key)
+        cx.stage([cx.replace(st, (fn, args, key))], [out], f"{fn} {key} on rows")
+    for st in cx.steps_of(_INL, only):
+        fn, (src, _table, out), key = st
+        what = f"{fn} ({key})"
+        rows_out(what, src, out, src.length if _base_of(src) is not None else None)
+        base = _base_of(src)
+        if not (base.is_input and base.source is not None and base.ext_key is None and _is_int_dtype(base)):
+            raise NotImplementedError(f"{what}: '{base.name}' is not an integer input column: inl_correction reads ADC codes, int16 or uint16 rows of the input table")
+        cx.stage([st], [], f"{fn} {key} on rows", wfs=[out], rows_first=True)
+
+
 def _stage_ml_layers(cx: _Stager, only=None):
     """The neural-network layers (ml.py) run on dsp_dense.hip and nowhere else, on rows in HBM: mandatory stages, like sort's.  Each dense or
     classification layer is a launch on rows in memory -- a chain input, a stage's waveform (the layer before it), or a waveform the program
@@ -1347,7 +1467,7 @@ def _stage_ml_layers(cx: _Stager, only=None):
 
 
 #: the family that stages each processor with a kernel of its own (``_stage_producers`` asks it for one step)
-_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _RC_CR2: _stage_pileup, _BI_LEVEL: _stage_pileup, _PEAK_SNR: _stage_pulses, _MULTI_A: _stage_pulses, **dict.fromkeys(_TAILFIT, _stage_tailfit), _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
+_FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _RC_CR2: _stage_pileup, _BI_LEVEL: _stage_pileup, _PEAK_SNR: _stage_pulses, _MULTI_A: _stage_pulses, **dict.fromkeys(_TAILFIT, _stage_tailfit), **dict.fromkeys(_ALIGN, _stage_align), _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
               _MULTI_EXTREMA: _stage_multi_extrema, _MULTI_TPT: _stage_thresholds, _TIME_OVER: _stage_thresholds, _PSD: _stage_spectrum,
               _SORT: _stage_sort, _INTERP: _stage_interp_upsampler, **dict.fromkeys(_ML, _stage_ml_layers)}
 
@@ -1380,6 +1500,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_pileup(cx)
     _stage_pulses(cx)
     _stage_tailfit(cx)
+    _stage_align(cx)
     _stage_spectrum(cx)
     _stage_sort(cx)
     _stage_interp_upsampler(cx)
@@ -2095,6 +2216,38 @@ class _Emitter:
         self.release(pars, si)
         self.release(src, si)
 
+    def inl_correction(self, si, fn, args, what):
+        """the whole program of the stage: LOAD of the integer rows, INL_CORRECTION; the store of the corrected row follows"""
+        src = self.ensure_loaded(args[0], si)
+        out = self.out_wf(args[2], src.length, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_INL_CORRECTION, dst=out.slot, src=src.slot, io=self.taps_io(args[1]))
+        self.release(src, si)
+
+    def get_wf_centroid(self, si, fn, args, what):
+        """the whole program of the stage: LOAD, WF_CENTROID; the store of the centroid follows"""
+        src = self.ensure_loaded(args[0], si)
+        o = self.out_scalar(args[2])
+        self.p.add_op(_lib.OP_WF_CENTROID, dst=o.sreg, src=src.slot, sp=(self.scalar_operand(args[1], args, what=what),))
+        self.release(src, si)
+
+    def wf_alignment(self, si, fn, args, what):
+        """LOAD, WF_ALIGNMENT of the aligner's stage; a wf_correction of the window may follow, then the stores"""
+        src = self.ensure_loaded(args[0], si)
+        sp = tuple(self.scalar_operand(args[k], args, what=what) for k in (1, 2, 3))
+        out = self.out_wf(args[4], None, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_WF_ALIGNMENT, dst=out.slot, src=src.slot, sp=sp)
+        self.release(src, si)
+
+    def wf_correction(self, si, fn, args, what):
+        """WF_CORRECTION on rows loaded from memory, or on the window of an alignment in the same program"""
+        src = self.ensure_loaded(args[0], si)
+        out = self.out_wf(args[4], src.length, fn)
+        out.slot = self.new_slot(out.length)
+        self.p.add_op(_lib.OP_WF_CORRECTION, dst=out.slot, src=src.slot, io=self.taps_io(args[1]), ip=(int(args[2]), int(args[3])))
+        self.release(src, si)
+
     def taps_io(self, v):
         """the binding of a constant array, made at its first use"""
         if v.io is None:
@@ -2307,6 +2460,7 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          _HISTOGRAM: _Emitter.histogram, _HISTOGRAM_STATS: _Emitter.histogram_stats, _MULTI_TPT: _Emitter.multi_time_point_thresh,
          _PSD: _Emitter.psd, _SORT: _Emitter.sort, _INTERP: _Emitter.interpolating_upsampler, _REFLECT: _Emitter.reflected_convolve, _RC_CR2: _Emitter.rc_cr2,
          _BI_LEVEL: _Emitter.bi_level_zero_crossing, _PEAK_SNR: _Emitter.peak_snr_threshold, _MULTI_A: _Emitter.multi_a_filter,
+         _INL: _Emitter.inl_correction, _WF_CENTROID: _Emitter.get_wf_centroid, _WF_ALIGN: _Emitter.wf_alignment, _WF_CORR: _Emitter.wf_correction,
          _LOG_CHECK: _Emitter.log_check, _POLY_FIT: _Emitter.poly_fit, _POLY_DIFF: _Emitter.poly_residual, _POLY_EXP_RMS: _Emitter.poly_residual,
          _NORMALISE: _Emitter.normalisation_layer, **dict.fromkeys(_DENSE_LAYERS, _Emitter.dense_layer)}
 

@@ -574,6 +574,50 @@ int dsp_poly_residual_rows(ROWS, int compute_dtype, int32_t exp_rms, const void*
         return DSP_OK;
     });
 }
+// inl_correction, get_wf_centroid, wf_alignment, wf_correction: one entry each for both loops; the tables are bound like a filter's taps, in the
+// loop's type
+int dsp_inl_correction_rows(ROWS, int compute_dtype, const void* inl_dev, int32_t inl_len, void* out, int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "inl_correction: compute_dtype is DSP_F32 or DSP_F64");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (inl_len < 1 || !inl_dev) return dsp_fail(DSP_ERR_ARG, "inl_correction: inl_dev holds the inl_len >= 1 entries of the table on the device");
+        const int s_in = m.load(IN), s_out = m.add_slot(wf_len);
+        m.op(DSP_OP_INL_CORRECTION, s_out, s_in, m.add_io(DSP_IO_TAPS, compute_dtype, inl_len, 0, inl_dev));
+        m.store(s_out, {out, wf_len, out_stride});
+        return DSP_OK;
+    });
+}
+int dsp_wf_centroid_rows(ROWS, int compute_dtype, double shift, void* centroid_out, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "get_wf_centroid: compute_dtype is DSP_F32 or DSP_F64");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        m.n_sregs = 1;
+        const int s_in = m.load(IN);
+        m.op(DSP_OP_WF_CENTROID, 0, s_in, 0, {}, {{nullptr, shift}});
+        m.store_scalar(0, centroid_out, compute_dtype);
+        return DSP_OK;
+    });
+}
+int dsp_wf_alignment_rows(ROWS, int compute_dtype, const void* centroid_dev, double centroid, double shift, double size, void* out, int32_t out_len,
+                          int64_t out_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "wf_alignment: compute_dtype is DSP_F32 or DSP_F64");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (out_len < 1) return dsp_fail(DSP_ERR_ARG, "wf_alignment: w_out holds at least one sample");
+        const int s_in = m.load(IN), s_out = m.add_slot(out_len);
+        m.op(DSP_OP_WF_ALIGNMENT, s_out, s_in, 0, {}, {{centroid_dev, centroid}, {nullptr, shift}, {nullptr, size}});
+        m.store(s_out, {out, out_len, out_stride});
+        return DSP_OK;
+    });
+}
+int dsp_wf_correction_rows(ROWS, int compute_dtype, const void* corr_dev, int32_t corr_len, int32_t start_idx, int32_t stop_idx, void* out, int64_t out_stride,
+                           TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "wf_correction: compute_dtype is DSP_F32 or DSP_F64");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (corr_len < 1 || !corr_dev) return dsp_fail(DSP_ERR_ARG, "wf_correction: corr_dev holds the corr_len >= 1 entries of w_corr on the device");
+        const int s_in = m.load(IN), s_out = m.add_slot(wf_len);
+        m.op(DSP_OP_WF_CORRECTION, s_out, s_in, m.add_io(DSP_IO_TAPS, compute_dtype, corr_len, 0, corr_dev), {start_idx, stop_idx});
+        m.store(s_out, {out, wf_len, out_stride});
+        return DSP_OK;
+    });
+}
 #undef ROWS
 #undef IN
 #undef TAIL

@@ -728,6 +728,21 @@ static int launch_tailfit(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, voi
     return launch_on_rows(ch, n_wf, stream, A, ch->tailfit_src, dsp_internal_launch_tailfit, "tail-fit kernel launch");
 }
 
+static int launch_align(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
+    AlignArgs A = ch->align;
+    A.wf = io_ptrs[ch->align_src.io];  // (the inputs' offsets travel in the arguments)
+    A.table = at(ch->gio_table);
+    A.table_nan = A.table ? ch->dev_err + DSP_ERR_TABLE_WORD : nullptr;
+    A.centroid = at(ch->gio_centroid);
+    A.out = at(ch->gio_out);
+    A.out2 = at(ch->gio_out2);
+    A.scalar_out = at(ch->gio_scalar);
+    // 16-byte stores of the outputs the kernel streams (inl_correction's, wf_correction's): launch_interp's rule
+    A.out_vec = A.mode != DSP_ALIGN_WINDOW && A.out && (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
+    return launch_on_rows(ch, n_wf, stream, A, ch->align_src, dsp_internal_launch_align, "align kernel launch");
+}
+
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
     hipError_t e = (hipError_t)dsp_internal_launch_scalar(ch->dev, ptrs, n_wf, ch->host.n_sregs, ch->i64 ? 2 : (ch->f64 ? 1 : 0), (hipStream_t)stream);
     return launched(ch, stream, e, "scalar kernel launch");
@@ -919,6 +934,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_PILEUP)) return launch_pileup(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_PULSES)) return launch_pulses(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_TAILFIT)) return launch_tailfit(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_ALIGN)) return launch_align(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -1050,6 +1066,7 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
         case DSP_ROUTE_EXTREMA:
         case DSP_ROUTE_THRESH:
         case DSP_ROUTE_PULSES:
+        case DSP_ROUTE_ALIGN:
         case DSP_ROUTE_PZ_ROWS:
         case DSP_ROUTE_REDUCE: lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4); break;
         case DSP_ROUTE_FIR_RUNS: lds = dsp_fir_runs::lds_bytes(ch->runs.m) / 4, wpb = 4, b = runs_blocks(ch, n_wf); break;

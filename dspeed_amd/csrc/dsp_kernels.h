@@ -21,6 +21,7 @@ enum dsp_route {
     DSP_ROUTE_PILEUP,   // (nor this: RC_CR2 and BI_LEVEL_ZERO_CROSSING)
     DSP_ROUTE_PULSES,   // (nor this: PEAK_SNR_THRESHOLD and MULTI_A_FILTER)
     DSP_ROUTE_TAILFIT,  // (nor this: LOG_CHECK, POLY_FIT, POLY_DIFF and POLY_EXP_RMS)
+    DSP_ROUTE_ALIGN,    // (nor this: INL_CORRECTION, WF_CENTROID, WF_ALIGNMENT and WF_CORRECTION)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -37,6 +38,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_pileup_kernel",
     "dsp_pulses_kernel",
     "dsp_tailfit_kernel",
+    "dsp_align_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");

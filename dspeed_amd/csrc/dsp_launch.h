@@ -59,6 +59,8 @@ int dsp_internal_launch_pileup(const PileupArgs* A, int64_t n_wf, int dtype, int
 int dsp_internal_launch_pulses(const PulsesArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_tailfit.hip (dtype: the rows'; vec as above, for the loads -- the stores' is A->out_vec; LDS: dsp_tailfit::lds_bytes, static)
 int dsp_internal_launch_tailfit(const TailfitArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+// dsp_align.hip (dtype: the rows'; the loop is A->f64; vec as above, for the streaming loads -- the stores' is A->out_vec; nothing in LDS)
+int dsp_internal_launch_align(const AlignArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_scalar.hip (type: 0 float32, 1 float64, 2 int64 registers)
 int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);
 int dsp_internal_set_scalar_lds(int lds_bytes);

@@ -79,6 +79,8 @@ extern "C" const char* dsp_fatal_message(int code) {
         case DSP_E_PSD_LEN: return "Size of psd must be len(w_in)//2+1";
         case DSP_E_RC_CR2_NAN: return "RC-CR^2 filter produced nans in output.";
         case DSP_E_MAF_LEN: return "The length of your return array must be smaller than the length of your waveform";
+        case DSP_E_INL_RANGE: return "ADC code out of range for INL array";  // (raised with the code and the table's length, as the reference formats it)
+        case DSP_E_ALIGN_CENTROID: return "centroid is nan";
         default: return "";
     }
 }
@@ -118,6 +120,7 @@ static bool match_reflect_shape(const PlanCtx& c, const char** why);
 static bool match_pileup_shape(const PlanCtx& c, const char** why);
 static bool match_pulses_shape(const PlanCtx& c, const char** why);
 static bool match_tailfit_shape(const PlanCtx& c, const char** why);
+static bool match_align_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -139,6 +142,8 @@ static const KernelOnlyRoute kernel_only_routes[] = {
      "DSP_OP_PEAK_SNR_THRESHOLD / DSP_OP_MULTI_A_FILTER (peak_snr_threshold, multi_a_filter) run on dsp_pulses_kernel only"},
     {DSP_ROUTE_TAILFIT, {DSP_OP_LOG_CHECK, DSP_OP_POLY_FIT, DSP_OP_POLY_DIFF, DSP_OP_POLY_EXP_RMS}, match_tailfit_shape,
      "DSP_OP_LOG_CHECK / DSP_OP_POLY_FIT / DSP_OP_POLY_DIFF / DSP_OP_POLY_EXP_RMS (log_check, poly_fit, poly_diff, poly_exp_rms) run on dsp_tailfit_kernel only"},
+    {DSP_ROUTE_ALIGN, {DSP_OP_INL_CORRECTION, DSP_OP_WF_CENTROID, DSP_OP_WF_ALIGNMENT, DSP_OP_WF_CORRECTION}, match_align_shape,
+     "DSP_OP_INL_CORRECTION / DSP_OP_WF_CENTROID / DSP_OP_WF_ALIGNMENT / DSP_OP_WF_CORRECTION (inl_correction, get_wf_centroid, wf_alignment, wf_correction) run on dsp_align_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -1019,6 +1024,89 @@ static bool match_tailfit_shape(const PlanCtx& c, const char** why) {
     return true;
 }
 
+// Is the program one of the waveform aligner's (dsp_align.hip)?
+//   LOAD s;  INL_CORRECTION of s;  STORE of its n samples
+//   LOAD s;  WF_CENTROID of s;  STORE_SCALAR of its register
+//   LOAD s;  WF_ALIGNMENT of s into a slot of `size` samples;  STORE of them
+//   LOAD s;  WF_CORRECTION of s;  STORE of its n samples
+//   LOAD s;  WF_ALIGNMENT of s;  WF_CORRECTION of the aligned row;  [STORE of the aligned row;]  STORE of the corrected row
+// Parameters, lengths and indices are lower_op's business (every program that holds one of the ops passes there first).  Why not, otherwise: `why`.
+static bool match_align_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    const dsp_io_desc* io = c.io;
+    const int n = c.n_ops;
+    *why = "the program must be exactly LOAD, INL_CORRECTION, STORE; or LOAD, WF_CENTROID, STORE_SCALAR; or LOAD, WF_ALIGNMENT, STORE; or LOAD, WF_CORRECTION, STORE; "
+           "or LOAD, WF_ALIGNMENT, WF_CORRECTION, [STORE of the aligned row,] STORE";
+    auto is = [&](int i, int opcode) { return i >= 0 && i < n && ops[i].opcode == opcode; };
+    if (n < 3 || !is(0, DSP_OP_LOAD)) return false;
+    const dsp_op &ld = ops[0], &op = ops[1];
+    const dsp_op* cr = is(1, DSP_OP_WF_ALIGNMENT) && is(2, DSP_OP_WF_CORRECTION) ? &ops[2] : nullptr;
+    const int first_store = cr ? 3 : 2, n_stores = n - first_store;
+    if (op.src != ld.dst || (cr ? n_stores != 1 && n_stores != 2 : n_stores != 1) || c.n_slots != (is(1, DSP_OP_WF_CENTROID) ? 1 : (cr ? 3 : 2))) return false;
+    for (int i = first_store; i < n; ++i)
+        if (!is(i, is(1, DSP_OP_WF_CENTROID) ? DSP_OP_STORE_SCALAR : DSP_OP_STORE)) return false;
+    AlignArgs& A = ch->align;
+    memset(&A, 0, sizeof A);
+    ch->gio_table = ch->gio_centroid = ch->gio_out = ch->gio_out2 = ch->gio_scalar = -1;
+    constexpr unsigned INTS = 1u << DSP_I16 | 1u << DSP_U16 | 1u << DSP_I32 | 1u << DSP_U32;
+    unsigned f32_rows = ROWS_F32_LOOP, f64_rows = ROWS_F64;
+    const char* type_why = "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows";
+    switch (op.opcode) {
+        case DSP_OP_INL_CORRECTION:
+            A.mode = DSP_ALIGN_INL;
+            f32_rows = f64_rows = INTS;
+            type_why = "inl_correction reads DSP_I16, DSP_U16, DSP_I32 or DSP_U32 rows: an ADC code is an integer";
+            break;
+        case DSP_OP_WF_CENTROID: A.mode = DSP_ALIGN_CENTROID; break;
+        case DSP_OP_WF_ALIGNMENT:
+            A.mode = DSP_ALIGN_WINDOW;
+            f64_rows |= INTS;  // (the float32 loop: int16 and uint16, which a float32 holds exactly -- int32 rows select the float64 loop, as everywhere)
+            type_why = "wf_alignment takes the loop's float rows, DSP_I16 or DSP_U16 rows in either loop, DSP_I32 or DSP_U32 rows in the float64 loop";
+            break;
+        case DSP_OP_WF_CORRECTION: A.mode = DSP_ALIGN_CORRECT; break;
+        default: return false;
+    }
+    if (!bind_rows(c, ld, f32_rows, f64_rows, A, ch->align_src, why, type_why)) return false;
+    A.f64 = c.f64 ? 1 : 0;
+    if (A.mode == DSP_ALIGN_CENTROID) {
+        const dsp_op& sc = ops[2];
+        *why = "the centroid is stored once, into a column of the loop's type";
+        if (sc.ip[0] != op.dst || io[sc.io].dtype != c.compute_dtype) return false;
+        ch->gio_scalar = sc.io;
+        A.scalar_stride = io[sc.io].row_stride;
+        A.shift = op_const(c, op, 0);
+        return true;
+    }
+    if (A.mode == DSP_ALIGN_WINDOW) {
+        *why = "centroid is a constant or a per-event column of the loop's type";
+        if (!bind_operand(c, op, 0, ch->gio_centroid, A.centroid_stride, A.centroid_const)) return false;
+        A.shift = op_const(c, op, 1);
+        A.size = c.slot_len[op.dst];
+    }
+    const dsp_op& tb = cr ? *cr : op;  // the op with a table
+    if (tb.opcode != DSP_OP_WF_ALIGNMENT) {
+        ch->gio_table = tb.io;
+        A.table_len = io[tb.io].len;
+        A.start = tb.ip[0];
+        A.stop = tb.ip[1];
+    }
+    *why = "wf_correction in the same program reads exactly the aligned row";
+    if (cr && (cr->src != op.dst || cr->dst == op.dst)) return false;
+    A.correct = cr ? 1 : 0;
+    *why = "each output row is stored once, whole, in the loop's type";
+    for (int i = first_store; i < n; ++i) {
+        const dsp_op& st = ops[i];
+        const dsp_io_desc& o = io[st.io];
+        int* slot = cr && st.src == cr->dst ? &ch->gio_out2 : (st.src == op.dst ? &ch->gio_out : nullptr);
+        if (!slot || *slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        *slot = st.io;
+        (slot == &ch->gio_out ? A.out_stride : A.out2_stride) = o.row_stride;
+    }
+    if (cr ? ch->gio_out2 < 0 || ch->gio_out2 == ch->gio_out : ch->gio_out < 0) return false;
+    return true;
+}
+
 // Does the program have the shape of the current-branch kernel (dsp_current.hip)?
 //   LOAD s0;  WINDOWER s1 <- s0 (start: constant or float32 column);  AVG_CURRENT s2 <- s1;  UPSAMPLER s3 <- s2;
 //   MOVING_WINDOW_MULTI d <- s3 (3 windows, alternating);  MIN_MAX of d;  STORE_SCALARs of its four registers
@@ -1553,7 +1641,11 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_RC_CR2:
         case DSP_OP_LOG_CHECK:
         case DSP_OP_POLY_FIT:
+        case DSP_OP_INL_CORRECTION:
+        case DSP_OP_WF_ALIGNMENT:
+        case DSP_OP_WF_CORRECTION:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
+        case DSP_OP_WF_CENTROID: out[0] = o.src; return 1;
         case DSP_OP_POLY_DIFF:
         case DSP_OP_POLY_EXP_RMS: out[0] = o.src; out[1] = o.ip[0]; return 2;
         case DSP_OP_NORMALISE: out[0] = o.src; return 1;
@@ -1749,7 +1841,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows; PEAK_SNR_THRESHOLD, MULTI_A_FILTER: nothing in LDS; LOG_CHECK, POLY_FIT, POLY_DIFF, POLY_EXP_RMS: a tile of 64 rows)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows; PEAK_SNR_THRESHOLD, MULTI_A_FILTER: nothing in LDS; LOG_CHECK, POLY_FIT, POLY_DIFF, POLY_EXP_RMS: a tile of 64 rows; INL_CORRECTION, WF_CENTROID, WF_ALIGNMENT, WF_CORRECTION: nothing in LDS)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1796,7 +1888,8 @@ static int bind_io(PlanCtx& c) {
         if ((a.kind == DSP_IO_WF_IN || a.kind == DSP_IO_WF_OUT) && (a.row_stride != 0 || a.kind == DSP_IO_WF_OUT) && (int64_t)a.offset + a.len > a.row_stride)
             return fail(DSP_ERR_ARG, "io %d: rows of %lld elements do not hold offset %d + len %d", k, (long long)a.row_stride, a.offset, a.len);
         // which rows may feed which loop: NumPy's can_cast rule as ProcessorManager applies it (processing_chain.py:1565-1572)
-        if (a.kind == DSP_IO_WF_IN && !f64 && (a.dtype == DSP_I32 || a.dtype == DSP_U32 || a.dtype == DSP_F64))
+        if (a.kind == DSP_IO_WF_IN && !f64 && (a.dtype == DSP_I32 || a.dtype == DSP_U32 || a.dtype == DSP_F64) &&
+            !(c.only && c.only->route == DSP_ROUTE_ALIGN && a.dtype != DSP_F64))  // (inl_correction's loop if->f: the matcher sees to the rest)
             return fail(DSP_ERR_ARG, "io %d: int32/uint32/float64 rows select the float64 loop (compute_dtype DSP_F64)", k);
         const bool is_out = a.kind == DSP_IO_WF_OUT || a.kind == DSP_IO_SCALAR_OUT;
         if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT) &&
@@ -2298,6 +2391,60 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
             const int m = slot_len[o.ip[0]];
             if (m > DSP_POLY_MAX) return fail(DSP_ERR_UNSUPPORTED, "%s: " DSP_POLY_MAX_TEXT, name, DSP_POLY_MAX, m);
             if (!dsp_poly_powers_fit(slot_len[o.src], m)) return fail(DSP_ERR_UNSUPPORTED, "%s: " DSP_POLY_POWER_TEXT, name, slot_len[o.src], m);
+            break;
+        }
+        case DSP_OP_INL_CORRECTION: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad INL_CORRECTION (src: the slot of the row; dst: another slot, for the corrected row; io: the table)", i);
+            if (slot_len[o.dst] != slot_len[o.src])
+                return fail(DSP_ERR_ARG, "inl_correction: the output has the length of the input (len(w_in) = %d, len(w_out) = %d)", slot_len[o.src], slot_len[o.dst]);
+            if (!need_io(c, o, DSP_IO_TAPS) || c.io[o.io].dtype != c.compute_dtype || c.io[o.io].len < 1)
+                return fail(DSP_ERR_ARG, "inl_correction: io is a DSP_IO_TAPS binding of the p >= 1 entries of inl in the loop's type");
+            break;
+        }
+        case DSP_OP_WF_CENTROID: {
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs)
+                return fail(DSP_ERR_ARG, "op %d: bad WF_CENTROID (src: the slot of the row; dst: the register of the centroid)", i);
+            if (o.sp[0].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "get_wf_centroid: shift is a constant of the program, not a per-event value");
+            const double shift = op_const(c, o, 0);  // get_wf_centroid.py:55-60
+            if (std::isnan(shift)) return fail(DSP_ERR_ARG, "shift is nan");
+            if (shift < 0) return fail(DSP_ERR_ARG, "shift must be positive");
+            if (shift > slot_len[o.src] - 1) return fail(DSP_ERR_ARG, "shift must be shorter than input waveform size");
+            break;
+        }
+        case DSP_OP_WF_ALIGNMENT: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad WF_ALIGNMENT (src: the slot of the row; dst: another slot, for the window; sp: centroid, shift, size)", i);
+            if (o.sp[0].kind == DSP_ARG_REG) return fail(DSP_ERR_UNSUPPORTED, "wf_alignment: centroid is a constant or a per-event column, not a register of the program");
+            if (o.sp[1].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "wf_alignment: shift is a constant of the program, not a per-event value");
+            if (o.sp[2].kind != DSP_ARG_CONST) return fail(DSP_ERR_UNSUPPORTED, "wf_alignment: size is a constant of the program, not a per-event value");
+            const int n = slot_len[o.src];
+            const double shift = op_const(c, o, 1), size = op_const(c, o, 2);  // wf_alignment.py:63-78
+            if (o.sp[0].kind == DSP_ARG_CONST && std::isnan(o.sp[0].value)) return fail(DSP_E_ALIGN_CENTROID, "%s", dsp_fatal_message(DSP_E_ALIGN_CENTROID));
+            if (std::isnan(shift)) return fail(DSP_ERR_ARG, "shift is nan");
+            if (shift < 0) return fail(DSP_ERR_ARG, "shift must be positive");
+            if (shift > n) return fail(DSP_ERR_ARG, "shift must be shorter than input waveform size");
+            if (std::isnan(size)) return fail(DSP_ERR_ARG, "size is nan");
+            if (size <= 0) return fail(DSP_ERR_ARG, "size must be positive");
+            if (size > n) return fail(DSP_ERR_ARG, "size must be shorter than input waveform size");
+            if (size != (double)slot_len[o.dst])
+                return fail(DSP_ERR_ARG, "wf_alignment: size is a whole number and equals len(w_out) (size = %g, len(w_out) = %d)", size, slot_len[o.dst]);
+            break;
+        }
+        case DSP_OP_WF_CORRECTION: {
+            if (!check_slot(P, o.src) || !check_slot(P, o.dst) || o.dst == o.src)
+                return fail(DSP_ERR_ARG, "op %d: bad WF_CORRECTION (src: the slot of the row; dst: another slot, for the corrected row; io: w_corr; ip: start_idx, stop_idx)", i);
+            if (slot_len[o.dst] != slot_len[o.src])
+                return fail(DSP_ERR_ARG, "wf_correction: the output has the length of the input (len(w_in) = %d, len(w_out) = %d)", slot_len[o.src], slot_len[o.dst]);
+            if (!need_io(c, o, DSP_IO_TAPS) || c.io[o.io].dtype != c.compute_dtype)
+                return fail(DSP_ERR_ARG, "wf_correction: io is a DSP_IO_TAPS binding of w_corr in the loop's type");
+            const int n = slot_len[o.src], start = o.ip[0], stop = o.ip[1];  // wf_correction.py:64-77
+            if (start < 0) return fail(DSP_ERR_ARG, "start_idx must be positive");
+            if (start > n) return fail(DSP_ERR_ARG, "start_idx must be shorter than input waveform size");
+            if (stop <= 0) return fail(DSP_ERR_ARG, "stop_idx must be positive");
+            if (stop > n) return fail(DSP_ERR_ARG, "stop_idx must be shorter than input waveform size");
+            if (start >= stop) return fail(DSP_ERR_ARG, "start_idx must be smaller than stop_idx");
+            if (stop - start > c.io[o.io].len) return fail(DSP_ERR_ARG, "stop_idx - start_idx must be smaller than len(w_corr)");
             break;
         }
         case DSP_OP_DWT_HAAR: {

@@ -91,7 +91,7 @@ struct ChainPlan {
     int dio_walk[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1}, dio_walk_thr[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1},
         dio_walk_ts[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1};
     // The ops no interpreter case stands behind: a program that holds one runs on that op's kernel or is refused (the table of these routes
-    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM, DSP_ROUTE_SORT, DSP_ROUTE_INTERP, DSP_ROUTE_DENSE, DSP_ROUTE_REFLECT, DSP_ROUTE_PILEUP, DSP_ROUTE_PULSES or DSP_ROUTE_TAILFIT; DSP_ROUTE_VM: the program holds none.
+    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM, DSP_ROUTE_SORT, DSP_ROUTE_INTERP, DSP_ROUTE_DENSE, DSP_ROUTE_REFLECT, DSP_ROUTE_PILEUP, DSP_ROUTE_PULSES, DSP_ROUTE_TAILFIT or DSP_ROUTE_ALIGN; DSP_ROUTE_VM: the program holds none.
     dsp_route kernel_only = DSP_ROUTE_VM;
     // the peak finder (dsp_extrema.hip): the one kernel a program with MULTI_EXTREMA runs on
     ExtremaArgs ext{};
@@ -137,6 +137,10 @@ struct ChainPlan {
     TailfitArgs tailfit{};
     RowSource tailfit_src{};
     int aio_sub = -1, aio_inv = -1, aio_pars = -1, aio_out = -1, aio_pars_out = -1, aio_mean = -1, aio_rms = -1;
+    // inl_correction, get_wf_centroid, wf_alignment and wf_correction, the last two apart or in one launch (dsp_align.hip): the one kernel a program with any of them runs on
+    AlignArgs align{};
+    RowSource align_src{};
+    int gio_table = -1, gio_centroid = -1, gio_out = -1, gio_out2 = -1, gio_scalar = -1;
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};

@@ -71,7 +71,9 @@ struct IoPtrs {
     void* p[DSP_MAX_IO];
 };
 
-// device error word layout: err[0] = DSP_E_* code (0 = none), err[1..2] = row (lo, hi)
+// device error word layout: err[0] = DSP_E_* code (0 = none), err[1..2] = row (lo, hi); behind the diagnostic sums, word DSP_ERR_TABLE_WORD:
+// the aligner's "the table holds a NaN" (dsp_align.hip), cleared and written by every launch that has a table
+#define DSP_ERR_TABLE_WORD 16
 #define DSP_ERR_WORDS 20 /* 4 error words + 6 x 64-bit diagnostic phase-cycle sums */
 
 // arguments of the lane-per-waveform fit kernel (dsp_fit.hip), filled by dsp_linear_slope_fit_rows
@@ -539,6 +541,70 @@ struct TailfitArgs {
     void* rms_out;
     int64_t rms_stride;
 };
+
+// arguments of the waveform aligner (dsp_align.hip), filled by the planner when a program has one of the shapes
+//   LOAD -> INL_CORRECTION -> STORE
+//   LOAD -> WF_CENTROID -> STORE_SCALAR
+//   LOAD -> WF_ALIGNMENT -> STORE
+//   LOAD -> WF_CORRECTION -> STORE
+//   LOAD -> WF_ALIGNMENT -> WF_CORRECTION [-> STORE of the aligned row] -> STORE of the corrected row
+// A wavefront per row, four to a workgroup, nothing in LDS (dsp_pulses.hip's geometry).
+enum { DSP_ALIGN_INL = 1, DSP_ALIGN_CENTROID = 2, DSP_ALIGN_WINDOW = 3, DSP_ALIGN_CORRECT = 4 };
+struct AlignArgs {
+    const void* wf;           // the rows: see DSP_OP_WF_ALIGNMENT (dspeed_hip.h) for the types each op takes
+    int64_t wf_stride;
+    int32_t wf_offset, len;   // first sample, samples
+    int32_t mode;             // DSP_ALIGN_*: the first op of the launch
+    int32_t f64;              // 1: the float64 loop (the rows' type alone does not tell: int32 rows feed both)
+    int32_t out_vec;          // 1: 16-byte stores of the streamed outputs (their start and stride are whole vectors: set per call)
+    int32_t correct;          // with DSP_ALIGN_WINDOW: 1, the template is subtracted from the window before it is stored
+    const void* table;        // inl (DSP_ALIGN_INL) or w_corr: table_len values of the loop's type
+    int32_t table_len;
+    int32_t start, stop;      // wf_correction: the template is subtracted on [start, stop) of the row it reads
+    const int* table_nan;     // device word: nonzero, the table holds a NaN (written by the scan that runs ahead of the launch); set per call
+    const void* centroid;     // wf_alignment: a column of the loop's type, or null: centroid_const
+    int64_t centroid_stride;
+    double centroid_const;
+    double shift;             // get_wf_centroid, wf_alignment: as the loop receives it
+    int32_t size;             // wf_alignment: samples of the window
+    void* out;                // rows of the loop's type: inl_correction's, wf_correction's, or the aligned row's (null: not stored)
+    int64_t out_stride;
+    void* out2;               // the corrected row behind an alignment in the same launch
+    int64_t out2_stride;
+    void* scalar_out;         // get_wf_centroid: a value of the loop's type per row
+    int64_t scalar_stride;
+};
+
+// ---- wf_alignment.py:80-87, the rule of a row: shared by the kernel, the planner's constant case and the tests' host program.
+// c, sh, s: centroid, shift, size as the loop receives them; all arithmetic in float64, int() truncating (the centroid is no NaN).
+//   kind 1  w_out = w_in[first : first + s]
+//   kind 2  w_out[:fill] = w_in[0], w_out[fill:] = w_in[:count]   (fill + count == s, count may be 0; count == 1 may also stand for
+//           NumPy's broadcast of one sample over s - fill places: count_bcast)
+//   kind 3  w_out = w_in[:s]
+//   kind 0  the two sides of line 85 differ in length and do not broadcast: the reference raises in NumPy; a NaN row here
+struct AlignWindow {
+    int kind, first, fill, count;
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline AlignWindow dsp_align_window(double c, double sh, int s, int n) {
+    const double half = (double)s / 2;
+    AlignWindow w = {3, 0, 0, 0};
+    if (c >= half && c < (double)n - half) {
+        w.kind = 1;
+        w.first = (int)(c - half);
+    } else if (c > half - sh && c < half) {
+        // (c > s/2 - sh >= s/2 - n: both casts stay far inside an int)
+        const long long ss = (long long)(((double)s + 1) / 2 - c), k = (long long)(c + half);
+        const long long lhs = ss >= s ? 0 : s - ss;                              // len(w_out[ss:]), ss >= 0 since c < s/2
+        const long long rhs = k >= 0 ? (k < n ? k : n) : (n + k > 0 ? n + k : 0);  // len(w_in[:k])
+        w.kind = (lhs == rhs || rhs == 1) ? 2 : 0;
+        w.fill = (int)(s - lhs);
+        w.count = (int)rhs;
+    }
+    return w;
+}
 
 // arguments of the matrix-core FIR kernel (dsp_fir_mfma.hip): convolve_wf 'v' + numpy.amax of up to DSP_FIR_MAXK kernels on one waveform
 #define DSP_FIR_MAXK 4

@@ -248,6 +248,8 @@ _SIGS = {
     "peak_snr_threshold": "wwssWS", "multi_a_filter": "wwW",
     # (w_in, w_log); (w_in, poly_pars[m]) with init_args (length, deg); (w_in, poly_pars[m], mean, rms) twice: the coefficients are a waveform of a stage, m theirs
     "log_check": "wW", "poly_fit": "wW", "poly_diff": "wwSS", "poly_exp_rms": "wwSS",
+    # (w_in, inl[p], w_out); (w_in, shift, centroid); (w_in, centroid, shift, size, w_out[size]); (w_in, w_corr[m], start_idx, stop_idx, w_out): inl and w_corr are constant arrays
+    "inl_correction": "waW", "get_wf_centroid": "wsS", "wf_alignment": "wsssW", "wf_correction": "waiiW",
     # ml.py: (x_in, means, variances, x_out); (x_in, kernel[n, m], [bias[m],] activation_func, x_out[m]); (x_in, kernel[n], [bias,] activation_func, x_out)
     "normalisation_layer": "waaW", "dense_layer_no_bias": "wacW", "dense_layer_with_bias": "waacW",
     "classification_layer_no_bias": "wacS", "classification_layer_with_bias": "waacS",
@@ -336,7 +338,7 @@ def _binop_unit(ua, ub, sym):
 _BOOL_MINUS = ("numpy boolean subtract, the `-` operator, is not supported, use the bitwise_xor, the `^` operator, or the logical_xor "
                "function instead.")  # (what numpy.subtract / numpy.negative raise for truth values when the reference's processor first runs)
 _WHERE_LOOPS = "BHILbhiq"  # processors/where.py:11-20: u1 u2 u4 u8 i1 i2 i4 i8 (then f4, f8)
-_GENERATORS = ("cusp_filter", "zac_filter", "t0_filter", "moving_slope")
+_GENERATORS = ("cusp_filter", "zac_filter", "t0_filter", "moving_slope", "step")
 _MODULES = ("dspeed.processors", "dspeed_amd.processors", "numpy", "np")
 # ``dspeed.processors.<file>``: the reference file that defines each processor of the registry (recipes name either the package or the file;
 # histogram_stats is also written as living in histogram)
@@ -362,6 +364,8 @@ _SMOOTHING_FILES = {"reflected_convolve_wf": ("convolutions",)}  # (processors.S
 _PILEUP_FILES = {"rc_cr2": ("rc_cr2",), "bi_level_zero_crossing_time_points": ("time_point_thresh",)}  # (processors.PILEUP, likewise)
 _PULSE_FILES = {"peak_snr_threshold": ("peak_snr_threshold",), "multi_a_filter": ("multi_a_filter",)}  # (processors.PULSES, likewise; in recipes under these strings only: compiler._add_step)
 _TAILFIT_FILES = {"log_check": ("log_check",), "poly_fit": ("poly_fit",), "poly_diff": ("poly_fit",), "poly_exp_rms": ("poly_fit",)}  # (processors.TAILFIT, likewise)
+_ALIGN_FILES = {"inl_correction": ("inl_correction",), "get_wf_centroid": ("get_wf_centroid",), "wf_alignment": ("wf_alignment",), "wf_correction": ("wf_correction",),
+                "step": ("kernels",)}  # (processors.ALIGNMENT, likewise)
 _ML_FILES = dict.fromkeys(("normalisation_layer", "dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias",
                            "classification_layer_with_bias"), ("ml",))  # (processors.ML, likewise)
 
@@ -370,7 +374,7 @@ def module_accepted(module, function) -> bool:
     """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
     pre = "dspeed.processors."
     files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ()) + _ORDER_FILES.get(function, ()) + _RESAMPLING_FILES.get(function, ())
-    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ()) + _PILEUP_FILES.get(function, ()) + _PULSE_FILES.get(function, ()) + _TAILFIT_FILES.get(function, ())
+    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ()) + _PILEUP_FILES.get(function, ()) + _PULSE_FILES.get(function, ()) + _TAILFIT_FILES.get(function, ()) + _ALIGN_FILES.get(function, ())
     return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in files)
 
 

@@ -1005,5 +1005,210 @@ poly_exp_rms = HipGUFunc("poly_exp_rms", "(n),(m)->(),()", ["ff->ff", "dd->dd"],
 # Listed here and not in __all__, like the pulse picker's processors: their call records are tests/test_tailfit_plan_cpu.py's.
 TAILFIT = ("log_check", "poly_fit", "poly_diff", "poly_exp_rms")
 
+
+# --------------------------------------------------------------------------------------------------- waveform aligner
+_INL_ROWS = (np.dtype(np.int16), np.dtype(np.uint16), np.dtype(np.int32), np.dtype(np.uint32))
+
+
+def _one_value(what, name, v):
+    """a parameter that is a constant of the call -> its value as a Python float"""
+    if isinstance(v, DeviceArray):
+        raise NotImplementedError(f"{what}: {name} is a constant of the call on the device, not a per-event value")
+    return float(_constant_of_call(v.magnitude if hasattr(v, "magnitude") else v, what, name))
+
+
+def check_centroid_shift(what, n, shift, loop_dtype=np.float32):
+    """get_wf_centroid.py:55-60 for rows of ``n`` samples: checked once for the call, in the reference's order and words -> shift as the loop receives it"""
+    shift = float(np.dtype(loop_dtype).type(_one_value(what, "shift", shift)))
+    if np.isnan(shift):
+        raise DSPFatal("shift is nan")
+    if shift < 0:
+        raise DSPFatal("shift must be positive")
+    if shift > n - 1:
+        raise DSPFatal("shift must be shorter than input waveform size")
+    return shift
+
+
+def check_alignment(what, n, shift, size, m_out, loop_dtype=np.float32):
+    """wf_alignment.py:66-78 for rows of ``n`` samples and an output of ``m_out``, in the reference's order and words; then the rule the
+    reference leaves to NumPy's broadcast: ``size`` is a whole number and equals ``len(w_out)`` -> (shift, size) as the loop receives them"""
+    ft = np.dtype(loop_dtype).type
+    shift, size = float(ft(_one_value(what, "shift", shift))), float(ft(_one_value(what, "size", size)))
+    if np.isnan(shift):
+        raise DSPFatal("shift is nan")
+    if shift < 0:
+        raise DSPFatal("shift must be positive")
+    if shift > n:
+        raise DSPFatal("shift must be shorter than input waveform size")
+    if np.isnan(size):
+        raise DSPFatal("size is nan")
+    if size <= 0:
+        raise DSPFatal("size must be positive")
+    if size > n:
+        raise DSPFatal("size must be shorter than input waveform size")
+    if size != m_out:
+        raise ValueError(f"{what}: size is a whole number and equals len(w_out) (size = {size:g}, len(w_out) = {m_out})")
+    return shift, size
+
+
+def check_correction(what, n, m, start_idx, stop_idx):
+    """wf_correction.py:64-77 for rows of ``n`` samples and a template of ``m``, in the reference's order and words -> (start, stop)"""
+    start, stop = (_as_int(_one_value(what, name, v), what) for name, v in (("start_idx", start_idx), ("stop_idx", stop_idx)))
+    if m < 1:
+        raise ValueError(f"{what}: w_corr holds at least one sample")
+    if start < 0:
+        raise DSPFatal("start_idx must be positive")
+    if start > n:
+        raise DSPFatal("start_idx must be shorter than input waveform size")
+    if stop <= 0:
+        raise DSPFatal("stop_idx must be positive")
+    if stop > n:
+        raise DSPFatal("stop_idx must be shorter than input waveform size")
+    if start >= stop:
+        raise DSPFatal("start_idx must be smaller than stop_idx")
+    if stop - start > m:
+        raise DSPFatal("stop_idx - start_idx must be smaller than len(w_corr)")
+    return start, stop
+
+
+def inl_range_error(row, p):
+    """the reference's text for the first sample of ``row`` outside ``[0, p)`` (inl_correction.py:59-61)"""
+    codes = np.asarray(row).astype(np.int64).reshape(-1)
+    bad = np.flatnonzero((codes < 0) | (codes >= p))
+    return DSPFatal(f"ADC code {int(codes[bad[0]]) if bad.size else '?'} out of range for INL array of length {p}")
+
+
+def _constant_array(c, what, name, v, ft):
+    """a '(p)' input that is one constant array for all rows -> (DeviceArray, length)"""
+    if isinstance(v, DeviceArray):
+        if np.dtype(v.dtype) != np.dtype(ft) or len(v.shape) != 1:
+            raise TypeError(f"{what}: {name} on the device is one row of {np.dtype(ft).name} values in the {np.dtype(ft).name} loop")
+        return v, int(v.shape[-1])
+    a = np.asarray(v.magnitude if hasattr(v, "magnitude") else v)
+    if a.ndim != 1:
+        raise NotImplementedError(f"{what}: {name} is one constant array of the call on the device, not an array per event")
+    if a.size == 0:
+        raise ValueError(f"{what}: {name} holds at least one value")
+    dev = DeviceArray.from_numpy(np.ascontiguousarray(a, dtype=ft))
+    c.st.keep.append(dev)
+    return dev, int(a.size)
+
+
+def _out_len(out):
+    return int(out.shape[-1]) if len(out.shape) else 0
+
+
+def _inl_correction(g, *args):
+    """one C entry for both loops; the table's type selects the loop (``if->f``, ``id->d``), the rows are integers.  ``w_out`` may be left out."""
+    what = g.__name__
+    (w_in, inl), (out,) = _split(g, args)
+    if np.dtype(dtype_of(w_in)) not in _INL_ROWS:
+        raise TypeError(f"{what}: w_in holds int16, uint16, int32 or uint32 ADC codes ({np.dtype(dtype_of(w_in))} given): the reference has no loop for anything else")
+    with device_call(what) as c:
+        c.ptr, c.code, c.n_wf, c.n, c.stride, c.one_d = c.st.wf_in(w_in)
+        c.ft = np.float64 if np.dtype(dtype_of(inl)) == np.dtype(np.float64) else np.float32
+        if out is not None and not isinstance(out, (np.ndarray, DeviceArray)):
+            raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+        if out is not None and _out_len(out) != c.n:
+            raise ValueError(f"{what}: the output has the length of the input (len(w_in) = {c.n}, len(w_out) = {_out_len(out)})")
+        table, p = _constant_array(c, what, "inl", inl, c.ft)
+        ptr, stride = c.out(out, "n")
+        row = _lib.C.c_int64(-1)
+        rc = _lib.lib().dsp_inl_correction_rows(*c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, table.ptr, p, ptr, stride, None, _lib.C.byref(row))
+        if rc == _lib.E_INL_RANGE and row.value >= 0:
+            # the error word holds a code and a row: that row is read back and its first offending sample named
+            r = int(row.value)
+            if isinstance(w_in, DeviceArray):  # (that row alone comes back)
+                codes = DeviceArray.from_ptr(w_in.ptr + r * c.n * np.dtype(w_in.dtype).itemsize, (c.n,), w_in.dtype).to_numpy()
+            else:
+                codes = np.asarray(w_in).reshape(c.n_wf, c.n)[r]
+            err = inl_range_error(codes, p)
+            err.wf_range, err.processor = range(r, r + 1), what
+            raise err
+        _lib.check(rc, row=row.value if row.value >= 0 else None, what=what)
+        c.st.finish()
+        return _results(c)
+
+
+def _get_wf_centroid(g, *args):
+    """one C entry for both loops; ``shift`` is a constant of the call, ``centroid`` may be left out"""
+    what = g.__name__
+    (w_in, shift), (out,) = _split(g, args)
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        shift = check_centroid_shift(what, c.n, shift, c.ft)
+        po = _pulse_out(c, out, None)
+        run(getattr(_lib.lib(), "dsp_wf_centroid_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, shift, po)
+        c.st.finish()
+        return _results(c)
+
+
+def _wf_alignment(g, *args):
+    """one C entry for both loops; ``centroid`` is one value or a value per row, ``shift`` and ``size`` constants of the call; ``w_out`` must
+    be passed: its length is ``size``.  Integer rows take their loop like any rows: (u)int16 the float32 one, (u)int32 the float64 one."""
+    what = g.__name__
+    if len(args) != 5:
+        raise TypeError(f"{what}(w_in, centroid, shift, size, w_out): w_out must be passed, its length is an argument ({len(args)} given)")
+    w_in, centroid, shift, size, out = args
+    if not isinstance(out, (np.ndarray, DeviceArray)):
+        raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+    with device_call(what, w_in) as c:
+        shift, size = check_alignment(what, c.n, shift, size, _out_len(out), c.ft)
+        col = c.col(centroid)
+        if col[0] is None and np.isnan(col[1]):
+            raise DSPFatal("centroid is nan")
+        m = int(size)
+        po = _pulse_out(c, out, m)
+        run(getattr(_lib.lib(), "dsp_wf_alignment_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, *col, shift, size, po, m, m)
+        c.st.finish()
+        return _results(c)
+
+
+def _wf_correction(g, *args):
+    """one C entry for both loops; ``w_corr`` is one constant array, the indices constants of the call; ``w_out`` may be left out"""
+    what = g.__name__
+    (w_in, w_corr, start_idx, stop_idx), (out,) = _split(g, args)
+    with device_call(what, w_in, f64_rows_only=True) as c:
+        if out is not None and not isinstance(out, (np.ndarray, DeviceArray)):
+            raise TypeError("output arguments must be NumPy arrays or DeviceArrays")
+        if out is not None and _out_len(out) != c.n:
+            raise ValueError(f"{what}: the output has the length of the input (len(w_in) = {c.n}, len(w_out) = {_out_len(out)})")
+        if not isinstance(w_corr, DeviceArray) and np.ndim(w_corr.magnitude if hasattr(w_corr, "magnitude") else w_corr) != 1:
+            raise NotImplementedError(f"{what}: w_corr is one constant array of the call on the device, not an array per event")
+        m = int(w_corr.shape[-1]) if isinstance(w_corr, DeviceArray) else int(np.size(w_corr.magnitude if hasattr(w_corr, "magnitude") else w_corr))
+        start, stop = check_correction(what, c.n, m, start_idx, stop_idx)
+        table, m = _constant_array(c, what, "w_corr", w_corr, c.ft)
+        ptr, stride = c.out(out, "n")
+        run(getattr(_lib.lib(), "dsp_wf_correction_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, table.ptr, m, start, stop, ptr, stride)
+        c.st.finish()
+        return _results(c)
+
+
+def _step(g, weight_pos, kernel):
+    """+1 on the middle half of the kernel, -1 on its outer quarters: ``len / 4 <= i < 3 len / 4`` as comparisons of real numbers.  ``weight_pos``
+    is accepted and not used, as in the reference (processors/kernels.py:103-142)."""
+    n = len(kernel)
+    x = np.arange(n)
+    kernel[:] = np.where((x >= n / 4) & (x < 3 * n / 4), 1, -1)
+    return kernel
+
+
+inl_correction = HipGUFunc("inl_correction", "(n),(p)->(n)", ["if->f", "id->d"], _inl_correction,
+                           "w_out[i] = w_in[i] + inl[w_in[i]], a float64 sum rounded once; integer rows; a NaN in inl: NaN rows; a sample outside the "
+                           "table: DSPFatal with the code (reference processors/inl_correction.py:12-61)")
+get_wf_centroid = HipGUFunc("get_wf_centroid", "(n),()->()", ["ff->f", "dd->d"], _get_wf_centroid,
+                            "the rounded middle (half to even) of the first positive and the last negative sample between the row's first minimum "
+                            "and first maximum, plus shift; NaN for a row with a NaN and where the reference defines nothing (reference "
+                            "processors/get_wf_centroid.py:12-69)")
+wf_alignment = HipGUFunc("wf_alignment", "(n),(),(),(),(m)", ["fffff", "ddddd"], _wf_alignment,
+                         "the window of size samples centred on the centroid, padded with w_in[0] near the start of the row, w_in[:size] otherwise; "
+                         "shift and size constants of the call (reference processors/wf_alignment.py:12-87)")
+wf_correction = HipGUFunc("wf_correction", "(n),(m),(),()->(n)", ["ffii->f", "ddii->d"], _wf_correction,
+                          "w_in with w_corr[: stop_idx - start_idx] subtracted on [start_idx, stop_idx); a NaN in the row or in w_corr: NaNs "
+                          "(reference processors/wf_correction.py:10-83)")
+step = HipGUFunc("step", "(),(n)", ["ff", "dd"], _step, "step kernel generator, host, once (reference processors/kernels.py:103-142)")
+
+# Listed here and not in __all__, like the decay-tail fitter's processors: their call records are tests/test_align_plan_cpu.py's.
+ALIGNMENT = ("inl_correction", "get_wf_centroid", "wf_alignment", "wf_correction", "step")
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

@@ -77,6 +77,9 @@ extern "C" {
 #define DSP_E_PSD_LEN 34       /* fft.py:119-120  "Size of psd must be len(w_in)//2+1 = ..." */
 #define DSP_E_RC_CR2_NAN 35    /* rc_cr2.py:93-94          data dependent */
 #define DSP_E_MAF_LEN 36       /* multi_a_filter.py:42-45  "The length of your return array must be smaller than the length of your waveform" */
+#define DSP_E_INL_RANGE 37     /* inl_correction.py:56-61  data dependent: "ADC code {code} out of range for INL array of length {p}" (the host reads
+                                * the row back and names the code) */
+#define DSP_E_ALIGN_CENTROID 38 /* wf_alignment.py:63-64   "centroid is nan"; data dependent for a centroid per event */
 
 /* ---- element types -------------------------------------------------------------------------- */
 #define DSP_F32 0
@@ -363,6 +366,30 @@ typedef struct dsp_scalar_arg {
                                  *   fitted coefficients as stored, [STORE of the logged row,] [STORE of the coefficients,] STORE_SCALAR, STORE_SCALAR
                                  * each with or without a BL_SUBTRACT of the loaded rows, in place, behind their LOAD.  The logged row and, in the
                                  * last shape, the coefficients go to memory only if they are stored */
+#define DSP_OP_INL_CORRECTION 54 /* inl_correction.py:12-61: dst (n samples, another slot than src) <- T(float64(src[i]) + float64(inl[src[i]])), one
+                                 * rounding; src holds DSP_I16, DSP_U16, DSP_I32 or DSP_U32 rows in either loop.  io = a DSP_IO_TAPS binding of the
+                                 * p >= 1 entries of inl in the loop's type.  A NaN anywhere in inl: NaN rows and no range error.  A sample outside
+                                 * [0, p): DSP_E_INL_RANGE with the row, whose output is then unspecified */
+#define DSP_OP_WF_CENTROID 55  /* get_wf_centroid.py:12-69: sreg[dst] <- round(((lo + a + shift) + (lo + b + shift)) / 2) in float64, half to even;
+                                 * lo, hi = the first argmin and argmax of src, a = the first index of [lo, hi) with a sample > 0, b the last with
+                                 * a sample < 0.  sp[0] = shift, a constant (NaN, < 0, > n - 1: the reference's DSPFatal texts).  A row with a NaN:
+                                 * NaN.  hi <= lo, or no positive or no negative sample in [lo, hi) (undefined in the reference): NaN, no error */
+#define DSP_OP_WF_ALIGNMENT 56 /* wf_alignment.py:12-87: dst (m = size samples) <- the window of src around sp[0] = centroid (a constant, or a
+                                 * column of the loop's type); sp[1] = shift, sp[2] = size, constants (the reference's DSPFatal texts; size is
+                                 * integral and equals m, else DSP_ERR_ARG).  The three branches of lines 80-87 in float64, int() truncating.  A
+                                 * float row with a NaN: a NaN row.  A NaN centroid on a row without one: DSP_E_ALIGN_CENTROID (with the row for
+                                 * a column).  Where the two sides of line 85 differ in length and NumPy cannot broadcast them: a NaN row, no error */
+#define DSP_OP_WF_CORRECTION 57 /* wf_correction.py:10-83: dst (n samples) <- src, with src[i] - w_corr[i - start] on [start, stop): one subtraction
+                                 * in the loop's type.  io = a DSP_IO_TAPS binding of w_corr in the loop's type; ip[0] = start_idx, ip[1] = stop_idx
+                                 * (the reference's DSPFatal texts).  A NaN in the row or anywhere in w_corr: a NaN row.
+                                 * The four run on dsp_align_kernel only, a wavefront per row, in a program of exactly
+                                 *   LOAD, INL_CORRECTION, STORE
+                                 *   LOAD, WF_CENTROID, STORE_SCALAR
+                                 *   LOAD, WF_ALIGNMENT, STORE
+                                 *   LOAD, WF_CORRECTION, STORE
+                                 *   LOAD, WF_ALIGNMENT, WF_CORRECTION of the aligned row, [STORE of the aligned row,] STORE of the corrected row
+                                 * where the aligned row goes to memory only if it is stored.  WF_ALIGNMENT also takes DSP_I16 / DSP_U16 (either
+                                 * loop) and DSP_I32 / DSP_U32 (the float64 loop) rows: they hold no NaN, and only the window is read */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -698,6 +725,28 @@ int dsp_poly_fit_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len
 int dsp_poly_residual_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, int32_t exp_rms,
                            const void* poly_pars_dev, int32_t n_pars, int64_t pars_stride, void* mean_out, void* rms_out, void* stream,
                            int64_t* err_row);
+
+/* "(n),(p)->(n)" inl_correction (inl_correction.py:12-61; DSP_OP_INL_CORRECTION).  One entry for both loops, like dsp_sort_rows: in holds
+ * DSP_I16, DSP_U16, DSP_I32 or DSP_U32 rows; inl_dev the inl_len >= 1 entries of the table on the device in the loop's type; out rows of
+ * wf_len values of the loop's type.  DSP_E_INL_RANGE with *err_row for a sample outside [0, inl_len). */
+int dsp_inl_correction_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, const void* inl_dev,
+                            int32_t inl_len, void* out, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),()->()" get_wf_centroid (get_wf_centroid.py:12-69; DSP_OP_WF_CENTROID).  shift is a constant; centroid_out a value of the loop's type
+ * per row. */
+int dsp_wf_centroid_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, double shift,
+                         void* centroid_out, void* stream, int64_t* err_row);
+
+/* "(n),(),(),(),(m)" wf_alignment (wf_alignment.py:12-87; DSP_OP_WF_ALIGNMENT).  centroid_dev: a value of the loop's type per row on the
+ * device, or NULL: centroid for every row.  shift and size are constants, size == out_len.  DSP_E_ALIGN_CENTROID for a NaN centroid on a
+ * row without a NaN (with *err_row for a column). */
+int dsp_wf_alignment_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, const void* centroid_dev,
+                          double centroid, double shift, double size, void* out, int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n),(m),(),()->(n)" wf_correction (wf_correction.py:10-83; DSP_OP_WF_CORRECTION).  corr_dev: the corr_len entries of w_corr on the device
+ * in the loop's type. */
+int dsp_wf_correction_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, const void* corr_dev,
+                           int32_t corr_len, int32_t start_idx, int32_t stop_idx, void* out, int64_t out_stride, void* stream, int64_t* err_row);
 
 /* the float64 loops: float64 (and int32 / uint32) rows, float64 scalars and outputs -- same argument order */
 int dsp_bl_subtract_f64(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, const double* baseline_dev,
