@@ -922,7 +922,9 @@ def _stage_producers(cx: _Stager, v):
     """Stages are made in the order the data flows.  Whatever ``v`` is computed from that runs on a kernel of its own is staged here, by its
     own family, before a reader of ``v`` is: the first such processor among ``v``'s ancestors has none above it, its stage takes it out of
     the program and makes its result rows in memory, where ``ancestors`` ends -- so every one of them is staged once, a producer ahead of
-    its readers, and what is then left between them and ``v`` is work of the interpreter.  (A folded normalisation goes with its layer.)"""
+    its readers, and what is then left between them and ``v`` is work of the interpreter.  (A folded normalisation goes with its layer.)
+    A family asked for a step that begins a fused group -- an ``rc_cr2``, a ``log_check``, a ``poly_fit`` -- stages the launch the step would
+    have joined in the family's own turn, so a reader staged first costs no fusion."""
     while True:
         own = next((a for a in cx.ancestors(v) if a[0] in _OWN_KERNEL and not (a[0] == _NORMALISE and _folded_normalisation(cx, a))), None)
         if own is None:
@@ -1172,6 +1174,18 @@ def _stage_pileup(cx: _Stager, only=None):
         check_rc_cr2(f"{fn} ({key})", src.length, out.length)
         return src, out
 
+    def filter_of(walk):
+        """the ``rc_cr2`` a walk takes into its launch: it reads exactly the filtered row, and none of its operands is computed from that row
+        (a threshold at 3*fwhm of the filtered row's histogram: the filter runs first, on its own)"""
+        src = walk[1][0]
+        flt = cx.producer_of(src) if isinstance(src, Var) else None
+        if flt is None or flt[0] != _RC_CR2 or not cx.has(flt):
+            return None
+        operands = [leaf for a in walk[1][1:5] for leaf in _leaves(a, [])]
+        return None if any(flt is x for leaf in operands for x in cx.ancestors(leaf)) else flt
+
+    if only is not None and only[0] == _RC_CR2:  # (asked for a filter: the launch it would have joined when the family's turn came)
+        only = next((w for w in cx.steps_of(_BI_LEVEL) if filter_of(w) is only), only)
     for st in cx.steps_of(_BI_LEVEL, only):
         fn, args, key = st[0], list(st[1]), st[2]
         src, gate, count, polarity, times = args[0], args[3], args[5], args[6], args[7]
@@ -1184,8 +1198,7 @@ def _stage_pileup(cx: _Stager, only=None):
             raise ValueError(f"{fn} ({key}): gate_time_in is a finite number of samples")
         if _base_of(src) is None:
             raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
-        flt = cx.producer_of(src) if isinstance(src, Var) else None
-        flt = flt if flt is not None and flt[0] == _RC_CR2 and cx.has(flt) else None
+        flt = filter_of(st)
         rows, out = filter_checked(flt) if flt is not None else (src, None)
         pre = _pileup_rows(cx, rows, fn if flt is None else _RC_CR2, key if flt is None else flt[2], st if flt is None else flt)
         for k in (1, 2, 3, 4):
@@ -1292,15 +1305,28 @@ def _stage_tailfit(cx: _Stager, only=None):
     def wanted(v, group):
         return v.name in cx.out_names or any(not any(u is g for g in group) for u in cx.users_of(v))
 
-    def fit_group(ft):
-        """the fit with the log_check it reads, if there is one: (steps, rows, the logged row or None, the coefficients)"""
-        src, pars = fit_checked(ft)
+    def fit_group(ft, checked=True):
+        """the fit with the log_check it reads, if there is one: (steps, rows, the logged row or None, the coefficients); ``checked``
+        false: only looked at, the shapes' errors are left to the step's own turn"""
+        src, pars = fit_checked(ft) if checked else ft[1][:2]
         lg = producer(src, _LOG_CHECK)
         if lg is None:
             return [ft], src, None, pars
-        rows, logged = log_checked(lg)
+        rows, logged = log_checked(lg) if checked else lg[1]
         return [lg, ft], rows, logged, pars
 
+    def fuses(st):
+        """the steps a ``poly_diff`` / ``poly_exp_rms`` would take into its launch, or None: it runs on coefficients in memory"""
+        ft = producer(st[1][1], _POLY_FIT)
+        if ft is None:
+            return None
+        group, rows, logged, _ = fit_group(ft, checked=False)
+        return group if _same_rows(st[1][0], rows) or (logged is not None and st[1][0] is logged) else None
+
+    if only is not None and only[0] in (_LOG_CHECK, _POLY_FIT):  # (asked for a group's head: the launch it would have joined in the family's turn)
+        joined = [st for fn in (_POLY_DIFF, _POLY_EXP_RMS) for st in cx.steps_of(fn) if any(g is only for g in fuses(st) or [])]
+        joined += [ft for ft in cx.steps_of(_POLY_FIT) if producer(ft[1][0], _LOG_CHECK) is only]
+        only = joined[0] if joined else only
     for fn in (_POLY_DIFF, _POLY_EXP_RMS):
         for st in cx.steps_of(fn, only):
             (src, pars, mean, rms), key = st[1], st[2]
