@@ -30,6 +30,8 @@ INTERP_F32_MAX, INTERP_SPLINE_F32_MAX, INTERP_SPLINE_F64_MAX = 16384, 5456, 4096
 # DSP_REFLECT_* (dsp_program.h): the longest staged row of reflected_convolve_wf, len(w_in) + len(kernel) - 1, in the float32 and the float64 loop
 REFLECT_F32_MAX, REFLECT_F64_MAX = 16384, 8192
 DENSE_N_MAX, DENSE_M_MAX = 16384, 256  # DSP_DENSE_*_MAX (dsp_program.h): the inputs and outputs of a dense / classification / normalisation layer
+SVM_CLASSES_MAX = 23  # DSP_SVM_CLASSES_MAX (dsp_program.h): the classes of an svm_predict model, 253 pairs in 16 blocks of decision accumulators (rows: DENSE_N_MAX)
+SVM_MODEL_MAX = 1 << 28  # DSP_SVM_MODEL_MAX (dsp_program.h): support-vector samples (n_sv * n) and coefficients (n_sv * P) of a model, the longest binding
 F32, F64, I16, U16, I32, U32, BOOL, I64, U64 = range(9)
 IO_WF_IN, IO_WF_OUT, IO_SCALAR_IN, IO_SCALAR_OUT, IO_TAPS = range(5)
 ARG_CONST, ARG_INPUT, ARG_REG = range(3)
@@ -39,7 +41,7 @@ ARG_CONST, ARG_INPUT, ARG_REG = range(3)
  OP_SCALAR_CONVERT, OP_SCALAR_DIV, OP_INTERP_TIME_POINT_THRESH, OP_MIN_MAX_NORM, OP_ELEMENTWISE, OP_SCALAR_FUNC, OP_MULTI_EXTREMA, OP_HISTOGRAM,
  OP_HISTOGRAM_STATS, OP_MULTI_TIME_POINT_THRESH, OP_TIME_OVER_THRESHOLD, OP_PSD, OP_FFT, OP_SORT, OP_INTERP_UPSAMPLE, OP_NORMALISE, OP_DENSE, OP_REFLECTED_CONVOLVE, OP_RC_CR2, OP_BI_LEVEL_ZERO_CROSSING,
  OP_PEAK_SNR_THRESHOLD, OP_MULTI_A_FILTER, OP_LOG_CHECK, OP_POLY_FIT, OP_POLY_DIFF, OP_POLY_EXP_RMS,
- OP_INL_CORRECTION, OP_WF_CENTROID, OP_WF_ALIGNMENT, OP_WF_CORRECTION) = range(1, 58)
+ OP_INL_CORRECTION, OP_WF_CENTROID, OP_WF_ALIGNMENT, OP_WF_CORRECTION, OP_SVM_PREDICT) = range(1, 59)
 (FN_ADD, FN_SUB, FN_MUL, FN_DIV, FN_LT, FN_LE, FN_GT, FN_GE, FN_EQ, FN_NE, FN_WHERE, FN_ISNAN, FN_ISFINITE, FN_NEG, FN_COPY, FN_FLOORDIV,
  FN_IADD, FN_ISUB, FN_IMUL, FN_IFLOORDIV, FN_ICAST, FN_LOR, FN_LAND, FN_RINT, FN_FLOOR, FN_CEIL, FN_TRUNC) = range(27)
 
@@ -159,6 +161,7 @@ SIG = {
         "dsp_sort_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i64, vp, pi64],
         "dsp_interp_upsample_rows": [vp, C.c_int, i64, i32, i64, C.c_int, i32, vp, i32, i64, vp, pi64],
         "dsp_dense_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, vp, i32, vp, i32, i64, vp, pi64],
+        "dsp_svm_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, vp, vp, vp, vp, i32, i32, i32, C.c_double, vp, vp, i64, vp, pi64],
         "dsp_normalisation_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, vp, vp, i64, vp, pi64],
         "dsp_reflected_convolve_rows": [vp, C.c_int, i64, i32, i64, C.c_int, vp, i32, vp, i64, vp, pi64],
         "dsp_rc_cr2_rows": [vp, C.c_int, i64, i32, i64, C.c_int, C.c_double, vp, i64, vp, pi64],

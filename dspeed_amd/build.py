@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdspeed_hip.so")
 LIB_DIAG = os.path.join(HERE, "libdspeed_hip_diag.so")
-SOURCES = ["dsp_vm.hip", "dsp_energy.hip", "dsp_energy_h.hip", "dsp_fit.hip", "dsp_rows.hip", "dsp_current.hip", "dsp_scalar.hip", "dsp_reduce.hip", "dsp_extrema.hip", "dsp_hist.hip", "dsp_thresh.hip", "dsp_spectrum.hip", "dsp_sort.hip", "dsp_interp.hip", "dsp_dense.hip", "dsp_reflect.hip", "dsp_pileup.hip", "dsp_tailfit.hip", "dsp_align.hip", "dsp_pulses.hip", "dsp_pz.hip", "dsp_fir_mfma.hip", "dsp_fir_f16.hip", "dsp_fir_runs.hip", "dsp_plan.cpp", "dsp_host.cpp", "dsp_gufuncs.cpp"]
+SOURCES = ["dsp_vm.hip", "dsp_energy.hip", "dsp_energy_h.hip", "dsp_fit.hip", "dsp_rows.hip", "dsp_current.hip", "dsp_scalar.hip", "dsp_reduce.hip", "dsp_extrema.hip", "dsp_hist.hip", "dsp_thresh.hip", "dsp_spectrum.hip", "dsp_sort.hip", "dsp_interp.hip", "dsp_dense.hip", "dsp_reflect.hip", "dsp_pileup.hip", "dsp_tailfit.hip", "dsp_align.hip", "dsp_pulses.hip", "dsp_svm.hip", "dsp_pz.hip", "dsp_fir_mfma.hip", "dsp_fir_f16.hip", "dsp_fir_runs.hip", "dsp_plan.cpp", "dsp_host.cpp", "dsp_gufuncs.cpp"]
 DEPS = SOURCES + ["dsp_program.h", "dsp_kernels.h", "dsp_launch.h", "dsp_plan.h", "dsp_gufuncs.h", "dsp_wave.h", "dsp_reduce_tail.h", "dsp_row_stream.h", "dsp_lane_tiles.h", "dsp_spectrum_tables.h", os.path.join("..", "..", "include", "dspeed_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall",
          "-Wno-unused-function"]

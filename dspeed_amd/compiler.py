@@ -26,6 +26,7 @@ from . import _lib
 from .chain import Program, Scalar
 from .device import dtype_code
 from .errors import DSPFatal, ProcessingChainError
+from .gufunc import loop_suffix
 from .language import (Char, Grid, Quantity, SExpr, Var, View, _Builder, _GENERATORS, _MODULES, _NUMPY_BINARY, module_accepted, _SIGS, _column, _grid_of, _is_int_dtype,
                        _is_scalar, _is_wf, _resolve, _roles, _time_unit_ns)
 
@@ -44,7 +45,8 @@ _ALIGN = (_INL, _WF_CENTROID, _WF_ALIGN, _WF_CORR)
 _NORMALISE = "normalisation_layer"
 _DENSE_LAYERS = ("dense_layer_no_bias", "dense_layer_with_bias", "classification_layer_no_bias", "classification_layer_with_bias")
 _ML = (_NORMALISE,) + _DENSE_LAYERS
-_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL, _PEAK_SNR, _MULTI_A) + _TAILFIT + _ALIGN + _ML  # processors that run as stages ahead of the program, on kernels of their own
+_SVM = "svm_predict"
+_OWN_KERNEL = (_MULTI_EXTREMA, _HISTOGRAM, _HISTOGRAM_STATS, _MULTI_TPT, _TIME_OVER, _PSD, _SORT, _INTERP, _REFLECT, _RC_CR2, _BI_LEVEL, _PEAK_SNR, _MULTI_A) + _TAILFIT + _ALIGN + _ML + (_SVM,)  # processors that run as stages ahead of the program, on kernels of their own
 _SAME_DIM = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "moving_window_multi", _SORT, _NORMALISE, _REFLECT, _RC_CR2, _LOG_CHECK, _INL, _WF_CORR)
 # processors whose result may take the place of their source waveform
 _IN_PLACE = ("bl_subtract", "numpy_subtract", "numpy_add", "min_max_norm", "pole_zero", "double_pole_zero")
@@ -126,7 +128,7 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         # dspeed.processors.multi_a_filter, as the SiPM configs write them; under the package's string they stay refused, in these words:
         # tests/test_histogram_plan_cpu.py and the recorded translations hold that -- as they hold gaussian_filter1d's refusal)
         raise NotImplementedError(f"processor '{function}' is not implemented on the device path")
-    if "init_args" in node and function != _POLY_FIT:
+    if "init_args" in node and function not in (_POLY_FIT, _SVM):
         raise NotImplementedError(f"{function} ({key}): init_args builds a processor from a factory; on the device path only poly_fit is one")
     roles = _SIGS[function]
     if len(args) != len(roles):
@@ -171,6 +173,11 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
         if function == _PEAK_SNR and isinstance(args[5], Var):
             args[5].out_dtype = np.dtype(np.uint32)
     inverse = _poly_fit_inverse(b, node, args, key) if function == _POLY_FIT else None
+    svm = _svm_model(b, node, args, key) if function == _SVM else None
+    if function == _SVM and svm is None:  # svm_file = 0: the label is the constant NaN, as the reference's null processor leaves it
+        loop = np.float64 if loop_suffix(args[0].dtype if args[0].dtype is not None else np.float32) == "f64" else np.float32  # (the type the staged label would have)
+        b.vars[args[1].name] = Var(args[1].name, "const", const=loop(np.nan))
+        return
     if function == _MULTI_TPT:
         # its thresholds are one constant list, or a list per event read from rows in memory; its times are sample indices of the input:
         # with a time unit they are coordinates on its grid, written in that unit like the peak finder's lists
@@ -192,6 +199,8 @@ def _add_step(b: _Builder, key, node, new_vars, proc_strings):
     _, args = _resolve(b, roles, args, same_dim_out=function in _SAME_DIM)
     if inverse is not None:
         args = list(args) + [inverse]  # (behind the arguments the roles name: a constant of the step)
+    if svm is not None:
+        args = list(args) + svm  # (likewise: the model's five arrays, gamma and the kernel function)
     b.steps.append((function, args, key))
     proc_strings.append(f"{function}({', '.join(str(a.name if isinstance(a, (Var, SExpr)) else a) for a in args)})")
 
@@ -234,6 +243,41 @@ def _poly_fit_inverse(b: _Builder, node, args, key):
     except np.linalg.LinAlgError as e:  # (length <= deg: the reference's factory raises there too)
         raise ProcessingChainError(f"{what}: the matrix of power sums over range({length}) cannot be inverted for deg = {deg} ({e})") from None
     return Var(f"inv#{out.name}", "taps", (deg + 1) ** 2, np.float64, const=np.ascontiguousarray(inv, dtype=np.float64))
+
+
+def _svm_model(b: _Builder, node, args, key):
+    """``svm_predict`` is a factory in the reference: ``init_args`` -- the file of the pickled SVC, a character constant or a ``db.`` value, or 0
+    -- builds the gufunc (processing_chain.py:2723-2773).  The model is read here, once, at chain build (``processors.load_svm_model``): its
+    arrays travel as float64 constants behind the step's arguments, with gamma and the kernel function: returned."""
+    from .processors import SVM_KERNELS, check_svm, load_svm_model, svm_device_arrays
+
+    what = f"{_SVM} ({key})"
+    init = node.get("init_args")
+    if not isinstance(init, (list, tuple)) or len(init) != 1:
+        raise ProcessingChainError(f"{what}: init_args holds the file of the fitted SVC (or 0), as the factory takes it")
+    src, out = args
+    if not _is_wf(src):
+        raise ProcessingChainError(f"{what}: '{src}' is not a waveform")
+    if not isinstance(out, Var):
+        raise ProcessingChainError(f"{what}: name the label")
+    file = init[0]
+    if isinstance(file, str):
+        text = file.strip()
+        file = text[1:-1] if len(text) >= 2 and text[0] == text[-1] and text[0] in "'\"" else (0 if text == "0" else text)
+    if _is_number(file) and file == 0:
+        return None  # (the null processor: NaN for every row, nothing launched)
+    if isinstance(file, (Var, SExpr, View)) or _is_number(file):
+        raise ProcessingChainError(f"{what}: init_args holds the file of the fitted SVC (or 0), as the factory takes it")
+    model = load_svm_model(file)
+    n_sv, n = model["support_vectors"].shape
+    check_svm(what, max(n, src.length), model["classes"].size, n_sv)
+    if src.length != n:
+        raise ProcessingChainError(f"{what}: '{src.name if hasattr(src, 'name') else src}' holds {src.length} samples, the model's support vectors {n}")
+    consts = []
+    for name, arr in zip(("support_vectors", "sv_norms", "coefficients", "intercepts", "classes"), svm_device_arrays(model)):
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        consts.append(Var(f"{name}#{out.name}", "taps", int(arr.size), np.float64, const=arr))
+    return consts + [float(model["gamma"]), SVM_KERNELS.index(model["kernel"])]
 
 
 class _PerEventInteger(Exception):
@@ -1492,10 +1536,23 @@ def _stage_ml_layers(cx: _Stager, only=None):
             cx.stage(group, [], what, wfs=[out], rows_first=True, drop=[st])
 
 
+def _stage_svm(cx: _Stager, only=None):
+    """``svm_predict`` runs on dsp_svm.hip and nowhere else, on rows in HBM: a mandatory stage, like a classification layer's.  Its rows are a
+    chain input, a stage's waveform (the normalisation before it), or a waveform the program computes, written to HBM first; its label is a
+    per-event value of the later entries."""
+    for st in cx.steps_of(_SVM, only):
+        fn, args, key = st
+        src, out = args[0], args[1]
+        if _base_of(src) is None:
+            raise ProcessingChainError(f"{fn} ({key}): '{src}' is not a waveform")
+        _rows_in_memory(cx, src, fn, key)
+        cx.stage([st], [out], f"{fn} {key} on rows")
+
+
 #: the family that stages each processor with a kernel of its own (``_stage_producers`` asks it for one step)
 _FAMILY_OF = {_REFLECT: _stage_reflected_convolve, _RC_CR2: _stage_pileup, _BI_LEVEL: _stage_pileup, _PEAK_SNR: _stage_pulses, _MULTI_A: _stage_pulses, **dict.fromkeys(_TAILFIT, _stage_tailfit), **dict.fromkeys(_ALIGN, _stage_align), _HISTOGRAM: _stage_histogram, _HISTOGRAM_STATS: _stage_histogram,
               _MULTI_EXTREMA: _stage_multi_extrema, _MULTI_TPT: _stage_thresholds, _TIME_OVER: _stage_thresholds, _PSD: _stage_spectrum,
-              _SORT: _stage_sort, _INTERP: _stage_interp_upsampler, **dict.fromkeys(_ML, _stage_ml_layers)}
+              _SORT: _stage_sort, _INTERP: _stage_interp_upsampler, **dict.fromkeys(_ML, _stage_ml_layers), _SVM: _stage_svm}
 
 
 def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
@@ -1531,6 +1588,7 @@ def _extract_stages(b: _Builder, steps, out_pars, n_rows, ft):
     _stage_sort(cx)
     _stage_interp_upsampler(cx)
     _stage_ml_layers(cx)
+    _stage_svm(cx)
     # what the stages' results replaced is not computed any more: producers of staged variables, and whatever only fed them
     staged = {id(v) for v in b.vars.values() if isinstance(v, Var) and v.ext_key is not None and v.aux_io is None}
     cx.steps = _live_steps(b, [x for x in cx.steps if not any(id(a) in staged for a in _outputs_of(x))], out_pars)
@@ -2305,6 +2363,20 @@ class _Emitter:
             self.p.add_op(_lib.OP_DENSE, dst=out.slot, src=src.slot, io=io_w, ip=(act, io_b, src.length, m))
         self.release(src, si)
 
+    def svm_predict(self, si, fn, args, what):
+        """the whole program of the stage: LOAD, SVM_PREDICT; the store of the label follows.  The model is float64 bindings in both loops"""
+        src = self.ensure_loaded(args[0], si)
+        ios = []
+        for v in args[2:7]:
+            if v.io is None:
+                v.io = self.p.add_io(f"taps:{v.name}", _lib.IO_TAPS, np.float64, v.length, 0, 0)
+                self.consts[f"taps:{v.name}"] = np.ascontiguousarray(v.const, dtype=np.float64).reshape(-1)
+            ios.append(v.io)
+        o = self.out_scalar(args[1])
+        self.p.add_op(_lib.OP_SVM_PREDICT, dst=o.sreg, src=src.slot, io=ios[0], ip=tuple(ios[1:]),
+                      sp=(Scalar.const(float(args[7])), Scalar.const(float(args[8])), Scalar.const(-1.0)))
+        self.release(src, si)
+
     def copy_slice(self, si, fn, args, what):
         src = self.ensure_loaded(args[0], si)
         dst = args[3]
@@ -2488,7 +2560,7 @@ _EMIT = {**dict.fromkeys(_IN_PLACE, _Emitter.in_place), **dict.fromkeys(_TRAP_OP
          _BI_LEVEL: _Emitter.bi_level_zero_crossing, _PEAK_SNR: _Emitter.peak_snr_threshold, _MULTI_A: _Emitter.multi_a_filter,
          _INL: _Emitter.inl_correction, _WF_CENTROID: _Emitter.get_wf_centroid, _WF_ALIGN: _Emitter.wf_alignment, _WF_CORR: _Emitter.wf_correction,
          _LOG_CHECK: _Emitter.log_check, _POLY_FIT: _Emitter.poly_fit, _POLY_DIFF: _Emitter.poly_residual, _POLY_EXP_RMS: _Emitter.poly_residual,
-         _NORMALISE: _Emitter.normalisation_layer, **dict.fromkeys(_DENSE_LAYERS, _Emitter.dense_layer)}
+         _NORMALISE: _Emitter.normalisation_layer, **dict.fromkeys(_DENSE_LAYERS, _Emitter.dense_layer), _SVM: _Emitter.svm_predict}
 
 
 def _emit_outputs(e: _Emitter, out_pars, island_out, n_rows, stage_mode):

@@ -456,6 +456,36 @@ int dsp_dense_rows(ROWS, int compute_dtype, const void* weights_dev, const void*
         return DSP_OK;
     });
 }
+// svm_predict: one entry for both loops; the model's five arrays are bound like a filter's taps, float64 in both loops; the decisions are an output
+// of the op's own (float64 too), bound only where the caller asks for them
+int dsp_svm_rows(ROWS, int compute_dtype, const void* sv_dev, const void* sv_norm_dev, const void* coef_dev, const void* intercept_dev,
+                 const void* classes_dev, int32_t n_sv, int32_t n_classes, int32_t kernel_kind, double gamma, void* label_out, void* dec_out,
+                 int64_t dec_stride, TAIL) {
+    if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "svm_predict: compute_dtype is DSP_F32 or DSP_F64");
+    if (!sv_dev || !sv_norm_dev || !coef_dev || !intercept_dev || !classes_dev || !label_out)
+        return dsp_fail(DSP_ERR_ARG, "svm_predict: the model's five arrays lie on the device as float64; label_out holds a value per row");
+    return tiny_chain(compute_dtype, n_wf, TAIL_ARGS, [&](Mini& m) -> int {
+        if (wf_len > DSP_DENSE_N_MAX || n_classes > DSP_SVM_CLASSES_MAX)  // (ahead of the products below)
+            return dsp_fail(DSP_ERR_UNSUPPORTED, "svm_predict: " DSP_SVM_LIMITS_TEXT " (n = %d, %d classes given)", DSP_DENSE_N_MAX, DSP_SVM_CLASSES_MAX, wf_len, n_classes);
+        if (n_classes < 2) return dsp_fail(DSP_ERR_ARG, "svm_predict: a model has at least 2 classes (%d given)", n_classes);
+        const int32_t pairs = n_classes * (n_classes - 1) / 2;
+        if (n_sv < 1 || wf_len < 1 || (int64_t)n_sv * wf_len > DSP_SVM_MODEL_MAX || (int64_t)n_sv * pairs > DSP_SVM_MODEL_MAX)
+            return dsp_fail(DSP_ERR_UNSUPPORTED, "svm_predict: " DSP_SVM_MODEL_TEXT, DSP_SVM_MODEL_MAX, n_sv, wf_len, pairs);
+        if (kernel_kind != 0 && kernel_kind != 1) return dsp_fail(DSP_ERR_ARG, "svm_predict: kernel_kind is 0 (rbf) or 1 (linear)");
+        if (dec_out && dec_stride < pairs) return dsp_fail(DSP_ERR_ARG, "svm_predict: rows of %d decisions lie at least as many values apart (%lld given)", pairs, (long long)dec_stride);
+        const int s_in = m.load(IN);
+        const int io_sv = m.add_io(DSP_IO_TAPS, DSP_F64, n_sv * wf_len, 0, sv_dev);
+        const int io_norm = m.add_io(DSP_IO_TAPS, DSP_F64, n_sv, 0, sv_norm_dev);
+        const int io_coef = m.add_io(DSP_IO_TAPS, DSP_F64, n_sv * pairs, 0, coef_dev);
+        const int io_icpt = m.add_io(DSP_IO_TAPS, DSP_F64, pairs, 0, intercept_dev);
+        const int io_cls = m.add_io(DSP_IO_TAPS, DSP_F64, n_classes, 0, classes_dev);
+        const int io_dec = dec_out ? m.add_io(DSP_IO_WF_OUT, DSP_F64, pairs, dec_stride, dec_out) : -1;
+        m.n_sregs = 1;
+        m.op(DSP_OP_SVM_PREDICT, 0, s_in, io_sv, {io_norm, io_coef, io_icpt, io_cls}, {{nullptr, gamma}, {nullptr, (double)kernel_kind}, {nullptr, (double)io_dec}});
+        m.store_scalar(0, label_out, compute_dtype);
+        return DSP_OK;
+    });
+}
 // normalisation_layer: means and variances are bound like a filter's taps; in place in its slot
 int dsp_normalisation_rows(ROWS, int compute_dtype, const void* means_dev, const void* variances_dev, void* out, int64_t out_stride, TAIL) {
     if (compute_dtype != DSP_F32 && compute_dtype != DSP_F64) return dsp_fail(DSP_ERR_ARG, "normalisation_layer: compute_dtype is DSP_F32 or DSP_F64");

@@ -428,6 +428,9 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     if (!rc)
         rc = raise_lds(ch->kernel_only == DSP_ROUTE_REFLECT, dsp_reflect::lds_bytes(ch->reflect.len, ch->reflect.n_taps, esz), 64 * 1024, "reflect kernel, %d",
                        [&](int n) { return dsp_internal_set_reflect_lds(ch->reflect_src.dtype, n); });
+    if (!rc)
+        rc = raise_lds(ch->kernel_only == DSP_ROUTE_SVM, dsp_svm::lds_bytes(ch->svm.len, ch->svm.n_pairs), 64 * 1024, "svm kernel, %d",
+                       [&](int) { return dsp_internal_set_svm_lds(ch->svm_src.dtype, ch->svm.f64, dsp_svm::LDS_MAX); });  // (the largest any chain needs: never lowered under another chain's launch)
     if (rc) return rc;
     *out = ch.release();
     return DSP_OK;
@@ -673,6 +676,19 @@ static int launch_dense(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void*
     A.variances = io_at(ch, io_ptrs, ch->eio_var);
     A.out = io_at(ch, io_ptrs, ch->eio_out);
     return launch_on_rows(ch, n_wf, stream, A, ch->dense_src, dsp_internal_launch_dense, "dense kernel launch");
+}
+
+static int launch_svm(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    SvmArgs A = ch->svm;
+    A.wf = io_ptrs[ch->svm_src.io];
+    A.sv = (const double*)io_at(ch, io_ptrs, ch->vio_sv);
+    A.sv_norm = (const double*)io_at(ch, io_ptrs, ch->vio_norm);
+    A.coef = (const double*)io_at(ch, io_ptrs, ch->vio_coef);
+    A.intercept = (const double*)io_at(ch, io_ptrs, ch->vio_icpt);
+    A.classes = (const double*)io_at(ch, io_ptrs, ch->vio_cls);
+    A.label = io_at(ch, io_ptrs, ch->vio_label);
+    A.dec = (double*)io_at(ch, io_ptrs, ch->vio_dec);
+    return launch_on_rows(ch, n_wf, stream, A, ch->svm_src, dsp_internal_launch_svm, "svm kernel launch");
 }
 
 static int launch_reflect(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
@@ -935,6 +951,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (kernel_only_applies(ch, DSP_ROUTE_PULSES)) return launch_pulses(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_TAILFIT)) return launch_tailfit(ch, io_ptrs, n_wf, stream);
     if (kernel_only_applies(ch, DSP_ROUTE_ALIGN)) return launch_align(ch, io_ptrs, n_wf, stream);
+    if (kernel_only_applies(ch, DSP_ROUTE_SVM)) return launch_svm(ch, io_ptrs, n_wf, stream);
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -1062,6 +1079,9 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
                 lds = dsp_dense::lds_bytes(ch->dense.m, ch->f64 ? 8 : 4) / 4, wpb = 4, b = (int)dsp_dense::tiles(n_wf);
             else
                 lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4);
+            break;
+        case DSP_ROUTE_SVM:  // the dense kernel's tile of 64 rows per workgroup
+            lds = dsp_svm::lds_bytes(ch->svm.len, ch->svm.n_pairs) / 4, wpb = 4, b = (int)dsp_svm::tiles(n_wf);
             break;
         case DSP_ROUTE_EXTREMA:
         case DSP_ROUTE_THRESH:

@@ -22,6 +22,7 @@ enum dsp_route {
     DSP_ROUTE_PULSES,   // (nor this: PEAK_SNR_THRESHOLD and MULTI_A_FILTER)
     DSP_ROUTE_TAILFIT,  // (nor this: LOG_CHECK, POLY_FIT, POLY_DIFF and POLY_EXP_RMS)
     DSP_ROUTE_ALIGN,    // (nor this: INL_CORRECTION, WF_CENTROID, WF_ALIGNMENT and WF_CORRECTION)
+    DSP_ROUTE_SVM,      // (nor this: SVM_PREDICT)
     DSP_ROUTE_SCALAR, DSP_ROUTE_PZ_ROWS, DSP_ROUTE_REDUCE, DSP_ROUTE_FIR_RUNS, DSP_ROUTE_CURRENT, DSP_ROUTE_FIR_F16, DSP_ROUTE_FIR_STORE,
     DSP_ROUTE_FIR_MFMA, DSP_ROUTE_ROWS, DSP_ROUTE_ENERGY_RR, DSP_ROUTE_ENERGY, DSP_ROUTE_VM
 };
@@ -39,6 +40,7 @@ inline constexpr const char* dsp_route_kernel_names[] = {
     "dsp_pulses_kernel",
     "dsp_tailfit_kernel",
     "dsp_align_kernel",
+    "dsp_svm_kernel",
     "dsp_scalar_kernel",    "dsp_pz_rows_kernel",  "dsp_reduce_kernel", "dsp_fir_runs_kernel",  "dsp_current_kernel", "dsp_fir_f16_kernel",
     "dsp_fir_store_kernel", "dsp_fir_mfma_kernel", "dsp_rows_kernel",   "dsp_energy_rr_kernel", "dsp_energy_kernel",  "dsp_vm_kernel<float>"};
 static_assert(sizeof dsp_route_kernel_names / sizeof dsp_route_kernel_names[0] == DSP_ROUTE_VM + 1, "a name per route");
@@ -216,6 +218,45 @@ constexpr int built_blocks(int m) { return blocks(m) <= 1 ? 1 : blocks(m) <= 4 ?
 constexpr int64_t tiles(int64_t n_wf) { return (n_wf + TILE_ROWS - 1) / TILE_ROWS; }
 static_assert(lds_bytes(M_MAX, 4) == 87040 && lds_bytes(M_MAX, 8) == 87040 && lds_bytes(1, 4) < 64 * 1024, "LDS of the widest layer: raised past 64 KiB (dsp_internal_set_dense_lds)");
 }  // namespace dsp_dense
+
+namespace dsp_svm {  // dsp_svm.hip: svm_predict (svm.py:13-71), an RBF or linear one-vs-one SVC: two chained float64 products on the matrix cores
+// ---- geometry.  dsp_dense's tile of rows: a workgroup of WAVES wavefronts takes TILE_ROWS rows, a wavefront WAVE_ROWS.  The support vectors
+// come SV_BLOCK at a time, SV_TILES accumulator tiles of v_mfma_f64_16x16x4 a wavefront, transposed: G^T = SV . X^T, so that a tile's
+// register r (support vectors 4 r .. 4 r + 3 of the tile, a row per lane & 15) is, once K is formed from it, the B operand of
+// DEC^T += D^T . K^T as it stands.  DEC^T lives in pair_blocks(P) accumulator tiles of BLOCK pairs across all support-vector blocks.
+//   x   [TILE_ROWS][x_pitch(n)]   the rows as float64: whole (n <= RESIDENT_MAX, staged once) or a chunk of KC samples, staged again per block
+//   sv  [SV_BLOCK][SV_PITCH]      the support vectors' chunk, zero beyond n and beyond n_sv
+//   dec [TILE_ROWS][dec_pitch(P)] behind the last block, over the same bytes: a row's decisions, for its vote
+// Pitches: dsp_dense's -- the lanes of an operand read differ in row (l & 15) and in k (l >> 4).
+using dsp_dense::BLOCK;
+using dsp_dense::DEPTH;
+using dsp_dense::N_MAX;
+using dsp_dense::TILE_ROWS;
+using dsp_dense::tiles;
+using dsp_dense::WAVE_ROWS;
+using dsp_dense::WAVES;
+constexpr int CLASSES_MAX = 23, P_MAX = 256, PAIR_BLOCKS_MAX = P_MAX / BLOCK;  // (DSP_SVM_CLASSES_MAX of dsp_program.h)
+constexpr int KC = 32, SV_TILES = 4, SV_BLOCK = SV_TILES * BLOCK, SV_PITCH = KC + 2;
+constexpr int RESIDENT_MAX = 256;
+constexpr int pairs(int k) { return k * (k - 1) / 2; }
+constexpr int pair(int i, int j, int k) { return i * (2 * k - i - 1) / 2 + (j - i - 1); }  // (i < j) in the order (0,1), (0,2) .. (k-2,k-1)
+constexpr bool resident(int n) { return n <= RESIDENT_MAX; }
+constexpr int x_cols(int n) { return resident(n) ? (n + KC - 1) / KC * KC : KC; }
+constexpr int x_pitch(int n) { return x_cols(n) + 2; }
+constexpr int pair_blocks(int P) { return (P + BLOCK - 1) / BLOCK; }
+// the kernel is built for 1, 4 or PAIR_BLOCKS_MAX blocks of pairs a wavefront: the smallest that holds P
+constexpr int built_blocks(int P) { return pair_blocks(P) <= 1 ? 1 : pair_blocks(P) <= 4 ? 4 : PAIR_BLOCKS_MAX; }
+constexpr int dec_pitch(int P) { return pair_blocks(P) * BLOCK + 1; }
+constexpr int stage_bytes(int n) { return (TILE_ROWS * x_pitch(n) + SV_BLOCK * SV_PITCH) * 8; }
+constexpr int vote_bytes(int P) { return TILE_ROWS * dec_pitch(P) * 8; }
+constexpr int lds_bytes(int n, int P) { return stage_bytes(n) > vote_bytes(P) ? stage_bytes(n) : vote_bytes(P); }
+// what the kernels' dynamic-LDS limit is raised to, once, whatever a chain needs: chains of one row type share a kernel, and a smaller
+// value set for a later chain would undercut an earlier one's launches
+constexpr int LDS_MAX = lds_bytes(RESIDENT_MAX, P_MAX);
+static_assert(LDS_MAX >= lds_bytes(N_MAX, P_MAX) && LDS_MAX >= lds_bytes(RESIDENT_MAX, 1), "the largest of both areas");
+static_assert(pairs(CLASSES_MAX) <= P_MAX && pairs(CLASSES_MAX + 1) > P_MAX && pair(0, 1, 4) == 0 && pair(1, 2, 4) == 3 && pair(2, 3, 4) == 5, "the pairs of the most classes fill the accumulators");
+static_assert(lds_bytes(RESIDENT_MAX, P_MAX) == 149504 && lds_bytes(N_MAX, 1) == 34816 && lds_bytes(N_MAX, P_MAX) == 131584, "LDS of the longest resident rows: raised past 64 KiB (dsp_internal_set_svm_lds)");
+}  // namespace dsp_svm
 
 namespace dsp_reflect {  // dsp_reflect.hip: reflected_convolve_wf (convolutions.py:122-182), a FIR of m taps over a row of n samples with mirrored edges
 // ---- the rule.  np.convolve(np.pad(w, int(m/2) + 1, "reflect"), kernel, "same") cut back to n samples is, for 1 <= m <= n,

@@ -61,6 +61,9 @@ int dsp_internal_launch_pulses(const PulsesArgs* A, int64_t n_wf, int dtype, int
 int dsp_internal_launch_tailfit(const TailfitArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
 // dsp_align.hip (dtype: the rows'; the loop is A->f64; vec as above, for the streaming loads -- the stores' is A->out_vec; nothing in LDS)
 int dsp_internal_launch_align(const AlignArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+// dsp_svm.hip (dtype: the rows'; the loop is A->f64; vec as above; LDS: dsp_svm::lds_bytes, past 64 KiB for resident rows of more than 64 samples and for more than 112 pairs)
+int dsp_internal_launch_svm(const SvmArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+int dsp_internal_set_svm_lds(int dtype, int f64, int lds_bytes);  // (called with dsp_svm::LDS_MAX: one value for every chain of a row type)
 // dsp_scalar.hip (type: 0 float32, 1 float64, 2 int64 registers)
 int dsp_internal_launch_scalar(const DevProgram* dev_prog, const IoPtrs* ptrs, int64_t n_wf, int n_sregs, int type, hipStream_t stream);
 int dsp_internal_set_scalar_lds(int lds_bytes);

@@ -121,6 +121,7 @@ static bool match_pileup_shape(const PlanCtx& c, const char** why);
 static bool match_pulses_shape(const PlanCtx& c, const char** why);
 static bool match_tailfit_shape(const PlanCtx& c, const char** why);
 static bool match_align_shape(const PlanCtx& c, const char** why);
+static bool match_svm_shape(const PlanCtx& c, const char** why);
 static const KernelOnlyRoute kernel_only_routes[] = {
     {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
      "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
@@ -144,6 +145,7 @@ static const KernelOnlyRoute kernel_only_routes[] = {
      "DSP_OP_LOG_CHECK / DSP_OP_POLY_FIT / DSP_OP_POLY_DIFF / DSP_OP_POLY_EXP_RMS (log_check, poly_fit, poly_diff, poly_exp_rms) run on dsp_tailfit_kernel only"},
     {DSP_ROUTE_ALIGN, {DSP_OP_INL_CORRECTION, DSP_OP_WF_CENTROID, DSP_OP_WF_ALIGNMENT, DSP_OP_WF_CORRECTION}, match_align_shape,
      "DSP_OP_INL_CORRECTION / DSP_OP_WF_CENTROID / DSP_OP_WF_ALIGNMENT / DSP_OP_WF_CORRECTION (inl_correction, get_wf_centroid, wf_alignment, wf_correction) run on dsp_align_kernel only"},
+    {DSP_ROUTE_SVM, {DSP_OP_SVM_PREDICT, DSP_OP_SVM_PREDICT}, match_svm_shape, "DSP_OP_SVM_PREDICT (svm_predict) runs on dsp_svm_kernel only"},
 };
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
@@ -735,6 +737,41 @@ static bool match_dense_shape(const PlanCtx& c, const char** why) {
     }
     ch->eio_out = st.io;
     A.out_stride = o.row_stride;
+    return true;
+}
+
+// Is the program the support-vector classifier's (dsp_svm.hip)?
+//   LOAD s;  SVM_PREDICT of s into a scalar register;  STORE_SCALAR of it
+// The model's bindings and the limits are lower_op's business (every program that holds the op passes there first).  Why not, otherwise: `why`.
+static bool match_svm_shape(const PlanCtx& c, const char** why) {
+    ChainPlan* ch = c.ch;
+    const dsp_op* ops = c.ops;
+    *why = "the program must be exactly LOAD, SVM_PREDICT, STORE_SCALAR";
+    if (c.n_ops != 3 || c.n_slots != 1 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_SVM_PREDICT || ops[2].opcode != DSP_OP_STORE_SCALAR) return false;
+    const dsp_op &ld = ops[0], &op = ops[1], &st = ops[2];
+    SvmArgs& A = ch->svm;
+    memset(&A, 0, sizeof A);
+    if (op.src != ld.dst || !bind_rows(c, ld, 1u << DSP_F32, ROWS_F64 | 1u << DSP_F32, A, ch->svm_src, why,
+                                       "the float32 loop takes float32 rows, the float64 loop float32 or float64 rows"))
+        return false;
+    *why = "the label is stored once, in the loop's type";
+    const dsp_io_desc& o = c.io[st.io];
+    if (st.ip[0] != op.dst || o.dtype != c.compute_dtype) return false;
+    A.n_sv = c.io[op.ip[0]].len;
+    A.n_classes = c.io[op.ip[3]].len;
+    A.n_pairs = c.io[op.ip[2]].len;
+    A.linear = op.sp[1].value != 0.0 ? 1 : 0;
+    A.f64 = c.f64 ? 1 : 0;
+    A.gamma = op.sp[0].value;
+    A.label_stride = o.row_stride;
+    ch->vio_sv = op.io;
+    ch->vio_norm = op.ip[0];
+    ch->vio_coef = op.ip[1];
+    ch->vio_icpt = op.ip[2];
+    ch->vio_cls = op.ip[3];
+    ch->vio_label = st.io;
+    ch->vio_dec = (int)op.sp[2].value;
+    if (ch->vio_dec >= 0) A.dec_stride = c.io[ch->vio_dec].row_stride;
     return true;
 }
 
@@ -1645,7 +1682,8 @@ static int op_slots(const dsp_op& o, int out[4]) {
         case DSP_OP_WF_ALIGNMENT:
         case DSP_OP_WF_CORRECTION:
         case DSP_OP_CONVOLVE: out[0] = o.src; out[1] = o.dst; return 2;
-        case DSP_OP_WF_CENTROID: out[0] = o.src; return 1;
+        case DSP_OP_WF_CENTROID:
+        case DSP_OP_SVM_PREDICT: out[0] = o.src; return 1;
         case DSP_OP_POLY_DIFF:
         case DSP_OP_POLY_EXP_RMS: out[0] = o.src; out[1] = o.ip[0]; return 2;
         case DSP_OP_NORMALISE: out[0] = o.src; return 1;
@@ -1841,7 +1879,7 @@ static int pack_lds(PlanCtx& c) {
     cursor += DSP_SCRATCH_ELEMS;
     P.lds_elems_per_wave = cursor;
     ch->lds_bytes_per_wave = cursor * c.esz;
-    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows; PEAK_SNR_THRESHOLD, MULTI_A_FILTER: nothing in LDS; LOG_CHECK, POLY_FIT, POLY_DIFF, POLY_EXP_RMS: a tile of 64 rows; INL_CORRECTION, WF_CENTROID, WF_ALIGNMENT, WF_CORRECTION: nothing in LDS)
+    if (ch->lds_bytes_per_wave > LDS_BYTES_PER_CU && !c.only)  // (MULTI_EXTREMA, HISTOGRAM, the threshold ops: their kernels stream the row through registers, no row lives in LDS; PSD, FFT, SORT, INTERP_UPSAMPLE, NORMALISE, DENSE, REFLECTED_CONVOLVE: their own layout and limits; RC_CR2, BI_LEVEL_ZERO_CROSSING: a tile of 64 rows; PEAK_SNR_THRESHOLD, MULTI_A_FILTER: nothing in LDS; LOG_CHECK, POLY_FIT, POLY_DIFF, POLY_EXP_RMS: a tile of 64 rows; INL_CORRECTION, WF_CENTROID, WF_ALIGNMENT, WF_CORRECTION: nothing in LDS; SVM_PREDICT: its own layout and limits)
         return fail(DSP_ERR_TOO_LONG, "chain needs %d bytes of LDS per waveform; a CU has %d", ch->lds_bytes_per_wave, LDS_BYTES_PER_CU);
     return DSP_OK;
 }
@@ -1894,7 +1932,8 @@ static int bind_io(PlanCtx& c) {
         const bool is_out = a.kind == DSP_IO_WF_OUT || a.kind == DSP_IO_SCALAR_OUT;
         if ((is_out || a.kind == DSP_IO_TAPS) && a.dtype != c.compute_dtype && !(is_out && a.dtype == DSP_BOOL) && !(i64 && a.kind == DSP_IO_SCALAR_OUT) &&
             !(c.only && (c.only->route == DSP_ROUTE_EXTREMA || c.only->route == DSP_ROUTE_PILEUP || c.only->route == DSP_ROUTE_PULSES) && a.kind == DSP_IO_SCALAR_OUT && a.dtype == DSP_U32) &&  // (the counts of MULTI_EXTREMA, BI_LEVEL_ZERO_CROSSING and PEAK_SNR_THRESHOLD: their matchers see to the rest)
-            !(c.only && c.only->route == DSP_ROUTE_TAILFIT && a.kind == DSP_IO_TAPS && a.dtype == DSP_F64))  // (POLY_FIT's inverted matrix: float64 in both loops)
+            !(c.only && c.only->route == DSP_ROUTE_TAILFIT && a.kind == DSP_IO_TAPS && a.dtype == DSP_F64) &&  // (POLY_FIT's inverted matrix: float64 in both loops)
+            !(c.only && c.only->route == DSP_ROUTE_SVM && (a.kind == DSP_IO_TAPS || a.kind == DSP_IO_WF_OUT) && a.dtype == DSP_F64))  // (SVM_PREDICT's model and decisions: float64 in both loops)
             return fail(DSP_ERR_ARG, "io %d: outputs have the chain's compute type or DSP_BOOL, taps the compute type", k);
         if ((a.dtype == DSP_BOOL || a.dtype == DSP_I64 || a.dtype == DSP_U64) && a.kind != DSP_IO_SCALAR_IN && a.kind != DSP_IO_SCALAR_OUT && !(a.dtype == DSP_BOOL && is_out))
             return fail(DSP_ERR_ARG, "io %d: DSP_BOOL / DSP_I64 / DSP_U64 are types of per-event columns (DSP_BOOL also of waveform outputs)", k);
@@ -2297,6 +2336,28 @@ static int lower_op(const PlanCtx& c, int i, const dsp_op& o, DevOp& d) {
                 return fail(DSP_ERR_ARG, "dense_layer: the weights (io) are a DSP_IO_TAPS binding of n * m = %d * %d values, row-major", n, m);
             if (o.ip[1] >= 0 && (o.ip[1] >= c.n_io || io[o.ip[1]].kind != DSP_IO_TAPS || io[o.ip[1]].len != m))
                 return fail(DSP_ERR_ARG, "dense_layer: the bias (ip[1]) is a DSP_IO_TAPS binding of m = %d values, or -1", m);
+            break;
+        }
+        case DSP_OP_SVM_PREDICT: {
+            if (!check_slot(P, o.src) || o.dst < 0 || o.dst >= n_sregs)
+                return fail(DSP_ERR_ARG, "op %d: bad SVM_PREDICT (src: the slot of the row; dst: the register of the label)", i);
+            static_assert(dsp_svm::N_MAX == DSP_DENSE_N_MAX && dsp_svm::CLASSES_MAX == DSP_SVM_CLASSES_MAX, "the limits the text names are the geometry's");
+            auto model = [&](int k) { return k >= 0 && k < c.n_io && io[k].kind == DSP_IO_TAPS && io[k].dtype == DSP_F64; };
+            if (!model(o.io) || !model(o.ip[0]) || !model(o.ip[1]) || !model(o.ip[2]) || !model(o.ip[3]))
+                return fail(DSP_ERR_ARG, "svm_predict: support vectors (io), their squared norms (ip[0]), D (ip[1]), intercepts (ip[2]) and classes (ip[3]) are DSP_IO_TAPS bindings of DSP_F64 in both loops");
+            const int n = slot_len[o.src], k = io[o.ip[3]].len, n_sv = io[o.ip[0]].len;
+            if (n > DSP_DENSE_N_MAX || k > DSP_SVM_CLASSES_MAX)
+                return fail(DSP_ERR_UNSUPPORTED, "svm_predict: " DSP_SVM_LIMITS_TEXT " (n = %d, %d classes given)", DSP_DENSE_N_MAX, DSP_SVM_CLASSES_MAX, n, k);
+            if (k < 2) return fail(DSP_ERR_ARG, "svm_predict: a model has at least 2 classes (%d given)", k);
+            const int pairs = dsp_svm::pairs(k);
+            if (io[o.ip[2]].len != pairs || (int64_t)io[o.io].len != (int64_t)n_sv * n || (int64_t)io[o.ip[1]].len != (int64_t)n_sv * pairs)
+                return fail(DSP_ERR_ARG, "svm_predict: %d classes, %d support vectors and rows of %d samples take %d intercepts, %lld support-vector samples and %lld coefficients (%d, %d and %d given)",
+                            k, n_sv, n, pairs, (long long)n_sv * n, (long long)n_sv * pairs, io[o.ip[2]].len, io[o.io].len, io[o.ip[1]].len);
+            if (o.sp[0].kind != DSP_ARG_CONST || o.sp[1].kind != DSP_ARG_CONST || o.sp[2].kind != DSP_ARG_CONST || (o.sp[1].value != 0.0 && o.sp[1].value != 1.0))
+                return fail(DSP_ERR_ARG, "svm_predict: gamma (sp[0]), the kernel function (sp[1]: 0 rbf, 1 linear) and the decisions' binding (sp[2]) are constants of the program");
+            const double dec = o.sp[2].value;
+            if (dec != -1.0 && !(dec >= 0 && dec < c.n_io && dec == (double)(int)dec && io[(int)dec].kind == DSP_IO_WF_OUT && io[(int)dec].dtype == DSP_F64 && io[(int)dec].len == pairs))
+                return fail(DSP_ERR_ARG, "svm_predict: the decisions (sp[2]) are a DSP_IO_WF_OUT binding of P = %d DSP_F64 values a row, or -1", pairs);
             break;
         }
         case DSP_OP_REFLECTED_CONVOLVE: {

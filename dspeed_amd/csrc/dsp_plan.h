@@ -91,7 +91,7 @@ struct ChainPlan {
     int dio_walk[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1}, dio_walk_thr[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1},
         dio_walk_ts[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1};
     // The ops no interpreter case stands behind: a program that holds one runs on that op's kernel or is refused (the table of these routes
-    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM, DSP_ROUTE_SORT, DSP_ROUTE_INTERP, DSP_ROUTE_DENSE, DSP_ROUTE_REFLECT, DSP_ROUTE_PILEUP, DSP_ROUTE_PULSES, DSP_ROUTE_TAILFIT or DSP_ROUTE_ALIGN; DSP_ROUTE_VM: the program holds none.
+    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM, DSP_ROUTE_SORT, DSP_ROUTE_INTERP, DSP_ROUTE_DENSE, DSP_ROUTE_REFLECT, DSP_ROUTE_PILEUP, DSP_ROUTE_PULSES, DSP_ROUTE_TAILFIT, DSP_ROUTE_ALIGN or DSP_ROUTE_SVM; DSP_ROUTE_VM: the program holds none.
     dsp_route kernel_only = DSP_ROUTE_VM;
     // the peak finder (dsp_extrema.hip): the one kernel a program with MULTI_EXTREMA runs on
     ExtremaArgs ext{};
@@ -141,6 +141,10 @@ struct ChainPlan {
     AlignArgs align{};
     RowSource align_src{};
     int gio_table = -1, gio_centroid = -1, gio_out = -1, gio_out2 = -1, gio_scalar = -1;
+    // svm_predict (dsp_svm.hip): the one kernel a program with SVM_PREDICT runs on; support vectors, their norms, D, intercepts, classes, label, decisions
+    SvmArgs svm{};
+    RowSource svm_src{};
+    int vio_sv = -1, vio_norm = -1, vio_coef = -1, vio_icpt = -1, vio_cls = -1, vio_label = -1, vio_dec = -1;
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};

@@ -410,6 +410,36 @@ struct DenseArgs {
     int64_t out_stride;
 };
 
+// arguments of the support-vector classifier's kernel (dsp_svm.hip), filled by the planner when a program has the shape
+//   LOAD -> SVM_PREDICT -> STORE_SCALAR
+// Rows and support vectors pass through LDS in chunks along n (dsp_kernels.h, dsp_svm); both products and the decisions stay in registers.
+// The model is float64 in both loops: the reference casts the row up and libsvm works in float64.
+#define DSP_SVM_CLASSES_MAX 23 /* classes of a model: 253 pairs, 16 blocks of decision accumulators a wavefront */
+#define DSP_SVM_LIMITS_TEXT "rows of up to %d samples and models of up to %d classes"
+#define DSP_SVM_MODEL_MAX (1 << 28) /* support-vector samples (n_sv * n) and coefficients (n_sv * P): the longest binding a chain takes */
+#define DSP_SVM_MODEL_TEXT "at least one support vector, and at most %d support-vector samples and coefficients (%d support vectors of %d samples, %d pairs of classes given)"
+struct SvmArgs {
+    const void* wf;          // float32 rows (either loop) or float64 rows (the float64 loop)
+    int64_t wf_stride;
+    int32_t wf_offset, len;  // first sample, samples (n)
+    int32_t n_sv;            // support vectors, grouped by class in class order
+    int32_t n_classes;       // k
+    int32_t n_pairs;         // P = k (k - 1) / 2
+    int32_t linear;          // 0: K = exp(-gamma |x - sv|^2), 1: K = x . sv
+    int32_t f64;             // 1: the float64 loop (the label is a float64)
+    int32_t pad_;
+    double gamma;
+    const double* sv;        // (n_sv, n) row-major
+    const double* sv_norm;   // n_sv squared norms, made on the host
+    const double* coef;      // D, (n_sv, P) row-major: the coefficient of support vector s in pair p, 0 where its class is not in the pair
+    const double* intercept; // P
+    const double* classes;   // k class values
+    void* label;             // one value of the loop's type per row
+    int64_t label_stride;
+    double* dec;             // rows of P decisions, or null
+    int64_t dec_stride;
+};
+
 // arguments of the mirrored-edge FIR kernel (dsp_reflect.hip), filled by the planner when a program has one of the shapes
 //   LOAD -> REFLECTED_CONVOLVE -> STORE        LOAD -> REFLECTED_CONVOLVE -> AVG_CURRENT -> STORE [of the filtered row too]
 // The row lives in LDS in the loop's type with its mirrored margins beside it (dsp_kernels.h, dsp_reflect).

@@ -253,6 +253,7 @@ _SIGS = {
     # ml.py: (x_in, means, variances, x_out); (x_in, kernel[n, m], [bias[m],] activation_func, x_out[m]); (x_in, kernel[n], [bias,] activation_func, x_out)
     "normalisation_layer": "waaW", "dense_layer_no_bias": "wacW", "dense_layer_with_bias": "waacW",
     "classification_layer_no_bias": "wacS", "classification_layer_with_bias": "waacS",
+    "svm_predict": "wS",  # (w_in, label) with init_args (svm_file)
     "get_multi_local_extrema": "wssissWWSS",  # (w_in, a_delta_max_in, a_delta_min_in, search_direction, a_abs_max_in, a_abs_min_in, two lists, two counts)
 }
 _SIGS.update({"sample": "wiS", "slice": "wiiW", "get": "wsS"})  # wf[i], wf[lo:hi:step], wf[variable] (reference :948-1071)
@@ -370,11 +371,14 @@ _ML_FILES = dict.fromkeys(("normalisation_layer", "dense_layer_no_bias", "dense_
                            "classification_layer_with_bias"), ("ml",))  # (processors.ML, likewise)
 
 
+_CLEANING_FILES = {"svm_predict": ("svm",)}  # (processors.CLEANING, likewise)
+
+
 def module_accepted(module, function) -> bool:
     """a recipe's module string: the package (``_MODULES``), or ``dspeed.processors.<file>`` for the file that defines ``function``"""
     pre = "dspeed.processors."
     files = _PROCESSOR_FILES.get(function, ()) + _SPECTRAL_FILES.get(function, ()) + _ORDER_FILES.get(function, ()) + _RESAMPLING_FILES.get(function, ())
-    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ()) + _PILEUP_FILES.get(function, ()) + _PULSE_FILES.get(function, ()) + _TAILFIT_FILES.get(function, ()) + _ALIGN_FILES.get(function, ())
+    files += _ML_FILES.get(function, ()) + _SMOOTHING_FILES.get(function, ()) + _PILEUP_FILES.get(function, ()) + _PULSE_FILES.get(function, ()) + _TAILFIT_FILES.get(function, ()) + _ALIGN_FILES.get(function, ()) + _CLEANING_FILES.get(function, ())
     return module in _MODULES or (isinstance(module, str) and module.startswith(pre) and module[len(pre):] in files)
 
 

@@ -1210,5 +1210,177 @@ step = HipGUFunc("step", "(),(n)", ["ff", "dd"], _step, "step kernel generator, 
 # Listed here and not in __all__, like the decay-tail fitter's processors: their call records are tests/test_align_plan_cpu.py's.
 ALIGNMENT = ("inl_correction", "get_wf_centroid", "wf_alignment", "wf_correction", "step")
 
+
+# --------------------------------------------------------------------------------------------------- data cleaning
+SVM_KERNELS = ("rbf", "linear")  # kernel_kind 0 and 1 of dsp_svm_rows
+SVM_LIMITS = f"rows of up to {_lib.DENSE_N_MAX} samples and models of up to {_lib.SVM_CLASSES_MAX} classes"  # (DSP_SVM_LIMITS_TEXT, dsp_program.h)
+_SVM_FIELDS = ("kernel", "gamma", "support_vectors", "n_support", "dual_coef", "intercept", "classes")
+
+
+def check_svm(what, n, n_classes, n_sv=None):
+    """what the planner and the C entry check, in their words: rows and classes; with ``n_sv``, the size of the model as well"""
+    if n > _lib.DENSE_N_MAX or n_classes > _lib.SVM_CLASSES_MAX:
+        raise NotImplementedError(f"{what}: {SVM_LIMITS} (n = {n}, {n_classes} classes given)")
+    pairs = n_classes * (n_classes - 1) // 2
+    if n_sv is not None and (n_sv < 1 or n < 1 or n_sv * n > _lib.SVM_MODEL_MAX or n_sv * pairs > _lib.SVM_MODEL_MAX):
+        raise NotImplementedError(f"{what}: at least one support vector, and at most {_lib.SVM_MODEL_MAX} support-vector samples and coefficients "
+                                  f"({n_sv} support vectors of {n} samples, {pairs} pairs of classes given)")
+
+
+def svm_model_arrays(svc):
+    """The constant arrays a fitted ``sklearn.svm.SVC`` predicts with, as a dict: ``kernel``, ``gamma``, ``support_vectors`` (n_sv, n),
+    ``n_support`` (k,), ``dual_coef`` and ``intercept`` (the UNDERSCORED attributes ``_dual_coef_`` and ``_intercept_``: for two classes the
+    public ones carry the opposite sign) and ``classes``.  Needs nothing of scikit-learn but the object."""
+    if type(svc).__name__ != "SVC" or not hasattr(svc, "support_vectors_") or not hasattr(svc, "_dual_coef_"):
+        raise TypeError(f"svm_predict: {type(svc).__name__!r} is no fitted sklearn.svm.SVC")
+    kernel = svc.kernel
+    if kernel not in SVM_KERNELS:
+        raise NotImplementedError(f"svm_predict: the kernel function {kernel if isinstance(kernel, str) else 'given as a callable'!r} is not "
+                                  "implemented on the device: 'rbf' and 'linear' are")
+    if getattr(svc, "break_ties", False):
+        raise NotImplementedError("svm_predict: break_ties=True is not implemented on the device (the vote's first maximum wins)")
+    classes = np.asarray(svc.classes_)
+    if classes.dtype.kind not in "fiub":
+        raise TypeError(f"svm_predict: the class labels are {classes.dtype.name}; the label of a row is a number (float32 in the reference)")
+    sv = svc.support_vectors_
+    if hasattr(sv, "toarray"):
+        raise NotImplementedError("svm_predict: sparse support vectors are not implemented on the device")
+    return _checked_svm_model({"kernel": kernel, "gamma": float(svc._gamma), "support_vectors": sv, "n_support": svc.n_support_,
+                               "dual_coef": svc._dual_coef_, "intercept": svc._intercept_, "classes": classes})
+
+
+def _checked_svm_model(m):
+    """the dict of ``svm_model_arrays`` -- from an SVC or from a file -- with its arrays in their types and its shapes checked"""
+    missing = [f for f in _SVM_FIELDS if f not in m]
+    if missing:
+        raise ValueError(f"svm_predict: the model lacks {', '.join(missing)}")
+    kernel = str(np.asarray(m["kernel"]).reshape(-1)[0]) if not isinstance(m["kernel"], str) else m["kernel"]
+    if kernel not in SVM_KERNELS:
+        raise NotImplementedError(f"svm_predict: the kernel function {kernel!r} is not implemented on the device: 'rbf' and 'linear' are")
+    classes = np.asarray(m["classes"])
+    if classes.dtype.kind not in "fiub":
+        raise TypeError(f"svm_predict: the class labels are {classes.dtype.name}; the label of a row is a number (float32 in the reference)")
+    out = {"kernel": kernel, "gamma": float(np.asarray(m["gamma"]).reshape(-1)[0]),
+           "support_vectors": np.ascontiguousarray(m["support_vectors"], dtype=np.float64), "n_support": np.asarray(m["n_support"], dtype=np.int32).reshape(-1),
+           "dual_coef": np.ascontiguousarray(m["dual_coef"], dtype=np.float64), "intercept": np.asarray(m["intercept"], dtype=np.float64).reshape(-1),
+           "classes": classes.astype(np.float64).reshape(-1)}
+    k, sv = out["classes"].size, out["support_vectors"]
+    if (k < 2 or sv.ndim != 2 or sv.shape[0] < 1 or out["n_support"].size != k or int(out["n_support"].sum()) != sv.shape[0] or (out["n_support"] < 0).any()
+            or out["dual_coef"].shape != (k - 1, sv.shape[0]) or out["intercept"].size != k * (k - 1) // 2):
+        raise ValueError(f"svm_predict: the model's arrays do not fit each other ({k} classes, support_vectors {sv.shape}, n_support {out['n_support'].shape}, "
+                         f"dual_coef {out['dual_coef'].shape}, intercept {out['intercept'].shape})")
+    return out
+
+
+def svm_device_arrays(model):
+    """what ``dsp_svm_rows`` takes of a model, float64 and contiguous on the host: the support vectors, their squared norms, D (n_sv, P) --
+    the coefficient of support vector s in pair p = (i, j) of classes, ``dual_coef[j - 1, s]`` for a support vector of class i and
+    ``dual_coef[i, s]`` for one of class j, 0 elsewhere; the pairs in the order (0,1), (0,2) .. (k-2,k-1) --, the intercepts and the classes"""
+    sv, k = model["support_vectors"], model["classes"].size
+    cls = np.repeat(np.arange(k), model["n_support"])
+    D = np.zeros((sv.shape[0], k * (k - 1) // 2))
+    p = 0
+    for i in range(k):
+        for j in range(i + 1, k):
+            D[cls == i, p] = model["dual_coef"][j - 1, cls == i]
+            D[cls == j, p] = model["dual_coef"][i, cls == j]
+            p += 1
+    return sv, np.ascontiguousarray((sv * sv).sum(axis=1)), D, model["intercept"], model["classes"]
+
+
+def save_svm_model(path, svc):
+    """``svm_model_arrays(svc)`` as an ``.npz`` file: what ``svm_predict(path)`` reads where scikit-learn is not installed"""
+    np.savez(path, **svm_model_arrays(svc))
+
+
+def load_svm_model(svm_file):
+    """the model behind ``svm_predict``'s argument: a fitted SVC, a dict of its arrays, an ``.npz`` of them, or a pickle of the SVC"""
+    if isinstance(svm_file, dict):
+        return _checked_svm_model(svm_file)
+    if isinstance(svm_file, (str, bytes)) or hasattr(svm_file, "__fspath__"):
+        import os
+
+        path = os.fspath(svm_file)
+        path = path.decode() if isinstance(path, bytes) else path
+        if path.endswith(".npz"):
+            with np.load(path, allow_pickle=False) as f:
+                return _checked_svm_model({name: f[name] for name in f.files})
+        try:
+            import sklearn.svm  # noqa: F401  (the pickle names its classes)
+        except ImportError:
+            raise ImportError(f"svm_predict: '{path}' is a pickle of a scikit-learn SVC, and scikit-learn is not installed where the chain is built; "
+                              "write the model's arrays with dspeed_amd.processors.save_svm_model(path.npz, svc) where it is") from None
+        import pickle
+
+        with open(path, "rb") as f:
+            return svm_model_arrays(pickle.load(f))
+    return svm_model_arrays(svm_file)
+
+
+def _null_svm(g, *args):
+    """``svm_predict(0)``: NaN for every row, nothing launched (reference processors/svm.py:45-51)"""
+    if len(args) not in (1, 2):
+        raise TypeError(f"{g.__name__}() takes w_in and label_out ({len(args)} given)")
+    w_in, out = args[0], (args[1] if len(args) == 2 else None)
+    shape, dt = tuple(w_in.shape), np.dtype(dtype_of(w_in))
+    ft = np.float64 if dt == np.dtype(np.float64) else np.float32
+    if out is None:
+        return np.full(shape[:-1], np.nan, dtype=ft)[()] if len(shape) == 1 else np.full(shape[:-1], np.nan, dtype=ft)
+    if isinstance(out, DeviceArray):
+        out.copy_from(np.full(tuple(out.shape), np.nan, dtype=out.dtype))
+    else:
+        out[...] = np.nan
+    return out
+
+
+def svm_predict(svm_file):
+    """The reference's factory (processors/svm.py:13-71): the gufunc ``svm_out``, ``(n)->()``, that gives every row the class label of a fitted
+    scikit-learn ``SVC``.  ``svm_file`` is 0 (the null processor: NaN for every row, nothing launched), the path of a pickle of the SVC (needs
+    scikit-learn importable here; UNPICKLING RUNS WHAT THE FILE SAYS, as in the reference: open files you trust), a path ending in ``.npz`` holding
+    ``svm_model_arrays`` (``save_svm_model``; needs no scikit-learn), or the fitted ``SVC`` itself.  Nothing of scikit-learn runs per row: the
+    model's arrays are taken out here, once, go to the device at the first call and stay with the returned processor.  "rbf" and "linear"
+    kernel functions; a row with a NaN -- or, unlike the reference, which raises scikit-learn's ValueError, with an infinite sample -- gives
+    NaN.  The float64 loop is this project's addition."""
+    doc = "the class label of a fitted sklearn.svm.SVC (rbf or linear, one-vs-one) for every row; a row with a NaN or an infinity: NaN (reference processors/svm.py:13-71)"
+    if isinstance(svm_file, (int, np.integer, float)) and not isinstance(svm_file, bool) and svm_file == 0:
+        g = HipGUFunc("svm_out", "(n)->()", ["f->f", "d->d"], _null_svm, doc)
+        g.model = None
+        return g
+    model = load_svm_model(svm_file)
+    host = svm_device_arrays(model)
+    n_sv, n = model["support_vectors"].shape
+    k = model["classes"].size
+    check_svm("svm_predict", n, k, n_sv)
+    kind = SVM_KERNELS.index(model["kernel"])
+    held = []  # the model on the device: made at the first call, kept
+
+    def impl(g, *args):
+        what = "svm_predict"
+        if len(args) not in (1, 2):
+            raise TypeError(f"{what}() takes w_in and label_out ({len(args)} given)")
+        w_in, out = args[0], (args[1] if len(args) == 2 else None)
+        if np.dtype(dtype_of(w_in)) not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise NotImplementedError(f"{what}: float32 rows (the float32 loop) or float64 rows (the float64 loop), not {np.dtype(dtype_of(w_in)).name}")
+        with device_call(what, w_in) as c:
+            if c.n != n:
+                raise ValueError(f"{what}: the rows hold {c.n} samples, the model's support vectors {n}")
+            check_svm(what, c.n, k, n_sv)
+            if not held:
+                held.extend(DeviceArray.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) for a in host)
+            (ptr,) = c.out(out)
+            run(getattr(_lib.lib(), "dsp_svm_rows"), what, *c.rows_args, _lib.F32 if c.ft is np.float32 else _lib.F64, *(d.ptr for d in held), n_sv, k, kind,
+                float(model["gamma"]), ptr, None, 0)  # (no decisions: the label alone)
+            c.st.finish()
+            res = c.results[0]
+            return res[()] if isinstance(res, np.ndarray) and res.ndim == 0 else res
+
+    g = HipGUFunc("svm_out", "(n)->()", ["f->f", "d->d"], impl, doc)
+    g.model, g.device_arrays = model, held
+    return g
+
+
+# Listed here and not in __all__, like the aligner's processors: its call record is tests/test_svm_plan_cpu.py's.
+CLEANING = ("svm_predict",)
+
 __all__ = ["bl_subtract", "pole_zero", "double_pole_zero", "trap_filter", "trap_norm", "asym_trap_filter", "fixed_time_pickoff",
            "time_point_thresh", "interpolated_time_point_thresh", "min_max", "min_max_norm", "linear_slope_fit", "mean_below_threshold", "windower", "avg_current", "upsampler", "moving_window_multi", "trap_pickoff", "discrete_wavelet_transform", "convolve_wf", "fft_convolve_wf", "cusp_filter", "zac_filter", "t0_filter", "moving_slope", "get_multi_local_extrema", "histogram", "histogram_stats", "multi_time_point_thresh", "time_over_threshold"]

@@ -390,6 +390,20 @@ typedef struct dsp_scalar_arg {
                                  *   LOAD, WF_ALIGNMENT, WF_CORRECTION of the aligned row, [STORE of the aligned row,] STORE of the corrected row
                                  * where the aligned row goes to memory only if it is stored.  WF_ALIGNMENT also takes DSP_I16 / DSP_U16 (either
                                  * loop) and DSP_I32 / DSP_U32 (the float64 loop) rows: they hold no NaN, and only the window is read */
+#define DSP_OP_SVM_PREDICT 58  /* svm.py:13-71 svm_predict: sreg[dst] <- the label a fitted sklearn.svm.SVC (libsvm, one-vs-one) gives src (n samples),
+                                 * as classes[c] in the loop's type.  The model is five DSP_IO_TAPS bindings of DSP_F64 in BOTH loops: io = the
+                                 * support vectors (n_sv * n values, row-major, grouped by class in class order), ip[0] = their squared norms
+                                 * (n_sv), ip[1] = D (n_sv * P, row-major: the dual coefficient of support vector s in pair p of classes, 0 where
+                                 * its class is not in the pair; P = k (k - 1) / 2, pairs in the order (0,1), (0,2) .. (k-2,k-1)), ip[2] = the P
+                                 * intercepts, ip[3] = the k class values.  sp[0] = gamma, sp[1] = the kernel function (0: rbf, K = exp(-gamma
+                                 * |x - sv|^2); 1: linear, K = x . sv), sp[2] = the io index of a DSP_IO_WF_OUT binding of P DSP_F64 values a row for the
+                                 * decisions, or -1: none are written -- constants all three.  dec_p = sum_s D[s, p] K_s + intercept[p] in
+                                 * float64 on the matrix cores; dec_p > 0 votes for class i of pair (i, j), anything else for j; the first class
+                                 * with the most votes wins.  A row with a NaN or an infinite sample: a NaN label and NaN decisions (the reference
+                                 * raises scikit-learn's ValueError for an infinite one).  n up to 16384, 2 <= k <= 23.  The float32 loop takes
+                                 * DSP_F32 rows, the float64 loop DSP_F32 or DSP_F64 rows.  The waveform interpreter has no such op: it runs on
+                                 * dsp_svm_kernel only, in a program of exactly
+                                 *   LOAD, SVM_PREDICT, STORE_SCALAR of dst */
 #define DSP_FN_ADD 0
 #define DSP_FN_SUB 1
 #define DSP_FN_MUL 2
@@ -663,6 +677,15 @@ int dsp_interp_upsample_rows(const void* in, int in_dtype, int64_t n_wf, int32_t
  * out_stride apart, or with out_len == 0 a column of one value per row (out_stride is not read). */
 int dsp_dense_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, const void* weights_dev,
                    const void* bias_dev, int32_t activation, void* out, int32_t out_len, int64_t out_stride, void* stream, int64_t* err_row);
+
+/* "(n)->()" svm_predict (svm.py:13-71; DSP_OP_SVM_PREDICT).  One entry for both loops: compute_dtype DSP_F32 takes DSP_F32 rows, DSP_F64
+ * takes DSP_F32 or DSP_F64 rows; label_out holds one value of the loop's type per row.  The model lies on the device as float64 arrays:
+ * sv_dev (n_sv * wf_len, row-major), sv_norm_dev (n_sv squared norms), coef_dev (D: n_sv * P, P = n_classes (n_classes - 1) / 2),
+ * intercept_dev (P), classes_dev (n_classes).  kernel_kind: 0 rbf, 1 linear.  dec_out: rows of P float64 decisions dec_stride values apart,
+ * or NULL: none are written. */
+int dsp_svm_rows(const void* in, int in_dtype, int64_t n_wf, int32_t wf_len, int64_t in_stride, int compute_dtype, const void* sv_dev,
+                 const void* sv_norm_dev, const void* coef_dev, const void* intercept_dev, const void* classes_dev, int32_t n_sv, int32_t n_classes,
+                 int32_t kernel_kind, double gamma, void* label_out, void* dec_out, int64_t dec_stride, void* stream, int64_t* err_row);
 
 /* "(n),(n),(n)->(n)" normalisation_layer (ml.py:358-390; DSP_OP_NORMALISE): (row - means) / sqrt(variances), means_dev and variances_dev
  * wf_len values of the loop's type on the device.  One entry for both loops. */
