@@ -353,7 +353,7 @@ const char* dsp_version(void) { return "dspeed_hip 0.1 (gfx950)"; }
 // transform's twiddles, then the unpacking twiddles (a power-of-two row) or the chirp and the filter (Bluestein).  No launch writes them.
 static int spectrum_tables(dsp_chain* ch) {
     namespace tb = dsp_spectrum_tables;
-    SpectrumArgs& A = ch->spec;
+    SpectrumArgs& A = ch->only.spec;
     std::vector<double> all = tb::twiddle(A.points);
     const size_t at_aux = all.size();
     const std::vector<double> aux = A.bluestein ? tb::chirp(A.len) : tb::unpack(A.len);
@@ -375,6 +375,49 @@ static int spectrum_tables(dsp_chain* ch) {
     return DSP_OK;
 }
 
+// ---- the kernel-only routes (dsp_plan.cpp's kernel_only_routes holds what is HIP-free about each): a row per route, at the route's index
+struct KernelOnlyLaunch {
+    int (*launch)(const KernelOnlyArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream);
+    const char* what;
+    int (*set_lds)(const dsp_chain* ch, int bytes) = nullptr;  // raises the kernel's dynamic-LDS limit, where the route has one to raise ...
+    const char* lds_label = nullptr;                           // ... and what the error text calls it
+    // what is the route's own, at most one of the two: device data of the chain, or a pointer no binding stands behind
+    int (*at_create)(dsp_chain* ch) = nullptr;
+    void (*at_launch)(const dsp_chain* ch, KernelOnlyArgs& A) = nullptr;
+};
+extern "C++" {
+template <typename Args, Args KernelOnlyArgs::*block, int (*launcher)(const Args*, int64_t, int, int, int*, hipStream_t)>
+static int launch_block(const KernelOnlyArgs* A, int64_t n_wf, int dtype, int vec, int* err, hipStream_t stream) {
+    return launcher(&(A->*block), n_wf, dtype, vec, err, stream);
+}
+template <int (*setter)(int dtype, int bytes)>
+static int set_lds_of_rows(const dsp_chain* ch, int bytes) {
+    return setter(ch->only_src.dtype, bytes);
+}
+}
+#define KERNEL_ONLY(Args, block, name) launch_block<Args, &KernelOnlyArgs::block, dsp_internal_launch_##name>
+static const KernelOnlyLaunch kernel_only_launches[] = {
+    {KERNEL_ONLY(ExtremaArgs, ext, extrema), "extrema kernel launch"},
+    {KERNEL_ONLY(HistArgs, hist, hist), "histogram kernel launch"},
+    {KERNEL_ONLY(ThreshArgs, thresh, thresh), "threshold kernel launch"},
+    {KERNEL_ONLY(SpectrumArgs, spec, spectrum), "spectrum kernel launch", set_lds_of_rows<dsp_internal_set_spectrum_lds>, "spectrum kernel, %d",
+     spectrum_tables},  // (the block's table pointers are the chain's)
+    {KERNEL_ONLY(SortArgs, sort, sort), "sort kernel launch", set_lds_of_rows<dsp_internal_set_sort_lds>, "sort kernel, %d"},
+    {KERNEL_ONLY(InterpArgs, interp, interp), "interp kernel launch", set_lds_of_rows<dsp_internal_set_interp_lds>, "interp kernel, %d"},
+    {KERNEL_ONLY(DenseArgs, dense, dense), "dense kernel launch", set_lds_of_rows<dsp_internal_set_dense_lds>, "dense kernel, %d"},
+    {KERNEL_ONLY(ReflectArgs, reflect, reflect), "reflect kernel launch", set_lds_of_rows<dsp_internal_set_reflect_lds>, "reflect kernel, %d"},
+    {KERNEL_ONLY(PileupArgs, pileup, pileup), "pile-up kernel launch"},
+    {KERNEL_ONLY(PulsesArgs, pulses, pulses), "pulse kernel launch"},
+    {KERNEL_ONLY(TailfitArgs, tailfit, tailfit), "tail-fit kernel launch"},
+    {KERNEL_ONLY(AlignArgs, align, align), "align kernel launch", nullptr, nullptr, nullptr,  // (no LDS)
+     [](const dsp_chain* ch, KernelOnlyArgs& A) { A.align.table_nan = A.align.table ? ch->dev_err + DSP_ERR_TABLE_WORD : nullptr; }},
+    // (the largest any chain needs, whatever this one does: never lowered under another chain's launch)
+    {KERNEL_ONLY(SvmArgs, svm, svm), "svm kernel launch",
+     [](const dsp_chain* ch, int) { return dsp_internal_set_svm_lds(ch->only_src.dtype, ch->only.svm.f64, dsp_svm::LDS_MAX); }, "svm kernel, %d"},
+};
+#undef KERNEL_ONLY
+static_assert(sizeof kernel_only_launches / sizeof kernel_only_launches[0] == DSP_KERNEL_ONLY_ROUTES, "a row per kernel-only route, as in dsp_plan.cpp");
+
 int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_io, const int32_t* slot_len, int n_slots,
                      int n_sregs, int compute_dtype, dsp_chain** out) {
     if (out) *out = nullptr;
@@ -392,8 +435,9 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
             HIP_TRY(hipMalloc(&buf, dsp_fir_f16::taps_bytes(ch->fir.kend)));
             ch->f16.taps16[k] = buf;
         }
-    if (ch->kernel_only == DSP_ROUTE_SPECTRUM)
-        if (const int rc = spectrum_tables(ch.get())) return rc;
+    const KernelOnlyLaunch* only = ch->kernel_only != DSP_ROUTE_VM ? &kernel_only_launches[ch->kernel_only] : nullptr;
+    if (only && only->at_create)
+        if (const int rc = only->at_create(ch.get())) return rc;
     HIP_TRY(hipGetDevice(&ch->device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, ch->device));
@@ -413,24 +457,8 @@ int dsp_chain_create(const dsp_op* ops, int n_ops, const dsp_io_desc* io, int n_
     if (!rc) rc = raise_lds(ch->scalar_ok, n_sregs * 64 * esz, 48 * 1024, "scalar kernel", dsp_internal_set_scalar_lds);
     if (!rc) rc = raise_lds(ch->cur_ok, ch->cur_lds_bytes, 64 * 1024, "current kernel, %d", dsp_internal_set_current_lds);
     if (!rc) rc = raise_lds(ch->rows_ok, ch->rows_lds_bytes, 64 * 1024, "rows kernel, %d", dsp_internal_set_rows_lds);
-    if (!rc)
-        rc = raise_lds(ch->kernel_only == DSP_ROUTE_SPECTRUM, dsp_spectrum::lds_bytes(ch->spec.len, esz), 64 * 1024, "spectrum kernel, %d",
-                       [&](int n) { return dsp_internal_set_spectrum_lds(ch->spec_src.dtype, n); });
-    if (!rc)
-        rc = raise_lds(ch->kernel_only == DSP_ROUTE_SORT, dsp_sort::lds_bytes(ch->sort.len, esz), 64 * 1024, "sort kernel, %d",
-                       [&](int n) { return dsp_internal_set_sort_lds(ch->sort_src.dtype, n); });
-    if (!rc)
-        rc = raise_lds(ch->kernel_only == DSP_ROUTE_INTERP, dsp_interp::lds_bytes(ch->interp.mode, ch->interp.len, esz), 64 * 1024, "interp kernel, %d",
-                       [&](int n) { return dsp_internal_set_interp_lds(ch->interp_src.dtype, n); });
-    if (!rc)
-        rc = raise_lds(ch->kernel_only == DSP_ROUTE_DENSE, dsp_dense::lds_bytes(ch->dense.m, esz), 64 * 1024, "dense kernel, %d",
-                       [&](int n) { return dsp_internal_set_dense_lds(ch->dense_src.dtype, n); });
-    if (!rc)
-        rc = raise_lds(ch->kernel_only == DSP_ROUTE_REFLECT, dsp_reflect::lds_bytes(ch->reflect.len, ch->reflect.n_taps, esz), 64 * 1024, "reflect kernel, %d",
-                       [&](int n) { return dsp_internal_set_reflect_lds(ch->reflect_src.dtype, n); });
-    if (!rc)
-        rc = raise_lds(ch->kernel_only == DSP_ROUTE_SVM, dsp_svm::lds_bytes(ch->svm.len, ch->svm.n_pairs), 64 * 1024, "svm kernel, %d",
-                       [&](int) { return dsp_internal_set_svm_lds(ch->svm_src.dtype, ch->svm.f64, dsp_svm::LDS_MAX); });  // (the largest any chain needs: never lowered under another chain's launch)
+    if (!rc && only && only->set_lds)
+        rc = raise_lds(true, dsp_plan_kernel_only_lds(ch.get()), 64 * 1024, only->lds_label, [&](int n) { return only->set_lds(ch.get(), n); });
     if (rc) return rc;
     *out = ch.release();
     return DSP_OK;
@@ -445,7 +473,6 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // Does the kernel of a route run THIS launch?  The program has its shape, the specialised kernels are on, and the buffers of this call keep
 // the 16-byte alignment its wide loads need (the plan vouches for strides and offsets, nobody for the pointers).  dsp_chain_execute asks
 // in the order of dsp_plan_route; a launch whose planned route does not apply runs on the next that does.
-static bool kernel_only_applies(const dsp_chain* ch, dsp_route route) { return ch->kernel_only == route; }  // (always: the program runs nowhere else; unaligned rows: the kernel's scalar loads)
 static bool scalar_applies(const dsp_chain* ch, void* const*) { return ch->scalar_ok && ch->fused_on; }
 static bool pz_rows_applies(const dsp_chain* ch, void* const* io_ptrs) {
     return ch->pz_ok && ch->fused_on && aligned16(io_ptrs[ch->pio_wf]) && aligned16(io_at(ch, io_ptrs, ch->pio_out));
@@ -609,154 +636,14 @@ static int launch_on_rows(dsp_chain* ch, int64_t n_wf, void* stream, const Args&
     return launched(ch, stream, e, what);
 }
 
-static int launch_extrema(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
-    ExtremaArgs A = ch->ext;
-    A.wf = io_ptrs[ch->ext_src.io];
-    for (int k = 0; k < 4; ++k) A.par[k] = at(ch->xio_par[k]);
-    for (int k = 0; k < 2; ++k) {
-        A.vt_out[k] = at(ch->xio_vt[k]);
-        A.n_out[k] = (uint32_t*)at(ch->xio_n[k]);
-    }
-    return launch_on_rows(ch, n_wf, stream, A, ch->ext_src, dsp_internal_launch_extrema, "extrema kernel launch");
-}
-
-static int launch_hist(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
-    HistArgs A = ch->hist;
-    auto raw = [&](int k) -> void* { return k < 0 ? nullptr : io_ptrs[k]; };  // (the inputs' offsets travel in the arguments)
-    A.wf = raw(ch->hist_src.io);
-    A.w_in = raw(ch->hio_w_in);
-    A.e_in = raw(ch->hio_e_in);
-    A.w_out = at(ch->hio_w);
-    A.b_out = at(ch->hio_b);
-    A.max_in = at(ch->hio_max_in);
-    for (int k = 0; k < 3; ++k) A.s_out[k] = at(ch->hio_s[k]);
-    return launch_on_rows(ch, n_wf, stream, A, ch->hist_src, dsp_internal_launch_hist, "histogram kernel launch");
-}
-
-static int launch_thresh(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    ThreshArgs A = ch->thresh;
-    A.wf = io_ptrs[ch->thresh_src.io];  // (the inputs' offsets travel in the arguments)
-    A.thr = ch->tio_thr < 0 ? nullptr : io_ptrs[ch->tio_thr];
-    A.ts = io_at(ch, io_ptrs, ch->tio_ts);
-    A.out = io_at(ch, io_ptrs, ch->tio_out);
-    return launch_on_rows(ch, n_wf, stream, A, ch->thresh_src, dsp_internal_launch_thresh, "threshold kernel launch");
-}
-
-static int launch_spectrum(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    SpectrumArgs A = ch->spec;  // (its table pointers are the chain's)
-    A.wf = io_ptrs[ch->spec_src.io];
-    A.out = io_at(ch, io_ptrs, ch->sio_out);
-    return launch_on_rows(ch, n_wf, stream, A, ch->spec_src, dsp_internal_launch_spectrum, "spectrum kernel launch");
-}
-
-static int launch_sort(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    SortArgs A = ch->sort;
-    A.wf = io_ptrs[ch->sort_src.io];
-    A.out = io_at(ch, io_ptrs, ch->oio_out);
-    return launch_on_rows(ch, n_wf, stream, A, ch->sort_src, dsp_internal_launch_sort, "sort kernel launch");
-}
-
-static int launch_interp(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    InterpArgs A = ch->interp;
-    A.wf = io_ptrs[ch->interp_src.io];
-    A.out = io_at(ch, io_ptrs, ch->iuo_out);
-    // 16-byte stores: launch_on_rows' rule for the loads, on the output side (the plan vouches for the stride, this call's pointer for the start)
-    A.out_vec = (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
-    return launch_on_rows(ch, n_wf, stream, A, ch->interp_src, dsp_internal_launch_interp, "interp kernel launch");
-}
-
-static int launch_dense(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    DenseArgs A = ch->dense;
-    A.wf = io_ptrs[ch->dense_src.io];
-    A.weights = io_at(ch, io_ptrs, ch->eio_w);
-    A.bias = io_at(ch, io_ptrs, ch->eio_b);
-    A.means = io_at(ch, io_ptrs, ch->eio_mean);
-    A.variances = io_at(ch, io_ptrs, ch->eio_var);
-    A.out = io_at(ch, io_ptrs, ch->eio_out);
-    return launch_on_rows(ch, n_wf, stream, A, ch->dense_src, dsp_internal_launch_dense, "dense kernel launch");
-}
-
-static int launch_svm(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    SvmArgs A = ch->svm;
-    A.wf = io_ptrs[ch->svm_src.io];
-    A.sv = (const double*)io_at(ch, io_ptrs, ch->vio_sv);
-    A.sv_norm = (const double*)io_at(ch, io_ptrs, ch->vio_norm);
-    A.coef = (const double*)io_at(ch, io_ptrs, ch->vio_coef);
-    A.intercept = (const double*)io_at(ch, io_ptrs, ch->vio_icpt);
-    A.classes = (const double*)io_at(ch, io_ptrs, ch->vio_cls);
-    A.label = io_at(ch, io_ptrs, ch->vio_label);
-    A.dec = (double*)io_at(ch, io_ptrs, ch->vio_dec);
-    return launch_on_rows(ch, n_wf, stream, A, ch->svm_src, dsp_internal_launch_svm, "svm kernel launch");
-}
-
-static int launch_reflect(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    ReflectArgs A = ch->reflect;
-    A.wf = io_ptrs[ch->reflect_src.io];
-    A.taps = io_at(ch, io_ptrs, ch->rio_taps);
-    A.out = io_at(ch, io_ptrs, ch->rio_out);
-    A.cur = io_at(ch, io_ptrs, ch->rio_cur);
-    // 16-byte stores: launch_interp's rule (the plan vouches for the stride, this call's pointer for the start)
-    A.out_vec = A.out && (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
-    return launch_on_rows(ch, n_wf, stream, A, ch->reflect_src, dsp_internal_launch_reflect, "reflect kernel launch");
-}
-
-static int launch_pileup(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
-    PileupArgs A = ch->pileup;
-    A.wf = io_ptrs[ch->pileup_src.io];
-    for (int k = 0; k < 4; ++k) A.par[k] = at(ch->lio_par[k]);
-    A.out = at(ch->lio_out);
-    A.sub = at(ch->lio_sub);
-    for (int k = 0; k < 2; ++k) A.list[k] = at(ch->lio_list[k]);
-    A.n_out = (uint32_t*)at(ch->lio_n);
-    // 16-byte stores: launch_interp's rule (the plan vouches for the stride, this call's pointer for the start)
-    A.out_vec = A.out && (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
-    return launch_on_rows(ch, n_wf, stream, A, ch->pileup_src, dsp_internal_launch_pileup, "pile-up kernel launch");
-}
-
-static int launch_pulses(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
-    PulsesArgs A = ch->pulses;
-    A.wf = io_ptrs[ch->pulses_src.io];  // (the inputs' offsets travel in the arguments)
-    A.list = io_ptrs[ch->uio_list];
-    A.ratio = at(ch->uio_ratio);
-    A.idx_out = at(ch->uio_idx);
-    A.n_out = (uint32_t*)at(ch->uio_n);
-    A.amp_out = at(ch->uio_amp);
-    return launch_on_rows(ch, n_wf, stream, A, ch->pulses_src, dsp_internal_launch_pulses, "pulse kernel launch");
-}
-
-static int launch_tailfit(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
-    TailfitArgs A = ch->tailfit;
-    A.wf = io_ptrs[ch->tailfit_src.io];  // (the inputs' offsets travel in the arguments)
-    A.pars = ch->aio_pars < 0 ? nullptr : io_ptrs[ch->aio_pars];
-    A.sub = at(ch->aio_sub);
-    A.inv = (const double*)at(ch->aio_inv);
-    A.out = at(ch->aio_out);
-    A.pars_out = at(ch->aio_pars_out);
-    A.mean_out = at(ch->aio_mean);
-    A.rms_out = at(ch->aio_rms);
-    // 16-byte stores: launch_interp's rule (the plan vouches for the stride, this call's pointer for the start)
-    A.out_vec = A.out && (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
-    return launch_on_rows(ch, n_wf, stream, A, ch->tailfit_src, dsp_internal_launch_tailfit, "tail-fit kernel launch");
-}
-
-static int launch_align(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
-    auto at = [&](int k) { return io_at(ch, io_ptrs, k); };
-    AlignArgs A = ch->align;
-    A.wf = io_ptrs[ch->align_src.io];  // (the inputs' offsets travel in the arguments)
-    A.table = at(ch->gio_table);
-    A.table_nan = A.table ? ch->dev_err + DSP_ERR_TABLE_WORD : nullptr;
-    A.centroid = at(ch->gio_centroid);
-    A.out = at(ch->gio_out);
-    A.out2 = at(ch->gio_out2);
-    A.scalar_out = at(ch->gio_scalar);
-    // 16-byte stores of the outputs the kernel streams (inl_correction's, wf_correction's): launch_interp's rule
-    A.out_vec = A.mode != DSP_ALIGN_WINDOW && A.out && (A.out_stride * (ch->f64 ? 8 : 4)) % 16 == 0 && aligned16(A.out) ? 1 : 0;
-    return launch_on_rows(ch, n_wf, stream, A, ch->align_src, dsp_internal_launch_align, "align kernel launch");
+// the one launch of them all: the plan's block with this call's pointers (dsp_internal_plan_fill_args, which the CPU tests check), the
+// route's own, the kernel
+static int launch_kernel_only(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* stream) {
+    const KernelOnlyLaunch& r = kernel_only_launches[ch->kernel_only];
+    KernelOnlyArgs A;
+    dsp_internal_plan_fill_args(ch, io_ptrs, &A);
+    if (r.at_launch) r.at_launch(ch, A);
+    return launch_on_rows(ch, n_wf, stream, A, ch->only_src, r.launch, r.what);
 }
 
 static int launch_scalar(dsp_chain* ch, const IoPtrs* ptrs, int64_t n_wf, void* stream) {
@@ -939,19 +826,7 @@ int dsp_chain_execute(dsp_chain* ch, void* const* io_ptrs, int64_t n_wf, void* s
     if (!on_chain_device.ok) return fail(DSP_ERR_HIP, "hipSetDevice(%d) failed", ch->device);
     (void)hipGetLastError();  // launch checks below report this launch, not a stale error of an unrelated earlier call
     // the first kernel, in the order of dsp_plan_route, that takes this launch's pointers
-    if (kernel_only_applies(ch, DSP_ROUTE_EXTREMA)) return launch_extrema(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_HIST)) return launch_hist(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_THRESH)) return launch_thresh(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_SPECTRUM)) return launch_spectrum(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_SORT)) return launch_sort(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_INTERP)) return launch_interp(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_DENSE)) return launch_dense(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_REFLECT)) return launch_reflect(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_PILEUP)) return launch_pileup(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_PULSES)) return launch_pulses(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_TAILFIT)) return launch_tailfit(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_ALIGN)) return launch_align(ch, io_ptrs, n_wf, stream);
-    if (kernel_only_applies(ch, DSP_ROUTE_SVM)) return launch_svm(ch, io_ptrs, n_wf, stream);
+    if (ch->kernel_only != DSP_ROUTE_VM) return launch_kernel_only(ch, io_ptrs, n_wf, stream);  // (always: the program runs nowhere else; unaligned rows: the kernel's scalar loads)
     if (scalar_applies(ch, io_ptrs)) return launch_scalar(ch, &ptrs, n_wf, stream);
     if (pz_rows_applies(ch, io_ptrs)) return launch_pz_rows(ch, io_ptrs, n_wf, stream);
     if (reduce_applies(ch, io_ptrs)) return launch_reduce(ch, io_ptrs, n_wf, stream);
@@ -1043,50 +918,6 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
         case DSP_ROUTE_SCALAR:
             lds = ch->host.n_sregs * 64 * ((ch->f64 || ch->i64) ? 8 : 4), wpb = 1, b = (int)((n_wf + 63) / 64);
             break;
-        case DSP_ROUTE_HIST: lds = dsp_hist::lds_bytes(ch->hist.m) / 4, wpb = 4, b = (int)((n_wf + 3) / 4); break;
-        case DSP_ROUTE_SPECTRUM: {
-            const int n = ch->spec.len, es = ch->f64 ? 8 : 4;
-            const bool wide = dsp_spectrum::wide(n, es);
-            lds = dsp_spectrum::row_bytes(n, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
-            break;
-        }
-        case DSP_ROUTE_SORT: {
-            const int n = ch->sort.len, es = ch->f64 ? 8 : 4;
-            const bool wide = dsp_sort::wide(n);
-            lds = dsp_sort::padded(n) * es / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
-            break;
-        }
-        case DSP_ROUTE_INTERP: {
-            const int n = ch->interp.len, mode = ch->interp.mode, es = ch->f64 ? 8 : 4;
-            const bool wide = dsp_interp::wide(mode, n, es);
-            lds = dsp_interp::row_bytes(mode, n, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
-            break;
-        }
-        case DSP_ROUTE_REFLECT: {
-            const int n = ch->reflect.len, m = ch->reflect.n_taps, es = ch->f64 ? 8 : 4;
-            const bool wide = dsp_reflect::wide(n, m, es);
-            lds = dsp_reflect::row_bytes(n, m, es) / (wide ? 4 : 1), wpb = 4, b = wide ? (int)n_wf : (int)((n_wf + 3) / 4);
-            break;
-        }
-        case DSP_ROUTE_PILEUP:  // a tile of 64 rows per wavefront, one wavefront a workgroup
-            lds = dsp_pileup::lds_bytes(ch->f64 ? 8 : 4), wpb = 1, b = (int)dsp_pileup::tiles(n_wf);
-            break;
-        case DSP_ROUTE_TAILFIT:  // the same tile, and the table of powers beside it
-            lds = dsp_tailfit::lds_bytes(ch->f64 ? 8 : 4), wpb = 1, b = (int)dsp_tailfit::tiles(n_wf);
-            break;
-        case DSP_ROUTE_DENSE:  // a tile of 64 rows per workgroup; the normalisation alone: a wavefront per row
-            if (ch->dense.m > 0)
-                lds = dsp_dense::lds_bytes(ch->dense.m, ch->f64 ? 8 : 4) / 4, wpb = 4, b = (int)dsp_dense::tiles(n_wf);
-            else
-                lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4);
-            break;
-        case DSP_ROUTE_SVM:  // the dense kernel's tile of 64 rows per workgroup
-            lds = dsp_svm::lds_bytes(ch->svm.len, ch->svm.n_pairs) / 4, wpb = 4, b = (int)dsp_svm::tiles(n_wf);
-            break;
-        case DSP_ROUTE_EXTREMA:
-        case DSP_ROUTE_THRESH:
-        case DSP_ROUTE_PULSES:
-        case DSP_ROUTE_ALIGN:
         case DSP_ROUTE_PZ_ROWS:
         case DSP_ROUTE_REDUCE: lds = 0, wpb = 4, b = (int)((n_wf + 3) / 4); break;
         case DSP_ROUTE_FIR_RUNS: lds = dsp_fir_runs::lds_bytes(ch->runs.m) / 4, wpb = 4, b = runs_blocks(ch, n_wf); break;
@@ -1107,6 +938,11 @@ int dsp_chain_geometry(dsp_chain* ch, int64_t n_wf, int* lds_bytes_per_wave, int
         case DSP_ROUTE_VM:
             lds = ch->lds_bytes_per_wave / ch->host.team;  // (a team of wavefronts shares a row's image)
             wpb = ch->waves_per_block * ch->host.team, b = vm_blocks(ch, n_wf);
+            break;
+        // the kernel-only routes, one case: a row each of the planner's table (no default: a new route without a case is a compiler warning)
+        case DSP_ROUTE_EXTREMA: case DSP_ROUTE_HIST: case DSP_ROUTE_THRESH: case DSP_ROUTE_SPECTRUM: case DSP_ROUTE_SORT: case DSP_ROUTE_INTERP: case DSP_ROUTE_DENSE:
+        case DSP_ROUTE_REFLECT: case DSP_ROUTE_PILEUP: case DSP_ROUTE_PULSES: case DSP_ROUTE_TAILFIT: case DSP_ROUTE_ALIGN: case DSP_ROUTE_SVM:
+            dsp_plan_kernel_only_geometry(ch, n_wf, &lds, &wpb, &b);
             break;
     }
     if (lds_bytes_per_wave) *lds_bytes_per_wave = lds;

@@ -100,53 +100,7 @@ static void note(ChainPlan* ch, const char* fmt, ...) {
     ch->note = buf;
 }
 
-struct PlanCtx;
-// The routes that are no optimisation: ops the interpreter has no case for.  A program that holds one of `opcodes` has the shape `match`
-// accepts, or is refused with `refusal` and the matcher's reason.  (A program never matches two: every shape is exact.)
-struct KernelOnlyRoute {
-    dsp_route route;
-    int opcodes[4];  // (0: none)
-    bool (*match)(const PlanCtx& c, const char** why);
-    const char* refusal;
-};
-static bool match_extrema_shape(const PlanCtx& c, const char** why);
-static bool match_hist_shape(const PlanCtx& c, const char** why);
-static bool match_thresh_shape(const PlanCtx& c, const char** why);
-static bool match_spectrum_shape(const PlanCtx& c, const char** why);
-static bool match_sort_shape(const PlanCtx& c, const char** why);
-static bool match_interp_shape(const PlanCtx& c, const char** why);
-static bool match_dense_shape(const PlanCtx& c, const char** why);
-static bool match_reflect_shape(const PlanCtx& c, const char** why);
-static bool match_pileup_shape(const PlanCtx& c, const char** why);
-static bool match_pulses_shape(const PlanCtx& c, const char** why);
-static bool match_tailfit_shape(const PlanCtx& c, const char** why);
-static bool match_align_shape(const PlanCtx& c, const char** why);
-static bool match_svm_shape(const PlanCtx& c, const char** why);
-static const KernelOnlyRoute kernel_only_routes[] = {
-    {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
-     "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only"},
-    {DSP_ROUTE_HIST, {DSP_OP_HISTOGRAM, DSP_OP_HISTOGRAM_STATS}, match_hist_shape,
-     "DSP_OP_HISTOGRAM / DSP_OP_HISTOGRAM_STATS (histogram, histogram_stats) run on dsp_hist_kernel only"},
-    {DSP_ROUTE_THRESH, {DSP_OP_MULTI_TIME_POINT_THRESH, DSP_OP_TIME_OVER_THRESHOLD}, match_thresh_shape,
-     "DSP_OP_MULTI_TIME_POINT_THRESH / DSP_OP_TIME_OVER_THRESHOLD (multi_time_point_thresh, time_over_threshold) run on dsp_thresh_kernel only"},
-    {DSP_ROUTE_SPECTRUM, {DSP_OP_PSD, DSP_OP_FFT}, match_spectrum_shape, "DSP_OP_PSD / DSP_OP_FFT (psd, fft) run on dsp_spectrum_kernel only"},
-    {DSP_ROUTE_SORT, {DSP_OP_SORT, DSP_OP_SORT}, match_sort_shape, "DSP_OP_SORT (sort) runs on dsp_sort_kernel only"},
-    {DSP_ROUTE_INTERP, {DSP_OP_INTERP_UPSAMPLE, DSP_OP_INTERP_UPSAMPLE}, match_interp_shape,
-     "DSP_OP_INTERP_UPSAMPLE (interpolating_upsampler) runs on dsp_interp_kernel only"},
-    {DSP_ROUTE_DENSE, {DSP_OP_NORMALISE, DSP_OP_DENSE}, match_dense_shape,
-     "DSP_OP_NORMALISE / DSP_OP_DENSE (normalisation_layer, dense_layer_*, classification_layer_*) run on dsp_dense_kernel only"},
-    {DSP_ROUTE_REFLECT, {DSP_OP_REFLECTED_CONVOLVE, DSP_OP_REFLECTED_CONVOLVE}, match_reflect_shape,
-     "DSP_OP_REFLECTED_CONVOLVE (reflected_convolve_wf) runs on dsp_reflect_kernel only"},
-    {DSP_ROUTE_PILEUP, {DSP_OP_RC_CR2, DSP_OP_BI_LEVEL_ZERO_CROSSING}, match_pileup_shape,
-     "DSP_OP_RC_CR2 / DSP_OP_BI_LEVEL_ZERO_CROSSING (rc_cr2, bi_level_zero_crossing_time_points) run on dsp_pileup_kernel only"},
-    {DSP_ROUTE_PULSES, {DSP_OP_PEAK_SNR_THRESHOLD, DSP_OP_MULTI_A_FILTER}, match_pulses_shape,
-     "DSP_OP_PEAK_SNR_THRESHOLD / DSP_OP_MULTI_A_FILTER (peak_snr_threshold, multi_a_filter) run on dsp_pulses_kernel only"},
-    {DSP_ROUTE_TAILFIT, {DSP_OP_LOG_CHECK, DSP_OP_POLY_FIT, DSP_OP_POLY_DIFF, DSP_OP_POLY_EXP_RMS}, match_tailfit_shape,
-     "DSP_OP_LOG_CHECK / DSP_OP_POLY_FIT / DSP_OP_POLY_DIFF / DSP_OP_POLY_EXP_RMS (log_check, poly_fit, poly_diff, poly_exp_rms) run on dsp_tailfit_kernel only"},
-    {DSP_ROUTE_ALIGN, {DSP_OP_INL_CORRECTION, DSP_OP_WF_CENTROID, DSP_OP_WF_ALIGNMENT, DSP_OP_WF_CORRECTION}, match_align_shape,
-     "DSP_OP_INL_CORRECTION / DSP_OP_WF_CENTROID / DSP_OP_WF_ALIGNMENT / DSP_OP_WF_CORRECTION (inl_correction, get_wf_centroid, wf_alignment, wf_correction) run on dsp_align_kernel only"},
-    {DSP_ROUTE_SVM, {DSP_OP_SVM_PREDICT, DSP_OP_SVM_PREDICT}, match_svm_shape, "DSP_OP_SVM_PREDICT (svm_predict) runs on dsp_svm_kernel only"},
-};
+struct KernelOnlyRoute;  // (a row of kernel_only_routes, behind the matchers)
 
 // What the passes of dsp_plan_build share: the caller's program, the plan they fill and the tables one pass leaves for the next.
 struct PlanCtx {
@@ -411,6 +365,40 @@ static bool bind_rows(const PlanCtx& c, const dsp_op& ld, unsigned f32_loop, uns
     return true;
 }
 
+// ---- the bindings of a kernel-only route.  A pointer of the plan's argument block is bound to a binding of the call here and filled in per
+// launch by dsp_internal_plan_fill_args; what nobody binds stays null.  Typed on the member: only a pointer can be bound, and only one of the block.
+template <typename T>
+static void bind(const PlanCtx& c, T*& member, int io, bool raw = false) {
+    ChainPlan* ch = c.ch;
+    const ptrdiff_t at = (const char*)&member - (const char*)&ch->only;
+    if (at < 0 || at + sizeof member > sizeof ch->only) ch->n_bound = DSP_KERNEL_BINDINGS_MAX;  // (no pointer of the block: refused as an overflow is)
+    if (ch->n_bound < DSP_KERNEL_BINDINGS_MAX) ch->bound[ch->n_bound] = {io, (uint16_t)at, raw};  // (io < 0, an operand the op does not have: the pointer stays null)
+    ++ch->n_bound;  // (past the capacity: dsp_plan_build refuses the program)
+}
+// the same for an input whose offset travels in the arguments: the pointer is the binding's as it is handed in
+template <typename T>
+static void bind_raw(const PlanCtx& c, T*& member, int io) {
+    bind(c, member, io, true);
+}
+template <typename T>
+static bool is_bound(const PlanCtx& c, T* const& member) {
+    return c.ch->bound_io(member) >= 0;
+}
+// the rows of a kernel-only route: the one row source of the plan, and the block's wf
+template <typename Args>
+static bool bind_rows(const PlanCtx& c, const dsp_op& ld, unsigned f32_loop, unsigned f64_loop, Args& A, const char** why, const char* type_why) {
+    if (!bind_rows(c, ld, f32_loop, f64_loop, A, c.ch->only_src, why, type_why)) return false;
+    bind_raw(c, A.wf, ld.io);
+    return true;
+}
+// The 16-byte stores of a kernel that has them: launch_on_rows' rule for the loads, on the output side.  The plan vouches for the stride
+// here, once; the call's pointer for the start (dsp_internal_plan_fill_args).
+static void vector_stores(const PlanCtx& c, int32_t& out_vec, void*& out, int64_t out_stride) {
+    if ((out_stride * c.esz) % 16 != 0) return;
+    c.ch->out_vec_at = (int)((const char*)&out_vec - (const char*)&c.ch->only);
+    c.ch->out_ptr_at = (int)((const char*)&out - (const char*)&c.ch->only);
+}
+
 // Operand k of `o`, a per-event value: a constant (`value`, as the loop receives it) or a column of the loop's type (`binding`, `stride`)
 static bool bind_operand(const PlanCtx& c, const dsp_op& o, int k, int& binding, int64_t& stride, double& value) {
     const dsp_scalar_arg& a = o.sp[k];
@@ -422,6 +410,14 @@ static bool bind_operand(const PlanCtx& c, const dsp_op& o, int k, int& binding,
     } else {
         return false;
     }
+    return true;
+}
+// (the column bound to a pointer of the kernel-only block; `raw`: as bind_raw)
+template <typename T>
+static bool bind_operand(const PlanCtx& c, const dsp_op& o, int k, T*& column, int64_t& stride, double& value, bool raw = false) {
+    int binding = -1;
+    if (!bind_operand(c, o, k, binding, stride, value)) return false;
+    if (binding >= 0) bind(c, column, binding, raw);
     return true;
 }
 
@@ -450,30 +446,26 @@ static bool match_extrema_shape(const PlanCtx& c, const char** why) {
         ops[3].opcode != DSP_OP_STORE || ops[4].opcode != DSP_OP_STORE_SCALAR || ops[5].opcode != DSP_OP_STORE_SCALAR)
         return false;
     const dsp_op &ld = ops[0], &ex = ops[1];
-    ExtremaArgs& A = ch->ext;
-    memset(&A, 0, sizeof A);
-    if (ex.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64_LOOP, A, ch->ext_src, why,
+    ExtremaArgs& A = ch->only.ext;
+    if (ex.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64_LOOP, A, why,
                                        "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64, int32 or uint32 rows"))
         return false;
     *why = "the two lists are stored once each, the two counts once each into DSP_U32 columns";
-    for (int k = 0; k < 2; ++k) ch->xio_vt[k] = ch->xio_n[k] = -1;
     for (int i = 2; i < 4; ++i) {
         const int which = ops[i].src == ex.dst ? 0 : (ops[i].src == ex.ip[1] ? 1 : -1);
-        if (which < 0 || ch->xio_vt[which] >= 0) return false;
-        ch->xio_vt[which] = ops[i].io;
+        if (which < 0 || is_bound(c, A.vt_out[which])) return false;
+        bind(c, A.vt_out[which], ops[i].io);
         A.vt_stride[which] = io[ops[i].io].row_stride;
     }
     for (int i = 4; i < 6; ++i) {
         const int which = ops[i].ip[0] - ex.ip[2];
-        if (which < 0 || which > 1 || ch->xio_n[which] >= 0 || io[ops[i].io].dtype != DSP_U32) return false;
-        ch->xio_n[which] = ops[i].io;
+        if (which < 0 || which > 1 || is_bound(c, A.n_out[which]) || io[ops[i].io].dtype != DSP_U32) return false;
+        bind(c, A.n_out[which], ops[i].io);
         A.n_stride[which] = io[ops[i].io].row_stride;
     }
     *why = "a parameter is a constant or a per-event column of the loop's type";
-    for (int k = 0; k < 4; ++k) {
-        ch->xio_par[k] = -1;
-        if (!bind_operand(c, ex, k, ch->xio_par[k], A.par_stride[k], A.par_const[k])) return false;
-    }
+    for (int k = 0; k < 4; ++k)
+        if (!bind_operand(c, ex, k, A.par[k], A.par_stride[k], A.par_const[k])) return false;
     A.m = c.slot_len[ex.dst];
     A.direction = ex.ip[0];
     return true;
@@ -502,10 +494,7 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
         if (!is(i, DSP_OP_STORE)) return false;
     for (int i = first_scalar; i < n; ++i)
         if (!is(i, DSP_OP_STORE_SCALAR)) return false;
-    HistArgs& A = ch->hist;
-    memset(&A, 0, sizeof A);
-    ch->hio_w = ch->hio_b = ch->hio_w_in = ch->hio_e_in = ch->hio_max_in = -1;
-    for (int k = 0; k < 3; ++k) ch->hio_s[k] = -1;
+    HistArgs& A = ch->only.hist;
     const dsp_op* st = nullptr;
     if (alone) {
         st = &ops[2];
@@ -515,17 +504,17 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
         *why = "histogram_stats alone reads weights and edges as rows of the loop's type";
         for (const dsp_op* l : {lw, le})
             if (l->ip[0] != 0 || l->ip[1] != 0 || io[l->io].dtype != c.compute_dtype) return false;
-        ch->hio_w_in = lw->io;
-        ch->hio_e_in = le->io;
+        bind_raw(c, A.w_in, lw->io);
+        bind_raw(c, A.e_in, le->io);
         A.w_in_stride = io[lw->io].row_stride;
         A.w_in_offset = io[lw->io].offset;
         A.e_in_stride = io[le->io].row_stride;
         A.e_in_offset = io[le->io].offset;
         A.m = c.slot_len[st->src];
-        ch->hist_src.dtype = c.compute_dtype;
+        ch->only_src.dtype = c.compute_dtype;
     } else {
         const dsp_op &ld = ops[0], &hi = ops[1];
-        if (hi.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->hist_src, why,
+        if (hi.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                                            "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
             return false;
         *why = "histogram_stats in the same program reads exactly the histogram's weights and borders";
@@ -535,9 +524,9 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
         }
         *why = "the weights and the borders are stored once each";
         for (int i = first_store; i < first_store + n_stores; ++i) {
-            int& slot = ops[i].src == hi.dst ? ch->hio_w : ch->hio_b;
-            if ((ops[i].src != hi.dst && ops[i].src != hi.ip[0]) || slot >= 0) return false;
-            slot = ops[i].io;
+            void*& out = ops[i].src == hi.dst ? A.w_out : A.b_out;
+            if ((ops[i].src != hi.dst && ops[i].src != hi.ip[0]) || is_bound(c, out)) return false;
+            bind(c, out, ops[i].io);
             (ops[i].src == hi.dst ? A.w_stride : A.b_stride) = io[ops[i].io].row_stride;
         }
         A.m = c.slot_len[hi.dst];
@@ -547,12 +536,12 @@ static bool match_hist_shape(const PlanCtx& c, const char** why) {
         *why = "mode_out, max_out and fwhm_out are stored once each, in the loop's type";
         for (int i = first_scalar; i < n; ++i) {
             const int which = ops[i].ip[0] - st->ip[1];
-            if (which < 0 || which > 2 || ch->hio_s[which] >= 0 || io[ops[i].io].dtype != c.compute_dtype) return false;
-            ch->hio_s[which] = ops[i].io;
+            if (which < 0 || which > 2 || is_bound(c, A.s_out[which]) || io[ops[i].io].dtype != c.compute_dtype) return false;
+            bind(c, A.s_out[which], ops[i].io);
             A.s_stride[which] = io[ops[i].io].row_stride;
         }
         *why = "max_in is a constant or a per-event column of the loop's type";
-        if (!bind_operand(c, *st, 0, ch->hio_max_in, A.max_in_stride, A.max_in_const)) return false;
+        if (!bind_operand(c, *st, 0, A.max_in, A.max_in_stride, A.max_in_const)) return false;
         A.stats = 1;
     }
     return true;
@@ -576,38 +565,37 @@ static bool match_thresh_shape(const PlanCtx& c, const char** why) {
     if (!tot && !one_list && !lists) return false;
     const dsp_op& op = ops[lists ? 2 : 1];
     const dsp_op* ld = ops[0].dst == op.src ? &ops[0] : (lists && ops[1].dst == op.src ? &ops[1] : nullptr);
-    ThreshArgs& A = ch->thresh;
-    memset(&A, 0, sizeof A);
-    ch->tio_thr = ch->tio_ts = ch->tio_out = -1;
-    if (!ld || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, ch->thresh_src, why,
+    ThreshArgs& A = ch->only.thresh;
+    if (!ld || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                           "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     const dsp_op& st = ops[n - 1];
     if (tot) {
         *why = "the threshold is a constant or a per-event column of the loop's type; the count is stored once, in the loop's type";
-        if (!bind_operand(c, op, 0, ch->tio_thr, A.thr_stride, A.thr_const) || st.ip[0] != op.dst || io[st.io].dtype != c.compute_dtype) return false;
+        // (raw, as the lists below: A.thr is one pointer for both ops, and the kernel reads time_over_threshold's column from it as it is handed in)
+        if (!bind_operand(c, op, 0, A.thr, A.thr_stride, A.thr_const, true) || st.ip[0] != op.dst || io[st.io].dtype != c.compute_dtype) return false;
         A.m = 0;
     } else {
         *why = "the thresholds are one list for every row (the op's DSP_IO_TAPS binding, ip[1] < 0) or a list per row, loaded into slot ip[1], in the loop's type";
         if (lists) {
             const dsp_op* lt = ld == &ops[0] ? &ops[1] : &ops[0];
             if (op.ip[1] != lt->dst || lt->dst == op.src || lt->ip[0] != 0 || lt->ip[1] != 0 || io[lt->io].dtype != c.compute_dtype) return false;
-            ch->tio_thr = lt->io;
+            bind_raw(c, A.thr, lt->io);
             A.thr_stride = io[lt->io].row_stride;
             A.thr_offset = io[lt->io].offset;
         } else {
             if (op.ip[1] >= 0 || !need_io(c, op, DSP_IO_TAPS) || io[op.io].len != c.slot_len[op.dst]) return false;
-            ch->tio_thr = op.io;
+            bind_raw(c, A.thr, op.io);
             A.thr_stride = 0;
             A.thr_offset = io[op.io].offset;
         }
         *why = "t_start is a constant or a per-event column of the loop's type; t_out is stored once, in the loop's type";
-        if (!bind_operand(c, op, 0, ch->tio_ts, A.ts_stride, A.ts_const) || st.src != op.dst || io[st.io].dtype != c.compute_dtype) return false;
+        if (!bind_operand(c, op, 0, A.ts, A.ts_stride, A.ts_const) || st.src != op.dst || io[st.io].dtype != c.compute_dtype) return false;
         A.m = c.slot_len[op.dst];
         A.polarity = op_const(c, op, 1) > 0 ? 1 : -1;
         A.mode = op.ip[0];
     }
-    ch->tio_out = st.io;
+    bind(c, A.out, st.io);
     A.out_stride = io[st.io].row_stride;
     return true;
 }
@@ -624,10 +612,8 @@ static bool match_spectrum_shape(const PlanCtx& c, const char** why) {
         ops[2].opcode != DSP_OP_STORE)
         return false;
     const dsp_op &ld = ops[0], &op = ops[1], &st = ops[2];
-    SpectrumArgs& A = ch->spec;
-    memset(&A, 0, sizeof A);
-    ch->sio_out = -1;
-    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->spec_src, why,
+    SpectrumArgs& A = ch->only.spec;
+    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                                        "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     *why = "the spectrum is stored once, in the loop's type";
@@ -638,7 +624,7 @@ static bool match_spectrum_shape(const PlanCtx& c, const char** why) {
     for (A.log2_points = 0; (1 << A.log2_points) < A.points; ++A.log2_points) {}
     A.bluestein = dsp_spectrum::pow2(A.len) ? 0 : 1;
     A.wide = dsp_spectrum::wide(A.len, c.esz) ? 1 : 0;
-    ch->sio_out = st.io;
+    bind(c, A.out, st.io);
     A.out_stride = c.io[st.io].row_stride;
     return true;
 }
@@ -652,10 +638,8 @@ static bool match_sort_shape(const PlanCtx& c, const char** why) {
     *why = "the program must be exactly LOAD, SORT, STORE";
     if (c.n_ops != 3 || c.n_slots != 2 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_SORT || ops[2].opcode != DSP_OP_STORE) return false;
     const dsp_op &ld = ops[0], &op = ops[1], &st = ops[2];
-    SortArgs& A = ch->sort;
-    memset(&A, 0, sizeof A);
-    ch->oio_out = -1;
-    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->sort_src, why,
+    SortArgs& A = ch->only.sort;
+    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                                        "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     *why = "the sorted row is stored once, whole, in the loop's type";
@@ -663,7 +647,7 @@ static bool match_sort_shape(const PlanCtx& c, const char** why) {
     if (st.src != op.dst || o.dtype != c.compute_dtype || o.len != A.len) return false;
     A.padded = dsp_sort::padded(A.len);
     A.wide = dsp_sort::wide(A.len) ? 1 : 0;
-    ch->oio_out = st.io;
+    bind(c, A.out, st.io);
     A.out_stride = o.row_stride;
     return true;
 }
@@ -678,10 +662,8 @@ static bool match_interp_shape(const PlanCtx& c, const char** why) {
     if (c.n_ops != 3 || c.n_slots != 2 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_INTERP_UPSAMPLE || ops[2].opcode != DSP_OP_STORE)
         return false;
     const dsp_op &ld = ops[0], &op = ops[1], &st = ops[2];
-    InterpArgs& A = ch->interp;
-    memset(&A, 0, sizeof A);
-    ch->iuo_out = -1;
-    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->interp_src, why,
+    InterpArgs& A = ch->only.interp;
+    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                                        "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     *why = "the resampled row is stored once, whole, in the loop's type";
@@ -690,8 +672,9 @@ static bool match_interp_shape(const PlanCtx& c, const char** why) {
     A.out_len = o.len;
     A.mode = op.ip[0];
     A.wide = dsp_interp::wide(A.mode, A.len, c.esz) ? 1 : 0;
-    ch->iuo_out = st.io;
+    bind(c, A.out, st.io);
     A.out_stride = o.row_stride;
+    vector_stores(c, A.out_vec, A.out, A.out_stride);
     return true;
 }
 
@@ -714,11 +697,9 @@ static bool match_dense_shape(const PlanCtx& c, const char** why) {
     const bool classify = dense && dense->ip[3] == 0;
     if (st.opcode != (classify ? DSP_OP_STORE_SCALAR : DSP_OP_STORE) || c.n_slots != (dense && !classify ? 2 : 1)) return false;
     const dsp_op& ld = ops[0];
-    DenseArgs& A = ch->dense;
-    memset(&A, 0, sizeof A);
-    ch->eio_w = ch->eio_b = ch->eio_mean = ch->eio_var = ch->eio_out = -1;
+    DenseArgs& A = ch->only.dense;
     if ((norm && norm->src != ld.dst) || (dense && dense->src != ld.dst) ||
-        !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->dense_src, why, "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
+        !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, why, "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     *why = "the result is stored once, whole, in the loop's type";
     const dsp_io_desc& o = c.io[st.io];
@@ -726,16 +707,16 @@ static bool match_dense_shape(const PlanCtx& c, const char** why) {
     if (classify ? st.ip[0] != dense->dst : (st.src != (dense ? dense->dst : ld.dst) || o.len != (dense ? dense->ip[3] : A.len))) return false;
     if (norm) {
         A.normalise = 1;
-        ch->eio_mean = norm->io;
-        ch->eio_var = norm->ip[0];
+        bind(c, A.means, norm->io);
+        bind(c, A.variances, norm->ip[0]);
     }
     if (dense) {
         A.m = classify ? 1 : dense->ip[3];
         A.activation = dense->ip[0];
-        ch->eio_w = dense->io;
-        ch->eio_b = dense->ip[1];
+        bind(c, A.weights, dense->io);
+        bind(c, A.bias, dense->ip[1]);
     }
-    ch->eio_out = st.io;
+    bind(c, A.out, st.io);
     A.out_stride = o.row_stride;
     return true;
 }
@@ -749,9 +730,8 @@ static bool match_svm_shape(const PlanCtx& c, const char** why) {
     *why = "the program must be exactly LOAD, SVM_PREDICT, STORE_SCALAR";
     if (c.n_ops != 3 || c.n_slots != 1 || ops[0].opcode != DSP_OP_LOAD || ops[1].opcode != DSP_OP_SVM_PREDICT || ops[2].opcode != DSP_OP_STORE_SCALAR) return false;
     const dsp_op &ld = ops[0], &op = ops[1], &st = ops[2];
-    SvmArgs& A = ch->svm;
-    memset(&A, 0, sizeof A);
-    if (op.src != ld.dst || !bind_rows(c, ld, 1u << DSP_F32, ROWS_F64 | 1u << DSP_F32, A, ch->svm_src, why,
+    SvmArgs& A = ch->only.svm;
+    if (op.src != ld.dst || !bind_rows(c, ld, 1u << DSP_F32, ROWS_F64 | 1u << DSP_F32, A, why,
                                        "the float32 loop takes float32 rows, the float64 loop float32 or float64 rows"))
         return false;
     *why = "the label is stored once, in the loop's type";
@@ -764,14 +744,15 @@ static bool match_svm_shape(const PlanCtx& c, const char** why) {
     A.f64 = c.f64 ? 1 : 0;
     A.gamma = op.sp[0].value;
     A.label_stride = o.row_stride;
-    ch->vio_sv = op.io;
-    ch->vio_norm = op.ip[0];
-    ch->vio_coef = op.ip[1];
-    ch->vio_icpt = op.ip[2];
-    ch->vio_cls = op.ip[3];
-    ch->vio_label = st.io;
-    ch->vio_dec = (int)op.sp[2].value;
-    if (ch->vio_dec >= 0) A.dec_stride = c.io[ch->vio_dec].row_stride;
+    bind(c, A.sv, op.io);
+    bind(c, A.sv_norm, op.ip[0]);
+    bind(c, A.coef, op.ip[1]);
+    bind(c, A.intercept, op.ip[2]);
+    bind(c, A.classes, op.ip[3]);
+    bind(c, A.label, st.io);
+    const int dec = (int)op.sp[2].value;
+    bind(c, A.dec, dec);
+    if (dec >= 0) A.dec_stride = c.io[dec].row_stride;
     return true;
 }
 
@@ -792,10 +773,8 @@ static bool match_reflect_shape(const PlanCtx& c, const char** why) {
     for (int i = first_store; i < n; ++i)
         if (!is(i, DSP_OP_STORE)) return false;
     const dsp_op &ld = ops[0], &op = ops[1];
-    ReflectArgs& A = ch->reflect;
-    memset(&A, 0, sizeof A);
-    ch->rio_taps = ch->rio_out = ch->rio_cur = -1;
-    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->reflect_src, why,
+    ReflectArgs& A = ch->only.reflect;
+    if (op.src != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                                        "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     if (fused) {
@@ -811,16 +790,17 @@ static bool match_reflect_shape(const PlanCtx& c, const char** why) {
         const dsp_op& st = ops[i];
         const dsp_io_desc& o = c.io[st.io];
         const bool current = fused && st.src == ops[2].dst;
-        int& slot = current ? ch->rio_cur : ch->rio_out;
-        if ((!current && st.src != op.dst) || slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
-        slot = st.io;
+        void*& out = current ? A.cur : A.out;
+        if ((!current && st.src != op.dst) || is_bound(c, out) || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        bind(c, out, st.io);
         (current ? A.cur_stride : A.out_stride) = o.row_stride;
     }
-    if (fused && ch->rio_cur < 0) return false;
+    if (fused && !is_bound(c, A.cur)) return false;
     A.n_taps = c.io[op.io].len;
     A.taps_nan = op.ip[0] & 1;
     A.wide = dsp_reflect::wide(A.len, A.n_taps, c.esz) ? 1 : 0;
-    ch->rio_taps = op.io;
+    bind(c, A.taps, op.io);
+    vector_stores(c, A.out_vec, A.out, A.out_stride);
     return true;
 }
 
@@ -852,17 +832,14 @@ static bool match_pileup_shape(const PlanCtx& c, const char** why) {
     const dsp_op& ld = ops[0];
     const dsp_op* fi = filter ? &ops[first] : nullptr;
     const dsp_op* wk = walk ? &ops[filter ? first + 1 : first] : nullptr;
-    PileupArgs& A = ch->pileup;
-    memset(&A, 0, sizeof A);
-    ch->lio_out = ch->lio_list[0] = ch->lio_list[1] = ch->lio_n = ch->lio_sub = -1;
-    for (int k = 0; k < 4; ++k) ch->lio_par[k] = -1;
-    if ((fi ? fi->src : wk->src) != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, ch->pileup_src, why,
+    PileupArgs& A = ch->only.pileup;
+    if ((fi ? fi->src : wk->src) != ld.dst || !bind_rows(c, ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                                                         "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     if (first == 2) {
         const dsp_op& bs = ops[1];
         *why = "the BL_SUBTRACT behind the LOAD works on the rows in place (bl_subtract, ip[0] = 0), its baseline a constant or a per-event column of the loop's type";
-        if (bs.dst != ld.dst || bs.src != ld.dst || bs.ip[0] != 0 || !bind_operand(c, bs, 0, ch->lio_sub, A.sub_stride, A.sub_const)) return false;
+        if (bs.dst != ld.dst || bs.src != ld.dst || bs.ip[0] != 0 || !bind_operand(c, bs, 0, A.sub, A.sub_stride, A.sub_const)) return false;
         A.sub_mode = 1;
     }
     *why = "the walk in the same program reads exactly the filtered row";
@@ -871,24 +848,25 @@ static bool match_pileup_shape(const PlanCtx& c, const char** why) {
     for (int i = first_store; i < first_store + n_stores; ++i) {
         const dsp_op& st = ops[i];
         const dsp_io_desc& o = io[st.io];
-        int* slot = fi && st.src == fi->dst ? &ch->lio_out : (wk && st.src == wk->dst ? &ch->lio_list[0] : (wk && st.src == wk->ip[0] ? &ch->lio_list[1] : nullptr));
-        if (!slot || *slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
-        *slot = st.io;
-        if (slot == &ch->lio_out) A.out_stride = o.row_stride;
-        else A.list_stride[slot == &ch->lio_list[0] ? 0 : 1] = o.row_stride;
+        void** out = fi && st.src == fi->dst ? &A.out : (wk && st.src == wk->dst ? &A.list[0] : (wk && st.src == wk->ip[0] ? &A.list[1] : nullptr));
+        if (!out || is_bound(c, *out) || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        bind(c, *out, st.io);
+        if (out == &A.out) A.out_stride = o.row_stride;
+        else A.list_stride[out == &A.list[0] ? 0 : 1] = o.row_stride;
     }
     if (wk) {
         const dsp_op& sc = ops[n - 1];
-        if (ch->lio_list[0] < 0 || ch->lio_list[1] < 0 || ch->lio_list[0] == ch->lio_list[1] || ch->lio_list[0] == ch->lio_out || ch->lio_list[1] == ch->lio_out ||
+        const int list0 = ch->bound_io(A.list[0]), list1 = ch->bound_io(A.list[1]), row = ch->bound_io(A.out);
+        if (list0 < 0 || list1 < 0 || list0 == list1 || list0 == row || list1 == row ||
             sc.ip[0] != wk->ip[1] || io[sc.io].dtype != DSP_U32)  // (every output its own binding)
             return false;
-        ch->lio_n = sc.io;
+        bind(c, A.n_out, sc.io);
         A.n_stride = io[sc.io].row_stride;
         *why = "a threshold, the gate and t_start are constants or per-event columns of the loop's type";
         for (int k = 0; k < 4; ++k)
-            if (!bind_operand(c, *wk, k, ch->lio_par[k], A.par_stride[k], A.par_const[k])) return false;
+            if (!bind_operand(c, *wk, k, A.par[k], A.par_stride[k], A.par_const[k])) return false;
         A.m = c.slot_len[wk->dst];
-    } else if (ch->lio_out < 0) {
+    } else if (!is_bound(c, A.out)) {
         return false;
     }
     if (fi) {  // rc_cr2.py:66-71 with numba's typing: -1 / t_tau in float64 whatever the loop, the powers as products
@@ -900,6 +878,7 @@ static bool match_pileup_shape(const PlanCtx& c, const char** why) {
     }
     A.filter = fi ? 1 : 0;
     A.walk = wk ? 1 : 0;
+    vector_stores(c, A.out_vec, A.out, A.out_stride);
     return true;
 }
 
@@ -930,17 +909,15 @@ static bool match_pulses_shape(const PlanCtx& c, const char** why) {
     const dsp_op* am = amp ? &ops[pick ? 3 : 2] : nullptr;
     const dsp_op& first = pk ? *pk : *am;
     const dsp_op* ld = ops[0].dst == first.src ? &ops[0] : (ops[1].dst == first.src ? &ops[1] : nullptr);
-    PulsesArgs& A = ch->pulses;
-    memset(&A, 0, sizeof A);
-    ch->uio_list = ch->uio_ratio = ch->uio_idx = ch->uio_n = ch->uio_amp = -1;
-    if (!ld || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, ch->pulses_src, why,
+    PulsesArgs& A = ch->only.pulses;
+    if (!ld || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                           "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     *why = "the list is loaded whole into slot ip[0], a list per row in the loop's type";
     const dsp_op* lt = ld == &ops[0] ? &ops[1] : &ops[0];
     if (first.ip[0] != lt->dst || lt->dst == first.src || lt->ip[0] != 0 || lt->ip[1] != 0 || io[lt->io].dtype != c.compute_dtype || io[lt->io].len != c.slot_len[lt->dst])
         return false;
-    ch->uio_list = lt->io;
+    bind_raw(c, A.list, lt->io);
     A.list_stride = io[lt->io].row_stride;
     A.list_offset = io[lt->io].offset;
     *why = "multi_a_filter in the same program reads the same row at exactly the picker's idx_out";
@@ -949,19 +926,19 @@ static bool match_pulses_shape(const PlanCtx& c, const char** why) {
     for (int i = first_store; i < first_store + n_stores; ++i) {
         const dsp_op& st = ops[i];
         const dsp_io_desc& o = io[st.io];
-        int* slot = pk && st.src == pk->dst ? &ch->uio_idx : (am && st.src == am->dst ? &ch->uio_amp : nullptr);
-        if (!slot || *slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
-        *slot = st.io;
-        (slot == &ch->uio_idx ? A.idx_stride : A.amp_stride) = o.row_stride;
+        void** out = pk && st.src == pk->dst ? &A.idx_out : (am && st.src == am->dst ? &A.amp_out : nullptr);
+        if (!out || is_bound(c, *out) || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        bind(c, *out, st.io);
+        (out == &A.idx_out ? A.idx_stride : A.amp_stride) = o.row_stride;
     }
-    if ((am && ch->uio_amp < 0) || (!am && ch->uio_idx < 0) || (ch->uio_idx >= 0 && ch->uio_idx == ch->uio_amp)) return false;
+    if ((am && !is_bound(c, A.amp_out)) || (!am && !is_bound(c, A.idx_out)) || (is_bound(c, A.idx_out) && ch->bound_io(A.idx_out) == ch->bound_io(A.amp_out))) return false;
     if (pk) {
         const dsp_op& sc = ops[n - 1];
         if (sc.ip[0] != pk->ip[1] || io[sc.io].dtype != DSP_U32) return false;
-        ch->uio_n = sc.io;
+        bind(c, A.n_out, sc.io);
         A.n_stride = io[sc.io].row_stride;
         *why = "ratio_in is a constant or a per-event column of the loop's type";
-        if (!bind_operand(c, *pk, 0, ch->uio_ratio, A.ratio_stride, A.ratio_const)) return false;
+        if (!bind_operand(c, *pk, 0, A.ratio, A.ratio_stride, A.ratio_const)) return false;
         A.width = dsp_pulses::clamped_width(op_const(c, *pk, 1), A.len);
     }
     A.m = c.slot_len[first.ip[0]];
@@ -1010,15 +987,13 @@ static bool match_tailfit_shape(const PlanCtx& c, const char** why) {
     const dsp_op& first = lg ? *lg : (ft ? *ft : *rs);
     const dsp_op* ld = ops[0].dst == first.src ? &ops[0] : (ld2 && ld2->dst == first.src ? ld2 : nullptr);
     const dsp_op* lp = ld2 ? (ld == &ops[0] ? ld2 : &ops[0]) : nullptr;
-    TailfitArgs& A = ch->tailfit;
-    memset(&A, 0, sizeof A);
-    ch->aio_sub = ch->aio_inv = ch->aio_pars = ch->aio_out = ch->aio_pars_out = ch->aio_mean = ch->aio_rms = -1;
-    if (!ld || (!ld2 && ld != &ops[0]) || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, ch->tailfit_src, why,
+    TailfitArgs& A = ch->only.tailfit;
+    if (!ld || (!ld2 && ld != &ops[0]) || !bind_rows(c, *ld, ROWS_F32_LOOP, ROWS_F64, A, why,
                                                      "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows"))
         return false;
     if (bs) {
         *why = "the BL_SUBTRACT behind the LOAD works on the rows in place (bl_subtract, ip[0] = 0), its baseline a constant or a per-event column of the loop's type";
-        if (bs->dst != ld->dst || bs->src != ld->dst || bs->ip[0] != 0 || !bind_operand(c, *bs, 0, ch->aio_sub, A.sub_stride, A.sub_const)) return false;
+        if (bs->dst != ld->dst || bs->src != ld->dst || bs->ip[0] != 0 || !bind_operand(c, *bs, 0, A.sub, A.sub_stride, A.sub_const)) return false;
         A.sub_mode = 1;
     }
     *why = "poly_fit in the same program reads exactly the logged row; the residuals the row as loaded or the logged row, with exactly the fitted coefficients";
@@ -1028,7 +1003,7 @@ static bool match_tailfit_shape(const PlanCtx& c, const char** why) {
         *why = "the coefficients are loaded whole into slot ip[0], a row of them per event in the loop's type";
         if (rs->ip[0] != lp->dst || lp->dst == rs->src || lp->ip[0] != 0 || lp->ip[1] != 0 || io[lp->io].dtype != c.compute_dtype || io[lp->io].len != c.slot_len[lp->dst])
             return false;
-        ch->aio_pars = lp->io;
+        bind_raw(c, A.pars, lp->io);
         A.pars_stride = io[lp->io].row_stride;
         A.pars_offset = io[lp->io].offset;
     }
@@ -1036,28 +1011,29 @@ static bool match_tailfit_shape(const PlanCtx& c, const char** why) {
     for (int i = first_store; i < first_store + n_stores; ++i) {
         const dsp_op& st = ops[i];
         const dsp_io_desc& o = io[st.io];
-        int* slot = lg && st.src == lg->dst ? &ch->aio_out : (ft && st.src == ft->dst ? &ch->aio_pars_out : nullptr);
-        if (!slot || *slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
-        *slot = st.io;
-        (slot == &ch->aio_out ? A.out_stride : A.pars_out_stride) = o.row_stride;
+        void** out = lg && st.src == lg->dst ? &A.out : (ft && st.src == ft->dst ? &A.pars_out : nullptr);
+        if (!out || is_bound(c, *out) || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        bind(c, *out, st.io);
+        (out == &A.out ? A.out_stride : A.pars_out_stride) = o.row_stride;
     }
-    if ((lg && !ft && ch->aio_out < 0) || (ft && !rs && ch->aio_pars_out < 0) || (ch->aio_out >= 0 && ch->aio_out == ch->aio_pars_out)) return false;
+    if ((lg && !ft && !is_bound(c, A.out)) || (ft && !rs && !is_bound(c, A.pars_out)) || (is_bound(c, A.out) && ch->bound_io(A.out) == ch->bound_io(A.pars_out))) return false;
     if (rs) {
         const dsp_op &s0 = ops[n - 2], &s1 = ops[n - 1];
         const dsp_op* mean = s0.ip[0] == rs->dst ? &s0 : (s1.ip[0] == rs->dst ? &s1 : nullptr);
         const dsp_op* rms = s0.ip[0] == rs->dst + 1 ? &s0 : (s1.ip[0] == rs->dst + 1 ? &s1 : nullptr);
         if (!mean || !rms || mean == rms || mean->io == rms->io || io[mean->io].dtype != c.compute_dtype || io[rms->io].dtype != c.compute_dtype) return false;
-        ch->aio_mean = mean->io;
-        ch->aio_rms = rms->io;
+        bind(c, A.mean_out, mean->io);
+        bind(c, A.rms_out, rms->io);
         A.mean_stride = io[mean->io].row_stride;
         A.rms_stride = io[rms->io].row_stride;
         A.resid = rs->opcode == DSP_OP_POLY_EXP_RMS ? 2 : 1;
         A.resid_log = lg && rs->src == lg->dst ? 1 : 0;
     }
-    if (ft) ch->aio_inv = ft->io;
+    if (ft) bind(c, A.inv, ft->io);
     A.m = ft ? c.slot_len[ft->dst] : (rs ? c.slot_len[rs->ip[0]] : 0);
     A.log = lg ? 1 : 0;
     A.fit = ft ? 1 : 0;
+    vector_stores(c, A.out_vec, A.out, A.out_stride);
     return true;
 }
 
@@ -1083,9 +1059,7 @@ static bool match_align_shape(const PlanCtx& c, const char** why) {
     if (op.src != ld.dst || (cr ? n_stores != 1 && n_stores != 2 : n_stores != 1) || c.n_slots != (is(1, DSP_OP_WF_CENTROID) ? 1 : (cr ? 3 : 2))) return false;
     for (int i = first_store; i < n; ++i)
         if (!is(i, is(1, DSP_OP_WF_CENTROID) ? DSP_OP_STORE_SCALAR : DSP_OP_STORE)) return false;
-    AlignArgs& A = ch->align;
-    memset(&A, 0, sizeof A);
-    ch->gio_table = ch->gio_centroid = ch->gio_out = ch->gio_out2 = ch->gio_scalar = -1;
+    AlignArgs& A = ch->only.align;
     constexpr unsigned INTS = 1u << DSP_I16 | 1u << DSP_U16 | 1u << DSP_I32 | 1u << DSP_U32;
     unsigned f32_rows = ROWS_F32_LOOP, f64_rows = ROWS_F64;
     const char* type_why = "the float32 loop takes float32, int16 or uint16 rows, the float64 loop float64 rows";
@@ -1104,26 +1078,26 @@ static bool match_align_shape(const PlanCtx& c, const char** why) {
         case DSP_OP_WF_CORRECTION: A.mode = DSP_ALIGN_CORRECT; break;
         default: return false;
     }
-    if (!bind_rows(c, ld, f32_rows, f64_rows, A, ch->align_src, why, type_why)) return false;
+    if (!bind_rows(c, ld, f32_rows, f64_rows, A, why, type_why)) return false;
     A.f64 = c.f64 ? 1 : 0;
     if (A.mode == DSP_ALIGN_CENTROID) {
         const dsp_op& sc = ops[2];
         *why = "the centroid is stored once, into a column of the loop's type";
         if (sc.ip[0] != op.dst || io[sc.io].dtype != c.compute_dtype) return false;
-        ch->gio_scalar = sc.io;
+        bind(c, A.scalar_out, sc.io);
         A.scalar_stride = io[sc.io].row_stride;
         A.shift = op_const(c, op, 0);
         return true;
     }
     if (A.mode == DSP_ALIGN_WINDOW) {
         *why = "centroid is a constant or a per-event column of the loop's type";
-        if (!bind_operand(c, op, 0, ch->gio_centroid, A.centroid_stride, A.centroid_const)) return false;
+        if (!bind_operand(c, op, 0, A.centroid, A.centroid_stride, A.centroid_const)) return false;
         A.shift = op_const(c, op, 1);
         A.size = c.slot_len[op.dst];
     }
     const dsp_op& tb = cr ? *cr : op;  // the op with a table
     if (tb.opcode != DSP_OP_WF_ALIGNMENT) {
-        ch->gio_table = tb.io;
+        bind(c, A.table, tb.io);
         A.table_len = io[tb.io].len;
         A.start = tb.ip[0];
         A.stop = tb.ip[1];
@@ -1135,14 +1109,110 @@ static bool match_align_shape(const PlanCtx& c, const char** why) {
     for (int i = first_store; i < n; ++i) {
         const dsp_op& st = ops[i];
         const dsp_io_desc& o = io[st.io];
-        int* slot = cr && st.src == cr->dst ? &ch->gio_out2 : (st.src == op.dst ? &ch->gio_out : nullptr);
-        if (!slot || *slot >= 0 || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
-        *slot = st.io;
-        (slot == &ch->gio_out ? A.out_stride : A.out2_stride) = o.row_stride;
+        void** out = cr && st.src == cr->dst ? &A.out2 : (st.src == op.dst ? &A.out : nullptr);
+        if (!out || is_bound(c, *out) || o.dtype != c.compute_dtype || o.len != c.slot_len[st.src]) return false;
+        bind(c, *out, st.io);
+        (out == &A.out ? A.out_stride : A.out2_stride) = o.row_stride;
     }
-    if (cr ? ch->gio_out2 < 0 || ch->gio_out2 == ch->gio_out : ch->gio_out < 0) return false;
+    if (cr ? !is_bound(c, A.out2) || ch->bound_io(A.out2) == ch->bound_io(A.out) : !is_bound(c, A.out)) return false;
+    if (A.mode != DSP_ALIGN_WINDOW) vector_stores(c, A.out_vec, A.out, A.out_stride);  // (the outputs the kernel streams: inl_correction's, wf_correction's)
     return true;
 }
+
+// what dsp_chain_geometry reports of a launch: LDS per wavefront, wavefronts per block, blocks for n_wf rows
+struct Geometry {
+    int lds, wpb;
+    int64_t blocks;
+};
+// The routes that are no optimisation: ops the interpreter has no case for, a row per route and everything HIP-free about the route in it.
+// A program that holds one of `opcodes` has the shape `match` accepts, or is refused with `refusal` and the matcher's reason.  (A program
+// never matches two: every shape is exact.)  `lds`: the dynamic LDS of a launch where the kernel's limit may have to be raised for it (null:
+// the route has no limit to raise); `geometry`: the launch as dsp_chain_geometry reports it.  dsp_host.cpp's kernel_only_launches holds
+// the HIP side, a row per route again.
+struct KernelOnlyRoute {
+    dsp_route route;
+    int opcodes[4];  // (0: none)
+    bool (*match)(const PlanCtx& c, const char** why);
+    const char* refusal;
+    int (*lds)(const ChainPlan& p);
+    Geometry (*geometry)(const ChainPlan& p, int64_t n_wf);
+};
+static int loop_esz(const ChainPlan& p) { return p.f64 ? 8 : 4; }
+// a wavefront per row, four rows to a workgroup, `lds` bytes each ...
+static Geometry wave_per_row(int lds, int64_t n_wf) { return {lds, 4, (n_wf + 3) / 4}; }
+// ... or, a row too long for that, a workgroup of four wavefronts per row
+static Geometry row_in_lds(int row_bytes, bool wide, int64_t n_wf) { return wide ? Geometry{row_bytes / 4, 4, n_wf} : wave_per_row(row_bytes, n_wf); }
+static Geometry rows_from_memory(const ChainPlan&, int64_t n_wf) { return wave_per_row(0, n_wf); }
+static constexpr KernelOnlyRoute kernel_only_routes[] = {
+    {DSP_ROUTE_EXTREMA, {DSP_OP_MULTI_EXTREMA, DSP_OP_MULTI_EXTREMA}, match_extrema_shape,
+     "DSP_OP_MULTI_EXTREMA (get_multi_local_extrema) runs on dsp_extrema_kernel only", nullptr, rows_from_memory},
+    {DSP_ROUTE_HIST, {DSP_OP_HISTOGRAM, DSP_OP_HISTOGRAM_STATS}, match_hist_shape,
+     "DSP_OP_HISTOGRAM / DSP_OP_HISTOGRAM_STATS (histogram, histogram_stats) run on dsp_hist_kernel only", nullptr,
+     [](const ChainPlan& p, int64_t n_wf) { return wave_per_row(dsp_hist::lds_bytes(p.only.hist.m) / 4, n_wf); }},
+    {DSP_ROUTE_THRESH, {DSP_OP_MULTI_TIME_POINT_THRESH, DSP_OP_TIME_OVER_THRESHOLD}, match_thresh_shape,
+     "DSP_OP_MULTI_TIME_POINT_THRESH / DSP_OP_TIME_OVER_THRESHOLD (multi_time_point_thresh, time_over_threshold) run on dsp_thresh_kernel only",
+     nullptr, rows_from_memory},
+    {DSP_ROUTE_SPECTRUM, {DSP_OP_PSD, DSP_OP_FFT}, match_spectrum_shape, "DSP_OP_PSD / DSP_OP_FFT (psd, fft) run on dsp_spectrum_kernel only",
+     [](const ChainPlan& p) { return dsp_spectrum::lds_bytes(p.only.spec.len, loop_esz(p)); },
+     [](const ChainPlan& p, int64_t n_wf) {
+         const int n = p.only.spec.len, es = loop_esz(p);
+         return row_in_lds(dsp_spectrum::row_bytes(n, es), dsp_spectrum::wide(n, es), n_wf);
+     }},
+    {DSP_ROUTE_SORT, {DSP_OP_SORT, DSP_OP_SORT}, match_sort_shape, "DSP_OP_SORT (sort) runs on dsp_sort_kernel only",
+     [](const ChainPlan& p) { return dsp_sort::lds_bytes(p.only.sort.len, loop_esz(p)); },
+     [](const ChainPlan& p, int64_t n_wf) {
+         const int n = p.only.sort.len;
+         return row_in_lds(dsp_sort::padded(n) * loop_esz(p), dsp_sort::wide(n), n_wf);
+     }},
+    {DSP_ROUTE_INTERP, {DSP_OP_INTERP_UPSAMPLE, DSP_OP_INTERP_UPSAMPLE}, match_interp_shape,
+     "DSP_OP_INTERP_UPSAMPLE (interpolating_upsampler) runs on dsp_interp_kernel only",
+     [](const ChainPlan& p) { return dsp_interp::lds_bytes(p.only.interp.mode, p.only.interp.len, loop_esz(p)); },
+     [](const ChainPlan& p, int64_t n_wf) {
+         const int n = p.only.interp.len, mode = p.only.interp.mode, es = loop_esz(p);
+         return row_in_lds(dsp_interp::row_bytes(mode, n, es), dsp_interp::wide(mode, n, es), n_wf);
+     }},
+    {DSP_ROUTE_DENSE, {DSP_OP_NORMALISE, DSP_OP_DENSE}, match_dense_shape,
+     "DSP_OP_NORMALISE / DSP_OP_DENSE (normalisation_layer, dense_layer_*, classification_layer_*) run on dsp_dense_kernel only",
+     [](const ChainPlan& p) { return dsp_dense::lds_bytes(p.only.dense.m, loop_esz(p)); },
+     [](const ChainPlan& p, int64_t n_wf) {  // a tile of 64 rows per workgroup; the normalisation alone: a wavefront per row
+         const int m = p.only.dense.m;
+         return m > 0 ? Geometry{dsp_dense::lds_bytes(m, loop_esz(p)) / 4, 4, dsp_dense::tiles(n_wf)} : wave_per_row(0, n_wf);
+     }},
+    {DSP_ROUTE_REFLECT, {DSP_OP_REFLECTED_CONVOLVE, DSP_OP_REFLECTED_CONVOLVE}, match_reflect_shape,
+     "DSP_OP_REFLECTED_CONVOLVE (reflected_convolve_wf) runs on dsp_reflect_kernel only",
+     [](const ChainPlan& p) { return dsp_reflect::lds_bytes(p.only.reflect.len, p.only.reflect.n_taps, loop_esz(p)); },
+     [](const ChainPlan& p, int64_t n_wf) {
+         const int n = p.only.reflect.len, m = p.only.reflect.n_taps, es = loop_esz(p);
+         return row_in_lds(dsp_reflect::row_bytes(n, m, es), dsp_reflect::wide(n, m, es), n_wf);
+     }},
+    {DSP_ROUTE_PILEUP, {DSP_OP_RC_CR2, DSP_OP_BI_LEVEL_ZERO_CROSSING}, match_pileup_shape,
+     "DSP_OP_RC_CR2 / DSP_OP_BI_LEVEL_ZERO_CROSSING (rc_cr2, bi_level_zero_crossing_time_points) run on dsp_pileup_kernel only", nullptr,
+     [](const ChainPlan& p, int64_t n_wf) {  // a tile of 64 rows per wavefront, one wavefront a workgroup
+         return Geometry{dsp_pileup::lds_bytes(loop_esz(p)), 1, dsp_pileup::tiles(n_wf)};
+     }},
+    {DSP_ROUTE_PULSES, {DSP_OP_PEAK_SNR_THRESHOLD, DSP_OP_MULTI_A_FILTER}, match_pulses_shape,
+     "DSP_OP_PEAK_SNR_THRESHOLD / DSP_OP_MULTI_A_FILTER (peak_snr_threshold, multi_a_filter) run on dsp_pulses_kernel only", nullptr, rows_from_memory},
+    {DSP_ROUTE_TAILFIT, {DSP_OP_LOG_CHECK, DSP_OP_POLY_FIT, DSP_OP_POLY_DIFF, DSP_OP_POLY_EXP_RMS}, match_tailfit_shape,
+     "DSP_OP_LOG_CHECK / DSP_OP_POLY_FIT / DSP_OP_POLY_DIFF / DSP_OP_POLY_EXP_RMS (log_check, poly_fit, poly_diff, poly_exp_rms) run on dsp_tailfit_kernel only",
+     nullptr, [](const ChainPlan& p, int64_t n_wf) {  // the pile-up kernel's tile, and the table of powers beside it
+         return Geometry{dsp_tailfit::lds_bytes(loop_esz(p)), 1, dsp_tailfit::tiles(n_wf)};
+     }},
+    {DSP_ROUTE_ALIGN, {DSP_OP_INL_CORRECTION, DSP_OP_WF_CENTROID, DSP_OP_WF_ALIGNMENT, DSP_OP_WF_CORRECTION}, match_align_shape,
+     "DSP_OP_INL_CORRECTION / DSP_OP_WF_CENTROID / DSP_OP_WF_ALIGNMENT / DSP_OP_WF_CORRECTION (inl_correction, get_wf_centroid, wf_alignment, wf_correction) run on dsp_align_kernel only",
+     nullptr, rows_from_memory},
+    {DSP_ROUTE_SVM, {DSP_OP_SVM_PREDICT, DSP_OP_SVM_PREDICT}, match_svm_shape, "DSP_OP_SVM_PREDICT (svm_predict) runs on dsp_svm_kernel only",
+     [](const ChainPlan& p) { return dsp_svm::lds_bytes(p.only.svm.len, p.only.svm.n_pairs); },
+     [](const ChainPlan& p, int64_t n_wf) {  // the dense kernel's tile of 64 rows per workgroup
+         return Geometry{dsp_svm::lds_bytes(p.only.svm.len, p.only.svm.n_pairs) / 4, 4, dsp_svm::tiles(n_wf)};
+     }},
+};
+constexpr bool kernel_only_routes_in_order() {
+    int n = 0;
+    for (const KernelOnlyRoute& r : kernel_only_routes)
+        if (r.route != n++) return false;
+    return n == DSP_KERNEL_ONLY_ROUTES;
+}
+static_assert(kernel_only_routes_in_order(), "a row per kernel-only route, at the route's own index");
 
 // Does the program have the shape of the current-branch kernel (dsp_current.hip)?
 //   LOAD s0;  WINDOWER s1 <- s0 (start: constant or float32 column);  AVG_CURRENT s2 <- s1;  UPSAMPLER s3 <- s2;
@@ -3046,7 +3116,12 @@ int dsp_plan_build(ChainPlan* ch, const dsp_op* ops, int n_ops, const dsp_io_des
     fold_load_bl_subtract(c);
     if (c.only) {  // no interpreter op behind it: its own kernel or nothing
         const char* why = "";
+        memset(&ch->only, 0, sizeof ch->only);  // once, for whichever block the matcher fills: what it binds nothing to stays null
+        ch->n_bound = 0;
+        ch->out_vec_at = ch->out_ptr_at = -1;
         if (!c.only->match(c, &why)) return fail(DSP_ERR_UNSUPPORTED, "%s, on rows in memory: %s", c.only->refusal, why);
+        if (ch->n_bound > DSP_KERNEL_BINDINGS_MAX)
+            return fail(DSP_ERR_UNSUPPORTED, "%s: its shape binds more than %d pointers", c.only->refusal, DSP_KERNEL_BINDINGS_MAX);
         ch->kernel_only = c.only->route;
     }
     match_shapes(c);
@@ -3069,6 +3144,36 @@ dsp_route dsp_plan_route(const ChainPlan* ch) {
     if (ch->rows_ok) return DSP_ROUTE_ROWS;
     if (ch->rr_ok && ch->variant != 1) return DSP_ROUTE_ENERGY_RR;
     return ch->fused_ok ? DSP_ROUTE_ENERGY : DSP_ROUTE_VM;
+}
+
+int dsp_plan_kernel_only_lds(const ChainPlan* ch) {
+    const KernelOnlyRoute* r = ch && ch->kernel_only != DSP_ROUTE_VM ? &kernel_only_routes[ch->kernel_only] : nullptr;
+    return r && r->lds ? r->lds(*ch) : 0;
+}
+
+void dsp_plan_kernel_only_geometry(const ChainPlan* ch, int64_t n_wf, int* lds_bytes_per_wave, int* waves_per_block, int* blocks) {
+    const Geometry g = kernel_only_routes[ch->kernel_only].geometry(*ch, n_wf);
+    *lds_bytes_per_wave = g.lds;
+    *waves_per_block = g.wpb;
+    *blocks = (int)g.blocks;
+}
+
+extern "C" void dsp_internal_plan_fill_args(const ChainPlan* ch, void* const* io_ptrs, KernelOnlyArgs* args) {
+    char* block = (char*)args;
+    memcpy(block, &ch->only, sizeof ch->only);
+    for (int k = 0; k < ch->n_bound; ++k) {
+        const KernelBinding& b = ch->bound[k];
+        if (b.io < 0) continue;
+        const DevIO& d = ch->host.io[b.io];
+        char* p = (char*)io_ptrs[b.io] + (b.raw ? 0 : (int64_t)d.offset * elem_size(d.dtype));
+        memcpy(block + b.at, &p, sizeof p);
+    }
+    if (ch->out_vec_at >= 0) {  // 16-byte stores: the plan has vouched for the stride, this call's pointer does for the start
+        void* out = nullptr;
+        memcpy(&out, block + ch->out_ptr_at, sizeof out);
+        const int32_t on = out && (reinterpret_cast<uintptr_t>(out) & 15u) == 0 ? 1 : 0;
+        memcpy(block + ch->out_vec_at, &on, sizeof on);
+    }
 }
 
 const char* dsp_plan_route_kernel_name(dsp_route route) {

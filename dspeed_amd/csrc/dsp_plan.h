@@ -25,8 +25,44 @@ struct RowSource {
     bool vec = false;
 };
 
+// The argument blocks of the kernel-only routes (dsp_program.h): plain data, and of one plan exactly one is live
+union KernelOnlyArgs {
+    const void* wf;  // (every block begins with its rows)
+    ExtremaArgs ext;
+    HistArgs hist;
+    ThreshArgs thresh;
+    SpectrumArgs spec;
+    SortArgs sort;
+    InterpArgs interp;
+    DenseArgs dense;
+    ReflectArgs reflect;
+    PileupArgs pileup;
+    PulsesArgs pulses;
+    TailfitArgs tailfit;
+    AlignArgs align;
+    SvmArgs svm;
+};
+static_assert(offsetof(ExtremaArgs, wf) == 0 && offsetof(HistArgs, wf) == 0 && offsetof(ThreshArgs, wf) == 0 && offsetof(SpectrumArgs, wf) == 0 &&
+                  offsetof(SortArgs, wf) == 0 && offsetof(InterpArgs, wf) == 0 && offsetof(DenseArgs, wf) == 0 && offsetof(ReflectArgs, wf) == 0 &&
+                  offsetof(PileupArgs, wf) == 0 && offsetof(PulsesArgs, wf) == 0 && offsetof(TailfitArgs, wf) == 0 && offsetof(AlignArgs, wf) == 0 &&
+                  offsetof(SvmArgs, wf) == 0,
+              "wf of KernelOnlyArgs");
+// "the pointer at byte `at` of the live block is binding `io`": its first element, io_ptrs[io] + offset -- or, raw, io_ptrs[io] as it is
+// handed in, for the inputs whose offset travels in the arguments
+struct KernelBinding {
+    int32_t io;  // (negative, as an op names an operand it does not have: the pointer stays null)
+    uint16_t at;
+    bool raw;
+};
+constexpr int DSP_KERNEL_BINDINGS_MAX = 14;  // (the pile-up kernel takes 10)
+constexpr int DSP_KERNEL_ONLY_ROUTES = DSP_ROUTE_SCALAR;  // DSP_ROUTE_EXTREMA .. DSP_ROUTE_SVM: the routes ahead of the optimisations
+
+struct ChainPlan;
 // (dsp_plan.cpp; exported for the CPU tests)
 extern "C" void dsp_internal_plan_energy_carries(int Ci, int S, const int32_t* lags, EnergyPlan* plan);
+// What a launch of a kernel-only chain hands its kernel: the plan's block with the pointers of this call, every one from the list of
+// bindings, and the flag of the 16-byte stores.  No HIP: tests/*_plan_fuzz.cpp call it with addresses nobody dereferences.
+extern "C" void dsp_internal_plan_fill_args(const ChainPlan* ch, void* const* io_ptrs, KernelOnlyArgs* args);
 
 // thread-local text behind dsp_last_error(); dsp_fail formats it and hands `code` back
 int dsp_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -90,61 +126,26 @@ struct ChainPlan {
     int dio_out[5] = {-1, -1, -1, -1, -1}, dio_pick[DSP_REDUCE_PICKS] = {-1, -1, -1, -1};
     int dio_walk[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1}, dio_walk_thr[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1},
         dio_walk_ts[DSP_REDUCE_WALKS] = {-1, -1, -1, -1, -1, -1};
-    // The ops no interpreter case stands behind: a program that holds one runs on that op's kernel or is refused (the table of these routes
-    // is dsp_plan.cpp's).  DSP_ROUTE_EXTREMA, DSP_ROUTE_HIST, DSP_ROUTE_THRESH, DSP_ROUTE_SPECTRUM, DSP_ROUTE_SORT, DSP_ROUTE_INTERP, DSP_ROUTE_DENSE, DSP_ROUTE_REFLECT, DSP_ROUTE_PILEUP, DSP_ROUTE_PULSES, DSP_ROUTE_TAILFIT, DSP_ROUTE_ALIGN or DSP_ROUTE_SVM; DSP_ROUTE_VM: the program holds none.
+    // The ops no interpreter case stands behind: a program that holds one runs on that op's kernel or is refused (kernel_only_routes,
+    // dsp_plan.cpp: a row per route).  A program never matches two, so one argument block, one row source and one list of bindings serve them
+    // all; DSP_ROUTE_VM: the program holds no such op and none of the four means anything.
     dsp_route kernel_only = DSP_ROUTE_VM;
-    // the peak finder (dsp_extrema.hip): the one kernel a program with MULTI_EXTREMA runs on
-    ExtremaArgs ext{};
-    RowSource ext_src{};
-    int xio_par[4] = {-1, -1, -1, -1}, xio_vt[2] = {-1, -1}, xio_n[2] = {-1, -1};
-    // histogram and histogram_stats (dsp_hist.hip): the one kernel a program with HISTOGRAM or HISTOGRAM_STATS runs on
-    HistArgs hist{};
-    RowSource hist_src{};  // (io < 0: histogram_stats alone, on weights and edges read from rows; dtype: the loop's)
-    int hio_w = -1, hio_b = -1, hio_w_in = -1, hio_e_in = -1, hio_max_in = -1, hio_s[3] = {-1, -1, -1};
-    // multi_time_point_thresh and time_over_threshold (dsp_thresh.hip): the one kernel a program with either op runs on
-    ThreshArgs thresh{};
-    RowSource thresh_src{};
-    int tio_thr = -1, tio_ts = -1, tio_out = -1;
-    // psd and fft (dsp_spectrum.hip): the one kernel a program with either op runs on
-    SpectrumArgs spec{};
-    RowSource spec_src{};
-    int sio_out = -1;
-    // sort (dsp_sort.hip): the one kernel a program with the op runs on
-    SortArgs sort{};
-    RowSource sort_src{};
-    int oio_out = -1;
-    // interpolating_upsampler (dsp_interp.hip): the one kernel a program with the op runs on
-    InterpArgs interp{};
-    RowSource interp_src{};
-    int iuo_out = -1;
-    // the neural-network layers (dsp_dense.hip): the one kernel a program with NORMALISE or DENSE runs on; weights, bias, means, variances, output
-    DenseArgs dense{};
-    RowSource dense_src{};
-    int eio_w = -1, eio_b = -1, eio_mean = -1, eio_var = -1, eio_out = -1;
-    // reflected_convolve_wf, with an avg_current of its output or without (dsp_reflect.hip): the one kernel a program with the op runs on
-    ReflectArgs reflect{};
-    RowSource reflect_src{};
-    int rio_taps = -1, rio_out = -1, rio_cur = -1;
-    // rc_cr2 and bi_level_zero_crossing_time_points, apart or in one launch (dsp_pileup.hip): the one kernel a program with either op runs on
-    PileupArgs pileup{};
-    RowSource pileup_src{};
-    int lio_par[4] = {-1, -1, -1, -1}, lio_out = -1, lio_list[2] = {-1, -1}, lio_n = -1, lio_sub = -1;
-    // peak_snr_threshold and multi_a_filter, apart or in one launch (dsp_pulses.hip): the one kernel a program with either op runs on
-    PulsesArgs pulses{};
-    RowSource pulses_src{};
-    int uio_list = -1, uio_ratio = -1, uio_idx = -1, uio_n = -1, uio_amp = -1;
-    // log_check, poly_fit, poly_diff and poly_exp_rms, apart or in one launch (dsp_tailfit.hip): the one kernel a program with any of them runs on
-    TailfitArgs tailfit{};
-    RowSource tailfit_src{};
-    int aio_sub = -1, aio_inv = -1, aio_pars = -1, aio_out = -1, aio_pars_out = -1, aio_mean = -1, aio_rms = -1;
-    // inl_correction, get_wf_centroid, wf_alignment and wf_correction, the last two apart or in one launch (dsp_align.hip): the one kernel a program with any of them runs on
-    AlignArgs align{};
-    RowSource align_src{};
-    int gio_table = -1, gio_centroid = -1, gio_out = -1, gio_out2 = -1, gio_scalar = -1;
-    // svm_predict (dsp_svm.hip): the one kernel a program with SVM_PREDICT runs on; support vectors, their norms, D, intercepts, classes, label, decisions
-    SvmArgs svm{};
-    RowSource svm_src{};
-    int vio_sv = -1, vio_norm = -1, vio_coef = -1, vio_icpt = -1, vio_cls = -1, vio_label = -1, vio_dec = -1;
+    KernelOnlyArgs only{};  // the block of `kernel_only`, its pointers null (dsp_internal_plan_fill_args fills them per call)
+    RowSource only_src{};   // (io < 0: histogram_stats alone, on weights and edges read from rows; dtype then the loop's)
+    KernelBinding bound[DSP_KERNEL_BINDINGS_MAX]{};
+    int n_bound = 0;
+    // the 16-byte stores of the kernels that have them: the int32 flag at out_vec_at of the block is set per call where the pointer at
+    // out_ptr_at is aligned and not null.  -1: none -- the route has no such stores, the output's stride is no whole number of vectors, or
+    // (dsp_align.hip) the launch starts with the op that streams nothing out
+    int out_vec_at = -1, out_ptr_at = -1;
+    // the binding recorded for a pointer of `only` (c.bound_io(c.only.sort.out)), or -1: the pointer stays null
+    template <typename T>
+    int bound_io(T* const& member) const {
+        const size_t at = (size_t)((const char*)&member - (const char*)&only);
+        for (int k = 0; k < n_bound && k < DSP_KERNEL_BINDINGS_MAX; ++k)  // (n_bound counts past the capacity: the overflow dsp_plan_build refuses)
+            if (bound[k].at == at) return bound[k].io;
+        return -1;
+    }
     // run-length FIR with the reductions of its output (dsp_fir_runs.hip); the reductions' bindings are dio_* above
     bool runs_ok = false;
     FirRunsArgs runs{};
@@ -166,6 +167,10 @@ const char* dsp_plan_kernel_name(const ChainPlan* ch);
 // does a specialised kernel's shape stand behind the chain (its note is then not shown)?  The route, but for one case: the classic energy
 // kernel asked for (variant 1) on a program only the register-resident one takes runs on the interpreter and still counts
 bool dsp_plan_specialised(const ChainPlan* ch);
+// what is HIP-free about the launch of a kernel-only chain (kernel_only_routes): the dynamic LDS its kernel's limit is raised to at chain
+// creation (0: the route has no limit to raise), and what dsp_chain_geometry reports
+int dsp_plan_kernel_only_lds(const ChainPlan* ch);
+void dsp_plan_kernel_only_geometry(const ChainPlan* ch, int64_t n_wf, int* lds_bytes_per_wave, int* waves_per_block, int* blocks);
 // a digest of every environment switch dsp_plan_build reads (DSPEED_HIP_FIR_F32, DSPEED_HIP_NO_FUSED, ...): a plan stands for the program
 // AND these, so whoever keeps planned chains by their program (dsp_gufuncs.cpp) keys on it as well
 uint64_t dsp_plan_switches();

@@ -8,21 +8,10 @@
 //                                                  "aligned_stored": .., "per_event": .., "integer_rows": .., "refused_by_name": .., "refused_shape": ..,
 //                                                  "refused_check": ..}
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -46,20 +35,6 @@ double wild_number(int32_t n) {
         case 5: return 1e300;
         default: return (double)draw(0, n > 0 ? n : 1);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
 }
 
 Prog draw_program() {
@@ -177,14 +152,6 @@ bool holds_op(const Prog& p) {
 }
 bool integer_rows(int dtype) { return dtype == DSP_I16 || dtype == DSP_U16 || dtype == DSP_I32 || dtype == DSP_U32; }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_op(p)) return true;  // (a mutation took the ops out: any route, tests/planner_fuzz.cpp's business)
     if (c.kernel_only != DSP_ROUTE_ALIGN) {
@@ -193,22 +160,22 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     }
     REQUIRE(dsp_plan_route(&c) == DSP_ROUTE_ALIGN);
     REQUIRE(std::strcmp(dsp_plan_kernel_name(&c), "dsp_align_kernel") == 0);
-    const AlignArgs& A = c.align;
+    const AlignArgs& A = c.only.align;
     const size_t n_ops = p.ops.size();
     // ---- one of the five shapes, and nothing else
     REQUIRE(n_ops >= 3 && n_ops <= 5 && p.ops[0].opcode == DSP_OP_LOAD);
     const int first = p.ops[1].opcode;
     const bool fused = first == DSP_OP_WF_ALIGNMENT && p.ops[2].opcode == DSP_OP_WF_CORRECTION;
     REQUIRE(is_mine(first) && A.mode == first - DSP_OP_INL_CORRECTION + 1 && A.correct == (fused ? 1 : 0));
-    REQUIRE(n_ops == (size_t)(fused ? (c.gio_out >= 0 ? 5 : 4) : 3));
+    REQUIRE(n_ops == (size_t)(fused ? (c.bound_io(A.out) >= 0 ? 5 : 4) : 3));
     for (size_t i = fused ? 3 : 2; i < n_ops; ++i) REQUIRE(p.ops[i].opcode == (first == DSP_OP_WF_CENTROID ? DSP_OP_STORE_SCALAR : DSP_OP_STORE));
     REQUIRE((int)p.slots.size() == (first == DSP_OP_WF_CENTROID ? 1 : (fused ? 3 : 2)));
     REQUIRE(A.f64 == (p.dtype == DSP_F64 ? 1 : 0));
     // ---- the rows
-    const dsp_io_desc& in = p.io[c.align_src.io];
+    const dsp_io_desc& in = p.io[c.only_src.io];
     REQUIRE(in.kind == DSP_IO_WF_IN && A.len >= 1 && A.len == in.len && A.len == p.slots[0] && A.wf_offset == in.offset && A.wf_stride == in.row_stride);
-    REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len && c.align_src.dtype == in.dtype);
-    REQUIRE(!c.align_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len && c.only_src.dtype == in.dtype);
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                  (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
     const bool loop_rows = p.dtype == DSP_F64 ? in.dtype == DSP_F64 : (in.dtype == DSP_F32 || in.dtype == DSP_I16 || in.dtype == DSP_U16);
     if (A.mode == DSP_ALIGN_INL) REQUIRE(integer_rows(in.dtype));
@@ -217,23 +184,23 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     // ---- the parameters: what the kernel forms addresses from
     const bool has_table = A.mode == DSP_ALIGN_INL || A.mode == DSP_ALIGN_CORRECT || fused;
     if (has_table) {
-        REQUIRE(c.gio_table >= 0 && c.gio_table < (int)p.io.size());
-        const dsp_io_desc& t = p.io[c.gio_table];
+        REQUIRE(c.bound_io(A.table) >= 0 && c.bound_io(A.table) < (int)p.io.size());
+        const dsp_io_desc& t = p.io[c.bound_io(A.table)];
         REQUIRE(t.kind == DSP_IO_TAPS && t.dtype == p.dtype && t.len >= 1 && A.table_len == t.len);
     } else {
-        REQUIRE(c.gio_table < 0);
+        REQUIRE(c.bound_io(A.table) < 0);
     }
     if (A.mode == DSP_ALIGN_CENTROID) {
-        REQUIRE(A.shift >= 0 && A.shift <= A.len - 1 && c.gio_scalar >= 0 && p.io[c.gio_scalar].kind == DSP_IO_SCALAR_OUT && p.io[c.gio_scalar].dtype == p.dtype);
-        REQUIRE(c.gio_out < 0 && c.gio_out2 < 0 && c.gio_centroid < 0);
+        REQUIRE(A.shift >= 0 && A.shift <= A.len - 1 && c.bound_io(A.scalar_out) >= 0 && p.io[c.bound_io(A.scalar_out)].kind == DSP_IO_SCALAR_OUT && p.io[c.bound_io(A.scalar_out)].dtype == p.dtype);
+        REQUIRE(c.bound_io(A.out) < 0 && c.bound_io(A.out2) < 0 && c.bound_io(A.centroid) < 0);
     } else {
-        REQUIRE(c.gio_scalar < 0);
+        REQUIRE(c.bound_io(A.scalar_out) < 0);
     }
     if (A.mode == DSP_ALIGN_WINDOW) {
         REQUIRE(A.size >= 1 && A.size <= A.len && A.size == p.slots[1] && A.shift >= 0 && A.shift <= A.len);
-        if (c.gio_centroid >= 0) REQUIRE(p.io[c.gio_centroid].kind == DSP_IO_SCALAR_IN && p.io[c.gio_centroid].dtype == p.dtype && A.centroid_stride == p.io[c.gio_centroid].row_stride);
+        if (c.bound_io(A.centroid) >= 0) REQUIRE(p.io[c.bound_io(A.centroid)].kind == DSP_IO_SCALAR_IN && p.io[c.bound_io(A.centroid)].dtype == p.dtype && A.centroid_stride == p.io[c.bound_io(A.centroid)].row_stride);
         else REQUIRE(A.centroid_const == A.centroid_const);  // (a NaN constant is refused at the plan)
-        const AlignWindow w = dsp_align_window(c.gio_centroid >= 0 ? 3.5 : A.centroid_const, A.shift, A.size, A.len);
+        const AlignWindow w = dsp_align_window(c.bound_io(A.centroid) >= 0 ? 3.5 : A.centroid_const, A.shift, A.size, A.len);
         REQUIRE(w.kind >= 0 && w.kind <= 3 && (w.kind != 1 || (w.first >= 0 && w.first + A.size <= A.len)) &&
                 (w.kind != 2 || (w.fill >= 0 && w.fill <= A.size && w.count >= 0 && w.count <= A.len && (w.count == 1 || w.fill + w.count == A.size))));
     }
@@ -244,16 +211,29 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     // ---- the outputs
     const int out_len = A.mode == DSP_ALIGN_WINDOW ? A.size : A.len;
     if (A.mode != DSP_ALIGN_CENTROID) {
-        const int last = fused ? c.gio_out2 : c.gio_out;
-        REQUIRE(last >= 0 && (fused || c.gio_out2 < 0));
-        for (int k : {c.gio_out, c.gio_out2}) {
+        const int last = fused ? c.bound_io(A.out2) : c.bound_io(A.out);
+        REQUIRE(last >= 0 && (fused || c.bound_io(A.out2) < 0));
+        for (int k : {c.bound_io(A.out), c.bound_io(A.out2)}) {
             if (k < 0) continue;
             const dsp_io_desc& o = p.io[k];
             REQUIRE(o.kind == DSP_IO_WF_OUT && o.dtype == p.dtype && o.len == out_len && o.offset >= 0 && o.row_stride >= (int64_t)o.offset + o.len);
-            REQUIRE((k == c.gio_out ? A.out_stride : A.out2_stride) == o.row_stride);
+            REQUIRE((k == c.bound_io(A.out) ? A.out_stride : A.out2_stride) == o.row_stride);
         }
-        REQUIRE(c.gio_out != c.gio_out2);
+        REQUIRE(c.bound_io(A.out) != c.bound_io(A.out2));
     }
+    // ---- the pointers a launch hands the kernel, from the program: the rows as they are handed in, table, column and outputs at their first
+    // element, null what the program has not; 16-byte stores of the rows the kernel streams out (not the aligned row's) where their start and
+    // stride are whole vectors.  table_nan is the chain's own: not filled here
+    const dsp_op& with_table = fused ? p.ops[2] : p.ops[1];
+    int out_io = -1, out2_io = -1;
+    if (first != DSP_OP_WF_CENTROID)
+        for (size_t i = fused ? 3 : 2; i < n_ops; ++i) (fused && p.ops[i].src == p.ops[2].dst ? out2_io : out_io) = p.ops[i].io;
+    const KernelOnlyArgs launch = launch_args(p, c);
+    const AlignArgs& L = launch.align;
+    REQUIRE(L.wf == raw_of(p.ops[0].io) && L.table == first_of(p, has_table ? with_table.io : -1) && L.table_nan == nullptr);
+    REQUIRE(L.centroid == first_of(p, first == DSP_OP_WF_ALIGNMENT ? column_of(p.ops[1], 0) : -1) && L.scalar_out == first_of(p, first == DSP_OP_WF_CENTROID ? p.ops[2].io : -1));
+    REQUIRE(L.out == first_of(p, out_io) && L.out2 == first_of(p, out2_io));
+    REQUIRE(L.out_vec == (first == DSP_OP_WF_ALIGNMENT ? 0 : vector_store(p, out_io, p.dtype == DSP_F64 ? 8 : 4)));
     return true;
 }
 
@@ -279,15 +259,9 @@ int main(int argc, char** argv) {
     }
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             const bool s = std::strstr(why, "(inl_correction, get_wf_centroid, wf_alignment, wf_correction) run on dsp_align_kernel only") != nullptr;
             const bool c = std::strstr(why, "shift ") == why || std::strstr(why, "size ") == why || std::strstr(why, "start_idx ") == why || std::strstr(why, "stop_idx ") == why ||
                            std::strstr(why, "centroid is nan") == why;
@@ -299,12 +273,12 @@ int main(int argc, char** argv) {
         }
         if (!check(number, p, *plan)) return 1;
         if (holds_op(p)) {
-            const AlignArgs& A = plan->align;
+            const AlignArgs& A = plan->only.align;
             ++accepted;
             ++kinds[A.correct ? 4 : A.mode - 1];
-            aligned_stored += A.correct && plan->gio_out >= 0;
-            per_event += A.mode == DSP_ALIGN_WINDOW && plan->gio_centroid >= 0;
-            ints += integer_rows(plan->align_src.dtype);
+            aligned_stored += A.correct && plan->bound_io(plan->only.align.out) >= 0;
+            per_event += A.mode == DSP_ALIGN_WINDOW && plan->bound_io(plan->only.align.centroid) >= 0;
+            ints += integer_rows(plan->only_src.dtype);
         }
     }
     std::printf("{\"programs\": %ld, \"accepted\": %ld, \"inl\": %ld, \"centroid\": %ld, \"align\": %ld, \"correct\": %ld, \"fused\": %ld, \"aligned_stored\": %ld, "

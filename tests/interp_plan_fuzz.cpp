@@ -3,20 +3,9 @@
 // (tests/test_interp_index_cpu.py), as tests/sort_plan_fuzz.cpp is for DSP_OP_SORT.  Every program is planned or refused; a planned one runs
 // on dsp_interp_kernel with an argument block that names the bindings' geometry, a mode the index rules know and an LDS footprint that fits.
 //   interp_plan_fuzz <programs> <seed>     prints {"programs": .., "accepted": .., "narrow": .., "wide": .., "refused_by_name": .., "modes": ..}
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -29,20 +18,6 @@ int64_t wild_length() {
         case 6: return 0x7fffffff - draw(0, 3);
         default: return draw(1, 20000);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
 }
 
 Prog draw_program() {
@@ -97,20 +72,12 @@ bool holds_op(const Prog& p) {
     return false;
 }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_op(p)) return true;  // (a mutation took the op out: any route, tests/planner_fuzz.cpp's business)
     REQUIRE(dsp_plan_route(&c) == DSP_ROUTE_INTERP && c.kernel_only == DSP_ROUTE_INTERP);
     REQUIRE(std::strcmp(dsp_plan_kernel_name(&c), "dsp_interp_kernel") == 0);
     REQUIRE(p.ops.size() == 3 && p.ops[0].opcode == DSP_OP_LOAD && p.ops[1].opcode == DSP_OP_INTERP_UPSAMPLE && p.ops[2].opcode == DSP_OP_STORE);
-    const InterpArgs& A = c.interp;
+    const InterpArgs& A = c.only.interp;
     const dsp_io_desc &in = p.io[p.ops[0].io], &out = p.io[p.ops[2].io];
     const int esz = p.dtype == DSP_F64 ? 8 : 4;
     REQUIRE(dsp_interp::mode_ok(A.mode) && A.mode == p.ops[1].ip[0]);
@@ -121,8 +88,13 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len && out.row_stride >= out.len && out.dtype == p.dtype);
     REQUIRE(A.wide == (dsp_interp::wide(A.mode, A.len, esz) ? 1 : 0));
     REQUIRE(dsp_interp::lds_bytes(A.mode, A.len, esz) <= 64 * 1024 + 16);
-    REQUIRE(c.interp_src.io == p.ops[0].io && c.interp_src.dtype == in.dtype && c.iuo_out == p.ops[2].io);
-    REQUIRE(!c.interp_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(c.only_src.io == p.ops[0].io && c.only_src.dtype == in.dtype && c.bound_io(A.out) == p.ops[2].io);
+    // ---- the pointers a launch hands the kernel, from the program: the rows as they are handed in, the output at its first element, and
+    // 16-byte stores where that and the stride are whole vectors
+    const KernelOnlyArgs launch = launch_args(p, c);
+    REQUIRE(launch.interp.wf == raw_of(p.ops[0].io) && launch.interp.out == first_of(p, p.ops[2].io));
+    REQUIRE(launch.interp.out_vec == vector_store(p, p.ops[2].io, p.dtype == DSP_F64 ? 8 : 4));
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                   (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
     // every output of the planned row has a segment inside the row (a sample of them: the first, the last, and 30 in between)
     for (int k = 0; k <= 31; ++k) {
@@ -142,15 +114,9 @@ int main(int argc, char** argv) {
     unsigned modes = 0;
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             if (std::strstr(why, "DSP_OP_INTERP_UPSAMPLE (interpolating_upsampler) runs on dsp_interp_kernel only") || std::strstr(why, "interpolating_upsampler"))
                 ++by_name;
             continue;
@@ -158,8 +124,8 @@ int main(int argc, char** argv) {
         if (!check(number, p, *plan)) return 1;
         if (holds_op(p)) {
             ++accepted;
-            ++(plan->interp.wide ? wide : narrow);
-            modes |= 1u << (std::strchr("infclhs", plan->interp.mode) - "infclhs");
+            ++(plan->only.interp.wide ? wide : narrow);
+            modes |= 1u << (std::strchr("infclhs", plan->only.interp.mode) - "infclhs");
         }
     }
     std::printf("{\"programs\": %ld, \"accepted\": %ld, \"narrow\": %ld, \"wide\": %ld, \"refused_by_name\": %ld, \"modes\": %u}\n", programs, accepted, narrow, wide,

@@ -4,20 +4,9 @@
 // Every program is planned or refused; a planned one runs on dsp_dense_kernel with an argument block that names bindings of the right
 // kind and size and fits the kernel's LDS and accumulators.
 //   ml_plan_fuzz <programs> <seed>     prints {"programs": .., "accepted": .., "dense": .., "classify": .., "normalise": .., "fused": .., "refused_by_name": ..}
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -30,20 +19,6 @@ int64_t wild_length() {
         case 6: return 0x7fffffff - draw(0, 3);
         default: return draw(1, 20000);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
 }
 
 Prog draw_program() {
@@ -127,14 +102,6 @@ bool holds_layer(const Prog& p) {
     return false;
 }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_layer(p)) return true;  // (a mutation took the ops out: any route, tests/planner_fuzz.cpp's business)
     for (const dsp_op& o : p.ops)      // (an op of another kernel-only route ahead of ours in the table: that route's business)
@@ -149,7 +116,7 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     const dsp_op& st = p.ops[n_ops - 1];
     const bool classify = dense && dense->ip[3] == 0;
     REQUIRE(st.opcode == (classify ? DSP_OP_STORE_SCALAR : DSP_OP_STORE));
-    const DenseArgs& A = c.dense;
+    const DenseArgs& A = c.only.dense;
     const dsp_io_desc &in = p.io[p.ops[0].io], &out = p.io[st.io];
     const int esz = p.dtype == DSP_F64 ? 8 : 4;
     REQUIRE(A.len >= 1 && A.len <= DSP_DENSE_N_MAX && A.m >= 0 && A.m <= DSP_DENSE_M_MAX);
@@ -157,19 +124,25 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len);
     REQUIRE(A.normalise == (norm ? 1 : 0) && (A.m > 0) == (dense != nullptr));
     auto taps_of = [&](int k, int64_t len) { return k >= 0 && k < (int)p.io.size() && p.io[k].kind == DSP_IO_TAPS && p.io[k].dtype == p.dtype && p.io[k].len == len; };
-    if (norm) REQUIRE(c.eio_mean == norm->io && c.eio_var == norm->ip[0] && taps_of(c.eio_mean, A.len) && taps_of(c.eio_var, A.len));
+    if (norm) REQUIRE(c.bound_io(A.means) == norm->io && c.bound_io(A.variances) == norm->ip[0] && taps_of(c.bound_io(A.means), A.len) && taps_of(c.bound_io(A.variances), A.len));
     if (dense) {
         REQUIRE(A.m == (classify ? 1 : dense->ip[3]) && A.activation == dense->ip[0] && dense->ip[2] == A.len);
-        REQUIRE(c.eio_w == dense->io && taps_of(c.eio_w, (int64_t)A.len * A.m));
-        REQUIRE(c.eio_b == dense->ip[1] && (c.eio_b < 0 || taps_of(c.eio_b, A.m)));
+        REQUIRE(c.bound_io(A.weights) == dense->io && taps_of(c.bound_io(A.weights), (int64_t)A.len * A.m));
+        REQUIRE(c.bound_io(A.bias) == dense->ip[1] && (c.bound_io(A.bias) < 0 || taps_of(c.bound_io(A.bias), A.m)));
         REQUIRE(classify ? out.kind == DSP_IO_SCALAR_OUT : (out.kind == DSP_IO_WF_OUT && out.len == A.m && out.row_stride >= out.len));
         REQUIRE(dsp_dense::lds_bytes(A.m, esz) <= 87040 && dsp_dense::blocks(A.m) <= dsp_dense::built_blocks(A.m));
     } else {
-        REQUIRE(c.eio_w < 0 && c.eio_b < 0 && out.kind == DSP_IO_WF_OUT && out.len == A.len && out.row_stride >= out.len);
+        REQUIRE(c.bound_io(A.weights) < 0 && c.bound_io(A.bias) < 0 && out.kind == DSP_IO_WF_OUT && out.len == A.len && out.row_stride >= out.len);
     }
-    REQUIRE(c.dense_src.io == p.ops[0].io && c.dense_src.dtype == in.dtype && c.eio_out == st.io);
-    REQUIRE(!c.dense_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(c.only_src.io == p.ops[0].io && c.only_src.dtype == in.dtype && c.bound_io(A.out) == st.io);
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                  (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
+    // ---- the pointers a launch hands the kernel, from the program: the rows as they are handed in, every other at its first element, null what the program has not
+    const KernelOnlyArgs launch = launch_args(p, c);
+    const DenseArgs& L = launch.dense;
+    REQUIRE(L.wf == raw_of(p.ops[0].io) && L.out == first_of(p, st.io));
+    REQUIRE(L.means == first_of(p, norm ? norm->io : -1) && L.variances == first_of(p, norm ? norm->ip[0] : -1));
+    REQUIRE(L.weights == first_of(p, dense ? dense->io : -1) && L.bias == first_of(p, dense ? dense->ip[1] : -1));
     return true;
 }
 
@@ -181,15 +154,9 @@ int main(int argc, char** argv) {
     long accepted = 0, n_dense = 0, n_classify = 0, n_norm = 0, n_fused = 0, by_name = 0;
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             if (std::strstr(why, "run on dsp_dense_kernel only") || std::strstr(why, "layers of up to") || std::strstr(why, "dense_layer: ") ||
                 std::strstr(why, "normalisation_layer: ") || std::strstr(why, "bad DENSE") || std::strstr(why, "bad NORMALISE") || std::strstr(why, "DENSE: ip[2]"))
                 ++by_name;
@@ -198,7 +165,7 @@ int main(int argc, char** argv) {
         if (!check(number, p, *plan)) return 1;
         if (holds_layer(p) && plan->kernel_only == DSP_ROUTE_DENSE) {
             ++accepted;
-            const DenseArgs& A = plan->dense;
+            const DenseArgs& A = plan->only.dense;
             if (A.m == 0)
                 ++n_norm;
             else if (p.ops.back().opcode == DSP_OP_STORE_SCALAR)

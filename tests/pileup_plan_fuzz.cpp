@@ -7,21 +7,10 @@
 //                                                   "subtracted": .., "columns": .., "refused_by_name": .., "refused_shape": .., "refused_short": ..,
 //                                                   "refused_start": .., "refused_lists": ..}
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -43,20 +32,6 @@ double wild_value() {
         case 3: return (double)draw(-5, 5) * 1e30;
         default: return (double)draw(-3, 300);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
 }
 
 Prog draw_program() {
@@ -157,14 +132,6 @@ bool holds_op(const Prog& p) {
     return false;
 }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_op(p)) return true;  // (a mutation took the ops out: any route, tests/planner_fuzz.cpp's business)
     if (c.kernel_only != DSP_ROUTE_PILEUP) {
@@ -173,7 +140,7 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     }
     REQUIRE(dsp_plan_route(&c) == DSP_ROUTE_PILEUP);
     REQUIRE(std::strcmp(dsp_plan_kernel_name(&c), "dsp_pileup_kernel") == 0);
-    const PileupArgs& A = c.pileup;
+    const PileupArgs& A = c.only.pileup;
     const size_t n_ops = p.ops.size();
     REQUIRE(n_ops >= 3 && n_ops <= 8 && p.ops[0].opcode == DSP_OP_LOAD);
     const size_t first = p.ops[1].opcode == DSP_OP_BL_SUBTRACT ? 2 : 1;
@@ -183,36 +150,52 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     const dsp_io_desc& in = p.io[p.ops[0].io];
     REQUIRE(A.len >= 1 && A.len == in.len && A.wf_offset == in.offset && A.wf_stride == in.row_stride && (!A.filter || A.len > 3));
     REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len && A.len <= (1 << 24));
-    REQUIRE(c.pileup_src.io == p.ops[0].io && c.pileup_src.dtype == in.dtype);
-    REQUIRE(!c.pileup_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(c.only_src.io == p.ops[0].io && c.only_src.dtype == in.dtype);
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                   (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
     REQUIRE(p.dtype == DSP_F64 ? in.dtype == DSP_F64 : (in.dtype == DSP_F32 || in.dtype == DSP_I16 || in.dtype == DSP_U16));
-    if (A.sub_mode) REQUIRE(c.lio_sub < 0 || (p.io[c.lio_sub].kind == DSP_IO_SCALAR_IN && p.io[c.lio_sub].dtype == p.dtype));
+    if (A.sub_mode) REQUIRE(c.bound_io(A.sub) < 0 || (p.io[c.bound_io(A.sub)].kind == DSP_IO_SCALAR_IN && p.io[c.bound_io(A.sub)].dtype == p.dtype));
     if (A.filter) {
         REQUIRE(A.tau_nan == 0 || A.tau_nan == 1);
         REQUIRE(A.tau_nan || (A.c1 == A.c1 && A.c2 == A.c2 && A.c3 == A.c3));
     }
-    if (c.lio_out >= 0) {
-        const dsp_io_desc& out = p.io[c.lio_out];
+    if (c.bound_io(A.out) >= 0) {
+        const dsp_io_desc& out = p.io[c.bound_io(A.out)];
         REQUIRE(A.filter && out.kind == DSP_IO_WF_OUT && out.dtype == p.dtype && out.len == A.len && out.row_stride >= out.len && A.out_stride == out.row_stride);
     } else {
         REQUIRE(A.walk);
     }
     if (A.walk) {
-        REQUIRE(A.m >= 1 && c.lio_list[0] >= 0 && c.lio_list[1] >= 0 && c.lio_list[0] != c.lio_list[1] && c.lio_n >= 0);
+        REQUIRE(A.m >= 1 && c.bound_io(A.list[0]) >= 0 && c.bound_io(A.list[1]) >= 0 && c.bound_io(A.list[0]) != c.bound_io(A.list[1]) && c.bound_io(A.n_out) >= 0);
         for (int k = 0; k < 2; ++k) {
-            const dsp_io_desc& l = p.io[c.lio_list[k]];
+            const dsp_io_desc& l = p.io[c.bound_io(A.list[k])];
             REQUIRE(l.kind == DSP_IO_WF_OUT && l.dtype == p.dtype && l.len == A.m && l.row_stride >= l.len && A.list_stride[k] == l.row_stride);
         }
-        REQUIRE(p.io[c.lio_n].kind == DSP_IO_SCALAR_OUT && p.io[c.lio_n].dtype == DSP_U32);
+        REQUIRE(p.io[c.bound_io(A.n_out)].kind == DSP_IO_SCALAR_OUT && p.io[c.bound_io(A.n_out)].dtype == DSP_U32);
         for (int k = 0; k < 4; ++k)
-            REQUIRE(c.lio_par[k] < 0 || (p.io[c.lio_par[k]].kind == DSP_IO_SCALAR_IN && p.io[c.lio_par[k]].dtype == p.dtype));
-        REQUIRE(c.lio_par[2] >= 0 || std::isfinite(A.par_const[2]));  // a constant gate is finite
-        if (c.lio_par[3] < 0 && A.par_const[3] == A.par_const[3])     // a constant start is integral and inside the row
+            REQUIRE(c.bound_io(A.par[k]) < 0 || (p.io[c.bound_io(A.par[k])].kind == DSP_IO_SCALAR_IN && p.io[c.bound_io(A.par[k])].dtype == p.dtype));
+        REQUIRE(c.bound_io(A.par[2]) >= 0 || std::isfinite(A.par_const[2]));  // a constant gate is finite
+        if (c.bound_io(A.par[3]) < 0 && A.par_const[3] == A.par_const[3])     // a constant start is integral and inside the row
             REQUIRE(std::floor(A.par_const[3]) == A.par_const[3] && A.par_const[3] >= 0 && A.par_const[3] < A.len);
     } else {
-        REQUIRE(c.lio_list[0] < 0 && c.lio_list[1] < 0 && c.lio_n < 0 && A.m == 0);
+        REQUIRE(c.bound_io(A.list[0]) < 0 && c.bound_io(A.list[1]) < 0 && c.bound_io(A.n_out) < 0 && A.m == 0);
     }
+    // ---- the pointers a launch hands the kernel, from the program: the rows as they are handed in, columns and outputs at their first element,
+    // null what the program has not; 16-byte stores of the filtered row where its start and stride are whole vectors
+    const dsp_op* fi = A.filter ? &p.ops[first] : nullptr;
+    const dsp_op* wk = A.walk ? &p.ops[first + A.filter] : nullptr;
+    int out_io = -1, list_io[2] = {-1, -1};
+    for (size_t i = first + A.filter + A.walk; i < n_ops; ++i) {
+        const dsp_op& st = p.ops[i];
+        if (st.opcode != DSP_OP_STORE) continue;
+        (fi && st.src == fi->dst ? out_io : list_io[st.src == wk->dst ? 0 : 1]) = st.io;
+    }
+    const KernelOnlyArgs launch = launch_args(p, c);
+    const PileupArgs& L = launch.pileup;
+    REQUIRE(L.wf == raw_of(p.ops[0].io) && L.sub == first_of(p, first == 2 ? column_of(p.ops[1], 0) : -1) && L.out == first_of(p, out_io));
+    REQUIRE(L.list[0] == first_of(p, list_io[0]) && L.list[1] == first_of(p, list_io[1]) && L.n_out == first_of(p, wk ? p.ops[n_ops - 1].io : -1));
+    for (int k = 0; k < 4; ++k) REQUIRE(L.par[k] == first_of(p, wk ? column_of(*wk, k) : -1));
+    REQUIRE(L.out_vec == vector_store(p, out_io, p.dtype == DSP_F64 ? 8 : 4));
     return true;
 }
 
@@ -224,15 +207,9 @@ int main(int argc, char** argv) {
     long accepted = 0, filter = 0, walk = 0, fused = 0, fused_row = 0, subtracted = 0, columns = 0, by_name = 0, shape = 0, too_short = 0, start = 0, lists = 0;
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             const bool s = std::strstr(why, "DSP_OP_RC_CR2 / DSP_OP_BI_LEVEL_ZERO_CROSSING (rc_cr2, bi_level_zero_crossing_time_points) run on dsp_pileup_kernel only") != nullptr;
             const bool l = std::strstr(why, "The length of the waveform must be larger than 3") != nullptr;
             const bool t = std::strstr(why, "The starting index") != nullptr;
@@ -245,16 +222,16 @@ int main(int argc, char** argv) {
         }
         if (!check(number, p, *plan)) return 1;
         if (holds_op(p)) {
-            const PileupArgs& A = plan->pileup;
+            const PileupArgs& A = plan->only.pileup;
             ++accepted;
             if (A.filter && A.walk) {
                 ++fused;
-                fused_row += plan->lio_out >= 0;
+                fused_row += plan->bound_io(plan->only.pileup.out) >= 0;
             } else {
                 ++(A.filter ? filter : walk);
             }
             subtracted += A.sub_mode;
-            for (int k = 0; k < 4; ++k) columns += A.walk && plan->lio_par[k] >= 0;
+            for (int k = 0; k < 4; ++k) columns += A.walk && plan->bound_io(plan->only.pileup.par[k]) >= 0;
         }
     }
     std::printf("{\"programs\": %ld, \"accepted\": %ld, \"filter\": %ld, \"walk\": %ld, \"fused\": %ld, \"fused_row_stored\": %ld, \"subtracted\": %ld, "

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz_launch.h"
 
 namespace {
 
@@ -878,58 +879,102 @@ bool check(const Prog& p, const ChainPlan& c) {
     };
     auto column_ok = [&](int k, int64_t stride) { return io_ok(k, DSP_IO_SCALAR_IN) && p.io[k].dtype == p.dtype && stride == p.io[k].row_stride; };
     auto out_ok = [&](int k, int kind, int64_t stride) { return io_ok(k, kind) && stride == p.io[k].row_stride; };
+    // ---- a pretended launch of a kernel-only chain (plan_fuzz_launch.h): every pointer of the block is the one the PROGRAM names -- an
+    // output's or a column's first element, an input whose offset travels in the arguments as it is handed in, null what the program has not
+    auto first_of = [&](int k) { return ::first_of(p, k); };
+    const KernelOnlyArgs launch = c.kernel_only != DSP_ROUTE_VM ? launch_args(p, c) : KernelOnlyArgs{};
     if (c.kernel_only == DSP_ROUTE_EXTREMA) {
-        const ExtremaArgs& A = c.ext;
-        REQUIRE(io_ok(c.ext_src.io, DSP_IO_WF_IN), "extrema kernel: row binding");
-        REQUIRE(A.wf_offset == p.io[c.ext_src.io].offset && A.wf_stride == p.io[c.ext_src.io].row_stride && A.len == p.io[c.ext_src.io].len, "extrema kernel: the row binding's offset / stride / length");
+        const ExtremaArgs& A = c.only.ext;
+        const ExtremaArgs& L = launch.ext;
+        const dsp_op& ex = p.ops[1];
+        REQUIRE(p.ops.size() == 6 && L.wf == raw_of(p.ops[0].io), "extrema kernel: the rows' pointer");
+        for (int k = 0; k < 4; ++k) REQUIRE(L.par[k] == first_of(column_of(ex, k)), "extrema kernel: the pointer of parameter %d", k);
+        for (int i = 2; i < 4; ++i) REQUIRE(L.vt_out[p.ops[i].src == ex.dst ? 0 : 1] == first_of(p.ops[i].io), "extrema kernel: the pointer of the list op %d stores", i);
+        for (int i = 4; i < 6; ++i) REQUIRE(L.n_out[p.ops[i].ip[0] == ex.ip[2] ? 0 : 1] == first_of(p.ops[i].io), "extrema kernel: the pointer of the count op %d stores", i);
+        REQUIRE(io_ok(c.only_src.io, DSP_IO_WF_IN), "extrema kernel: row binding");
+        REQUIRE(A.wf_offset == p.io[c.only_src.io].offset && A.wf_stride == p.io[c.only_src.io].row_stride && A.len == p.io[c.only_src.io].len, "extrema kernel: the row binding's offset / stride / length");
         for (int k = 0; k < 4; ++k)
-            if (c.xio_par[k] >= 0) REQUIRE(column_ok(c.xio_par[k], A.par_stride[k]), "extrema kernel: parameter column %d", k);
+            if (c.bound_io(A.par[k]) >= 0) REQUIRE(column_ok(c.bound_io(A.par[k]), A.par_stride[k]), "extrema kernel: parameter column %d", k);
         for (int k = 0; k < 2; ++k) {
-            REQUIRE(out_ok(c.xio_vt[k], DSP_IO_WF_OUT, A.vt_stride[k]) && p.io[c.xio_vt[k]].len == A.m, "extrema kernel: list %d", k);
-            REQUIRE(out_ok(c.xio_n[k], DSP_IO_SCALAR_OUT, A.n_stride[k]) && p.io[c.xio_n[k]].dtype == DSP_U32, "extrema kernel: count %d", k);
+            REQUIRE(out_ok(c.bound_io(A.vt_out[k]), DSP_IO_WF_OUT, A.vt_stride[k]) && p.io[c.bound_io(A.vt_out[k])].len == A.m, "extrema kernel: list %d", k);
+            REQUIRE(out_ok(c.bound_io(A.n_out[k]), DSP_IO_SCALAR_OUT, A.n_stride[k]) && p.io[c.bound_io(A.n_out[k])].dtype == DSP_U32, "extrema kernel: count %d", k);
         }
         REQUIRE(A.m >= 1 && A.m < A.len && A.direction >= 0 && A.direction <= 3 && A.direction != 2, "extrema kernel: lists of %d from rows of %d, direction %d", A.m, A.len, A.direction);
-        if (c.ext_src.vec) REQUIRE(rows_vec(c.ext_src.io), "extrema kernel: vector loads on rows that are not whole 16-byte vectors");
+        if (c.only_src.vec) REQUIRE(rows_vec(c.only_src.io), "extrema kernel: vector loads on rows that are not whole 16-byte vectors");
     }
     if (c.kernel_only == DSP_ROUTE_HIST) {
-        const HistArgs& A = c.hist;
+        const HistArgs& A = c.only.hist;
         REQUIRE(A.m >= 1 && A.m <= DSP_HIST_MAX_BINS, "histogram kernel: %d bins", A.m);
-        if (c.hist_src.io >= 0) {
-            REQUIRE(io_ok(c.hist_src.io, DSP_IO_WF_IN), "histogram kernel: row binding");
-            REQUIRE(A.wf_offset == p.io[c.hist_src.io].offset && A.wf_stride == p.io[c.hist_src.io].row_stride && A.len == p.io[c.hist_src.io].len, "histogram kernel: the row binding's offset / stride / length");
-            REQUIRE(c.hio_w_in < 0 && c.hio_e_in < 0, "histogram kernel: a row and weights read from memory");
-            if (c.hist_src.vec) REQUIRE(rows_vec(c.hist_src.io), "histogram kernel: vector loads on rows that are not whole 16-byte vectors");
+        const HistArgs& L = launch.hist;
+        const bool alone = p.ops[2].opcode == DSP_OP_HISTOGRAM_STATS && p.ops[1].opcode == DSP_OP_LOAD;
+        const dsp_op* st = p.ops[2].opcode == DSP_OP_HISTOGRAM_STATS ? &p.ops[2] : nullptr;
+        int w_out = -1, b_out = -1, s_out[3] = {-1, -1, -1};
+        for (const dsp_op& o : p.ops) {
+            if (o.opcode == DSP_OP_STORE) (o.src == p.ops[1].dst ? w_out : b_out) = o.io;
+            if (o.opcode == DSP_OP_STORE_SCALAR) s_out[o.ip[0] - st->ip[1]] = o.io;
+        }
+        if (alone) {
+            const dsp_op &lw = p.ops[0].dst == st->src ? p.ops[0] : p.ops[1], &le = p.ops[0].dst == st->ip[0] ? p.ops[0] : p.ops[1];
+            REQUIRE(L.wf == nullptr && L.w_in == raw_of(lw.io) && L.e_in == raw_of(le.io), "histogram_stats alone: the pointers of weights and edges");
         } else {
-            REQUIRE(A.stats && !c.hist_src.vec, "histogram kernel: neither a row nor histogram_stats alone");
-            REQUIRE(io_ok(c.hio_w_in, DSP_IO_WF_IN) && p.io[c.hio_w_in].dtype == p.dtype && A.w_in_stride == p.io[c.hio_w_in].row_stride && A.w_in_offset == p.io[c.hio_w_in].offset && p.io[c.hio_w_in].len == A.m,
+            REQUIRE(L.wf == raw_of(p.ops[0].io) && L.w_in == nullptr && L.e_in == nullptr, "histogram kernel: the rows' pointer");
+        }
+        REQUIRE(L.w_out == first_of(w_out) && L.b_out == first_of(b_out) && L.max_in == first_of(st ? column_of(*st, 0) : -1), "histogram kernel: the pointers of weights_out, borders_out and max_in");
+        for (int k = 0; k < 3; ++k) REQUIRE(L.s_out[k] == first_of(s_out[k]), "histogram kernel: the pointer of histogram_stats output %d", k);
+        if (c.only_src.io >= 0) {
+            REQUIRE(io_ok(c.only_src.io, DSP_IO_WF_IN), "histogram kernel: row binding");
+            REQUIRE(A.wf_offset == p.io[c.only_src.io].offset && A.wf_stride == p.io[c.only_src.io].row_stride && A.len == p.io[c.only_src.io].len, "histogram kernel: the row binding's offset / stride / length");
+            REQUIRE(c.bound_io(A.w_in) < 0 && c.bound_io(A.e_in) < 0, "histogram kernel: a row and weights read from memory");
+            if (c.only_src.vec) REQUIRE(rows_vec(c.only_src.io), "histogram kernel: vector loads on rows that are not whole 16-byte vectors");
+        } else {
+            REQUIRE(A.stats && !c.only_src.vec, "histogram kernel: neither a row nor histogram_stats alone");
+            REQUIRE(io_ok(c.bound_io(A.w_in), DSP_IO_WF_IN) && p.io[c.bound_io(A.w_in)].dtype == p.dtype && A.w_in_stride == p.io[c.bound_io(A.w_in)].row_stride && A.w_in_offset == p.io[c.bound_io(A.w_in)].offset && p.io[c.bound_io(A.w_in)].len == A.m,
                     "histogram_stats alone: the weights' rows");
-            REQUIRE(io_ok(c.hio_e_in, DSP_IO_WF_IN) && p.io[c.hio_e_in].dtype == p.dtype && A.e_in_stride == p.io[c.hio_e_in].row_stride && A.e_in_offset == p.io[c.hio_e_in].offset && p.io[c.hio_e_in].len == A.m + 1,
+            REQUIRE(io_ok(c.bound_io(A.e_in), DSP_IO_WF_IN) && p.io[c.bound_io(A.e_in)].dtype == p.dtype && A.e_in_stride == p.io[c.bound_io(A.e_in)].row_stride && A.e_in_offset == p.io[c.bound_io(A.e_in)].offset && p.io[c.bound_io(A.e_in)].len == A.m + 1,
                     "histogram_stats alone: the edges' rows");
         }
-        if (c.hio_w >= 0 || !A.stats) REQUIRE(out_ok(c.hio_w, DSP_IO_WF_OUT, A.w_stride) && p.io[c.hio_w].len == A.m, "histogram kernel: weights_out");
-        if (c.hio_b >= 0 || !A.stats) REQUIRE(out_ok(c.hio_b, DSP_IO_WF_OUT, A.b_stride) && p.io[c.hio_b].len == A.m + 1, "histogram kernel: borders_out");
+        if (c.bound_io(A.w_out) >= 0 || !A.stats) REQUIRE(out_ok(c.bound_io(A.w_out), DSP_IO_WF_OUT, A.w_stride) && p.io[c.bound_io(A.w_out)].len == A.m, "histogram kernel: weights_out");
+        if (c.bound_io(A.b_out) >= 0 || !A.stats) REQUIRE(out_ok(c.bound_io(A.b_out), DSP_IO_WF_OUT, A.b_stride) && p.io[c.bound_io(A.b_out)].len == A.m + 1, "histogram kernel: borders_out");
         if (A.stats) {
-            for (int k = 0; k < 3; ++k) REQUIRE(out_ok(c.hio_s[k], DSP_IO_SCALAR_OUT, A.s_stride[k]), "histogram kernel: histogram_stats output %d", k);
-            if (c.hio_max_in >= 0) REQUIRE(column_ok(c.hio_max_in, A.max_in_stride), "histogram kernel: max_in column");
+            for (int k = 0; k < 3; ++k) REQUIRE(out_ok(c.bound_io(A.s_out[k]), DSP_IO_SCALAR_OUT, A.s_stride[k]), "histogram kernel: histogram_stats output %d", k);
+            if (c.bound_io(A.max_in) >= 0) REQUIRE(column_ok(c.bound_io(A.max_in), A.max_in_stride), "histogram kernel: max_in column");
         }
     }
+    if (c.kernel_only == DSP_ROUTE_SPECTRUM) {  // (no generator draws psd or fft: main plans two fixed programs ahead of the drawn ones)
+        const SpectrumArgs &A = c.only.spec, &L = launch.spec;
+        REQUIRE(p.ops.size() == 3 && c.only_src.io == p.ops[0].io && c.bound_io(A.out) == p.ops[2].io, "spectrum kernel: the bindings of rows and output");
+        REQUIRE(L.wf == raw_of(p.ops[0].io) && L.out == first_of(p.ops[2].io), "spectrum kernel: the pointers of the rows and the output");
+        REQUIRE(L.twiddle == nullptr && L.aux == nullptr && L.filter == nullptr, "spectrum kernel: the tables are the chain's, not the plan's");
+    }
     if (c.kernel_only == DSP_ROUTE_THRESH) {
-        const ThreshArgs& A = c.thresh;
-        REQUIRE(io_ok(c.thresh_src.io, DSP_IO_WF_IN), "threshold kernel: row binding");
-        REQUIRE(A.wf_offset == p.io[c.thresh_src.io].offset && A.wf_stride == p.io[c.thresh_src.io].row_stride && A.len == p.io[c.thresh_src.io].len, "threshold kernel: the row binding's offset / stride / length");
-        REQUIRE(A.m >= 0 && A.m <= DSP_THRESH_MAX && A.len >= (A.m > 0 ? 2 : 1), "threshold kernel: %d thresholds on rows of %d", A.m, A.len);
-        REQUIRE(out_ok(c.tio_out, A.m > 0 ? DSP_IO_WF_OUT : DSP_IO_SCALAR_OUT, A.out_stride), "threshold kernel: output");
-        if (A.m > 0) {
-            REQUIRE((A.polarity == 1 || A.polarity == -1) && strchr("iafbcrnl", A.mode) && p.io[c.tio_out].len == A.m, "threshold kernel: polarity %d, mode %d", A.polarity, A.mode);
-            REQUIRE(c.tio_thr >= 0 && c.tio_thr < (int)p.io.size() && p.io[c.tio_thr].dtype == p.dtype && p.io[c.tio_thr].len == A.m && A.thr_offset == p.io[c.tio_thr].offset &&
-                        (p.io[c.tio_thr].kind == DSP_IO_WF_IN ? A.thr_stride == p.io[c.tio_thr].row_stride : (p.io[c.tio_thr].kind == DSP_IO_TAPS && A.thr_stride == 0)),
-                    "threshold kernel: the thresholds' binding");
-            if (c.tio_ts >= 0) REQUIRE(column_ok(c.tio_ts, A.ts_stride), "threshold kernel: t_start column");
+        const ThreshArgs& A = c.only.thresh;
+        REQUIRE(io_ok(c.only_src.io, DSP_IO_WF_IN), "threshold kernel: row binding");
+        const ThreshArgs& L = launch.thresh;
+        const bool lists = p.ops.size() == 4;
+        const dsp_op &op = p.ops[lists ? 2 : 1], &store = p.ops.back();
+        const dsp_op& ld = !lists || p.ops[0].dst == op.src ? p.ops[0] : p.ops[1];
+        REQUIRE(L.wf == raw_of(ld.io) && L.out == first_of(store.io), "threshold kernel: the pointers of the rows and the output");
+        if (op.opcode == DSP_OP_TIME_OVER_THRESHOLD) {
+            // (as it is handed in: the kernel has always read this column without the binding's offset)
+            REQUIRE(L.thr == raw_of(column_of(op, 0)) && L.ts == nullptr, "time_over_threshold: the pointer of the threshold column");
         } else {
-            REQUIRE(c.tio_ts < 0, "time_over_threshold with a t_start");
-            if (c.tio_thr >= 0) REQUIRE(column_ok(c.tio_thr, A.thr_stride), "threshold kernel: threshold column");
+            const int thr = lists ? (&ld == &p.ops[0] ? p.ops[1] : p.ops[0]).io : op.io;
+            REQUIRE(L.thr == raw_of(thr) && L.ts == first_of(column_of(op, 0)), "multi_time_point_thresh: the pointers of the thresholds and of t_start");
         }
-        if (c.thresh_src.vec) REQUIRE(rows_vec(c.thresh_src.io), "threshold kernel: vector loads on rows that are not whole 16-byte vectors");
+        REQUIRE(A.wf_offset == p.io[c.only_src.io].offset && A.wf_stride == p.io[c.only_src.io].row_stride && A.len == p.io[c.only_src.io].len, "threshold kernel: the row binding's offset / stride / length");
+        REQUIRE(A.m >= 0 && A.m <= DSP_THRESH_MAX && A.len >= (A.m > 0 ? 2 : 1), "threshold kernel: %d thresholds on rows of %d", A.m, A.len);
+        REQUIRE(out_ok(c.bound_io(A.out), A.m > 0 ? DSP_IO_WF_OUT : DSP_IO_SCALAR_OUT, A.out_stride), "threshold kernel: output");
+        if (A.m > 0) {
+            REQUIRE((A.polarity == 1 || A.polarity == -1) && strchr("iafbcrnl", A.mode) && p.io[c.bound_io(A.out)].len == A.m, "threshold kernel: polarity %d, mode %d", A.polarity, A.mode);
+            REQUIRE(c.bound_io(A.thr) >= 0 && c.bound_io(A.thr) < (int)p.io.size() && p.io[c.bound_io(A.thr)].dtype == p.dtype && p.io[c.bound_io(A.thr)].len == A.m && A.thr_offset == p.io[c.bound_io(A.thr)].offset &&
+                        (p.io[c.bound_io(A.thr)].kind == DSP_IO_WF_IN ? A.thr_stride == p.io[c.bound_io(A.thr)].row_stride : (p.io[c.bound_io(A.thr)].kind == DSP_IO_TAPS && A.thr_stride == 0)),
+                    "threshold kernel: the thresholds' binding");
+            if (c.bound_io(A.ts) >= 0) REQUIRE(column_ok(c.bound_io(A.ts), A.ts_stride), "threshold kernel: t_start column");
+        } else {
+            REQUIRE(c.bound_io(A.ts) < 0, "time_over_threshold with a t_start");
+            if (c.bound_io(A.thr) >= 0) REQUIRE(column_ok(c.bound_io(A.thr), A.thr_stride), "threshold kernel: threshold column");
+        }
+        if (c.only_src.vec) REQUIRE(rows_vec(c.only_src.io), "threshold kernel: vector loads on rows that are not whole 16-byte vectors");
     }
     return true;
 }
@@ -1031,20 +1076,41 @@ void digest_plan(Digest& H, const ChainPlan& c, int n_slots) {
         if (A.has_red) digest_reduce(H, A.red);
     }
     // the kernels that stream rows from memory and have no interpreter op behind them
-    H(c.kernel_only == DSP_ROUTE_EXTREMA), H(c.ext_src.dtype), H(c.ext_src.vec), H(c.ext_src.io), H(c.xio_par), H(c.xio_vt), H(c.xio_n);
-    H(c.kernel_only == DSP_ROUTE_HIST), H(c.hist_src.dtype), H(c.hist_src.vec), H(c.hist_src.io), H(c.hio_w), H(c.hio_b), H(c.hio_w_in), H(c.hio_e_in), H(c.hio_max_in), H(c.hio_s);
-    H(c.kernel_only == DSP_ROUTE_THRESH), H(c.thresh_src.dtype), H(c.thresh_src.vec), H(c.thresh_src.io), H(c.tio_thr), H(c.tio_ts), H(c.tio_out);
+    // (the values and the order of the members the plan held per route: a route that is not the plan's has no rows and no bindings)
+    const RowSource none{};
+    auto io = [&](dsp_route route, auto* const& member) { return c.kernel_only == route ? c.bound_io(member) : -1; };
+    {
+        const ExtremaArgs& A = c.only.ext;
+        const RowSource& src = c.kernel_only == DSP_ROUTE_EXTREMA ? c.only_src : none;
+        H(c.kernel_only == DSP_ROUTE_EXTREMA), H(src.dtype), H(src.vec), H(src.io);
+        for (int k = 0; k < 4; ++k) H(io(DSP_ROUTE_EXTREMA, A.par[k]));
+        for (int k = 0; k < 2; ++k) H(io(DSP_ROUTE_EXTREMA, A.vt_out[k]));
+        for (int k = 0; k < 2; ++k) H(io(DSP_ROUTE_EXTREMA, A.n_out[k]));
+    }
+    {
+        const HistArgs& A = c.only.hist;
+        const RowSource& src = c.kernel_only == DSP_ROUTE_HIST ? c.only_src : none;
+        H(c.kernel_only == DSP_ROUTE_HIST), H(src.dtype), H(src.vec), H(src.io);
+        H(io(DSP_ROUTE_HIST, A.w_out)), H(io(DSP_ROUTE_HIST, A.b_out)), H(io(DSP_ROUTE_HIST, A.w_in)), H(io(DSP_ROUTE_HIST, A.e_in)), H(io(DSP_ROUTE_HIST, A.max_in));
+        for (int k = 0; k < 3; ++k) H(io(DSP_ROUTE_HIST, A.s_out[k]));
+    }
+    {
+        const ThreshArgs& A = c.only.thresh;
+        const RowSource& src = c.kernel_only == DSP_ROUTE_THRESH ? c.only_src : none;
+        H(c.kernel_only == DSP_ROUTE_THRESH), H(src.dtype), H(src.vec), H(src.io);
+        H(io(DSP_ROUTE_THRESH, A.thr)), H(io(DSP_ROUTE_THRESH, A.ts)), H(io(DSP_ROUTE_THRESH, A.out));
+    }
     if (c.kernel_only == DSP_ROUTE_EXTREMA) {
-        const ExtremaArgs& A = c.ext;
+        const ExtremaArgs& A = c.only.ext;
         H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.m), H(A.direction), H(A.par_stride), H(A.par_const), H(A.vt_stride), H(A.n_stride);
     }
     if (c.kernel_only == DSP_ROUTE_HIST) {
-        const HistArgs& A = c.hist;
+        const HistArgs& A = c.only.hist;
         H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.m), H(A.stats), H(A.max_blocks), H(A.w_stride), H(A.b_stride), H(A.w_in_stride), H(A.e_in_stride), H(A.w_in_offset), H(A.e_in_offset);
         H(A.max_in_stride), H(A.max_in_const), H(A.s_stride);
     }
     if (c.kernel_only == DSP_ROUTE_THRESH) {
-        const ThreshArgs& A = c.thresh;
+        const ThreshArgs& A = c.only.thresh;
         H(A.wf_stride), H(A.wf_offset), H(A.len), H(A.m), H(A.polarity), H(A.mode), H(A.thr_stride), H(A.thr_offset), H(A.thr_const), H(A.ts_stride), H(A.ts_const), H(A.out_stride);
     }
 }
@@ -1057,6 +1123,22 @@ int main(int argc, char** argv) {
     const bool with_digest = argc > 3 && !strcmp(argv[3], "digest");
     Digest digest;
     rng.seed(seed);
+    // the one kernel-only route no generator here or in tests/*_plan_fuzz.cpp draws: psd and fft of rows and spectra that start off their
+    // bindings' first element, planned and checked ahead of the drawn programs (no draw is spent, nothing enters the digest)
+    for (const int opcode : {DSP_OP_PSD, DSP_OP_FFT}) {
+        Prog p;
+        const int n = 24, bins = n / 2 + 1, m = opcode == DSP_OP_FFT ? 2 * bins : bins;
+        p.slots = {n, m};
+        const int in = add_io(p, DSP_IO_WF_IN, DSP_F32, n, 5, n + 9), out = add_io(p, DSP_IO_WF_OUT, DSP_F32, m, 3, m + 3);
+        for (const int code : {DSP_OP_LOAD, opcode, DSP_OP_STORE}) p.ops.push_back(op0(code));
+        p.ops[0].dst = 0, p.ops[0].io = in, p.ops[1].dst = 1, p.ops[1].src = 0, p.ops[2].src = 1, p.ops[2].io = out;
+        ChainPlan plan;
+        const int rc = dsp_plan_build(&plan, p.ops.data(), 3, p.io.data(), 2, p.slots.data(), 2, 0, DSP_F32);
+        if (rc != DSP_OK || plan.kernel_only != DSP_ROUTE_SPECTRUM || !check(p, plan)) {
+            fprintf(stderr, "the fixed %s program: code %d, %s\n", opcode == DSP_OP_PSD ? "psd" : "fft", rc, dsp_plan_last_error());
+            return 1;
+        }
+    }
     long accepted = 0, by_kind[12] = {0}, n_integer = 0;
     long kernels[14] = {0};
     for (long it = 0; it < n_programs; ++it) {

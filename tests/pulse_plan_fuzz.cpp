@@ -7,21 +7,10 @@
 //                                                  "ratio_columns": .., "refused_by_name": .., "refused_shape": .., "refused_long": ..,
 //                                                  "refused_width": .., "refused_lengths": .., "refused_return": ..}
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -43,20 +32,6 @@ double wild_value() {
         case 3: return (double)draw(-5, 5) * 1e30;
         default: return (double)draw(-3, 300);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
 }
 
 Prog draw_program() {
@@ -152,14 +127,6 @@ bool holds_op(const Prog& p) {
     return false;
 }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_op(p)) return true;  // (a mutation took the ops out: any route, tests/planner_fuzz.cpp's business)
     if (c.kernel_only != DSP_ROUTE_PULSES) {
@@ -168,7 +135,7 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     }
     REQUIRE(dsp_plan_route(&c) == DSP_ROUTE_PULSES);
     REQUIRE(std::strcmp(dsp_plan_kernel_name(&c), "dsp_pulses_kernel") == 0);
-    const PulsesArgs& A = c.pulses;
+    const PulsesArgs& A = c.only.pulses;
     const size_t n_ops = p.ops.size();
     REQUIRE(n_ops >= 4 && n_ops <= 7 && p.ops[0].opcode == DSP_OP_LOAD && p.ops[1].opcode == DSP_OP_LOAD);
     REQUIRE((A.pick == 0 || A.pick == 1) && (A.amp == 0 || A.amp == 1) && (A.pick || A.amp));
@@ -181,33 +148,44 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     REQUIRE(ld.dst == first.src && lt.dst == first.ip[0] && ld.dst != lt.dst);
     REQUIRE(A.len >= 1 && A.len == in.len && A.wf_offset == in.offset && A.wf_stride == in.row_stride);
     REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len);
-    REQUIRE(c.pulses_src.io == ld.io && c.pulses_src.dtype == in.dtype && c.uio_list == lt.io);
-    REQUIRE(!c.pulses_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(c.only_src.io == ld.io && c.only_src.dtype == in.dtype && c.bound_io(A.list) == lt.io);
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                   (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
     REQUIRE(p.dtype == DSP_F64 ? in.dtype == DSP_F64 : (in.dtype == DSP_F32 || in.dtype == DSP_I16 || in.dtype == DSP_U16));
     // the kernel's bounds: an entry per lane, the list inside its rows, the width within the row
     REQUIRE(A.m >= 1 && A.m <= DSP_PEAKS_MAX && li.kind == DSP_IO_WF_IN && li.dtype == p.dtype && li.len == A.m && li.offset >= 0);
     REQUIRE(A.list_stride == li.row_stride && A.list_offset == li.offset && li.row_stride >= (int64_t)li.offset + li.len);
     if (A.pick) {
-        REQUIRE(A.width >= 0 && A.width <= A.len && c.uio_n >= 0 && p.io[c.uio_n].kind == DSP_IO_SCALAR_OUT && p.io[c.uio_n].dtype == DSP_U32);
-        REQUIRE(c.uio_ratio < 0 || (p.io[c.uio_ratio].kind == DSP_IO_SCALAR_IN && p.io[c.uio_ratio].dtype == p.dtype));
+        REQUIRE(A.width >= 0 && A.width <= A.len && c.bound_io(A.n_out) >= 0 && p.io[c.bound_io(A.n_out)].kind == DSP_IO_SCALAR_OUT && p.io[c.bound_io(A.n_out)].dtype == DSP_U32);
+        REQUIRE(c.bound_io(A.ratio) < 0 || (p.io[c.bound_io(A.ratio)].kind == DSP_IO_SCALAR_IN && p.io[c.bound_io(A.ratio)].dtype == p.dtype));
         REQUIRE(first.sp[1].kind == DSP_ARG_CONST && first.sp[1].value >= 0 && std::isfinite(first.sp[1].value));
         REQUIRE(A.width == (first.sp[1].value >= A.len ? A.len : (int)first.sp[1].value));
     } else {
-        REQUIRE(c.uio_n < 0 && c.uio_ratio < 0 && c.uio_idx < 0 && A.width == 0);
+        REQUIRE(c.bound_io(A.n_out) < 0 && c.bound_io(A.ratio) < 0 && c.bound_io(A.idx_out) < 0 && A.width == 0);
     }
     if (A.amp) {
-        REQUIRE(A.m < A.len && c.uio_amp >= 0);
-        const dsp_io_desc& out = p.io[c.uio_amp];
+        REQUIRE(A.m < A.len && c.bound_io(A.amp_out) >= 0);
+        const dsp_io_desc& out = p.io[c.bound_io(A.amp_out)];
         REQUIRE(out.kind == DSP_IO_WF_OUT && out.dtype == p.dtype && out.len == A.m && out.row_stride >= out.len && A.amp_stride == out.row_stride);
     } else {
-        REQUIRE(c.uio_amp < 0 && c.uio_idx >= 0);
+        REQUIRE(c.bound_io(A.amp_out) < 0 && c.bound_io(A.idx_out) >= 0);
     }
-    if (c.uio_idx >= 0) {
-        const dsp_io_desc& out = p.io[c.uio_idx];
+    if (c.bound_io(A.idx_out) >= 0) {
+        const dsp_io_desc& out = p.io[c.bound_io(A.idx_out)];
         REQUIRE(A.pick && out.kind == DSP_IO_WF_OUT && out.dtype == p.dtype && out.len == A.m && out.row_stride >= out.len && A.idx_stride == out.row_stride);
-        REQUIRE(c.uio_idx != c.uio_amp);
+        REQUIRE(c.bound_io(A.idx_out) != c.bound_io(A.amp_out));
     }
+    // ---- the pointers a launch hands the kernel, from the program: rows and list as they are handed in, the column and the outputs at their
+    // first element, null what the program has not
+    const dsp_op* pk = A.pick ? &p.ops[2] : nullptr;
+    const dsp_op* am = A.amp ? &p.ops[2 + A.pick] : nullptr;
+    int idx_io = -1, amp_io = -1;
+    for (size_t i = 2 + A.pick + A.amp; i < n_ops; ++i)
+        if (p.ops[i].opcode == DSP_OP_STORE) (pk && p.ops[i].src == pk->dst ? idx_io : amp_io) = p.ops[i].io;
+    const KernelOnlyArgs launch = launch_args(p, c);
+    const PulsesArgs& L = launch.pulses;
+    REQUIRE(L.wf == raw_of(ld.io) && L.list == raw_of(lt.io) && L.ratio == first_of(p, pk ? column_of(*pk, 0) : -1));
+    REQUIRE(L.idx_out == first_of(p, idx_io) && L.amp_out == first_of(p, am ? amp_io : -1) && L.n_out == first_of(p, pk ? p.ops[n_ops - 1].io : -1));
     return true;
 }
 
@@ -219,15 +197,9 @@ int main(int argc, char** argv) {
     long accepted = 0, picker = 0, pickoff = 0, fused = 0, fused_list = 0, columns = 0, by_name = 0, shape = 0, too_long = 0, width = 0, lengths = 0, ret = 0;
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             const bool s = std::strstr(why, "DSP_OP_PEAK_SNR_THRESHOLD / DSP_OP_MULTI_A_FILTER (peak_snr_threshold, multi_a_filter) run on dsp_pulses_kernel only") != nullptr;
             const bool l = std::strstr(why, ": a wavefront keeps one per lane") != nullptr && (std::strstr(why, "candidates") || std::strstr(why, "positions"));
             const bool w = std::strstr(why, "width_in is a") != nullptr;
@@ -239,15 +211,15 @@ int main(int argc, char** argv) {
         }
         if (!check(number, p, *plan)) return 1;
         if (holds_op(p) && plan->kernel_only == DSP_ROUTE_PULSES) {
-            const PulsesArgs& A = plan->pulses;
+            const PulsesArgs& A = plan->only.pulses;
             ++accepted;
             if (A.pick && A.amp) {
                 ++fused;
-                fused_list += plan->uio_idx >= 0;
+                fused_list += plan->bound_io(plan->only.pulses.idx_out) >= 0;
             } else {
                 ++(A.pick ? picker : pickoff);
             }
-            columns += A.pick && plan->uio_ratio >= 0;
+            columns += A.pick && plan->bound_io(plan->only.pulses.ratio) >= 0;
         }
     }
     std::printf("{\"programs\": %ld, \"accepted\": %ld, \"picker\": %ld, \"pickoff\": %ld, \"fused\": %ld, \"fused_list_stored\": %ld, \"ratio_columns\": %ld, "

@@ -5,20 +5,9 @@
 // with an argument block that names the bindings' geometry and an LDS footprint that fits.
 //   reflect_plan_fuzz <programs> <seed>     prints {"programs": .., "accepted": .., "plain": .., "fused": .., "fused_row_stored": .., "narrow": ..,
 //                                                    "wide": .., "refused_by_name": .., "refused_shape": .., "refused_long": .., "refused_limit": ..}
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -31,20 +20,6 @@ int64_t wild_length() {
         case 6: return 0x7fffffff - draw(0, 3);
         default: return draw(1, 20000);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
 }
 
 Prog draw_program() {
@@ -117,14 +92,6 @@ bool holds_op(const Prog& p) {
     return false;
 }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_op(p)) return true;  // (a mutation took the op out: any route, tests/planner_fuzz.cpp's business)
     if (c.kernel_only != DSP_ROUTE_REFLECT) {  // (a mutation put an op of an earlier kernel-only route in as well and the program has that shape: impossible)
@@ -138,29 +105,37 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     const bool fused = p.ops[2].opcode == DSP_OP_AVG_CURRENT;
     for (size_t i = fused ? 3 : 2; i < n_ops; ++i) REQUIRE(p.ops[i].opcode == DSP_OP_STORE);
     REQUIRE(n_ops == (fused ? 4u : 3u) || (fused && n_ops == 5));
-    const ReflectArgs& A = c.reflect;
+    const ReflectArgs& A = c.only.reflect;
     const dsp_io_desc &in = p.io[p.ops[0].io], &taps = p.io[p.ops[1].io];
     const int esz = p.dtype == DSP_F64 ? 8 : 4;
     REQUIRE(A.len >= 1 && A.n_taps >= 1 && A.n_taps <= A.len && dsp_reflect::fits(A.len, A.n_taps, esz));
     REQUIRE(A.len == in.len && A.wf_offset == in.offset && A.wf_stride == in.row_stride && A.n_taps == taps.len);
-    REQUIRE(taps.kind == DSP_IO_TAPS && taps.dtype == p.dtype && c.rio_taps == p.ops[1].io);
+    REQUIRE(taps.kind == DSP_IO_TAPS && taps.dtype == p.dtype && c.bound_io(A.taps) == p.ops[1].io);
     REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len);
     REQUIRE(A.wide == (dsp_reflect::wide(A.len, A.n_taps, esz) ? 1 : 0) && (A.taps_nan == 0 || A.taps_nan == 1));
     REQUIRE(dsp_reflect::lds_bytes(A.len, A.n_taps, esz) <= 64 * 1024 + 32 + 16 && dsp_reflect::row_bytes(A.len, A.n_taps, esz) >= dsp_reflect::staged(A.len, A.n_taps) * esz);
-    REQUIRE(c.reflect_src.io == p.ops[0].io && c.reflect_src.dtype == in.dtype);
-    REQUIRE(!c.reflect_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(c.only_src.io == p.ops[0].io && c.only_src.dtype == in.dtype);
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                    (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
-    if (c.rio_out >= 0) {
-        const dsp_io_desc& out = p.io[c.rio_out];
+    if (c.bound_io(A.out) >= 0) {
+        const dsp_io_desc& out = p.io[c.bound_io(A.out)];
         REQUIRE(out.kind == DSP_IO_WF_OUT && out.dtype == p.dtype && out.len == A.len && out.row_stride >= out.len && A.out_stride == out.row_stride);
     }
     if (fused) {
-        REQUIRE(c.rio_cur >= 0 && A.lag >= 1 && A.lag < A.len && A.lag == (int)A.length && A.length >= 1.0);
-        const dsp_io_desc& cur = p.io[c.rio_cur];
+        REQUIRE(c.bound_io(A.cur) >= 0 && A.lag >= 1 && A.lag < A.len && A.lag == (int)A.length && A.length >= 1.0);
+        const dsp_io_desc& cur = p.io[c.bound_io(A.cur)];
         REQUIRE(cur.kind == DSP_IO_WF_OUT && cur.dtype == p.dtype && cur.len == A.len - A.lag && cur.row_stride >= cur.len && A.cur_stride == cur.row_stride);
     } else {
-        REQUIRE(c.rio_cur < 0 && A.lag == 0 && c.rio_out >= 0);
+        REQUIRE(c.bound_io(A.cur) < 0 && A.lag == 0 && c.bound_io(A.out) >= 0);
     }
+    // ---- the pointers a launch hands the kernel, from the program: the rows as they are handed in, taps and outputs at their first element,
+    // null what is not stored; 16-byte stores of the filtered row where its start and stride are whole vectors
+    int out_io = -1, cur_io = -1;
+    for (size_t i = fused ? 3 : 2; i < n_ops; ++i) (fused && p.ops[i].src == p.ops[2].dst ? cur_io : out_io) = p.ops[i].io;
+    const KernelOnlyArgs launch = launch_args(p, c);
+    const ReflectArgs& L = launch.reflect;
+    REQUIRE(L.wf == raw_of(p.ops[0].io) && L.taps == first_of(p, p.ops[1].io) && L.out == first_of(p, out_io) && L.cur == first_of(p, cur_io));
+    REQUIRE(L.out_vec == vector_store(p, out_io, esz));
     return true;
 }
 
@@ -172,15 +147,9 @@ int main(int argc, char** argv) {
     long accepted = 0, plain = 0, fused = 0, fused_row = 0, narrow = 0, wide = 0, by_name = 0, shape = 0, too_long = 0, limit = 0;
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             const bool s = std::strstr(why, "DSP_OP_REFLECTED_CONVOLVE (reflected_convolve_wf) runs on dsp_reflect_kernel only") != nullptr;
             const bool l = std::strstr(why, "The filter is longer than the input waveform") != nullptr;
             const bool x = std::strstr(why, "reflected_convolve_wf: len(w_in) + len(kernel) - 1 of up to") != nullptr;
@@ -191,10 +160,10 @@ int main(int argc, char** argv) {
         if (!check(number, p, *plan)) return 1;
         if (holds_op(p)) {
             ++accepted;
-            ++(plan->reflect.wide ? wide : narrow);
-            if (plan->reflect.lag > 0) {
+            ++(plan->only.reflect.wide ? wide : narrow);
+            if (plan->only.reflect.lag > 0) {
                 ++fused;
-                fused_row += plan->rio_out >= 0;
+                fused_row += plan->bound_io(plan->only.reflect.out) >= 0;
             } else {
                 ++plain;
             }

@@ -3,20 +3,9 @@
 // tests/planner_fuzz.cpp draws the opcodes before this one and stays as it is.  Every program is planned or refused; a planned one runs on
 // dsp_sort_kernel with an argument block that names the bindings' geometry and fits the kernel's LDS.
 //   sort_plan_fuzz <programs> <seed>     prints {"programs": .., "accepted": .., "narrow": .., "wide": .., "refused_by_name": ..}
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -29,20 +18,6 @@ int64_t wild_length() {
         case 6: return 0x7fffffff - draw(0, 3);
         default: return draw(1, 20000);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
 }
 
 Prog draw_program() {
@@ -94,20 +69,12 @@ bool holds_sort(const Prog& p) {
     return false;
 }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_sort(p)) return true;  // (a mutation took the op out: any route, tests/planner_fuzz.cpp's business)
     REQUIRE(dsp_plan_route(&c) == DSP_ROUTE_SORT && c.kernel_only == DSP_ROUTE_SORT);
     REQUIRE(std::strcmp(dsp_plan_kernel_name(&c), "dsp_sort_kernel") == 0);
     REQUIRE(p.ops.size() == 3 && p.ops[0].opcode == DSP_OP_LOAD && p.ops[1].opcode == DSP_OP_SORT && p.ops[2].opcode == DSP_OP_STORE);
-    const SortArgs& A = c.sort;
+    const SortArgs& A = c.only.sort;
     const dsp_io_desc &in = p.io[p.ops[0].io], &out = p.io[p.ops[2].io];
     const int esz = p.dtype == DSP_F64 ? 8 : 4;
     REQUIRE(A.len >= 1 && A.len <= DSP_SORT_F32_MAX / (esz / 4));
@@ -115,8 +82,11 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len && out.row_stride >= out.len && out.dtype == p.dtype);
     REQUIRE(A.padded == dsp_sort::padded(A.len) && A.padded >= A.len && A.wide == (dsp_sort::wide(A.len) ? 1 : 0));
     REQUIRE(dsp_sort::lds_bytes(A.len, esz) <= 64 * 1024 + 16);
-    REQUIRE(c.sort_src.io == p.ops[0].io && c.sort_src.dtype == in.dtype && c.oio_out == p.ops[2].io);
-    REQUIRE(!c.sort_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(c.only_src.io == p.ops[0].io && c.only_src.dtype == in.dtype && c.bound_io(A.out) == p.ops[2].io);
+    // ---- the pointers a launch hands the kernel, from the program: the rows as they are handed in, the output at its first element
+    const KernelOnlyArgs launch = launch_args(p, c);
+    REQUIRE(launch.sort.wf == raw_of(p.ops[0].io) && launch.sort.out == first_of(p, p.ops[2].io));
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                 (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
     return true;
 }
@@ -129,22 +99,16 @@ int main(int argc, char** argv) {
     long accepted = 0, narrow = 0, wide = 0, by_name = 0;
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             if (std::strstr(why, "DSP_OP_SORT (sort) runs on dsp_sort_kernel only") || std::strstr(why, "sort: rows of up to")) ++by_name;
             continue;
         }
         if (!check(number, p, *plan)) return 1;
         if (holds_sort(p)) {
             ++accepted;
-            ++(plan->sort.wide ? wide : narrow);
+            ++(plan->only.sort.wide ? wide : narrow);
         }
     }
     std::printf("{\"programs\": %ld, \"accepted\": %ld, \"narrow\": %ld, \"wide\": %ld, \"refused_by_name\": %ld}\n", programs, accepted, narrow, wide, by_name);

@@ -4,20 +4,9 @@
 // Every program is planned or refused; a planned one runs on dsp_svm_kernel with an argument block that names bindings of the right kind
 // and size and fits the kernel's LDS and accumulators.
 //   svm_plan_fuzz <programs> <seed>     prints {"programs": .., "accepted": .., "with_decisions": .., "f64": .., "refused_by_name": ..}
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -30,26 +19,6 @@ int64_t wild_length() {
         case 6: return 0x7fffffff - draw(0, 3);
         default: return draw(1, 20000);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
-}
-
-int32_t clip(int64_t v) { return (int32_t)(v > 0x7fffffff ? 0x7fffffff : v < -0x7fffffff ? -0x7fffffff : v); }
-int64_t times(int64_t a, int64_t b) {  // a product that saturates instead of overflowing
-    const __int128 v = (__int128)a * b;
-    return v > 0x7fffffff ? 0x7fffffff : v < -0x7fffffff ? -0x7fffffff : (int64_t)v;
 }
 
 Prog draw_program() {
@@ -121,14 +90,6 @@ bool holds_svm(const Prog& p) {
     return false;
 }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_svm(p)) return true;  // (a mutation took the op out: any route, tests/planner_fuzz.cpp's business)
     // (an op of another kernel-only route beside ours belongs to that route, whose shapes hold no SVM_PREDICT: such a program is refused, never accepted)
@@ -136,7 +97,7 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     REQUIRE(dsp_plan_route(&c) == DSP_ROUTE_SVM && std::strcmp(dsp_plan_kernel_name(&c), "dsp_svm_kernel") == 0);
     REQUIRE(p.ops.size() == 3 && p.ops[0].opcode == DSP_OP_LOAD && p.ops[1].opcode == DSP_OP_SVM_PREDICT && p.ops[2].opcode == DSP_OP_STORE_SCALAR);
     const dsp_op &op = p.ops[1], &st = p.ops[2];
-    const SvmArgs& A = c.svm;
+    const SvmArgs& A = c.only.svm;
     const dsp_io_desc &in = p.io[p.ops[0].io], &out = p.io[st.io];
     REQUIRE(A.len >= 1 && A.len <= DSP_DENSE_N_MAX && A.n_classes >= 2 && A.n_classes <= DSP_SVM_CLASSES_MAX && A.n_sv >= 1);
     REQUIRE(A.n_pairs == A.n_classes * (A.n_classes - 1) / 2 && A.n_pairs <= dsp_svm::P_MAX);
@@ -144,20 +105,25 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     REQUIRE(A.f64 == (p.dtype == DSP_F64) && out.dtype == p.dtype && out.kind == DSP_IO_SCALAR_OUT && A.label_stride == out.row_stride && (A.linear == 0 || A.linear == 1));
     REQUIRE(in.dtype == DSP_F32 || (in.dtype == DSP_F64 && p.dtype == DSP_F64));
     auto model = [&](int k, int64_t len) { return k >= 0 && k < (int)p.io.size() && p.io[k].kind == DSP_IO_TAPS && p.io[k].dtype == DSP_F64 && p.io[k].len == len; };
-    REQUIRE(c.vio_sv == op.io && model(c.vio_sv, (int64_t)A.n_sv * A.len) && c.vio_norm == op.ip[0] && model(c.vio_norm, A.n_sv));
-    REQUIRE(c.vio_coef == op.ip[1] && model(c.vio_coef, (int64_t)A.n_sv * A.n_pairs) && c.vio_icpt == op.ip[2] && model(c.vio_icpt, A.n_pairs));
-    REQUIRE(c.vio_cls == op.ip[3] && model(c.vio_cls, A.n_classes) && c.vio_label == st.io);
-    if (c.vio_dec >= 0) {
-        REQUIRE(c.vio_dec < (int)p.io.size());
-        const dsp_io_desc& d = p.io[c.vio_dec];
+    REQUIRE(c.bound_io(A.sv) == op.io && model(c.bound_io(A.sv), (int64_t)A.n_sv * A.len) && c.bound_io(A.sv_norm) == op.ip[0] && model(c.bound_io(A.sv_norm), A.n_sv));
+    REQUIRE(c.bound_io(A.coef) == op.ip[1] && model(c.bound_io(A.coef), (int64_t)A.n_sv * A.n_pairs) && c.bound_io(A.intercept) == op.ip[2] && model(c.bound_io(A.intercept), A.n_pairs));
+    REQUIRE(c.bound_io(A.classes) == op.ip[3] && model(c.bound_io(A.classes), A.n_classes) && c.bound_io(A.label) == st.io);
+    if (c.bound_io(A.dec) >= 0) {
+        REQUIRE(c.bound_io(A.dec) < (int)p.io.size());
+        const dsp_io_desc& d = p.io[c.bound_io(A.dec)];
         REQUIRE(d.kind == DSP_IO_WF_OUT && d.dtype == DSP_F64 && d.len == A.n_pairs && d.row_stride >= (int64_t)d.offset + d.len && A.dec_stride == d.row_stride);
     } else {
-        REQUIRE(c.vio_dec == -1);
+        REQUIRE(c.bound_io(A.dec) == -1);
     }
     REQUIRE(dsp_svm::lds_bytes(A.len, A.n_pairs) <= 149504 && dsp_svm::lds_bytes(A.len, A.n_pairs) <= LDS_BYTES_PER_CU);
     REQUIRE(dsp_svm::pair_blocks(A.n_pairs) <= dsp_svm::built_blocks(A.n_pairs) && dsp_svm::built_blocks(A.n_pairs) <= dsp_svm::PAIR_BLOCKS_MAX);
-    REQUIRE(c.svm_src.io == p.ops[0].io && c.svm_src.dtype == in.dtype);
-    REQUIRE(!c.svm_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(c.only_src.io == p.ops[0].io && c.only_src.dtype == in.dtype);
+    // ---- the pointers a launch hands the kernel, from the program: the rows as they are handed in, the model, the label and the decisions at their first element
+    const KernelOnlyArgs launch = launch_args(p, c);
+    const SvmArgs& L = launch.svm;
+    REQUIRE(L.wf == raw_of(p.ops[0].io) && L.sv == first_of(p, op.io) && L.sv_norm == first_of(p, op.ip[0]) && L.coef == first_of(p, op.ip[1]));
+    REQUIRE(L.intercept == first_of(p, op.ip[2]) && L.classes == first_of(p, op.ip[3]) && L.label == first_of(p, st.io) && L.dec == first_of(p, (int)op.sp[2].value));
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
     return true;
 }
@@ -170,22 +136,16 @@ int main(int argc, char** argv) {
     long accepted = 0, with_dec = 0, n_f64 = 0, by_name = 0;
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             if (std::strstr(why, "runs on dsp_svm_kernel only") || std::strstr(why, "svm_predict: ") || std::strstr(why, "bad SVM_PREDICT")) ++by_name;
             continue;
         }
         if (!check(number, p, *plan)) return 1;
         if (holds_svm(p) && plan->kernel_only == DSP_ROUTE_SVM) {
             ++accepted;
-            with_dec += plan->vio_dec >= 0;
+            with_dec += plan->bound_io(plan->only.svm.dec) >= 0;
             n_f64 += plan->f64;
         }
     }

@@ -8,21 +8,10 @@
 //                                                    "log_stored": .., "pars_stored": .., "subtracted": .., "refused_by_name": .., "refused_shape": ..,
 //                                                    "refused_many": .., "refused_power": ..}
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
-#include <memory>
-#include <random>
-#include <vector>
-
-#include "../dspeed_amd/csrc/dsp_plan.h"
+#include "plan_fuzz.h"
 
 namespace {
-
-std::mt19937_64 rng;
-int64_t draw(int64_t lo, int64_t hi) { return lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1)); }
-bool chance(int percent) { return draw(0, 99) < percent; }
 
 int64_t wild_length() {
     switch (draw(0, 9)) {
@@ -34,20 +23,6 @@ int64_t wild_length() {
         case 5: return 0x7fffffff - draw(0, 3);
         default: return draw(1, 20000);
     }
-}
-
-struct Prog {
-    std::vector<dsp_op> ops;
-    std::vector<dsp_io_desc> io;
-    std::vector<int32_t> slots;
-    int n_sregs = 0, dtype = DSP_F32;
-};
-
-dsp_op make_op(int opcode, int dst, int src, int io) {
-    dsp_op o;
-    std::memset(&o, 0, sizeof o);
-    o.opcode = opcode, o.dst = dst, o.src = src, o.io = io;
-    return o;
 }
 
 Prog draw_program() {
@@ -156,14 +131,6 @@ bool holds_op(const Prog& p) {
     return false;
 }
 
-#define REQUIRE(cond)                                                          \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::printf("program %ld: accepted, but not %s\n", number, #cond); \
-            return false;                                                      \
-        }                                                                      \
-    } while (0)
-
 bool check(long number, const Prog& p, const ChainPlan& c) {
     if (!holds_op(p)) return true;  // (a mutation took the ops out: any route, tests/planner_fuzz.cpp's business)
     if (c.kernel_only != DSP_ROUTE_TAILFIT) {
@@ -172,7 +139,7 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     }
     REQUIRE(dsp_plan_route(&c) == DSP_ROUTE_TAILFIT);
     REQUIRE(std::strcmp(dsp_plan_kernel_name(&c), "dsp_tailfit_kernel") == 0);
-    const TailfitArgs& A = c.tailfit;
+    const TailfitArgs& A = c.only.tailfit;
     const size_t n_ops = p.ops.size();
     REQUIRE(n_ops >= 3 && n_ops <= 9 && p.ops[0].opcode == DSP_OP_LOAD);
     int count[4] = {0, 0, 0, 0}, subs = 0, loads = 0;
@@ -183,46 +150,67 @@ bool check(long number, const Prog& p, const ChainPlan& c) {
     REQUIRE(count[0] == A.log && count[1] == A.fit && count[2] == (A.resid == 1) && count[3] == (A.resid == 2) && subs == A.sub_mode);
     REQUIRE((A.log == 0 || A.log == 1) && (A.fit == 0 || A.fit == 1) && A.resid >= 0 && A.resid <= 2 && (A.log || A.fit || A.resid));
     REQUIRE(!(A.log && A.resid && !A.fit) && (!A.resid_log || A.log) && loads == 1 + (A.resid && !A.fit ? 1 : 0));
-    const dsp_io_desc& in = p.io[c.tailfit_src.io];
+    const dsp_io_desc& in = p.io[c.only_src.io];
     REQUIRE(in.kind == DSP_IO_WF_IN && A.len >= 1 && A.len == in.len && A.wf_offset == in.offset && A.wf_stride == in.row_stride);
-    REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len && c.tailfit_src.dtype == in.dtype);
-    REQUIRE(!c.tailfit_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
+    REQUIRE(in.offset >= 0 && in.row_stride >= (int64_t)in.offset + in.len && c.only_src.dtype == in.dtype);
+    REQUIRE(!c.only_src.vec || ((in.row_stride * dsp_elem_size(in.dtype)) % 16 == 0 && (in.offset * dsp_elem_size(in.dtype)) % 16 == 0 &&
                                    (in.len * dsp_elem_size(in.dtype)) % 16 == 0));
     REQUIRE(p.dtype == DSP_F64 ? in.dtype == DSP_F64 : (in.dtype == DSP_F32 || in.dtype == DSP_I16 || in.dtype == DSP_U16));
-    if (A.sub_mode) REQUIRE(c.aio_sub < 0 || (p.io[c.aio_sub].kind == DSP_IO_SCALAR_IN && p.io[c.aio_sub].dtype == p.dtype));
+    if (A.sub_mode) REQUIRE(c.bound_io(A.sub) < 0 || (p.io[c.bound_io(A.sub)].kind == DSP_IO_SCALAR_IN && p.io[c.bound_io(A.sub)].dtype == p.dtype));
     if (A.fit || A.resid) REQUIRE(A.m >= 1 && A.m <= DSP_POLY_MAX && dsp_poly_powers_fit(A.len, A.m));
     if (A.fit) {
-        REQUIRE(c.aio_inv >= 0 && c.aio_pars < 0);
-        const dsp_io_desc& inv = p.io[c.aio_inv];
+        REQUIRE(c.bound_io(A.inv) >= 0 && c.bound_io(A.pars) < 0);
+        const dsp_io_desc& inv = p.io[c.bound_io(A.inv)];
         REQUIRE(inv.kind == DSP_IO_TAPS && inv.dtype == DSP_F64 && inv.len == A.m * A.m);
     } else {
-        REQUIRE(c.aio_inv < 0 && c.aio_pars_out < 0);
+        REQUIRE(c.bound_io(A.inv) < 0 && c.bound_io(A.pars_out) < 0);
     }
     if (A.resid && !A.fit) {
-        REQUIRE(c.aio_pars >= 0);
-        const dsp_io_desc& pars = p.io[c.aio_pars];
+        REQUIRE(c.bound_io(A.pars) >= 0);
+        const dsp_io_desc& pars = p.io[c.bound_io(A.pars)];
         REQUIRE(pars.kind == DSP_IO_WF_IN && pars.dtype == p.dtype && pars.len == A.m && pars.offset >= 0 && pars.row_stride >= (int64_t)pars.offset + pars.len);
         REQUIRE(A.pars_stride == pars.row_stride && A.pars_offset == pars.offset);
     }
-    if (c.aio_out >= 0) {
-        const dsp_io_desc& out = p.io[c.aio_out];
+    if (c.bound_io(A.out) >= 0) {
+        const dsp_io_desc& out = p.io[c.bound_io(A.out)];
         REQUIRE(A.log && out.kind == DSP_IO_WF_OUT && out.dtype == p.dtype && out.len == A.len && out.row_stride >= out.len && A.out_stride == out.row_stride);
     } else {
         REQUIRE(!A.log || A.fit);
     }
-    if (c.aio_pars_out >= 0) {
-        const dsp_io_desc& out = p.io[c.aio_pars_out];
+    if (c.bound_io(A.pars_out) >= 0) {
+        const dsp_io_desc& out = p.io[c.bound_io(A.pars_out)];
         REQUIRE(A.fit && out.kind == DSP_IO_WF_OUT && out.dtype == p.dtype && out.len == A.m && out.row_stride >= out.len && A.pars_out_stride == out.row_stride);
-        REQUIRE(c.aio_pars_out != c.aio_out);
+        REQUIRE(c.bound_io(A.pars_out) != c.bound_io(A.out));
     } else {
         REQUIRE(!A.fit || A.resid);
     }
     if (A.resid) {
-        REQUIRE(c.aio_mean >= 0 && c.aio_rms >= 0 && c.aio_mean != c.aio_rms);
-        for (int k : {c.aio_mean, c.aio_rms}) REQUIRE(p.io[k].kind == DSP_IO_SCALAR_OUT && p.io[k].dtype == p.dtype);
+        REQUIRE(c.bound_io(A.mean_out) >= 0 && c.bound_io(A.rms_out) >= 0 && c.bound_io(A.mean_out) != c.bound_io(A.rms_out));
+        for (int k : {c.bound_io(A.mean_out), c.bound_io(A.rms_out)}) REQUIRE(p.io[k].kind == DSP_IO_SCALAR_OUT && p.io[k].dtype == p.dtype);
     } else {
-        REQUIRE(c.aio_mean < 0 && c.aio_rms < 0);
+        REQUIRE(c.bound_io(A.mean_out) < 0 && c.bound_io(A.rms_out) < 0);
     }
+    // ---- the pointers a launch hands the kernel, from the program: rows and loaded coefficients as they are handed in, column, matrix and outputs
+    // at their first element, null what the program has not; 16-byte stores of the logged row where its start and stride are whole vectors
+    const dsp_op *lg = nullptr, *ft = nullptr, *rs = nullptr, *bs = nullptr;
+    for (const dsp_op& o : p.ops) {
+        if (o.opcode == DSP_OP_LOG_CHECK) lg = &o;
+        if (o.opcode == DSP_OP_POLY_FIT) ft = &o;
+        if (o.opcode == DSP_OP_POLY_DIFF || o.opcode == DSP_OP_POLY_EXP_RMS) rs = &o;
+        if (o.opcode == DSP_OP_BL_SUBTRACT) bs = &o;
+    }
+    const dsp_op& first = lg ? *lg : (ft ? *ft : *rs);
+    int rows_io = -1, pars_io = -1, out_io = -1, pars_out_io = -1, mean_io = -1, rms_io = -1;
+    for (const dsp_op& o : p.ops) {
+        if (o.opcode == DSP_OP_LOAD) (o.dst == first.src ? rows_io : pars_io) = o.io;
+        if (o.opcode == DSP_OP_STORE) (lg && o.src == lg->dst ? out_io : pars_out_io) = o.io;
+        if (o.opcode == DSP_OP_STORE_SCALAR) (o.ip[0] == rs->dst ? mean_io : rms_io) = o.io;
+    }
+    const KernelOnlyArgs launch = launch_args(p, c);
+    const TailfitArgs& L = launch.tailfit;
+    REQUIRE(L.wf == raw_of(rows_io) && L.pars == raw_of(pars_io) && L.sub == first_of(p, bs ? column_of(*bs, 0) : -1) && L.inv == first_of(p, ft ? ft->io : -1));
+    REQUIRE(L.out == first_of(p, out_io) && L.pars_out == first_of(p, pars_out_io) && L.mean_out == first_of(p, mean_io) && L.rms_out == first_of(p, rms_io));
+    REQUIRE(L.out_vec == vector_store(p, out_io, p.dtype == DSP_F64 ? 8 : 4));
     return true;
 }
 
@@ -234,15 +222,9 @@ int main(int argc, char** argv) {
     long accepted = 0, log = 0, fit = 0, resid = 0, log_fit = 0, chain = 0, log_stored = 0, pars_stored = 0, subtracted = 0, by_name = 0, shape = 0, many = 0, power = 0;
     for (long number = 0; number < programs; ++number) {
         const Prog p = draw_program();
-        std::unique_ptr<ChainPlan> plan(new ChainPlan());
-        const int rc = dsp_plan_build(plan.get(), p.ops.data(), (int)p.ops.size(), p.io.data(), (int)p.io.size(), p.slots.data(), (int)p.slots.size(),
-                                      p.n_sregs, p.dtype);
-        if (rc != DSP_OK) {
-            const char* why = dsp_plan_last_error();
-            if (!why || !*why) {
-                std::printf("program %ld: refused (%d) without a reason\n", number, rc);
-                return 1;
-            }
+        const char* why = nullptr;
+        const std::unique_ptr<ChainPlan> plan = plan_or_refuse(number, p, &why);
+        if (!plan) {
             const bool s = std::strstr(why, "(log_check, poly_fit, poly_diff, poly_exp_rms) run on dsp_tailfit_kernel only") != nullptr;
             const bool c = std::strstr(why, "a lane keeps one float64 accumulator each") != nullptr;
             const bool w = std::strstr(why, "int64 power i**j wraps silently") != nullptr;
@@ -253,13 +235,13 @@ int main(int argc, char** argv) {
         }
         if (!check(number, p, *plan)) return 1;
         if (holds_op(p)) {
-            const TailfitArgs& A = plan->tailfit;
+            const TailfitArgs& A = plan->only.tailfit;
             ++accepted;
             if (A.fit && A.resid) ++chain;
             else if (A.log && A.fit) ++log_fit;
             else ++(A.log ? log : (A.fit ? fit : resid));
-            log_stored += A.fit && plan->aio_out >= 0;
-            pars_stored += A.resid && plan->aio_pars_out >= 0;
+            log_stored += A.fit && plan->bound_io(plan->only.tailfit.out) >= 0;
+            pars_stored += A.resid && plan->bound_io(plan->only.tailfit.pars_out) >= 0;
             subtracted += A.sub_mode;
         }
     }

@@ -5,43 +5,19 @@ AddressSanitizer and UndefinedBehaviorSanitizer: a stand-alone program with a ``
 and strides -- each processor alone, wf_alignment -> wf_correction with the aligned row stored or not --: each is planned -- in one of the five
 shapes, on dsp_align_kernel, with an argument block whose lengths, indices and bindings are in range -- or refused with a reason.  The rule of
 a window (dsp_align_window, which the kernel runs per row) is held inside the row for every centroid, shift and size beside it."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dspeed_amd", "csrc")
-FLAGS = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include")]
+from plan_fuzz_util import build, run
 
 
 @pytest.fixture(scope="module")
 def fuzzer(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    probe = subprocess.run(["g++", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(probe) and os.path.exists(probe)):
-        pytest.skip("g++ has no AddressSanitizer runtime here")
-    exe = str(tmp_path_factory.mktemp("align_plan_fuzz") / "align_plan_fuzz")
-    subprocess.check_call(FLAGS + [os.path.join(ROOT, "tests", "align_plan_fuzz.cpp"), os.path.join(CSRC, "dsp_plan.cpp"), "-o", exe])
-    return exe
-
-
-def _run(cmd):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    for k in list(env):
-        if k.startswith("DSPEED_HIP_"):
-            del env[k]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, (r.stdout[-3000:] + r.stderr[-6000:])
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return build(tmp_path_factory.mktemp("align_plan_fuzz"), "align_plan_fuzz")
 
 
 @pytest.mark.parametrize("seed", [0x2F, 7])
 def test_programs_with_the_ops_plan_clean_under_asan_and_ubsan(fuzzer, seed):
-    rep = _run([fuzzer, "20000", str(seed)])
+    rep = run([fuzzer, "20000", str(seed)])
     assert rep["programs"] == 20000
     # every shape was planned: each processor alone, the pair with the aligned row stored and without, a centroid per event, integer rows ...
     assert min(rep["inl"], rep["centroid"], rep["align"], rep["correct"], rep["fused"]) > 200, rep

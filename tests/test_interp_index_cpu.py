@@ -8,41 +8,14 @@ length up to the limits.
 
 ``tests/interp_plan_fuzz.cpp`` feeds ``dsp_plan_build`` programs that hold the op with wild modes, lengths, slots, offsets and strides:
 each is planned -- on dsp_interp_kernel, with an argument block that fits its LDS -- or refused with a reason."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dspeed_amd", "csrc")
-FLAGS = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include")]
+from plan_fuzz_util import build, run
 
 
-@pytest.fixture(scope="module")
-def sanitizers():
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    probe = subprocess.run(["g++", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(probe) and os.path.exists(probe)):
-        pytest.skip("g++ has no AddressSanitizer runtime here")
-
-
-def _run(cmd):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    for k in list(env):
-        if k.startswith("DSPEED_HIP_"):
-            del env[k]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, (r.stdout[-3000:] + r.stderr[-6000:])
-    return json.loads(r.stdout.strip().splitlines()[-1])
-
-
-def test_the_index_map_is_the_references_loops_run_forward(sanitizers, tmp_path):
-    exe = str(tmp_path / "interp_index")
-    subprocess.check_call(FLAGS + [os.path.join(ROOT, "tests", "interp_index.cpp"), "-o", exe])
-    rep = _run([exe])
+def test_the_index_map_is_the_references_loops_run_forward(tmp_path):
+    exe = build(tmp_path, "interp_index", with_planner=False)
+    rep = run([exe])
     # 130 x 400 pairs; per pair m outputs in each of the six modes that always apply ('h' from n = 2 on) and in 'i' where n divides m
     outputs = sum(m * (5 + (n >= 2) + (m % n == 0)) for n in range(1, 131) for m in range(1, 401))
     assert rep["pairs"] == 130 * 400 and rep["outputs"] == outputs and rep["failures"] == 0
@@ -50,15 +23,13 @@ def test_the_index_map_is_the_references_loops_run_forward(sanitizers, tmp_path)
 
 
 @pytest.fixture(scope="module")
-def fuzzer(sanitizers, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("interp_plan_fuzz") / "interp_plan_fuzz")
-    subprocess.check_call(FLAGS + [os.path.join(ROOT, "tests", "interp_plan_fuzz.cpp"), os.path.join(CSRC, "dsp_plan.cpp"), "-o", exe])
-    return exe
+def fuzzer(tmp_path_factory):
+    return build(tmp_path_factory.mktemp("interp_plan_fuzz"), "interp_plan_fuzz")
 
 
 @pytest.mark.parametrize("seed", [0x17E, 2])
 def test_programs_with_the_op_plan_clean_under_asan_and_ubsan(fuzzer, seed):
-    rep = _run([fuzzer, "20000", str(seed)])
+    rep = run([fuzzer, "20000", str(seed)])
     assert rep["programs"] == 20000
     # both geometries and all seven modes were planned, and refusals by name were reached: the shape's, the mode's and the limits'
     assert rep["narrow"] > 500 and rep["wide"] > 1000 and rep["accepted"] == rep["narrow"] + rep["wide"] and rep["refused_by_name"] > 500, rep

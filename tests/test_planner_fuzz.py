@@ -7,40 +7,19 @@ specialised kernels' shapes with random geometry and single-field mutations -- a
 alive together never share LDS, regions and register file inside the wavefront's LDS and the CU's 160 kB, a specialised kernel's argument
 block carrying the bindings' offsets / strides / lengths.  (What this found when first run: four signed overflows on out-of-range slot
 lengths, register indices, binding offsets and fit windows -- all now refused with DSP_ERR_ARG / DSP_ERR_TOO_LONG.)"""
-import json
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dspeed_amd", "csrc")
+from plan_fuzz_util import build, run
 
 
 @pytest.fixture(scope="module")
 def fuzzer(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    probe = subprocess.run(["g++", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(probe) and os.path.exists(probe)):
-        pytest.skip("g++ has no AddressSanitizer runtime here")
-    exe = str(tmp_path_factory.mktemp("planner_fuzz") / "planner_fuzz")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "planner_fuzz.cpp"), os.path.join(CSRC, "dsp_plan.cpp"),
-                           "-o", exe])
-    return exe
+    return build(tmp_path_factory.mktemp("planner_fuzz"), "planner_fuzz")
 
 
 def _run(exe, programs, seed):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    for k in list(env):
-        if k.startswith("DSPEED_HIP_"):  # (the planner reads the library's switches: the default plan is what is fuzzed)
-            del env[k]
-    r = subprocess.run([exe, str(programs), str(seed)], capture_output=True, text=True, timeout=900, env=env)
-    assert r.returncode == 0, (r.stdout[-2000:] + r.stderr[-6000:])
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return run([exe, str(programs), str(seed)], timeout=900)
 
 
 def test_ten_thousand_random_programs_plan_clean_under_asan_and_ubsan(fuzzer):

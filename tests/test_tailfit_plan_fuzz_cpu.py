@@ -5,43 +5,19 @@ UndefinedBehaviorSanitizer: a stand-alone program with a ``main`` of its own, pl
 bindings, offsets and strides -- each processor alone, log_check -> poly_fit, the chain with its residuals, each with or without a
 BL_SUBTRACT behind the LOAD --: each is planned -- on dsp_tailfit_kernel, with an argument block whose bindings have the right kind, type
 and size and whose powers stay inside int64 -- or refused with a reason."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dspeed_amd", "csrc")
-FLAGS = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include")]
+from plan_fuzz_util import build, run
 
 
 @pytest.fixture(scope="module")
 def fuzzer(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    probe = subprocess.run(["g++", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(probe) and os.path.exists(probe)):
-        pytest.skip("g++ has no AddressSanitizer runtime here")
-    exe = str(tmp_path_factory.mktemp("tailfit_plan_fuzz") / "tailfit_plan_fuzz")
-    subprocess.check_call(FLAGS + [os.path.join(ROOT, "tests", "tailfit_plan_fuzz.cpp"), os.path.join(CSRC, "dsp_plan.cpp"), "-o", exe])
-    return exe
-
-
-def _run(cmd):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    for k in list(env):
-        if k.startswith("DSPEED_HIP_"):
-            del env[k]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, (r.stdout[-3000:] + r.stderr[-6000:])
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return build(tmp_path_factory.mktemp("tailfit_plan_fuzz"), "tailfit_plan_fuzz")
 
 
 @pytest.mark.parametrize("seed", [0x2F, 7])
 def test_programs_with_the_ops_plan_clean_under_asan_and_ubsan(fuzzer, seed):
-    rep = _run([fuzzer, "20000", str(seed)])
+    rep = run([fuzzer, "20000", str(seed)])
     assert rep["programs"] == 20000
     # every shape was planned: each processor alone, the fit behind the logarithm, the chain with either store or none, with a subtraction ...
     assert rep["log"] > 300 and rep["fit"] > 200 and rep["resid"] > 200 and rep["log_fit"] > 200 and rep["chain"] > 200, rep
